@@ -11,6 +11,14 @@ points (with their observations) are sharded over the ranks (strong scaling), ca
 and the reduced camera system is all-reduced over RCCL.  The matcher leg times the 50k x 50k x 128
 brute-force L2 + ratio test (queries sharded over ranks).  Inputs are resident in HBM before timing.
 
+A plain run measures the headline alone: scene, W warm-up and K timed outer iterations, the line.  `--full` adds
+everything else the line has carried (the per-kernel table and rooflines from a second pass, the secondary BA rows,
+the drop-in calls, the matcher leg, the driver rows, the CPU baseline, the scaling model).  `--dump-outputs DIR`
+writes the headline solve's cameras, points and cost after its last timed step as DIR/<name>.npy (float64); the
+inputs are seeded, so two builds can be compared output for output.  Any K can be timed: far past convergence the
+trust region collapses and the library ends the loop (the headline's solve after 1,687 outer iterations), and the
+schedule then starts over from the same start (`restarts` in the line counts how often, within the timed steps).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -34,7 +42,9 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     # 20 timed outer iterations after 5 (the schedule the round driver runs): the chip raises its clock only under sustained
     # load - at 10 after 2 (7 ms of warm-up) the same build reads ~9 % lower
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20,
+                    help="timed outer iterations, any number: a solve that ends (its trust region collapses far past convergence) "
+                         "starts over from the same start")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--cams", type=int, default=200)
     ap.add_argument("--pts", type=int, default=100000)
@@ -64,7 +74,16 @@ def parse():
                     help="(tests) JSON list: the command every rank runs instead of this script")
     ap.add_argument("--launch-timeout", type=float, default=float(os.environ.get("SFM_BENCH_LAUNCH_TIMEOUT", "2400")),
                     help="seconds the group of ranks may take before all of it is killed")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the per-kernel table and rooflines (a second pass), the "
+                         "secondary BA rows, the drop-in calls, the matcher, the driver rows, the CPU baseline and the scaling model "
+                         "(the --no-* options above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the headline solve computed (cameras, points, cost) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def launch_ranks(args):
@@ -290,20 +309,46 @@ def main():
         ci_, pi_, uv_, pts_ = shard_arrays(scene.cam_idx, scene.pt_idx, scene.uv, scene.pts0, a, b)
         return scene.cams0, pts_, ci_, pi_, uv_
 
-    def fixed_schedule_run(cam_dim, precision, profile, solver="dense", camera_solver=None, shard=None):
+    def fixed_schedule_run(cam_dim, precision, profile, solver="dense", camera_solver=None, shard=None, keep_x=False):
         """W warm-up + K timed outer iterations of the trust-region loop (library side, termination tests off).
-        The profiled pass (never the timed one) also reads the cost after every outer iteration."""
+        The profiled pass (never the timed one) also reads the cost after every outer iteration.  keep_x: the result
+        carries this rank's parameters after the last step ("x": cams [C, d], pts [P_local, 3]).
+        Far past convergence the trust region collapses and the library ends the loop (trf_loop.h; the headline scene's
+        d = 10 solve after 1,687 outer iterations, d = 6 after 40): the schedule then starts over from the same start, so
+        any K can be timed.  Every call of outer() is a step, the one that ended a solve included."""
         cams0_, pts0_, ci_, pi_, uv_ = shard if shard is not None else (sc.cams0, pts0, ci, pi, uv)
         be = GpuBA(cams0_[:, :cam_dim], pts0_, ci_, pi_, uv_, synth.K_REF, device=local_rank, comm=comm, precision=precision,
                    solver=solver, camera_solver=camera_solver or args.camera_solver)
+        x_start = be.x.clone()
         st = be.trf_begin(max_nfev=2 ** 31 - 1, check_tolerances=False)
         cost0 = st.result().cost
+        ended = {"restarts": 0, "n_solves": 0, "nfev": 0}        # counts of the solves that have ended
+
+        def step():
+            nonlocal st
+            if st.outer():
+                return
+            r = st.result()
+            ended["restarts"] += 1
+            ended["n_solves"] += r.n_solves
+            ended["nfev"] += r.nfev
+            st.close()
+            torch.cuda.synchronize()                             # the library's stream has written x
+            be.x.copy_(x_start)
+            torch.cuda.synchronize()
+            st = be.trf_begin(max_nfev=2 ** 31 - 1, check_tolerances=False)
+
+        def totals():
+            r = st.result()
+            return r, ended["n_solves"] + r.n_solves, ended["nfev"] + r.nfev
+
         cost_trace = []
         for _ in range(args.warmup):
-            st.outer()
+            step()
             if profile:
                 cost_trace.append(st.result().cost)
-        r0 = st.result()
+        _, solves0, nfev0 = totals()
+        restarts0 = ended["restarts"]
         cg0, pcg0 = be.solver_stats(), be.cg_iters          # counters are cumulative: the timed pass is the difference
         if profile:
             be.h.set_profiling(True)
@@ -311,7 +356,7 @@ def main():
         barrier_sync()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            st.outer()
+            step()
             if profile:
                 cost_trace.append(st.result().cost)
         barrier_sync()
@@ -320,14 +365,17 @@ def main():
         if profile:
             prof = be.h.profile()
             be.h.set_profiling(False)
-        r1 = st.result()
+        r1, solves1, nfev1 = totals()
         cg1 = be.solver_stats()
         st.close()
         out = {"cg_iters": be.cg_iters - pcg0, "camera_cg": (cg1[0] - cg0[0], cg1[1] - cg0[1]), "camera_cg_warmup": cg0,
                "pcg_stats": be.pcg_stats() if solver == "pcg" else None,
                "elapsed": elapsed, "value": args.steps / elapsed, "ms_per_step": elapsed / args.steps * 1e3,
-               "damped_solves": r1.n_solves - r0.n_solves, "trial_steps": r1.nfev - r0.nfev, "cost_start": cost0,
+               "restarts": ended["restarts"] - restarts0,
+               "damped_solves": solves1 - solves0, "trial_steps": nfev1 - nfev0, "cost_start": cost0,
                "cost_end": r1.cost, "n_pairs": be.n_pairs, "n_obs_local": be.N, "prof": prof, "cost_trace": cost_trace}
+        if keep_x:
+            out["x"] = be.params()
         del st, be
         torch.cuda.empty_cache()
         return out
@@ -341,9 +389,72 @@ def main():
         r["prof"], r["cost_trace"] = rp["prof"], rp["cost_trace"]
         return r
 
-    # the timed run carries NO per-kernel events; the kernel table comes from a second, identical pass
-    main = fixed_schedule_run(d, "fp64", profile=False)
+    def dump_outputs(path, run):
+        """DIR/cams.npy [C, d], DIR/points.npy [P, 3] (float64, the scene's point order) and DIR/cost.npy [1]: the parameters and
+        the cost the headline solve holds after its last timed step.  Beyond 60 MiB in all (the outputs stay under 64 MB, .npy
+        headers included), points.npy is a fixed sample of rows (seed 0) whose indices DIR/points_rows.npy holds."""
+        cams, pts = run["x"]
+        if world > 1:                                    # ranks hold contiguous point ranges, in rank order
+            parts = [None] * world
+            dist.all_gather_object(parts, pts)
+            pts = np.concatenate(parts)
+        if rank != 0:
+            return
+        out = {"cams": cams, "points": pts, "cost": np.array([run["cost_end"]], dtype=np.float64)}
+        limit = 60 << 20
+        if cams.nbytes + pts.nbytes + 8 > limit:
+            k = (limit - cams.nbytes - 8) // (pts.shape[1] * 8 + 8)
+            rows = np.sort(np.random.default_rng(0).choice(pts.shape[0], size=k, replace=False))
+            out["points"], out["points_rows"] = pts[rows], rows.astype(np.float64)
+        os.makedirs(path, exist_ok=True)
+        for name, a in out.items():
+            np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+    # the timed run carries NO per-kernel events; the kernel table comes from a second, identical pass (--full)
+    main = fixed_schedule_run(d, "fp64", profile=False, keep_x=args.dump_outputs is not None)
     elapsed, value = main["elapsed"], main["value"]
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, main)
+
+    rccl_seen = None
+    if getattr(comm, "in_library", False):
+        import ctypes
+        a_, b_ = _lib.i32(0), _lib.i32(0)
+        if comm.h.lib.sfm_comm_info(comm.h._h, ctypes.byref(a_), ctypes.byref(b_)) == 0:
+            rccl_seen = int(a_.value)          # ncclCommCount of the communicator the exchanges ran on
+
+    def headline():
+        """The fields of the JSON line a plain run prints; --full adds its measurements to them."""
+        return {
+            "metric": "BA LM-iterations/sec + descriptor-pairs/sec, 200 cams / 100k pts, 1->8 MI355X",
+            "value": value, "unit": "LM-iterations/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"BA: {C} cams / {P} pts / {n_obs_total} obs, cam block {d} "
+                                   f"({'reference 10-parameter block + regulariser' if d == 10 else 'fixed K'}), "
+                                   "aligned residual order, Huber, SciPy-TRF control flow, fixed schedule"
+                                   + ("" if args.visibility == "random" else ", spatially coherent visibility"),
+                       "parallelism": f"points sharded over {world} rank(s), cameras replicated, RCCL all-reduce of [S|r]",
+                       "comm": comm_kind, "rccl_ranks_seen": rccl_seen,
+                       "seed": 1004},
+            "ba": {"damped_solves": main["damped_solves"], "trial_steps": main["trial_steps"], "cost_start": main["cost_start"],
+                   "cost_end": main["cost_end"], "solves_per_s": main["damped_solves"] / elapsed,
+                   "loop": "sfm_ba_trf_outer (library-side trust-region loop)", "camera_solver": args.camera_solver,
+                   "camera_cg_iterations_and_fallbacks_timed_pass": main["camera_cg"],
+                   "camera_cg_iterations_and_fallbacks_warmup": main["camera_cg_warmup"],
+                   "restarts": main["restarts"]},
+        }
+
+    def finish(out):
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if use_dist:
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish(headline())
+        return
+
     profd = fixed_schedule_run(d, "fp64", profile=True)
     prof, prof_elapsed = profd["prof"], profd["elapsed"]
     kernels = {k: {"ms_total": round(v[0], 3), "launches": v[1], "us_per_launch": round(v[0] / v[1] * 1e3, 2),
@@ -479,7 +590,7 @@ def main():
 
     # ------------------------------------------------------------------ secondary BA figures on the same scene
     def brief(r, what):
-        return {"value": r["value"], "unit": "LM-iterations/s", "ms_per_step": r["ms_per_step"],
+        return {"value": r["value"], "unit": "LM-iterations/s", "ms_per_step": r["ms_per_step"], "restarts": r["restarts"],
                 "damped_solves": r["damped_solves"], "cost_end": r["cost_end"], "workload": what}
     ba_d6 = ba_mixed = None
     if d == 10 and not args.no_d6:
@@ -812,41 +923,17 @@ def main():
                 "assumed": {"launch_bound_floor_us_per_iteration": FLOOR_US, "exchanged_per_iteration_bytes": n_sys * 8},
                 "projected": projp}
 
-    rccl_seen = None
-    if getattr(comm, "in_library", False):
-        import ctypes
-        a_, b_ = _lib.i32(0), _lib.i32(0)
-        if comm.h.lib.sfm_comm_info(comm.h._h, ctypes.byref(a_), ctypes.byref(b_)) == 0:
-            rccl_seen = int(a_.value)          # ncclCommCount of the communicator the exchanges ran on
-
-    if rank == 0:
-        out = {
-            "metric": "BA LM-iterations/sec + descriptor-pairs/sec, 200 cams / 100k pts, 1->8 MI355X",
-            "value": value, "unit": "LM-iterations/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"BA: {C} cams / {P} pts / {n_obs_total} obs, cam block {d} "
-                                   f"({'reference 10-parameter block + regulariser' if d == 10 else 'fixed K'}), "
-                                   "aligned residual order, Huber, SciPy-TRF control flow, fixed schedule"
-                                   + ("" if args.visibility == "random" else ", spatially coherent visibility"),
-                       "parallelism": f"points sharded over {world} rank(s), cameras replicated, RCCL all-reduce of [S|r]",
-                       "comm": comm_kind, "rccl_ranks_seen": rccl_seen,
-                       "seed": 1004},
-            "ba": {"damped_solves": main["damped_solves"], "trial_steps": main["trial_steps"], "cost_start": main["cost_start"],
-                   "cost_end": main["cost_end"], "solves_per_s": main["damped_solves"] / elapsed, "kernels": kernels,
-                   "kernels_note": "HIP-event times from a second pass of the same schedule; the timed pass carries no events",
-                   "loop": "sfm_ba_trf_outer (library-side trust-region loop)", "camera_solver": args.camera_solver,
-                   "camera_cg_iterations_and_fallbacks_timed_pass": main["camera_cg"],
-                   "camera_cg_iterations_and_fallbacks_warmup": main["camera_cg_warmup"]},
-            "ba_cam_dim6": ba_d6, "ba_mixed_precision": ba_mixed, "ba_other_camera_solver": ba_alt, "ba_pcg_solver": ba_pcg,
-            "ba_coherent_scene": ba_coherent, "ba_reference_order": ba_reference,
-            "dropin": dropin, "scaling_model": scaling_model,
-            "roofline": roofline, "rooflines": roofs, "cpu_baseline": cpu_baseline, "matcher": matcher,
-            "driver_rows": driver_rows,
-        }
-        print(json.dumps(out), flush=True)
-    if use_dist:
-        dist.destroy_process_group()
+    out = headline()
+    out["ba"].update(kernels=kernels,
+                     kernels_note="HIP-event times from a second pass of the same schedule; the timed pass carries no events")
+    out.update({
+        "ba_cam_dim6": ba_d6, "ba_mixed_precision": ba_mixed, "ba_other_camera_solver": ba_alt, "ba_pcg_solver": ba_pcg,
+        "ba_coherent_scene": ba_coherent, "ba_reference_order": ba_reference,
+        "dropin": dropin, "scaling_model": scaling_model,
+        "roofline": roofline, "rooflines": roofs, "cpu_baseline": cpu_baseline, "matcher": matcher,
+        "driver_rows": driver_rows,
+    })
+    finish(out)
 
 
 if __name__ == "__main__":

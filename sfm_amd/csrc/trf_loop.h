@@ -14,6 +14,8 @@
 namespace trf_core {
 
 constexpr double ALPHA_FLOOR_REL = 1e-13;
+// solve_tr_more -> outer: no trial step is left to take (see solve_tr_more); never a backend's code
+constexpr int TR_COLLAPSED = 1 << 30;
 
 struct Options { double ftol, xtol, gtol; int max_nfev, max_outer, check_tolerances; };
 
@@ -55,6 +57,10 @@ int solve_tr_more(BE& be, double g_norm, double Delta, double& alpha, double alp
     if (alpha < alpha_lower || alpha > alpha_upper) alpha = std::fmax(0.001 * alpha_upper, std::sqrt(alpha_lower * alpha_upper));
     const bool on_floor = alpha <= alpha_floor;
     if (on_floor) alpha = alpha_floor;
+    // Far past convergence with the termination tests off (a fixed schedule), rejected trials shrink Delta towards underflow
+    // and the update below turns alpha into NaN.  SciPy never gets here: one of its tolerances is at least EPS, so xtol ends
+    // the loop first.  outer() ends it here, as xtol would.
+    if (!(alpha > 0)) return TR_COLLAPSED;
     double p_norm, pq;
     if ((rc = be.solve(alpha, 1, &p_norm, &pq))) return rc;
     const double phi = p_norm - Delta;
@@ -95,7 +101,9 @@ int outer(BE& be, State& s, const Options& o, int* more) {
   int rc;
   while (actual <= 0 && s.nfev < o.max_nfev) {
     double p_norm;
-    if ((rc = solve_tr_more(be, s.g_norm, s.Delta, s.alpha, ALPHA_FLOOR_REL * s.hdiag, &p_norm))) return rc;
+    rc = solve_tr_more(be, s.g_norm, s.Delta, s.alpha, ALPHA_FLOOR_REL * s.hdiag, &p_norm);
+    if (rc == TR_COLLAPSED) { s.status = 3; return 0; }      // the trust region has collapsed: the loop ends (*more = 0)
+    if (rc) return rc;
     double js2, gts, step_norm;
     if ((rc = be.step(s.Delta / p_norm, &js2, &gts, &cost_new, &step_norm, &xnew_norm))) return rc;
     const double predicted = -(0.5 * js2 + gts);

@@ -72,10 +72,24 @@ def check_termination(dF, F, dx_norm, x_norm, ratio, ftol, xtol):
     return None
 
 
+def _div(a, b):
+    """a / b with IEEE 754 semantics, as trf_loop.h computes it in C++: x / 0 is +-inf, 0 / 0 and nan / 0 are nan (Python
+    floats raise instead).  Keeps this loop on the C++ loop's path when a trust region collapses."""
+    if b != 0:
+        return a / b
+    if a != a or a == 0:
+        return math.nan
+    return math.copysign(math.inf, a) * math.copysign(1.0, b)
+
+
+class TrustRegionCollapsed(Exception):
+    """No trial step is left to take: see solve_tr_more."""
+
+
 def solve_tr_more(backend, g_norm, Delta, initial_alpha, alpha_floor=0.0, rtol=0.01, max_iter=10):
     """More' iteration on alpha; leaves p(alpha_final) in the backend.
     Returns (||p||, alpha, n_iter, n_solves)."""
-    alpha_upper = g_norm / Delta
+    alpha_upper = _div(g_norm, Delta)
     alpha_lower = 0.0
     if initial_alpha is None or initial_alpha == 0:
         alpha = max(0.001 * alpha_upper, (alpha_lower * alpha_upper) ** 0.5)
@@ -89,20 +103,25 @@ def solve_tr_more(backend, g_norm, Delta, initial_alpha, alpha_floor=0.0, rtol=0
         on_floor = alpha <= alpha_floor
         if on_floor:
             alpha = alpha_floor
+        # far past convergence with the termination tests off, rejected trials shrink Delta towards underflow and the update
+        # below turns alpha into NaN; SciPy never gets here (one of its tolerances is >= EPS, so xtol ends the loop first)
+        if not alpha > 0:
+            raise TrustRegionCollapsed
         p_norm, pq = backend.solve(alpha, True)
         solves += 1
         phi = p_norm - Delta
         if on_floor and phi < 0:          # interior Gauss-Newton step: p(alpha_floor) is the answer
             return p_norm, alpha, it + 1, solves
-        phi_prime = -pq / p_norm
+        phi_prime = _div(-pq, p_norm)
         if phi < 0:
             alpha_upper = alpha
-        ratio = phi / phi_prime
+        ratio = _div(phi, phi_prime)
         alpha_lower = max(alpha_lower, alpha - ratio)
-        alpha -= (phi + Delta) * ratio / Delta
+        alpha -= _div((phi + Delta) * ratio, Delta)
         if abs(phi) < rtol * Delta:
             break
-    alpha = max(alpha, alpha_floor, 1e-300)      # the Schur route needs alpha > 0 (SciPy's SVD form does not)
+    # the Schur route needs alpha > 0 (SciPy's SVD form does not); a NaN alpha gives way, as in std::fmax
+    alpha = max(alpha_floor, 1e-300) if math.isnan(alpha) else max(alpha, alpha_floor, 1e-300)
     p_norm, _ = backend.solve(alpha, False)
     return p_norm, alpha, it + 1, solves + 1
 
@@ -136,10 +155,14 @@ class TRFState:
         cost_new = self.cost
         xnew_norm = self.x_norm
         while actual_reduction <= 0 and self.nfev < self.max_nfev:
-            p_norm, self.alpha, _, ns = solve_tr_more(be, self.g_norm, self.Delta, self.alpha,
-                                                      ALPHA_FLOOR_REL * self.hdiag)
+            try:
+                p_norm, self.alpha, _, ns = solve_tr_more(be, self.g_norm, self.Delta, self.alpha,
+                                                          ALPHA_FLOOR_REL * self.hdiag)
+            except TrustRegionCollapsed:      # the loop ends as xtol would end it
+                self.status = 3
+                return False
             self.n_solves += ns
-            js2, gts, cost_new, step_norm, xnew_norm = be.step(self.Delta / p_norm)
+            js2, gts, cost_new, step_norm, xnew_norm = be.step(_div(self.Delta, p_norm))
             predicted_reduction = -(0.5 * js2 + gts)
             self.nfev += 1
             if not math.isfinite(cost_new):
@@ -154,7 +177,7 @@ class TRFState:
                                                 self.ftol, self.xtol)
                 if self.status is not None:
                     break
-            self.alpha *= self.Delta / Delta_new
+            self.alpha *= _div(self.Delta, Delta_new)
             self.Delta = Delta_new
         if actual_reduction > 0:
             be.accept()

@@ -1,7 +1,7 @@
 // Host-only run of sfm_amd/csrc/trf_loop.h (the trust-region state machine of sfm_ba_trf_*) on a small dense problem,
 // built with -fsanitize=address,undefined by tests/test_host_logic.py and compared there with sfm_amd/trf.py driving the
 // same problem in NumPy.  Problem: f_i(x) = x0 exp(-x1 t_i) + x2 exp(-x3 t_i) + x4 - y_i, 16 samples, cost 1/2 |f|^2.
-// argv: ftol xtol max_nfev x0..x4.  Prints: nfev njev status cost x0..x4 n_trials.
+// argv: ftol xtol max_nfev x0..x4 [max_outer check_tolerances noise (0.01)].  Prints: nfev njev status cost x0..x4 n_trials.
 #include "trf_loop.h"
 #include <cstdio>
 #include <cstdlib>
@@ -72,15 +72,17 @@ struct Dense {
 }  // namespace
 
 int main(int argc, char** argv) {
-  if (argc != 4 + N) { std::printf("usage: ftol xtol max_nfev x0..x4\n"); return 2; }
+  if (argc != 4 + N && argc != 7 + N) { std::printf("usage: ftol xtol max_nfev x0..x4 [max_outer check_tolerances noise]\n"); return 2; }
+  const double noise = argc == 7 + N ? std::atof(argv[6 + N]) : 0.01;
   Dense be;
   const double truth[N] = {2.0, 0.7, 1.5, 0.1, 0.3};
   for (int i = 0; i < M; ++i) {
     be.t[i] = 0.25 * i;
-    be.y[i] = truth[0] * std::exp(-truth[1] * be.t[i]) + truth[2] * std::exp(-truth[3] * be.t[i]) + truth[4] + 0.01 * std::sin(3.7 * i);
+    be.y[i] = truth[0] * std::exp(-truth[1] * be.t[i]) + truth[2] * std::exp(-truth[3] * be.t[i]) + truth[4] + noise * std::sin(3.7 * i);
   }
   for (int a = 0; a < N; ++a) be.x[a] = std::atof(argv[4 + a]);
   trf_core::Options o = {std::atof(argv[1]), std::atof(argv[2]), 1e-8, std::atoi(argv[3]), -1, 1};
+  if (argc == 7 + N) { o.max_outer = std::atoi(argv[4 + N]); o.check_tolerances = std::atoi(argv[5 + N]); }
   trf_core::State s;
   int rc = trf_core::begin(be, s), more = 1;
   while (!rc && more) rc = trf_core::outer(be, s, o, &more);

@@ -365,11 +365,11 @@ def test_matcher_plan_under_address_and_ub_sanitizers(tmp_path):
 class _DenseFitBackend:
     """The problem of tests/native/trf_loop_check.cpp in NumPy, behind the backend protocol of sfm_amd/trf.py."""
 
-    def __init__(self, x0):
+    def __init__(self, x0, noise=0.01):
         self.t = 0.25 * np.arange(16)
         truth = np.array([2.0, 0.7, 1.5, 0.1, 0.3])
         self.y = (truth[0] * np.exp(-truth[1] * self.t) + truth[2] * np.exp(-truth[3] * self.t) + truth[4]
-                  + 0.01 * np.sin(3.7 * np.arange(16)))
+                  + noise * np.sin(3.7 * np.arange(16)))
         self.x = np.array(x0, dtype=np.float64)
 
     def _f(self, v):
@@ -385,7 +385,8 @@ class _DenseFitBackend:
         return 0.5 * float(self.f @ self.f), float(np.linalg.norm(self.g)), float(np.abs(self.g).max()), float(np.diag(self.H).max())
 
     def solve(self, alpha, want_q):
-        A = self.H + alpha * np.eye(5)
+        A = self.H.copy()
+        A[np.diag_indices(5)] += alpha          # as trf_loop_check.cpp: alpha on the diagonal only (alpha = inf stays off it)
         self.p = np.linalg.solve(A, -self.g)
         pq = float(self.p @ np.linalg.solve(A, self.p)) if want_q else 0.0
         return float(np.linalg.norm(self.p)), pq
@@ -404,6 +405,19 @@ class _DenseFitBackend:
         self.x = self.xn
 
 
+def _build_trf_loop_check(tmp_path):
+    import shutil
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = tmp_path / "trf_loop_check"
+    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                            "-I" + os.path.join(root, "sfm_amd", "csrc"), os.path.join(root, "tests", "native", "trf_loop_check.cpp"),
+                            "-o", str(exe)], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr
+    return exe
+
+
 @pytest.mark.parametrize("ftol,xtol,max_nfev,x0", [(1e-8, 1e-8, 100, (1.0, 1.0, 1.0, 0.5, 0.0)),
                                                    (1e-4, 1e-4, 100, (3.0, 0.2, 0.5, 0.4, 1.0)),
                                                    (1e-10, 1e-10, 12, (1.0, 2.0, 3.0, 0.01, -1.0)),
@@ -414,16 +428,8 @@ def test_native_trf_loop_equals_python_loop_under_sanitizers(tmp_path, ftol, xto
     (the loop the multi-rank CPU tests and the oracle comparisons drive) on the same problem in NumPy: same evaluation
     counts, termination status and number of trials, same parameters.  The GPU suite holds the two loops together on the
     real backend (test_c_loop_equals_python_loop); this is the part of that which needs no GPU."""
-    import shutil
     from sfm_amd.trf import trf
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = tmp_path / "trf_loop_check"
-    build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                            "-I" + os.path.join(root, "sfm_amd", "csrc"), os.path.join(root, "tests", "native", "trf_loop_check.cpp"),
-                            "-o", str(exe)], capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
+    exe = _build_trf_loop_check(tmp_path)
     run = subprocess.run([str(exe), repr(ftol), repr(xtol), str(max_nfev)] + [repr(v) for v in x0], capture_output=True, text=True)
     assert run.returncode == 0, (run.stdout, run.stderr[-2000:])
     vals = run.stdout.split()
@@ -433,6 +439,28 @@ def test_native_trf_loop_equals_python_loop_under_sanitizers(tmp_path, ftol, xto
     assert (nfev, njev, status, n_trials) == (ref.nfev, ref.njev, ref.status, len(ref.trace))
     assert cost == pytest.approx(ref.cost, rel=1e-9)
     assert np.allclose(x, be.x, rtol=1e-8, atol=1e-10)
+
+
+@pytest.mark.parametrize("x0", [(3.0, 0.2, 0.5, 0.4, 1.0), (1.0, 2.0, 3.0, 0.01, -1.0)])
+def test_fixed_schedule_past_convergence_ends_the_loop_as_xtol(tmp_path, x0):
+    """The termination tests off (the fixed schedule bench.py times) for 500 outer iterations on noise-free data: the fit is
+    exact long before the schedule ends, rejected trials then shrink Delta until the More' update turns alpha into NaN.  Both
+    loops end there with status 3 and the exact fit (trf_loop.h used to hand the NaN to the solver: the library failed with
+    "alpha must be > 0").  Past the fit the two loops follow round-off, so their counts are not compared."""
+    from sfm_amd.trf import trf
+    exe = _build_trf_loop_check(tmp_path)
+    run = subprocess.run([str(exe), "1e-8", "1e-8", "100000"] + [repr(v) for v in x0] + ["500", "0", "0"],
+                         capture_output=True, text=True)
+    assert run.returncode == 0, (run.stdout, run.stderr[-2000:])
+    vals = run.stdout.split()
+    njev, status, x = int(vals[1]), int(vals[2]), np.array(vals[4:9], float)
+    truth = np.array([2.0, 0.7, 1.5, 0.1, 0.3])
+    fit = lambda v: v if v[1] > v[3] else v[[2, 3, 0, 1, 4]]          # the two exponentials in either order
+    assert status == 3 and njev < 501 and np.allclose(fit(x), truth, rtol=1e-9, atol=1e-12)
+    be = _DenseFitBackend(x0, noise=0.0)
+    with np.errstate(invalid="ignore"):           # the collapse passes through inf * 0, as in C++
+        ref = trf(be, ftol=1e-8, xtol=1e-8, max_nfev=100000, max_outer=500, check_tolerances=False)
+    assert ref.status == 3 and ref.njev < 501 and np.allclose(fit(be.x), truth, rtol=1e-9, atol=1e-12)
 
 
 def test_dmatchlist_serves_every_use_the_reference_makes_of_the_match_list(tmp_path):

@@ -12,7 +12,7 @@ OUT=$R/gpurun_out/${1:-exp_mall}
 mkdir -p $OUT
 BA="--cams 1000 --pts 500000 --steps 3 --warmup 1 --no-cpu-baseline --no-matcher --no-d6 --no-mixed --no-pcg --no-dropin --no-driver-rows --no-alt-camera-solver --no-coherent --no-reference-order"
 for zz in ${ZZ:-0 1 2}; do for rev in ${REV:-0 1 3}; do
-  SFM_SCHUR_FUSE_SCALE=0 SFM_CGB_ZIGZAG=$zz SFM_SCALE_REV=$rev timeout -k 10 300 python3 $R/bench.py $BA > $OUT/zz${zz}_rev${rev}.json 2> $OUT/zz${zz}_rev${rev}.err
+  SFM_SCHUR_FUSE_SCALE=0 SFM_CGB_ZIGZAG=$zz SFM_SCALE_REV=$rev timeout -k 10 300 python3 $R/bench.py --full $BA > $OUT/zz${zz}_rev${rev}.json 2> $OUT/zz${zz}_rev${rev}.err
   python3 - $OUT/zz${zz}_rev${rev}.json $zz $rev <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); k = d["ba"]["kernels"]

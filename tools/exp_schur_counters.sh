@@ -18,7 +18,7 @@ for vis in random nearest; do
   i=0
   for P in "$P1" "$P2" "$P3" "$P4"; do
     i=$((i + 1))
-    timeout -k 10 300 rocprofv3 --pmc $P --kernel-trace --output-format csv -d $OUT/${vis}_p$i -- python3 $R/bench.py --steps 2 --warmup 1 --visibility $vis $BA > $OUT/${vis}_p$i.log 2>&1 || exit 1
+    timeout -k 10 300 rocprofv3 --pmc $P --kernel-trace --output-format csv -d $OUT/${vis}_p$i -- python3 $R/bench.py --full --steps 2 --warmup 1 --visibility $vis $BA > $OUT/${vis}_p$i.log 2>&1 || exit 1
     python3 $R/tools/pmc_summary.py k_schur_items $OUT/${vis}_p$i > $OUT/${vis}_p$i.txt
     find $OUT/${vis}_p$i -name "*.csv" -delete
     echo "$vis pass $i done"

@@ -28,9 +28,9 @@ for v in $VARIANTS; do
   W=${v%%:*}; U=${v##*:}
   export SFM_AMD_LIB=$R/sfm_amd/lib/libsfm_amd_w${W}_u${U}.so
   [ -f $SFM_AMD_LIB ] || { echo "missing $SFM_AMD_LIB: run '$0 build' first"; exit 1; }
-  timeout -k 10 200 python3 $R/bench.py $BA > $OUT/d10_w${W}_u${U}.json 2> $OUT/d10_w${W}_u${U}.err
-  timeout -k 10 200 python3 $R/bench.py --cam-dim 6 $BA > $OUT/d6_w${W}_u${U}.json 2> $OUT/d6_w${W}_u${U}.err
-  timeout -k 10 200 python3 $R/bench.py --visibility nearest $BA > $OUT/coh_w${W}_u${U}.json 2> $OUT/coh_w${W}_u${U}.err
-  SFM_XCD_GROUP=contig timeout -k 10 200 python3 $R/bench.py --visibility nearest $BA > $OUT/cohc_w${W}_u${U}.json 2> $OUT/cohc_w${W}_u${U}.err
+  timeout -k 10 200 python3 $R/bench.py --full $BA > $OUT/d10_w${W}_u${U}.json 2> $OUT/d10_w${W}_u${U}.err
+  timeout -k 10 200 python3 $R/bench.py --full --cam-dim 6 $BA > $OUT/d6_w${W}_u${U}.json 2> $OUT/d6_w${W}_u${U}.err
+  timeout -k 10 200 python3 $R/bench.py --full --visibility nearest $BA > $OUT/coh_w${W}_u${U}.json 2> $OUT/coh_w${W}_u${U}.err
+  SFM_XCD_GROUP=contig timeout -k 10 200 python3 $R/bench.py --full --visibility nearest $BA > $OUT/cohc_w${W}_u${U}.json 2> $OUT/cohc_w${W}_u${U}.err
   echo "done W=$W U=$U"
 done

@@ -43,10 +43,9 @@ __device__ __forceinline__ void publish_ticket(double* hsc, double seq) { publis
 
 // Stride of a G block in doubles.  D = 10: 32 = 256 bytes, so that a block is exactly two whole 128-byte lines - the Schur
 // gather is bound by the lines it pulls through the fabric, and a 240-byte block at 16-byte alignment straddles 2.75 on
-// average: k_schur_items 357 -> 305 us, fabric traffic 2.34 -> 1.94 GB per launch (round 3, profiles/).  SFM_G_PAD=0 restores
-// the packed 30.  D = 6: 18 doubles = 144 bytes straddle exactly two lines at any 16-byte offset already.
-static int g_pad() { static const int v = (getenv("SFM_G_PAD") && getenv("SFM_G_PAD")[0] == '0') ? 0 : 1; return v; }
-static int64_t g_stride(int64_t D) { return (D == 10 && g_pad()) ? 32 : 3 * D; }
+// average: k_schur_items 357 -> 305 us, fabric traffic 2.34 -> 1.94 GB per launch (round 3, profiles/).  D = 6: 18 doubles =
+// 144 bytes straddle exactly two lines at any 16-byte offset already.  The strides DISPATCH_DT instantiates (GG) must match.
+static int64_t g_stride(int64_t D) { return D == 10 ? 32 : 3 * D; }
 
 // ------------------------------------------------------------------------------------ layout
 Lay ba_layout(int64_t C, int64_t P, int64_t N, int64_t D, int64_t n_items, int64_t n_cchunks, int precision) {
@@ -94,9 +93,8 @@ Lay ba_layout(int64_t C, int64_t P, int64_t N, int64_t D, int64_t n_items, int64
   // implicit-Schur PCG (sfm_ba_solve_pcg): residual, preconditioned residual, direction, S p; block-Jacobi blocks
   L.cg_r = take(n); L.cg_z = take(n); L.cg_p = take(n); L.cg_Ap = take(n);
   L.cg_M = take(C * D * D); L.cg_Minv = take(C * D * D);
-  L.cg_scal = take(64);                  // [0, 16) status words of the camera CG; [16, 32) / [32, 48): XCD tickets of its two launches
+  L.cg_scal = take(CG_SCAL_WORDS);       // status words of the camera CG
   L.cg_mail = take(4 * n);               // k_cgs_persist: two slots of n doubles as pairs of 8-byte {tag, half} granules
-  L.cg_warm = take(4 * n);               // warm start of the camera CG: p_c and q_c of the previous damped solve, start vector, scratch
   L.total = o;
   return L;
 }
@@ -636,10 +634,10 @@ __global__ __launch_bounds__(256) void k_build_G(int64_t N, const int* __restric
                                                  const double* __restrict__ Cp, const double* __restrict__ gp, double alpha, int P,
                                                  unsigned nblk_obs, double* __restrict__ cg_scal /* may be null */) {
   static_assert(GS % 2 == 0 && GS >= 3 * D, "G blocks are written as 16-byte pieces");
-  // the status and ticket words of the camera CG that follows start from zero: cleared HERE, by the first kernel of
+  // the status words of the camera CG that follows start from zero: cleared HERE, by the first kernel of
   // sfm_ba_schur_build, instead of by a memset between two kernels of the chain (a fill kernel of its own, ~5 us with its
   // boundaries) - and before k_schur_assemble, whose diagonal-block workgroups may RAISE the failure word
-  if (cg_scal && blockIdx.x == 0 && threadIdx.x < 64) cg_scal[threadIdx.x] = 0.0;
+  if (cg_scal && blockIdx.x == 0 && threadIdx.x < CG_SCAL_WORDS) cg_scal[threadIdx.x] = 0.0;
   // The point factors M_j = L_j^-1 and e_j = M_j g_pj for the kernels further down the chain (k_backsub, the camera-wise passes)
   // are the work of the LAST cdiv(P, 256) workgroups of this launch - a kernel of its own until round 4 (k_point_factor: 6 us
   // and a boundary in front of every damped solve).  The observation workgroups do not wait for them: every observation forms
@@ -810,7 +808,7 @@ extern "C" int sfm_debug_schur_stamps(unsigned long long* dst, int n_words) {
 #ifndef SFM_SCHUR_WG_WAVES
 #define SFM_SCHUR_WG_WAVES 1
 #endif
-template <int D, typename T, int GS, bool KPACK, bool NTK2>
+template <int D, typename T, int GS>
 __global__ __launch_bounds__(64 * SFM_SCHUR_WG_WAVES) __attribute__((amdgpu_waves_per_eu(D == 6 ? SFM_SCHUR_WAVES_D6 : SFM_SCHUR_WAVES_D10, D == 6 ? SFM_SCHUR_WAVES_D6 : SFM_SCHUR_WAVES_D10))) void k_schur_items(const int* __restrict__ xcd_ptr, const int* __restrict__ xcd_items,
                                                      const int* __restrict__ item_beg,
                                                      const int* __restrict__ item_end,
@@ -857,8 +855,6 @@ __global__ __launch_bounds__(64 * SFM_SCHUR_WG_WAVES) __attribute__((amdgpu_wave
   const int it = __builtin_amdgcn_readfirstlane(xcd_items[pos]);
   const int beg = __builtin_amdgcn_readfirstlane(item_beg[it]), end = __builtin_amdgcn_readfirstlane(item_end[it]);
   const int row = lane & 15, m = lane >> 4;
-  const bool valid = (row < D) && (m < 3);
-  const int off = valid ? m * D + row : 0;
   const int lb = lane / CH, lc = lane - lb * CH;          // this lane's block / chunk within a load
   const bool loader = lb < BPL;
   char* sA = s_stage[w][0];
@@ -869,7 +865,6 @@ __global__ __launch_bounds__(64 * SFM_SCHUR_WG_WAVES) __attribute__((amdgpu_wave
   // wave-uniform.  A diagonal block holds nothing but self-pairs UNLESS a camera appears twice on a track (fuse_rhs == 0,
   // sfm_ba_prob::has_dup): then it is processed like any other block and the right-hand side comes from k_cam_reduce_chunks
   const bool diag = fuse_rhs && k_first == k2_first;
-  const bool e_lane = (row == D) && (m < 3);              // B operand column D
   // K-packed form (see the MFMA loop): slot s = 4 j + m of MFMA j -> pair s / 3 of the slab, point coordinate s % 3
   constexpr int NM = (3 * BPL + 3) / 4;                   // MFMAs per full slab (3 for 4 pairs, 6 for 7)
   const bool krow = row < D, ke_lane = row == D;
@@ -917,11 +912,7 @@ __global__ __launch_bounds__(64 * SFM_SCHUR_WG_WAVES) __attribute__((amdgpu_wave
           for (int t = 0; t < U; ++t) {
             const int p = u0 + t * BPL + (loader ? lb : BPL - 1);
             ra[t] = *(const chunk_t*)(Gb + (size_t)(unsigned)__shfl(kk, p, 64) * BB + 16 * lc);
-            if (!DIAG) {
-              const char* pb = Gb + (size_t)(unsigned)__shfl(kk2, p, 64) * BB + 16 * lc;
-              if (NTK2) rb[t] = __builtin_nontemporal_load((const chunk_t*)pb);
-              else rb[t] = *(const chunk_t*)pb;
-            }
+            if (!DIAG) rb[t] = *(const chunk_t*)(Gb + (size_t)(unsigned)__shfl(kk2, p, 64) * BB + 16 * lc);
           }
         } else
 #pragma unroll
@@ -932,9 +923,7 @@ __global__ __launch_bounds__(64 * SFM_SCHUR_WG_WAVES) __attribute__((amdgpu_wave
           ra[t] = ok ? *(const chunk_t*)(Gb + (size_t)k * BB + 16 * lc) : (chunk_t){0, 0, 0, 0};
           if (!DIAG) {
             const int k2 = __shfl(kk2, p & 63, 64);
-            // the k2 side of a block row is single-use: NTK2 asks for a non-temporal load (experiment, SFM_SCHUR_NT=1)
-            if (NTK2) rb[t] = ok ? __builtin_nontemporal_load((const chunk_t*)(Gb + (size_t)k2 * BB + 16 * lc)) : (chunk_t){0, 0, 0, 0};
-            else rb[t] = ok ? *(const chunk_t*)(Gb + (size_t)k2 * BB + 16 * lc) : (chunk_t){0, 0, 0, 0};
+            rb[t] = ok ? *(const chunk_t*)(Gb + (size_t)k2 * BB + 16 * lc) : (chunk_t){0, 0, 0, 0};
           }
         }
 #pragma unroll
@@ -946,47 +935,35 @@ __global__ __launch_bounds__(64 * SFM_SCHUR_WG_WAVES) __attribute__((amdgpu_wave
           }
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-          if (KPACK) {
-            // the contraction index of a slab is (pair, m): 3 nb slots for nb pairs, 4 per MFMA - four pairs = 12 slots = 3 FULL
-            // v_mfma_f64_16x16x4 instead of 4 with K = 3 of 4 used.  Slot s = 4 j + (lane >> 4) of MFMA j reads pair s / 3,
-            // m = s % 3 (offsets precomputed per lane: koff[j]); pairs past the end of the item were stored as zeros.
-            // ALL operands of the slab are read before the first MFMA (one LDS latency per slab, not one per MFMA).
-            const int nb = (cnt - (u0 + t * BPL)) < BPL ? (cnt - (u0 + t * BPL)) : BPL;
-            const int nm = (3 * nb + 3) >> 2;
-            // (d = 6 runs at 8 waves per SIMD on 64 registers: its six MFMAs per slab take their operands one at a time)
-            constexpr int PFN = D == 6 ? 1 : NM;
+          // the contraction index of a slab is (pair, m): 3 nb slots for nb pairs, 4 per MFMA - four pairs = 12 slots = 3 FULL
+          // v_mfma_f64_16x16x4 instead of 4 with K = 3 of 4 used.  Slot s = 4 j + (lane >> 4) of MFMA j reads pair s / 3,
+          // m = s % 3 (offsets precomputed per lane: koff[j]); pairs past the end of the item were stored as zeros.
+          // ALL operands of the slab are read before the first MFMA (one LDS latency per slab, not one per MFMA).
+          const int nb = (cnt - (u0 + t * BPL)) < BPL ? (cnt - (u0 + t * BPL)) : BPL;
+          const int nm = (3 * nb + 3) >> 2;
+          // (d = 6 runs at 8 waves per SIMD on 64 registers: its six MFMAs per slab take their operands one at a time)
+          constexpr int PFN = D == 6 ? 1 : NM;
 #pragma unroll
-            for (int j0 = 0; j0 < NM; j0 += PFN) {
-              if (j0 >= nm) break;                            // wave-uniform
-              double av[PFN], bv[PFN];
+          for (int j0 = 0; j0 < NM; j0 += PFN) {
+            if (j0 >= nm) break;                            // wave-uniform
+            double av[PFN], bv[PFN];
 #pragma unroll
-              for (int q = 0; q < PFN; ++q) {
-                const int j = j0 + q;
-                if (j < NM) {
-                  const int ko = koff[j];
-                  av[q] = (double)((const T*)sA)[ko];
-                  if (DIAG) {
-                    const int sl = 4 * j + m, pi = (sl * 11) >> 5;
-                    bv[q] = ko != ZSLOT ? av[q] : ((ke_lane && pi < nb) ? s_e[w][u0 + t * BPL + pi][sl - 3 * pi] : 0.0);
-                  } else bv[q] = (double)((const T*)sB)[ko];
-                }
-              }
-#pragma unroll
-              for (int q = 0; q < PFN; ++q) {
-                if (j0 + q >= nm || j0 + q >= NM) break;      // wave-uniform
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[q], bv[q], acc, 0, 0, 0);
+            for (int q = 0; q < PFN; ++q) {
+              const int j = j0 + q;
+              if (j < NM) {
+                const int ko = koff[j];
+                av[q] = (double)((const T*)sA)[ko];
+                if (DIAG) {
+                  const int sl = 4 * j + m, pi = (sl * 11) >> 5;
+                  bv[q] = ko != ZSLOT ? av[q] : ((ke_lane && pi < nb) ? s_e[w][u0 + t * BPL + pi][sl - 3 * pi] : 0.0);
+                } else bv[q] = (double)((const T*)sB)[ko];
               }
             }
-          } else {
 #pragma unroll
-          for (int bb = 0; bb < BPL; ++bb) {
-            if (u0 + t * BPL + bb >= cnt) break;            // wave-uniform
-            const double a = valid ? (double)((const T*)sA)[bb * GS + off] : 0.0;
-            double b;
-            if (DIAG) b = valid ? a : (e_lane ? s_e[w][u0 + t * BPL + bb][m] : 0.0);
-            else b = valid ? (double)((const T*)sB)[bb * GS + off] : 0.0;
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-          }
+            for (int q = 0; q < PFN; ++q) {
+              if (j0 + q >= nm || j0 + q >= NM) break;      // wave-uniform
+              acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[q], bv[q], acc, 0, 0, 0);
+            }
           }
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the slab is rewritten by the next t
         }
@@ -1687,19 +1664,15 @@ static int check_problem(sfm_ctx* h, sfm_ba_problem p, Lay* L) {
     else { constexpr int DD = 6; __VA_ARGS__; }            \
   } while (0)
 // camera block width DD, storage type TT of the Jacobian records, G block stride GG (doubles; G is always float64)
-#define DISPATCH_DT(D, PREC, ...)                                                                     \
-  do {                                                                                                \
-    if ((PREC) == SFM_BA_MIXED) {                                                                     \
-      if ((D) == 10) {                                                                                \
-        if (g_pad()) { constexpr int DD = 10; constexpr int GG = 32; typedef float TT; __VA_ARGS__; } \
-        else { constexpr int DD = 10; constexpr int GG = 30; typedef float TT; __VA_ARGS__; }         \
-      } else { constexpr int DD = 6; constexpr int GG = 18; typedef float TT; __VA_ARGS__; }          \
-    } else {                                                                                          \
-      if ((D) == 10) {                                                                                \
-        if (g_pad()) { constexpr int DD = 10; constexpr int GG = 32; typedef double TT; __VA_ARGS__; } \
-        else { constexpr int DD = 10; constexpr int GG = 30; typedef double TT; __VA_ARGS__; }        \
-      } else { constexpr int DD = 6; constexpr int GG = 18; typedef double TT; __VA_ARGS__; }         \
-    }                                                                                                 \
+#define DISPATCH_DT(D, PREC, ...)                                                                 \
+  do {                                                                                            \
+    if ((PREC) == SFM_BA_MIXED) {                                                                 \
+      if ((D) == 10) { constexpr int DD = 10; constexpr int GG = 32; typedef float TT; __VA_ARGS__; }  \
+      else { constexpr int DD = 6; constexpr int GG = 18; typedef float TT; __VA_ARGS__; }             \
+    } else {                                                                                      \
+      if ((D) == 10) { constexpr int DD = 10; constexpr int GG = 32; typedef double TT; __VA_ARGS__; } \
+      else { constexpr int DD = 6; constexpr int GG = 18; typedef double TT; __VA_ARGS__; }            \
+    }                                                                                             \
   } while (0)
 #define WST(L, field) ((TT*)(ws + (L).field))
 
@@ -1809,8 +1782,7 @@ extern "C" int sfm_ba_linearize(sfm_handle h, sfm_ba_problem p, const double* x)
   const int C = p->n_cams, P = p->n_pts, D = p->cam_dim, n = C * D;
   const int64_t N = p->n_obs;
   const double* pts = x + (size_t)n;
-  p->warm_pc_ok = p->warm_qc_ok = 0;                  // a new linearisation: the previous damped solves are another system's
-  p->cgp_fail_rel *= 0.8;                             // ... and what was hopeless for the camera CG there may not be here: let it try lower again
+  p->cgp_fail_rel *= 0.8;                             // a new linearisation: what was hopeless for the camera CG may not be here, let it try lower again
   DISPATCH_DT(D, p->precision, {
     hipLaunchKernelGGL(k_campre<DD>, dim3(cdiv(C, 64)), dim3(64), 0, h->stream, x, C, p->fx0, p->fy0, p->cx0,
                        p->cy0, WS(L, campre));
@@ -1869,18 +1841,10 @@ extern "C" int sfm_ba_schur_build(sfm_handle h, sfm_ba_problem p, double alpha) 
     sfm_prof_begin(h, SFM_PROF_SCHUR);
     if (p->n_items > 0) { // 8 groups x ceil(largest group / 4) workgroups
       sfm_prof_begin(h, SFM_PROF_SCHUR_ITEMS);
-      // SFM_SCHUR_KPACK=0: the one-pair-per-MFMA form (K = 3 of 4 used) for comparison
-      static const bool kpack = !(getenv("SFM_SCHUR_KPACK") && getenv("SFM_SCHUR_KPACK")[0] == '0');
-      static const bool ntk2 = getenv("SFM_SCHUR_NT") && getenv("SFM_SCHUR_NT")[0] == '1';    // experiment: non-temporal k2-side loads
-      auto schur_items = [&](auto kp, auto nt) {
-        hipLaunchKernelGGL((k_schur_items<DD, double, GG, decltype(kp)::value, decltype(nt)::value>), dim3(8 * cdiv(p->xcd_max_items, SFM_SCHUR_WG_WAVES)),
-                           dim3(64 * SFM_SCHUR_WG_WAVES), 0, h->stream,
-                           p->xcd_ptr, p->xcd_items, p->item_beg, p->item_end, p->pair_k, p->pair_k2, WS(L, G), WS(L, sch_part),
-                           p->cam_idx, p->item_ptr, p->cch_ptr, C, WS(L, eobs), WS(L, cch_part), p->has_dup ? 0 : 1);
-      };
-      if (ntk2) schur_items(std::true_type{}, std::true_type{});
-      else if (kpack) schur_items(std::true_type{}, std::false_type{});
-      else schur_items(std::false_type{}, std::false_type{});
+      hipLaunchKernelGGL((k_schur_items<DD, double, GG>), dim3(8 * cdiv(p->xcd_max_items, SFM_SCHUR_WG_WAVES)),
+                         dim3(64 * SFM_SCHUR_WG_WAVES), 0, h->stream,
+                         p->xcd_ptr, p->xcd_items, p->item_beg, p->item_end, p->pair_k, p->pair_k2, WS(L, G), WS(L, sch_part),
+                         p->cam_idx, p->item_ptr, p->cch_ptr, C, WS(L, eobs), WS(L, cch_part), p->has_dup ? 0 : 1);
       sfm_prof_end(h, SFM_PROF_SCHUR_ITEMS);
     }
     if (p->has_dup && p->n_cchunks > 0)        // the chunk partials of sum_k G_k e_j by the camera-wise pass over G
@@ -2050,7 +2014,7 @@ enum { CGS_RR0 = 0, CGS_RR = 1, CGS_ITER = 2, CGS_FAIL = 3, CGS_DONE = 4,
 // E_c = chol(S_cc + alpha I); Einv[c] = E_c^-1 (lower, zeros above).  One thread per camera.
 template <int D>
 __global__ __launch_bounds__(64) void k_diag_einv(int C, const double* __restrict__ S, int n, double alpha, double* __restrict__ Einv,
-                            double* __restrict__ Efac /* E_c itself (lower), for warm starts: x~ = E^T y */, double* __restrict__ scal) {
+                            double* __restrict__ Efac /* E_c itself (lower) */, double* __restrict__ scal) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   double L[D][D], X[D][D];
@@ -2140,12 +2104,13 @@ __global__ __launch_bounds__(128) void k_scale_system(int n, int C, const double
 template <int D>
 __global__ __launch_bounds__(128) void k_scale_system_lower(int n, int C, const double* __restrict__ S, double alpha,
                                                             const double* __restrict__ Einv, double* __restrict__ St,
-                                                            const double* __restrict__ rhs, double* __restrict__ rhs_t, int rev) {
+                                                            const double* __restrict__ rhs, double* __restrict__ rhs_t) {
   constexpr int BAND = 128 / D + 2;
   __shared__ double sB[SCALE_NB][D * D], sT[SCALE_NB][D * D], sE2[SCALE_NB][D * D], sE1[D * D];
-  const int c = (rev & 2) ? (int)(gridDim.x - 1u - blockIdx.x) : (int)blockIdx.x, e = threadIdx.x;
+  // descending strips and rows: what k_schur_assemble wrote last is read first - still in the memory-side cache at 1000 cameras
+  const int c = (int)(gridDim.x - 1u - blockIdx.x), e = threadIdx.x;
   const int a = e / D, b = e - a * D;
-  const int by = (rev & 1) ? (int)(gridDim.y - 1u - blockIdx.y) : (int)blockIdx.y;
+  const int by = (int)(gridDim.y - 1u - blockIdx.y);
   const int c2_0 = by * SCALE_NB;
   if (rhs_t && by == 0 && e < D) {
     double t = 0.0;
@@ -2200,11 +2165,6 @@ __global__ void k_block_mv(int C, const double* __restrict__ Einv, const double*
 #pragma unroll
   for (int k = 0; k < D; ++k) t += (transpose ? E[k * D + a] : E[a * D + k]) * (v[c * D + k] + (v2 ? v2[c * D + k] : 0.0));
   out[i] = sgn * t;
-}
-// out = a - delta * b (b may be null)
-__global__ void k_taylor(int n, const double* __restrict__ a, const double* __restrict__ b, double delta, double* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = a[i] - (b ? delta * b[i] : 0.0);
 }
 // state 0 of the recurrence: x = 0, r = p = rhs; rr0
 __global__ __launch_bounds__(256) void k_cgs_init(int n, const double* __restrict__ rhs, double* __restrict__ x,
@@ -2368,38 +2328,15 @@ struct PrFuse {
 template <int NC, int D>
 __global__ __launch_bounds__(256, 1) void k_cgs_persist(int n, double rtol2, int max_iter, unsigned salt,
                                                         const double* __restrict__ St, const double* __restrict__ rhs,
-                                                        const double* __restrict__ x0 /* may be null: start from 0 */,
                                                         double* __restrict__ x_out, pr_u64* mail /* [2][n][2] granules */,
                                                         pr_u64* abort_w, double* __restrict__ scal, PrFuse f, int sabotage,
-                                                        double* __restrict__ host_status /* pinned host memory, device-mapped: 8 words */,
-                                                        unsigned* __restrict__ tickets /* null: every workgroup of the grid works */) {
+                                                        double* __restrict__ host_status /* pinned host memory, device-mapped: 8 words */) {
   __shared__ double s_part[PR_ROWS][4];
   __shared__ double s_red[4];
   __shared__ int s_ok[4];
-  __shared__ int s_blk;
   __shared__ double s_x[PR_MAX_N];                  // workgroup 0, epilogue: x~ for the block-wise back-transformation
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  // ONE-XCD MODE (tickets != null; n <= PR_XCD_MAX_N): the grid is 8 x the workgroups the system needs, dealt round-robin over
-  // the XCDs by the dispatcher; only the workgroups that find themselves on XCD 0 work, each on the block of rows its ticket
-  // names, the rest leave at once.  The all-gather then never leaves that XCD's L2: entries are published with PLAIN stores
-  // (the line stays in L2) and polled with loads that bypass L1 only - a hop is an L2 access, where the device-wide form pays
-  // the fabric twice per iteration (store to the memory side, reload from it).  Same arithmetic in the same order: bitwise the
-  // device-wide result.  Placement is a speed matter only: should fewer than `need` workgroups ever land on XCD 0, the ones
-  // that did see it (all 8 x need tickets drawn, XCD 0 short) and abandon the launch; the host then uses the device-wide form.
-  const bool one_xcd = tickets != nullptr;
-  const int need = (n + PR_ROWS - 1) / PR_ROWS;
-  int blk = (int)blockIdx.x;
-  if (one_xcd) {
-    if (tid == 0) {
-      const unsigned xcc = (unsigned)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u;        // HW_REG_XCC_ID[3:0]
-      const unsigned t = __hip_atomic_fetch_add(tickets + xcc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_fetch_add(tickets + 8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_blk = (xcc == 0u && t < (unsigned)need) ? (int)t : -1;
-    }
-    __syncthreads();
-    blk = s_blk;
-    if (blk < 0) return;
-  }
+  const int blk = (int)blockIdx.x;
   // test hook (SFM_CGS_SABOTAGE=1): workgroup 1 never publishes, as if it had not become resident - the others must run into
   // their spin bound, post the abort word and leave; the host then takes the launch-per-iteration route
   if (sabotage > 0 && blk == 1) return;
@@ -2447,7 +2384,7 @@ __global__ __launch_bounds__(256, 1) void k_cgs_persist(int n, double rtol2, int
       rv[2 * c] = in ? rhs[col] : 0.0; rv[2 * c + 1] = in ? rhs[col + 1] : 0.0;
     }
     bv[2 * c] = rv[2 * c]; bv[2 * c + 1] = rv[2 * c + 1];
-    xv[2 * c] = (in && x0) ? x0[col] : 0.0; xv[2 * c + 1] = (in && x0) ? x0[col + 1] : 0.0;
+    xv[2 * c] = 0.0; xv[2 * c + 1] = 0.0;
   }
   double rr0;
   {
@@ -2488,8 +2425,7 @@ __global__ __launch_bounds__(256, 1) void k_cgs_persist(int n, double rtol2, int
       // from one instruction); each 8-byte half carries its own tag, so the store need not be atomic as a whole
       typedef unsigned pr_st4 __attribute__((ext_vector_type(4)));
       const pr_st4 pk = {(unsigned)(bits & 0xFFFFFFFFull), tag, (unsigned)(bits >> 32), tag};
-      if (one_xcd) asm volatile("global_store_dwordx4 %0, %1, off" :: "v"(slot + 2 * (size_t)(row0 + tid)), "v"(pk) : "memory");
-      else asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(slot + 2 * (size_t)(row0 + tid)), "v"(pk) : "memory");
+      asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(slot + 2 * (size_t)(row0 + tid)), "v"(pk) : "memory");
     }
     // gather this thread's columns: 4 granules per chunk (two doubles), re-read until every tag matches
     // ... but not at once: nothing can have arrived before the slowest workgroup's store has crossed the fabric, and a pass that
@@ -2497,11 +2433,7 @@ __global__ __launch_bounds__(256, 1) void k_cgs_persist(int n, double rtol2, int
     // and the lines they pull are invalidated again a moment later.  In-kernel stamps (tools/exp_cgs_phases.sh, n = 2,000):
     // publish -> gather complete 2.83 us polling at once, 1.78 with s_sleep 8 (x 64 clocks) in front, 1.56-1.59 with 24, 1.91
     // with 40, 2.57 with 64; n = 500 (63 workgroups, one chunk per thread): 0.98 at once, 1.08 with 8, 1.31 with 24.
-#ifdef SFM_CGS_FIRST_SLEEP
-    constexpr int FIRST_SLEEP = SFM_CGS_FIRST_SLEEP;               // (sweeps: tools/exp_cgs_phases.sh)
-#else
     constexpr int FIRST_SLEEP = NC == 1 ? 0 : 6 * NC - 4;          // 8 / 14 / 20 for two / three / four chunks per thread
-#endif
     if (FIRST_SLEEP > 0) __builtin_amdgcn_s_sleep(FIRST_SLEEP);
     bool ok = false;
     for (unsigned spins = 0; spins < PR_SPIN_LIMIT; ++spins) {
@@ -2537,16 +2469,8 @@ __global__ __launch_bounds__(256, 1) void k_cgs_persist(int n, double rtol2, int
         yv[2 * c + 1] = in ? __longlong_as_double((long long)((g[4 * c + 2] & 0xFFFFFFFFull) | (g[4 * c + 3] << 32))) : 0.0;
       }
       if (__all(all)) { ok = true; break; }
-      if ((spins & 31u) == 31u) {
-        if (__hip_atomic_load(abort_w, PR_RLX_AGENT) == (pr_u64)salt) break;     // somebody gave up
-        if (one_xcd && __hip_atomic_load(tickets + 8, PR_RLX_AGENT) == 8u * (unsigned)need &&
-            __hip_atomic_load(tickets, PR_RLX_AGENT) < (unsigned)need) break;     // every ticket is drawn and XCD 0 holds too few
-      }
-#ifdef SFM_CGS_LOOP_SLEEP
-      __builtin_amdgcn_s_sleep(SFM_CGS_LOOP_SLEEP);
-#else
+      if ((spins & 31u) == 31u && __hip_atomic_load(abort_w, PR_RLX_AGENT) == (pr_u64)salt) break;     // somebody gave up
       __builtin_amdgcn_s_sleep(2);                    // (polling without the sleep measured the same: 135.1 / 100.1 us per system)
-#endif
     }
     CGS_STAMP(3);
     double td = 0.0;
@@ -2634,25 +2558,12 @@ __global__ __launch_bounds__(256, 1) void k_cgs_persist(int n, double rtol2, int
   };
 
   int round = 0;
-  if (x0) {                                         // warm start: r = rhs - S~ x0 (one more round of the same exchange)
-    double unused;
-    if (!exchange(xv, round++, unused)) { finish(rr0, 0, -1.0, 0.0); return; }
+  double rr = rr0;                                  // x = 0: r = p = rhs
 #pragma unroll
-    for (int i = 0; i < 2 * NC; ++i) rv[i] -= yv[i];
-  }
-  double rr;
-  {
-    double t = 0.0;
-#pragma unroll
-    for (int i = 0; i < 2 * NC; ++i) { pv[i] = rv[i]; t += rv[i] * rv[i]; }
-    rr = block_sum256_fast(t, s_red);
-  }
+  for (int i = 0; i < 2 * NC; ++i) pv[i] = rv[i];
   if (!(rr0 > 0.0)) {                               // zero right-hand side: x = 0; NaN / Inf in it: not a system CG can solve (fail 2 ->
-    if (rr0 == 0.0) {                               // the caller's factorisation route reports the non-finite step)
-#pragma unroll
-      for (int i = 0; i < 2 * NC; ++i) xv[i] = 0.0;
-      finish(0.0, 0, 1.0, 0.0);
-    } else finish(rr0, 0, 1.0, 2.0);
+    if (rr0 == 0.0) finish(0.0, 0, 1.0, 0.0);       // the caller's factorisation route reports the non-finite step)
+    else finish(rr0, 0, 1.0, 2.0);
     return;
   }
   int it = 0;
@@ -2695,51 +2606,34 @@ static unsigned cgs_next_salt() {
   do { s = (seq.fetch_add(1u, std::memory_order_relaxed) + 1u) & 0xFFFFFFu; } while (s == 0u);
   return s;
 }
-// n up to which the whole grid fits ONE XCD (32 CUs x 3 workgroups of 256 threads at <= 168 registers: NC <= 2): there the
-// all-gather can run through that XCD's L2 (k_cgs_persist, one-XCD mode).  OPT-IN (SFM_CGS_XCD=1): measured at n = 500 (cfg3,
-// tools/exp_cg_fixed_cost.py 50 20000) it saves 6 % per iteration (2.44 against 2.60 us) and costs 10 us more per launch (the
-// 8 x grid, the ticket draw): 735 against 772 LM-iterations/s at cfg3 - an iteration is bound by its wave sums, barriers and
-// the poll loop, not by where the granules travel (tools/experiments/README.md).
-constexpr int PR_XCD_MAX_N = 768;
-static bool cgs_one_xcd(sfm_ctx* h, int n) {
-  const char* e = getenv("SFM_CGS_XCD");
-  return n <= PR_XCD_MAX_N && !h->cgs_xcd_off && e && e[0] == '1';
-}
 struct PrLaunch {      // everything a (re)launch of one system needs
-  int n, D; const double* St; const double* rhs; const double* x0_t; double* x_t; double* mail; double* scal; double rtol; PrFuse fuse;
+  int n, D; const double* St; const double* rhs; double* x_t; double* mail; double* scal; double rtol; PrFuse fuse;
   double* pin;         // pinned host words the kernel writes its verdict to
-  int which;           // 0: step system, 1: q system (each has its own ticket words in scal)
 };
-static int cgs_persist_launch(sfm_ctx* h, const PrLaunch& a, bool one_xcd) {
+static int cgs_persist_launch(sfm_ctx* h, const PrLaunch& a) {
   const int n = a.n, D = a.D;
-  const unsigned need = (unsigned)cdiv(n, PR_ROWS);
-  const unsigned grid = one_xcd ? 8u * need : need;
+  const unsigned grid = (unsigned)cdiv(n, PR_ROWS);
   const int nc = (int)cdiv(n, 512);
   pr_u64* abort_w = (pr_u64*)(a.scal + 12);
-  unsigned* tickets = one_xcd ? (unsigned*)(a.scal + 16 + 16 * a.which) : nullptr;
   const unsigned salt = cgs_next_salt();
   const double rtol2 = a.rtol * a.rtol;
-  const int sabotage = (getenv("SFM_CGS_SABOTAGE") && getenv("SFM_CGS_SABOTAGE")[0] == '1' && need > 1) ? 1 : 0;
+  const int sabotage = (getenv("SFM_CGS_SABOTAGE") && getenv("SFM_CGS_SABOTAGE")[0] == '1' && grid > 1) ? 1 : 0;
   a.pin[CGS_DONE] = -1.0;                          // what a launch that never wrote its verdict reads as: abandoned
-  a.pin[7] = one_xcd ? 1.0 : 0.0;                  // (host-side note beside the verdict: which mode this launch ran in)
-#define PR_LAUNCH(NC, DD_) hipLaunchKernelGGL((k_cgs_persist<NC, DD_>), dim3(grid), dim3(256), 0, h->stream, n, rtol2, CGS_MAX_ITER, salt, a.St, a.rhs, a.x0_t, a.x_t, (pr_u64*)a.mail, abort_w, a.scal, a.fuse, sabotage, a.pin, tickets)
+#define PR_LAUNCH(NC, DD_) hipLaunchKernelGGL((k_cgs_persist<NC, DD_>), dim3(grid), dim3(256), 0, h->stream, n, rtol2, CGS_MAX_ITER, salt, a.St, a.rhs, a.x_t, (pr_u64*)a.mail, abort_w, a.scal, a.fuse, sabotage, a.pin)
   if (D == 10) { if (nc <= 1) PR_LAUNCH(1, 10); else if (nc == 2) PR_LAUNCH(2, 10); else if (nc == 3) PR_LAUNCH(3, 10); else PR_LAUNCH(4, 10); }
   else { if (nc <= 1) PR_LAUNCH(1, 6); else if (nc == 2) PR_LAUNCH(2, 6); else if (nc == 3) PR_LAUNCH(3, 6); else PR_LAUNCH(4, 6); }
 #undef PR_LAUNCH
   SFM_LAUNCH_CHECK(h, "cgs_persist_launch");
   return SFM_OK;
 }
-static int cgs_persist_launch(sfm_ctx* h, const PrLaunch& a) { return cgs_persist_launch(h, a, cgs_one_xcd(h, a.n)); }
 static void cgs_persist_read(const double* st, int* iters_out, int* status, int* ran) {
   *ran = 0; *status = 1;
-  if (st[CGS_DONE] == -1.0) return;                 // the launch was abandoned (a spin ran out, or XCD 0 came up short)
+  if (st[CGS_DONE] == -1.0) return;                 // the launch was abandoned (a spin ran out)
   *ran = 1;
   *iters_out += (int)st[CGS_ITER];
   if (st[CGS_FAIL] == 0.0 && st[CGS_DONE] != 0.0) *status = 0;
 }
 // The verdict of a launch has arrived (an event or a stream synchronisation behind it).  An abandoned launch is dealt with here:
-//   * it ran in one-XCD mode: that mode is switched off for the handle and the SAME system is launched again device-wide - the
-//     two modes are bitwise the same computation, so this is invisible in the results (and to the other ranks of a sharded solve);
 //   * `sharded` (the problem is one rank's shard): every rank must take the SAME route through the camera solve - the
 //     launch-per-iteration kernel sums in another order, and a rank that switched on its own would hold a replicated camera step
 //     that differs from its peers' in the last bits and, sooner or later, a different trial history and a different sequence of
@@ -2751,24 +2645,18 @@ static int cgs_persist_verdict(sfm_ctx* h, const PrLaunch& a, int sharded, int* 
   *relaunched = 0;
   cgs_persist_read(a.pin, iters_out, status, ran);
   if (*ran) return SFM_OK;
-  auto again = [&](bool one_xcd) -> int {
+  auto again = [&]() -> int {
     *relaunched = 1;
-    SFM_HIP(h, hipMemsetAsync(a.scal, 0, 64 * sizeof(double), h->stream));
-    int rc = cgs_persist_launch(h, a, one_xcd); if (rc) return rc;
+    SFM_HIP(h, hipMemsetAsync(a.scal, 0, CG_SCAL_WORDS * sizeof(double), h->stream));
+    int rc = cgs_persist_launch(h, a); if (rc) return rc;
     SFM_HIP(h, hipStreamSynchronize(h->stream));
     cgs_persist_read(a.pin, iters_out, status, ran);
     return SFM_OK;
   };
-  if (a.pin[7] == 1.0) {
-    h->cgs_xcd_off = 1;
-    fprintf(stderr, "sfm_amd: the one-XCD launch of the persistent CG was abandoned (workgroups not dealt evenly over the XCDs?); using the device-wide form from now on\n");
-    int rc = again(false); if (rc) return rc;
-    if (*ran) return SFM_OK;
-  }
   if (sharded) {
     for (int attempt = 1; attempt <= CGS_SHARDED_RETRIES && !*ran; ++attempt) {
       fprintf(stderr, "sfm_amd: the persistent CG launch of a sharded solve was abandoned; launching it again (%d of %d)\n", attempt, CGS_SHARDED_RETRIES);
-      int rc = again(false); if (rc) return rc;
+      int rc = again(); if (rc) return rc;
     }
     if (!*ran)
       return sfm_fail(h, SFM_ERR_HIP, "camera CG",
@@ -2789,23 +2677,17 @@ static int cgs_solve(sfm_ctx* h, int n, const double* St, const double* rhs_t, d
   *status = 1;
   // (column chunks per thread, rows per workgroup): 128 registers of prefetched matrix per thread in the two larger shapes
   // four rows per workgroup: at n = 2000 that is 512 workgroups (two per CU) - 8 rows / 256 workgroups measured 6 % slower per
-  // iteration, 2 rows / 1,024 workgroups 9 % slower (twice the redundant vector work).  SFM_CGS_ROWS=8 restores the old shapes.
-  const char* cg_env = getenv("SFM_CGS_ROWS");
-  const bool rows8 = cg_env && cg_env[0] == '8';
-  const int shape = n <= 1024 ? (rows8 ? 0 : 5) : (n <= 2048 ? (rows8 ? 1 : 3) : 2);
-  const int rows = (shape == 0 || shape == 1) ? 8 : 4;
-  const int per_xcd_wg = (int)cdiv(cdiv(n, 8), rows);
-  const unsigned grid = 8u * (unsigned)per_xcd_wg;
+  // iteration, 2 rows / 1,024 workgroups 9 % slower (twice the redundant vector work).
+  constexpr int ROWS = 4;
+  const unsigned grid = 8u * (unsigned)cdiv(cdiv(n, 8), ROWS);
   hipLaunchKernelGGL(k_cgs_init, dim3(1), dim3(256), 0, h->stream, n, rhs_t, x_t, vec, vec + n, scal);
   int it = 0;
   int batch = 13;                                                  // launch 0 only multiplies: first look after 12 iterations
   while (it <= CGS_MAX_ITER) {
     for (int b = 0; b < batch; ++b, ++it)
-      if (shape == 0) hipLaunchKernelGGL((k_cgs_iter<2, 8>), dim3(grid), dim3(256), 0, h->stream, n, it, rtol2, St, vec, x_t, scal);
-      else if (shape == 1) hipLaunchKernelGGL((k_cgs_iter<4, 8>), dim3(grid), dim3(256), 0, h->stream, n, it, rtol2, St, vec, x_t, scal);
-      else if (shape == 3) hipLaunchKernelGGL((k_cgs_iter<4, 4>), dim3(grid), dim3(256), 0, h->stream, n, it, rtol2, St, vec, x_t, scal);
-      else if (shape == 5) hipLaunchKernelGGL((k_cgs_iter<2, 4>), dim3(grid), dim3(256), 0, h->stream, n, it, rtol2, St, vec, x_t, scal);
-      else hipLaunchKernelGGL((k_cgs_iter<8, 4>), dim3(grid), dim3(256), 0, h->stream, n, it, rtol2, St, vec, x_t, scal);
+      if (n <= 1024) hipLaunchKernelGGL((k_cgs_iter<2, ROWS>), dim3(grid), dim3(256), 0, h->stream, n, it, rtol2, St, vec, x_t, scal);
+      else if (n <= 2048) hipLaunchKernelGGL((k_cgs_iter<4, ROWS>), dim3(grid), dim3(256), 0, h->stream, n, it, rtol2, St, vec, x_t, scal);
+      else hipLaunchKernelGGL((k_cgs_iter<8, ROWS>), dim3(grid), dim3(256), 0, h->stream, n, it, rtol2, St, vec, x_t, scal);
     SFM_HIP(h, hipMemcpyAsync(h->pinned, scal, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     SFM_HIP(h, hipStreamSynchronize(h->stream));
     if (h->pinned[CGS_FAIL] != 0.0) break;
@@ -3068,9 +2950,8 @@ static int cgs_solve_big(sfm_ctx* h, int n, const double* St, const double* rhs_
   // The triangle (405 MB at n = 10,000) is larger than the memory-side cache (256 MB): walked in the same direction every
   // iteration, nothing of it is ever found there (a cyclic walk is LRU's worst case); walked back and forth, the tail of the
   // previous pass is.  Odd launches therefore take the tiles in descending order: 1,361 -> 1,215 us per second system at cfg5
-  // (tools/exp_mall_order.sh; SFM_CGB_ZIGZAG=0 restores the one-way walk).  Which tile a workgroup takes changes nothing in the
-  // arithmetic: every tile's partial sums go to its own slot.
-  static const int zigzag = getenv("SFM_CGB_ZIGZAG") ? atoi(getenv("SFM_CGB_ZIGZAG")) : 1;
+  // (tools/experiments/README.md).  Which tile a workgroup takes changes nothing in the arithmetic: every tile's partial sums go
+  // to its own slot.
   int it = 0;
   int batch = its_hint > 0 ? (its_hint + 4 > 48 ? 48 : its_hint + 4) : 24;
   const int budget = cgs_big_budget();
@@ -3085,7 +2966,7 @@ static int cgs_solve_big(sfm_ctx* h, int n, const double* St, const double* rhs_
   constexpr unsigned SPIN_QUERY = 4096;
   while (it < budget + 2) {
     for (int b = 0; b < batch && it < budget + 2; ++b, ++it) {
-      hipLaunchKernelGGL(k_cgb_symv, dim3(n_tiles), dim3(256), 0, h->stream, n, nb, nbp, it, rtol2, St, vec, wv, dots, P, scal, x_t, zigzag == 1 ? (it & 1) : (zigzag == 2 ? ((it + 1) & 1) : 0),
+      hipLaunchKernelGGL(k_cgb_symv, dim3(n_tiles), dim3(256), 0, h->stream, n, nb, nbp, it, rtol2, St, vec, wv, dots, P, scal, x_t, it & 1,
                          h->pinned + SFM_PIN_CGB, seq);
       hipLaunchKernelGGL(k_cgb_reduce, dim3(nb), dim3(128), 0, h->stream, n, nb, nbp, it, P, vec, wv, dots, scal);
     }
@@ -3197,7 +3078,7 @@ extern "C" int sfm_ba_schur_solve(sfm_handle h, sfm_ba_problem p, double alpha, 
     // S~ = E^-1 (S + alpha I) E^-T into the factor's buffer (S stays as it is: the fallback below needs it), r~ = E^-1 r
     sfm_prof_begin(h, SFM_PROF_CHOL);
     // (cleared by k_schur_assemble when this solve follows its own sfm_ba_schur_build, as it does in every loop of this library)
-    if (!p->cg_scal_clean) { SFM_HIP(h, hipMemsetAsync(WS(L, cg_scal), 0, 64 * sizeof(double), h->stream)); p->einv_alpha = -1.0; }
+    if (!p->cg_scal_clean) { SFM_HIP(h, hipMemsetAsync(WS(L, cg_scal), 0, CG_SCAL_WORDS * sizeof(double), h->stream)); p->einv_alpha = -1.0; }
     p->cg_scal_clean = 0;
     const bool have_einv = p->einv_alpha == alpha && !p->sharded;      // k_schur_assemble of THIS system left them
     p->einv_alpha = -1.0;
@@ -3205,40 +3086,23 @@ extern "C" int sfm_ba_schur_solve(sfm_handle h, sfm_ba_problem p, double alpha, 
     const bool have_st = have_einv && p->st_alpha == alpha && cgs_use_big(n) && !cgs_persist_usable(h, n);
     if (!have_st && (rc = schur_materialise_S(h, p, L))) return rc;
     if (!have_st) DISPATCH_D(D, {
-      // (descending strips and rows: what k_schur_assemble wrote last is read first - still in the memory-side cache at 1000 cameras)
-      static const int scale_rev = getenv("SFM_SCALE_REV") ? atoi(getenv("SFM_SCALE_REV")) : 3;
       if (!have_einv)
         hipLaunchKernelGGL(k_diag_einv<DD>, dim3(cdiv(C, 64)), dim3(64), 0, h->stream, C, S, n, alpha, WS(L, cg_Minv), WS(L, cg_M), WS(L, cg_scal));
       if (cgs_use_big(n) && !cgs_persist_usable(h, n))   // the tile-streaming CG reads the lower triangle (+ the diagonal tiles) only
         hipLaunchKernelGGL(k_scale_system_lower<DD>, dim3(C, cdiv(C, SCALE_NB)), dim3(128), 0, h->stream, n, C, S, alpha, WS(L, cg_Minv), dw.Lm,
-                           S + (size_t)n * n, WS(L, cg_r), scale_rev);
+                           S + (size_t)n * n, WS(L, cg_r));
       else
         hipLaunchKernelGGL(k_scale_system<DD>, dim3(C, cdiv(C, SCALE_NB)), dim3(128), 0, h->stream, n, C, S, alpha, WS(L, cg_Minv), dw.Lm,
                            S + (size_t)n * n, WS(L, cg_r));
     });
     int status = 1, ran = 0;
-    // Warm start (persistent kernel only; SFM_CGS_WARM=1, off by default: measured 13 % fewer iterations and no time saved).
-    // Inside More's iteration consecutive damped systems differ only in alpha, and dp/dalpha = -(H + alpha I)^-1 p = -q is
-    // what the previous solve's second system produced: p_c(alpha') ~ p_c(alpha) - (alpha' - alpha) q_c(alpha), second-order
-    // accurate.  In the scaled variables x~_0 = E'^T y_0 with y_0 = -p_c.
-    double* warm = WS(L, cg_warm);                    // [pc_prev | qc_prev | x0 | scratch]
-    const double* x0 = nullptr;
-    static const bool warm_on = getenv("SFM_CGS_WARM") && getenv("SFM_CGS_WARM")[0] == '1';
-    if (warm_on && p->warm_pc_ok && std::fabs(alpha - p->warm_alpha) <= 0.5 * p->warm_alpha) {
-      hipLaunchKernelGGL(k_taylor, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, n, warm, p->warm_qc_ok ? warm + n : (const double*)nullptr,
-                         alpha - p->warm_alpha, warm + 3 * (size_t)n);
-      DISPATCH_D(D, hipLaunchKernelGGL(k_block_mv<DD>, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, C, WS(L, cg_M), warm + 3 * (size_t)n,
-                                       warm + 2 * (size_t)n, 1, -1.0));          // x~_0 = E^T (-p_c guess)
-      x0 = warm + 2 * (size_t)n;
-    }
-    p->warm_pc_ok = p->warm_qc_ok = 0;
     if (cgs_persist_usable(h, n)) {
       // ONE persistent launch: r~ = E^-1 r in its prologue, p_c = -E^-T x~ in its epilogue.  The host needs its verdict
       // (converged / fall back) but must not idle the GPU for it: the status words are copied to pinned memory, an event is
       // recorded behind the copy, the back-substitution is enqueued on the assumption that the solve converged (it does: 0
       // fallbacks in the bench schedules), and only then the host waits - for the event, not for the stream.
       PrFuse fuse = {WS(L, cg_Minv), nullptr, WS(L, pc), nullptr, nullptr, nullptr, nullptr, 1, 0.0};      // rhs~ = cg_r (k_scale_system)
-      const PrLaunch pl = {n, D, dw.Lm, WS(L, cg_r), x0, WS(L, cg_z), WS(L, cg_mail), WS(L, cg_scal), CGS_RTOL, fuse, h->pinned + SFM_PIN_CG1, 0};
+      const PrLaunch pl = {n, D, dw.Lm, WS(L, cg_r), WS(L, cg_z), WS(L, cg_mail), WS(L, cg_scal), CGS_RTOL, fuse, h->pinned + SFM_PIN_CG1};
       rc = cgs_persist_launch(h, pl);
       if (rc) return rc;
       SFM_HIP(h, hipEventRecord(h->cg_event, h->stream));
@@ -3250,10 +3114,6 @@ extern "C" int sfm_ba_schur_solve(sfm_handle h, sfm_ba_problem p, double alpha, 
       if (rc) return rc;
       if (relaunched && ran && status == 0) launch_backsub(h, p, L, ws, want_q);      // the first one ran on an unfinished p_c
       if (ran && status == 0) {
-        if (warm_on) {
-          SFM_HIP(h, hipMemcpyAsync(warm, WS(L, pc), (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-          p->warm_pc_ok = 1; p->warm_alpha = alpha;
-        }
         p->cg_state = 1;
         cgp_note_ok(p->cg_iters - its_before);
         SFM_LAUNCH_CHECK(h, "sfm_ba_schur_solve");
@@ -3272,10 +3132,6 @@ extern "C" int sfm_ba_schur_solve(sfm_handle h, sfm_ba_problem p, double alpha, 
                                          WS(L, pc), 1, -1.0));                      // p_c = -E^-T x~
     }
     if (status == 0) {
-      if (warm_on) {
-        SFM_HIP(h, hipMemcpyAsync(warm, WS(L, pc), (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        p->warm_pc_ok = 1; p->warm_alpha = alpha;
-      }
       p->cg_state = 1;
       cgp_note_ok(p->cg_iters - its_before);
     } else {
@@ -3342,9 +3198,6 @@ extern "C" int sfm_ba_finish_solve(sfm_handle h, sfm_ba_problem p, int want_q) {
     int status = 0;
     if (want_q) {
       sfm_prof_begin(h, SFM_PROF_TRSV);
-      int ran = 0;
-      status = 1;
-      static const bool warm_on = getenv("SFM_CGS_WARM") && getenv("SFM_CGS_WARM")[0] == '1';
       if (cgs_persist_usable(h, n)) {
         // ONE persistent launch: r~2 = E^-1 (p_c + rhs2 pieces) in its prologue, r~2 . x~2 and the scalars of the solve in its
         // epilogue.  Its verdict travels to pinned memory with the copy enqueued behind it and is looked at where the host
@@ -3353,40 +3206,22 @@ extern "C" int sfm_ba_finish_solve(sfm_handle h, sfm_ba_problem p, int want_q) {
         DISPATCH_D(D, hipLaunchKernelGGL(k_block_mv<DD>, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, C, WS(L, cg_Minv), WS(L, pc),
                                          WS(L, cg_r), 0, 1.0, WS(L, red_q)));
         PrFuse fuse = {WS(L, cg_Minv), nullptr, nullptr, WS(L, pc), WS(L, red_q), WS(L, scalars), p->host_sc, 1, next_ticket(p)};
-        const PrLaunch pl = {n, D, dw.Lm, WS(L, cg_r), nullptr, WS(L, cg_z), WS(L, cg_mail), WS(L, cg_scal), CGS_RTOL, fuse, p->host_sc + SFM_HSC_CG2, 1};
+        const PrLaunch pl = {n, D, dw.Lm, WS(L, cg_r), WS(L, cg_z), WS(L, cg_mail), WS(L, cg_scal), CGS_RTOL, fuse, p->host_sc + SFM_HSC_CG2};
         rc = cgs_persist_launch(h, pl);
         if (rc) return rc;
-        if (!warm_on) {
-          p->cg2_pending = 1;
-          sfm_prof_end(h, SFM_PROF_TRSV);
-          return SFM_OK;
-        }
-        SFM_HIP(h, hipStreamSynchronize(h->stream));
-        int relaunched = 0;
-        rc = cgs_persist_verdict(h, pl, p->sharded, &p->cg_iters, &status, &ran, &relaunched);
-        if (rc) return rc;
-        if (ran && status == 0) {
-          if (p->warm_pc_ok) {                       // q_c = E^-T x~_2 = -dp_c/dalpha for the next system's start vector
-            DISPATCH_D(D, hipLaunchKernelGGL(k_block_mv<DD>, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, C, WS(L, cg_Minv), WS(L, cg_z),
-                                             WS(L, cg_warm) + n, 1, 1.0));
-            p->warm_qc_ok = 1;
-          }
-          sfm_prof_end(h, SFM_PROF_TRSV);
-          SFM_LAUNCH_CHECK(h, "sfm_ba_finish_solve");
-          return SFM_OK;                             // the scalars were written by the kernel's epilogue
-        }
+        p->cg2_pending = 1;
+        sfm_prof_end(h, SFM_PROF_TRSV);
+        return SFM_OK;
       }
-      if (!ran) {
-        hipLaunchKernelGGL(k_add_vec, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, WS(L, pc), WS(L, red_q), WS(L, tvec), n);
-        DISPATCH_D(D, hipLaunchKernelGGL(k_block_mv<DD>, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, C, WS(L, cg_Minv), WS(L, tvec),
-                                         WS(L, cg_r), 0, 1.0));
-        // (the q system of a damped solve takes about as many iterations as its step system just did)
-        if (cgs_use_big(n)) rc = cgs_solve_big(h, n, dw.Lm, WS(L, cg_r), WS(L, cg_z), dw.LmT, WS(L, cg_scal), CGS_RTOL, &p->cg_iters, &status, p->cg_its_sys1);
-        else rc = cgs_solve(h, n, dw.Lm, WS(L, cg_r), WS(L, cg_z), dw.LmT, WS(L, cg_scal), CGS_RTOL, &p->cg_iters, &status);
-        if (rc) return rc;
-        if (status == 0)
-          hipLaunchKernelGGL(k_dot, dim3(1), dim3(1024), 0, h->stream, n, WS(L, cg_r), WS(L, cg_z), WS(L, cg_scal) + 8);
-      }
+      hipLaunchKernelGGL(k_add_vec, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, WS(L, pc), WS(L, red_q), WS(L, tvec), n);
+      DISPATCH_D(D, hipLaunchKernelGGL(k_block_mv<DD>, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, C, WS(L, cg_Minv), WS(L, tvec),
+                                       WS(L, cg_r), 0, 1.0));
+      // (the q system of a damped solve takes about as many iterations as its step system just did)
+      if (cgs_use_big(n)) rc = cgs_solve_big(h, n, dw.Lm, WS(L, cg_r), WS(L, cg_z), dw.LmT, WS(L, cg_scal), CGS_RTOL, &p->cg_iters, &status, p->cg_its_sys1);
+      else rc = cgs_solve(h, n, dw.Lm, WS(L, cg_r), WS(L, cg_z), dw.LmT, WS(L, cg_scal), CGS_RTOL, &p->cg_iters, &status);
+      if (rc) return rc;
+      if (status == 0)
+        hipLaunchKernelGGL(k_dot, dim3(1), dim3(1024), 0, h->stream, n, WS(L, cg_r), WS(L, cg_z), WS(L, cg_scal) + 8);
       sfm_prof_end(h, SFM_PROF_TRSV);
     }
     if (status == 0) {
@@ -3676,7 +3511,7 @@ extern "C" int sfm_ba_solve_pcg(sfm_handle h, sfm_ba_problem p, double alpha, in
   const int64_t N = p->n_obs;
   Pcg cg{h, p, L, ws, alpha, rtol, max_iter, reduce, reduce_user, 0};
   if (reduce) p->sharded = 1;          // the formed-S fallback below solves a replicated camera system: same route on every rank
-  SFM_HIP(h, hipMemsetAsync(WS(L, cg_scal), 0, 64 * sizeof(double), h->stream));
+  SFM_HIP(h, hipMemsetAsync(WS(L, cg_scal), 0, CG_SCAL_WORDS * sizeof(double), h->stream));
   // point factors, G, and this rank's part of the right-hand side r = g_c - W C_a^-1 g_p and of the diagonal blocks
   sfm_prof_begin(h, SFM_PROF_BUILD_G);
   DISPATCH_DT(D, p->precision, {
@@ -3855,7 +3690,7 @@ extern "C" int sfm_ba_read_scalars(sfm_handle h, sfm_ba_problem p, double* out_h
       const int C = p->n_cams, D = p->cam_dim, n = C * D;
       DenseWs dw; dense_ws_carve(WS(L, dense), n, &dw);
       PrFuse fuse = {WS(L, cg_Minv), nullptr, nullptr, WS(L, pc), WS(L, red_q), WS(L, scalars), p->host_sc, 1, p->look_seq};
-      const PrLaunch pl = {n, D, dw.Lm, WS(L, cg_r), nullptr, WS(L, cg_z), WS(L, cg_mail), WS(L, cg_scal), CGS_RTOL, fuse, p->host_sc + SFM_HSC_CG2, 1};
+      const PrLaunch pl = {n, D, dw.Lm, WS(L, cg_r), WS(L, cg_z), WS(L, cg_mail), WS(L, cg_scal), CGS_RTOL, fuse, p->host_sc + SFM_HSC_CG2};
       rc = cgs_persist_verdict(h, pl, p->sharded, &p->cg_iters, &status, &ran, &relaunched);
       if (rc) return rc;
     }

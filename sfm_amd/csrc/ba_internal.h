@@ -5,9 +5,12 @@
 struct Lay {   // workspace offsets in doubles (regions holding float32 in mixed precision are sized in doubles too)
   int64_t recA, recB, campre, campre2, B, gc, Cp, gp, Linv, e, v, tmp3, G, eobs, red_lin, gmax, red_S, red_q,
       red_step, pc, pp, y, tvec, scalars, part_obs, part_pt, part_x, cost_reg, regrec, dense, sch_part, cch_part, cbl_part,
-      cg_r, cg_z, cg_p, cg_Ap, cg_M, cg_Minv, cg_scal, cg_mail, cg_warm, total;
+      cg_r, cg_z, cg_p, cg_Ap, cg_M, cg_Minv, cg_scal, cg_mail, total;
   int64_t nblk_obs, nblk_pt;
 };
+// doubles of the camera CG's status words (cg_scal): every kernel's indices stay below this, the abort word of k_cgs_persist
+// (word 12) included; each clear covers all of them
+constexpr int CG_SCAL_WORDS = 16;
 
 struct sfm_ba_prob {
   sfm_ctx* h;
@@ -70,9 +73,6 @@ struct sfm_ba_prob {
   double cgp_fail_rel, cgp_ok_rel[2];
   int cgp_ok_its[2];
   int cg_its_sys1;           // iterations of the step system of the current damped solve (launch-per-iteration routes)
-  // warm start of the camera CG (ba.hip, sfm_ba_schur_solve): p_c / q_c of the previous damped solve of THIS linearisation
-  int warm_pc_ok, warm_qc_ok;
-  double warm_alpha;
 };
 
 // layout of the pinned page host_sc: the SFM_SC_* scalars, the 8 status words of the pending second-system CG, the ticket

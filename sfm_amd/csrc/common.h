@@ -32,7 +32,6 @@ struct sfm_ctx {
   void* comm;              // ncclComm_t of this handle (comm_rccl.hip), or null
   int comm_owned, comm_ranks, comm_rank;
   int cgs_persist_off;     // set once a persistent CG launch had to be abandoned: per-launch kernel from then on
-  int cgs_xcd_off;         // set once a one-XCD launch of the persistent CG had to be abandoned: device-wide form from then on
   double cgb_seq;          // tickets of the tile-streaming CG's systems (cgs_solve_big spins on word SFM_PIN_CGB + 7)
 };
 

@@ -480,6 +480,6 @@ extern "C" int sfm_ba_bind_workspace(sfm_handle h, sfm_ba_problem p, void* works
   // what it reads from its mailbox by tags alone, so the mailbox must not hold a previous owner's granules: cleared here, with
   // the CG status words (the salts are process-wide and never repeat either - cgs_persist_launch).
   SFM_HIP(h, hipMemsetAsync((double*)workspace + p->L.cg_mail, 0, (size_t)(4 * (int64_t)p->n_cams * p->cam_dim) * sizeof(double), h->stream));
-  SFM_HIP(h, hipMemsetAsync((double*)workspace + p->L.cg_scal, 0, 16 * sizeof(double), h->stream));
+  SFM_HIP(h, hipMemsetAsync((double*)workspace + p->L.cg_scal, 0, CG_SCAL_WORDS * sizeof(double), h->stream));
   return SFM_OK;
 }

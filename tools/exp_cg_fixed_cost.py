@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Camera-solve slots (HIP events) against CG iterations per system at cfg4, over a range of alpha: what a system costs
-before its first iteration.  usage: exp_cg_fixed_cost.py [cams pts]; SFM_CGS_RTOL=1 gives zero iterations, SFM_CGS_XCD=0 the
-device-wide exchange at sizes where the one-XCD form would run."""
+before its first iteration.  usage: exp_cg_fixed_cost.py [cams pts]; SFM_CGS_RTOL=1 gives zero iterations."""
 import sys, os
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -22,8 +22,6 @@
 // float32 value over the whole train set by k_knn2_u8_rerank (k_merge_splits_u8 lists them).
 #include "common.h"
 #include "match_plan.h"
-#include <cstdlib>
-#include <cstdio>
 #include <vector>
 #include <type_traits>
 
@@ -127,7 +125,7 @@ template <int I, int N, class F> __device__ __forceinline__ void static_for(F&& 
 typedef __attribute__((address_space(1))) const void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 // grid.x = n_qblocks * nsplit: split = blockIdx.x % nsplit, the workgroups of one query block run side by side.
-// 256 threads = 4 waves, each wave owns QB blocks of 32 queries; the train split is streamed through LDS in chunks of 128
+// 256 threads = 4 waves, each wave owns two blocks of 32 queries; the train split is streamed through LDS in chunks of 128
 // rows (XOR-swizzled 16-byte granules: conflict-free ds_read_b128), double buffered through registers: the loads of chunk
 // ch + 1 are issued before chunk ch is worked on and written to LDS after it.  (Direct global->LDS loads into a ring of
 // three buffers, two chunks in flight, measured 8-13 % slower here: ~100 cycles of issue per 1 KiB piece and wave.)
@@ -139,22 +137,18 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // (10 min operations + 1 compare per lane instead of 48 ranking operations) is skipped, and in a tile that is not, only
 // the groups of four rows that hold a candidate are ranked.  Skipping is exact, not approximate: the test keeps every
 // candidate with d^2 <= U2, and ties are still resolved on (d^2, index) by the ranking and the merge.
-#ifndef KNN_WAVES
-#define KNN_WAVES 2
-#endif
+//
 // dim 256 (KS = 8: Hamming-256 / ORB over unpacked bits) holds twice the query and operand fragments and spills 7-15 registers
-// at two waves per SIMD.  Measured (round 3, 30,000 x 30,000 x 256 bits): one wave per SIMD, no spills (-DSFM_KNN_KS8_WAVES=1)
-// 535 us = 1.68e12 pairs/s; two waves with the spills 429 us = 2.10e12 - the second wave is worth more than the spills cost.
+// at two waves per SIMD.  Measured (round 3, 30,000 x 30,000 x 256 bits): one wave per SIMD, no spills, 535 us = 1.68e12
+// pairs/s; two waves with the spills 429 us = 2.10e12 - the second wave is worth more than the spills cost.
 // Pairs of 8e6 distances and more no longer come here: they take k_knn2_u8_direct<2, 8> (no LDS, 230 registers, no spill in the
 // loop): 30,000 x 30,000: 461 -> 289 us per call = 3.1e12 pairs/s, 50,000 x 50,000: 1,130 -> 660 us = 3.8e12.
-#ifndef SFM_KNN_KS8_WAVES
-#define SFM_KNN_KS8_WAVES KNN_WAVES
-#endif
-template <int KS, int QB, bool FILTER>   // KS = dim / 32
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS == 8 ? SFM_KNN_KS8_WAVES : KNN_WAVES, KS == 8 ? SFM_KNN_KS8_WAVES : KNN_WAVES))) void k_knn2_u8(
+template <int KS, bool FILTER>   // KS = dim / 32
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_knn2_u8(
     const uint8_t* __restrict__ q, int64_t nq, const uint8_t* __restrict__ tf, int64_t nt,
     const int* __restrict__ th_g, const int* __restrict__ par_g, const int* __restrict__ qn,
     int nsplit, int64_t rows_per_split, const MatchWG* __restrict__ wg, int64_t total_out, Cand* __restrict__ part, int* u2g) {
+  constexpr int QB = 2;                         // query blocks of 32 per wave
   constexpr int DIM = KS * 32;
   constexpr int GPR = DIM / 16;                 // 16-byte granules per row
   constexpr int CHUNK = 128;                   // rows per LDS chunk
@@ -259,9 +253,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS == 8 ? S
     // unit ranks the accumulators of step s - 1 in the gaps between its MFMAs, and the LDS operands of the next tile are
     // fetched a tile ahead into a second register set.
     constexpr int TILES = CHUNK / 32, STEPS = TILES * QB;
-    // with four query blocks a tile is 16 MFMAs long: one operand set, refilled behind the tile's last chain (the other
-    // wave of the SIMD covers the LDS round trip), leaves the registers to the query fragments
-    constexpr int SETS = (QB * KS >= 16 || KNN_WAVES >= 3) ? 1 : 2;
+    // at dim 256 a tile is 16 MFMAs long: one operand set, refilled behind the tile's last chain (the other wave of the
+    // SIMD covers the LDS round trip), leaves the registers to the query fragments
+    constexpr int SETS = KS == 8 ? 1 : 2;
     v4i at[SETS][KS];
     v16i th[SETS];       // accumulator start values of the 16 train rows a lane's registers hold: rows (r&3) + 8 (r>>2) + 4 half
     int4 kp[4];          // parity bits of the rows of the tile being ranked (one set: fetched right after the previous tile's last ranking)
@@ -294,7 +288,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS == 8 ? S
         const int mn = min(min(min(gm[0], gm[1]), gm[2]), gm[3]);
         if (__builtin_amdgcn_ballot_w64(mn < thr[qb]) == 0ull) return;               // wave-uniform: nothing in this tile can enter a top-2
       }
-      if (KNN_WAVES >= 3) load_kp(tile);                    // lean build: the parity bits only when a tile is ranked at all
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         // past the first windows a tile that is not skipped has one or two candidates: only their groups are ranked
@@ -313,7 +306,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS == 8 ? S
       }
     };
     load_ops(0, 0);
-    if (KNN_WAVES < 3) load_kp(0);
+    load_kp(0);
 #pragma unroll
     for (int st = 0; st < STEPS; ++st) {
       const int tile = st / QB, qb = st % QB, set = tile & (SETS - 1);
@@ -331,7 +324,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KS == 8 ? S
       }
       if (SETS == 1 && qb == QB - 1 && tile + 1 < TILES) load_ops(tile + 1, 0);      // behind the last chain that reads the set
       if (st > 0) rank_finish(prev, (st - 1) / QB, (st - 1) % QB);
-      if (KNN_WAVES < 3 && qb == 0 && tile > 0) load_kp(tile);          // after the last ranking that read the previous tile's
+      if (qb == 0 && tile > 0) load_kp(tile);                           // after the last ranking that read the previous tile's
     }
 #pragma unroll
     for (int g = 0; g < 4; ++g) rank_group_min(acc[(STEPS - 1) & 1], g);
@@ -480,14 +473,8 @@ __global__ __launch_bounds__(64 * KS) void k_train_tile_u8(const uint8_t* __rest
   if (threadIdx.x < 2) pb_t[tile * 2 + threadIdx.x] = s_pb[threadIdx.x];
 }
 
-// train rows per workgroup, first : second on a CU (k_knn2_u8_direct).  Measured at 50k x 50k, distance kernel by HIP events:
-// even 378 us, 128:100 370, 135:100 367-368, 150:100 367 (the wave end stamps then lie within 306-354 us instead of 283-375)
-constexpr int MATCH_W_FIRST = 135, MATCH_W_SECOND = 100;
 #ifndef SFM_MATCH_STAMPS
 #define SFM_MATCH_STAMPS 0
-#endif
-#ifndef SFM_MATCH_TH_AHEAD
-#define SFM_MATCH_TH_AHEAD 1
 #endif
 #if SFM_MATCH_STAMPS
 __device__ unsigned long long g_match_stamps[4 * 4096 * 4];
@@ -606,20 +593,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QB == 2 &&
   };
 #undef QUAD_BCAST
   auto load_tile = [&](int64_t tile, int set) {
-#if SFM_MATCH_TH_AHEAD
-    // (first: it is used one step before the operands - see th_carry - and loads return in order)
-    thq[set] = *(const int4*)(th_t + (tile * 2 + half) * 16 + 4 * (lane & 3));
-#endif
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) at[set][ks] = *(const v4i*)(xt + ((tile * KS + ks) * 64 + lane) * 16);
     // the 16 start values of a half-wave: every lane fetches ONE quarter (the quarter its position in its quad names), the
     // quads then pass the quarters round with DPP moves (spread_th).  Four 16-byte loads per lane instead of one would give
     // every lane all 16 directly - and cost the CU's single texture-address path 64 cycles per wave and tile instead of 16;
     // with 13 vector loads per tile that path, not the matrix unit, bounded the kernel (8 waves x 13 x 16 cycles against
-    // 1,024 cycles of MFMAs per tile and SIMD).
-#if !SFM_MATCH_TH_AHEAD
+    // 1,024 cycles of MFMAs per tile and SIMD).  Loaded first: they are used one step before the operands (see th_carry),
+    // and loads return in order.
     thq[set] = *(const int4*)(th_t + (tile * 2 + half) * 16 + 4 * (lane & 3));
-#endif
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) at[set][ks] = *(const v4i*)(xt + ((tile * KS + ks) * 64 + lane) * 16);
     pb[set] = pb_t[tile * 2 + half];
   };
   // The ranking of a step's accumulators (see k_knn2_u8) is issued in the gaps between the MFMAs of the NEXT step, across
@@ -700,9 +682,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QB == 2 &&
     }
   };
   v16i acc[2];
-#if SFM_MATCH_TH_AHEAD
   v16i th_carry;
-#endif
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[1][r] = SENT_TH;         // "previous step" of the first one: padding rows, ranked and ignored
   pb[1] = 0;
@@ -731,14 +711,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QB == 2 &&
     }
     load_tile(tile0 + (t + 1 < n_tiles ? t + 1 : t), pset);
     const int wb_prev = (((t - 1) & 7) << 5) | (4 * half), wb_cur = ((t & 7) << 5) | (4 * half);
-#if SFM_MATCH_TH_AHEAD
-    // The 16 DPP moves that spread a tile's start values used to stand between the last MFMA of one tile and the first of the
-    // next (the first MFMA takes them as its C operand).  They now run in the MFMA gaps of the PREVIOUS tile's last step, four
+    // The 16 DPP moves that spread a tile's start values would stand between the last MFMA of one tile and the first of the
+    // next (the first MFMA takes them as its C operand).  They run in the MFMA gaps of the PREVIOUS tile's last step, four
     // per gap, into th_carry - whose registers are free by then (the last step has copied its start values already).
     const v16i th = th_carry;
-#else
-    const v16i th = spread_th(thq[set]);
-#endif
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
       const v16i& prev = acc[(qb - 1) & 1];                // the very first step ranks the padding values acc[1] starts with
@@ -748,9 +724,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QB == 2 &&
         acc[qb & 1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(at[set][ks], bq[qb][ks], acc[qb & 1], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
         if (ks < 4) rank_group_min(prev, ks);              // the four group minima of the previous step: one per MFMA gap
-#if SFM_MATCH_TH_AHEAD
         if (qb == QB - 1 && ks < 4) spread_th_piece(th_carry, thq[pset], ks);
-#endif
         __builtin_amdgcn_sched_barrier(0);
       }
       if (qb > 0) rank_finish(prev, qb - 1, pb[set], wb_cur);
@@ -761,9 +735,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QB == 2 &&
     }
   };
   if (n_tiles > 0) load_tile(tile0, 0);
-#if SFM_MATCH_TH_AHEAD
   th_carry = spread_th(thq[0]);
-#endif
   // pairs of tiles in a loop with ONE exit, an odd last tile after it: with `if (t + 1 >= n_tiles) break;` between the two
   // halves of the body the compiler kept the running keys of every query block in two register homes, one per exit, and
   // copied them from one to the other after every step (4 of the ~16 vector instructions of a step nothing is ranked in)
@@ -1076,57 +1048,33 @@ static int match_launch(sfm_ctx* h, int metric, const void* q, int64_t nq_rows, 
   if (wg)   // segments choose their own number of splits: slots a segment does not use must read as "empty" (i = -1)
     SFM_HIP(h, hipMemsetAsync(w.part, 0xFF, (size_t)8 * n_out * 2 * sizeof(Cand), h->stream));
   if (metric == SFM_METRIC_L2_U8) {
-    const bool qb4 = qpw == 512;
-    const char* d_env = getenv("SFM_MATCH_DIRECT");        // test / tuning knob: "0" = the LDS kernel also for the large case
-    // one pair at dim 128: the LDS-free kernel, with 4 query blocks per wave from 28,672 queries on and 2 below (8-20 % faster
-    // than the LDS kernel at 2,000 .. 11,000 queries against 4,000 .. 50,000 train rows); the LDS kernel serves the batched
-    // form, the smaller dims and the smallest pairs
-    // dim 256 (ORB over unpacked bits; SFM_MATCH_DIRECT256=0 keeps the LDS kernel): two query blocks per wave, eight MFMAs per step
-    const char* d256_env = getenv("SFM_MATCH_DIRECT256");
-    const bool direct256 = !wg && dim == 256 && !qb4 && (double)nq_rows * (double)nt_rows >= 8e6 && !(d256_env && d256_env[0] == '0');
-    const bool direct2 = !wg && (dim == 128 || direct256) && !qb4 && (double)nq_rows * (double)nt_rows >= 8e6;      // below: launch-bound, the LDS kernel's lighter pre-pass wins by ~3 us
-    const bool direct = (qb4 || direct2) && !(d_env && d_env[0] == '0');
-    if (direct)
-      {
+    const MatchU8Choice k = match_u8_kernel(dim, nq_rows, nt_rows, qpw, wg != nullptr, filter_rows, grid, nsplit);
+    if (k.kernel != MATCH_U8_LDS) {
       // one pre-pass launch: train tiles, then the query norms, and the bounds' initial value on the side
       const unsigned tb = (unsigned)((nt_rows + 31) >> 5);
       const int64_t n_u2 = n_out + 128;
-      if (dim == 256) hipLaunchKernelGGL(k_train_tile_u8<8>, dim3(tb + cdiv(nq_rows * 16, 512)), dim3(512), 0, h->stream, t8, nt_rows, w.tf, w.th, w.par, w.fix_cnt,
-                                         (int)tb, q8, nq_rows, w.qn, w.u2, n_u2);
+      if (k.kernel == MATCH_U8_DIRECT2_KS8) hipLaunchKernelGGL(k_train_tile_u8<8>, dim3(tb + cdiv(nq_rows * 16, 512)), dim3(512), 0, h->stream, t8, nt_rows, w.tf, w.th, w.par, w.fix_cnt,
+                                                               (int)tb, q8, nq_rows, w.qn, w.u2, n_u2);
       else hipLaunchKernelGGL(k_train_tile_u8<4>, dim3(tb + cdiv(nq_rows * 8, 256)), dim3(256), 0, h->stream, t8, nt_rows, w.tf, w.th, w.par, w.fix_cnt,
                               (int)tb, q8, nq_rows, w.qn, w.u2, n_u2);
-    }
-    else {
+    } else {
       hipLaunchKernelGGL(k_train_prep_u8, dim3(cdiv((nt_rows + 1) * (dim >> 4), 256)), dim3(256), 0, h->stream, t8, nt_rows, dim, w.tf, w.th, w.par, w.fix_cnt);
       hipLaunchKernelGGL(k_row_norm_u8, dim3(cdiv(nq_rows * (dim >> 4), 256)), dim3(256), 0, h->stream, q8, nq_rows, dim, 0x7F, 0, w.qn);
     }
-    // the candidate filter pays once the queries see a few thousand train rows (see k_knn2_u8); below that it is 10
-    // operations per tile for nothing
-    const char* f_env = getenv("SFM_MATCH_FILTER");        // test / tuning knob: "0" off, "1" on
-    const bool filter = f_env ? f_env[0] == '1' : filter_rows >= 2048;
-    if (filter && !direct) SFM_HIP(h, hipMemsetAsync(w.u2, 0x7F, (size_t)(n_out + 128) * sizeof(int), h->stream));      // "no bound yet" (the direct path's pre-pass writes it)
+    if (k.filter) SFM_HIP(h, hipMemsetAsync(w.u2, 0x7F, (size_t)(n_out + 128) * sizeof(int), h->stream));      // "no bound yet" (the direct path's pre-pass writes it)
     sfm_prof_begin(h, SFM_PROF_KNN);
-#define KNN_LAUNCH(KS, QB, F) hipLaunchKernelGGL((k_knn2_u8<KS, QB, F>), dim3(grid), dim3(256), 0, h->stream, q8, nq_rows, w.tf, nt_rows, w.th, w.par, w.qn, nsplit, rps, wg, n_out, w.part, w.u2)
-    if (direct) {
-      // uneven train splits for the two workgroups of a CU (see the kernel): grids of one round at two workgroups per CU only
-      // (256 < grid <= 512, four query blocks per wave), splits long enough to cut.  SFM_MATCH_SPLIT_W="first:second" overrides,
-      // "0" = even splits
-      int w_first = 0, w_second = 0;
-      if (!direct2 && grid > 256 && grid <= 512 && nsplit > 1 && nt_rows / nsplit >= 2048) { w_first = MATCH_W_FIRST; w_second = MATCH_W_SECOND; }
-      if (const char* we = getenv("SFM_MATCH_SPLIT_W")) {
-        int a = 0, b = 0;
-        if (sscanf(we, "%d:%d", &a, &b) == 2 && a > 0 && b > 0 && a <= 1024 && b <= 1024 && nsplit > 1) { w_first = a; w_second = b; }
-        else { w_first = w_second = 0; }
-      }
-      if (direct256) hipLaunchKernelGGL((k_knn2_u8_direct<2, 8>), dim3(grid), dim3(256), 0, h->stream, q8, nq_rows, w.tf, nt_rows, w.th, w.par, w.qn, nsplit, rps, w.part, w.u2, w_first, w_second);
-      else if (direct2) hipLaunchKernelGGL((k_knn2_u8_direct<2>), dim3(grid), dim3(256), 0, h->stream, q8, nq_rows, w.tf, nt_rows, w.th, w.par, w.qn, nsplit, rps, w.part, w.u2, w_first, w_second);
-      else hipLaunchKernelGGL((k_knn2_u8_direct<4>), dim3(grid), dim3(256), 0, h->stream, q8, nq_rows, w.tf, nt_rows, w.th, w.par, w.qn, nsplit, rps, w.part, w.u2, w_first, w_second);
-    } else if (filter) {
-      if (qb4) KNN_LAUNCH(4, 4, true); else if (dim == 256) KNN_LAUNCH(8, 2, true); else if (dim == 128) KNN_LAUNCH(4, 2, true); else if (dim == 64) KNN_LAUNCH(2, 2, true); else KNN_LAUNCH(1, 2, true);
+#define DIRECT_LAUNCH(...) hipLaunchKernelGGL((k_knn2_u8_direct<__VA_ARGS__>), dim3(grid), dim3(256), 0, h->stream, q8, nq_rows, w.tf, nt_rows, w.th, w.par, w.qn, nsplit, rps, w.part, w.u2, k.w_first, k.w_second)
+#define KNN_LAUNCH(KS, F) hipLaunchKernelGGL((k_knn2_u8<KS, F>), dim3(grid), dim3(256), 0, h->stream, q8, nq_rows, w.tf, nt_rows, w.th, w.par, w.qn, nsplit, rps, wg, n_out, w.part, w.u2)
+    if (k.kernel == MATCH_U8_DIRECT2_KS8) DIRECT_LAUNCH(2, 8);
+    else if (k.kernel == MATCH_U8_DIRECT2) DIRECT_LAUNCH(2);
+    else if (k.kernel == MATCH_U8_DIRECT4) DIRECT_LAUNCH(4);
+    else if (k.filter) {
+      if (dim == 256) KNN_LAUNCH(8, true); else if (dim == 128) KNN_LAUNCH(4, true); else if (dim == 64) KNN_LAUNCH(2, true); else KNN_LAUNCH(1, true);
     } else {
-      if (qb4) KNN_LAUNCH(4, 4, false); else if (dim == 256) KNN_LAUNCH(8, 2, false); else if (dim == 128) KNN_LAUNCH(4, 2, false); else if (dim == 64) KNN_LAUNCH(2, 2, false); else KNN_LAUNCH(1, 2, false);
+      if (dim == 256) KNN_LAUNCH(8, false); else if (dim == 128) KNN_LAUNCH(4, false); else if (dim == 64) KNN_LAUNCH(2, false); else KNN_LAUNCH(1, false);
     }
 #undef KNN_LAUNCH
+#undef DIRECT_LAUNCH
     sfm_prof_end(h, SFM_PROF_KNN);
     hipLaunchKernelGGL(k_merge_splits_u8, dim3(cdiv(n_out, 256)), dim3(256), 0, h->stream, n_out, wg ? 8 : nsplit, w.part, idx1, idx2,
                        d1, d2, w.fix_cnt, w.fix_list, take_root ? 1 : 0);

@@ -1,7 +1,8 @@
 // Host-only check of sfm_amd/csrc/match_plan.h, built with -fsanitize=address,undefined by tests/test_host_logic.py.
 // Random segment tables -> plan_segments: every (query row, train row) of every segment must be covered by exactly one
 // piece, pieces stay inside their segment, splits are whole 128-row chunks except the last, output rows are the
-// segment's query rows in order; pick_nsplit respects its limits.  Prints "ok <pieces>" or a diagnostic and exits 1.
+// segment's query rows in order; pick_nsplit respects its limits; match_u8_kernel picks the expected uint8 kernel, filter
+// and split weights on each side of its thresholds.  Prints "ok <pieces>" or a diagnostic and exits 1.
 #define SFM_MATCH_PLAN_STANDALONE 1
 #include "match_plan.h"
 #include <cstdio>
@@ -61,6 +62,49 @@ int main(int argc, char** argv) {
       const int ns = pick_nsplit(nt, nqb);
       if (ns < 1 || ns > 8 || (ns > 1 && nt / ns < 512)) return fail("pick_nsplit", (long)nt, ns);
     }
+  // the uint8 distance kernel on each side of every threshold of match_u8_kernel, for one pair planned as sfm_match_knn2
+  // plans it (nsplit / grid checked where given: they decide the split weights)
+  struct KernelCase { int64_t nq, nt; int dim; MatchU8Kernel kernel; bool filter; int w_first, w_second, nsplit; int64_t grid; };
+  const KernelCase cases[] = {
+      {50000, 50000, 128, MATCH_U8_DIRECT4, false, MATCH_W_FIRST, MATCH_W_SECOND, 5, 490},   // one round of two workgroups per CU
+      {50000, 10240, 128, MATCH_U8_DIRECT4, false, MATCH_W_FIRST, MATCH_W_SECOND, 5, 490},   // 2,048 train rows per split
+      {131072, 8192, 128, MATCH_U8_DIRECT4, false, MATCH_W_FIRST, MATCH_W_SECOND, 2, 512},   // 512 workgroups, two splits
+      {50000, 10000, 128, MATCH_U8_DIRECT4, false, 0, 0, 5, 490},                            // 2,000 per split: even
+      {150000, 600, 128, MATCH_U8_DIRECT4, false, 0, 0, 1, 293},                             // one split: even
+      {28672, 2000, 128, MATCH_U8_DIRECT4, false, 0, 0, 3, 168},                             // 256 workgroups or fewer: even
+      {300000, 50000, 128, MATCH_U8_DIRECT4, false, 0, 0, 6, 3516},                          // more than 512 workgroups: even
+      {28671, 2000, 128, MATCH_U8_DIRECT2, false, 0, 0, 0, 0},                               // below 28,672 queries: two query blocks
+      {20000, 20000, 128, MATCH_U8_DIRECT2, false, 0, 0, 6, 474},                            // weights only for four query blocks
+      {20000, 400, 128, MATCH_U8_DIRECT2, false, 0, 0, 0, 0},                                // 8e6 distances
+      {20000, 399, 128, MATCH_U8_LDS, false, 0, 0, 0, 0},                                    // below 8e6: the LDS kernel
+      {20001, 3, 128, MATCH_U8_LDS, false, 0, 0, 0, 0},
+      {2000, 2300, 128, MATCH_U8_LDS, true, 0, 0, 0, 0},                                     // the filter from 2,048 train rows
+      {2000, 2048, 128, MATCH_U8_LDS, true, 0, 0, 0, 0},
+      {2000, 2047, 128, MATCH_U8_LDS, false, 0, 0, 0, 0},
+      {30000, 30000, 256, MATCH_U8_DIRECT2_KS8, false, 0, 0, 0, 0},                          // dim 256 (ORB over unpacked bits)
+      {2000, 4000, 256, MATCH_U8_DIRECT2_KS8, false, 0, 0, 0, 0},
+      {2000, 3999, 256, MATCH_U8_LDS, true, 0, 0, 0, 0},
+      {30000, 30000, 64, MATCH_U8_LDS, true, 0, 0, 0, 0},                                    // dims below 128: always the LDS kernel
+      {30000, 30000, 32, MATCH_U8_LDS, true, 0, 0, 0, 0},
+  };
+  for (const KernelCase& e : cases) {
+    const int64_t qpw = match_qpw(SFM_METRIC_L2_U8, e.dim, e.nq, false);
+    int nsplit; int64_t rps;
+    match_tiling(SFM_METRIC_L2_U8, e.nq, qpw, e.nt, &nsplit, &rps);
+    const int64_t grid = (e.nq + qpw - 1) / qpw * nsplit;
+    const MatchU8Choice c = match_u8_kernel(e.dim, e.nq, e.nt, qpw, false, e.nt, grid, nsplit);
+    if (c.kernel != e.kernel || c.filter != e.filter) return fail("kernel", (long)e.nq, (long)e.nt);
+    if (c.w_first != e.w_first || c.w_second != e.w_second) return fail("split weights", (long)e.nq, (long)e.nt);
+    if (e.nsplit && (nsplit != e.nsplit || grid != e.grid)) return fail("tiling", nsplit, (long)grid);
+  }
+  // a batched plan takes the LDS kernel whatever its size; the filter follows the longest segment
+  for (int64_t longest : {2047L, 2048L, 30000L}) {
+    const int64_t qb[2] = {0, 30000}, qe[2] = {30000, 60000}, tb[2] = {0, 1000}, te[2] = {1000, 1000 + longest};
+    std::vector<MatchWG> wgs; std::vector<int64_t> out_ptr;
+    plan_segments(SFM_METRIC_L2_U8, 128, 2, qb, qe, tb, te, &wgs, &out_ptr);
+    const MatchU8Choice c = match_u8_kernel(128, 60000, 1000 + longest, 256, true, longest, (int64_t)wgs.size(), 1);
+    if (c.kernel != MATCH_U8_LDS || c.filter != (longest >= 2048) || c.w_first || c.w_second) return fail("batched kernel", (long)longest, c.kernel);
+  }
   std::printf("ok %ld\n", total_pieces);
   return 0;
 }

@@ -342,8 +342,8 @@ def test_oracle_statistics_equal_the_reference_run():
 
 # ------------------------------------------------------------------ native host logic under the sanitizers
 def test_matcher_plan_under_address_and_ub_sanitizers(tmp_path):
-    """sfm_amd/csrc/match_plan.h (how a batch of image pairs is cut into workgroup pieces, how many train splits a
-    launch takes) is plain C++: built here with g++ -fsanitize=address,undefined and driven over random segment tables
+    """sfm_amd/csrc/match_plan.h (how a batch of image pairs is cut into workgroup pieces, how many train splits and
+    which uint8 distance kernel a launch takes) is plain C++: built here with g++ -fsanitize=address,undefined and driven over random segment tables
     (empty images, images around the 512-row split limit, large ones).  Found on its first run: a division by zero for a
     segment without train rows in sfm_match_batched_workspace_bytes, which validates nothing before it plans."""
     import shutil, subprocess

@@ -1076,10 +1076,7 @@ __device__ __forceinline__ void strip_item_sums(int C, int r, int c_0, int nv, i
     if (j < nv && c_0 + j == r) v[j] += B[(size_t)r * D * D + e];
   }
 }
-constexpr int ASM_ROUNDS_FROM = 512;   // cameras from which k_schur_assemble walks its item tiles round by round (strip_item_sums)
-// ASM_NB blocks per workgroup: 8 (640-byte rows) from 128 cameras on; 2 below - a thread sums its element of every block of the
-// workgroup in turn, and with few cameras a block holds many items (50 cameras / 200k observations: 4 per block) while the grid
-// is small: at cfg3 eight blocks per workgroup cost 11 us more than they saved
+// <ASM_NB blocks per workgroup, ROUNDS> by camera count: schur_assemble_shape (ba_plan.h)
 template <int D, int ASM_NB, bool ROUNDS>
 __global__ __launch_bounds__(128) void k_schur_assemble(int C, const int* __restrict__ item_ptr,
                                                         const double* __restrict__ part,
@@ -1782,7 +1779,7 @@ extern "C" int sfm_ba_linearize(sfm_handle h, sfm_ba_problem p, const double* x)
   const int C = p->n_cams, P = p->n_pts, D = p->cam_dim, n = C * D;
   const int64_t N = p->n_obs;
   const double* pts = x + (size_t)n;
-  p->cgp_fail_rel *= 0.8;                             // a new linearisation: what was hopeless for the camera CG may not be here, let it try lower again
+  p->cgp.fail_rel *= 0.8;                             // a new linearisation: what was hopeless for the camera CG may not be here, let it try lower again
   DISPATCH_DT(D, p->precision, {
     hipLaunchKernelGGL(k_campre<DD>, dim3(cdiv(C, 64)), dim3(64), 0, h->stream, x, C, p->fx0, p->fy0, p->cx0,
                        p->cy0, WS(L, campre));
@@ -1823,8 +1820,39 @@ extern "C" int sfm_ba_finish_linearize(sfm_handle h, sfm_ba_problem p) {
   return SFM_OK;
 }
 
-static bool cgs_use_big(int n);
-static bool cgs_persist_usable(sfm_ctx* h, int n);
+// S (red_S) and its right-hand side from the item tiles; einv_out / m_out: the diagonal blocks' factors of S + alpha I for the
+// camera CG as well (null: not wanted)
+static void launch_schur_assemble(sfm_ctx* h, sfm_ba_problem p, const Lay& L, double alpha, double* einv_out, double* m_out) {
+  double* ws = (double*)p->workspace;
+  const int C = p->n_cams, D = p->cam_dim, n = C * D;
+  const AsmShape shape = schur_assemble_shape(C);
+#define ASM_LAUNCH(NB, ROUNDS)                                                                                                  \
+  hipLaunchKernelGGL((k_schur_assemble<DD, NB, ROUNDS>), dim3(C, cdiv(C, NB)), dim3(128), 0, h->stream, C, p->item_ptr,          \
+                     WS(L, sch_part), WS(L, B), WS(L, red_S), WS(L, cg_scal), p->cch_ptr, WS(L, cch_part), WS(L, gc),             \
+                     WS(L, red_S) + (size_t)n * n, alpha, einv_out, m_out)
+  DISPATCH_D(D, {
+    if (shape.rounds) ASM_LAUNCH(8, true);
+    else if (shape.nb == 8) ASM_LAUNCH(8, false);
+    else ASM_LAUNCH(2, false);
+  });
+#undef ASM_LAUNCH
+}
+// the scaled system S~ (lower triangle) and r~ instead, behind the diagonal blocks' factors (k_schur_diag)
+static void launch_schur_assemble_scaled(sfm_ctx* h, sfm_ba_problem p, const Lay& L, double alpha, double* St) {
+  double* ws = (double*)p->workspace;
+  const int C = p->n_cams, D = p->cam_dim, n = C * D;
+#define ASM_LAUNCH(NB)                                                                                                          \
+  hipLaunchKernelGGL((k_schur_assemble_scaled<DD, NB>), dim3(C, cdiv(C, NB)), dim3(128), 0, h->stream, C, p->item_ptr,           \
+                     WS(L, sch_part), WS(L, B), St, p->cch_ptr, WS(L, cch_part), WS(L, gc), WS(L, red_S) + (size_t)n * n,         \
+                     WS(L, cg_r), alpha, WS(L, cg_Minv))
+  DISPATCH_D(D, {
+    hipLaunchKernelGGL(k_schur_diag<DD>, dim3(C), dim3(128), 0, h->stream, C, p->item_ptr, WS(L, sch_part), WS(L, B), alpha,
+                       WS(L, cg_Minv), WS(L, cg_M), WS(L, cg_scal));
+    if (schur_assemble_scaled_nb(C) == 4) ASM_LAUNCH(4);
+    else ASM_LAUNCH(2);
+  });
+#undef ASM_LAUNCH
+}
 
 extern "C" int sfm_ba_schur_build(sfm_handle h, sfm_ba_problem p, double alpha) {
   Lay L; int rc = check_problem(h, p, &L); if (rc) return rc;
@@ -1832,6 +1860,8 @@ extern "C" int sfm_ba_schur_build(sfm_handle h, sfm_ba_problem p, double alpha) 
   double* ws = (double*)p->workspace;
   const int C = p->n_cams, P = p->n_pts, D = p->cam_dim, n = C * D;
   const int64_t N = p->n_obs;
+  const BaSwitches sw = ba_switches_from_env();
+  const CamPlan plan = cam_plan(n, p->camera_solver, h->cgs_persist_off != 0, sw);
   sfm_prof_begin(h, SFM_PROF_BUILD_G);
   DISPATCH_DT(D, p->precision, {
     hipLaunchKernelGGL((k_build_G<DD, TT, double, GG>), dim3(cdiv(N, 256) + cdiv(P, 256)), dim3(256), 0, h->stream, N, p->pt_idx, WST(L, recA),
@@ -1850,45 +1880,21 @@ extern "C" int sfm_ba_schur_build(sfm_handle h, sfm_ba_problem p, double alpha) 
     if (p->has_dup && p->n_cchunks > 0)        // the chunk partials of sum_k G_k e_j by the camera-wise pass over G
       hipLaunchKernelGGL((k_cam_reduce_chunks<DD, double, GG>), dim3((unsigned)p->n_cchunks), dim3(256), 0, h->stream, p->cch_beg,
                          p->cch_end, p->cam_obs, p->cam_pt, WS(L, G), WS(L, e), WS(L, cch_part));
-    // the diagonal blocks' factors for the camera CG come out of this kernel too (unsharded problems whose camera system may go to
-    // the CG: a rank's S is a partial sum until the exchange)
-    const bool fuse_einv = !p->sharded && p->camera_solver != SFM_CAMERA_SOLVER_CHOLESKY && (n & 1) == 0;
-    // ... and on the tile-streaming route the scaled system itself (S is then formed on demand only: schur_materialise_S)
-    const char* fse = getenv("SFM_SCHUR_FUSE_SCALE");      // "0": S first, then k_scale_system_lower (looked at per build: a test switches it)
-    const bool fuse_scale_on = !(fse && fse[0] == '0');
-    const bool fuse_scale = fuse_scale_on && fuse_einv && cgs_use_big(n) && !cgs_persist_usable(h, n);
-    p->st_alpha = -1.0;
-    p->s_valid = fuse_scale ? 0 : 1;
-    if (fuse_scale) {
-      DenseWs dw; dense_ws_carve(WS(L, dense), n, &dw);
-      hipLaunchKernelGGL(k_schur_diag<DD>, dim3(C), dim3(128), 0, h->stream, C, p->item_ptr, WS(L, sch_part), WS(L, B), alpha,
-                         WS(L, cg_Minv), WS(L, cg_M), WS(L, cg_scal));
-      // (blocks per workgroup at >= 128 cameras, us per launch at 1000: 2: 397, 4: 277-285, 8: 299)
-      if (C >= 128)
-        hipLaunchKernelGGL((k_schur_assemble_scaled<DD, 4>), dim3(C, cdiv(C, 4)), dim3(128), 0, h->stream, C, p->item_ptr,
-                           WS(L, sch_part), WS(L, B), dw.Lm, p->cch_ptr, WS(L, cch_part), WS(L, gc), WS(L, red_S) + (size_t)n * n,
-                           WS(L, cg_r), alpha, WS(L, cg_Minv));
-      else
-        hipLaunchKernelGGL((k_schur_assemble_scaled<DD, 2>), dim3(C, cdiv(C, 2)), dim3(128), 0, h->stream, C, p->item_ptr,
-                           WS(L, sch_part), WS(L, B), dw.Lm, p->cch_ptr, WS(L, cch_part), WS(L, gc), WS(L, red_S) + (size_t)n * n,
-                           WS(L, cg_r), alpha, WS(L, cg_Minv));
-      p->st_alpha = alpha;
-    } else if (C >= ASM_ROUNDS_FROM)
-      hipLaunchKernelGGL((k_schur_assemble<DD, 8, true>), dim3(C, cdiv(C, 8)), dim3(128), 0, h->stream, C, p->item_ptr,
-                         WS(L, sch_part), WS(L, B), WS(L, red_S), WS(L, cg_scal), p->cch_ptr, WS(L, cch_part), WS(L, gc),
-                         WS(L, red_S) + (size_t)n * n, alpha, fuse_einv ? WS(L, cg_Minv) : (double*)nullptr, WS(L, cg_M));
-    else if (C >= 128)
-      hipLaunchKernelGGL((k_schur_assemble<DD, 8, false>), dim3(C, cdiv(C, 8)), dim3(128), 0, h->stream, C, p->item_ptr,
-                         WS(L, sch_part), WS(L, B), WS(L, red_S), WS(L, cg_scal), p->cch_ptr, WS(L, cch_part), WS(L, gc),
-                         WS(L, red_S) + (size_t)n * n, alpha, fuse_einv ? WS(L, cg_Minv) : (double*)nullptr, WS(L, cg_M));
-    else
-      hipLaunchKernelGGL((k_schur_assemble<DD, 2, false>), dim3(C, cdiv(C, 2)), dim3(128), 0, h->stream, C, p->item_ptr,
-                         WS(L, sch_part), WS(L, B), WS(L, red_S), WS(L, cg_scal), p->cch_ptr, WS(L, cch_part), WS(L, gc),
-                         WS(L, red_S) + (size_t)n * n, alpha, fuse_einv ? WS(L, cg_Minv) : (double*)nullptr, WS(L, cg_M));
-    p->cg_scal_clean = 1;
-    p->einv_alpha = fuse_einv ? alpha : -1.0;
-    sfm_prof_end(h, SFM_PROF_SCHUR);
   });
+  // what the solve of this system will consume decides what is left for it: S (with the diagonal blocks' factors), or S~ alone
+  // (S is then formed on demand only: schur_materialise_S)
+  const BuildFusion fuse = build_fusion(plan, p->sharded != 0, p->camera_solver, n, sw);
+  p->st_alpha = -1.0;
+  p->s_valid = fuse.scale ? 0 : 1;
+  if (fuse.scale) {
+    DenseWs dw; dense_ws_carve(WS(L, dense), n, &dw);
+    launch_schur_assemble_scaled(h, p, L, alpha, dw.Lm);
+    p->st_alpha = alpha;
+  } else
+    launch_schur_assemble(h, p, L, alpha, fuse.einv ? WS(L, cg_Minv) : (double*)nullptr, WS(L, cg_M));
+  p->cg_scal_clean = 1;
+  p->einv_alpha = fuse.einv ? alpha : -1.0;
+  sfm_prof_end(h, SFM_PROF_SCHUR);
   SFM_LAUNCH_CHECK(h, "sfm_ba_schur_build");
   return SFM_OK;
 }
@@ -1897,22 +1903,7 @@ extern "C" int sfm_ba_schur_build(sfm_handle h, sfm_ba_problem p, double alpha) 
 // that formed S~ only: the factorisation (a system the CG is not given, or did not finish) and sfm_ba_pack_system.
 static int schur_materialise_S(sfm_ctx* h, sfm_ba_problem p, const Lay& L) {
   if (p->s_valid) return SFM_OK;
-  double* ws = (double*)p->workspace;
-  const int C = p->n_cams, D = p->cam_dim, n = C * D;
-  DISPATCH_D(D, {
-    if (C >= ASM_ROUNDS_FROM)
-      hipLaunchKernelGGL((k_schur_assemble<DD, 8, true>), dim3(C, cdiv(C, 8)), dim3(128), 0, h->stream, C, p->item_ptr,
-                         WS(L, sch_part), WS(L, B), WS(L, red_S), WS(L, cg_scal), p->cch_ptr, WS(L, cch_part), WS(L, gc),
-                         WS(L, red_S) + (size_t)n * n, 0.0, (double*)nullptr, (double*)nullptr);
-    else if (C >= 128)
-      hipLaunchKernelGGL((k_schur_assemble<DD, 8, false>), dim3(C, cdiv(C, 8)), dim3(128), 0, h->stream, C, p->item_ptr,
-                         WS(L, sch_part), WS(L, B), WS(L, red_S), WS(L, cg_scal), p->cch_ptr, WS(L, cch_part), WS(L, gc),
-                         WS(L, red_S) + (size_t)n * n, 0.0, (double*)nullptr, (double*)nullptr);
-    else
-      hipLaunchKernelGGL((k_schur_assemble<DD, 2, false>), dim3(C, cdiv(C, 2)), dim3(128), 0, h->stream, C, p->item_ptr,
-                         WS(L, sch_part), WS(L, B), WS(L, red_S), WS(L, cg_scal), p->cch_ptr, WS(L, cch_part), WS(L, gc),
-                         WS(L, red_S) + (size_t)n * n, 0.0, (double*)nullptr, (double*)nullptr);
-  });
+  launch_schur_assemble(h, p, L, 0.0, nullptr, nullptr);
   p->s_valid = 1;
   SFM_LAUNCH_CHECK(h, "schur_materialise_S");
   return SFM_OK;
@@ -1999,11 +1990,7 @@ __global__ void k_finish_solve_pcg(int n, const double* __restrict__ pc, const d
 // workgroups so that one XCD owns a contiguous eighth of S~ (4 MB at n = 2000: stays in its L2 across iterations).
 // The host reads ||r||^2 every few launches.  If CG has not converged after CGS_MAX_ITER iterations, or meets a
 // direction of non-positive curvature, the caller falls back to the Cholesky route: S itself is left untouched.
-constexpr int CGS_MAX_N = 4096;          // the direction vector lives in LDS (32 KB); larger systems use the factorisation
-constexpr int CGS_MAX_ITER = 160;
-constexpr int CGS_BIG_MAX_ITER = 400;   // the tile-streaming route for n > CGS_MAX_N (cgs_solve_big)
-// (SFM_CGS_BIG_BUDGET: a TEST knob, looked at per solve - a budget of a few iterations makes a system fall back to the factorisation)
-static int cgs_big_budget() { const char* e = getenv("SFM_CGS_BIG_BUDGET"); const int v = e ? atoi(e) : 0; return v > 0 ? v : CGS_BIG_MAX_ITER; }
+// (CGS_MAX_N, CGS_MAX_ITER and the budget of the tile-streaming route: ba_plan.h)
 // ||r|| <= CGS_RTOL ||r_0|| on the scaled system.  SFM_CGS_RTOL overrides it - a DIAGNOSTIC knob (tools/exp_cg_fixed_cost.py
 // sets 1.0: zero iterations, what remains is the fixed cost of a system), never set by the product
 static double cgs_rtol() { static const double v = getenv("SFM_CGS_RTOL") ? atof(getenv("SFM_CGS_RTOL")) : 1e-13; return v; }
@@ -2305,7 +2292,6 @@ extern "C" int sfm_debug_cgs_stamps(unsigned long long* dst, int n_words, unsign
 #define CGS_STAMP(tag) do {} while (0)
 #endif
 constexpr int PR_ROWS = 8;
-constexpr int PR_MAX_N = 2048;                    // 8 rows x 2048 columns per workgroup in registers; grid = n / 8 <= 256
 constexpr unsigned PR_SPIN_LIMIT = 1u << 17;      // passes over a thread's granules (~1 us each) before giving up
 typedef unsigned long long pr_u64;
 #define PR_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
@@ -2588,14 +2574,10 @@ __global__ __launch_bounds__(256, 1) void k_cgs_persist(int n, double rtol2, int
 
 // One persistent launch for a system (k_cgs_persist), in two halves so that the host never idles the GPU on its status:
 // cgs_persist_launch enqueues the kernel and the copy of its 8 status words into pinned memory (slot pin: SFM_PIN_CG1 /
-// the problem's own slot for the second system) and returns false when the kernel is not usable here (n, handle state, SFM_CGS_PERSIST=0);
+// the problem's own slot for the second system) (which systems take it: cam_plan);
 // cgs_persist_status interprets the copy once the caller knows it has arrived (an event behind it, or a later stream
 // synchronisation).  *ran = 0: the launch was abandoned - the caller takes the launch-per-iteration route (cgs_solve) with its
 // separate pre / post kernels; *status = 0: converged (and whatever `fuse` asked for has been done by workgroup 0).
-static bool cgs_persist_usable(sfm_ctx* h, int n) {
-  const char* e = getenv("SFM_CGS_PERSIST");       // looked at per solve (a test switches it): "0" = one launch per iteration
-  return n <= PR_MAX_N && (n & 1) == 0 && !h->cgs_persist_off && !(e && e[0] == '0');
-}
 // The salt of a launch's granule tags comes from ONE process-wide counter (24 bits, never 0 = what cleared memory reads as),
 // started from the clock: a handle that is destroyed and created again, or two handles sharing a workspace over time, can never
 // replay a salt whose granules still sit in a mailbox (a per-handle counter restarting at 1 could: the reader would then take
@@ -2920,25 +2902,11 @@ __global__ __launch_bounds__(128) void k_cgb_reduce(int n, int nb, int nbp, int 
   if (threadIdx.x == 0) { dots[blockIdx.x] = s_w[0][0] + s_w[0][1]; dots[nbp + blockIdx.x] = s_w[1][0] + s_w[1][1]; }
 }
 
-// Which launch-per-iteration CG a system of n unknowns takes when the persistent kernel does not apply: the tile-streaming
-// one (cgs_solve_big) from SFM_CGS_BIG_FROM unknowns on, k_cgs_iter below.  Default: everything beyond the persistent kernel's
-// 2,048 - measured at n = 3,000 / 4,000: camera-solve slots 392 + 356 -> 329 + 290 us and 583 + 520 -> 422 + 348 us per damped
-// solve against k_cgs_iter<8, 4> (half the bytes per iteration outweigh two more launches).  SFM_CGS_BIG=0 switches the
-// tile-streaming route off: systems beyond CGS_MAX_N then take the factorisation, as before round 3.  Looked at per solve (a
-// test switches it).
-static bool cgs_use_big(int n) {
-  const char* e = getenv("SFM_CGS_BIG");
-  if (e && e[0] == '0') return false;
-  const char* f = getenv("SFM_CGS_BIG_FROM");
-  const int from = f ? (atoi(f) > 256 ? atoi(f) : 257) : PR_MAX_N + 1;
-  return n >= from;
-}
-static bool cgs_possible(int n) { return (n & 1) == 0 && (n <= CGS_MAX_N || cgs_use_big(n)); }
 // its_hint: iterations the last converged system of this problem took (0: unknown) - the first batch of launches is sized for it
 // (a batch is enqueued blind and the host looks at the residual behind it; launches past convergence return at once but still
 // cost ~3 us each: at 14 iterations per system, 30 of the fixed first batch of 72 launches were such)
 static int cgs_solve_big(sfm_ctx* h, int n, const double* St, const double* rhs_t, double* x_t, double* buf, double* scal,
-                         double rtol, int* iters_out, int* status, int its_hint = 0) {
+                         double rtol, int budget, int* iters_out, int* status, int its_hint) {
   const double rtol2 = rtol * rtol;
   *status = 1;
   const int nb = (int)cdiv(n, SY_T), nbp = (nb + 127) & ~127;
@@ -2954,7 +2922,6 @@ static int cgs_solve_big(sfm_ctx* h, int n, const double* St, const double* rhs_
   // to its own slot.
   int it = 0;
   int batch = its_hint > 0 ? (its_hint + 4 > 48 ? 48 : its_hint + 4) : 24;
-  const int budget = cgs_big_budget();
   // The verdict comes through the pinned page (k_cgb_symv): the host spins on this system's ticket and, every SPIN_QUERY spins,
   // asks whether the stream has drained (a batch that ended without a verdict).  No status copy, no stream synchronisation
   // on the way of a system that converges within its batch - and the caller's next launches queue up behind the blind launches
@@ -3001,6 +2968,27 @@ static int cgs_solve_big(sfm_ctx* h, int n, const double* St, const double* rhs_
   return SFM_OK;
 }
 
+// S~ x~ = r~ (r~ in cg_r, x~ into cg_z) by the plan's launch-per-iteration CG
+static int cgs_solve_per_launch(sfm_ctx* h, sfm_ba_problem p, const Lay& L, const DenseWs& dw, const CamPlan& plan, int* status, int its_hint) {
+  double* ws = (double*)p->workspace;
+  const int n = p->n_cams * p->cam_dim;
+  if (plan.per_launch == CAM_CG_TILES)
+    return cgs_solve_big(h, n, dw.Lm, WS(L, cg_r), WS(L, cg_z), dw.LmT, WS(L, cg_scal), CGS_RTOL, plan.budget, &p->cg_iters, status, its_hint);
+  return cgs_solve(h, n, dw.Lm, WS(L, cg_r), WS(L, cg_z), dw.LmT, WS(L, cg_scal), CGS_RTOL, &p->cg_iters, status);
+}
+
+// S + alpha I = L L^T into the factor's buffer, where S~ was (S is formed from the item tiles first if the build left S~ only);
+// row n of [S | r]: r -> L^-1 r
+static int factor_system(sfm_ctx* h, sfm_ba_problem p, const Lay& L, const DenseWs& dw, double alpha) {
+  double* ws = (double*)p->workspace;
+  const int n = p->n_cams * p->cam_dim;
+  int rc = schur_materialise_S(h, p, L); if (rc) return rc;
+  p->st_alpha = -1.0;
+  SFM_HIP(h, hipMemsetAsync(dw.flag, 0, sizeof(int), h->stream));       // the factorisation's failure flag (k_finish_solve reads it)
+  hipLaunchKernelGGL(k_add_diag, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, WS(L, red_S), n, alpha);
+  return dense_cholesky(h, WS(L, red_S), n, n + 1, dw);
+}
+
 // point back-substitution for the p_c in the workspace, and (want_q) the pieces of rhs2 = p_c - W C_a^-1 p_p
 static void launch_backsub(sfm_ctx* h, sfm_ba_problem p, const Lay& L, double* ws, int want_q) {
   const int C = p->n_cams, P = p->n_pts, D = p->cam_dim, n = C * D;
@@ -3042,38 +3030,14 @@ extern "C" int sfm_ba_schur_solve(sfm_handle h, sfm_ba_problem p, double alpha, 
   p->cg_state = 0;
   p->cg2_pending = 0;
   p->cg_alpha = alpha;
-  // AUTO only: a system the CG cannot finish within its budget costs the budget (160 iterations = 0.77 ms at n = 2000) AND the
-  // factorisation (0.9 ms).  SciPy's More' iteration resets alpha to 0.001 alpha_upper whenever the carried-over value falls
-  // outside its bracket (common.py:117-118) - on the spatially coherent scene that is one hopeless system every third outer
-  // iteration, seven in the first.  Whether a system is hopeless is predicted from this problem's own history; the prediction
-  // depends on replicated quantities only (alpha, max diag H, iteration counts), so every rank of a sharded solve decides alike.
+  const BaSwitches sw = ba_switches_from_env();
+  const CamPlan plan = cam_plan(n, p->camera_solver, h->cgs_persist_off != 0, sw);
+  // AUTO only: a system predicted to exhaust the CG's budget goes to the factorisation at once (CgPredictor)
   const double hdiag = p->host_sc[SFM_SC_HDIAG];
   const double arel = hdiag > 0.0 ? alpha / hdiag : 0.0;
-  const int cg_budget = cgs_use_big(n) ? cgs_big_budget() : CGS_MAX_ITER;
-  bool hopeless = false;
-  if (p->camera_solver == SFM_CAMERA_SOLVER_AUTO && arel > 0.0 && !(getenv("SFM_CGS_PREDICT") && getenv("SFM_CGS_PREDICT")[0] == '0')) {
-    if (p->cgp_fail_rel > 0.0 && arel <= 4.0 * p->cgp_fail_rel) hopeless = true;
-    else if (p->cgp_ok_its[0] > 0 && arel < p->cgp_ok_rel[0]) {
-      double slope = 0.2;                            // one record only: the flatter of the two measured exponents
-      if (p->cgp_ok_its[1] > 0) {
-        slope = -std::log((double)p->cgp_ok_its[0] / p->cgp_ok_its[1]) / std::log(p->cgp_ok_rel[0] / p->cgp_ok_rel[1]);
-        slope = slope < 0.0 ? 0.0 : (slope > 0.5 ? 0.5 : slope);
-      }
-      if (p->cgp_ok_its[0] * std::pow(p->cgp_ok_rel[0] / arel, 0.85 * slope) > 1.25 * cg_budget) hopeless = true;
-    }
-  }
-  // a converged step system joins the record: [0] the latest, [1] the one before it at an alpha at least 1.5 x away
-  auto cgp_note_ok = [&](int its) {
-    if (its <= 0) return;
-    if (p->cgp_ok_its[0] > 0) {
-      const double r = arel / p->cgp_ok_rel[0];
-      if (r >= 1.5 || r <= 1.0 / 1.5) { p->cgp_ok_rel[1] = p->cgp_ok_rel[0]; p->cgp_ok_its[1] = p->cgp_ok_its[0]; }
-    }
-    p->cgp_ok_rel[0] = arel; p->cgp_ok_its[0] = its;
-    if (arel <= p->cgp_fail_rel) p->cgp_fail_rel = 0.5 * arel;      // it does converge here after all
-  };
+  const bool hopeless = p->camera_solver == SFM_CAMERA_SOLVER_AUTO && arel > 0.0 && sw.predict && p->cgp.hopeless(arel, plan.budget);
   if (hopeless) p->cg_fallbacks++;
-  if (p->camera_solver != SFM_CAMERA_SOLVER_CHOLESKY && cgs_possible(n) && !hopeless) {
+  if (plan.route != CAM_FACTOR && !hopeless) {
     const int its_before = p->cg_iters;
     // S~ = E^-1 (S + alpha I) E^-T into the factor's buffer (S stays as it is: the fallback below needs it), r~ = E^-1 r
     sfm_prof_begin(h, SFM_PROF_CHOL);
@@ -3083,12 +3047,12 @@ extern "C" int sfm_ba_schur_solve(sfm_handle h, sfm_ba_problem p, double alpha, 
     const bool have_einv = p->einv_alpha == alpha && !p->sharded;      // k_schur_assemble of THIS system left them
     p->einv_alpha = -1.0;
     // ... or the scaled system itself (tile-streaming route: k_schur_assemble_scaled)
-    const bool have_st = have_einv && p->st_alpha == alpha && cgs_use_big(n) && !cgs_persist_usable(h, n);
+    const bool have_st = have_einv && p->st_alpha == alpha && plan.lower_only;
     if (!have_st && (rc = schur_materialise_S(h, p, L))) return rc;
     if (!have_st) DISPATCH_D(D, {
       if (!have_einv)
         hipLaunchKernelGGL(k_diag_einv<DD>, dim3(cdiv(C, 64)), dim3(64), 0, h->stream, C, S, n, alpha, WS(L, cg_Minv), WS(L, cg_M), WS(L, cg_scal));
-      if (cgs_use_big(n) && !cgs_persist_usable(h, n))   // the tile-streaming CG reads the lower triangle (+ the diagonal tiles) only
+      if (plan.lower_only)
         hipLaunchKernelGGL(k_scale_system_lower<DD>, dim3(C, cdiv(C, SCALE_NB)), dim3(128), 0, h->stream, n, C, S, alpha, WS(L, cg_Minv), dw.Lm,
                            S + (size_t)n * n, WS(L, cg_r));
       else
@@ -3096,7 +3060,7 @@ extern "C" int sfm_ba_schur_solve(sfm_handle h, sfm_ba_problem p, double alpha, 
                            S + (size_t)n * n, WS(L, cg_r));
     });
     int status = 1, ran = 0;
-    if (cgs_persist_usable(h, n)) {
+    if (plan.route == CAM_CG_PERSIST) {
       // ONE persistent launch: r~ = E^-1 r in its prologue, p_c = -E^-T x~ in its epilogue.  The host needs its verdict
       // (converged / fall back) but must not idle the GPU for it: the status words are copied to pinned memory, an event is
       // recorded behind the copy, the back-substitution is enqueued on the assumption that the solve converged (it does: 0
@@ -3115,16 +3079,15 @@ extern "C" int sfm_ba_schur_solve(sfm_handle h, sfm_ba_problem p, double alpha, 
       if (relaunched && ran && status == 0) launch_backsub(h, p, L, ws, want_q);      // the first one ran on an unfinished p_c
       if (ran && status == 0) {
         p->cg_state = 1;
-        cgp_note_ok(p->cg_iters - its_before);
+        p->cgp.note_ok(arel, p->cg_iters - its_before);
         SFM_LAUNCH_CHECK(h, "sfm_ba_schur_solve");
         return SFM_OK;
       }
       sfm_prof_begin(h, SFM_PROF_CHOL);             // not converged or abandoned: the routes below, then the back-substitution again
     }
-    if (!ran) {                                       // launch per iteration, with the scaling of r and of the solution as kernels of their own
+    if (!ran) {                                       // plan.per_launch: one launch (pair) per iteration, with the scaling of r and of the solution as kernels of their own
       DISPATCH_D(D, hipLaunchKernelGGL(k_block_mv<DD>, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, C, WS(L, cg_Minv), S + (size_t)n * n, WS(L, cg_r), 0, 1.0));
-      if (cgs_use_big(n)) rc = cgs_solve_big(h, n, dw.Lm, WS(L, cg_r), WS(L, cg_z), dw.LmT, WS(L, cg_scal), CGS_RTOL, &p->cg_iters, &status, p->cgp_ok_its[0]);
-      else rc = cgs_solve(h, n, dw.Lm, WS(L, cg_r), WS(L, cg_z), dw.LmT, WS(L, cg_scal), CGS_RTOL, &p->cg_iters, &status);
+      rc = cgs_solve_per_launch(h, p, L, dw, plan, &status, p->cgp.ok_its[0]);
       if (rc) return rc;
       p->cg_its_sys1 = p->cg_iters - its_before;
       if (status == 0)
@@ -3133,20 +3096,16 @@ extern "C" int sfm_ba_schur_solve(sfm_handle h, sfm_ba_problem p, double alpha, 
     }
     if (status == 0) {
       p->cg_state = 1;
-      cgp_note_ok(p->cg_iters - its_before);
+      p->cgp.note_ok(arel, p->cg_iters - its_before);
     } else {
       p->cg_fallbacks++;
-      if (p->cg_iters - its_before >= cg_budget && arel > p->cgp_fail_rel) p->cgp_fail_rel = arel;      // out of iterations (not: broken)
+      p->cgp.note_out_of_budget(arel, p->cg_iters - its_before, plan.budget);
     }
     sfm_prof_end(h, SFM_PROF_CHOL);
   }
   if (p->cg_state == 0) {
     sfm_prof_begin(h, SFM_PROF_CHOL);
-    if ((rc = schur_materialise_S(h, p, L))) return rc;
-    p->st_alpha = -1.0;                                // the factor goes where S~ was
-    SFM_HIP(h, hipMemsetAsync(dw.flag, 0, sizeof(int), h->stream));       // the factorisation's failure flag (k_finish_solve reads it)
-    hipLaunchKernelGGL(k_add_diag, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, S, n, alpha);
-    rc = dense_cholesky(h, S, n, n + 1, dw); if (rc) return rc;   // row n: r -> L^-1 r
+    rc = factor_system(h, p, L, dw, alpha); if (rc) return rc;
     sfm_prof_end(h, SFM_PROF_CHOL);
     sfm_prof_begin(h, SFM_PROF_TRSV);
     // p_c = -L^-T (L^-1 r)
@@ -3167,11 +3126,7 @@ static int finish_solve_by_factor(sfm_ctx* h, sfm_ba_problem p, const Lay& L, do
   if (factor_first) {
     p->cg_fallbacks++;
     p->cg_state = 0;
-    if ((rc = schur_materialise_S(h, p, L))) return rc;
-    p->st_alpha = -1.0;
-    SFM_HIP(h, hipMemsetAsync(dw.flag, 0, sizeof(int), h->stream));
-    hipLaunchKernelGGL(k_add_diag, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, WS(L, red_S), n, p->cg_alpha);
-    rc = dense_cholesky(h, WS(L, red_S), n, n + 1, dw); if (rc) return rc;
+    rc = factor_system(h, p, L, dw, p->cg_alpha); if (rc) return rc;
   }
   if (want_q) {
     // rhs2 = p_c - W C_a^-1 p_p ;  y = L^-1 rhs2
@@ -3191,6 +3146,7 @@ extern "C" int sfm_ba_finish_solve(sfm_handle h, sfm_ba_problem p, int want_q) {
   double* ws = (double*)p->workspace;
   const int n = p->n_cams * p->cam_dim;
   DenseWs dw; dense_ws_carve(WS(L, dense), n, &dw);
+  const CamPlan plan = cam_plan(n, p->camera_solver, h->cgs_persist_off != 0, ba_switches_from_env());
   if (p->cg_state == 1) {
     // the camera system was solved by CG on the scaled system S~ (still in dw.Lm): p^T (H + alpha I)^-1 p needs
     // rhs2^T S^-1 rhs2 = r~2^T x~2 with r~2 = E^-1 rhs2, S~ x~2 = r~2
@@ -3198,7 +3154,7 @@ extern "C" int sfm_ba_finish_solve(sfm_handle h, sfm_ba_problem p, int want_q) {
     int status = 0;
     if (want_q) {
       sfm_prof_begin(h, SFM_PROF_TRSV);
-      if (cgs_persist_usable(h, n)) {
+      if (plan.route == CAM_CG_PERSIST) {
         // ONE persistent launch: r~2 = E^-1 (p_c + rhs2 pieces) in its prologue, r~2 . x~2 and the scalars of the solve in its
         // epilogue.  Its verdict travels to pinned memory with the copy enqueued behind it and is looked at where the host
         // synchronises anyway: in sfm_ba_read_scalars, which redoes this step from the factorisation if it has to.
@@ -3217,8 +3173,7 @@ extern "C" int sfm_ba_finish_solve(sfm_handle h, sfm_ba_problem p, int want_q) {
       DISPATCH_D(D, hipLaunchKernelGGL(k_block_mv<DD>, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, C, WS(L, cg_Minv), WS(L, tvec),
                                        WS(L, cg_r), 0, 1.0));
       // (the q system of a damped solve takes about as many iterations as its step system just did)
-      if (cgs_use_big(n)) rc = cgs_solve_big(h, n, dw.Lm, WS(L, cg_r), WS(L, cg_z), dw.LmT, WS(L, cg_scal), CGS_RTOL, &p->cg_iters, &status, p->cg_its_sys1);
-      else rc = cgs_solve(h, n, dw.Lm, WS(L, cg_r), WS(L, cg_z), dw.LmT, WS(L, cg_scal), CGS_RTOL, &p->cg_iters, &status);
+      rc = cgs_solve_per_launch(h, p, L, dw, plan, &status, p->cg_its_sys1);
       if (rc) return rc;
       if (status == 0)
         hipLaunchKernelGGL(k_dot, dim3(1), dim3(1024), 0, h->stream, n, WS(L, cg_r), WS(L, cg_z), WS(L, cg_scal) + 8);

@@ -1,6 +1,7 @@
 // Internal representation of a bundle-adjustment problem (include/sfm_amd.h: sfm_ba_problem is a pointer to this).
 #pragma once
 #include "dense.h"
+#include "ba_plan.h"
 
 struct Lay {   // workspace offsets in doubles (regions holding float32 in mixed precision are sized in doubles too)
   int64_t recA, recB, campre, campre2, B, gc, Cp, gp, Linv, e, v, tmp3, G, eobs, red_lin, gmax, red_S, red_q,
@@ -64,14 +65,7 @@ struct sfm_ba_prob {
   int64_t pcg_fallbacks;
   double pcg_worst_relres;
   double cg_alpha;
-  // Camera CG, SFM_CAMERA_SOLVER_AUTO: what this problem has taught about where the iteration budget runs out (alpha relative
-  // to max diag H): the largest alpha at which CG ran out of iterations (forgotten by 20 % per linearisation), and the last two
-  // converged step systems at different alpha, whose iteration counts give the local exponent of iterations ~ alpha^-s
-  // (measured: s ~ 0.4 on the spatially coherent scene, ~ 0.2 on the random one, falling towards alpha -> 0).  A damped solve at
-  // or below 4 x the failure bound, or for which that power law - with 0.85 s - predicts more than 1.25 x the budget, goes to
-  // the factorisation at once instead of burning the whole budget first (sfm_ba_schur_solve).
-  double cgp_fail_rel, cgp_ok_rel[2];
-  int cgp_ok_its[2];
+  CgPredictor cgp;           // SFM_CAMERA_SOLVER_AUTO: which damped solves skip the camera CG (ba_plan.h)
   int cg_its_sys1;           // iterations of the step system of the current damped solve (launch-per-iteration routes)
 };
 

@@ -362,6 +362,27 @@ def test_matcher_plan_under_address_and_ub_sanitizers(tmp_path):
         assert run.returncode == 0 and run.stdout.startswith("ok "), (run.stdout, run.stderr[-2000:])
 
 
+def test_ba_plan_under_address_and_ub_sanitizers(tmp_path):
+    """sfm_amd/csrc/ba_plan.h (which route forms and solves the camera system of a damped solve, what the build may fuse
+    for it, the assembler shapes, the prediction of systems the CG cannot finish) is plain C++: built here with
+    g++ -fsanitize=address,undefined and driven over the route table - every size threshold from both sides, the switches set
+    through the environment by the program itself - and over predictor histories whose verdicts were computed by hand."""
+    import shutil, subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = tmp_path / "ba_plan_check"
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-fno-omit-frame-pointer", "-I" + os.path.join(root, "sfm_amd", "csrc"),
+           os.path.join(root, "tests", "native", "ba_plan_check.cpp"), "-o", str(exe)]
+    build = subprocess.run(cmd, capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True,
+                         env={k: v for k, v in os.environ.items()
+                              if not k.startswith("SFM_CGS_") and k != "SFM_SCHUR_FUSE_SCALE"})
+    assert run.returncode == 0 and run.stdout.startswith("ok "), (run.stdout, run.stderr[-2000:])
+
+
 class _DenseFitBackend:
     """The problem of tests/native/trf_loop_check.cpp in NumPy, behind the backend protocol of sfm_amd/trf.py."""
 

@@ -226,7 +226,9 @@ typedef struct {
   int64_t reduce_Sp_off, reduce_Sp_count;       /* doubles: lower triangle of S by rows, then r: n(n+1)/2 + n - what
                                                    sfm_ba_pack_system fills and sfm_ba_unpack_system reads (the factorisation
                                                    only reads the lower triangle, so ranks exchange half the bytes) SUM */
-  int64_t reduce_q_off, reduce_q_count;         /* doubles: [rhs2 (n) | ||p_pts||^2 | p_pts^T C_a^-1 p_pts]  SUM */
+  int64_t reduce_q_off, reduce_q_count;         /* doubles: [q_c (n) | ||p_pts||^2 | p_pts^T C_a^-1 p_pts]   SUM
+                                                   q_c = -W C_a^-1 p_pts, the point part of rhs2 = p_c + q_c (sfm_ba_finish_solve adds p_c);
+                                                   q_c is written only when want_q, the two sums always */
   int64_t reduce_step_off, reduce_step_count;   /* doubles: [||J~ s||^2 | f~^T J~ s | cost(x+s) | ||s_pts||^2 | ||x_pts+s_pts||^2 ] SUM */
   int64_t pc_off, pp_off;           /* camera / point part of p = -(H + alpha I)^-1 g */
   int64_t scalars_off;              /* 16 doubles, see SFM_SC_* */

@@ -3,7 +3,9 @@
 counts that are not multiples of 8, cameras with very few or very many observations), RAGGED tracks (2 .. 14 cameras per
 point, different for every point), both camera blocks (d = 6, 10), float64 and mixed storage, both camera solvers.
 Per case: linearisation scalars, one damped solve (step vector, ||p||, p^T (H + aI)^-1 p) at two dampings, one trial step.
-Prints one line per case; exits 1 on a mismatch."""
+Prints one line per case; exits 1 on a mismatch.  Everything here is judged through the final step p, whose forward error is
+limited by cond(H + aI); the stages of the damped solve one by one (G, S, r, p_c, p_p, the q pieces) are held to their own
+bounds against an 80-bit reference by tests/test_ba_stages_gpu.py (tests/stage_reference.py)."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -56,7 +56,8 @@ enum { SFM_PROF_LIN_OBS = 0,   /* k_lin_obs: residual + Jacobian + Huber scaling
        SFM_PROF_STEP = 7,      /* trial step: x + s, predicted reduction sums, cost(x + s) */
        SFM_PROF_KNN = 8,       /* matcher distance + top-2 kernel */
        SFM_PROF_SCHUR_ITEMS = 9, /* k_schur_items alone (inside SFM_PROF_SCHUR) */
-       SFM_PROF_COUNT = 10 };
+       SFM_PROF_FUND_HYP = 10, /* k_fund_hypotheses alone (inside sfm_fund_ransac) */
+       SFM_PROF_COUNT = 11 };
 int sfm_set_profiling(sfm_handle h, int enabled);
 int sfm_profile_read(sfm_handle h, int slot, double* total_ms_host, int64_t* count_host);
 
@@ -399,6 +400,32 @@ int sfm_triangulate2(sfm_handle h, const double* proj, int32_t n_cams, const int
 int sfm_epipolar_errors(sfm_handle h, const double* F, const int64_t* seg_ptr, int32_t n_seg,
                         const float* pts1, const float* pts2, int64_t n, float threshold,
                         float* err, uint8_t* mask);
+
+/* ------------------------------------------------------------------ fundamental-matrix RANSAC, batched over pairs
+ * The step between match_features and geometric_verification in the reference's pair loop
+ * (cv2.findFundamentalMat with cv2.FM_RANSAC, /root/reference/utils/find_matches.py:282), for every pair of a
+ * driver step in one call.  Structure as OpenCV's FM_RANSAC is recalled (not pinned): samples of 7, the 7-point
+ * solver (up to three real solutions), error = the larger of the two squared point-to-epipolar-line distances,
+ * inlier when error <= threshold^2, best model = most inliers (ties: lowest hypothesis index), F scaled to
+ * F[2][2] = 1.  Deviations: every one of the n_hyp hypotheses runs (no early exit on confidence), and the samples
+ * are data: drawn by a stateless integer hash of (seed, segment, hypothesis, draw) written out in
+ * sfm_amd/csrc/twoview.hip, or supplied by the caller.  The result is a function of (points, samples) alone.
+ * All arithmetic float64.  seg_ptr [n_seg+1] device int64; pts1 / pts2 [n][2] float32 pixels.  A match with a NaN
+ * or infinite coordinate is never an inlier; a sample index outside its segment voids that hypothesis.
+ *
+ * samples [n_seg][n_hyp][7] int32, segment-local indices, 7 distinct per hypothesis (-1 for segments with fewer
+ * than 7 points).  status [n_seg]: 0 ok, 1 fewer than 7 points, 2 no sample gave a model; status 1 / 2 segments get
+ * F = 0, an all-zero mask and count 0.  hyp_count [n_seg][n_hyp] (may be NULL): per hypothesis the best inlier count
+ * of its candidates.  refine != 0: normalised 8-point least squares over the winner's inliers, rank 2 enforced,
+ * re-scored with the same error; it replaces the winner only if its count is not lower (refined[s] = 1 then;
+ * refined may be NULL).  Everything runs on the handle's stream without host synchronisation. */
+int sfm_fund_workspace_bytes(int64_t n_points, int32_t n_seg, int32_t n_hyp, int64_t* bytes_host);
+int sfm_fund_draw_samples(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, int32_t n_hyp, uint64_t seed,
+                          int32_t* samples);
+int sfm_fund_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, const float* pts1, const float* pts2,
+                    int64_t n, const int32_t* samples, int32_t n_hyp, double threshold, int32_t refine,
+                    double* F, uint8_t* mask, int32_t* n_inliers, int32_t* status, int32_t* hyp_count,
+                    int32_t* refined, void* workspace, int64_t workspace_bytes);
 
 #ifdef __cplusplus
 }

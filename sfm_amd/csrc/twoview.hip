@@ -1,0 +1,669 @@
+// Fundamental-matrix RANSAC for every image pair of a driver step in one call (gfx950 only): the step between
+// match_features and geometric_verification in the reference's pair loop, cv2.findFundamentalMat(pts1, pts2,
+// cv2.FM_RANSAC, 3.0) at find_matches.py:282.
+//
+// Structure as OpenCV's FM_RANSAC is RECALLED (its source is not pinned here, like the matcher's rules): minimal
+// samples of 7, the 7-point solver with up to three real solutions per sample, error of a match = the larger of its
+// two squared point-to-epipolar-line distances, inlier when that is <= threshold^2, best model = most inliers, F
+// scaled to F[2][2] = 1.  Deviations, on purpose: a FIXED number of hypotheses (no early exit on confidence) and an
+// own, stateless sample generator, so that the result is a function of (points, seed) alone and a NumPy reference
+// can follow the device hypothesis by hypothesis (tests/fundamental_reference.py).
+//
+// Sample generator (k_fund_samples), restated in NumPy by the tests.  All arithmetic is uint64, wrapping:
+//   mix(z):  z += 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+//            z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)          (the splitmix64 finaliser)
+//   key  = mix(mix(mix(seed) ^ segment) ^ hypothesis)
+//   draw d (d = 0, 1, 2, ...) of a segment with M points:  index = ((mix(key ^ d) >> 32) * M) >> 32
+//   the 7 slots are filled in order; a draw equal to an earlier slot is discarded and the next d is taken.  After
+//   256 draws (never reached in practice: 7 * (6/7)^256 = 5e-17 at M = 7) a slot takes the lowest unused index.
+//
+// All arithmetic in float64.  Points arrive as float32 pixels [n][2] with a device seg_ptr[n_seg+1] (int64), the
+// convention of sfm_epipolar_errors.  A match with a NaN or infinite coordinate is left out of the Hartley
+// statistics and is staged as NaN for the scoring, so it fails every comparison; a sample that holds one gives no
+// model.  Sample indices are range-checked on the device before they index anything.
+#include "common.h"
+#include <cfloat>
+
+namespace {
+
+constexpr int FUND_CHUNK = 512;      // points per LDS stage of the scoring loop: 512 x 4 doubles = 16 KiB
+constexpr int FUND_MAX_DRAWS = 256;
+
+// segment s as [b, b + M) inside [0, n): seg_ptr is trusted to ascend, the clamps keep a bad one inside the arrays
+__device__ __forceinline__ void seg_range(const int64_t* __restrict__ seg_ptr, int s, int64_t n, int64_t& b, int& M) {
+  int64_t lo = seg_ptr[s], hi = seg_ptr[s + 1];
+  hi = hi < 0 ? 0 : (hi > n ? n : hi);
+  lo = lo < 0 ? 0 : (lo > hi ? hi : lo);
+  const int64_t m = hi - lo;
+  b = lo;
+  M = (int)(m > 0x7fffffffLL ? 0x7fffffffLL : m);
+}
+
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ bool finite4(float2 p, float2 q) {
+  return isfinite(p.x) && isfinite(p.y) && isfinite(q.x) && isfinite(q.y);
+}
+
+// ------------------------------------------------------------------------------------------------ samples
+__global__ __launch_bounds__(256) void k_fund_samples(const int64_t* __restrict__ seg_ptr, int n_seg, int H, int64_t n,
+                                                      uint64_t seed, int* __restrict__ samples) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (int64_t)n_seg * H) return;
+  const int s = (int)(g / H), hyp = (int)(g % H);
+  int64_t b; int M;
+  seg_range(seg_ptr, s, n, b, M);
+  int idx[7];
+  if (M < 7) {
+#pragma unroll
+    for (int k = 0; k < 7; ++k) samples[g * 7 + k] = -1;
+    return;
+  }
+  const uint64_t key = mix64(mix64(mix64(seed) ^ (uint64_t)s) ^ (uint64_t)hyp);
+  uint64_t d = 0;
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    int v = -1;
+    while (d < (uint64_t)FUND_MAX_DRAWS) {
+      const int c = (int)(((mix64(key ^ d) >> 32) * (uint64_t)M) >> 32);
+      ++d;
+      bool dup = false;
+#pragma unroll
+      for (int j = 0; j < 7; ++j) dup |= (j < k) && (idx[j] == c);
+      if (!dup) { v = c; break; }
+    }
+    if (v < 0) {                                     // lowest unused index (at most 6 are taken, M >= 7)
+      for (int c = 0; c < 7 && v < 0; ++c) {
+        bool dup = false;
+#pragma unroll
+        for (int j = 0; j < 7; ++j) dup |= (j < k) && (idx[j] == c);
+        if (!dup) v = c;
+      }
+    }
+    idx[k] = v;
+  }
+#pragma unroll
+  for (int k = 0; k < 7; ++k) samples[g * 7 + k] = idx[k];
+}
+
+// ------------------------------------------------------------------------------------------ normalisation
+// sum of one double per thread over a 256-thread block, fixed order (deterministic); every thread gets the total
+__device__ __forceinline__ double block_sum(double v, double* s_w) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+}
+
+// Hartley transform per segment and image: x' = sc * (x - c), centroid c, mean distance sqrt(2) after scaling.
+// T[s] = {sc1, cx1, cy1, sc2, cx2, cy2}: the 2 x 3 upper rows [sc 0 -sc*cx; 0 sc -sc*cy] in factored form.
+__global__ __launch_bounds__(256) void k_fund_normalise(const int64_t* __restrict__ seg_ptr, int64_t n,
+                                                        const float2* __restrict__ pts1, const float2* __restrict__ pts2,
+                                                        double* __restrict__ T) {
+  __shared__ double s_w[4];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  int64_t b; int M;
+  seg_range(seg_ptr, s, n, b, M);
+  double sx1 = 0, sy1 = 0, sx2 = 0, sy2 = 0, cnt = 0;
+  for (int i = tid; i < M; i += 256) {
+    const float2 p = pts1[b + i], q = pts2[b + i];
+    if (finite4(p, q)) { sx1 += p.x; sy1 += p.y; sx2 += q.x; sy2 += q.y; cnt += 1.0; }
+  }
+  cnt = block_sum(cnt, s_w);
+  const double inv = cnt > 0 ? 1.0 / cnt : 0.0;
+  const double cx1 = block_sum(sx1, s_w) * inv, cy1 = block_sum(sy1, s_w) * inv;
+  const double cx2 = block_sum(sx2, s_w) * inv, cy2 = block_sum(sy2, s_w) * inv;
+  double d1 = 0, d2 = 0;
+  for (int i = tid; i < M; i += 256) {
+    const float2 p = pts1[b + i], q = pts2[b + i];
+    if (finite4(p, q)) {
+      const double ax = p.x - cx1, ay = p.y - cy1, bx = q.x - cx2, by = q.y - cy2;
+      d1 += sqrt(ax * ax + ay * ay); d2 += sqrt(bx * bx + by * by);
+    }
+  }
+  d1 = block_sum(d1, s_w) * inv; d2 = block_sum(d2, s_w) * inv;
+  if (tid == 0) {
+    double* t = T + 6 * (int64_t)s;
+    t[0] = d1 > 0 ? sqrt(2.0) / d1 : 1.0; t[1] = cx1; t[2] = cy1;
+    t[3] = d2 > 0 ? sqrt(2.0) / d2 : 1.0; t[4] = cx2; t[5] = cy2;
+  }
+}
+
+// --------------------------------------------------------------------------------------------- the models
+__device__ __forceinline__ double det3(double a0, double a1, double a2, double a3, double a4, double a5, double a6,
+                                       double a7, double a8) {
+  return a0 * (a4 * a8 - a5 * a7) - a1 * (a3 * a8 - a5 * a6) + a2 * (a3 * a7 - a4 * a6);
+}
+
+// F = T2^T Fn T1 with T = [sc 0 -sc*cx; 0 sc -sc*cy; 0 0 1]
+__device__ __forceinline__ void denormalise(const double (&fn)[9], const double* __restrict__ t, double (&f)[9]) {
+  const double s1 = t[0], tx1 = -t[0] * t[1], ty1 = -t[0] * t[2];
+  const double s2 = t[3], tx2 = -t[3] * t[4], ty2 = -t[3] * t[5];
+  double g[9];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    g[3 * r] = s1 * fn[3 * r];
+    g[3 * r + 1] = s1 * fn[3 * r + 1];
+    g[3 * r + 2] = fn[3 * r] * tx1 + fn[3 * r + 1] * ty1 + fn[3 * r + 2];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    f[c] = s2 * g[c];
+    f[3 + c] = s2 * g[3 + c];
+    f[6 + c] = tx2 * g[c] + ty2 * g[3 + c] + g[6 + c];
+  }
+}
+
+// the error rule without its divisions: max(s^2/den2, s^2/den1) <= thr2  <=>  s^2 <= thr2 * min(den1, den2), with
+// min > 0 required so that a zero line (or F = 0, the empty candidate slot) never counts.  NaN fails every test.
+__device__ __forceinline__ bool fund_inlier(const double (&f)[9], double x1, double y1, double x2, double y2, double thr2) {
+  const double a = f[0] * x1 + f[1] * y1 + f[2], b = f[3] * x1 + f[4] * y1 + f[5], c = f[6] * x1 + f[7] * y1 + f[8];
+  const double s = x2 * a + y2 * b + c;
+  const double ta = f[0] * x2 + f[3] * y2 + f[6], tb = f[1] * x2 + f[4] * y2 + f[7];
+  const double den = fmin(a * a + b * b, ta * ta + tb * tb);
+  return (den > 0.0) && (s * s <= thr2 * den);
+}
+
+// stage points [c0, c0 + cnt) of a segment into LDS as doubles; a non-finite match becomes NaN in all four
+__device__ __forceinline__ void stage_points(double2* s_pt, const float2* __restrict__ pts1, const float2* __restrict__ pts2,
+                                             int64_t base, int cnt, int nthreads) {
+  for (int t = threadIdx.x; t < cnt; t += nthreads) {
+    const float2 p = pts1[base + t], q = pts2[base + t];
+    const bool ok = finite4(p, q);
+    const double nan = __builtin_nan("");
+    s_pt[2 * t] = ok ? make_double2((double)p.x, (double)p.y) : make_double2(nan, nan);
+    s_pt[2 * t + 1] = ok ? make_double2((double)q.x, (double)q.y) : make_double2(nan, nan);
+  }
+}
+
+// rotation k of the elimination acts on columns (i, j), j > i: k = i*8 - i*(i-1)/2 + (j - i - 1), 35 in all
+__device__ __forceinline__ constexpr int rot_index(int i, int j) { return i * 8 - i * (i - 1) / 2 + (j - i - 1); }
+
+// One lane per (segment, hypothesis); a workgroup covers 256 hypotheses of ONE segment, so the scoring loop's points
+// are wave-uniform: fetched from global memory once per workgroup and chunk into LDS, read back as broadcasts.
+//
+// Null space of the 7 x 9 system without pivoting: Givens rotations of column pairs from the right, A G = [L 0] with
+// L lower triangular; the last two columns of G = G_1 ... G_35 span the null space.  Rows are formed one at a time
+// (row i: apply the rotations so far, then zero its entries i+1..8), so only the 35 (c, s) pairs are live, and every
+// array index is a compile-time constant after unrolling: nothing is indexed at run time, nothing goes to scratch.
+__global__ __launch_bounds__(256) void k_fund_hypotheses(const int64_t* __restrict__ seg_ptr, int64_t n,
+                                                         const float2* __restrict__ pts1, const float2* __restrict__ pts2,
+                                                         const int* __restrict__ samples, int H, int nblk, double thr2,
+                                                         const double* __restrict__ T, int* __restrict__ hyp_count,
+                                                         double* __restrict__ hyp_F) {
+  __shared__ double2 s_pt[2 * FUND_CHUNK];
+  const int s = blockIdx.x / nblk;
+  const int hyp = (blockIdx.x % nblk) * 256 + threadIdx.x;
+  const bool active = hyp < H;
+  const int64_t slot = (int64_t)s * H + hyp;
+  int64_t b; int M;
+  seg_range(seg_ptr, s, n, b, M);
+  if (M < 7) {                                           // uniform over the workgroup
+    if (active) {
+      hyp_count[slot] = 0;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) hyp_F[slot * 9 + k] = 0.0;
+    }
+    return;
+  }
+  const double* t = T + 6 * (int64_t)s;
+  double Fc[3][9];
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int e = 0; e < 9; ++e) Fc[k][e] = 0.0;
+  {
+    bool ok = active;
+    int idx[7];
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+      idx[k] = active ? samples[slot * 7 + k] : 0;
+      ok = ok && idx[k] >= 0 && idx[k] < M;
+    }
+    double rc[35], rs[35];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+      const int id = ok ? idx[i] : 0;
+      const float2 p = pts1[b + id], q = pts2[b + id];
+      const double xa = ((double)p.x - t[1]) * t[0], xb = ((double)p.y - t[2]) * t[0];
+      const double xc = ((double)q.x - t[4]) * t[3], xd = ((double)q.y - t[5]) * t[3];
+      double r[9] = {xc * xa, xc * xb, xc, xd * xa, xd * xb, xd, xa, xb, 1.0};
+#pragma unroll
+      for (int ii = 0; ii < i; ++ii)
+#pragma unroll
+        for (int j = ii + 1; j < 9; ++j) {
+          const double c = rc[rot_index(ii, j)], sn = rs[rot_index(ii, j)];
+          const double u = r[ii], v = r[j];
+          r[ii] = c * u + sn * v; r[j] = c * v - sn * u;
+        }
+#pragma unroll
+      for (int j = i + 1; j < 9; ++j) {
+        const double u = r[i], v = r[j];
+        const double hh = sqrt(u * u + v * v);
+        const bool nz = hh > 0.0;                          // NaN: (1, 0), and the NaN travels on in r
+        const double c = nz ? u / hh : 1.0, sn = nz ? v / hh : 0.0;
+        rc[rot_index(i, j)] = c; rs[rot_index(i, j)] = sn;
+        r[i] = nz ? hh : u; r[j] = nz ? 0.0 : v;
+      }
+      ok = ok && (r[i] == r[i]);
+    }
+    // null vectors G e7, G e8: the rotations applied in reverse order to the unit vectors
+    double f1[9], f2[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) { f1[e] = (e == 7) ? 1.0 : 0.0; f2[e] = (e == 8) ? 1.0 : 0.0; }
+#pragma unroll
+    for (int i = 6; i >= 0; --i)
+#pragma unroll
+      for (int j = 8; j > i; --j) {
+        const double c = rc[rot_index(i, j)], sn = rs[rot_index(i, j)];
+        double u = f1[i], v = f1[j];
+        f1[i] = c * u - sn * v; f1[j] = sn * u + c * v;
+        u = f2[i]; v = f2[j];
+        f2[i] = c * u - sn * v; f2[j] = sn * u + c * v;
+      }
+    // det(l f1 + (1 - l) f2) is a cubic in l: its values at l = -1, 0, 1, 2 give the coefficients
+    double pv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const double l = (double)(k - 1);
+      double m[9];
+#pragma unroll
+      for (int e = 0; e < 9; ++e) m[e] = l * f1[e] + (1.0 - l) * f2[e];
+      pv[k] = det3(m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8]);
+    }
+    const double c0 = pv[1];
+    const double c3 = (pv[3] - 3.0 * pv[2] + 3.0 * pv[1] - pv[0]) / 6.0;
+    const double c2 = 0.5 * (pv[2] + pv[0]) - pv[1];
+    const double c1 = pv[2] - c0 - c2 - c3;
+    const double cmax = fmax(fmax(fabs(c0), fabs(c1)), fmax(fabs(c2), fabs(c3)));
+    ok = ok && isfinite(cmax) && (c0 == c0) && (c1 == c1) && (c2 == c2) && (c3 == c3) && !(fabs(c3) < 1e-14 * cmax);
+    // monic x^3 + A x^2 + B x + C: closed form (trigonometric / Cardano), then two Newton steps on the monic cubic
+    const double A = c2 / c3, B = c1 / c3, Cc = c0 / c3;
+    const double Q = (A * A - 3.0 * B) / 9.0, R = (2.0 * A * A * A - 9.0 * A * B + 27.0 * Cc) / 54.0;
+    const double Q3 = Q * Q * Q;
+    double root[3];
+    int nr;
+    if (R * R < Q3) {
+      const double sq = sqrt(Q);
+      double ct = R / (sq * sq * sq);
+      ct = ct < -1.0 ? -1.0 : (ct > 1.0 ? 1.0 : ct);
+      const double th = acos(ct);
+      const double two_pi = 6.283185307179586476925286766559;
+      root[0] = -2.0 * sq * cos(th / 3.0) - A / 3.0;                 // ascending for th in [0, pi]
+      root[1] = -2.0 * sq * cos((th + 2.0 * two_pi) / 3.0) - A / 3.0;
+      root[2] = -2.0 * sq * cos((th + two_pi) / 3.0) - A / 3.0;
+      nr = 3;
+    } else {
+      const double e = cbrt(fabs(R) + sqrt(R * R - Q3));
+      const double aa = R > 0.0 ? -e : e;
+      const double bb = aa != 0.0 ? Q / aa : 0.0;
+      root[0] = aa + bb - A / 3.0; root[1] = 0.0; root[2] = 0.0;
+      nr = 1;
+    }
+    if (!ok) nr = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      double x = root[k];
+#pragma unroll
+      for (int it = 0; it < 2; ++it) {
+        const double fx = ((x + A) * x + B) * x + Cc, dx = (3.0 * x + 2.0 * A) * x + B;
+        const double xn = x - fx / dx;
+        x = (dx != 0.0 && isfinite(xn)) ? xn : x;
+      }
+      double fn[9], f[9];
+#pragma unroll
+      for (int e = 0; e < 9; ++e) fn[e] = x * f1[e] + (1.0 - x) * f2[e];
+      denormalise(fn, t, f);
+      bool good = k < nr;
+#pragma unroll
+      for (int e = 0; e < 9; ++e) good = good && isfinite(f[e]);
+#pragma unroll
+      for (int e = 0; e < 9; ++e) Fc[k][e] = good ? f[e] : 0.0;
+    }
+  }
+  // scoring: every lane walks all points of the segment with its (up to) three candidates in registers
+  int cnt0 = 0, cnt1 = 0, cnt2 = 0;
+  for (int base = 0; base < M; base += FUND_CHUNK) {
+    const int cnt = (M - base < FUND_CHUNK) ? (M - base) : FUND_CHUNK;
+    __syncthreads();
+    stage_points(s_pt, pts1, pts2, b + base, cnt, 256);
+    __syncthreads();
+    for (int i = 0; i < cnt; ++i) {
+      const double2 p = s_pt[2 * i], q = s_pt[2 * i + 1];
+      cnt0 += fund_inlier(Fc[0], p.x, p.y, q.x, q.y, thr2) ? 1 : 0;
+      cnt1 += fund_inlier(Fc[1], p.x, p.y, q.x, q.y, thr2) ? 1 : 0;
+      cnt2 += fund_inlier(Fc[2], p.x, p.y, q.x, q.y, thr2) ? 1 : 0;
+    }
+  }
+  if (!active) return;
+  int best = cnt0;
+  const bool use1 = cnt1 > best;
+  best = use1 ? cnt1 : best;
+  const bool use2 = cnt2 > best;
+  best = use2 ? cnt2 : best;
+  hyp_count[slot] = best;
+#pragma unroll
+  for (int e = 0; e < 9; ++e) hyp_F[slot * 9 + e] = use2 ? Fc[2][e] : (use1 ? Fc[1][e] : Fc[0][e]);
+}
+
+// ---------------------------------------------------------------------------------------------- selection
+// F / F[8] when that is finite (F[8] / F[8] == 1 exactly), F as it is otherwise
+__device__ __forceinline__ void scale_f22(double (&f)[9]) {
+  const double d = f[8];
+  bool ok = d != 0.0;
+  double g[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) { g[e] = f[e] / d; ok = ok && isfinite(g[e]); }
+#pragma unroll
+  for (int e = 0; e < 9; ++e) f[e] = ok ? g[e] : f[e];
+}
+
+// inliers of f over the whole segment, counted by the workgroup (staged through LDS like the scoring loop is not
+// needed here: every thread takes its own points); writes the mask when `mask` is not null
+__device__ __forceinline__ int segment_count(const double (&f)[9], const float2* __restrict__ pts1,
+                                             const float2* __restrict__ pts2, int64_t b, int M, double thr2,
+                                             uint8_t* __restrict__ mask, int* s_i) {
+  int c = 0;
+  for (int i = threadIdx.x; i < M; i += 256) {
+    const float2 p = pts1[b + i], q = pts2[b + i];
+    const bool in = finite4(p, q) && fund_inlier(f, (double)p.x, (double)p.y, (double)q.x, (double)q.y, thr2);
+    if (mask) mask[b + i] = in ? 1 : 0;
+    c += in ? 1 : 0;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s_i[threadIdx.x >> 6] = c;
+  __syncthreads();
+  return s_i[0] + s_i[1] + s_i[2] + s_i[3];
+}
+
+// winner per segment: largest count, ties to the lowest hypothesis index, as one integer key
+// (count << 32 | ~hypothesis) reduced by a tree; then F scaled to F[2][2] = 1, its mask and its count
+__global__ __launch_bounds__(256) void k_fund_select(const int64_t* __restrict__ seg_ptr, int64_t n,
+                                                     const float2* __restrict__ pts1, const float2* __restrict__ pts2,
+                                                     int H, double thr2, const int* __restrict__ hyp_count,
+                                                     const double* __restrict__ hyp_F, double* __restrict__ F,
+                                                     uint8_t* __restrict__ mask, int* __restrict__ n_inliers,
+                                                     int* __restrict__ status, int* __restrict__ refined) {
+  __shared__ unsigned long long s_key[256];
+  __shared__ int s_i[4];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  int64_t b; int M;
+  seg_range(seg_ptr, s, n, b, M);
+  unsigned long long key = 0;
+  if (M >= 7)
+    for (int hp = tid; hp < H; hp += 256) {
+      const int c = hyp_count[(int64_t)s * H + hp];
+      const unsigned long long k = ((unsigned long long)(unsigned)(c < 0 ? 0 : c) << 32) | (0xFFFFFFFFu - (unsigned)hp);
+      key = k > key ? k : key;
+    }
+  s_key[tid] = key;
+  __syncthreads();
+#pragma unroll
+  for (int d = 128; d >= 1; d >>= 1) {
+    if (tid < d) { const unsigned long long o = s_key[tid + d]; if (o > s_key[tid]) s_key[tid] = o; }
+    __syncthreads();
+  }
+  key = s_key[0];
+  const int best = (int)(key >> 32);
+  const int st = (M < 7) ? 1 : (best == 0 ? 2 : 0);
+  double f[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) f[e] = 0.0;
+  int count = 0;
+  if (st == 0) {                                         // uniform over the workgroup
+    const int hp = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFu));
+#pragma unroll
+    for (int e = 0; e < 9; ++e) f[e] = hyp_F[((int64_t)s * H + hp) * 9 + e];
+    scale_f22(f);
+    count = segment_count(f, pts1, pts2, b, M, thr2, mask, s_i);
+  } else {
+    for (int i = tid; i < M; i += 256) mask[b + i] = 0;
+  }
+  if (tid == 0) {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) F[9 * (int64_t)s + e] = f[e];
+    n_inliers[s] = count;
+    status[s] = st;
+    if (refined) refined[s] = 0;
+  }
+}
+
+// -------------------------------------------------------------------------------------------------- refit
+// Normalised 8-point least squares over the winner's inliers (the segment's Hartley transforms), one workgroup per
+// segment: the 9 x 9 normal matrix summed by the workgroup in a fixed order, its smallest eigenvector by cyclic
+// Jacobi in LDS (lanes 0..8 rotate one row / column entry each), rank 2 by zeroing the smallest singular value of the
+// 3 x 3 (one-sided Jacobi in registers, as k_triangulate2 does its 4 x 4), then re-scored with the same error rule.
+// The refit replaces the winner only if its inlier count is not lower.
+__global__ __launch_bounds__(256) void k_fund_refit(const int64_t* __restrict__ seg_ptr, int64_t n,
+                                                    const float2* __restrict__ pts1, const float2* __restrict__ pts2,
+                                                    double thr2, const double* __restrict__ T, double* __restrict__ F,
+                                                    uint8_t* __restrict__ mask, int* __restrict__ n_inliers,
+                                                    const int* __restrict__ status, int* __restrict__ refined) {
+  __shared__ double s_red[4][45];
+  __shared__ double s_A[9][9], s_V[9][9];
+  __shared__ int s_i[4];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  int64_t b; int M;
+  seg_range(seg_ptr, s, n, b, M);
+  const int have = n_inliers[s];
+  if (status[s] != 0 || have < 8) return;                // uniform; refined[s] stays 0
+  const double* t = T + 6 * (int64_t)s;
+  double acc[45];
+#pragma unroll
+  for (int k = 0; k < 45; ++k) acc[k] = 0.0;
+  for (int i = tid; i < M; i += 256) {
+    if (!mask[b + i]) continue;
+    const float2 p = pts1[b + i], q = pts2[b + i];
+    const double xa = ((double)p.x - t[1]) * t[0], xb = ((double)p.y - t[2]) * t[0];
+    const double xc = ((double)q.x - t[4]) * t[3], xd = ((double)q.y - t[5]) * t[3];
+    const double r[9] = {xc * xa, xc * xb, xc, xd * xa, xd * xb, xd, xa, xb, 1.0};
+    int k = 0;
+#pragma unroll
+    for (int u = 0; u < 9; ++u)
+#pragma unroll
+      for (int v = u; v < 9; ++v) acc[k++] += r[u] * r[v];
+  }
+#pragma unroll
+  for (int k = 0; k < 45; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    acc[k] = v;
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 45; ++k) s_red[tid >> 6][k] = acc[k];
+  }
+  __syncthreads();
+  if (tid < 81) {
+    const int u = tid / 9, v = tid % 9;
+    const int lo = u < v ? u : v, hi = u < v ? v : u;
+    const int k = lo * 9 - lo * (lo - 1) / 2 + (hi - lo);
+    s_A[u][v] = (s_red[0][k] + s_red[1][k]) + (s_red[2][k] + s_red[3][k]);
+    s_V[u][v] = (u == v) ? 1.0 : 0.0;
+  }
+  __syncthreads();
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    double off = 0.0, diag = 0.0;
+    for (int u = 0; u < 9; ++u)
+      for (int v = 0; v < 9; ++v) { const double a = s_A[u][v]; if (u == v) diag += a * a; else off += a * a; }
+    if (!(off > 1e-30 * diag)) break;                    // uniform: every thread read the same values
+    for (int p = 0; p < 8; ++p)
+      for (int q = p + 1; q < 9; ++q) {
+        const double app = s_A[p][p], aqq = s_A[q][q], apq = s_A[p][q];
+        double c = 1.0, sn = 0.0;
+        if (fabs(apq) > DBL_EPSILON * 1e-3 * sqrt(fabs(app * aqq)) && apq != 0.0) {
+          const double zeta = (aqq - app) / (2.0 * apq);
+          const double tt = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+          c = 1.0 / sqrt(1.0 + tt * tt); sn = c * tt;
+        }
+        __syncthreads();
+        if (tid < 9) {                                   // A <- A J, V <- V J (columns p, q)
+          const double ap = s_A[tid][p], aq = s_A[tid][q];
+          s_A[tid][p] = c * ap - sn * aq; s_A[tid][q] = sn * ap + c * aq;
+          const double vp = s_V[tid][p], vq = s_V[tid][q];
+          s_V[tid][p] = c * vp - sn * vq; s_V[tid][q] = sn * vp + c * vq;
+        }
+        __syncthreads();
+        if (tid < 9) {                                   // A <- J^T A (rows p, q)
+          const double ap = s_A[p][tid], aq = s_A[q][tid];
+          s_A[p][tid] = c * ap - sn * aq; s_A[q][tid] = sn * ap + c * aq;
+        }
+        __syncthreads();
+      }
+  }
+  int kmin = 0;
+  for (int k = 1; k < 9; ++k) if (s_A[k][k] < s_A[kmin][kmin]) kmin = k;
+  double U[3][3], V[3][3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { U[r][c] = s_V[3 * r + c][kmin]; V[r][c] = (r == c) ? 1.0 : 0.0; }
+  double fn[9];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) fn[3 * r + c] = U[r][c];
+  const double eps = 10.0 * DBL_EPSILON;
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    bool changed = false;
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+      for (int q = p + 1; q < 3; ++q) {
+        double a = 0.0, bq = 0.0, g = 0.0;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) { a += U[r][p] * U[r][p]; bq += U[r][q] * U[r][q]; g += U[r][p] * U[r][q]; }
+        if (fabs(g) > eps * sqrt(a * bq)) {
+          changed = true;
+          const double zeta = (bq - a) / (2.0 * g);
+          const double tt = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+          const double c = 1.0 / sqrt(1.0 + tt * tt), sn = c * tt;
+#pragma unroll
+          for (int r = 0; r < 3; ++r) {
+            const double up = U[r][p], uq = U[r][q];
+            U[r][p] = c * up - sn * uq; U[r][q] = sn * up + c * uq;
+            const double vp = V[r][p], vq = V[r][q];
+            V[r][p] = c * vp - sn * vq; V[r][q] = sn * vp + c * vq;
+          }
+        }
+      }
+    if (!changed) break;
+  }
+  // Fn = U V^T (U's columns carry the singular values); drop the column pair of the smallest one
+  double nrm[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) nrm[k] = U[0][k] * U[0][k] + U[1][k] * U[1][k] + U[2][k] * U[2][k];
+  const bool m1 = nrm[1] < nrm[0];
+  const double n01 = m1 ? nrm[1] : nrm[0];
+  const bool m2 = nrm[2] < n01;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const double ur = m2 ? U[r][2] : (m1 ? U[r][1] : U[r][0]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double vc = m2 ? V[c][2] : (m1 ? V[c][1] : V[c][0]);
+      fn[3 * r + c] -= ur * vc;
+    }
+  }
+  double f[9];
+  denormalise(fn, t, f);
+  bool good = true;
+#pragma unroll
+  for (int e = 0; e < 9; ++e) good = good && isfinite(f[e]);
+  if (!good) return;                                     // uniform: every thread computed the same f
+  scale_f22(f);
+  const int count = segment_count(f, pts1, pts2, b, M, thr2, nullptr, s_i);
+  if (count < have) return;
+  (void)segment_count(f, pts1, pts2, b, M, thr2, mask, s_i);
+  if (tid == 0) {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) F[9 * (int64_t)s + e] = f[e];
+    n_inliers[s] = count;
+    if (refined) refined[s] = 1;
+  }
+}
+
+struct fund_ws {
+  double* T;
+  double* hyp_F;
+  int* hyp_count;
+  int64_t bytes;
+};
+
+fund_ws fund_layout(void* workspace, int32_t n_seg, int32_t n_hyp) {
+  fund_ws w;
+  char* p = (char*)workspace;
+  int64_t off = 0;
+  w.T = (double*)(p + off);         off += align_up((int64_t)n_seg * 6 * 8, 256);
+  w.hyp_F = (double*)(p + off);     off += align_up((int64_t)n_seg * n_hyp * 9 * 8, 256);
+  w.hyp_count = (int*)(p + off);    off += align_up((int64_t)n_seg * n_hyp * 4, 256);
+  w.bytes = off + 256;
+  return w;
+}
+
+}  // namespace
+
+// ================================================================================================ C ABI
+extern "C" int sfm_fund_workspace_bytes(int64_t n_points, int32_t n_seg, int32_t n_hyp, int64_t* bytes_host) {
+  if (!bytes_host || n_points < 0 || n_seg < 0 || n_hyp < 1) return SFM_ERR_ARG;
+  *bytes_host = fund_layout(nullptr, n_seg, n_hyp).bytes;
+  return SFM_OK;
+}
+
+extern "C" int sfm_fund_draw_samples(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, int32_t n_hyp, uint64_t seed,
+                                     int32_t* samples) {
+  if (!h) return SFM_ERR_ARG;
+  if (n_seg < 0 || n_hyp < 1 || (int64_t)n_seg * n_hyp > 0x7fffffffLL * 64)
+    return sfm_fail(h, SFM_ERR_ARG, "sfm_fund_draw_samples", "bad argument");
+  if (n_seg == 0) return SFM_OK;
+  if (!seg_ptr || !samples) return sfm_fail(h, SFM_ERR_ARG, "sfm_fund_draw_samples", "null pointer");
+  const int64_t total = (int64_t)n_seg * n_hyp;
+  // the segment's extent comes from seg_ptr alone here: no clamp to a point count (INT64_MAX passes every segment)
+  hipLaunchKernelGGL(k_fund_samples, dim3(cdiv(total, 256)), dim3(256), 0, h->stream, seg_ptr, n_seg, n_hyp,
+                     (int64_t)0x7fffffffffffffffLL, (uint64_t)seed, samples);
+  SFM_LAUNCH_CHECK(h, "sfm_fund_draw_samples");
+  return SFM_OK;
+}
+
+extern "C" int sfm_fund_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, const float* pts1, const float* pts2,
+                               int64_t n, const int32_t* samples, int32_t n_hyp, double threshold, int32_t refine,
+                               double* F, uint8_t* mask, int32_t* n_inliers, int32_t* status, int32_t* hyp_count,
+                               int32_t* refined, void* workspace, int64_t workspace_bytes) {
+  if (!h) return SFM_ERR_ARG;
+  if (n < 0 || n_seg < 0 || n_hyp < 1 || !(threshold >= 0.0) || !(threshold < DBL_MAX) ||
+      (int64_t)n_seg * ((n_hyp + 255) / 256) > 0x7fffffffLL)
+    return sfm_fail(h, SFM_ERR_ARG, "sfm_fund_ransac", "bad argument");
+  if (n == 0 || n_seg == 0) return SFM_OK;
+  if (!seg_ptr || !pts1 || !pts2 || !samples || !F || !mask || !n_inliers || !status || !workspace)
+    return sfm_fail(h, SFM_ERR_ARG, "sfm_fund_ransac", "null pointer");
+  const fund_ws w = fund_layout(workspace, n_seg, n_hyp);
+  if (workspace_bytes < w.bytes) return sfm_fail(h, SFM_ERR_WORKSPACE, "sfm_fund_ransac", "workspace too small");
+  int* counts = hyp_count ? hyp_count : w.hyp_count;
+  const double thr2 = threshold * threshold;
+  const float2* p1 = (const float2*)pts1;
+  const float2* p2 = (const float2*)pts2;
+  const int nblk = (n_hyp + 255) / 256;
+  SFM_HIP(h, hipMemsetAsync(mask, 0, (size_t)n, h->stream));    // matches outside every segment
+  hipLaunchKernelGGL(k_fund_normalise, dim3(n_seg), dim3(256), 0, h->stream, seg_ptr, n, p1, p2, w.T);
+  sfm_prof_begin(h, SFM_PROF_FUND_HYP);
+  hipLaunchKernelGGL(k_fund_hypotheses, dim3((unsigned)n_seg * nblk), dim3(256), 0, h->stream, seg_ptr, n, p1, p2,
+                     samples, n_hyp, nblk, thr2, (const double*)w.T, counts, w.hyp_F);
+  sfm_prof_end(h, SFM_PROF_FUND_HYP);
+  hipLaunchKernelGGL(k_fund_select, dim3(n_seg), dim3(256), 0, h->stream, seg_ptr, n, p1, p2, n_hyp, thr2,
+                     (const int*)counts, (const double*)w.hyp_F, F, mask, n_inliers, status, refined);
+  if (refine)
+    hipLaunchKernelGGL(k_fund_refit, dim3(n_seg), dim3(256), 0, h->stream, seg_ptr, n, p1, p2, thr2,
+                       (const double*)w.T, F, mask, n_inliers, (const int*)status, refined);
+  SFM_LAUNCH_CHECK(h, "sfm_fund_ransac");
+  return SFM_OK;
+}

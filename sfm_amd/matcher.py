@@ -1,6 +1,7 @@
 """Drop-in for the reference's `ImageMatcher.match_features`
 (/root/reference/utils/find_matches.py:141-155): brute-force kNN (k=2) + Lowe ratio test on
-the GPU through libsfm_amd.so; `geometric_verification` (:157-214) comes from sfm_amd.driver.
+the GPU through libsfm_amd.so; `geometric_verification` (:157-214) comes from sfm_amd.driver,
+`find_fundamental_mat` (the cv2.findFundamentalMat call at :282) from sfm_amd.twoview.
 No CPU fallback."""
 from __future__ import annotations
 
@@ -10,7 +11,8 @@ from collections.abc import Sequence
 import numpy as np
 
 from . import _lib
-from .driver import VerificationMixin
+from .driver import VerificationMixin, verify_pairs
+from .twoview import FundamentalMixin, estimate_fundamental_batched, keypoints_xy
 
 
 class DMatch:
@@ -335,7 +337,7 @@ def match_pairs(descs, pairs, ratio=0.75, metric="auto", device=0):
     return out
 
 
-class ImageMatcher(VerificationMixin):
+class ImageMatcher(VerificationMixin, FundamentalMixin):
     """`match_features` with the reference's call shape (find_matches.py:141).  The in-tree
     reference matches ORB bit strings with NORM_HAMMING and ratio 0.75; its shipped results come
     from SIFT / L2.  metric="auto" follows the descriptor type."""
@@ -363,4 +365,44 @@ class ImageMatcher(VerificationMixin):
                 out.append(None)
                 continue
             out.append(DMatchList(*res))
+        return out
+
+    def process_pairs(self, keypoints, descs, pairs, min_matches=5):
+        """process_image_pair (find_matches.py:246-310) for every (i, j) of `pairs`, minus the image I/O and the visualisation,
+        in three batched device steps: match_pairs (:272) -> the float32 pts1 / pts2 gathers (:278-279), pairs under
+        `min_matches` dropped (:274) -> estimate_fundamental_batched (:282) -> verify_pairs (:288).
+
+        keypoints: per image an [n,2] array of pixel coordinates or a list of objects with `.pt` (cv2.KeyPoint).  Returns one
+        entry per pair: None where the reference returns None (too few matches, a pair its try / except skips, no model), else
+        {'matches': DMatchList, 'pts1', 'pts2' [M,2] float32, 'F' [3,3], 'inlier_mask' [M] bool, 'symmetric_errors',
+        'metrics': the dictionary of geometric_verification, 'quality_ok': verify_match_quality of it}."""
+        import logging
+        pairs = [(int(i), int(j)) for i, j in pairs]
+        xy = {}
+        out = [None] * len(pairs)
+        live, p1, p2, ml = [], [], [], []
+        for s, ((i, j), res) in enumerate(zip(pairs, match_pairs(descs, pairs, self.ratio, self.metric, self.device))):
+            if isinstance(res, Exception):
+                logging.error(f"Error processing pair ({i}, {j}): {res}")
+                continue
+            q, t, d = res
+            if len(q) < min_matches:
+                continue
+            for img in (i, j):
+                if img not in xy:
+                    xy[img] = keypoints_xy(keypoints[img])
+            live.append(s); ml.append(DMatchList(q, t, d))
+            p1.append(xy[i][q]); p2.append(xy[j][t])
+        if not live:
+            return out
+        models = estimate_fundamental_batched(p1, p2, self.fund_threshold, n_hypotheses=self.fund_hypotheses,
+                                              seed=self.fund_seed, device=self.device)
+        ok = [k for k, (F, _) in enumerate(models) if F is not None]
+        if not ok:
+            return out
+        verified = verify_pairs([(p1[k], p2[k], models[k][0]) for k in ok], 3.0, self.device)
+        for k, v in zip(ok, verified):
+            out[live[k]] = {"matches": ml[k], "pts1": p1[k], "pts2": p2[k], "F": models[k][0],
+                            "inlier_mask": v["inlier_mask"], "symmetric_errors": v["symmetric_errors"],
+                            "metrics": v["metrics"], "quality_ok": self.verify_match_quality(v)}
         return out

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Device-time measurement of the driver-row kernels with inputs resident in HBM:
-association (pair tests/s), two-view triangulation (tracks/s), epipolar verification (matches/s).  Prints one
-JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
+association (pair tests/s), two-view triangulation (tracks/s), epipolar verification (matches/s), and the batched
+fundamental-matrix RANSAC beside the batched matcher it follows in the pair loop.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
 functions to time on a bounded sample of the same inputs (this tool itself never imports oracle/).
-usage: python tools/bench_driver.py [--reps 20]"""
+usage: python tools/bench_driver.py [--reps 20] [--fundamental-only]"""
 import argparse
 import ctypes as C
 import json
@@ -128,13 +128,123 @@ def measure(reps=20, tracks=100000, corr=20000, cpu_fns=None, emit=None):
     return results
 
 
+FUND_FLOP_PER_TEST = 40          # one candidate against one match: two epipolar lines, s, two norms, the comparison
+
+
+def _synthetic_pairs(rng, n_pairs, M, outlier_share=0.3, noise=0.5):
+    """Two-view scenes with the reference's K: points in a box in front of two cameras, float32 pixels."""
+    K = np.array([[1228.0, 0, 512], [0, 1228.0, 384], [0, 0, 1]])
+    p1, p2 = [], []
+    for _ in range(n_pairs):
+        X = rng.uniform(-1, 1, (M, 3)) + [0, 0, 6.0]
+        yaw = rng.uniform(0.1, 0.4)
+        R = np.array([[np.cos(yaw), 0, np.sin(yaw)], [0, 1, 0], [-np.sin(yaw), 0, np.cos(yaw)]])
+        t = np.array([-1.5, 0.1, 0.3]) * rng.uniform(0.5, 1.5)
+        x1 = X @ K.T; x1 = x1[:, :2] / x1[:, 2:] + rng.normal(size=(M, 2)) * noise
+        x2 = (X @ R.T + t) @ K.T; x2 = x2[:, :2] / x2[:, 2:] + rng.normal(size=(M, 2)) * noise
+        k = int(M * outlier_share)
+        x2[:k] = rng.uniform(0, 1, (k, 2)) * [1024, 768]
+        p1.append(x1.astype(np.float32)); p2.append(x2.astype(np.float32))
+    return p1, p2
+
+
+def measure_fundamental(reps=20, n_hyp=1024, emit=None):
+    """sfm_fund_ransac on (a) the 148 shipped pairs and (b) 630 synthetic pairs of 300 matches, inputs resident in HBM:
+    the whole call and k_fund_hypotheses alone (the handle's event slot), and, from the same run, the device time of the
+    batched matcher's two launches over the same 630 pairs (36 images x 500 descriptors of dimension 128)."""
+    import torch
+    from sfm_amd import _lib, matcher
+    from sfm_amd.driver import _p, _ptr_array
+    h = _lib.get_handle(0)
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0)
+    g = np.load(os.path.join(ROOT, "tests", "golden", "bunny_pairs.npz"), allow_pickle=False)
+    off = g["offsets"]
+    shipped = ([g["pts1"][off[s]:off[s + 1]] for s in range(len(off) - 1)], [g["pts2"][off[s]:off[s + 1]] for s in range(len(off) - 1)])
+    results = []
+    for name, (p1, p2) in (("shipped_148_pairs", shipped), ("synthetic_630_pairs_x_300", _synthetic_pairs(rng, 630, 300))):
+        n_seg = len(p1)
+        lengths = [len(a) for a in p1]
+        n = int(sum(lengths))
+        _, ptr = _ptr_array(lengths, dev)
+        d1 = torch.from_numpy(np.concatenate(p1).astype(np.float32)).to(dev)
+        d2 = torch.from_numpy(np.concatenate(p2).astype(np.float32)).to(dev)
+        smp = torch.empty((n_seg, n_hyp, 7), dtype=torch.int32, device=dev)
+        h.call("sfm_fund_draw_samples", _p(ptr), n_seg, n_hyp, C.c_uint64(0), _p(smp))
+        need = C.c_int64(); h.lib.sfm_fund_workspace_bytes(n, n_seg, n_hyp, C.byref(need))
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        F = torch.empty((n_seg, 9), dtype=torch.float64, device=dev)
+        mask = torch.empty(n, dtype=torch.uint8, device=dev)
+        meta = torch.empty((3, n_seg), dtype=torch.int32, device=dev)
+
+        def ransac(refine=1):
+            h.call("sfm_fund_ransac", _p(ptr), n_seg, _p(d1), _p(d2), n, _p(smp), n_hyp, C.c_double(3.0), refine, _p(F),
+                   _p(mask), _p(meta[0]), _p(meta[1]), C.c_void_p(0), _p(meta[2]), _p(ws), need.value)
+        for _ in range(3):
+            ransac()
+        sec = timed(ransac, reps)
+        sec_plain = timed(lambda: ransac(0), reps)
+        h.set_profiling(True); h.profile()
+        for _ in range(reps):
+            ransac()
+        ms, launches = h.profile()["fund_hyp"]
+        h.set_profiling(False)
+        k_sec = ms * 1e-3 / max(launches, 1)
+        tests = float(n) * n_hyp * 3                     # pairs x hypotheses x candidates x points, summed over the pairs
+        r = {"kernel": "fund_ransac", "case": name, "pairs": n_seg, "matches": n, "hypotheses": n_hyp,
+             "ms_call_with_refit": sec * 1e3, "ms_call_without_refit": sec_plain * 1e3, "ms_k_fund_hypotheses": k_sec * 1e3,
+             "candidate_point_tests_per_s": tests / k_sec, "flop_per_test": FUND_FLOP_PER_TEST,
+             "fp64_flop_per_s_scoring": FUND_FLOP_PER_TEST * tests / k_sec,
+             "pairs_with_model": int((meta[1] == 0).sum().item()), "refit_kept": int(meta[2].sum().item())}
+        results.append(r)
+        if emit:
+            emit(r)
+
+    # the step this one follows: the batched matcher over the same 630 pairs, two launches, descriptors resident
+    n_img, n_desc, dim = 36, 500, 128
+    descs = [rng.integers(0, 256, (n_desc, dim)).astype(np.uint8) for _ in range(n_img)]
+    pairs = [(i, j) for i in range(n_img) for j in range(i + 1, n_img)]
+    rows, ptr_h, dim = matcher._upload_sets(descs, dev)
+    q_beg = np.array([ptr_h[i] for i, _ in pairs], dtype=np.int64); q_end = np.array([ptr_h[i + 1] for i, _ in pairs], dtype=np.int64)
+    t_beg = np.array([ptr_h[j] for _, j in pairs], dtype=np.int64); t_end = np.array([ptr_h[j + 1] for _, j in pairs], dtype=np.int64)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    n_out, need = C.c_int64(), C.c_int64()
+    n_rows, n_seg, code = int(rows.shape[0]), len(pairs), _lib.METRIC_L2_U8
+    h.check(h.lib.sfm_match_batched_workspace_bytes(code, n_seg, hp(q_beg), hp(q_end), hp(t_beg), hp(t_end), n_rows, n_rows,
+                                                    C.byref(n_out), C.byref(need)), "sfm_match_batched_workspace_bytes")
+    nq = n_out.value
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    i1, i2, qi, ti = (torch.empty(nq, dtype=torch.int32, device=dev) for _ in range(4))
+    e1, e2, dd = (torch.empty(nq, dtype=torch.float32, device=dev) for _ in range(3))
+    out_ptr = torch.empty(n_seg + 1, dtype=torch.int64, device=dev); seg_ptr = torch.empty(n_seg + 1, dtype=torch.int64, device=dev)
+
+    def match():
+        h.call("sfm_match_knn2_batched", code, _p(rows), n_rows, _p(rows), n_rows, dim, n_seg, hp(q_beg), hp(q_end), hp(t_beg),
+               hp(t_end), _p(i1), _p(i2), _p(e1), _p(e2), _p(out_ptr), _p(ws), need.value)
+        h.call("sfm_match_ratio_batched", nq, n_seg, _p(out_ptr), _p(i1), _p(e1), _p(e2), C.c_double(0.75), _p(qi), _p(ti),
+               _p(dd), _p(seg_ptr), _p(ws), need.value)
+    for _ in range(3):
+        match()
+    sec = timed(match, reps)
+    r = {"kernel": "match_pairs_device", "pairs": n_seg, "images": n_img, "descriptors_per_image": n_desc, "dim": dim,
+         "ms": sec * 1e3, "note": "knn2_batched + ratio_batched, descriptors resident: the step sfm_fund_ransac follows"}
+    results.append(r)
+    if emit:
+        emit(r)
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--tracks", type=int, default=100000)
     ap.add_argument("--corr", type=int, default=20000)
+    ap.add_argument("--fundamental-only", action="store_true", help="only the fundamental-matrix RANSAC rows")
     a = ap.parse_args()
-    measure(a.reps, a.tracks, a.corr, emit=lambda d: print(json.dumps(d), flush=True))
+    emit = lambda d: print(json.dumps(d), flush=True)
+    if not a.fundamental_only:
+        measure(a.reps, a.tracks, a.corr, emit=emit)
+    measure_fundamental(a.reps, emit=emit)
 
 
 if __name__ == "__main__":

@@ -57,7 +57,8 @@ enum { SFM_PROF_LIN_OBS = 0,   /* k_lin_obs: residual + Jacobian + Huber scaling
        SFM_PROF_KNN = 8,       /* matcher distance + top-2 kernel */
        SFM_PROF_SCHUR_ITEMS = 9, /* k_schur_items alone (inside SFM_PROF_SCHUR) */
        SFM_PROF_FUND_HYP = 10, /* k_fund_hypotheses alone (inside sfm_fund_ransac) */
-       SFM_PROF_COUNT = 11 };
+       SFM_PROF_PNP_HYP = 11,  /* k_pnp_hypotheses alone (inside sfm_pnp_ransac) */
+       SFM_PROF_COUNT = 12 };
 int sfm_set_profiling(sfm_handle h, int enabled);
 int sfm_profile_read(sfm_handle h, int slot, double* total_ms_host, int64_t* count_host);
 
@@ -426,6 +427,38 @@ int sfm_fund_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, const f
                     int64_t n, const int32_t* samples, int32_t n_hyp, double threshold, int32_t refine,
                     double* F, uint8_t* mask, int32_t* n_inliers, int32_t* status, int32_t* hyp_count,
                     int32_t* refined, void* workspace, int64_t workspace_bytes);
+
+/* ------------------------------------------------------------------ PnP RANSAC, batched over candidate images
+ * The camera-registration step of the reference's add_new_image (`pnp_ransac`: cv2.solvePnPRansac with 1,000
+ * iterations, 8 px, SOLVEPNP_ITERATIVE), for every candidate image of a step in one call; one segment = one image.
+ * Structure as OpenCV's solvePnPRansac is recalled (not pinned): EPnP on samples of 5 inside the loop, reprojection
+ * error against the threshold, most inliers wins, then the ITERATIVE (Levenberg-Marquardt) solver on the inliers.
+ * Deviations, on purpose: minimal samples of 3 solved by closed-form P3P with all of its (up to four) roots scored;
+ * every one of the n_hyp hypotheses runs (no early exit on confidence); the samples are data, drawn by the stateless
+ * integer hash of sfm_fund_draw_samples with 3 slots, or supplied by the caller.  The result is a function of
+ * (points, K, samples) alone, bitwise.
+ * All arithmetic float64.  seg_ptr [n_seg+1] device int64; X [n][3] float64 world points; uv [n][2] float32 pixels;
+ * Kseg [n_seg][4] float64 (fx, fy, cx, cy).  Inlier rule, without division: p = K [R|t] [X; 1], inlier when p2 > 0
+ * and (p0 - u p2)^2 + (p1 - v p2)^2 <= threshold^2 p2^2; best model = most inliers (ties: lowest hypothesis index,
+ * then lowest root slot).  A point with a NaN or infinite coordinate is never an inlier; a sample that holds one, or
+ * whose three world points span no area (|d1 x d2|^2 <= 1e-20 |d1|^2 |d2|^2), gives no model; a sample index
+ * outside its segment voids that hypothesis.
+ *
+ * samples [n_seg][n_hyp][3] int32, segment-local indices, 3 distinct per hypothesis (-1 for segments with fewer
+ * than 4 points).  status [n_seg]: 0 ok, 1 fewer than 4 points, 2 no sample gave a model; status 1 / 2 segments get
+ * Rt = 0, an all-zero mask and count 0.  Rt [n_seg][12]: row-major 3 x 4 [R|t].  hyp_count [n_seg][n_hyp] (may be
+ * NULL): per hypothesis the best inlier count of its candidates.  refine != 0: Levenberg-Marquardt on (rvec, t) -
+ * the rotation vector taken about the current rotation - over the winner's inliers, at most 30 steps, re-scored
+ * over all points with the same rule; it replaces the winner only if its count is not lower (refined[s] = 1 then;
+ * refined may be NULL).  Everything runs on the handle's stream without host synchronisation. */
+int sfm_pnp_workspace_bytes(int64_t n_points, int32_t n_seg, int32_t n_hyp, int64_t* bytes_host);
+int sfm_pnp_draw_samples(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, int32_t n_hyp, uint64_t seed,
+                         int32_t* samples);
+int sfm_pnp_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, const double* X, const float* uv, int64_t n,
+                   const double* Kseg, const int32_t* samples, int32_t n_hyp, double threshold, int32_t refine,
+                   double* Rt /* [n_seg][12], row-major [R|t] */, uint8_t* mask, int32_t* n_inliers, int32_t* status,
+                   int32_t* hyp_count /* may be NULL */, int32_t* refined /* may be NULL */, void* workspace,
+                   int64_t workspace_bytes);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,8 @@
 // own, stateless sample generator, so that the result is a function of (points, seed) alone and a NumPy reference
 // can follow the device hypothesis by hypothesis (tests/fundamental_reference.py).
 //
-// Sample generator (k_fund_samples), restated in NumPy by the tests.  All arithmetic is uint64, wrapping:
+// Sample generator (k_fund_samples; draw_distinct<7> of ransac_common.h), restated in NumPy by the tests.  All
+// arithmetic is uint64, wrapping:
 //   mix(z):  z += 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
 //            z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)          (the splitmix64 finaliser)
 //   key  = mix(mix(mix(seed) ^ segment) ^ hypothesis)
@@ -22,29 +23,12 @@
 // statistics and is staged as NaN for the scoring, so it fails every comparison; a sample that holds one gives no
 // model.  Sample indices are range-checked on the device before they index anything.
 #include "common.h"
+#include "ransac_common.h"
 #include <cfloat>
 
 namespace {
 
 constexpr int FUND_CHUNK = 512;      // points per LDS stage of the scoring loop: 512 x 4 doubles = 16 KiB
-constexpr int FUND_MAX_DRAWS = 256;
-
-// segment s as [b, b + M) inside [0, n): seg_ptr is trusted to ascend, the clamps keep a bad one inside the arrays
-__device__ __forceinline__ void seg_range(const int64_t* __restrict__ seg_ptr, int s, int64_t n, int64_t& b, int& M) {
-  int64_t lo = seg_ptr[s], hi = seg_ptr[s + 1];
-  hi = hi < 0 ? 0 : (hi > n ? n : hi);
-  lo = lo < 0 ? 0 : (lo > hi ? hi : lo);
-  const int64_t m = hi - lo;
-  b = lo;
-  M = (int)(m > 0x7fffffffLL ? 0x7fffffffLL : m);
-}
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 __device__ __forceinline__ bool finite4(float2 p, float2 q) {
   return isfinite(p.x) && isfinite(p.y) && isfinite(q.x) && isfinite(q.y);
@@ -64,29 +48,7 @@ __global__ __launch_bounds__(256) void k_fund_samples(const int64_t* __restrict_
     for (int k = 0; k < 7; ++k) samples[g * 7 + k] = -1;
     return;
   }
-  const uint64_t key = mix64(mix64(mix64(seed) ^ (uint64_t)s) ^ (uint64_t)hyp);
-  uint64_t d = 0;
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    int v = -1;
-    while (d < (uint64_t)FUND_MAX_DRAWS) {
-      const int c = (int)(((mix64(key ^ d) >> 32) * (uint64_t)M) >> 32);
-      ++d;
-      bool dup = false;
-#pragma unroll
-      for (int j = 0; j < 7; ++j) dup |= (j < k) && (idx[j] == c);
-      if (!dup) { v = c; break; }
-    }
-    if (v < 0) {                                     // lowest unused index (at most 6 are taken, M >= 7)
-      for (int c = 0; c < 7 && v < 0; ++c) {
-        bool dup = false;
-#pragma unroll
-        for (int j = 0; j < 7; ++j) dup |= (j < k) && (idx[j] == c);
-        if (!dup) v = c;
-      }
-    }
-    idx[k] = v;
-  }
+  draw_distinct<7>(seed, s, hyp, M, idx);
 #pragma unroll
   for (int k = 0; k < 7; ++k) samples[g * 7 + k] = idx[k];
 }
@@ -286,37 +248,12 @@ __global__ __launch_bounds__(256) void k_fund_hypotheses(const int64_t* __restri
     ok = ok && isfinite(cmax) && (c0 == c0) && (c1 == c1) && (c2 == c2) && (c3 == c3) && !(fabs(c3) < 1e-14 * cmax);
     // monic x^3 + A x^2 + B x + C: closed form (trigonometric / Cardano), then two Newton steps on the monic cubic
     const double A = c2 / c3, B = c1 / c3, Cc = c0 / c3;
-    const double Q = (A * A - 3.0 * B) / 9.0, R = (2.0 * A * A * A - 9.0 * A * B + 27.0 * Cc) / 54.0;
-    const double Q3 = Q * Q * Q;
     double root[3];
-    int nr;
-    if (R * R < Q3) {
-      const double sq = sqrt(Q);
-      double ct = R / (sq * sq * sq);
-      ct = ct < -1.0 ? -1.0 : (ct > 1.0 ? 1.0 : ct);
-      const double th = acos(ct);
-      const double two_pi = 6.283185307179586476925286766559;
-      root[0] = -2.0 * sq * cos(th / 3.0) - A / 3.0;                 // ascending for th in [0, pi]
-      root[1] = -2.0 * sq * cos((th + 2.0 * two_pi) / 3.0) - A / 3.0;
-      root[2] = -2.0 * sq * cos((th + two_pi) / 3.0) - A / 3.0;
-      nr = 3;
-    } else {
-      const double e = cbrt(fabs(R) + sqrt(R * R - Q3));
-      const double aa = R > 0.0 ? -e : e;
-      const double bb = aa != 0.0 ? Q / aa : 0.0;
-      root[0] = aa + bb - A / 3.0; root[1] = 0.0; root[2] = 0.0;
-      nr = 1;
-    }
+    int nr = cubic_roots_monic(A, B, Cc, root);
     if (!ok) nr = 0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      double x = root[k];
-#pragma unroll
-      for (int it = 0; it < 2; ++it) {
-        const double fx = ((x + A) * x + B) * x + Cc, dx = (3.0 * x + 2.0 * A) * x + B;
-        const double xn = x - fx / dx;
-        x = (dx != 0.0 && isfinite(xn)) ? xn : x;
-      }
+      const double x = cubic_newton2(root[k], A, B, Cc);
       double fn[9], f[9];
 #pragma unroll
       for (int e = 0; e < 9; ++e) fn[e] = x * f1[e] + (1.0 - x) * f2[e];

@@ -16,6 +16,7 @@ import numpy as np
 
 from .driver import DriverMixin
 from .interchange import ReconstructionIOMixin
+from .pnp import PnPMixin
 from .rotation import rodrigues, log_so3
 
 BUNDLE_ADJUST_FREQUENCY = 7      # sfm_reconstruction.py:19 (used by the reference's driver loop)
@@ -203,10 +204,10 @@ class BundleAdjustMixin:
                 'num_points': n_pts, 'num_cameras': n_cams}
 
 
-class StructureFromMotion(BundleAdjustMixin, DriverMixin, ReconstructionIOMixin):
+class StructureFromMotion(BundleAdjustMixin, DriverMixin, PnPMixin, ReconstructionIOMixin):
     """Minimal stand-alone holder of the reconstruction state (sfm_reconstruction.py:40-59) for
-    users who only need the hot path and the driver steps either side of it (sfm_amd.driver); the
-    incremental driver loop itself stays the reference's."""
+    users who only need the hot path, the driver steps either side of it (sfm_amd.driver) and the camera
+    registration (sfm_amd.pnp); the incremental driver loop itself stays the reference's."""
 
     def __init__(self, data_dir=None, order="reference", cam_dim=10, device=0, precision="fp64"):
         self.data_dir = Path(data_dir) if data_dir is not None else None

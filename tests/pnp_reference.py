@@ -1,0 +1,245 @@
+"""NumPy float64 reference of the batched PnP RANSAC (sfm_amd/csrc/pnp.hip), taking the samples as input, plus the
+3-slot restatement of the sample generator and the synthetic views the tests share.
+
+It is a reference for the tests, not a second implementation to fall back to, and not the kernel's algebra restated:
+the kernel intersects the conics of the depth pencil (one cubic root, two quadratics, Newton polish, frame-to-frame
+pose); here the depths come from Grunert's quartic through np.roots and the pose from a rigid alignment of the three
+points by SVD.
+
+    bearings   f = normalise(K^-1 [u, v, 1])
+    inlier     p = K [R|t] [X; 1]:  p2 > 0  and  (p0 - u p2)^2 + (p1 - v p2)^2 <= thr^2 p2^2     (no division)
+    degenerate sample (no model):  |(P1-P0) x (P2-P0)|^2 <= 1e-20 |P1-P0|^2 |P2-P0|^2, or a non-finite coordinate
+"""
+import numpy as np
+
+from fundamental_reference import K_REF, MAX_DRAWS, mix64
+
+_U = np.uint64
+
+
+# ------------------------------------------------------------------------------------------- the generator
+def draw_samples(seed, segment, n_points, n_hyp):
+    """[n_hyp, 3] int32: the samples k_pnp_samples draws for segment `segment` holding `n_points` points (all -1 when
+    it has fewer than 4).  A function of (seed, segment, hypothesis) and n_points only."""
+    out = np.full((n_hyp, 3), -1, dtype=np.int32)
+    if n_points < 4:
+        return out
+    hyp = np.arange(n_hyp, dtype=np.uint64)
+    key = mix64(mix64(mix64(np.array([seed], dtype=np.uint64)) ^ _U(segment)) ^ hyp)
+    d = np.zeros(n_hyp, dtype=np.uint64)
+    for k in range(3):
+        pending = np.ones(n_hyp, dtype=bool)
+        while True:
+            pending &= d < MAX_DRAWS
+            if not pending.any():
+                break
+            i = np.flatnonzero(pending)
+            c = (((mix64(key[i] ^ d[i]) >> _U(32)) * _U(n_points)) >> _U(32)).astype(np.int32)
+            d[i] += _U(1)
+            dup = (out[i, :k] == c[:, None]).any(axis=1)
+            out[i[~dup], k] = c[~dup]
+            pending[i[~dup]] = False
+        for h in np.flatnonzero(out[:, k] < 0):          # draws exhausted: the lowest unused index
+            out[h, k] = min(set(range(3)) - set(out[h, :k].tolist()))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ geometry
+def k_matrix(k4):
+    fx, fy, cx, cy = (float(v) for v in k4)
+    return np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1.0]])
+
+
+def bearings(uv, K):
+    """Unit rays of pixels uv [M,2] through K."""
+    uv = np.asarray(uv, dtype=np.float64).reshape(-1, 2)
+    f = np.stack([(uv[:, 0] - K[0, 2]) / K[0, 0], (uv[:, 1] - K[1, 2]) / K[1, 1], np.ones(len(uv))], 1)
+    with np.errstate(invalid="ignore"):
+        return f / np.linalg.norm(f, axis=1)[:, None]
+
+
+def degenerate(P):
+    """The rule of the kernel: a triangle without area, or a non-finite coordinate, gives no model."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        d1, d2 = P[1] - P[0], P[2] - P[0]
+        n = np.cross(d1, d2)
+        return not (n @ n > 1e-20 * (d1 @ d1) * (d2 @ d2))
+
+
+def _polish_depths(s, P, f):
+    """Three Newton steps on |s_i f_i - s_j f_j|^2 = |P_i - P_j|^2 (np.linalg.solve).  The quartic's roots lose
+    digits when the triangle is small against its distance (all four roots crowd near 1: the shipped scene), and the
+    congruence test below would then drop a correct pose."""
+    pairs = ((0, 1), (0, 2), (1, 2))
+    for _ in range(3):
+        g = np.array([((s[i] * f[i] - s[j] * f[j]) ** 2).sum() - ((P[i] - P[j]) ** 2).sum() for i, j in pairs])
+        J = np.zeros((3, 3))
+        for r, (i, j) in enumerate(pairs):
+            J[r, i] = 2 * (s[i] - (f[i] @ f[j]) * s[j])
+            J[r, j] = 2 * (s[j] - (f[i] @ f[j]) * s[i])
+        try:
+            step = np.linalg.solve(J, g)
+        except np.linalg.LinAlgError:
+            break
+        if not np.isfinite(step).all():
+            break
+        s = s - step
+    return s
+
+
+def p3p(P, f):
+    """P [3,3] world points, f [3,3] unit bearings -> list of up to four (R, t) with depth_i f_i = R P_i + t.
+    Grunert's quartic in v = s3 / s1 (as in Haralick et al., "Review and analysis of solutions of the three point
+    perspective pose estimation problem", 1994), u = s2 / s1 from v, the depths polished by Newton on the three
+    distance equations, then the rigid motion of the three points.  A root is taken as real when
+    |imag| <= 1e-7 (1 + |real|); a candidate is kept when both ratios and the depths are positive and the aligned
+    triangle meets the three camera points within 1e-6 of their size."""
+    P = np.asarray(P, dtype=np.float64)
+    f = np.asarray(f, dtype=np.float64)
+    if not (np.isfinite(P).all() and np.isfinite(f).all()) or degenerate(P):
+        return []
+    a2, b2, c2 = ((P[1] - P[2]) ** 2).sum(), ((P[0] - P[2]) ** 2).sum(), ((P[0] - P[1]) ** 2).sum()
+    ca, cb, cg = f[1] @ f[2], f[0] @ f[2], f[0] @ f[1]
+    k1, k2, k3, k4 = (a2 - c2) / b2, (a2 + c2) / b2, (b2 - c2) / b2, (b2 - a2) / b2
+    A4 = (k1 - 1) ** 2 - 4 * c2 / b2 * ca * ca
+    A3 = 4 * (k1 * (1 - k1) * cb - (1 - k2) * ca * cg + 2 * c2 / b2 * ca * ca * cb)
+    A2 = 2 * (k1 * k1 - 1 + 2 * k1 * k1 * cb * cb + 2 * k3 * ca * ca - 4 * k2 * ca * cb * cg + 2 * k4 * cg * cg)
+    A1 = 4 * (-k1 * (1 + k1) * cb + 2 * a2 / b2 * cg * cg * cb - (1 - k2) * ca * cg)
+    A0 = (1 + k1) ** 2 - 4 * a2 / b2 * cg * cg
+    co = np.array([A4, A3, A2, A1, A0])
+    if not np.isfinite(co).all() or abs(A4) < 1e-14 * np.abs(co).max():
+        return []
+    out = []
+    for v in np.roots(co):
+        if abs(v.imag) > 1e-7 * (1 + abs(v.real)):
+            continue
+        v = v.real
+        den = 2 * (cg - v * ca)
+        if v <= 0 or den == 0:
+            continue
+        u = ((k1 - 1) * v * v - 2 * k1 * cb * v + 1 + k1) / den
+        d = 1 + v * v - 2 * v * cb
+        if u <= 0 or d <= 0:
+            continue
+        s1 = np.sqrt(b2 / d)
+        s = _polish_depths(np.array([s1, u * s1, v * s1]), P, f)
+        if not (s > 0).all():
+            continue
+        Q = f * s[:, None]
+        pc, qc = P.mean(0), Q.mean(0)
+        U, _, Vt = np.linalg.svd((Q - qc).T @ (P - pc))                 # Kabsch: the points are coplanar, so the
+        R = U @ np.diag([1.0, 1.0, np.linalg.det(U @ Vt)]) @ Vt           # third direction is fixed by det = +1
+        t = qc - R @ pc
+        if np.abs(P @ R.T + t - Q).max() > 1e-6 * np.abs(Q).max():
+            continue
+        out.append((R, t))
+    return out[:4]
+
+
+def projection(K, R, t):
+    return K @ np.c_[R, np.asarray(t, dtype=np.float64).reshape(3)]
+
+
+def inliers(K, R, t, X, uv, threshold):
+    """The kernel's rule, without division; a non-finite point fails it."""
+    Pm = projection(K, R, t)
+    with np.errstate(invalid="ignore", over="ignore"):
+        p = X @ Pm[:, :3].T + Pm[:, 3]
+        e0, e1 = p[:, 0] - uv[:, 0] * p[:, 2], p[:, 1] - uv[:, 1] * p[:, 2]
+        return (p[:, 2] > 0) & (e0 * e0 + e1 * e1 <= threshold * threshold * p[:, 2] * p[:, 2])
+
+
+def residuals(x, K, X, uv):
+    """Reprojection residuals [2k] of the pose x = (rvec, t) in pixels."""
+    from sfm_amd.rotation import rodrigues
+    p = X @ rodrigues(x[:3]).T + x[3:6]
+    return np.r_[K[0, 0] * p[:, 0] / p[:, 2] + K[0, 2] - uv[:, 0], K[1, 1] * p[:, 1] / p[:, 2] + K[1, 2] - uv[:, 1]]
+
+
+def cost(K, R, t, X, uv):
+    """Summed squared reprojection error of (R, t) over the given points."""
+    from sfm_amd.rotation import log_so3
+    return float((residuals(np.r_[log_so3(R), np.asarray(t).reshape(3)], K, X, uv) ** 2).sum())
+
+
+def refit(K, R, t, X, uv):
+    from scipy.optimize import least_squares
+    from sfm_amd.rotation import log_so3, rodrigues
+    o = least_squares(residuals, np.r_[log_so3(R), np.asarray(t).reshape(3)], args=(K, X, uv), method="lm",
+                      xtol=1e-14, ftol=1e-14)
+    return rodrigues(o.x[:3]), o.x[3:6].copy()
+
+
+def ransac(X, uv, K, samples, threshold=8.0, refine=False):
+    """Follows the device for one segment on given samples [H,3].  Returns a dict: `hyp_count` [H] (best candidate
+    count per hypothesis), `status` (0 ok, 1 fewer than 4 points, 2 no model), `R`, `t` (or None), `mask` [M] bool,
+    `n_inliers`, `refined`, `winner` (hypothesis index) and `cand_count` [H,4]."""
+    X = np.asarray(X, dtype=np.float64).reshape(-1, 3)
+    uv = np.asarray(uv, dtype=np.float64).reshape(-1, 2)
+    K = np.asarray(K, dtype=np.float64)
+    M, H = len(X), len(samples)
+    res = {"hyp_count": np.zeros(H, np.int32), "status": 1, "R": None, "t": None, "mask": np.zeros(M, bool),
+           "n_inliers": 0, "refined": False, "winner": -1, "cand_count": np.zeros((H, 4), np.int32)}
+    if M < 4:
+        return res
+    f = bearings(uv, K)
+    cnt = np.zeros((H, 4), np.int32)
+    best = (0, None)
+    for h, s in enumerate(np.asarray(samples, dtype=np.int64)):
+        for k, (R, t) in enumerate(p3p(X[s], f[s])):
+            cnt[h, k] = inliers(K, R, t, X, uv, threshold).sum()
+            if cnt[h, k] > best[0]:                      # first maximum: lowest hypothesis, then lowest candidate
+                best = (int(cnt[h, k]), (h, R, t))
+    res["cand_count"] = cnt
+    res["hyp_count"] = cnt.max(1).astype(np.int32)
+    res["status"] = 2
+    if best[0] == 0:
+        return res
+    h, R, t = best[1]
+    mask = inliers(K, R, t, X, uv, threshold)
+    res.update(status=0, R=R, t=t, mask=mask, n_inliers=int(mask.sum()), winner=int(h))
+    if refine and mask.sum() >= 3:                       # 6 residuals for 6 unknowns, as the kernel asks
+        Rr, tr = refit(K, R, t, X[mask], uv[mask])
+        if np.isfinite(Rr).all() and np.isfinite(tr).all():
+            mr = inliers(K, Rr, tr, X, uv, threshold)
+            if mr.sum() >= mask.sum():
+                res.update(R=Rr, t=tr, mask=mr, n_inliers=int(mr.sum()), refined=True)
+    return res
+
+
+def stable(X, uv, K, samples, threshold=8.0):
+    """[H] bool: True where hyp_count does not change when X is replaced by X (1 + 1e-13 N(0,1)), for two fixed-seed
+    replays.  A hypothesis near a double root gains or loses a candidate under such a change; comparing it with the
+    device would compare rounding."""
+    X = np.asarray(X, dtype=np.float64).reshape(-1, 3)
+    base = ransac(X, uv, K, samples, threshold)["hyp_count"]
+    ok = np.ones(len(samples), bool)
+    for rep in range(2):
+        rng = np.random.default_rng(77 + rep)
+        ok &= ransac(X * (1 + 1e-13 * rng.standard_normal(X.shape)), uv, K, samples, threshold)["hyp_count"] == base
+    return ok
+
+
+# ---------------------------------------------------------------------------------------- synthetic views
+CASES = [(3, 0.0), (4, 0.0), (40, 0.3), (300, 0.3), (300, 0.6), (2000, 0.5)]       # (M, outlier share), ONE batch
+
+
+def synth_view(rng, M, outlier_share=0.0, noise=0.5):
+    """Points in a box in front of a camera with the reference's K; the first int(M * outlier_share) pixels are
+    replaced by uniform ones.  Returns X [M,3] float64, uv [M,2] float32 and the true R, t."""
+    X = rng.uniform(-1, 1, (M, 3)) + [0, 0, 6.0]
+    yaw = 0.25
+    R = np.array([[np.cos(yaw), 0, np.sin(yaw)], [0, 1, 0], [-np.sin(yaw), 0, np.cos(yaw)]])
+    t = np.array([-1.5, 0.1, 0.3])
+    x = (X @ R.T + t) @ K_REF.T
+    x = x[:, :2] / x[:, 2:]
+    if noise:
+        x = x + rng.normal(size=x.shape) * noise
+    k = int(M * outlier_share)
+    x[:k] = rng.uniform(0, 1, (k, 2)) * [1024, 768]
+    return X, x.astype(np.float32), R, t
+
+
+def synth_batch():
+    out = [synth_view(np.random.default_rng(1000 * M + int(100 * share)), M, share) for M, share in CASES]
+    return [o[0] for o in out], [o[1] for o in out], [o[2] for o in out], [o[3] for o in out]

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Device-time measurement of the driver-row kernels with inputs resident in HBM:
 association (pair tests/s), two-view triangulation (tracks/s), epipolar verification (matches/s), and the batched
-fundamental-matrix RANSAC beside the batched matcher it follows in the pair loop.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
+fundamental-matrix RANSAC beside the batched matcher it follows in the pair loop, and the batched PnP RANSAC of the
+camera registration.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
 functions to time on a bounded sample of the same inputs (this tool itself never imports oracle/).
-usage: python tools/bench_driver.py [--reps 20] [--fundamental-only]"""
+usage: python tools/bench_driver.py [--reps 20] [--fundamental-only | --pnp-only]"""
 import argparse
 import ctypes as C
 import json
@@ -233,6 +234,74 @@ def measure_fundamental(reps=20, n_hyp=1024, emit=None):
         emit(r)
     return results
 
+PNP_FLOP_PER_TEST = 30       # 9 fma for p = P [X; 1], 2 fma + 1 fma + 1 mul for the error, 2 mul for thr^2 p2^2 (fma = 2)
+
+
+def measure_pnp(reps=20, n_hyp=1024, emit=None):
+    """sfm_pnp_ransac on (a) the 4 shipped 2D-3D match sets (images 3, 12, 20, 33) and (b) 64 synthetic segments of 1,000
+    points with 40 % outliers, inputs resident in HBM: the whole call with and without the refinement (HIP events around
+    `reps` calls) and k_pnp_hypotheses alone (the handle's event slot)."""
+    import torch
+    from sfm_amd import _lib
+    from sfm_amd.driver import _p, _ptr_array
+    h = _lib.get_handle(0)
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0)
+    g = np.load(os.path.join(ROOT, "tests", "golden", "driver_bunny.npz"), allow_pickle=False)
+    shipped = ([g[f"f{im}_points3D"] for im in g["f_images"]], [g[f"f{im}_points2D"] for im in g["f_images"]])
+    K = np.array([1228.0, 1228.0, 512.0, 384.0])
+    X3, x2 = [], []
+    for s in range(64):
+        yaw = rng.uniform(-0.4, 0.4)
+        R = np.array([[np.cos(yaw), 0, np.sin(yaw)], [0, 1, 0], [-np.sin(yaw), 0, np.cos(yaw)]])
+        X = rng.uniform(-1, 1, (1000, 3)) + [0, 0, 6.0]
+        p = X @ R.T + rng.uniform(-1, 1, 3) * [1.5, 0.3, 0.3]
+        x = p[:, :2] / p[:, 2:] * K[:2] + K[2:] + rng.normal(size=(1000, 2)) * 0.5
+        x[:400] = rng.uniform(0, 1, (400, 2)) * [1024, 768]
+        X3.append(X); x2.append(x.astype(np.float32))
+    results = []
+    for name, (p3, p2) in (("shipped_4_images", shipped), ("synthetic_64_segments_x_1000", (X3, x2))):
+        n_seg = len(p3)
+        lengths = [len(a) for a in p3]
+        n = int(sum(lengths))
+        _, ptr = _ptr_array(lengths, dev)
+        dX = torch.from_numpy(np.concatenate(p3).astype(np.float64)).to(dev)
+        duv = torch.from_numpy(np.concatenate(p2).astype(np.float32)).to(dev)
+        dK = torch.from_numpy(np.tile(K, (n_seg, 1))).to(dev)
+        smp = torch.empty((n_seg, n_hyp, 3), dtype=torch.int32, device=dev)
+        h.call("sfm_pnp_draw_samples", _p(ptr), n_seg, n_hyp, C.c_uint64(0), _p(smp))
+        need = C.c_int64(); h.lib.sfm_pnp_workspace_bytes(n, n_seg, n_hyp, C.byref(need))
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        Rt = torch.empty((n_seg, 12), dtype=torch.float64, device=dev)
+        mask = torch.empty(n, dtype=torch.uint8, device=dev)
+        meta = torch.empty((3, n_seg), dtype=torch.int32, device=dev)
+
+        def ransac(refine=1):
+            h.call("sfm_pnp_ransac", _p(ptr), n_seg, _p(dX), _p(duv), n, _p(dK), _p(smp), n_hyp, C.c_double(8.0), refine,
+                   _p(Rt), _p(mask), _p(meta[0]), _p(meta[1]), C.c_void_p(0), _p(meta[2]), _p(ws), need.value)
+        for _ in range(3):
+            ransac()
+        sec = timed(ransac, reps)
+        sec_plain = timed(lambda: ransac(0), reps)
+        ransac()
+        h.set_profiling(True); h.profile()
+        for _ in range(reps):
+            ransac()
+        ms, launches = h.profile()["pnp_hyp"]
+        h.set_profiling(False)
+        k_sec = ms * 1e-3 / max(launches, 1)
+        tests = float(n) * n_hyp * 4                     # segments x hypotheses x candidate slots x points
+        r = {"kernel": "pnp_ransac", "case": name, "segments": n_seg, "points": n, "hypotheses": n_hyp,
+             "ms_call_with_refine": sec * 1e3, "ms_call_without_refine": sec_plain * 1e3, "ms_k_pnp_hypotheses": k_sec * 1e3,
+             "candidate_point_tests_per_s": tests / k_sec, "flop_per_test": PNP_FLOP_PER_TEST,
+             "fp64_flop_per_s_scoring": PNP_FLOP_PER_TEST * tests / k_sec,
+             "segments_with_model": int((meta[1] == 0).sum().item()), "refine_kept": int(meta[2].sum().item()),
+             "inliers": [int(v) for v in meta[0].cpu().numpy()[:4]]}
+        results.append(r)
+        if emit:
+            emit(r)
+    return results
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -240,11 +309,15 @@ def main():
     ap.add_argument("--tracks", type=int, default=100000)
     ap.add_argument("--corr", type=int, default=20000)
     ap.add_argument("--fundamental-only", action="store_true", help="only the fundamental-matrix RANSAC rows")
+    ap.add_argument("--pnp-only", action="store_true", help="only the PnP RANSAC rows")
     a = ap.parse_args()
     emit = lambda d: print(json.dumps(d), flush=True)
-    if not a.fundamental_only:
+    if not a.fundamental_only and not a.pnp_only:
         measure(a.reps, a.tracks, a.corr, emit=emit)
-    measure_fundamental(a.reps, emit=emit)
+    if not a.pnp_only:
+        measure_fundamental(a.reps, emit=emit)
+    if not a.fundamental_only:
+        measure_pnp(a.reps, emit=emit)
 
 
 if __name__ == "__main__":

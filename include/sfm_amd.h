@@ -58,7 +58,8 @@ enum { SFM_PROF_LIN_OBS = 0,   /* k_lin_obs: residual + Jacobian + Huber scaling
        SFM_PROF_SCHUR_ITEMS = 9, /* k_schur_items alone (inside SFM_PROF_SCHUR) */
        SFM_PROF_FUND_HYP = 10, /* k_fund_hypotheses alone (inside sfm_fund_ransac) */
        SFM_PROF_PNP_HYP = 11,  /* k_pnp_hypotheses alone (inside sfm_pnp_ransac) */
-       SFM_PROF_COUNT = 12 };
+       SFM_PROF_POSE_VOTE = 12, /* k_pose_vote alone (inside sfm_pose_recover) */
+       SFM_PROF_COUNT = 13 };
 int sfm_set_profiling(sfm_handle h, int enabled);
 int sfm_profile_read(sfm_handle h, int slot, double* total_ms_host, int64_t* count_host);
 
@@ -459,6 +460,35 @@ int sfm_pnp_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, const do
                    double* Rt /* [n_seg][12], row-major [R|t] */, uint8_t* mask, int32_t* n_inliers, int32_t* status,
                    int32_t* hyp_count /* may be NULL */, int32_t* refined /* may be NULL */, void* workspace,
                    int64_t workspace_bytes);
+
+/* ------------------------------------------------------------- relative-pose recovery, batched over image pairs
+ * The cv2.recoverPose(E, pts1, pts2, K) call of the reference's find_best_initial_pair / initialize_reconstruction, for
+ * every pair of a data set in one call; one segment = one pair.  opencv-python 4.11's recoverPose and
+ * decomposeEssentialMat as recalled (not pinned; the reference's shipped run pins this row, tests/pose_reference.py):
+ * float32 pixels widened to double and normalised as (u - cx) / fx, (v - cy) / fy; E = U S V^T with both determinants
+ * +1, R1 = U W V^T, R2 = U W^T V^T, t = U[:, 2]; the candidates [R1|t], [R2|t], [R1|-t], [R2|-t] each triangulate every
+ * point against [I|0] by the DLT of sfm_triangulate2; a point is good when Q.z Q.w > 0, X.z < dist and 0 < z2 < dist
+ * (X = Q / Q.w, z2 its depth in the second camera) and its byte of mask_in is not zero; a point with a NaN or infinite
+ * coordinate is never good.  The winner is the FIRST candidate with the largest count.  The order of the four
+ * candidates follows the sign choices of this library's own decomposition, not cv2's: a tie may go to another
+ * candidate than cv2's.
+ *
+ * seg_ptr [n_seg+1] device int64; pts1 / pts2 [n][2] float32 pixels; EorF [n_seg][9] float64 row-major: essential
+ * matrices, or with is_fundamental != 0 fundamental matrices (E = K^T F K is formed on the device); Kseg [n_seg][4]
+ * float64 (fx, fy, cx, cy).  Outputs: R [n_seg][9], t [n_seg][3], n_good [n_seg], status [n_seg] (0 ok, 1 empty
+ * segment, 2 no model: E not finite or its second singular value not > 0; status 1 / 2 get R = t = 0, n_good = 0),
+ * mask_out [n] (255 / 0: the winner's good points), X [n][3] (may be NULL): the winner's good points triangulated again
+ * in PIXEL coordinates with K [I|0], K [R|t] - what initialize_reconstruction stores - and NaN elsewhere.  Debug
+ * outputs, each may be NULL: cand_count [n_seg][4], cand_pose [n_seg][4][12] (row-major [R|t]; NaN without a model),
+ * winner [n_seg].  Everything runs on the handle's stream without host synchronisation. */
+int sfm_pose_workspace_bytes(int64_t n_points, int32_t n_seg, int64_t* bytes_host);
+int sfm_pose_recover(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, const float* pts1, const float* pts2,
+                     int64_t n, const double* EorF /* [n_seg][9] */, int32_t is_fundamental,
+                     const double* Kseg /* [n_seg][4] */, const uint8_t* mask_in /* may be NULL */, double dist,
+                     double* R, double* t, int32_t* n_good, int32_t* status, uint8_t* mask_out,
+                     double* X /* [n][3], may be NULL */, int32_t* cand_count /* [n_seg][4], may be NULL */,
+                     double* cand_pose /* [n_seg][4][12], may be NULL */, int32_t* winner /* may be NULL */,
+                     void* workspace, int64_t workspace_bytes);
 
 #ifdef __cplusplus
 }

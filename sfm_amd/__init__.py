@@ -1,3 +1,4 @@
 """sfm_amd: MI355X-native matching + bundle-adjustment hot path."""
 
 from .twoview import FundamentalMixin, estimate_fundamental_batched, find_fundamental  # noqa: F401
+from .pose import InitialPairMixin, recover_pose, recover_pose_batched  # noqa: F401

@@ -14,7 +14,7 @@ METRIC_L2_U8, METRIC_L2_F32, METRIC_HAMMING = 0, 1, 2
  SC_XNEW_NORM2, SC_CHOL_FAIL, SC_HDIAG) = range(12)
 SC_COUNT = 16
 PROF_SLOTS = ("lin_obs", "lin_rest", "build_G", "schur", "chol", "trsv", "backsub", "step", "knn", "schur_items",
-              "fund_hyp", "pnp_hyp")
+              "fund_hyp", "pnp_hyp", "pose_vote")
 
 i32, i64, f64, vp = C.c_int32, C.c_int64, C.c_double, C.c_void_p
 
@@ -131,6 +131,8 @@ SIGNATURES = {
     "sfm_pnp_workspace_bytes": (C.c_int, [i64, i32, i32, C.POINTER(i64)]),
     "sfm_pnp_draw_samples": (C.c_int, [vp, vp, i32, i32, C.c_uint64, vp]),
     "sfm_pnp_ransac": (C.c_int, [vp, vp, i32, vp, vp, i64, vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_pose_workspace_bytes": (C.c_int, [i64, i32, C.POINTER(i64)]),
+    "sfm_pose_recover": (C.c_int, [vp, vp, i32, vp, vp, i64, vp, i32, vp, vp, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64]),
 }
 
 _lib = None

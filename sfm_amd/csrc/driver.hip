@@ -6,6 +6,7 @@
 // pair of a driver step (segments) and that the arithmetic is the reference's, operation for operation:
 // no FMA contraction anywhere in this file (NumPy / OpenCV's generic x86 code do not fuse).
 #include "common.h"
+#include "pose_solve.h"
 #include <cfloat>
 
 #pragma clang fp contract(off)
@@ -161,7 +162,8 @@ __global__ __launch_bounds__(256) void k_scan_blocks(int n, const int* __restric
 // One thread per candidate track.  cv2.triangulatePoints (opencv-python 4.11.0) builds, per point, the
 // 4x4 matrix with rows x*P[2]-P[0], y*P[2]-P[1] for both views and takes the right singular vector of the
 // smallest singular value from its one-sided Jacobi SVD; the same Hestenes iteration runs here on the
-// columns of A held in registers (eps = 10*DBL_EPSILON, <= 30 sweeps).
+// columns of A held in registers (eps = 10*DBL_EPSILON, <= 30 sweeps): jacobi::dlt2 of pose_solve.h, shared with the
+// relative-pose kernels (pose.hip).
 __global__ __launch_bounds__(256) void k_triangulate2(const double* __restrict__ proj, const int* __restrict__ cam0,
                                                       const int* __restrict__ cam1, const double2* __restrict__ x0,
                                                       const double2* __restrict__ x1, int64_t n, double max_err,
@@ -177,56 +179,8 @@ __global__ __launch_bounds__(256) void k_triangulate2(const double* __restrict__
     for (int k = 0; k < 12; ++k) { P0[k] = a[k]; P1[k] = b[k]; }
   }
   const double2 p0 = x0[i], p1 = x1[i];
-  double U[4][4], V[4][4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    U[0][k] = p0.x * P0[8 + k] - P0[k];
-    U[1][k] = p0.y * P0[8 + k] - P0[4 + k];
-    U[2][k] = p1.x * P1[8 + k] - P1[k];
-    U[3][k] = p1.y * P1[8 + k] - P1[4 + k];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) V[r][k] = (r == k) ? 1.0 : 0.0;
-  }
-  const double eps = 10.0 * DBL_EPSILON;
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    bool changed = false;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < 4; ++q) {
-        double a = 0.0, b = 0.0, g = 0.0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { a += U[r][p] * U[r][p]; b += U[r][q] * U[r][q]; g += U[r][p] * U[r][q]; }
-        if (fabs(g) > eps * sqrt(a * b)) {
-          changed = true;
-          const double zeta = (b - a) / (2.0 * g);
-          const double tt = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-          const double c = 1.0 / sqrt(1.0 + tt * tt), s = c * tt;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const double up = U[r][p], uq = U[r][q];
-            U[r][p] = c * up - s * uq; U[r][q] = s * up + c * uq;
-            const double vp = V[r][p], vq = V[r][q];
-            V[r][p] = c * vp - s * vq; V[r][q] = s * vp + c * vq;
-          }
-        }
-      }
-    }
-    if (!changed) break;
-  }
-  double best = 0.0;
-  double v[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    double nk = 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) nk += U[r][k] * U[r][k];
-    if (k == 0 || nk < best) {
-      best = nk;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = V[r][k];
-    }
-  }
+  double v[4];
+  jacobi::dlt2(P0, P1, p0.x, p0.y, p1.x, p1.y, v);
   const double Xx = v[0] / v[3], Xy = v[1] / v[3], Xz = v[2] / v[3];
   X[3 * i] = Xx; X[3 * i + 1] = Xy; X[3 * i + 2] = Xz;
   // reprojection gate, sfm_reconstruction.py:298-305

@@ -17,6 +17,7 @@ import numpy as np
 from .driver import DriverMixin
 from .interchange import ReconstructionIOMixin
 from .pnp import PnPMixin
+from .pose import InitialPairMixin
 from .rotation import rodrigues, log_so3
 
 BUNDLE_ADJUST_FREQUENCY = 7      # sfm_reconstruction.py:19 (used by the reference's driver loop)
@@ -204,10 +205,11 @@ class BundleAdjustMixin:
                 'num_points': n_pts, 'num_cameras': n_cams}
 
 
-class StructureFromMotion(BundleAdjustMixin, DriverMixin, PnPMixin, ReconstructionIOMixin):
+class StructureFromMotion(BundleAdjustMixin, DriverMixin, PnPMixin, InitialPairMixin, ReconstructionIOMixin):
     """Minimal stand-alone holder of the reconstruction state (sfm_reconstruction.py:40-59) for
-    users who only need the hot path, the driver steps either side of it (sfm_amd.driver) and the camera
-    registration (sfm_amd.pnp); the incremental driver loop itself stays the reference's."""
+    users who only need the hot path, the driver steps either side of it (sfm_amd.driver), the camera
+    registration (sfm_amd.pnp) and the choice and set-up of the initial pair (sfm_amd.pose); the incremental driver
+    loop itself stays the reference's."""
 
     def __init__(self, data_dir=None, order="reference", cam_dim=10, device=0, precision="fp64"):
         self.data_dir = Path(data_dir) if data_dir is not None else None

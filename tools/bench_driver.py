@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Device-time measurement of the driver-row kernels with inputs resident in HBM:
 association (pair tests/s), two-view triangulation (tracks/s), epipolar verification (matches/s), and the batched
-fundamental-matrix RANSAC beside the batched matcher it follows in the pair loop, and the batched PnP RANSAC of the
-camera registration.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
+fundamental-matrix RANSAC beside the batched matcher it follows in the pair loop, the batched PnP RANSAC of the
+camera registration, and the batched relative-pose recovery of the initial-pair scan.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
 functions to time on a bounded sample of the same inputs (this tool itself never imports oracle/).
-usage: python tools/bench_driver.py [--reps 20] [--fundamental-only | --pnp-only]"""
+usage: python tools/bench_driver.py [--reps 20] [--fundamental-only | --pnp-only | --pose-only]"""
 import argparse
 import ctypes as C
 import json
@@ -303,6 +303,87 @@ def measure_pnp(reps=20, n_hyp=1024, emit=None):
     return results
 
 
+def _synthetic_pose_pairs(rng, n_pairs, M, noise=0.5):
+    """(E [n_pairs,9], pts1, pts2 [n_pairs*M,2] float32): one random two-view geometry per pair with the reference's K,
+    points at depths of 4 to 12 baselines, vectorised (4,950 pairs of 2,000 matches are 9.9 M points)."""
+    fx, cx, cy = 1228.0, 512.0, 384.0
+    w = rng.normal(size=(n_pairs, 3))
+    w *= (rng.uniform(0.05, 0.5, n_pairs) / np.linalg.norm(w, axis=1))[:, None]
+    th = np.linalg.norm(w, axis=1)[:, None, None]
+    Kx = np.zeros((n_pairs, 3, 3))
+    Kx[:, 0, 1], Kx[:, 0, 2], Kx[:, 1, 0] = -w[:, 2], w[:, 1], w[:, 2]
+    Kx[:, 1, 2], Kx[:, 2, 0], Kx[:, 2, 1] = -w[:, 0], -w[:, 1], w[:, 0]
+    Kx /= th
+    R = np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * Kx @ Kx
+    t = rng.normal(size=(n_pairs, 3))
+    t /= np.linalg.norm(t, axis=1)[:, None]
+    tx = np.zeros((n_pairs, 3, 3))
+    tx[:, 0, 1], tx[:, 0, 2], tx[:, 1, 0] = -t[:, 2], t[:, 1], t[:, 2]
+    tx[:, 1, 2], tx[:, 2, 0], tx[:, 2, 1] = -t[:, 0], -t[:, 1], t[:, 0]
+    E = (tx @ R).reshape(n_pairs, 9)
+    z = rng.uniform(4.0, 12.0, (n_pairs, M))
+    X = np.stack([rng.uniform(-0.35, 0.35, (n_pairs, M)) * z, rng.uniform(-0.25, 0.25, (n_pairs, M)) * z, z], axis=2)
+    Y = X @ R.transpose(0, 2, 1) + t[:, None, :]
+    p1 = X[..., :2] / X[..., 2:] * fx + [cx, cy] + rng.normal(size=(n_pairs, M, 2)) * noise
+    p2 = Y[..., :2] / Y[..., 2:] * fx + [cx, cy] + rng.normal(size=(n_pairs, M, 2)) * noise
+    return E, p1.reshape(-1, 2).astype(np.float32), p2.reshape(-1, 2).astype(np.float32)
+
+
+def measure_pose(reps=20, emit=None):
+    """sfm_pose_recover on (a) the 148 shipped pairs (all matched points, E = K^T F K formed on the device) and (b) 4,950
+    synthetic pairs - all pairs of 100 images - of 2,000 matches, inputs resident in HBM: the whole call with and without
+    the pixel-space triangulation (HIP events around `reps` calls) and k_pose_vote alone (the handle's event slot)."""
+    import torch
+    from sfm_amd import _lib
+    from sfm_amd.driver import _p, _ptr_array
+    h = _lib.get_handle(0)
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0)
+    g = np.load(os.path.join(ROOT, "tests", "golden", "bunny_pairs.npz"), allow_pickle=False)
+    cases = [("shipped_148_pairs", g["F"].reshape(-1, 9), g["pts1"], g["pts2"], np.diff(g["offsets"]).tolist(), 1)]
+    n_pairs, M = 4950, 2000
+    E, p1, p2 = _synthetic_pose_pairs(rng, n_pairs, M)
+    cases.append(("synthetic_4950_pairs_x_2000", E, p1, p2, [M] * n_pairs, 0))
+    results = []
+    for name, EF, p1, p2, lengths, is_f in cases:
+        n_seg, n = len(lengths), int(sum(lengths))
+        _, ptr = _ptr_array(lengths, dev)
+        d1 = torch.from_numpy(np.ascontiguousarray(p1, dtype=np.float32)).to(dev)
+        d2 = torch.from_numpy(np.ascontiguousarray(p2, dtype=np.float32)).to(dev)
+        dE = torch.from_numpy(np.ascontiguousarray(EF, dtype=np.float64)).to(dev)
+        dK = torch.from_numpy(np.tile(np.array([1228.0, 1228.0, 512.0, 384.0]), (n_seg, 1))).to(dev)
+        need = C.c_int64(); h.lib.sfm_pose_workspace_bytes(n, n_seg, C.byref(need))
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        R = torch.empty((n_seg, 9), dtype=torch.float64, device=dev); t = torch.empty((n_seg, 3), dtype=torch.float64, device=dev)
+        meta = torch.empty((2, n_seg), dtype=torch.int32, device=dev)
+        mask = torch.empty(n, dtype=torch.uint8, device=dev)
+        X = torch.empty((n, 3), dtype=torch.float64, device=dev)
+
+        def recover(tri=True):
+            h.call("sfm_pose_recover", _p(ptr), n_seg, _p(d1), _p(d2), n, _p(dE), is_f, _p(dK), C.c_void_p(0), C.c_double(50.0),
+                   _p(R), _p(t), _p(meta[0]), _p(meta[1]), _p(mask), _p(X) if tri else C.c_void_p(0), C.c_void_p(0),
+                   C.c_void_p(0), C.c_void_p(0), _p(ws), need.value)
+        for _ in range(3):
+            recover()
+        sec = timed(recover, reps)
+        sec_plain = timed(lambda: recover(False), reps)
+        h.set_profiling(True); h.profile()
+        for _ in range(reps):
+            recover()
+        ms, launches = h.profile()["pose_vote"]
+        h.set_profiling(False)
+        k_sec = ms * 1e-3 / max(launches, 1)
+        r = {"kernel": "pose_recover", "case": name, "pairs": n_seg, "points": n,
+             "ms_call_with_triangulation": sec * 1e3, "ms_call_without_triangulation": sec_plain * 1e3,
+             "ms_k_pose_vote": k_sec * 1e3, "candidate_point_triangulations_per_s": 4.0 * n / k_sec,
+             "pairs_with_model": int((meta[1] == 0).sum().item()), "good_points": int(meta[0].sum().item()),
+             "best_pair_count": int(meta[0].max().item())}
+        results.append(r)
+        if emit:
+            emit(r)
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -310,14 +391,18 @@ def main():
     ap.add_argument("--corr", type=int, default=20000)
     ap.add_argument("--fundamental-only", action="store_true", help="only the fundamental-matrix RANSAC rows")
     ap.add_argument("--pnp-only", action="store_true", help="only the PnP RANSAC rows")
+    ap.add_argument("--pose-only", action="store_true", help="only the relative-pose recovery rows")
     a = ap.parse_args()
     emit = lambda d: print(json.dumps(d), flush=True)
-    if not a.fundamental_only and not a.pnp_only:
+    only = a.fundamental_only or a.pnp_only or a.pose_only
+    if not only:
         measure(a.reps, a.tracks, a.corr, emit=emit)
-    if not a.pnp_only:
+    if a.fundamental_only or not only:
         measure_fundamental(a.reps, emit=emit)
-    if not a.fundamental_only:
+    if a.pnp_only or not only:
         measure_pnp(a.reps, emit=emit)
+    if a.pose_only or not only:
+        measure_pose(a.reps, emit=emit)
 
 
 if __name__ == "__main__":

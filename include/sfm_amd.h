@@ -490,6 +490,34 @@ int sfm_pose_recover(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, const 
                      double* cand_pose /* [n_seg][4][12], may be NULL */, int32_t* winner /* may be NULL */,
                      void* workspace, int64_t workspace_bytes);
 
+/* ------------------------------------------------------------- multi-view feature tracks from pairwise matches
+ * One call joins the matches of all image pairs of a data set into tracks in CSR form.  A node is one keypoint of one
+ * image: id = kp_ptr[image] + keypoint with kp_ptr [n_img+1] device int64 ascending from 0 to n_nodes < 2^31.  Segment s of
+ * seg_ptr [n_seg+1] (device int64, ascending from 0 to n_edges) is the image pair pair_img[s] = (i, j) ([n_seg][2] int32);
+ * edge e of segment s joins (i, query_idx[e]) and (j, train_idx[e]) (int32).  An edge whose byte of mask (may be NULL) is 0
+ * is skipped.  An edge is counted in n_bad_edges, skipped and never followed when i == j, when an image is out of range,
+ * when a keypoint index is outside its image's range, or when it lies in no segment.  Duplicate edges are harmless.
+ *
+ * A track is a connected component with at least min_len (>= 2) nodes.  A component that holds two nodes of one image is
+ * conflicting: policy 0 (drop) removes it, policy 1 (keep) keeps it with track_conflict = 1.  Tracks are numbered by their
+ * smallest node id and the observations of a track ascend by node id: the outputs do not depend on the order of the edges
+ * or of the pairs, bit for bit.
+ *
+ * Outputs (device): track_ptr [cap_tracks+1] int64, obs_image / obs_kp [cap_obs] int32, track_conflict [cap_tracks] uint8,
+ * node_track [n_nodes] int32 (track id; -1 unmatched keypoint; -2 component shorter than min_len; -3 dropped for a
+ * conflict), counts [5] int64: n_tracks, n_obs, n_conflicting (components of at least min_len, whatever the policy),
+ * n_bad_edges, status.  cap_tracks >= n_nodes / 2 and cap_obs >= n_nodes are required (SFM_ERR_ARG otherwise).  Without
+ * nodes or without edges there are no tracks and every node_track entry is -1.  The kernels run on the handle's stream and
+ * nothing is read back between them; the call then waits for the stream and reads the status word once: it is nonzero
+ * only if the union loop exhausted its step budget, which the algorithm excludes, and gives SFM_ERR_NUMERIC. */
+int sfm_tracks_workspace_bytes(int64_t n_nodes, int64_t n_edges, int64_t* bytes_host);
+int sfm_tracks_build(sfm_handle h, const int64_t* kp_ptr, int32_t n_img, int64_t n_nodes, const int64_t* seg_ptr,
+                     int32_t n_seg, const int32_t* pair_img /* [n_seg][2] */, const int32_t* query_idx,
+                     const int32_t* train_idx, const uint8_t* mask /* may be NULL */, int64_t n_edges, int32_t min_len,
+                     int32_t policy, int64_t* track_ptr, int32_t* obs_image, int32_t* obs_kp, uint8_t* track_conflict,
+                     int32_t* node_track, int64_t* counts, int64_t cap_tracks, int64_t cap_obs, void* workspace,
+                     int64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@ PREC_FP64, PREC_MIXED = 0, 1
 SOLVER_DENSE, SOLVER_PCG = 0, 1
 CAMERA_AUTO, CAMERA_CHOLESKY, CAMERA_CG = 0, 1, 2
 UV_AS_GIVEN, UV_REFERENCE_PAIRING = 0, 1
+TRACKS_DROP, TRACKS_KEEP = 0, 1
 
 
 class BADesc(C.Structure):
@@ -133,6 +134,8 @@ SIGNATURES = {
     "sfm_pnp_ransac": (C.c_int, [vp, vp, i32, vp, vp, i64, vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, vp, vp, i64]),
     "sfm_pose_workspace_bytes": (C.c_int, [i64, i32, C.POINTER(i64)]),
     "sfm_pose_recover": (C.c_int, [vp, vp, i32, vp, vp, i64, vp, i32, vp, vp, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_tracks_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
+    "sfm_tracks_build": (C.c_int, [vp, vp, i32, i64, vp, i32, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, i64, vp, i64]),
 }
 
 _lib = None

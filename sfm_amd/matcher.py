@@ -406,3 +406,17 @@ class ImageMatcher(VerificationMixin, FundamentalMixin):
                             "inlier_mask": v["inlier_mask"], "symmetric_errors": v["symmetric_errors"],
                             "metrics": v["metrics"], "quality_ok": self.verify_match_quality(v)}
         return out
+
+    def build_tracks(self, keypoints, pairs, results, min_length=2, conflicts="drop", verified_only=True):
+        """Multi-view tracks (sfm_amd.tracks.Tracks) from what `process_pairs(keypoints, descs, pairs)` returned: the verified
+        matches of every pair with a result joined on the device (sfm_tracks_build); pairs whose result is None are skipped.
+        verified_only=False joins all matches of those pairs instead of the inliers of the epipolar check."""
+        from .tracks import build_tracks
+        pairs = [(int(i), int(j)) for i, j in pairs]
+        if len(results) != len(pairs):
+            raise ValueError("pairs / results differ in length")
+        live = [s for s, r in enumerate(results) if r is not None]
+        sizes = [0 if k is None else len(keypoints_xy(k)) for k in keypoints]
+        return build_tracks(sizes, [pairs[s] for s in live], [results[s]["matches"] for s in live],
+                            masks=[results[s]["inlier_mask"] for s in live] if verified_only else None,
+                            min_length=min_length, conflicts=conflicts, device=self.device)

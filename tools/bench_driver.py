@@ -384,6 +384,83 @@ def measure_pose(reps=20, emit=None):
     return results
 
 
+def measure_tracks(reps=20, emit=None):
+    """sfm_tracks_build on (a) the shipped matches (148 pairs, 35 images of 500 keypoints: verified matches only and all
+    matches) and (b) a synthetic data set of 100 images x 2,000 keypoints with all 4,950 pairs matched on the points both
+    images see (85 % visibility, 2 % of the matches wrong), inputs resident in HBM: device time of the whole call by HIP
+    events around `reps` calls after warm-up, edges per second, and beside it the host time of the same join with
+    scipy.sparse.csgraph.connected_components (the labelling alone, without the CSR output)."""
+    import torch
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    from sfm_amd import _lib
+    from sfm_amd.driver import _dev, _p
+    h = _lib.get_handle(0)
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0)
+    gold = os.path.join(ROOT, "tests", "golden")
+    bm = np.load(os.path.join(gold, "bunny_matches.npz"), allow_pickle=False)
+    bp = np.load(os.path.join(gold, "bunny_pairs.npz"), allow_pickle=False)
+    pairs = np.array([[int(x) - 1 for x in str(n).split("_")[1:3]] for n in bp["names"]], dtype=np.int32)
+    kp35 = np.arange(36, dtype=np.int64) * 500
+    cases = [("shipped_verified", kp35, bm["offsets"], pairs, bm["queryIdx"], bm["trainIdx"], bp["mask"].astype(np.uint8)),
+             ("shipped_all_matches", kp35, bm["offsets"], pairs, bm["queryIdx"], bm["trainIdx"], None)]
+    n_img, n_kp = 100, 2000
+    sees = rng.random((n_img, n_kp)) < 0.85
+    slot = np.stack([rng.permutation(n_kp) for _ in range(n_img)])           # keypoint index of point p in image i
+    pl, ql, tl = [], [], []
+    for i in range(n_img):
+        for j in range(i + 1, n_img):
+            both = np.flatnonzero(sees[i] & sees[j])
+            q, t = slot[i][both], slot[j][both].copy()
+            wrong = rng.random(len(both)) < 0.02
+            t[wrong] = rng.integers(0, n_kp, int(wrong.sum()))
+            pl.append((i, j)); ql.append(q); tl.append(t)
+    seg = np.concatenate([[0], np.cumsum([len(q) for q in ql])]).astype(np.int64)
+    cases.append((f"synthetic_{n_img}_images_x_{n_kp}_all_{len(pl)}_pairs", np.arange(n_img + 1, dtype=np.int64) * n_kp, seg,
+                  np.array(pl, dtype=np.int32), np.concatenate(ql), np.concatenate(tl), None))
+    results = []
+    for name, kp_ptr, seg_ptr, pair_img, q, t, mask in cases:
+        n_nodes, n_edges, n_seg = int(kp_ptr[-1]), len(q), len(pair_img)
+        d_kp, d_seg, d_pair = _dev(kp_ptr, np.int64, dev), _dev(seg_ptr, np.int64, dev), _dev(pair_img, np.int32, dev)
+        d_q, d_t = _dev(q, np.int32, dev), _dev(t, np.int32, dev)
+        d_mask = _dev(mask, np.uint8, dev) if mask is not None else None
+        need = C.c_int64(); h.lib.sfm_tracks_workspace_bytes(n_nodes, n_edges, C.byref(need))
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        track_ptr = torch.empty(n_nodes // 2 + 1, dtype=torch.int64, device=dev)
+        obs = torch.empty((2, n_nodes), dtype=torch.int32, device=dev)
+        conflict = torch.empty(n_nodes // 2, dtype=torch.uint8, device=dev)
+        node_track = torch.empty(n_nodes, dtype=torch.int32, device=dev)
+        counts = torch.empty(5, dtype=torch.int64, device=dev)
+        row = {"kernel": "tracks_build", "case": name, "images": len(kp_ptr) - 1, "pairs": n_seg, "nodes": n_nodes,
+               "edges": n_edges, "edges_followed": int(n_edges if mask is None else mask.sum())}
+        for policy, key in ((0, "drop"), (1, "keep")):
+            def build():
+                h.call("sfm_tracks_build", _p(d_kp), len(kp_ptr) - 1, n_nodes, _p(d_seg), n_seg, _p(d_pair), _p(d_q), _p(d_t),
+                       _p(d_mask), n_edges, 2, policy, _p(track_ptr), _p(obs[0]), _p(obs[1]), _p(conflict), _p(node_track),
+                       _p(counts), n_nodes // 2, n_nodes, _p(ws), need.value)
+            for _ in range(3):
+                build()
+            sec = timed(build, reps)
+            c = counts.cpu().numpy()
+            row.update({f"ms_call_{key}": sec * 1e3, f"edges_per_s_{key}": n_edges / sec, f"tracks_{key}": int(c[0]),
+                        f"observations_{key}": int(c[1])})
+            row["conflicting"] = int(c[2])
+        seg_of = np.repeat(np.arange(n_seg), np.diff(seg_ptr))
+        live = np.ones(n_edges, bool) if mask is None else mask != 0
+        t0 = time.perf_counter()
+        a = kp_ptr[pair_img[seg_of, 0]] + q
+        b = kp_ptr[pair_img[seg_of, 1]] + t
+        g = coo_matrix((np.ones(int(live.sum()), np.int8), (a[live], b[live])), shape=(n_nodes, n_nodes))
+        n_comp, _ = connected_components(g, directed=False)
+        row["ms_scipy_connected_components_host"] = (time.perf_counter() - t0) * 1e3
+        row["scipy_components_incl_singletons"] = int(n_comp)
+        results.append(row)
+        if emit:
+            emit(row)
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -392,9 +469,10 @@ def main():
     ap.add_argument("--fundamental-only", action="store_true", help="only the fundamental-matrix RANSAC rows")
     ap.add_argument("--pnp-only", action="store_true", help="only the PnP RANSAC rows")
     ap.add_argument("--pose-only", action="store_true", help="only the relative-pose recovery rows")
+    ap.add_argument("--tracks-only", action="store_true", help="only the track-building rows")
     a = ap.parse_args()
     emit = lambda d: print(json.dumps(d), flush=True)
-    only = a.fundamental_only or a.pnp_only or a.pose_only
+    only = a.fundamental_only or a.pnp_only or a.pose_only or a.tracks_only
     if not only:
         measure(a.reps, a.tracks, a.corr, emit=emit)
     if a.fundamental_only or not only:
@@ -403,6 +481,8 @@ def main():
         measure_pnp(a.reps, emit=emit)
     if a.pose_only or not only:
         measure_pose(a.reps, emit=emit)
+    if a.tracks_only or not only:
+        measure_tracks(a.reps, emit=emit)
 
 
 if __name__ == "__main__":

@@ -71,3 +71,16 @@ static inline int sfm_fail(sfm_ctx* h, int code, const char* what, const char* d
 
 static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 static inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
+
+// 256-byte aligned arrays out of a caller's workspace, in order; bytes() after the last take is what the matching
+// *_workspace_bytes call reports (one alignment's slack on top).  A null base only measures.
+struct ws_carve {
+  char* base;
+  int64_t off = 0;
+  template <typename T> T* take(int64_t count) {
+    const int64_t at = off;
+    off += align_up(count * (int64_t)sizeof(T), 256);
+    return (T*)(base + at);
+  }
+  int64_t bytes() const { return off + 256; }
+};

@@ -6,9 +6,10 @@
 // EPnP inside the loop, reprojection error against the threshold in pixels, most inliers wins, then the ITERATIVE
 // (Levenberg-Marquardt) solver over the inliers.  Deviations, on purpose: minimal samples of 3 solved by closed-form
 // P3P with ALL of its (up to four) roots scored; a FIXED number of hypotheses (no early exit on confidence); the
-// stateless hash sampler of twoview.hip with 3 slots (draw_distinct<3>, ransac_common.h) - so the result is a
-// function of (points, K, samples) alone and a NumPy reference can follow the device hypothesis by hypothesis
-// (tests/pnp_reference.py).
+// stateless hash sampler of twoview.hip with 3 slots (k_ransac_samples<3, 4>; draw_distinct<3>, ransac_common.h) - so
+// the result is a function of (points, K, samples) alone and a NumPy reference can follow the device hypothesis by
+// hypothesis (tests/pnp_reference.py).  The sample kernel, the block sums, the whole-segment count and the winner rule
+// are those of the fundamental-matrix RANSAC (ransac_kernels.h).
 //
 // One segment is one candidate image: seg_ptr[n_seg+1] device int64 (the convention of sfm_fund_ransac), X [n][3]
 // float64 world points, uv [n][2] float32 pixels, Kseg [n_seg][4] float64 (fx, fy, cx, cy).  All arithmetic in
@@ -16,9 +17,8 @@
 // (p0 - u p2)^2 + (p1 - v p2)^2 <= thr^2 p2^2,  written with explicit fma so that the three kernels that apply it
 // round alike.  A point with a NaN or infinite coordinate is never an inlier; a sample that holds one, or whose
 // triangle has no area (pnp_solve.h), gives no model.  Sample indices are range-checked before they index anything.
-#include "common.h"
+#include "ransac_kernels.h"
 #include "pnp_solve.h"
-#include <cfloat>
 
 namespace {
 
@@ -49,20 +49,6 @@ __device__ __forceinline__ bool pnp_inlier(const double (&P)[12], double x, doub
   return (p2 > 0.0) && (fma(e0, e0, e1 * e1) <= thr2 * (p2 * p2));
 }
 
-// ------------------------------------------------------------------------------------------------ samples
-__global__ __launch_bounds__(256) void k_pnp_samples(const int64_t* __restrict__ seg_ptr, int n_seg, int H, int64_t n,
-                                                     uint64_t seed, int* __restrict__ samples) {
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= (int64_t)n_seg * H) return;
-  const int s = (int)(g / H), hyp = (int)(g % H);
-  int64_t b; int M;
-  seg_range(seg_ptr, s, n, b, M);
-  int idx[3] = {-1, -1, -1};
-  if (M >= 4) draw_distinct<3>(seed, s, hyp, M, idx);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) samples[g * 3 + k] = idx[k];
-}
-
 // --------------------------------------------------------------------------------------------- hypotheses
 // One lane per (segment, hypothesis); a workgroup covers 256 hypotheses of ONE segment, so the scoring loop's points
 // are wave-uniform: fetched from global memory once per workgroup and chunk into LDS, read back as broadcasts.  The
@@ -84,7 +70,7 @@ __global__ __launch_bounds__(256) void k_pnp_hypotheses(const int64_t* __restric
     if (active) { hyp_count[slot] = 0; hyp_cand[slot] = 0; }
     return;
   }
-  const double fx = Kseg[4 * s], fy = Kseg[4 * s + 1], cx = Kseg[4 * s + 2], cy = Kseg[4 * s + 3];
+  const auto [fx, fy, cx, cy] = load_k4(Kseg, s);
   double Pc[4][12];
   {
     bool ok = active;
@@ -154,30 +140,19 @@ __global__ __launch_bounds__(256) void k_pnp_hypotheses(const int64_t* __restric
 }
 
 // ---------------------------------------------------------------------------------------------- selection
-// inliers of P over the whole segment, counted by the workgroup (every thread takes its own points); writes the
-// mask when `mask` is not null
-__device__ __forceinline__ int segment_count(const double (&P)[12], const double* __restrict__ X,
-                                             const float2* __restrict__ uv, int64_t b, int M, double thr2,
-                                             uint8_t* __restrict__ mask, int* s_i) {
-  int c = 0;
-  for (int i = threadIdx.x; i < M; i += 256) {
-    const int64_t id = b + i;
+// inliers of P over the whole segment; writes the mask when `mask` is not null
+__device__ __forceinline__ int pnp_count(const double (&P)[12], const double* __restrict__ X,
+                                         const float2* __restrict__ uv, int64_t b, int M, double thr2,
+                                         uint8_t* __restrict__ mask) {
+  return segment_count(b, M, mask, [&](int64_t id) {
     const float2 p = uv[id];
-    const bool in = finite_point(&X[3 * id], p) &&
-                    pnp_inlier(P, X[3 * id], X[3 * id + 1], X[3 * id + 2], (double)p.x, (double)p.y, thr2);
-    if (mask) mask[id] = in ? 1 : 0;
-    c += in ? 1 : 0;
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_i[threadIdx.x >> 6] = c;
-  __syncthreads();
-  return s_i[0] + s_i[1] + s_i[2] + s_i[3];
+    return finite_point(&X[3 * id], p) &&
+           pnp_inlier(P, X[3 * id], X[3 * id + 1], X[3 * id + 2], (double)p.x, (double)p.y, thr2);
+  });
 }
 
-// winner per segment: largest count, ties to the lowest hypothesis index (then the lowest candidate slot, settled in
-// k_pnp_hypotheses), as one integer key (count << 32 | ~hypothesis) reduced by a tree; then its mask and its count
+// winner per segment (ransac_winner; ties between the candidates of one hypothesis were settled in k_pnp_hypotheses,
+// to the lowest slot): its [R|t], its mask and its count
 __global__ __launch_bounds__(256) void k_pnp_select(const int64_t* __restrict__ seg_ptr, int64_t n,
                                                     const double* __restrict__ X, const float2* __restrict__ uv,
                                                     const double* __restrict__ Kseg, int H, double thr2,
@@ -185,50 +160,26 @@ __global__ __launch_bounds__(256) void k_pnp_select(const int64_t* __restrict__ 
                                                     const double* __restrict__ cand_Rt, double* __restrict__ Rt_out,
                                                     uint8_t* __restrict__ mask, int* __restrict__ n_inliers,
                                                     int* __restrict__ status, int* __restrict__ refined) {
-  __shared__ unsigned long long s_key[256];
-  __shared__ int s_i[4];
-  const int s = blockIdx.x, tid = threadIdx.x;
+  const int s = blockIdx.x;
   int64_t b; int M;
   seg_range(seg_ptr, s, n, b, M);
-  unsigned long long key = 0;
-  if (M >= 4)
-    for (int hp = tid; hp < H; hp += 256) {
-      const int c = hyp_count[(int64_t)s * H + hp];
-      const unsigned long long k = ((unsigned long long)(unsigned)(c < 0 ? 0 : c) << 32) | (0xFFFFFFFFu - (unsigned)hp);
-      key = k > key ? k : key;
-    }
-  s_key[tid] = key;
-  __syncthreads();
-#pragma unroll
-  for (int d = 128; d >= 1; d >>= 1) {
-    if (tid < d) { const unsigned long long o = s_key[tid + d]; if (o > s_key[tid]) s_key[tid] = o; }
-    __syncthreads();
-  }
-  key = s_key[0];
-  const int best = (int)(key >> 32);
-  const int st = (M < 4) ? 1 : (best == 0 ? 2 : 0);
+  int hp;
+  const int st = ransac_winner(hyp_count, s, H, M, 4, hp);
   double Rt[12];
 #pragma unroll
   for (int e = 0; e < 12; ++e) Rt[e] = 0.0;
   int count = 0;
   if (st == 0) {                                         // uniform over the workgroup
-    const int64_t slot = (int64_t)s * H + (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFu));
+    const int64_t slot = (int64_t)s * H + hp;
     const int cand = hyp_cand[slot] & 3;
 #pragma unroll
     for (int e = 0; e < 12; ++e) Rt[e] = cand_Rt[(slot * 4 + cand) * 12 + e];
+    const auto [fx, fy, cx, cy] = load_k4(Kseg, s);
     double P[12];
-    make_P(Kseg[4 * s], Kseg[4 * s + 1], Kseg[4 * s + 2], Kseg[4 * s + 3], Rt, P);
-    count = segment_count(P, X, uv, b, M, thr2, mask, s_i);
-  } else {
-    for (int i = tid; i < M; i += 256) mask[b + i] = 0;
+    make_P(fx, fy, cx, cy, Rt, P);
+    count = pnp_count(P, X, uv, b, M, thr2, mask);
   }
-  if (tid == 0) {
-#pragma unroll
-    for (int e = 0; e < 12; ++e) Rt_out[12 * (int64_t)s + e] = Rt[e];
-    n_inliers[s] = count;
-    status[s] = st;
-    if (refined) refined[s] = 0;
-  }
+  ransac_store_winner(s, st, b, M, Rt, count, Rt_out, mask, n_inliers, status, refined);
 }
 
 // ------------------------------------------------------------------------------------------------- refine
@@ -267,13 +218,12 @@ __global__ __launch_bounds__(256) void k_pnp_refine(const int64_t* __restrict__ 
                                                     int* __restrict__ n_inliers, const int* __restrict__ status,
                                                     int* __restrict__ refined) {
   __shared__ double s_red[4][PNP_SUMS];
-  __shared__ int s_i[4];
   const int s = blockIdx.x, tid = threadIdx.x;
   int64_t b; int M;
   seg_range(seg_ptr, s, n, b, M);
   const int have = n_inliers[s];
   if (status[s] != 0 || have < 3) return;                // uniform; refined[s] stays 0
-  const double fx = Kseg[4 * s], fy = Kseg[4 * s + 1], cx = Kseg[4 * s + 2], cy = Kseg[4 * s + 3];
+  const auto [fx, fy, cx, cy] = load_k4(Kseg, s);
   double R[9], t[3], Rn[9], tn[3];                       // the accepted pose and the trial
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
@@ -311,21 +261,9 @@ __global__ __launch_bounds__(256) void k_pnp_refine(const int64_t* __restrict__ 
       for (int r = 0; r < 6; ++r) acc[21 + r] += ju[r] * ru + jv[r] * rv;
       acc[27] += ru * ru + rv * rv;
     }
+    block_sum_wide(acc, s_red);
 #pragma unroll
-    for (int k = 0; k < PNP_SUMS; ++k) {
-      double v = acc[k];
-#pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-      acc[k] = v;
-    }
-    __syncthreads();
-    if ((tid & 63) == 0) {
-#pragma unroll
-      for (int k = 0; k < PNP_SUMS; ++k) s_red[tid >> 6][k] = acc[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < PNP_SUMS; ++k) acc[k] = (s_red[0][k] + s_red[1][k]) + (s_red[2][k] + s_red[3][k]);
+    for (int k = 0; k < PNP_SUMS; ++k) acc[k] = block_total(s_red, k);
     // from here on every thread holds the same numbers
     if (it == 0 || acc[27] < Hc[27]) {
 #pragma unroll
@@ -406,9 +344,9 @@ __global__ __launch_bounds__(256) void k_pnp_refine(const int64_t* __restrict__ 
   }
   if (!good) return;                                     // uniform: every thread holds the same pose
   make_P(fx, fy, cx, cy, Rt, P);
-  const int count = segment_count(P, X, uv, b, M, thr2, nullptr, s_i);
+  const int count = pnp_count(P, X, uv, b, M, thr2, nullptr);
   if (count < have) return;
-  (void)segment_count(P, X, uv, b, M, thr2, mask, s_i);
+  (void)pnp_count(P, X, uv, b, M, thr2, mask);
   if (tid == 0) {
 #pragma unroll
     for (int e = 0; e < 12; ++e) Rt_out[12 * (int64_t)s + e] = Rt[e];
@@ -425,13 +363,12 @@ struct pnp_ws {
 };
 
 pnp_ws pnp_layout(void* workspace, int32_t n_seg, int32_t n_hyp) {
+  ws_carve c{(char*)workspace};
   pnp_ws w;
-  char* p = (char*)workspace;
-  int64_t off = 0;
-  w.cand_Rt = (double*)(p + off);   off += align_up((int64_t)n_seg * n_hyp * 4 * 12 * 8, 256);
-  w.hyp_count = (int*)(p + off);    off += align_up((int64_t)n_seg * n_hyp * 4, 256);
-  w.hyp_cand = (int*)(p + off);     off += align_up((int64_t)n_seg * n_hyp * 4, 256);
-  w.bytes = off + 256;
+  w.cand_Rt = c.take<double>((int64_t)n_seg * n_hyp * 4 * 12);
+  w.hyp_count = c.take<int>((int64_t)n_seg * n_hyp);
+  w.hyp_cand = c.take<int>((int64_t)n_seg * n_hyp);
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -446,17 +383,7 @@ extern "C" int sfm_pnp_workspace_bytes(int64_t n_points, int32_t n_seg, int32_t 
 
 extern "C" int sfm_pnp_draw_samples(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, int32_t n_hyp, uint64_t seed,
                                     int32_t* samples) {
-  if (!h) return SFM_ERR_ARG;
-  if (n_seg < 0 || n_hyp < 1 || (int64_t)n_seg * n_hyp > 0x7fffffffLL * 64)
-    return sfm_fail(h, SFM_ERR_ARG, "sfm_pnp_draw_samples", "bad argument");
-  if (n_seg == 0) return SFM_OK;
-  if (!seg_ptr || !samples) return sfm_fail(h, SFM_ERR_ARG, "sfm_pnp_draw_samples", "null pointer");
-  const int64_t total = (int64_t)n_seg * n_hyp;
-  // the segment's extent comes from seg_ptr alone here: no clamp to a point count (INT64_MAX passes every segment)
-  hipLaunchKernelGGL(k_pnp_samples, dim3(cdiv(total, 256)), dim3(256), 0, h->stream, seg_ptr, n_seg, n_hyp,
-                     (int64_t)0x7fffffffffffffffLL, (uint64_t)seed, samples);
-  SFM_LAUNCH_CHECK(h, "sfm_pnp_draw_samples");
-  return SFM_OK;
+  return ransac_draw_samples<3, 4>(h, "sfm_pnp_draw_samples", seg_ptr, n_seg, n_hyp, seed, samples);
 }
 
 extern "C" int sfm_pnp_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, const double* X, const float* uv,
@@ -464,9 +391,7 @@ extern "C" int sfm_pnp_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_se
                               int32_t refine, double* Rt, uint8_t* mask, int32_t* n_inliers, int32_t* status,
                               int32_t* hyp_count, int32_t* refined, void* workspace, int64_t workspace_bytes) {
   if (!h) return SFM_ERR_ARG;
-  if (n < 0 || n_seg < 0 || n_hyp < 1 || !(threshold >= 0.0) || !(threshold < DBL_MAX) ||
-      (int64_t)n_seg * ((n_hyp + 255) / 256) > 0x7fffffffLL)
-    return sfm_fail(h, SFM_ERR_ARG, "sfm_pnp_ransac", "bad argument");
+  if (ransac_bad_args(n, n_seg, n_hyp, threshold)) return sfm_fail(h, SFM_ERR_ARG, "sfm_pnp_ransac", "bad argument");
   if (n == 0 || n_seg == 0) return SFM_OK;
   if (!seg_ptr || !X || !uv || !Kseg || !samples || !Rt || !mask || !n_inliers || !status || !workspace)
     return sfm_fail(h, SFM_ERR_ARG, "sfm_pnp_ransac", "null pointer");

@@ -18,9 +18,8 @@
 // One segment is one image pair: seg_ptr [n_seg+1] device int64 (the convention of sfm_fund_ransac), pts1 / pts2 [n][2]
 // float32 pixels, EorF [n_seg][9] float64 row-major, Kseg [n_seg][4] float64 as sfm_pnp_ransac takes it.  Nothing goes
 // back to the host between the stages.  No FMA contraction anywhere in this file.
-#include "common.h"
+#include "ransac_kernels.h"
 #include "pose_solve.h"
-#include <cfloat>
 
 #pragma clang fp contract(off)
 
@@ -51,7 +50,7 @@ __global__ __launch_bounds__(256) void k_pose_decompose(const int64_t* __restric
 #pragma unroll
   for (int k = 0; k < 9; ++k) E[k] = EorF[9 * (int64_t)s + k];
   if (is_fundamental) {                                  // E = K^T F K, K = [[fx,0,cx],[0,fy,cy],[0,0,1]]
-    const double fx = Kseg[4 * (int64_t)s], fy = Kseg[4 * (int64_t)s + 1], cx = Kseg[4 * (int64_t)s + 2], cy = Kseg[4 * (int64_t)s + 3];
+    const auto [fx, fy, cx, cy] = load_k4(Kseg, s);
     double G[9];                                         // G = K^T F
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -104,7 +103,7 @@ __global__ __launch_bounds__(256) void k_pose_vote(const int64_t* __restrict__ s
   }
   unsigned bits = 0;
   if (active) {
-    const double fx = Kseg[4 * (int64_t)s], fy = Kseg[4 * (int64_t)s + 1], cx = Kseg[4 * (int64_t)s + 2], cy = Kseg[4 * (int64_t)s + 3];
+    const auto [fx, fy, cx, cy] = load_k4(Kseg, s);
     const float2 a = pts1[i], c2 = pts2[i];
     const double x0 = ((double)a.x - cx) / fx, y0 = ((double)a.y - cy) / fy;
     const double x1 = ((double)c2.x - cx) / fx, y1 = ((double)c2.y - cy) / fy;
@@ -194,7 +193,7 @@ __global__ __launch_bounds__(256) void k_pose_finish(const int64_t* __restrict__
   const double nan = __builtin_nan("");
   double Xx = nan, Xy = nan, Xz = nan;
   if (good) {
-    const double fx = Kseg[4 * (int64_t)s], fy = Kseg[4 * (int64_t)s + 1], cx = Kseg[4 * (int64_t)s + 2], cy = Kseg[4 * (int64_t)s + 3];
+    const auto [fx, fy, cx, cy] = load_k4(Kseg, s);
     const double* __restrict__ src = cand_pose + ((int64_t)s * 4 + w) * 12;
     const double P0[12] = {fx, 0.0, cx, 0.0, 0.0, fy, cy, 0.0, 0.0, 0.0, 1.0, 0.0};
     double P1[12];
@@ -221,14 +220,13 @@ struct pose_ws {
 };
 
 pose_ws pose_layout(void* workspace, int64_t n, int32_t n_seg) {
+  ws_carve c{(char*)workspace};
   pose_ws w;
-  char* p = (char*)workspace;
-  int64_t off = 0;
-  w.cand_pose = (double*)(p + off);  off += align_up((int64_t)n_seg * 4 * 12 * 8, 256);
-  w.cand_count = (int*)(p + off);    off += align_up((int64_t)n_seg * 4 * 4, 256);
-  w.winner = (int*)(p + off);        off += align_up((int64_t)n_seg * 4, 256);
-  w.good4 = (uint8_t*)(p + off);     off += align_up(n, 256);
-  w.bytes = off + 256;
+  w.cand_pose = c.take<double>((int64_t)n_seg * 4 * 12);
+  w.cand_count = c.take<int>((int64_t)n_seg * 4);
+  w.winner = c.take<int>(n_seg);
+  w.good4 = c.take<uint8_t>(n);
+  w.bytes = c.bytes();
   return w;
 }
 

@@ -1,6 +1,7 @@
-// Device helpers shared by the batched RANSAC kernels (twoview.hip, pnp.hip): the segment convention, the stateless
-// sample generator and the closed-form cubic.  The functions marked SFM_HD also compile for the host, so that the
-// minimal solvers built on them can be checked on a CPU (tests/native/).
+// What the batched RANSAC stages (twoview.hip, pnp.hip, pose.hip) share and the host can compile too: the segment
+// convention, the stateless sample generator and the closed-form cubic.  The functions marked SFM_HD build with g++, so
+// that the generator and the minimal solvers built on them can be checked on a CPU (tests/native/).  The device-only
+// part - kernels, block sums, the winner rule - is in ransac_kernels.h.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -30,7 +31,8 @@ SFM_HD void seg_range(const int64_t* __restrict__ seg_ptr, int s, int64_t n, int
   M = (int)(m > 0x7fffffffLL ? 0x7fffffffLL : m);
 }
 
-// N distinct indices of [0, M), M >= N, for (seed, segment s, hypothesis hyp).  All arithmetic is uint64, wrapping:
+// N distinct indices of [0, M), M >= N, for (seed, segment s, hypothesis hyp).  All arithmetic is uint64, wrapping,
+// and mix is mix64 above (the splitmix64 finaliser):
 //   key  = mix(mix(mix(seed) ^ s) ^ hyp);  draw d = 0, 1, 2, ...:  index = ((mix(key ^ d) >> 32) * M) >> 32
 // The slots are filled in order; a draw equal to an earlier slot is discarded and the next d is taken.  After
 // RANSAC_MAX_DRAWS draws a slot takes the lowest unused index.

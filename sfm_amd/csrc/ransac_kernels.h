@@ -1,0 +1,148 @@
+// The device side of a batched, replayable RANSAC, shared by twoview.hip and pnp.hip (and, for load_k4, pose.hip): the
+// sample kernel, the block sums, the whole-segment inlier count and the winner rule, for workgroups of 256 threads.
+// Included by .hip files only; what also compiles for the host stays in ransac_common.h.
+#pragma once
+#include "common.h"
+#include "ransac_common.h"
+#include <cfloat>
+
+// One lane per (segment, hypothesis): N distinct indices, or -1 in all N slots of a segment under MIN_POINTS points
+template <int N, int MIN_POINTS>
+__global__ __launch_bounds__(256) void k_ransac_samples(const int64_t* __restrict__ seg_ptr, int n_seg, int H, int64_t n,
+                                                        uint64_t seed, int* __restrict__ samples) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (int64_t)n_seg * H) return;
+  const int s = (int)(g / H), hyp = (int)(g % H);
+  int64_t b; int M;
+  seg_range(seg_ptr, s, n, b, M);
+  int idx[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) idx[k] = -1;
+  if (M >= MIN_POINTS) draw_distinct<N>(seed, s, hyp, M, idx);
+#pragma unroll
+  for (int k = 0; k < N; ++k) samples[g * N + k] = idx[k];
+}
+
+// what stands behind sfm_fund_draw_samples and sfm_pnp_draw_samples; `what` names the entry point in the error string
+template <int N, int MIN_POINTS>
+int ransac_draw_samples(sfm_handle h, const char* what, const int64_t* seg_ptr, int32_t n_seg, int32_t n_hyp,
+                        uint64_t seed, int32_t* samples) {
+  if (!h) return SFM_ERR_ARG;
+  if (n_seg < 0 || n_hyp < 1 || (int64_t)n_seg * n_hyp > 0x7fffffffLL * 64) return sfm_fail(h, SFM_ERR_ARG, what, "bad argument");
+  if (n_seg == 0) return SFM_OK;
+  if (!seg_ptr || !samples) return sfm_fail(h, SFM_ERR_ARG, what, "null pointer");
+  const int64_t total = (int64_t)n_seg * n_hyp;
+  // the segment's extent comes from seg_ptr alone here: no clamp to a point count (INT64_MAX passes every segment)
+  hipLaunchKernelGGL((k_ransac_samples<N, MIN_POINTS>), dim3(cdiv(total, 256)), dim3(256), 0, h->stream, seg_ptr, n_seg,
+                     n_hyp, (int64_t)0x7fffffffffffffffLL, (uint64_t)seed, samples);
+  SFM_LAUNCH_CHECK(h, what);
+  return SFM_OK;
+}
+
+// the scalar arguments sfm_fund_ransac and sfm_pnp_ransac turn down (the grid is n_seg x ceil(n_hyp / 256) workgroups)
+inline bool ransac_bad_args(int64_t n, int32_t n_seg, int32_t n_hyp, double threshold) {
+  return n < 0 || n_seg < 0 || n_hyp < 1 || !(threshold >= 0.0) || !(threshold < DBL_MAX) ||
+         (int64_t)n_seg * ((n_hyp + 255) / 256) > 0x7fffffffLL;
+}
+
+// --------------------------------------------------------------------------------------------- block sums
+// Fixed order (deterministic): the lanes of a wave by butterfly d = 32..1, then the four waves as (s0 + s1) + (s2 + s3)
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+
+// one value per thread (double or int); every thread gets the total
+template <typename T>
+__device__ __forceinline__ T block_sum(T v) {
+  __shared__ T s_w[4];
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
+}
+
+// K values per thread: the four wave sums go to s_red, and block_total(s_red, k) is total k for every thread.  The
+// totals stay in LDS on purpose: a caller that picks k at run time reads LDS, where a register array would go to scratch.
+template <int K>
+__device__ __forceinline__ void block_sum_wide(double (&acc)[K], double (*s_red)[K]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc[k] = wave_sum(acc[k]);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) s_red[threadIdx.x >> 6][k] = acc[k];
+  }
+  __syncthreads();
+}
+
+template <int K>
+__device__ __forceinline__ double block_total(const double (*s_red)[K], int k) {
+  return (s_red[0][k] + s_red[1][k]) + (s_red[2][k] + s_red[3][k]);
+}
+
+// ---------------------------------------------------------------------------------------------- selection
+// inliers of a model over the whole segment [b, b + M), counted by the workgroup (every thread takes its own points);
+// inlier(i) is the stage's rule for point i of the batch.  Writes the mask when `mask` is not null.
+template <typename Inlier>
+__device__ __forceinline__ int segment_count(int64_t b, int M, uint8_t* __restrict__ mask, Inlier inlier) {
+  int c = 0;
+  for (int i = threadIdx.x; i < M; i += 256) {
+    const bool in = inlier(b + i);
+    if (mask) mask[b + i] = in ? 1 : 0;
+    c += in ? 1 : 0;
+  }
+  return block_sum(c);
+}
+
+// winner of segment s: largest count, ties to the lowest hypothesis index, as one integer key
+// (count << 32 | ~hypothesis) reduced by a tree.  Returns the status (1: fewer than min_points points, 2: no
+// hypothesis with an inlier, 0: `hyp` is the winner), uniform over the workgroup.
+__device__ __forceinline__ int ransac_winner(const int* __restrict__ hyp_count, int s, int H, int M, int min_points, int& hyp) {
+  __shared__ unsigned long long s_key[256];
+  const int tid = threadIdx.x;
+  unsigned long long key = 0;
+  if (M >= min_points)
+    for (int hp = tid; hp < H; hp += 256) {
+      const int c = hyp_count[(int64_t)s * H + hp];
+      const unsigned long long k = ((unsigned long long)(unsigned)(c < 0 ? 0 : c) << 32) | (0xFFFFFFFFu - (unsigned)hp);
+      key = k > key ? k : key;
+    }
+  s_key[tid] = key;
+  __syncthreads();
+#pragma unroll
+  for (int d = 128; d >= 1; d >>= 1) {
+    if (tid < d) { const unsigned long long o = s_key[tid + d]; if (o > s_key[tid]) s_key[tid] = o; }
+    __syncthreads();
+  }
+  key = s_key[0];
+  hyp = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFu));
+  return (M < min_points) ? 1 : ((int)(key >> 32) == 0 ? 2 : 0);
+}
+
+// what a select kernel leaves for segment s: the model's W doubles (zero without a model), count, status, refined = 0;
+// a segment without a model gets a zero mask
+template <int W>
+__device__ __forceinline__ void ransac_store_winner(int s, int st, int64_t b, int M, const double (&model)[W], int count,
+                                                    double* __restrict__ out, uint8_t* __restrict__ mask,
+                                                    int* __restrict__ n_inliers, int* __restrict__ status,
+                                                    int* __restrict__ refined) {
+  if (st != 0)
+    for (int i = threadIdx.x; i < M; i += 256) mask[b + i] = 0;
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int e = 0; e < W; ++e) out[W * (int64_t)s + e] = model[e];
+    n_inliers[s] = count;
+    status[s] = st;
+    if (refined) refined[s] = 0;
+  }
+}
+
+// Kseg [n_seg][4] = (fx, fy, cx, cy) of segment s
+struct k4 { double fx, fy, cx, cy; };
+__device__ __forceinline__ k4 load_k4(const double* __restrict__ Kseg, int64_t s) {
+  return {Kseg[4 * s], Kseg[4 * s + 1], Kseg[4 * s + 2], Kseg[4 * s + 3]};
+}

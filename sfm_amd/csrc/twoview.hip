@@ -9,22 +9,16 @@
 // own, stateless sample generator, so that the result is a function of (points, seed) alone and a NumPy reference
 // can follow the device hypothesis by hypothesis (tests/fundamental_reference.py).
 //
-// Sample generator (k_fund_samples; draw_distinct<7> of ransac_common.h), restated in NumPy by the tests.  All
-// arithmetic is uint64, wrapping:
-//   mix(z):  z += 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
-//            z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)          (the splitmix64 finaliser)
-//   key  = mix(mix(mix(seed) ^ segment) ^ hypothesis)
-//   draw d (d = 0, 1, 2, ...) of a segment with M points:  index = ((mix(key ^ d) >> 32) * M) >> 32
-//   the 7 slots are filled in order; a draw equal to an earlier slot is discarded and the next d is taken.  After
-//   256 draws (never reached in practice: 7 * (6/7)^256 = 5e-17 at M = 7) a slot takes the lowest unused index.
+// The sample kernel (k_ransac_samples<7, 7>), the block sums, the whole-segment count and the winner rule are shared with
+// pnp.hip (ransac_kernels.h).  The generator's rule stands above draw_distinct<N> in ransac_common.h and is restated in
+// NumPy by the tests (tests/ransac_reference.py); its fallback after 256 draws is never reached in practice:
+// 7 * (6/7)^256 = 5e-17 at M = 7.
 //
 // All arithmetic in float64.  Points arrive as float32 pixels [n][2] with a device seg_ptr[n_seg+1] (int64), the
 // convention of sfm_epipolar_errors.  A match with a NaN or infinite coordinate is left out of the Hartley
 // statistics and is staged as NaN for the scoring, so it fails every comparison; a sample that holds one gives no
 // model.  Sample indices are range-checked on the device before they index anything.
-#include "common.h"
-#include "ransac_common.h"
-#include <cfloat>
+#include "ransac_kernels.h"
 
 namespace {
 
@@ -34,42 +28,12 @@ __device__ __forceinline__ bool finite4(float2 p, float2 q) {
   return isfinite(p.x) && isfinite(p.y) && isfinite(q.x) && isfinite(q.y);
 }
 
-// ------------------------------------------------------------------------------------------------ samples
-__global__ __launch_bounds__(256) void k_fund_samples(const int64_t* __restrict__ seg_ptr, int n_seg, int H, int64_t n,
-                                                      uint64_t seed, int* __restrict__ samples) {
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= (int64_t)n_seg * H) return;
-  const int s = (int)(g / H), hyp = (int)(g % H);
-  int64_t b; int M;
-  seg_range(seg_ptr, s, n, b, M);
-  int idx[7];
-  if (M < 7) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) samples[g * 7 + k] = -1;
-    return;
-  }
-  draw_distinct<7>(seed, s, hyp, M, idx);
-#pragma unroll
-  for (int k = 0; k < 7; ++k) samples[g * 7 + k] = idx[k];
-}
-
 // ------------------------------------------------------------------------------------------ normalisation
-// sum of one double per thread over a 256-thread block, fixed order (deterministic); every thread gets the total
-__device__ __forceinline__ double block_sum(double v, double* s_w) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
-}
-
 // Hartley transform per segment and image: x' = sc * (x - c), centroid c, mean distance sqrt(2) after scaling.
 // T[s] = {sc1, cx1, cy1, sc2, cx2, cy2}: the 2 x 3 upper rows [sc 0 -sc*cx; 0 sc -sc*cy] in factored form.
 __global__ __launch_bounds__(256) void k_fund_normalise(const int64_t* __restrict__ seg_ptr, int64_t n,
                                                         const float2* __restrict__ pts1, const float2* __restrict__ pts2,
                                                         double* __restrict__ T) {
-  __shared__ double s_w[4];
   const int s = blockIdx.x, tid = threadIdx.x;
   int64_t b; int M;
   seg_range(seg_ptr, s, n, b, M);
@@ -78,10 +42,10 @@ __global__ __launch_bounds__(256) void k_fund_normalise(const int64_t* __restric
     const float2 p = pts1[b + i], q = pts2[b + i];
     if (finite4(p, q)) { sx1 += p.x; sy1 += p.y; sx2 += q.x; sy2 += q.y; cnt += 1.0; }
   }
-  cnt = block_sum(cnt, s_w);
+  cnt = block_sum(cnt);
   const double inv = cnt > 0 ? 1.0 / cnt : 0.0;
-  const double cx1 = block_sum(sx1, s_w) * inv, cy1 = block_sum(sy1, s_w) * inv;
-  const double cx2 = block_sum(sx2, s_w) * inv, cy2 = block_sum(sy2, s_w) * inv;
+  const double cx1 = block_sum(sx1) * inv, cy1 = block_sum(sy1) * inv;
+  const double cx2 = block_sum(sx2) * inv, cy2 = block_sum(sy2) * inv;
   double d1 = 0, d2 = 0;
   for (int i = tid; i < M; i += 256) {
     const float2 p = pts1[b + i], q = pts2[b + i];
@@ -90,7 +54,7 @@ __global__ __launch_bounds__(256) void k_fund_normalise(const int64_t* __restric
       d1 += sqrt(ax * ax + ay * ay); d2 += sqrt(bx * bx + by * by);
     }
   }
-  d1 = block_sum(d1, s_w) * inv; d2 = block_sum(d2, s_w) * inv;
+  d1 = block_sum(d1) * inv; d2 = block_sum(d2) * inv;
   if (tid == 0) {
     double* t = T + 6 * (int64_t)s;
     t[0] = d1 > 0 ? sqrt(2.0) / d1 : 1.0; t[1] = cx1; t[2] = cy1;
@@ -302,76 +266,40 @@ __device__ __forceinline__ void scale_f22(double (&f)[9]) {
   for (int e = 0; e < 9; ++e) f[e] = ok ? g[e] : f[e];
 }
 
-// inliers of f over the whole segment, counted by the workgroup (staged through LDS like the scoring loop is not
-// needed here: every thread takes its own points); writes the mask when `mask` is not null
-__device__ __forceinline__ int segment_count(const double (&f)[9], const float2* __restrict__ pts1,
-                                             const float2* __restrict__ pts2, int64_t b, int M, double thr2,
-                                             uint8_t* __restrict__ mask, int* s_i) {
-  int c = 0;
-  for (int i = threadIdx.x; i < M; i += 256) {
-    const float2 p = pts1[b + i], q = pts2[b + i];
-    const bool in = finite4(p, q) && fund_inlier(f, (double)p.x, (double)p.y, (double)q.x, (double)q.y, thr2);
-    if (mask) mask[b + i] = in ? 1 : 0;
-    c += in ? 1 : 0;
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_i[threadIdx.x >> 6] = c;
-  __syncthreads();
-  return s_i[0] + s_i[1] + s_i[2] + s_i[3];
+// inliers of f over the whole segment (staged through LDS like the scoring loop is not needed here: every thread takes
+// its own points); writes the mask when `mask` is not null
+__device__ __forceinline__ int fund_count(const double (&f)[9], const float2* __restrict__ pts1,
+                                          const float2* __restrict__ pts2, int64_t b, int M, double thr2,
+                                          uint8_t* __restrict__ mask) {
+  return segment_count(b, M, mask, [&](int64_t i) {
+    const float2 p = pts1[i], q = pts2[i];
+    return finite4(p, q) && fund_inlier(f, (double)p.x, (double)p.y, (double)q.x, (double)q.y, thr2);
+  });
 }
 
-// winner per segment: largest count, ties to the lowest hypothesis index, as one integer key
-// (count << 32 | ~hypothesis) reduced by a tree; then F scaled to F[2][2] = 1, its mask and its count
+// winner per segment (ransac_winner): its F scaled to F[2][2] = 1, its mask and its count
 __global__ __launch_bounds__(256) void k_fund_select(const int64_t* __restrict__ seg_ptr, int64_t n,
                                                      const float2* __restrict__ pts1, const float2* __restrict__ pts2,
                                                      int H, double thr2, const int* __restrict__ hyp_count,
                                                      const double* __restrict__ hyp_F, double* __restrict__ F,
                                                      uint8_t* __restrict__ mask, int* __restrict__ n_inliers,
                                                      int* __restrict__ status, int* __restrict__ refined) {
-  __shared__ unsigned long long s_key[256];
-  __shared__ int s_i[4];
-  const int s = blockIdx.x, tid = threadIdx.x;
+  const int s = blockIdx.x;
   int64_t b; int M;
   seg_range(seg_ptr, s, n, b, M);
-  unsigned long long key = 0;
-  if (M >= 7)
-    for (int hp = tid; hp < H; hp += 256) {
-      const int c = hyp_count[(int64_t)s * H + hp];
-      const unsigned long long k = ((unsigned long long)(unsigned)(c < 0 ? 0 : c) << 32) | (0xFFFFFFFFu - (unsigned)hp);
-      key = k > key ? k : key;
-    }
-  s_key[tid] = key;
-  __syncthreads();
-#pragma unroll
-  for (int d = 128; d >= 1; d >>= 1) {
-    if (tid < d) { const unsigned long long o = s_key[tid + d]; if (o > s_key[tid]) s_key[tid] = o; }
-    __syncthreads();
-  }
-  key = s_key[0];
-  const int best = (int)(key >> 32);
-  const int st = (M < 7) ? 1 : (best == 0 ? 2 : 0);
+  int hp;
+  const int st = ransac_winner(hyp_count, s, H, M, 7, hp);
   double f[9];
 #pragma unroll
   for (int e = 0; e < 9; ++e) f[e] = 0.0;
   int count = 0;
   if (st == 0) {                                         // uniform over the workgroup
-    const int hp = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFu));
 #pragma unroll
     for (int e = 0; e < 9; ++e) f[e] = hyp_F[((int64_t)s * H + hp) * 9 + e];
     scale_f22(f);
-    count = segment_count(f, pts1, pts2, b, M, thr2, mask, s_i);
-  } else {
-    for (int i = tid; i < M; i += 256) mask[b + i] = 0;
+    count = fund_count(f, pts1, pts2, b, M, thr2, mask);
   }
-  if (tid == 0) {
-#pragma unroll
-    for (int e = 0; e < 9; ++e) F[9 * (int64_t)s + e] = f[e];
-    n_inliers[s] = count;
-    status[s] = st;
-    if (refined) refined[s] = 0;
-  }
+  ransac_store_winner(s, st, b, M, f, count, F, mask, n_inliers, status, refined);
 }
 
 // -------------------------------------------------------------------------------------------------- refit
@@ -387,7 +315,6 @@ __global__ __launch_bounds__(256) void k_fund_refit(const int64_t* __restrict__ 
                                                     const int* __restrict__ status, int* __restrict__ refined) {
   __shared__ double s_red[4][45];
   __shared__ double s_A[9][9], s_V[9][9];
-  __shared__ int s_i[4];
   const int s = blockIdx.x, tid = threadIdx.x;
   int64_t b; int M;
   seg_range(seg_ptr, s, n, b, M);
@@ -409,23 +336,12 @@ __global__ __launch_bounds__(256) void k_fund_refit(const int64_t* __restrict__ 
 #pragma unroll
       for (int v = u; v < 9; ++v) acc[k++] += r[u] * r[v];
   }
-#pragma unroll
-  for (int k = 0; k < 45; ++k) {
-    double v = acc[k];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    acc[k] = v;
-  }
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 45; ++k) s_red[tid >> 6][k] = acc[k];
-  }
-  __syncthreads();
+  block_sum_wide(acc, s_red);
   if (tid < 81) {
     const int u = tid / 9, v = tid % 9;
     const int lo = u < v ? u : v, hi = u < v ? v : u;
     const int k = lo * 9 - lo * (lo - 1) / 2 + (hi - lo);
-    s_A[u][v] = (s_red[0][k] + s_red[1][k]) + (s_red[2][k] + s_red[3][k]);
+    s_A[u][v] = block_total(s_red, k);
     s_V[u][v] = (u == v) ? 1.0 : 0.0;
   }
   __syncthreads();
@@ -519,9 +435,9 @@ __global__ __launch_bounds__(256) void k_fund_refit(const int64_t* __restrict__ 
   for (int e = 0; e < 9; ++e) good = good && isfinite(f[e]);
   if (!good) return;                                     // uniform: every thread computed the same f
   scale_f22(f);
-  const int count = segment_count(f, pts1, pts2, b, M, thr2, nullptr, s_i);
+  const int count = fund_count(f, pts1, pts2, b, M, thr2, nullptr);
   if (count < have) return;
-  (void)segment_count(f, pts1, pts2, b, M, thr2, mask, s_i);
+  (void)fund_count(f, pts1, pts2, b, M, thr2, mask);
   if (tid == 0) {
 #pragma unroll
     for (int e = 0; e < 9; ++e) F[9 * (int64_t)s + e] = f[e];
@@ -538,13 +454,12 @@ struct fund_ws {
 };
 
 fund_ws fund_layout(void* workspace, int32_t n_seg, int32_t n_hyp) {
+  ws_carve c{(char*)workspace};
   fund_ws w;
-  char* p = (char*)workspace;
-  int64_t off = 0;
-  w.T = (double*)(p + off);         off += align_up((int64_t)n_seg * 6 * 8, 256);
-  w.hyp_F = (double*)(p + off);     off += align_up((int64_t)n_seg * n_hyp * 9 * 8, 256);
-  w.hyp_count = (int*)(p + off);    off += align_up((int64_t)n_seg * n_hyp * 4, 256);
-  w.bytes = off + 256;
+  w.T = c.take<double>((int64_t)n_seg * 6);
+  w.hyp_F = c.take<double>((int64_t)n_seg * n_hyp * 9);
+  w.hyp_count = c.take<int>((int64_t)n_seg * n_hyp);
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -559,17 +474,7 @@ extern "C" int sfm_fund_workspace_bytes(int64_t n_points, int32_t n_seg, int32_t
 
 extern "C" int sfm_fund_draw_samples(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, int32_t n_hyp, uint64_t seed,
                                      int32_t* samples) {
-  if (!h) return SFM_ERR_ARG;
-  if (n_seg < 0 || n_hyp < 1 || (int64_t)n_seg * n_hyp > 0x7fffffffLL * 64)
-    return sfm_fail(h, SFM_ERR_ARG, "sfm_fund_draw_samples", "bad argument");
-  if (n_seg == 0) return SFM_OK;
-  if (!seg_ptr || !samples) return sfm_fail(h, SFM_ERR_ARG, "sfm_fund_draw_samples", "null pointer");
-  const int64_t total = (int64_t)n_seg * n_hyp;
-  // the segment's extent comes from seg_ptr alone here: no clamp to a point count (INT64_MAX passes every segment)
-  hipLaunchKernelGGL(k_fund_samples, dim3(cdiv(total, 256)), dim3(256), 0, h->stream, seg_ptr, n_seg, n_hyp,
-                     (int64_t)0x7fffffffffffffffLL, (uint64_t)seed, samples);
-  SFM_LAUNCH_CHECK(h, "sfm_fund_draw_samples");
-  return SFM_OK;
+  return ransac_draw_samples<7, 7>(h, "sfm_fund_draw_samples", seg_ptr, n_seg, n_hyp, seed, samples);
 }
 
 extern "C" int sfm_fund_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, const float* pts1, const float* pts2,
@@ -577,9 +482,7 @@ extern "C" int sfm_fund_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_s
                                double* F, uint8_t* mask, int32_t* n_inliers, int32_t* status, int32_t* hyp_count,
                                int32_t* refined, void* workspace, int64_t workspace_bytes) {
   if (!h) return SFM_ERR_ARG;
-  if (n < 0 || n_seg < 0 || n_hyp < 1 || !(threshold >= 0.0) || !(threshold < DBL_MAX) ||
-      (int64_t)n_seg * ((n_hyp + 255) / 256) > 0x7fffffffLL)
-    return sfm_fail(h, SFM_ERR_ARG, "sfm_fund_ransac", "bad argument");
+  if (ransac_bad_args(n, n_seg, n_hyp, threshold)) return sfm_fail(h, SFM_ERR_ARG, "sfm_fund_ransac", "bad argument");
   if (n == 0 || n_seg == 0) return SFM_OK;
   if (!seg_ptr || !pts1 || !pts2 || !samples || !F || !mask || !n_inliers || !status || !workspace)
     return sfm_fail(h, SFM_ERR_ARG, "sfm_fund_ransac", "null pointer");

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from .driver import _dev, _p, _ptr_array
-from .pnp import _check_K
+from ._ransac import check_K
 
 STATUS_OK, STATUS_EMPTY, STATUS_NO_MODEL = 0, 1, 2
 NO_MODEL = (0, None, None, None)
@@ -76,7 +76,7 @@ def recover_pose_batched(E_list, pts1_list, pts2_list, K, masks=None, distance_t
 
     if n_seg == 0:
         return ([], []) if return_debug else []
-    k4 = _check_K(K, n_seg)
+    k4 = check_K(K, n_seg)
     if n == 0:                                     # nothing to upload: every pair is an empty one
         res = [nothing] * n_seg
         dbg = [debug_row(np.zeros(4, np.int32), np.full((4, 3, 4), np.nan), 0, STATUS_EMPTY) for _ in range(n_seg)]

@@ -1,5 +1,5 @@
 """NumPy float64 restatement of the batched fundamental-matrix RANSAC (sfm_amd/csrc/twoview.hip), taking the samples
-as input, plus the restatement of its sample generator and the synthetic two-view scenes the tests share.
+as input, plus its sample generator (tests/ransac_reference.py at 7 slots) and the synthetic two-view scenes the tests share.
 
 It is a reference for the tests, not a second implementation to fall back to: null space by np.linalg.svd, the cubic
 through four determinant evaluations and np.roots, where the kernel rotates columns and solves in closed form.
@@ -9,45 +9,13 @@ through four determinant evaluations and np.roots, where the kernel rotates colu
 """
 import numpy as np
 
-MAX_DRAWS = 256
-_U = np.uint64
-
-
-# ------------------------------------------------------------------------------------------- the generator
-def mix64(z):
-    """splitmix64 finaliser on uint64 arrays (wrapping arithmetic)."""
-    z = np.asarray(z, dtype=np.uint64)
-    with np.errstate(over="ignore"):
-        z = z + _U(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> _U(30))) * _U(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> _U(27))) * _U(0x94D049BB133111EB)
-    return z ^ (z >> _U(31))
+import ransac_reference
+from ransac_reference import mix64  # noqa: F401
 
 
 def draw_samples(seed, segment, n_points, n_hyp):
-    """[n_hyp, 7] int32: the samples k_fund_samples draws for segment `segment` holding `n_points` matches
-    (all -1 when it has fewer than 7).  A function of (seed, segment, hypothesis) and n_points only."""
-    out = np.full((n_hyp, 7), -1, dtype=np.int32)
-    if n_points < 7:
-        return out
-    hyp = np.arange(n_hyp, dtype=np.uint64)
-    key = mix64(mix64(mix64(np.array([seed], dtype=np.uint64)) ^ _U(segment)) ^ hyp)
-    d = np.zeros(n_hyp, dtype=np.uint64)
-    for k in range(7):
-        pending = np.ones(n_hyp, dtype=bool)
-        while True:
-            pending &= d < MAX_DRAWS
-            if not pending.any():
-                break
-            i = np.flatnonzero(pending)
-            c = (((mix64(key[i] ^ d[i]) >> _U(32)) * _U(n_points)) >> _U(32)).astype(np.int32)
-            d[i] += _U(1)
-            dup = (out[i, :k] == c[:, None]).any(axis=1)
-            out[i[~dup], k] = c[~dup]
-            pending[i[~dup]] = False
-        for h in np.flatnonzero(out[:, k] < 0):          # draws exhausted: the lowest unused index
-            out[h, k] = min(set(range(7)) - set(out[h, :k].tolist()))
-    return out
+    """[n_hyp, 7] int32: the samples drawn for segment `segment` holding `n_points` matches (all -1 under 7)."""
+    return ransac_reference.draw_samples(seed, segment, n_points, n_hyp, 7, 7)
 
 
 # ------------------------------------------------------------------------------------------------ geometry

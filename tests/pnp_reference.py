@@ -1,5 +1,5 @@
 """NumPy float64 reference of the batched PnP RANSAC (sfm_amd/csrc/pnp.hip), taking the samples as input, plus the
-3-slot restatement of the sample generator and the synthetic views the tests share.
+sample generator (tests/ransac_reference.py at 3 slots) and the synthetic views the tests share.
 
 It is a reference for the tests, not a second implementation to fall back to, and not the kernel's algebra restated:
 the kernel intersects the conics of the depth pencil (one cubic root, two quadratics, Newton polish, frame-to-frame
@@ -12,36 +12,13 @@ points by SVD.
 """
 import numpy as np
 
-from fundamental_reference import K_REF, MAX_DRAWS, mix64
+import ransac_reference
+from fundamental_reference import K_REF
 
-_U = np.uint64
 
-
-# ------------------------------------------------------------------------------------------- the generator
 def draw_samples(seed, segment, n_points, n_hyp):
-    """[n_hyp, 3] int32: the samples k_pnp_samples draws for segment `segment` holding `n_points` points (all -1 when
-    it has fewer than 4).  A function of (seed, segment, hypothesis) and n_points only."""
-    out = np.full((n_hyp, 3), -1, dtype=np.int32)
-    if n_points < 4:
-        return out
-    hyp = np.arange(n_hyp, dtype=np.uint64)
-    key = mix64(mix64(mix64(np.array([seed], dtype=np.uint64)) ^ _U(segment)) ^ hyp)
-    d = np.zeros(n_hyp, dtype=np.uint64)
-    for k in range(3):
-        pending = np.ones(n_hyp, dtype=bool)
-        while True:
-            pending &= d < MAX_DRAWS
-            if not pending.any():
-                break
-            i = np.flatnonzero(pending)
-            c = (((mix64(key[i] ^ d[i]) >> _U(32)) * _U(n_points)) >> _U(32)).astype(np.int32)
-            d[i] += _U(1)
-            dup = (out[i, :k] == c[:, None]).any(axis=1)
-            out[i[~dup], k] = c[~dup]
-            pending[i[~dup]] = False
-        for h in np.flatnonzero(out[:, k] < 0):          # draws exhausted: the lowest unused index
-            out[h, k] = min(set(range(3)) - set(out[h, :k].tolist()))
-    return out
+    """[n_hyp, 3] int32: the samples drawn for segment `segment` holding `n_points` points (all -1 under 4)."""
+    return ransac_reference.draw_samples(seed, segment, n_points, n_hyp, 3, 4)
 
 
 # ------------------------------------------------------------------------------------------------ geometry

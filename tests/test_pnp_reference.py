@@ -50,6 +50,30 @@ def test_generator_is_a_function_of_seed_segment_hypothesis():
     assert np.array_equal(a, fr.draw_samples(5, 3, 40, 256)[:, :3])
 
 
+def test_device_generator_on_the_host_equals_the_numpy_generator(tmp_path):
+    """draw_distinct<3> and draw_distinct<7> of ransac_common.h compiled by g++ against the NumPy generator
+    (tests/ransac_reference.py), index for index: 64 hypotheses at M = size (where duplicate rejection runs longest), just above it and at 1000, for two
+    seeds (one >= 2^63: the wrapping arithmetic) and segments 0 and 147."""
+    import shutil
+    import subprocess
+    import fundamental_reference as fr
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "ransac_common_check")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-I" + os.path.join(ROOT, "sfm_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "native", "ransac_common_check.cpp"), "-o", exe], check=True)
+    cases = [(size, seed, seg, M, 64) for size, Ms in ((3, (4, 5, 1000)), (7, (7, 8, 1000))) for M in Ms
+             for seed in (12345, 2 ** 63 + 0x1234567) for seg in (0, 147)]
+    np.array(cases, dtype=np.uint64).tofile(exe + ".in")
+    subprocess.run([exe, exe + ".in", exe + ".out"], check=True)
+    got, at = np.fromfile(exe + ".out", dtype=np.int32), 0
+    for size, seed, seg, M, H in cases:
+        want = (pr if size == 3 else fr).draw_samples(seed, seg, M, H)
+        assert np.array_equal(got[at:at + H * size].reshape(H, size), want), (size, seed, seg, M)
+        at += H * size
+    assert at == len(got)
+
+
 # ---------------------------------------------------------------------------------------- the minimal solver
 def test_noise_free_view_every_sample_recovers_the_pose():
     """No noise, no outliers (pixels rounded to float32, 3e-5 px): every hypothesis reaches all M points at 0.01 px."""

@@ -24,6 +24,8 @@ SOLVER_DENSE, SOLVER_PCG = 0, 1
 CAMERA_AUTO, CAMERA_CHOLESKY, CAMERA_CG = 0, 1, 2
 UV_AS_GIVEN, UV_REFERENCE_PAIRING = 0, 1
 TRACKS_DROP, TRACKS_KEEP = 0, 1
+# status of a track from sfm_triangulate_tracks (SFM_TRI_* of include/sfm_amd.h): the first failing gate
+(TRI_OK, TRI_TOO_FEW_VIEWS, TRI_DEGENERATE, TRI_BEHIND, TRI_LOW_ANGLE, TRI_HIGH_ERROR) = range(6)
 
 
 class BADesc(C.Structure):
@@ -136,6 +138,9 @@ SIGNATURES = {
     "sfm_pose_recover": (C.c_int, [vp, vp, i32, vp, vp, i64, vp, i32, vp, vp, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64]),
     "sfm_tracks_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
     "sfm_tracks_build": (C.c_int, [vp, vp, i32, i64, vp, i32, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, i64, vp, i64]),
+    "sfm_triangulate_tracks_workspace_bytes": (C.c_int, [i32, C.POINTER(i64)]),
+    "sfm_triangulate_tracks": (C.c_int, [vp, vp, i32, vp, i32, vp, vp, i64, vp, i64, vp, vp, i64, i32, i32, f64, f64,
+                                         vp, vp, vp, vp, vp, vp, i64]),
 }
 
 _lib = None

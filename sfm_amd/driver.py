@@ -275,6 +275,23 @@ class DriverMixin:
                 return None
         return point3D
 
+    def triangulate_tracks(self, tracks, keypoints, **options):
+        """N-view triangulation of a `Tracks` object against `self.poses` / `self.K` (sfm_amd.triangulate): sets
+        `self.points3D` and `self.point_tracks` ({image_id: [x, y]} over the registered images only) to the valid tracks
+        and returns the `Triangulation`."""
+        from .triangulate import triangulate_tracks
+        options.setdefault("device", getattr(self, "ba_device", 0))
+        tri = triangulate_tracks(tracks, keypoints, dict(self.poses), K=self.K, **options)
+        ids = tracks.image_ids if tracks.image_ids is not None else list(range(len(tracks.kp_ptr) - 1))
+        sel, pt = tri._valid_observations()
+        point_tracks = [dict() for _ in range(int(tri.valid.sum()))]
+        for o, p, uv in zip(sel.tolist(), pt.tolist(), tri._uv[sel].tolist()):
+            point_tracks[p][ids[tracks.image[o]]] = uv
+        self.points3D = tri.X[tri.valid].tolist()
+        self.point_tracks = point_tracks
+        logging.info(f"Triangulated {len(self.points3D)} of {len(tracks)} tracks")
+        return tri
+
     def add_new_matches(self, pair, image_id):
         try:
             pts1 = np.asarray(np.load(self.corr_dir / f'{pair}_pts1.npy')).reshape(-1, 2)

@@ -2,9 +2,10 @@
 """Device-time measurement of the driver-row kernels with inputs resident in HBM:
 association (pair tests/s), two-view triangulation (tracks/s), epipolar verification (matches/s), and the batched
 fundamental-matrix RANSAC beside the batched matcher it follows in the pair loop, the batched PnP RANSAC of the
-camera registration, and the batched relative-pose recovery of the initial-pair scan.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
+camera registration, the batched relative-pose recovery of the initial-pair scan, the track building and the N-view
+triangulation of the tracks.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
 functions to time on a bounded sample of the same inputs (this tool itself never imports oracle/).
-usage: python tools/bench_driver.py [--reps 20] [--fundamental-only | --pnp-only | --pose-only]"""
+usage: python tools/bench_driver.py [--reps 20] [--fundamental-only | --pnp-only | --pose-only | --tracks-only | --triangulate-only]"""
 import argparse
 import ctypes as C
 import json
@@ -461,6 +462,100 @@ def measure_tracks(reps=20, emit=None):
     return results
 
 
+HBM_STREAM_BPS = 6.3e12         # achievable HBM read rate of an MI355X (8 TB/s on paper): what the stream floor divides by
+
+
+def _triangulate_case(name, proj, cam_idx, uv, lengths, launch_bound):
+    """Flat arrays of one workload: every camera an image of its own, every observation a keypoint of its own (numbered
+    inside its image in track order), observations point-major."""
+    n_cams = len(proj)
+    order = np.argsort(cam_idx, kind="stable")
+    kp_ptr = np.concatenate([[0], np.cumsum(np.bincount(cam_idx, minlength=n_cams))]).astype(np.int64)
+    obs_kp = np.empty(len(cam_idx), np.int32)
+    obs_kp[order] = (np.arange(len(cam_idx)) - kp_ptr[cam_idx[order]]).astype(np.int32)
+    kp_xy = np.empty((len(cam_idx), 2))
+    kp_xy[kp_ptr[cam_idx] + obs_kp] = uv
+    track_ptr = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    return dict(name=name, proj=proj.reshape(-1, 12), cam_of_image=np.arange(n_cams, dtype=np.int32), kp_ptr=kp_ptr, kp_xy=kp_xy,
+                track_ptr=track_ptr, obs_image=cam_idx.astype(np.int32), obs_kp=obs_kp, launch_bound=launch_bound)
+
+
+def measure_triangulate(reps=20, emit=None):
+    """sfm_triangulate_tracks, inputs resident in HBM, device time of the whole call (camera-centre prologue, counter reset
+    and the track kernel) by HIP events around `reps` calls after warm-up, on (a) a set shaped like the shipped tracks (35
+    images, 1,641 tracks of 2 to 12 views, 4 on average: launch-bound) and (b) 200 cameras / 100,000 points / 10 views
+    each from sfm_amd.synth with both visibility patterns of bench.py, for refine_iters 0 and 5.  Per row: ms,
+    observations per second and the share of the HBM stream floor (every input array read once and every output written
+    once, over HBM_STREAM_BPS); beside it the time of sfm_triangulate2 on as many two-view tracks as an anchor."""
+    import torch
+    from sfm_amd import _lib, synth
+    from sfm_amd.driver import _dev, _p
+    from sfm_amd.rotation import rodrigues
+    h = _lib.get_handle(0)
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0)
+
+    def projections(sc):
+        return np.stack([sc.K @ np.hstack([rodrigues(c[:3]), c[3:6].reshape(3, 1)]) for c in sc.cams_true])
+    cases = []
+    sc = synth.make_scene(35, 1641, obs_per_point=None, seed=5, noise_px=0.5, visibility="nearest")
+    lengths = np.minimum(2 + rng.geometric(0.4, 1641) - 1 + (rng.random(1641) < 0.64), 12).astype(np.int64)    # mean 4, max 12
+    first = rng.integers(0, 35 - lengths + 1)
+    keep = np.concatenate([p * 35 + first[p] + np.arange(lengths[p]) for p in range(1641)])                     # neighbouring views
+    cases.append(_triangulate_case("shipped_shape_35_images_1641_tracks", projections(sc), sc.cam_idx[keep], sc.uv[keep], lengths, True))
+    for vis in ("random", "nearest"):
+        sc = synth.make_scene(200, 100000, obs_per_point=10, seed=1004, noise_px=0.5, visibility=vis)
+        cases.append(_triangulate_case(f"synth_200_cameras_100000_points_{vis}", projections(sc), sc.cam_idx, sc.uv,
+                                       np.full(100000, 10, np.int64), False))
+    results = []
+    for c in cases:
+        n_cams, n_tracks, n_obs = len(c["proj"]), len(c["track_ptr"]) - 1, len(c["obs_image"])
+        d = {k: _dev(c[k], t, dev) for k, t in (("proj", np.float64), ("cam_of_image", np.int32), ("kp_ptr", np.int64),
+                                                ("kp_xy", np.float64), ("track_ptr", np.int64), ("obs_image", np.int32),
+                                                ("obs_kp", np.int32))}
+        need = C.c_int64(); h.lib.sfm_triangulate_tracks_workspace_bytes(n_cams, C.byref(need))
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        X = torch.empty((n_tracks, 3), dtype=torch.float64, device=dev); me = torch.empty(n_tracks, dtype=torch.float64, device=dev)
+        st = torch.empty(n_tracks, dtype=torch.int32, device=dev); nv = torch.empty(n_tracks, dtype=torch.int32, device=dev)
+        counts = torch.empty(6, dtype=torch.int64, device=dev)
+        stream_bytes = (sum(c[k].nbytes for k in ("proj", "cam_of_image", "kp_ptr", "kp_xy", "track_ptr", "obs_image", "obs_kp"))
+                        + n_tracks * (24 + 8 + 4 + 4) + 48)
+        floor_s = stream_bytes / HBM_STREAM_BPS
+        row = {"kernel": "triangulate_tracks", "case": c["name"], "cameras": n_cams, "tracks": n_tracks, "observations": n_obs,
+               "stream_bytes": int(stream_bytes), "hbm_stream_floor_ms": floor_s * 1e3, "hbm_stream_Bps_assumed": HBM_STREAM_BPS}
+        for iters in (0, 5):
+            def run():
+                h.call("sfm_triangulate_tracks", _p(d["proj"]), n_cams, _p(d["cam_of_image"]), n_cams, _p(d["kp_ptr"]),
+                       _p(d["kp_xy"]), n_obs, _p(d["track_ptr"]), n_tracks, _p(d["obs_image"]), _p(d["obs_kp"]), n_obs, 2, iters,
+                       C.c_double(4.0), C.c_double(1.0), _p(X), _p(st), _p(nv), _p(me), _p(counts), _p(ws), need.value)
+            for _ in range(3):
+                run()
+            sec = timed(run, reps)
+            row.update({f"ms_refine{iters}": sec * 1e3, f"observations_per_s_refine{iters}": n_obs / sec,
+                        f"share_of_hbm_stream_floor_refine{iters}": floor_s / sec,
+                        f"ok_tracks_refine{iters}": int(counts.cpu().numpy()[0])})
+        # anchor: sfm_triangulate2 on as many two-view tracks (the first two observations of every track)
+        a = c["track_ptr"][:-1]
+        node = c["kp_ptr"][c["obs_image"]] + c["obs_kp"]
+        t2 = [_dev(v, t, dev) for v, t in ((c["obs_image"][a], np.int32), (c["obs_image"][a + 1], np.int32),
+                                           (c["kp_xy"][node[a]], np.float64), (c["kp_xy"][node[a + 1]], np.float64))]
+        valid = torch.empty(n_tracks, dtype=torch.int32, device=dev)
+
+        def tri2():
+            h.call("sfm_triangulate2", _p(d["proj"]), n_cams, _p(t2[0]), _p(t2[1]), _p(t2[2]), _p(t2[3]), n_tracks,
+                   C.c_double(4.0), _p(X), _p(valid), C.c_void_p(0))
+        for _ in range(3):
+            tri2()
+        row["ms_triangulate2_same_number_of_two_view_tracks"] = timed(tri2, reps) * 1e3
+        row["note"] = ("launch-bound: two launches and a counter reset over a few microseconds of work; the share of the stream "
+                       "floor says nothing at this size") if c["launch_bound"] else \
+                      "gather- and latency-bound: the passes re-read the observations from cache; the floor counts every array once"
+        results.append(row)
+        if emit:
+            emit(row)
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -470,9 +565,10 @@ def main():
     ap.add_argument("--pnp-only", action="store_true", help="only the PnP RANSAC rows")
     ap.add_argument("--pose-only", action="store_true", help="only the relative-pose recovery rows")
     ap.add_argument("--tracks-only", action="store_true", help="only the track-building rows")
+    ap.add_argument("--triangulate-only", action="store_true", help="only the N-view track triangulation rows")
     a = ap.parse_args()
     emit = lambda d: print(json.dumps(d), flush=True)
-    only = a.fundamental_only or a.pnp_only or a.pose_only or a.tracks_only
+    only = a.fundamental_only or a.pnp_only or a.pose_only or a.tracks_only or a.triangulate_only
     if not only:
         measure(a.reps, a.tracks, a.corr, emit=emit)
     if a.fundamental_only or not only:
@@ -483,6 +579,8 @@ def main():
         measure_pose(a.reps, emit=emit)
     if a.tracks_only or not only:
         measure_tracks(a.reps, emit=emit)
+    if a.triangulate_only or not only:
+        measure_triangulate(a.reps, emit=emit)
 
 
 if __name__ == "__main__":

@@ -552,6 +552,48 @@ int sfm_triangulate_tracks(sfm_handle h, const double* proj, int32_t n_cams, con
                            int32_t* status, int32_t* n_views, double* max_err, int64_t* counts /* [6] by status */,
                            void* workspace, int64_t workspace_bytes);
 
+/* ------------------------------------------------------------------- the gates at points that are given
+ * sfm_triangulate_tracks can only recompute a point; after a bundle adjustment the cameras and the points have moved and
+ * the point to judge is the adjusted one.  Same arrays, same observation source and same camera-centre prologue (the
+ * workspace is that of sfm_triangulate_tracks_workspace_bytes), one thread per track, X [n_tracks][3] and has_point
+ * [n_tracks] uint8 given.  A track with has_point == 0 gets status SFM_EVAL_NO_POINT, its n_views is still counted, its
+ * max_err is NaN and it is left out of counts.  Every other track is judged at X by the gates of sfm_triangulate_tracks in
+ * their order (SFM_TRI_*; DEGENERATE: a non-finite input of a used observation or a non-finite X); max_err is NaN for
+ * status 1 and 2, else the largest reprojection error of a used view.  obs_err [n_obs] (may be NULL): the reprojection
+ * error of every observation at its track's X, NaN when the observation's image is not registered or the track has no
+ * point.  counts [6] int64: the tracks that have a point, by status.  Fed the X of sfm_triangulate_tracks with the same
+ * cameras and gates, a track of status 0, 3, 4 or 5 gets the same status, the same n_views and the same max_err bits.
+ * Everything runs on the handle's stream without host synchronisation. */
+enum { SFM_EVAL_NO_POINT = -1 };
+int sfm_tracks_evaluate(sfm_handle h, const double* proj, int32_t n_cams, const int32_t* cam_of_image, int32_t n_img,
+                        const int64_t* kp_ptr, const double* kp_xy, int64_t n_nodes, const int64_t* track_ptr,
+                        int64_t n_tracks, const int32_t* obs_image, const int32_t* obs_kp, int64_t n_obs,
+                        const double* X, const uint8_t* has_point, int32_t min_views, double max_error,
+                        double min_angle_deg, int32_t* status, int32_t* n_views, double* max_err,
+                        double* obs_err /* [n_obs], may be NULL */, int64_t* counts /* [6] */,
+                        void* workspace, int64_t workspace_bytes);
+
+/* ------------------------------------------------------------------- 2D-3D correspondences of the unregistered images
+ * What sfm_pnp_ransac consumes, taken from the tracks by index.  Node n of image i (kp_ptr[i] <= n < kp_ptr[i+1]) is
+ * listed when cam_of_image[i] < 0, 0 <= node_track[n] < n_tracks and has_point[node_track[n]] != 0: integers only, so a
+ * non-finite X or pixel is still listed (the PnP stage never counts such a point as an inlier).  A node that lies in no
+ * image is not listed.  The listed nodes are written in ascending node id, so the lists of all images are contiguous
+ * segments: seg_ptr[i] (device int64 [n_img+1]) is the number of listed nodes below kp_ptr[i] (segments of registered
+ * images are empty) and *total (device int64) = seg_ptr[n_img].  For entry k < min(total, cap_corr): corr_node[k],
+ * corr_track[k], corr_X[k] = X[track] (a bit copy), corr_uv[k] = (float)kp_xy[node] (round to nearest).  Nothing is
+ * written at or beyond cap_corr; seg_ptr and total are always complete, so the caller can retry with a larger buffer.
+ * seg_ptr, corr_X and corr_uv are the first arguments of sfm_pnp_ransac as they are.  Flag, exclusive scan and scatter
+ * over the nodes in integers: the output bytes are a function of the inputs alone.  SFM_ERR_ARG for n_nodes >= 2^31, a
+ * negative size, a NULL required pointer or a workspace that is too small; n_nodes == 0 writes seg_ptr = 0 and total = 0.
+ * Everything runs on the handle's stream; nothing is read back and the stream is not synchronised. */
+int sfm_resection_workspace_bytes(int64_t n_nodes, int64_t* bytes_host);
+int sfm_tracks_resection(sfm_handle h, const int64_t* kp_ptr, int32_t n_img, int64_t n_nodes, const double* kp_xy,
+                         const int32_t* node_track, const int32_t* cam_of_image, const double* X /* [n_tracks][3] */,
+                         const uint8_t* has_point /* [n_tracks] */, int64_t n_tracks,
+                         int64_t* seg_ptr /* [n_img+1] */, int32_t* corr_node, int32_t* corr_track,
+                         double* corr_X /* [cap][3] */, float* corr_uv /* [cap][2] */, int64_t cap_corr,
+                         int64_t* total, void* workspace, int64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

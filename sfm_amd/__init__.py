@@ -4,3 +4,4 @@ from .twoview import FundamentalMixin, estimate_fundamental_batched, find_fundam
 from .pose import InitialPairMixin, recover_pose, recover_pose_batched  # noqa: F401
 from .tracks import Tracks, build_tracks, tracks_from_pair_files  # noqa: F401
 from .triangulate import Triangulation, triangulate_tracks, triangulate_tracks_raw  # noqa: F401
+from .incremental import Reconstruction, evaluate_tracks, reconstruct_tracks, resection_lists  # noqa: F401

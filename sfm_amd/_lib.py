@@ -26,6 +26,7 @@ UV_AS_GIVEN, UV_REFERENCE_PAIRING = 0, 1
 TRACKS_DROP, TRACKS_KEEP = 0, 1
 # status of a track from sfm_triangulate_tracks (SFM_TRI_* of include/sfm_amd.h): the first failing gate
 (TRI_OK, TRI_TOO_FEW_VIEWS, TRI_DEGENERATE, TRI_BEHIND, TRI_LOW_ANGLE, TRI_HIGH_ERROR) = range(6)
+EVAL_NO_POINT = -1          # sfm_tracks_evaluate: the track has no point to judge (SFM_EVAL_NO_POINT)
 
 
 class BADesc(C.Structure):
@@ -141,6 +142,10 @@ SIGNATURES = {
     "sfm_triangulate_tracks_workspace_bytes": (C.c_int, [i32, C.POINTER(i64)]),
     "sfm_triangulate_tracks": (C.c_int, [vp, vp, i32, vp, i32, vp, vp, i64, vp, i64, vp, vp, i64, i32, i32, f64, f64,
                                          vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_tracks_evaluate": (C.c_int, [vp, vp, i32, vp, i32, vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, i32, f64, f64,
+                                      vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_resection_workspace_bytes": (C.c_int, [i64, C.POINTER(i64)]),
+    "sfm_tracks_resection": (C.c_int, [vp, vp, i32, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64]),
 }
 
 _lib = None

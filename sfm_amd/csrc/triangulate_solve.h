@@ -4,6 +4,8 @@
 //   tri::solve           linear stage (streaming Givens QR of the DLT rows, jacobi::null4 of the factor; a two-view track
 //                        goes through jacobi::dlt2 and gives the bits of sfm_triangulate2), a fixed number of Gauss-Newton
 //                        steps on the reprojection error, then the gates of include/sfm_amd.h (SFM_TRI_*)
+//   tri::gates           the gate tail alone at a given X: cheirality, triangulation angle, reprojection error
+//   tri::judge           views, finiteness, then tri::gates: a point that was not triangulated here (sfm_tracks_evaluate)
 // The observations come from a source `src` that is walked several times, always in the track's own order:
 //   bool src.get(k, tri::Obs&)        false: observation k is not used (its image is not registered)
 //   bool src.centre(k, double (&C)[3])   the same answer, the camera centre alone (the pairwise angle test)
@@ -64,6 +66,19 @@ SFM_HD void fold_row(double (&R)[4][4], double (&r)[4]) {
   }
 }
 
+// reprojection error of one observation at X (e2 its square, hw the depth P[2].(X,1)): the one formula behind every gate
+SFM_HD double reproj(const Obs& o, const double (&X)[3], double& hw, double& e2) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double hx = o.P[0] * X[0] + o.P[1] * X[1] + o.P[2] * X[2] + o.P[3];
+  const double hy = o.P[4] * X[0] + o.P[5] * X[1] + o.P[6] * X[2] + o.P[7];
+  hw = o.P[8] * X[0] + o.P[9] * X[1] + o.P[10] * X[2] + o.P[11];
+  const double du = hx / hw - o.x, dv = hy / hw - o.y;
+  e2 = du * du + dv * dv;
+  return sqrt(e2);
+}
+
 // cost = sum of squared reprojection errors at X over the used observations, max_err the largest error (NaN once one is
 // NaN), behind: some depth P[2].(X,1) <= 0, high: some error > max_error
 template <class Src>
@@ -76,17 +91,43 @@ SFM_HD void evaluate(const Src& src, int n_raw, const double (&X)[3], double max
   cost = 0.0; max_err = 0.0; behind = false; high = false;
   for (int k = 0; k < n_raw; ++k) {
     if (!src.get(k, o)) continue;
-    const double hx = o.P[0] * X[0] + o.P[1] * X[1] + o.P[2] * X[2] + o.P[3];
-    const double hy = o.P[4] * X[0] + o.P[5] * X[1] + o.P[6] * X[2] + o.P[7];
-    const double hw = o.P[8] * X[0] + o.P[9] * X[1] + o.P[10] * X[2] + o.P[11];
-    const double du = hx / hw - o.x, dv = hy / hw - o.y;
-    const double e2 = du * du + dv * dv;
-    const double e = sqrt(e2);
+    double hw, e2;
+    const double e = reproj(o, X, hw, e2);
     cost += e2;
     max_err = (e > max_err || e != e) ? e : max_err;
     behind = behind || (hw <= 0.0);
     high = high || (e > max_error);
   }
+}
+
+// The gates of a point X, in their order: evaluate, BEHIND, LOW_ANGLE (when check_angle: no pair of used views has
+// d_i.d_j / (|d_i||d_j|) <= cos_min_angle with d = X - C), HIGH_ERROR.  cost and max_err as evaluate gives them.
+template <class Src>
+SFM_HD int gates(const Src& src, int n_raw, const double (&X)[3], double max_error, bool check_angle, double cos_min_angle,
+                 double& cost, double& max_err) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  bool behind = false, high = false;
+  evaluate(src, n_raw, X, max_error, cost, max_err, behind, high);
+  if (behind) return SFM_TRI_BEHIND;
+  if (check_angle) {
+    bool wide = false;
+    double Ci[3], Cj[3];
+    for (int i = 0; i < n_raw && !wide; ++i) {
+      if (!src.centre(i, Ci)) continue;
+      const double a0 = X[0] - Ci[0], a1 = X[1] - Ci[1], a2 = X[2] - Ci[2];
+      const double na = sqrt(a0 * a0 + a1 * a1 + a2 * a2);
+      for (int j = i + 1; j < n_raw; ++j) {
+        if (!src.centre(j, Cj)) continue;
+        const double b0 = X[0] - Cj[0], b1 = X[1] - Cj[1], b2 = X[2] - Cj[2];
+        const double nb = sqrt(b0 * b0 + b1 * b1 + b2 * b2);
+        if ((a0 * b0 + a1 * b1 + a2 * b2) / (na * nb) <= cos_min_angle) { wide = true; break; }
+      }
+    }
+    if (!wide) return SFM_TRI_LOW_ANGLE;
+  }
+  return high ? SFM_TRI_HIGH_ERROR : SFM_TRI_OK;
 }
 
 // Returns the status (SFM_TRI_*).  X and max_err are NaN for TOO_FEW_VIEWS and DEGENERATE and written for every other
@@ -206,31 +247,38 @@ SFM_HD int solve(const Src& src, int n_raw, int min_views, int refine_iters, dou
 
   // ---- the gates, on the refined point unless it costs more than the linear one
   double cost = 0.0;
-  bool behind = false, high = false;
-  evaluate(src, n_raw, Xc, max_error, cost, max_err, behind, high);
+  int st = gates(src, n_raw, Xc, max_error, check_angle, cos_min_angle, cost, max_err);
   if (refine_iters > 0 && cost > cost_lin) {
     Xc[0] = Xl[0]; Xc[1] = Xl[1]; Xc[2] = Xl[2];
-    evaluate(src, n_raw, Xc, max_error, cost, max_err, behind, high);
+    st = gates(src, n_raw, Xc, max_error, check_angle, cos_min_angle, cost, max_err);
   }
   X[0] = Xc[0]; X[1] = Xc[1]; X[2] = Xc[2];
-  if (behind) return SFM_TRI_BEHIND;
-  if (check_angle) {
-    bool wide = false;
-    double Ci[3], Cj[3];
-    for (int i = 0; i < n_raw && !wide; ++i) {
-      if (!src.centre(i, Ci)) continue;
-      const double a0 = Xc[0] - Ci[0], a1 = Xc[1] - Ci[1], a2 = Xc[2] - Ci[2];
-      const double na = sqrt(a0 * a0 + a1 * a1 + a2 * a2);
-      for (int j = i + 1; j < n_raw; ++j) {
-        if (!src.centre(j, Cj)) continue;
-        const double b0 = Xc[0] - Cj[0], b1 = Xc[1] - Cj[1], b2 = Xc[2] - Cj[2];
-        const double nb = sqrt(b0 * b0 + b1 * b1 + b2 * b2);
-        if ((a0 * b0 + a1 * b1 + a2 * b2) / (na * nb) <= cos_min_angle) { wide = true; break; }
-      }
-    }
-    if (!wide) return SFM_TRI_LOW_ANGLE;
+  return st;
+}
+
+// A point that came from somewhere else (a bundle adjustment moved it) judged by the gates of solve, in solve's order:
+// too few views, degenerate (a non-finite input of a used view or a non-finite X), then gates().  max_err is NaN for the
+// first two and the largest reprojection error otherwise.  Fed the X solve returned with status OK, BEHIND, LOW_ANGLE or
+// HIGH_ERROR it runs the operations of solve's last gates() call on the same numbers: same status, same max_err bits.
+template <class Src>
+SFM_HD int judge(const Src& src, int n_raw, int min_views, const double (&X)[3], double max_error, bool check_angle,
+                 double cos_min_angle, int& n_views, double& max_err) {
+  max_err = NAN;
+  n_views = 0;
+  Obs o;
+  bool finite = finite3(X);
+  for (int k = 0; k < n_raw; ++k) {
+    if (!src.get(k, o)) continue;
+    ++n_views;
+    bool f = std::isfinite(o.x) && std::isfinite(o.y) && finite3(o.C);
+#pragma unroll
+    for (int e = 0; e < 12; ++e) f = f && std::isfinite(o.P[e]);
+    finite = finite && f;
   }
-  return high ? SFM_TRI_HIGH_ERROR : SFM_TRI_OK;
+  if (n_views < min_views) return SFM_TRI_TOO_FEW_VIEWS;
+  if (!finite) return SFM_TRI_DEGENERATE;
+  double cost = 0.0;
+  return gates(src, n_raw, X, max_error, check_angle, cos_min_angle, cost, max_err);
 }
 
 }  // namespace tri

@@ -208,8 +208,8 @@ class BundleAdjustMixin:
 class StructureFromMotion(BundleAdjustMixin, DriverMixin, PnPMixin, InitialPairMixin, ReconstructionIOMixin):
     """Minimal stand-alone holder of the reconstruction state (sfm_reconstruction.py:40-59) for
     users who only need the hot path, the driver steps either side of it (sfm_amd.driver), the camera
-    registration (sfm_amd.pnp) and the choice and set-up of the initial pair (sfm_amd.pose); the incremental driver
-    loop itself stays the reference's."""
+    registration (sfm_amd.pnp) and the choice and set-up of the initial pair (sfm_amd.pose).  The reference's own
+    incremental driver loop stays the reference's; `reconstruct_from_tracks` is the track-based loop of this package."""
 
     def __init__(self, data_dir=None, order="reference", cam_dim=10, device=0, precision="fp64"):
         self.data_dir = Path(data_dir) if data_dir is not None else None
@@ -228,6 +228,21 @@ class StructureFromMotion(BundleAdjustMixin, DriverMixin, PnPMixin, InitialPairM
         self.ba_cam_dim = cam_dim
         self.ba_device = device
         self.ba_precision = precision
+
+    def reconstruct_from_tracks(self, tracks, keypoints, **options):
+        """The incremental loop on a `Tracks` object (sfm_amd.incremental.reconstruct_tracks) with `self.K`: fills
+        `self.poses` ({image_id: (R, t [3,1])}), `self.points3D` and `self.point_tracks` in the reference's shapes, image
+        ids through `tracks.image_ids`, and returns the `Reconstruction`."""
+        from .incremental import reconstruct_tracks
+        options.setdefault("device", self.ba_device)
+        options.setdefault("image_size", (self.image_width, self.image_height))
+        rec = reconstruct_tracks(tracks, keypoints, self.K, **options)
+        self.poses, self.points3D, self.point_tracks = rec.as_state()
+        self.K = rec.K.copy()
+        ids = tracks.image_ids if tracks.image_ids is not None else list(range(len(tracks.kp_ptr) - 1))
+        self.constructed = [f"{ids[i]:04d}.ppm" for i in rec.order]
+        logging.info(f"Registered {len(rec.order)} of {len(ids)} images, {len(self.points3D)} points")
+        return rec
 
     def find_image_pairs(self, image_id):
         """Pairs of `image_id` whose other image is already reconstructed (sfm_reconstruction.py:551-580):

@@ -133,20 +133,11 @@ def _cameras(tracks, proj_or_poses, K, registered):
     return proj.reshape(-1, 12), cam_of_image
 
 
-def triangulate_tracks(tracks, keypoints, proj_or_poses, K=None, registered=None, min_views=2, refine_iters=5,
-                       max_error=TRIANGULATION_MAX_ERROR, min_angle_deg=0.0, device=0):
-    """Triangulate every track.  keypoints: per image position what `twoview.keypoints_xy` accepts ([n,2] array or
-    cv2.KeyPoints); cameras: [n,3,4] projections K[R|t] with `registered` (the image position of each; default: one per
-    image, in order) or a {image_id: (R, t)} dict with K, mapped to positions through `tracks.image_ids`.  An observation in
-    an image without a camera is ignored.  Everything is validated on the host first (ValueError); returns a Triangulation."""
+def keypoint_table(tracks, keypoints):
+    """kp_xy [n_nodes,2] float64: the pixels by node id (node = kp_ptr[image] + keypoint).  ValueError for an image with
+    fewer keypoints than the tracks count or an observation that names a keypoint outside its image."""
     from .twoview import keypoints_xy
-    _check_options(min_views, refine_iters, max_error, min_angle_deg)
     n_img = len(tracks.kp_ptr) - 1
-    if len(keypoints) != n_img:
-        raise ValueError(f"{len(keypoints)} keypoint lists for {n_img} images")
-    if tracks.n_obs and (tracks.image.min() < 0 or tracks.image.max() >= n_img):
-        raise ValueError("an observation names an image out of range")
-    proj, cam_of_image = _cameras(tracks, proj_or_poses, K, registered)
     counts = np.diff(tracks.kp_ptr)
     kp_xy = np.zeros((int(tracks.kp_ptr[-1]), 2), dtype=np.float64)
     for i in range(n_img):
@@ -161,6 +152,23 @@ def triangulate_tracks(tracks, keypoints, proj_or_poses, K=None, registered=None
         kp_xy[tracks.kp_ptr[i]:tracks.kp_ptr[i + 1]] = xy[:counts[i]]
     if tracks.n_obs and (tracks.keypoint.min() < 0 or (tracks.keypoint >= counts[tracks.image]).any()):
         raise ValueError("an observation names a keypoint outside its image")
+    return kp_xy
+
+
+def triangulate_tracks(tracks, keypoints, proj_or_poses, K=None, registered=None, min_views=2, refine_iters=5,
+                       max_error=TRIANGULATION_MAX_ERROR, min_angle_deg=0.0, device=0):
+    """Triangulate every track.  keypoints: per image position what `twoview.keypoints_xy` accepts ([n,2] array or
+    cv2.KeyPoints); cameras: [n,3,4] projections K[R|t] with `registered` (the image position of each; default: one per
+    image, in order) or a {image_id: (R, t)} dict with K, mapped to positions through `tracks.image_ids`.  An observation in
+    an image without a camera is ignored.  Everything is validated on the host first (ValueError); returns a Triangulation."""
+    _check_options(min_views, refine_iters, max_error, min_angle_deg)
+    n_img = len(tracks.kp_ptr) - 1
+    if len(keypoints) != n_img:
+        raise ValueError(f"{len(keypoints)} keypoint lists for {n_img} images")
+    if tracks.n_obs and (tracks.image.min() < 0 or tracks.image.max() >= n_img):
+        raise ValueError("an observation names an image out of range")
+    proj, cam_of_image = _cameras(tracks, proj_or_poses, K, registered)
+    kp_xy = keypoint_table(tracks, keypoints)
     out = triangulate_tracks_raw(proj, cam_of_image, tracks.kp_ptr, kp_xy, tracks.track_ptr, tracks.image, tracks.keypoint,
                                  min_views, refine_iters, max_error, min_angle_deg, device)
     uv = kp_xy[tracks.kp_ptr[tracks.image] + tracks.keypoint] if tracks.n_obs else np.zeros((0, 2))

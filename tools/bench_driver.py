@@ -2,10 +2,11 @@
 """Device-time measurement of the driver-row kernels with inputs resident in HBM:
 association (pair tests/s), two-view triangulation (tracks/s), epipolar verification (matches/s), and the batched
 fundamental-matrix RANSAC beside the batched matcher it follows in the pair loop, the batched PnP RANSAC of the
-camera registration, the batched relative-pose recovery of the initial-pair scan, the track building and the N-view
-triangulation of the tracks.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
+camera registration, the batched relative-pose recovery of the initial-pair scan, the track building, the N-view
+triangulation of the tracks, and the resection lists, the gate evaluation and the incremental loop on top of them.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
 functions to time on a bounded sample of the same inputs (this tool itself never imports oracle/).
-usage: python tools/bench_driver.py [--reps 20] [--fundamental-only | --pnp-only | --pose-only | --tracks-only | --triangulate-only]"""
+usage: python tools/bench_driver.py [--reps 20] [--fundamental-only | --pnp-only | --pose-only | --tracks-only | --triangulate-only |
+       --incremental-only]"""
 import argparse
 import ctypes as C
 import json
@@ -480,19 +481,12 @@ def _triangulate_case(name, proj, cam_idx, uv, lengths, launch_bound):
                 track_ptr=track_ptr, obs_image=cam_idx.astype(np.int32), obs_kp=obs_kp, launch_bound=launch_bound)
 
 
-def measure_triangulate(reps=20, emit=None):
-    """sfm_triangulate_tracks, inputs resident in HBM, device time of the whole call (camera-centre prologue, counter reset
-    and the track kernel) by HIP events around `reps` calls after warm-up, on (a) a set shaped like the shipped tracks (35
-    images, 1,641 tracks of 2 to 12 views, 4 on average: launch-bound) and (b) 200 cameras / 100,000 points / 10 views
-    each from sfm_amd.synth with both visibility patterns of bench.py, for refine_iters 0 and 5.  Per row: ms,
-    observations per second and the share of the HBM stream floor (every input array read once and every output written
-    once, over HBM_STREAM_BPS); beside it the time of sfm_triangulate2 on as many two-view tracks as an anchor."""
-    import torch
-    from sfm_amd import _lib, synth
-    from sfm_amd.driver import _dev, _p
+def _triangulate_cases():
+    """The workloads of measure_triangulate and measure_incremental: (a) a set shaped like the shipped tracks (35 images,
+    1,641 tracks of 2 to 12 views, 4 on average), (b) 200 cameras / 100,000 points / 10 views each from sfm_amd.synth with
+    both visibility patterns of bench.py."""
+    from sfm_amd import synth
     from sfm_amd.rotation import rodrigues
-    h = _lib.get_handle(0)
-    dev = torch.device("cuda", 0)
     rng = np.random.default_rng(0)
 
     def projections(sc):
@@ -507,6 +501,22 @@ def measure_triangulate(reps=20, emit=None):
         sc = synth.make_scene(200, 100000, obs_per_point=10, seed=1004, noise_px=0.5, visibility=vis)
         cases.append(_triangulate_case(f"synth_200_cameras_100000_points_{vis}", projections(sc), sc.cam_idx, sc.uv,
                                        np.full(100000, 10, np.int64), False))
+    return cases
+
+
+def measure_triangulate(reps=20, emit=None):
+    """sfm_triangulate_tracks, inputs resident in HBM, device time of the whole call (camera-centre prologue, counter reset
+    and the track kernel) by HIP events around `reps` calls after warm-up, on (a) a set shaped like the shipped tracks (35
+    images, 1,641 tracks of 2 to 12 views, 4 on average: launch-bound) and (b) 200 cameras / 100,000 points / 10 views
+    each from sfm_amd.synth with both visibility patterns of bench.py, for refine_iters 0 and 5.  Per row: ms,
+    observations per second and the share of the HBM stream floor (every input array read once and every output written
+    once, over HBM_STREAM_BPS); beside it the time of sfm_triangulate2 on as many two-view tracks as an anchor."""
+    import torch
+    from sfm_amd import _lib
+    from sfm_amd.driver import _dev, _p
+    h = _lib.get_handle(0)
+    dev = torch.device("cuda", 0)
+    cases = _triangulate_cases()
     results = []
     for c in cases:
         n_cams, n_tracks, n_obs = len(c["proj"]), len(c["track_ptr"]) - 1, len(c["obs_image"])
@@ -556,6 +566,127 @@ def measure_triangulate(reps=20, emit=None):
     return results
 
 
+def _arc_scene(n_cams, n_pts, seed=21, noise=0.5):
+    """The scene of the loop tests at any size: cameras on an arc of 2 radians around the unit cube looking at its centre,
+    K of StructureFromMotion, points uniform in the cube seen by 3/8 to 8/8 of the cameras, pixel noise 0.5 px.  Returns
+    (Tracks, keypoints per image, K)."""
+    from sfm_amd import Tracks
+    rng = np.random.default_rng(seed)
+    K = np.array([[1228.0, 0, 512], [0, 1228.0, 384], [0, 0, 1]])
+    target = np.array([0.5, 0.5, 0.5])
+    proj = []
+    for a in np.linspace(-1.0, 1.0, n_cams):
+        c = target + [6.0 * np.sin(a), 1.5, -6.0 * np.cos(a)]
+        z = (target - c) / np.linalg.norm(target - c)
+        x = np.cross([0.0, 1.0, 0.0], z); x /= np.linalg.norm(x)
+        R = np.stack([x, np.cross(z, x), z])
+        proj.append(K @ np.hstack([R, (-R @ c)[:, None]]))
+    proj = np.stack(proj)
+    X = rng.uniform(0, 1, (n_pts, 3))
+    lengths = np.rint(rng.integers(3, 9, n_pts) * (n_cams / 8.0)).astype(np.int64)
+    cam_idx = np.concatenate([np.sort(rng.choice(n_cams, int(n), replace=False)) for n in lengths])
+    pt = np.repeat(np.arange(n_pts), lengths)
+    hm = np.einsum("oij,oj->oi", proj[cam_idx], np.hstack([X[pt], np.ones((len(pt), 1))]))
+    uv = hm[:, :2] / hm[:, 2:3] + rng.normal(0, noise, (len(pt), 2))
+    c = _triangulate_case("arc", proj, cam_idx, uv, lengths, False)
+    T = Tracks(c["kp_ptr"], c["track_ptr"], c["obs_image"], c["obs_kp"])
+    return T, [c["kp_xy"][c["kp_ptr"][i]:c["kp_ptr"][i + 1]] for i in range(n_cams)], K
+
+
+def measure_incremental(reps=20, emit=None):
+    """sfm_tracks_resection and sfm_tracks_evaluate, inputs resident in HBM, device time of the whole call by HIP events
+    around `reps` calls after warm-up, on the workloads of measure_triangulate (points: those sfm_triangulate_tracks gives;
+    for the resection every second image is unregistered), beside the wall time of the NumPy restatement
+    (tests/incremental_reference.py) on the same arrays; then the wall time of reconstruct_tracks on the synthetic scene
+    of the loop tests at 36 cameras / 2,000 points."""
+    import torch
+    from sfm_amd import _lib, reconstruct_tracks
+    from sfm_amd.driver import _dev, _p
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    try:
+        import incremental_reference as ir
+    except ImportError:
+        ir = None
+    h = _lib.get_handle(0)
+    dev = torch.device("cuda", 0)
+    results = []
+    for c in _triangulate_cases():
+        n_cams, n_tracks, n_obs = len(c["proj"]), len(c["track_ptr"]) - 1, len(c["obs_image"])
+        d = {k: _dev(c[k], t, dev) for k, t in (("proj", np.float64), ("cam_of_image", np.int32), ("kp_ptr", np.int64),
+                                                ("kp_xy", np.float64), ("track_ptr", np.int64), ("obs_image", np.int32),
+                                                ("obs_kp", np.int32))}
+        need = C.c_int64(); h.lib.sfm_triangulate_tracks_workspace_bytes(n_cams, C.byref(need))
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        X = torch.empty((n_tracks, 3), dtype=torch.float64, device=dev); me = torch.empty(n_tracks, dtype=torch.float64, device=dev)
+        st = torch.empty(n_tracks, dtype=torch.int32, device=dev); nv = torch.empty(n_tracks, dtype=torch.int32, device=dev)
+        counts = torch.empty(6, dtype=torch.int64, device=dev)
+        h.call("sfm_triangulate_tracks", _p(d["proj"]), n_cams, _p(d["cam_of_image"]), n_cams, _p(d["kp_ptr"]), _p(d["kp_xy"]),
+               n_obs, _p(d["track_ptr"]), n_tracks, _p(d["obs_image"]), _p(d["obs_kp"]), n_obs, 2, 5, C.c_double(4.0),
+               C.c_double(1.0), _p(X), _p(st), _p(nv), _p(me), _p(counts), _p(ws), need.value)
+        has = (st == 0).to(torch.uint8)
+        X_h, has_h = X.cpu().numpy(), has.cpu().numpy()
+        obs_err = torch.empty(n_obs, dtype=torch.float64, device=dev)
+
+        def evaluate():
+            h.call("sfm_tracks_evaluate", _p(d["proj"]), n_cams, _p(d["cam_of_image"]), n_cams, _p(d["kp_ptr"]), _p(d["kp_xy"]),
+                   n_obs, _p(d["track_ptr"]), n_tracks, _p(d["obs_image"]), _p(d["obs_kp"]), n_obs, _p(X), _p(has), 2,
+                   C.c_double(4.0), C.c_double(1.0), _p(st), _p(nv), _p(me), _p(obs_err), _p(counts), _p(ws), need.value)
+        for _ in range(3):
+            evaluate()
+        sec = timed(evaluate, reps)
+        row = {"kernel": "tracks_evaluate", "case": c["name"], "cameras": n_cams, "tracks": n_tracks, "observations": n_obs,
+               "ms": sec * 1e3, "observations_per_s": n_obs / sec, "ok_tracks": int(counts.cpu().numpy()[0])}
+        if ir is not None:
+            t0 = time.perf_counter()
+            ref = ir.evaluate(c["proj"], c["cam_of_image"], c["kp_ptr"], c["kp_xy"], c["track_ptr"], c["obs_image"], c["obs_kp"],
+                              np.where(has_h[:, None] != 0, X_h, 0.0), has_h, max_error=4.0, min_angle_deg=1.0)
+            row["numpy_ms"] = (time.perf_counter() - t0) * 1e3
+            row["status_equal_numpy"] = bool(np.array_equal(ref["status"], st.cpu().numpy()))
+        results.append(row)
+        if emit:
+            emit(row)
+        # resection: every second image unregistered
+        cam = c["cam_of_image"].copy()
+        cam[::2] = -1
+        node_track = np.full(n_obs, -1, np.int32)
+        node_track[c["kp_ptr"][c["obs_image"]] + c["obs_kp"]] = np.repeat(np.arange(n_tracks), np.diff(c["track_ptr"]))
+        d_cam, d_nt = _dev(cam, np.int32, dev), _dev(node_track, np.int32, dev)
+        need_r = C.c_int64(); h.lib.sfm_resection_workspace_bytes(n_obs, C.byref(need_r))
+        ws_r = torch.empty(need_r.value, dtype=torch.uint8, device=dev)
+        seg_ptr = torch.empty(n_cams + 1, dtype=torch.int64, device=dev); total = torch.empty(1, dtype=torch.int64, device=dev)
+        cn = torch.empty(n_obs, dtype=torch.int32, device=dev); ct = torch.empty(n_obs, dtype=torch.int32, device=dev)
+        cX = torch.empty((n_obs, 3), dtype=torch.float64, device=dev); cuv = torch.empty((n_obs, 2), dtype=torch.float32, device=dev)
+
+        def resection():
+            h.call("sfm_tracks_resection", _p(d["kp_ptr"]), n_cams, n_obs, _p(d["kp_xy"]), _p(d_nt), _p(d_cam), _p(X), _p(has),
+                   n_tracks, _p(seg_ptr), _p(cn), _p(ct), _p(cX), _p(cuv), n_obs, _p(total), _p(ws_r), need_r.value)
+        for _ in range(3):
+            resection()
+        sec = timed(resection, reps)
+        n_listed = int(total.item())
+        row = {"kernel": "tracks_resection", "case": c["name"], "images": n_cams, "nodes": n_obs, "listed": n_listed,
+               "ms": sec * 1e3, "nodes_per_s": n_obs / sec}
+        if ir is not None:
+            t0 = time.perf_counter()
+            ref = ir.resection_lists(c["kp_ptr"], c["kp_xy"], node_track, cam, X_h, has_h)
+            row["numpy_ms"] = (time.perf_counter() - t0) * 1e3
+            row["equal_numpy"] = bool(ref["total"] == n_listed and np.array_equal(ref["corr_node"], cn[:n_listed].cpu().numpy()))
+        results.append(row)
+        if emit:
+            emit(row)
+    T, keypoints, K = _arc_scene(36, 2000)
+    reconstruct_tracks(T, keypoints, K)                                        # warm-up: module loads, allocator
+    t0 = time.perf_counter()
+    rec = reconstruct_tracks(T, keypoints, K)
+    row = {"kernel": "reconstruct_tracks", "case": "arc_36_cameras_2000_points", "observations": int(T.n_obs),
+           "wall_s": time.perf_counter() - t0, "registered": len(rec.order), "points": int(rec.has_point.sum()),
+           "bundle_adjustments": sum(1 for e in rec.log if e.get("ba"))}
+    results.append(row)
+    if emit:
+        emit(row)
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -566,9 +697,10 @@ def main():
     ap.add_argument("--pose-only", action="store_true", help="only the relative-pose recovery rows")
     ap.add_argument("--tracks-only", action="store_true", help="only the track-building rows")
     ap.add_argument("--triangulate-only", action="store_true", help="only the N-view track triangulation rows")
+    ap.add_argument("--incremental-only", action="store_true", help="only the resection / evaluation / incremental-loop rows")
     a = ap.parse_args()
     emit = lambda d: print(json.dumps(d), flush=True)
-    only = a.fundamental_only or a.pnp_only or a.pose_only or a.tracks_only or a.triangulate_only
+    only = a.fundamental_only or a.pnp_only or a.pose_only or a.tracks_only or a.triangulate_only or a.incremental_only
     if not only:
         measure(a.reps, a.tracks, a.corr, emit=emit)
     if a.fundamental_only or not only:
@@ -581,6 +713,8 @@ def main():
         measure_tracks(a.reps, emit=emit)
     if a.triangulate_only or not only:
         measure_triangulate(a.reps, emit=emit)
+    if a.incremental_only or not only:
+        measure_incremental(a.reps, emit=emit)
 
 
 if __name__ == "__main__":

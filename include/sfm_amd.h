@@ -59,7 +59,12 @@ enum { SFM_PROF_LIN_OBS = 0,   /* k_lin_obs: residual + Jacobian + Huber scaling
        SFM_PROF_FUND_HYP = 10, /* k_fund_hypotheses alone (inside sfm_fund_ransac) */
        SFM_PROF_PNP_HYP = 11,  /* k_pnp_hypotheses alone (inside sfm_pnp_ransac) */
        SFM_PROF_POSE_VOTE = 12, /* k_pose_vote alone (inside sfm_pose_recover) */
-       SFM_PROF_COUNT = 13 };
+       SFM_PROF_FEAT_SCORE = 13,    /* k_feat_score alone (inside sfm_features_detect) */
+       SFM_PROF_FEAT_SELECT = 14,   /* suppression, cut, ties and the row scan (the rest of sfm_features_detect) */
+       SFM_PROF_FEAT_SCATTER = 15,  /* k_feat_scatter (inside sfm_features_describe) */
+       SFM_PROF_FEAT_BLUR = 16,     /* k_feat_blur */
+       SFM_PROF_FEAT_DESCRIBE = 17, /* k_feat_describe */
+       SFM_PROF_COUNT = 18 };
 int sfm_set_profiling(sfm_handle h, int enabled);
 int sfm_profile_read(sfm_handle h, int slot, double* total_ms_host, int64_t* count_host);
 
@@ -593,6 +598,71 @@ int sfm_tracks_resection(sfm_handle h, const int64_t* kp_ptr, int32_t n_img, int
                          int64_t* seg_ptr /* [n_img+1] */, int32_t* corr_node, int32_t* corr_track,
                          double* corr_X /* [cap][3] */, float* corr_uv /* [cap][2] */, int64_t cap_corr,
                          int64_t* total, void* workspace, int64_t workspace_bytes);
+
+/* ------------------------------------------------------------------- feature detection and description, batched
+ * The detect_features step of the reference (find_matches.py:74-139: FAST with threshold 20, ORB descriptors, the
+ * silhouette-mask filter) for all images of a data set in two calls with one read-back between them.  The detector is
+ * FAST-9/16 to its published definition.  The descriptor is this library's own steered binary descriptor - OpenCV's
+ * learned sampling table is not part of this project - specified here completely; every step is integer arithmetic.
+ *
+ * Input: n_img gray uint8 images, each with its own height and width, rows contiguous, all in one device buffer; image i
+ * starts at img_off[i] and ends at or before img_off[i+1].  masks (may be NULL) has the same layout: a keypoint is kept
+ * only where mask[y, x] > 0.  img_off [n_img+1] int64, heights / widths [n_img] int32 are HOST arrays (the calls size
+ * their launches from them and check them before any device work).  An image with h < 2 edge + 1 or w < 2 edge + 1 has
+ * no keypoints; no kernel reads outside an image.
+ *
+ * FAST-9/16: the circle is (0,3) (1,3) (2,2) (3,1) (3,0) (3,-1) (2,-2) (1,-3) (0,-3) (-1,-3) (-2,-2) (-3,-1) (-3,0)
+ *   (-3,1) (-2,2) (-1,3) as (dx, dy); d_i = I(circle_i) - I(p); b = the maximum, over the 16 arcs of 9 contiguous circle
+ *   pixels and both polarities, of the smallest +d_i (or the smallest -d_i) on the arc.  p is a corner iff b > threshold
+ *   (1 <= threshold <= 254); its score is b - 1, the largest threshold at which it still passes (uint8); a non-corner
+ *   and every pixel closer than 3 to the image border score 0.
+ * Suppression: a corner is kept iff its score is strictly greater than the scores of all 8 neighbours (two equal adjacent
+ *   maxima both go), taken from the whole image: a corner outside the gate or under the mask still suppresses its
+ *   neighbour.  Then the gate edge <= x < w - edge, edge <= y < h - edge (edge >= 16), then the mask.
+ * Selection: max_features = 0 keeps all.  An image with more than max_features survivors gets the cut score s with
+ *   #(score > s) < max_features <= #(score >= s) from a 256-bin histogram; all above s stay, and of those equal to s the
+ *   first max_features - #(score > s) in row-major order.  Nothing is sorted.
+ * Order: the keypoints of an image are row-major (y ascending, then x); image i owns kp_ptr[i] .. kp_ptr[i+1].  The
+ *   output bytes are the same from run to run and do not depend on the launch geometry or on the other images.
+ * Orientation: m10 = sum dx I, m01 = sum dy I over the disc dx^2 + dy^2 <= 225 of the unblurred image (exact in int32);
+ *   a = atan2((double)m01, (double)m10), 0 when both are 0; bin = ((int)floor(a * 15 / pi + 0.5) mod 30 + 30) mod 30;
+ *   the angle is 12 bin degrees.
+ * Blur: separable 7-tap, weights (18, 33, 49, 56, 49, 33, 18) (sum 256), borders reflect-101,
+ *   B = (sum_y sum_x w_y w_x I + 32768) >> 16: exact in int32, rounded once.
+ * Descriptor: rot [30][256][4] int8 holds (ax, ay, bx, by) per bin; bit k = B(p + a_k) < B(p + b_k) with the table of
+ *   the keypoint's bin, stored in byte k / 8 at bit position k % 8: 32 bytes in the layout of cv2.ORB.
+ * Pattern (host only): sfm_orb_default_pattern writes this library's base table - 256 pairs from a splitmix64 stream
+ *   with a fixed seed, coordinates centre-weighted, every endpoint within x^2 + y^2 <= 169, no pair with two equal
+ *   endpoints, no pair twice.  sfm_orb_rotate_pattern turns a base table by 12 bin degrees: x' = round(x cos - y sin),
+ *   y' = round(x sin + y cos) in double, rounding half away from zero; bin 0 is the identity and bins 15 .. 29 are the
+ *   exact negatives of bins 0 .. 14.  A base table with an endpoint outside radius 13 is refused (SFM_ERR_ARG): with it
+ *   every rotated sample plus the 3-pixel blur support stays within 16 pixels of the keypoint, hence edge >= 16.
+ *
+ * sfm_features_detect: score map, suppression with gate and mask, histogram and cut, keypoints per row and their scan;
+ *   writes kp_ptr (device int64 [n_img+1]) on the handle's stream; nothing is read back.  The caller reads kp_ptr and
+ *   sizes the outputs exactly: n_kp = kp_ptr[n_img].
+ * sfm_features_describe: the ordered scatter (xy int32 [n_kp][2] as (x, y), score uint8), the blur, the moments
+ *   (angle_bin uint8) and the descriptor (desc uint8 [n_kp][32]), with the SAME images, sizes and workspace, untouched
+ *   since detect.  blurred_out (may be NULL) receives the blurred images in the layout of `images`.  n_kp == 0 with
+ *   blurred_out == NULL returns at once.
+ * The workspace holds the image table, one uint8 map of the scores after suppression, one uint8 map that is the raw score
+ * during detect and the blurred image during describe, three int32 per row of an image at least 33 wide, the histograms
+ * and the cuts; its size depends on img_off alone.  SFM_ERR_ARG before any device work for a null handle, an argument
+ * out of range, an img_off that does not ascend, an image larger than its slot or a workspace that is too small. */
+int sfm_orb_default_pattern(int8_t base[256][4]);
+int sfm_orb_rotate_pattern(const int8_t base[256][4], int8_t rot[30][256][4]);
+int sfm_features_workspace_bytes(int32_t n_img, const int64_t* img_off_host, int64_t* bytes_host);
+int sfm_features_detect(sfm_handle h, const uint8_t* images, const uint8_t* masks /* may be NULL */,
+                        const int64_t* img_off /* host */, const int32_t* heights /* host */,
+                        const int32_t* widths /* host */, int32_t n_img, int32_t threshold, int32_t edge,
+                        int32_t max_features, int64_t* kp_ptr /* device int64 [n_img+1] */, void* workspace,
+                        int64_t workspace_bytes);
+int sfm_features_describe(sfm_handle h, const uint8_t* images, const int64_t* img_off /* host */,
+                          const int32_t* heights /* host */, const int32_t* widths /* host */, int32_t n_img,
+                          const int64_t* kp_ptr /* device */, int64_t n_kp, const int8_t* rot_pattern /* device */,
+                          int32_t* xy /* int32 [n_kp][2] */, uint8_t* score, uint8_t* angle_bin,
+                          uint8_t* desc /* uint8 [n_kp][32] */, uint8_t* blurred_out /* may be NULL */, void* workspace,
+                          int64_t workspace_bytes);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ METRIC_L2_U8, METRIC_L2_F32, METRIC_HAMMING = 0, 1, 2
  SC_XNEW_NORM2, SC_CHOL_FAIL, SC_HDIAG) = range(12)
 SC_COUNT = 16
 PROF_SLOTS = ("lin_obs", "lin_rest", "build_G", "schur", "chol", "trsv", "backsub", "step", "knn", "schur_items",
-              "fund_hyp", "pnp_hyp", "pose_vote")
+              "fund_hyp", "pnp_hyp", "pose_vote", "feat_score", "feat_select", "feat_scatter", "feat_blur", "feat_describe")
 
 i32, i64, f64, vp = C.c_int32, C.c_int64, C.c_double, C.c_void_p
 
@@ -146,6 +146,11 @@ SIGNATURES = {
                                       vp, vp, vp, vp, vp, vp, i64]),
     "sfm_resection_workspace_bytes": (C.c_int, [i64, C.POINTER(i64)]),
     "sfm_tracks_resection": (C.c_int, [vp, vp, i32, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64]),
+    "sfm_orb_default_pattern": (C.c_int, [vp]),
+    "sfm_orb_rotate_pattern": (C.c_int, [vp, vp]),
+    "sfm_features_workspace_bytes": (C.c_int, [i32, vp, C.POINTER(i64)]),
+    "sfm_features_detect": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i64]),
+    "sfm_features_describe": (C.c_int, [vp, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64]),
 }
 
 _lib = None

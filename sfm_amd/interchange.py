@@ -6,6 +6,7 @@ Writers produce byte-for-byte what the reference's writers produce, so results c
 * pair files            save_pair_data            /root/reference/utils/find_matches.py:312-327
 * poses/points JSON+PLY save_reconstruction/_ply  /root/reference/utils/sfm_reconstruction.py:711-767
 * COLMAP text + db      SfMExporter               /root/reference/utils/export.py:9-187
+* images / silhouettes  read_pnm / write_pnm      binary .ppm / .pgm, what cv2.imread returns for them
 
 tests/test_interchange.py regenerates the five artefacts the reference ships under
 bunny_data/{reconstruction,exports/colmap}/ from the shipped state and compares SHA-256 digests.
@@ -211,3 +212,59 @@ class SfMExporter:
         self._create_colmap_database(colmap_dir / 'database.db')
         self.export_colmap(colmap_dir)
         logging.info(f"Exported all formats to {output_dir}")
+
+
+# --------------------------------------------------------------------------------------------------- PNM
+def _pnm_token(data, pos):
+    """The next whitespace-delimited header token from `pos`, comments ('#' to the end of the line) skipped."""
+    n = len(data)
+    while pos < n:
+        c = data[pos:pos + 1]
+        if c == b"#":
+            while pos < n and data[pos:pos + 1] not in (b"\n", b"\r"):
+                pos += 1
+        elif c.isspace():
+            pos += 1
+        else:
+            break
+    start = pos
+    while pos < n and not data[pos:pos + 1].isspace() and data[pos:pos + 1] != b"#":
+        pos += 1
+    if start == pos:
+        raise ValueError("truncated PNM header")
+    return data[start:pos], pos
+
+
+def read_pnm(path):
+    """A binary PGM (P5) or PPM (P6) with maxval 255 - the reference's silhouettes and images - as [h,w] or [h,w,3] uint8.
+    Colour comes back in BGR order, so that the result stands in for cv2.imread.  ValueError for any other file."""
+    data = Path(path).read_bytes()
+    magic, pos = _pnm_token(data, 0)
+    if magic not in (b"P5", b"P6"):
+        raise ValueError(f"{path}: not a binary PGM / PPM (magic {magic!r})")
+    try:
+        w, pos = _pnm_token(data, pos)
+        h, pos = _pnm_token(data, pos)
+        maxval, pos = _pnm_token(data, pos)
+        w, h, maxval = int(w), int(h), int(maxval)
+    except ValueError as e:
+        raise ValueError(f"{path}: bad PNM header ({e})") from None
+    if w < 0 or h < 0 or maxval != 255:
+        raise ValueError(f"{path}: only maxval 255 is read (got {w} x {h}, maxval {maxval})")
+    pos += 1                                              # the single whitespace byte behind maxval
+    ch = 3 if magic == b"P6" else 1
+    if len(data) - pos < w * h * ch:
+        raise ValueError(f"{path}: truncated: {len(data) - pos} bytes of pixels for {w} x {h} x {ch}")
+    a = np.frombuffer(data, dtype=np.uint8, count=w * h * ch, offset=pos)
+    return a.reshape(h, w).copy() if ch == 1 else a.reshape(h, w, 3)[:, :, ::-1].copy()
+
+
+def write_pnm(path, image, comment=None):
+    """[h,w] uint8 as P5, [h,w,3] uint8 in BGR order as P6; `comment` goes into the header as a '#' line."""
+    a = np.asarray(image)
+    if a.dtype != np.uint8 or not (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 3)):
+        raise ValueError("write_pnm takes [h,w] or [h,w,3] uint8")
+    head = (b"P5\n" if a.ndim == 2 else b"P6\n") + (b"# " + str(comment).encode() + b"\n" if comment is not None else b"")
+    head += f"{a.shape[1]} {a.shape[0]}\n255\n".encode()
+    body = a if a.ndim == 2 else a[:, :, ::-1]
+    Path(path).write_bytes(head + np.ascontiguousarray(body).tobytes())

@@ -407,6 +407,26 @@ class ImageMatcher(VerificationMixin, FundamentalMixin):
                             "metrics": v["metrics"], "quality_ok": self.verify_match_quality(v)}
         return out
 
+    def detect_features(self, image, mask=None):
+        """detect_features of the reference (find_matches.py:74-139) for one image on the device: (keypoints [n,2] float32,
+        descriptors uint8 [n,32] or None); see sfm_amd.features for the detector, the descriptor and what differs from ORB."""
+        from .features import detect_features
+        return detect_features(image, mask, device=self.device)
+
+    def process_images(self, images, pairs, masks=None, min_matches=5):
+        """From pixel arrays to verified pairs: detect_and_describe_batched over all images, then process_pairs with the
+        Hamming metric.  Returns (features, results): one sfm_amd.features.Features per image and what
+        process_pairs([f.xy ...], [f.descriptors ...], pairs) gives; `self.build_tracks([f.xy for f in features], pairs,
+        results)` joins them into Tracks."""
+        from .features import detect_and_describe_batched
+        feats = detect_and_describe_batched(images, masks, device=self.device)
+        metric, self.metric = self.metric, "hamming"
+        try:
+            results = self.process_pairs([f.xy for f in feats], [f.descriptors for f in feats], pairs, min_matches)
+        finally:
+            self.metric = metric
+        return feats, results
+
     def build_tracks(self, keypoints, pairs, results, min_length=2, conflicts="drop", verified_only=True):
         """Multi-view tracks (sfm_amd.tracks.Tracks) from what `process_pairs(keypoints, descs, pairs)` returned: the verified
         matches of every pair with a result joined on the device (sfm_tracks_build); pairs whose result is None are skipped.

@@ -3,10 +3,11 @@
 association (pair tests/s), two-view triangulation (tracks/s), epipolar verification (matches/s), and the batched
 fundamental-matrix RANSAC beside the batched matcher it follows in the pair loop, the batched PnP RANSAC of the
 camera registration, the batched relative-pose recovery of the initial-pair scan, the track building, the N-view
-triangulation of the tracks, and the resection lists, the gate evaluation and the incremental loop on top of them.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
+triangulation of the tracks, the resection lists, the gate evaluation and the incremental loop on top of them, and the
+feature detection / description stage in front of them all.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
 functions to time on a bounded sample of the same inputs (this tool itself never imports oracle/).
 usage: python tools/bench_driver.py [--reps 20] [--fundamental-only | --pnp-only | --pose-only | --tracks-only | --triangulate-only |
-       --incremental-only]"""
+       --incremental-only | --features-only]"""
 import argparse
 import ctypes as C
 import json
@@ -686,6 +687,72 @@ def measure_incremental(reps=20, emit=None):
         emit(row)
     return results
 
+def measure_features(reps=20, emit=None):
+    """sfm_features_detect + sfm_features_describe on a batch of 36 synthetic 1600 x 1200 images (the scene generator of
+    tests/features_reference.py, seeds 100 .. 135), threshold 20, max_features 10,000, images
+    resident in HBM: device time of each call by HIP events around `reps` calls, the time of each kernel (group) by the
+    library's own event brackets (sfm_set_profiling), and the achieved bytes per second of the score and the blur kernel
+    against their unique bytes (one read and one write per pixel each)."""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from features_reference import make_scene
+    from sfm_amd import _lib, features
+    from sfm_amd.driver import _p
+    h = _lib.get_handle(0)
+    dev = torch.device("cuda", 0)
+    H, W, n_img, threshold, edge, max_features = 1200, 1600, 36, 20, 31, 10000
+    imgs = [make_scene(H, W, seed=100 + k) for k in range(n_img)]
+    off = np.arange(n_img + 1, dtype=np.int64) * (H * W)
+    heights, widths = np.full(n_img, H, np.int32), np.full(n_img, W, np.int32)
+    d_img = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).to(dev)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    need = C.c_int64()
+    h.check(h.lib.sfm_features_workspace_bytes(n_img, hp(off), C.byref(need)), "sfm_features_workspace_bytes")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    kp_ptr = torch.empty(n_img + 1, dtype=torch.int64, device=dev)
+    rot = features._rot_table(None, 0)
+
+    def detect():
+        h.call("sfm_features_detect", _p(d_img), None, hp(off), hp(heights), hp(widths), n_img, threshold, edge, max_features,
+               _p(kp_ptr), _p(ws), need.value)
+    detect()
+    kp = kp_ptr.cpu().numpy()
+    n = int(kp[-1])
+    xy = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    score = torch.empty(n, dtype=torch.uint8, device=dev)
+    abin = torch.empty(n, dtype=torch.uint8, device=dev)
+    desc = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+
+    def describe():
+        h.call("sfm_features_describe", _p(d_img), hp(off), hp(heights), hp(widths), n_img, _p(kp_ptr), n, _p(rot), _p(xy),
+               _p(score), _p(abin), _p(desc), None, _p(ws), need.value)
+
+    def both():
+        detect(); describe()
+    for _ in range(3):
+        both()
+    pixels = n_img * H * W
+    row = {"kernel": "features", "images": n_img, "height": H, "width": W, "threshold": threshold, "edge": edge,
+           "max_features": max_features, "keypoints": n, "keypoints_per_image_min": int(np.diff(kp).min()),
+           "keypoints_per_image_max": int(np.diff(kp).max()),
+           "ms_detect": timed(detect, reps) * 1e3, "ms_describe": timed(describe, reps) * 1e3}
+    row["pixels_per_s_detect_plus_describe"] = pixels / ((row["ms_detect"] + row["ms_describe"]) * 1e-3)
+    h.set_profiling(True)
+    h.profile()
+    for _ in range(reps):
+        both()
+    prof = h.profile()
+    h.set_profiling(False)
+    for slot in ("feat_score", "feat_select", "feat_scatter", "feat_blur", "feat_describe"):
+        ms, cnt = prof[slot]
+        row[f"ms_{slot}"] = ms / max(cnt, 1)
+    for slot in ("feat_score", "feat_blur"):
+        row[f"unique_bytes_per_s_{slot}"] = 2 * pixels / (row[f"ms_{slot}"] * 1e-3) if row[f"ms_{slot}"] > 0 else None
+        row[f"share_of_hbm_stream_{slot}"] = (row[f"unique_bytes_per_s_{slot}"] or 0.0) / HBM_STREAM_BPS
+    if emit:
+        emit(row)
+    return [row]
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -698,9 +765,11 @@ def main():
     ap.add_argument("--tracks-only", action="store_true", help="only the track-building rows")
     ap.add_argument("--triangulate-only", action="store_true", help="only the N-view track triangulation rows")
     ap.add_argument("--incremental-only", action="store_true", help="only the resection / evaluation / incremental-loop rows")
+    ap.add_argument("--features-only", action="store_true", help="only the feature detection / description row")
     a = ap.parse_args()
     emit = lambda d: print(json.dumps(d), flush=True)
-    only = a.fundamental_only or a.pnp_only or a.pose_only or a.tracks_only or a.triangulate_only or a.incremental_only
+    only = a.fundamental_only or a.pnp_only or a.pose_only or a.tracks_only or a.triangulate_only or a.incremental_only or \
+        a.features_only
     if not only:
         measure(a.reps, a.tracks, a.corr, emit=emit)
     if a.fundamental_only or not only:
@@ -715,6 +784,8 @@ def main():
         measure_triangulate(a.reps, emit=emit)
     if a.incremental_only or not only:
         measure_incremental(a.reps, emit=emit)
+    if a.features_only or not only:
+        measure_features(a.reps, emit=emit)
 
 
 if __name__ == "__main__":

@@ -64,7 +64,9 @@ enum { SFM_PROF_LIN_OBS = 0,   /* k_lin_obs: residual + Jacobian + Huber scaling
        SFM_PROF_FEAT_SCATTER = 15,  /* k_feat_scatter (inside sfm_features_describe) */
        SFM_PROF_FEAT_BLUR = 16,     /* k_feat_blur */
        SFM_PROF_FEAT_DESCRIBE = 17, /* k_feat_describe */
-       SFM_PROF_COUNT = 18 };
+       SFM_PROF_ESS_SOLVE = 18,     /* k_ess_solve alone (inside sfm_ess_ransac) */
+       SFM_PROF_ESS_SCORE = 19,     /* k_ess_score alone (inside sfm_ess_ransac) */
+       SFM_PROF_COUNT = 20 };
 int sfm_set_profiling(sfm_handle h, int enabled);
 int sfm_profile_read(sfm_handle h, int slot, double* total_ms_host, int64_t* count_host);
 
@@ -465,6 +467,38 @@ int sfm_pnp_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, const do
                    double* Rt /* [n_seg][12], row-major [R|t] */, uint8_t* mask, int32_t* n_inliers, int32_t* status,
                    int32_t* hyp_count /* may be NULL */, int32_t* refined /* may be NULL */, void* workspace,
                    int64_t workspace_bytes);
+
+/* ------------------------------------------------------------------ essential-matrix RANSAC, batched over pairs
+ * cv2.findEssentialMat(pts1, pts2, K, cv2.RANSAC, threshold) for every pair of a step in one call: the calibrated
+ * counterpart of sfm_fund_ransac, for callers that go on to a pose (sfm_pose_recover with is_fundamental = 0).
+ * E = K^T F K of a 7-point F is not an essential matrix, and the pose taken from it leaves errors of many pixels.
+ * Structure as OpenCV's is recalled (not pinned): samples of 5, Nister's five-point solver (up to 10 real solutions;
+ * its steps are listed in sfm_amd/csrc/essential_solve.h), most inliers wins (ties: lowest hypothesis index, then
+ * lowest root slot).  Deviations, on purpose: the error rule is sfm_fund_ransac's, in pixels on F = K^-T E K^-1 (the
+ * larger of the two squared point-to-epipolar-line distances <= threshold^2); every one of the n_hyp hypotheses runs;
+ * the samples are data, drawn by the stateless integer hash of sfm_fund_draw_samples with 5 slots, or supplied by the
+ * caller.  The result is a function of (points, K, samples) alone, bitwise, run to run and independent of the batch.
+ * All arithmetic float64.  seg_ptr [n_seg+1] device int64; pts1 / pts2 [n][2] float32 pixels; Kseg [n_seg][4] float64
+ * (fx, fy, cx, cy).  A match with a NaN or infinite coordinate is never an inlier.  A hypothesis gives no model if its
+ * sample holds such a match or an index outside its segment, or if two matches of its sample share a pixel in image 1
+ * or share a pixel in image 2 (float32 == on both coordinates: a doubled match leaves the 5 x 9 system with rank 4).
+ *
+ * samples [n_seg][n_hyp][5] int32, segment-local indices, 5 distinct per hypothesis (-1 for segments with fewer than
+ * 5 matches).  status [n_seg]: 0 ok, 1 fewer than 5 matches, 2 no hypothesis gave an inlier; status 1 / 2 segments get
+ * E = 0, an all-zero mask and count 0.  E [n_seg][9] row-major, in normalised coordinates (x2^T E x1 = 0 for
+ * x = K^-1 [u, v, 1]), |E|_F = sqrt(2), its entry of largest magnitude (the first on a tie) positive.  hyp_count
+ * [n_seg][n_hyp] (may be NULL): per hypothesis the best inlier count of its candidates.  refine != 0: the same solver
+ * over all inliers of the winner (the four eigenvectors of the smallest eigenvalues of A^T A in place of the null
+ * space), every candidate re-scored with the same rule; the best replaces the winner only if its count is not lower
+ * (refined[s] = 1 then; refined may be NULL).  Everything runs on the handle's stream without host synchronisation. */
+int sfm_ess_workspace_bytes(int64_t n_points, int32_t n_seg, int32_t n_hyp, int64_t* bytes_host);
+int sfm_ess_draw_samples(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, int32_t n_hyp, uint64_t seed,
+                         int32_t* samples);
+int sfm_ess_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, const float* pts1, const float* pts2, int64_t n,
+                   const double* Kseg /* [n_seg][4] */, const int32_t* samples /* [n_seg][n_hyp][5] */, int32_t n_hyp,
+                   double threshold /* pixels */, int32_t refine, double* E /* [n_seg][9] */, uint8_t* mask,
+                   int32_t* n_inliers, int32_t* status, int32_t* hyp_count /* may be NULL */,
+                   int32_t* refined /* may be NULL */, void* workspace, int64_t workspace_bytes);
 
 /* ------------------------------------------------------------- relative-pose recovery, batched over image pairs
  * The cv2.recoverPose(E, pts1, pts2, K) call of the reference's find_best_initial_pair / initialize_reconstruction, for

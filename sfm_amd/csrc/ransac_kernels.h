@@ -1,5 +1,6 @@
 // The device side of a batched, replayable RANSAC, shared by twoview.hip and pnp.hip (and, for load_k4, pose.hip): the
-// sample kernel, the block sums, the whole-segment inlier count and the winner rule, for workgroups of 256 threads.
+// sample kernel, the block sums, the whole-segment inlier count, the winner rule and the 9 x 9 Jacobi of the refits, for
+// workgroups of 256 threads.
 // Included by .hip files only; what also compiles for the host stays in ransac_common.h.
 #pragma once
 #include "common.h"
@@ -138,6 +139,44 @@ __device__ __forceinline__ void ransac_store_winner(int s, int st, int64_t b, in
     n_inliers[s] = count;
     status[s] = st;
     if (refined) refined[s] = 0;
+  }
+}
+
+// ------------------------------------------------------------------------------------------- 9 x 9 Jacobi
+// Cyclic Jacobi on the symmetric s_A [9][9] in LDS, run by a whole workgroup (lanes 0..8 rotate one row / column entry
+// each): on return the diagonal of s_A holds the eigenvalues and the columns of s_V, which must enter as the identity,
+// the eigenvectors.  Every thread reads the same values, so the control flow is uniform.  Shared by k_fund_refit and
+// k_ess_refit.
+__device__ __forceinline__ void jacobi9_lds(double (*s_A)[9], double (*s_V)[9]) {
+  const int tid = threadIdx.x;
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    double off = 0.0, diag = 0.0;
+    for (int u = 0; u < 9; ++u)
+      for (int v = 0; v < 9; ++v) { const double a = s_A[u][v]; if (u == v) diag += a * a; else off += a * a; }
+    if (!(off > 1e-30 * diag)) break;                    // uniform: every thread read the same values
+    for (int p = 0; p < 8; ++p)
+      for (int q = p + 1; q < 9; ++q) {
+        const double app = s_A[p][p], aqq = s_A[q][q], apq = s_A[p][q];
+        double c = 1.0, sn = 0.0;
+        if (fabs(apq) > DBL_EPSILON * 1e-3 * sqrt(fabs(app * aqq)) && apq != 0.0) {
+          const double zeta = (aqq - app) / (2.0 * apq);
+          const double tt = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+          c = 1.0 / sqrt(1.0 + tt * tt); sn = c * tt;
+        }
+        __syncthreads();
+        if (tid < 9) {                                   // A <- A J, V <- V J (columns p, q)
+          const double ap = s_A[tid][p], aq = s_A[tid][q];
+          s_A[tid][p] = c * ap - sn * aq; s_A[tid][q] = sn * ap + c * aq;
+          const double vp = s_V[tid][p], vq = s_V[tid][q];
+          s_V[tid][p] = c * vp - sn * vq; s_V[tid][q] = sn * vp + c * vq;
+        }
+        __syncthreads();
+        if (tid < 9) {                                   // A <- J^T A (rows p, q)
+          const double ap = s_A[p][tid], aq = s_A[q][tid];
+          s_A[p][tid] = c * ap - sn * aq; s_A[q][tid] = sn * ap + c * aq;
+        }
+        __syncthreads();
+      }
   }
 }
 

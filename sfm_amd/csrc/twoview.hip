@@ -19,14 +19,9 @@
 // statistics and is staged as NaN for the scoring, so it fails every comparison; a sample that holds one gives no
 // model.  Sample indices are range-checked on the device before they index anything.
 #include "ransac_kernels.h"
+#include "epipolar_rule.h"
 
 namespace {
-
-constexpr int FUND_CHUNK = 512;      // points per LDS stage of the scoring loop: 512 x 4 doubles = 16 KiB
-
-__device__ __forceinline__ bool finite4(float2 p, float2 q) {
-  return isfinite(p.x) && isfinite(p.y) && isfinite(q.x) && isfinite(q.y);
-}
 
 // ------------------------------------------------------------------------------------------ normalisation
 // Hartley transform per segment and image: x' = sc * (x - c), centroid c, mean distance sqrt(2) after scaling.
@@ -84,28 +79,6 @@ __device__ __forceinline__ void denormalise(const double (&fn)[9], const double*
     f[c] = s2 * g[c];
     f[3 + c] = s2 * g[3 + c];
     f[6 + c] = tx2 * g[c] + ty2 * g[3 + c] + g[6 + c];
-  }
-}
-
-// the error rule without its divisions: max(s^2/den2, s^2/den1) <= thr2  <=>  s^2 <= thr2 * min(den1, den2), with
-// min > 0 required so that a zero line (or F = 0, the empty candidate slot) never counts.  NaN fails every test.
-__device__ __forceinline__ bool fund_inlier(const double (&f)[9], double x1, double y1, double x2, double y2, double thr2) {
-  const double a = f[0] * x1 + f[1] * y1 + f[2], b = f[3] * x1 + f[4] * y1 + f[5], c = f[6] * x1 + f[7] * y1 + f[8];
-  const double s = x2 * a + y2 * b + c;
-  const double ta = f[0] * x2 + f[3] * y2 + f[6], tb = f[1] * x2 + f[4] * y2 + f[7];
-  const double den = fmin(a * a + b * b, ta * ta + tb * tb);
-  return (den > 0.0) && (s * s <= thr2 * den);
-}
-
-// stage points [c0, c0 + cnt) of a segment into LDS as doubles; a non-finite match becomes NaN in all four
-__device__ __forceinline__ void stage_points(double2* s_pt, const float2* __restrict__ pts1, const float2* __restrict__ pts2,
-                                             int64_t base, int cnt, int nthreads) {
-  for (int t = threadIdx.x; t < cnt; t += nthreads) {
-    const float2 p = pts1[base + t], q = pts2[base + t];
-    const bool ok = finite4(p, q);
-    const double nan = __builtin_nan("");
-    s_pt[2 * t] = ok ? make_double2((double)p.x, (double)p.y) : make_double2(nan, nan);
-    s_pt[2 * t + 1] = ok ? make_double2((double)q.x, (double)q.y) : make_double2(nan, nan);
   }
 }
 
@@ -345,35 +318,7 @@ __global__ __launch_bounds__(256) void k_fund_refit(const int64_t* __restrict__ 
     s_V[u][v] = (u == v) ? 1.0 : 0.0;
   }
   __syncthreads();
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    double off = 0.0, diag = 0.0;
-    for (int u = 0; u < 9; ++u)
-      for (int v = 0; v < 9; ++v) { const double a = s_A[u][v]; if (u == v) diag += a * a; else off += a * a; }
-    if (!(off > 1e-30 * diag)) break;                    // uniform: every thread read the same values
-    for (int p = 0; p < 8; ++p)
-      for (int q = p + 1; q < 9; ++q) {
-        const double app = s_A[p][p], aqq = s_A[q][q], apq = s_A[p][q];
-        double c = 1.0, sn = 0.0;
-        if (fabs(apq) > DBL_EPSILON * 1e-3 * sqrt(fabs(app * aqq)) && apq != 0.0) {
-          const double zeta = (aqq - app) / (2.0 * apq);
-          const double tt = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-          c = 1.0 / sqrt(1.0 + tt * tt); sn = c * tt;
-        }
-        __syncthreads();
-        if (tid < 9) {                                   // A <- A J, V <- V J (columns p, q)
-          const double ap = s_A[tid][p], aq = s_A[tid][q];
-          s_A[tid][p] = c * ap - sn * aq; s_A[tid][q] = sn * ap + c * aq;
-          const double vp = s_V[tid][p], vq = s_V[tid][q];
-          s_V[tid][p] = c * vp - sn * vq; s_V[tid][q] = sn * vp + c * vq;
-        }
-        __syncthreads();
-        if (tid < 9) {                                   // A <- J^T A (rows p, q)
-          const double ap = s_A[p][tid], aq = s_A[q][tid];
-          s_A[p][tid] = c * ap - sn * aq; s_A[q][tid] = sn * ap + c * aq;
-        }
-        __syncthreads();
-      }
-  }
+  jacobi9_lds(s_A, s_V);
   int kmin = 0;
   for (int k = 1; k < 9; ++k) if (s_A[k][k] < s_A[kmin][kmin]) kmin = k;
   double U[3][3], V[3][3];

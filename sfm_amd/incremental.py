@@ -296,24 +296,31 @@ def _pair_pixels(tracks, kp_xy, i, j):
 
 
 def _initial_pair(tracks, kp_xy, K, initial_pair, o, device):
-    """((i, j), R, t, n_good, good tracks, candidates log) of the start: F on the common tracks, then the pose, all
+    """((i, j), R, t, n_good, good tracks, candidates log) of the start: F - or, with `initial_model` "essential", E by
+    five-point RANSAC with the same threshold, hypothesis count and seed - on the common tracks, then the pose, all
     candidates in one batch each; the winner has the most good points (ties: the lower (i, j)).  The good tracks are the
-    ones the pose stage counted: inliers of F that lie in front of both cameras."""
+    ones the pose stage counted: inliers of the model that lie in front of both cameras."""
     from ._lib import SfmError
     from .pose import recover_pose_batched
+    from .essential import estimate_essential_batched
     from .twoview import estimate_fundamental_batched
     pairs = [tuple(initial_pair)] if initial_pair is not None else _common_track_pairs(tracks, o["initial_candidates"])
     if not pairs:
         raise SfmError("no image pair shares a track")
     px = [_pair_pixels(tracks, kp_xy, i, j) for i, j in pairs]
-    fund = estimate_fundamental_batched([p[0] for p in px], [p[1] for p in px], threshold=o["fund_threshold"],
-                                        n_hypotheses=o["fund_hypotheses"], seed=o["seed"], device=device)
+    essential = o["initial_model"] == "essential"
+    if essential:
+        fund = estimate_essential_batched([p[0] for p in px], [p[1] for p in px], K, threshold=o["fund_threshold"],
+                                          n_hypotheses=o["fund_hypotheses"], seed=o["seed"], device=device)
+    else:
+        fund = estimate_fundamental_batched([p[0] for p in px], [p[1] for p in px], threshold=o["fund_threshold"],
+                                            n_hypotheses=o["fund_hypotheses"], seed=o["seed"], device=device)
     live = [k for k, (F, _) in enumerate(fund) if F is not None]
     rows = [{"pair": pairs[k], "common": len(px[k][0]), "n_good": 0} for k in range(len(pairs))]
     best = None
     if live:
         pose = recover_pose_batched([fund[k][0] for k in live], [px[k][0] for k in live], [px[k][1] for k in live], K,
-                                    masks=[fund[k][1] for k in live], from_fundamental=True, device=device)
+                                    masks=[fund[k][1] for k in live], from_fundamental=not essential, device=device)
         for k, (n_good, R, t, mask) in zip(live, pose):
             rows[k]["n_good"] = int(n_good)
             if R is not None and (best is None or (-n_good, pairs[k]) < (-best[3], best[0])):
@@ -327,12 +334,13 @@ def _initial_pair(tracks, kp_xy, K, initial_pair, o, device):
 DEFAULTS = dict(initial_candidates=32, min_initial_points=50, min_visible=15, candidates_per_step=8, pnp_threshold=8.0,
                 pnp_hypotheses=1024, pnp_min_inliers=15, seed=0, ba_every=7, cam_dim=6, max_error=TRIANGULATION_MAX_ERROR,
                 min_angle_deg=1.0, refine_iters=5, min_views=2, fund_threshold=3.0, fund_hypotheses=1024,
-                refine_initial_pair=True, image_size=(1024, 768))
+                refine_initial_pair=True, image_size=(1024, 768), initial_model="fundamental")
 
 
 def reconstruct_tracks(tracks, keypoints, K, initial_pair=None, device=0, **options):
     """Cameras and points from tracks: initial pair (given, or the best of the `initial_candidates` pairs with the most
-    common tracks; its pose is refined by a two-camera bundle adjustment unless `refine_initial_pair` is False), then
+    common tracks; its pose comes from F, or with `initial_model="essential"` from a five-point E, and is refined by a
+    two-camera bundle adjustment unless `refine_initial_pair` is False), then
     per step the resection lists of all unregistered images, one batched PnP over the `candidates_per_step` images that see the most points, registration of the one with the most inliers, triangulation
     of the tracks that have no point yet; a bundle adjustment (`solve_ba`, `cam_dim` 6 = fixed K or 10) every `ba_every`
     registrations and at the end, each followed by `evaluate_tracks` - points that fail a gate are dropped and
@@ -352,6 +360,8 @@ def reconstruct_tracks(tracks, keypoints, K, initial_pair=None, device=0, **opti
     _check_options(o["min_views"], o["refine_iters"], o["max_error"], o["min_angle_deg"])
     if o["cam_dim"] not in (6, 10):
         raise ValueError("cam_dim must be 6 or 10")
+    if o["initial_model"] not in ("fundamental", "essential"):
+        raise ValueError('initial_model must be "fundamental" or "essential"')
     n_img = _check_tracks(tracks, keypoints)
     K = np.asarray(K, dtype=np.float64)
     if K.shape != (3, 3):
@@ -397,11 +407,12 @@ def reconstruct_tracks(tracks, keypoints, K, initial_pair=None, device=0, **opti
                  "n_points": len(pts), "n_observations": len(uv)}, cams, pts)
 
     def refine_pair():
-        """The pose of the initial pair comes from E = K^T F K, and F has two more degrees of freedom than E: with noisy
+        """By default the pose of the initial pair comes from E = K^T F K, and F has two more degrees of freedom than E: with noisy
         pixels the essential matrix nearest to it leaves reprojection errors of several pixels, above the `max_error` gate,
         and the first triangulation would adopt nothing.  So the pair gets a bundle adjustment of its own (fixed K) over
         its good tracks, triangulated without the error gate; the result goes back to the gauge [I|0], [R|t] with
-        |t| = 1 and no point is kept.  Without success the pose stays as it was.  Returns the result for the log."""
+        |t| = 1 and no point is kept.  Without success the pose stays as it was.  Returns the result for the log.
+        (`initial_model="essential"` removes the cause; the refinement keeps its meaning there.)"""
         sc.triangulate(**dict(tri_gates, max_error=float("inf")))
         seed = np.zeros(len(tracks), dtype=bool)
         seed[good] = True
@@ -442,7 +453,7 @@ def reconstruct_tracks(tracks, keypoints, K, initial_pair=None, device=0, **opti
     if refined is not None and refined["success"]:
         cameras_up()
     added = sc.adopt_new_points(**tri_gates)
-    rec.log.append({"step": 0, "initial_pair": (i0, j0), "n_good": n_good, "candidates": rows, "pair_refinement": refined,
+    rec.log.append({"step": 0, "initial_pair": (i0, j0), "initial_model": o["initial_model"], "n_good": n_good, "candidates": rows, "pair_refinement": refined,
                     "points_added": added})
     since_ba = 0
     while unregistered:

@@ -122,6 +122,32 @@ int sfm_match_ratio_batched(sfm_handle h, int64_t n_out, int32_t n_seg, const in
  * *all_integral (device int32) is 0 if any value is not such an integer. */
 int sfm_match_f32_to_u8(sfm_handle h, const float* src, int64_t n_elems, uint8_t* dst, int32_t* all_integral);
 
+/* ------------------------------------------------------------------ guided matching
+ * Matching again under each pair's fundamental matrix: a query q of image i is compared only with
+ * C(q) = { t of image j : both point-line distances of (q, t) under F are <= gate_px } (the rule of
+ * sfm_amd/csrc/guided_rule.h, float64 without FMA contraction, image i always in its first slot).  best = the minimum
+ * over C(q) of (distance, t), second = the minimum of the rest; distances as in the matcher (popcount, or sqrtf of the
+ * integer d^2, float32).  q is kept iff |C(q)| >= 1, (double)d1 <= max_distance (max_distance < 0: no such test),
+ * |C(q)| == 1 or (double)d1 < ratio * (double)d2, and - with cross_check - q is the (distance, q') minimum over
+ * { q' : gate(q', best) }.  Ratio and max_distance apply in the forward direction only.
+ *
+ * desc uint8 [n_rows, dim] and xy float32 [n_rows, 2] describe the same rows (the keypoints of all images back to back);
+ * segment s (= one pair, described as for sfm_match_knn2_batched, HOST arrays) takes its queries from rows
+ * [q_beg[s], q_end[s]) and its candidates from [t_beg[s], t_end[s]); either may be empty, and a single candidate row is
+ * legal.  F: device double [n_seg, 9], row-major, x_j^T F x_i = 0.  Supported: SFM_METRIC_HAMMING with dim 16 / 32 / 64
+ * bytes, SFM_METRIC_L2_U8 with dim 32 / 64 / 128; anything else is SFM_ERR_ARG.
+ * Outputs (device): query_idx / train_idx / distance with room for n_out entries (sfm_guided_workspace_bytes reports
+ * n_out = all query rows), the matches of segment s at [seg_ptr[s], seg_ptr[s+1]) (int64 [n_seg+1]), indices relative
+ * to the segment, in query order; train_idx may repeat without cross_check.  n_candidates (optional, int32 [n_out]):
+ * |C(q)| of every query row.  The output bytes are a function of the inputs alone. */
+int sfm_guided_workspace_bytes(int metric, int32_t n_seg, const int64_t* q_beg_host, const int64_t* q_end_host,
+                               const int64_t* t_beg_host, const int64_t* t_end_host, int64_t* n_out_host, int64_t* bytes_host);
+int sfm_guided_match(sfm_handle h, int metric, const void* desc, int64_t n_rows, int dim, const float* xy, int32_t n_seg,
+                     const int64_t* q_beg_host, const int64_t* q_end_host, const int64_t* t_beg_host, const int64_t* t_end_host,
+                     const double* F, double gate_px, double ratio, double max_distance, int cross_check, int32_t* query_idx,
+                     int32_t* train_idx, float* distance, int32_t* n_candidates, int64_t* seg_ptr, void* workspace,
+                     int64_t workspace_bytes);
+
 /* ------------------------------------------------------------------ bundle adjustment
  * Replaces what scipy.optimize.least_squares does for bundle_adjust: evaluation of the
  * closure `objective` (sfm_reconstruction.py:472-501), its Jacobian, the Huber scaling

@@ -8,3 +8,4 @@ from .triangulate import Triangulation, triangulate_tracks, triangulate_tracks_r
 from .incremental import Reconstruction, evaluate_tracks, reconstruct_tracks, resection_lists  # noqa: F401
 from .features import Features, detect_and_describe_batched, detect_features  # noqa: F401
 from .interchange import read_pnm, write_pnm  # noqa: F401
+from .guided import guided_match_pairs  # noqa: F401

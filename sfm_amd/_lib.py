@@ -87,6 +87,9 @@ SIGNATURES = {
     "sfm_match_batched_workspace_bytes": (C.c_int, [C.c_int, i32, vp, vp, vp, vp, i64, i64, C.POINTER(i64), C.POINTER(i64)]),
     "sfm_match_knn2_batched": (C.c_int, [vp, C.c_int, vp, i64, vp, i64, C.c_int, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64]),
     "sfm_match_ratio_batched": (C.c_int, [vp, i64, i32, vp, vp, vp, vp, f64, vp, vp, vp, vp, vp, i64]),
+    "sfm_guided_workspace_bytes": (C.c_int, [C.c_int, i32, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64)]),
+    "sfm_guided_match": (C.c_int, [vp, C.c_int, vp, i64, C.c_int, vp, i32, vp, vp, vp, vp, vp, f64, f64, f64, C.c_int,
+                                   vp, vp, vp, vp, vp, vp, i64]),
     "sfm_copy_to_host": (C.c_int, [vp, vp, vp, i64]),
     "sfm_comm_unique_id": (C.c_int, [vp, vp]),
     "sfm_comm_init_rank": (C.c_int, [vp, vp, i32, i32]),

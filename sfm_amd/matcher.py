@@ -367,7 +367,7 @@ class ImageMatcher(VerificationMixin, FundamentalMixin):
             out.append(DMatchList(*res))
         return out
 
-    def process_pairs(self, keypoints, descs, pairs, min_matches=5):
+    def process_pairs(self, keypoints, descs, pairs, min_matches=5, guided=False, **guided_options):
         """process_image_pair (find_matches.py:246-310) for every (i, j) of `pairs`, minus the image I/O and the visualisation,
         in three batched device steps: match_pairs (:272) -> the float32 pts1 / pts2 gathers (:278-279), pairs under
         `min_matches` dropped (:274) -> estimate_fundamental_batched (:282) -> verify_pairs (:288).
@@ -375,9 +375,15 @@ class ImageMatcher(VerificationMixin, FundamentalMixin):
         keypoints: per image an [n,2] array of pixel coordinates or a list of objects with `.pt` (cv2.KeyPoint).  Returns one
         entry per pair: None where the reference returns None (too few matches, a pair its try / except skips, no model), else
         {'matches': DMatchList, 'pts1', 'pts2' [M,2] float32, 'F' [3,3], 'inlier_mask' [M] bool, 'symmetric_errors',
-        'metrics': the dictionary of geometric_verification, 'quality_ok': verify_match_quality of it}."""
+        'metrics': the dictionary of geometric_verification, 'quality_ok': verify_match_quality of it}.
+        guided=True passes the result through `guided_pairs` (with `guided_options`): every pair with a model is matched again
+        under its F."""
         import logging
         pairs = [(int(i), int(j)) for i, j in pairs]
+        if guided:
+            return self.guided_pairs(keypoints, descs, pairs, self.process_pairs(keypoints, descs, pairs, min_matches), **guided_options)
+        if guided_options:
+            raise TypeError(f"options {sorted(guided_options)} need guided=True")
         xy = {}
         out = [None] * len(pairs)
         live, p1, p2, ml = [], [], [], []
@@ -407,22 +413,59 @@ class ImageMatcher(VerificationMixin, FundamentalMixin):
                             "metrics": v["metrics"], "quality_ok": self.verify_match_quality(v)}
         return out
 
+    def guided_pairs(self, keypoints, descs, pairs, results, gate=3.0, ratio=None, max_distance=None, cross_check=False):
+        """Guided matching on top of what `process_pairs(keypoints, descs, pairs)` returned: every pair with a result is matched
+        again under that result's F (sfm_amd.guided.guided_match_pairs: candidates within `gate` pixels of the epipolar lines,
+        ratio test among them; `ratio` defaults to the matcher's).  Returns a list of the same shape in which every non-None
+        entry has 'matches' (DMatchList), 'pts1', 'pts2' replaced by the guided set, 'F' unchanged, 'inlier_mask' /
+        'symmetric_errors' / 'metrics' / 'quality_ok' recomputed by verify_pairs, and 'n_unguided' = the number of matches the
+        entry came with.  An entry whose guided set is empty becomes None.  `build_tracks` consumes the list as it is."""
+        from .guided import guided_match_pairs
+        pairs = [(int(i), int(j)) for i, j in pairs]
+        if len(results) != len(pairs):
+            raise ValueError("pairs / results differ in length")
+        out = [None] * len(pairs)
+        live = [s for s, r in enumerate(results) if r is not None]
+        if not live:
+            return out
+        got = guided_match_pairs(keypoints, descs, [pairs[s] for s in live], [results[s]["F"] for s in live], gate=gate,
+                                 ratio=self.ratio if ratio is None else ratio, max_distance=max_distance, cross_check=cross_check,
+                                 metric=self.metric, device=self.device)
+        xy = {}
+        for s in live:
+            for img in pairs[s]:
+                if img not in xy:
+                    xy[img] = keypoints_xy(keypoints[img])
+        keep = [(s, g) for s, g in zip(live, got) if len(g[0]) > 0]
+        if not keep:
+            return out
+        p1 = [xy[pairs[s][0]][g[0]] for s, g in keep]
+        p2 = [xy[pairs[s][1]][g[1]] for s, g in keep]
+        verified = verify_pairs([(a, b, results[s]["F"]) for a, b, (s, _) in zip(p1, p2, keep)], 3.0, self.device)
+        for (s, g), a, b, v in zip(keep, p1, p2, verified):
+            out[s] = {"matches": DMatchList(*g), "pts1": a, "pts2": b, "F": results[s]["F"],
+                      "inlier_mask": v["inlier_mask"], "symmetric_errors": v["symmetric_errors"],
+                      "metrics": v["metrics"], "quality_ok": self.verify_match_quality(v),
+                      "n_unguided": len(results[s]["matches"])}
+        return out
+
     def detect_features(self, image, mask=None):
         """detect_features of the reference (find_matches.py:74-139) for one image on the device: (keypoints [n,2] float32,
         descriptors uint8 [n,32] or None); see sfm_amd.features for the detector, the descriptor and what differs from ORB."""
         from .features import detect_features
         return detect_features(image, mask, device=self.device)
 
-    def process_images(self, images, pairs, masks=None, min_matches=5):
+    def process_images(self, images, pairs, masks=None, min_matches=5, guided=False, **guided_options):
         """From pixel arrays to verified pairs: detect_and_describe_batched over all images, then process_pairs with the
         Hamming metric.  Returns (features, results): one sfm_amd.features.Features per image and what
         process_pairs([f.xy ...], [f.descriptors ...], pairs) gives; `self.build_tracks([f.xy for f in features], pairs,
-        results)` joins them into Tracks."""
+        results)` joins them into Tracks.  guided / guided_options: as in process_pairs."""
         from .features import detect_and_describe_batched
         feats = detect_and_describe_batched(images, masks, device=self.device)
         metric, self.metric = self.metric, "hamming"
         try:
-            results = self.process_pairs([f.xy for f in feats], [f.descriptors for f in feats], pairs, min_matches)
+            results = self.process_pairs([f.xy for f in feats], [f.descriptors for f in feats], pairs, min_matches, guided=guided,
+                                         **guided_options)
         finally:
             self.metric = metric
         return feats, results

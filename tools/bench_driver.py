@@ -8,7 +8,7 @@ triangulation of the tracks, the resection lists, the gate evaluation and the in
 feature detection / description stage in front of them all.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
 functions to time on a bounded sample of the same inputs (this tool itself never imports oracle/).
 usage: python tools/bench_driver.py [--reps 20] [--fundamental-only | --essential-only | --pnp-only | --pose-only | --tracks-only | --triangulate-only |
-       --incremental-only | --features-only]"""
+       --incremental-only | --features-only | --guided-only]"""
 import argparse
 import ctypes as C
 import json
@@ -806,6 +806,81 @@ def measure_features(reps=20, emit=None):
     return [row]
 
 
+def measure_guided(reps=20, emit=None):
+    """sfm_guided_match with and without cross_check beside the blind batched matcher (knn2_batched + ratio_batched) on
+    the same batch in the same run, inputs resident in HBM: the sizes of the matcher row of measure_fundamental (36 images
+    x 500 keypoints, all 630 pairs) with ORB-sized descriptors (32 bytes, Hamming).  Keypoints are uniform in 1024 x 768 and
+    every pair has the F of one synthetic two-view geometry, so a 3 px gate passes about 1 % of the combinations.  A third
+    guided figure with a 0 px gate (no candidate, no descriptor distance) is the gate loop alone."""
+    import torch
+    from sfm_amd import _lib, matcher
+    from sfm_amd.driver import _p
+    h = _lib.get_handle(0)
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0)
+    n_img, n_kp, dim = 36, 500, 32
+    descs = [rng.integers(0, 256, (n_kp, dim)).astype(np.uint8) for _ in range(n_img)]
+    kps = [(rng.uniform(0, 1, (n_kp, 2)) * [1024, 768]).astype(np.float32) for _ in range(n_img)]
+    pairs = [(i, j) for i in range(n_img) for j in range(i + 1, n_img)]
+    yaw = 0.25
+    R = np.array([[np.cos(yaw), 0, np.sin(yaw)], [0, 1, 0], [-np.sin(yaw), 0, np.cos(yaw)]])
+    t = np.array([-1.5, 0.1, 0.3])
+    K = np.array([[1228.0, 0, 512], [0, 1228.0, 384], [0, 0, 1]])
+    tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
+    F = np.linalg.inv(K).T @ tx @ R @ np.linalg.inv(K)
+    F = F / F[2, 2]
+    rows, ptr_h, dim = matcher._upload_sets(descs, dev)
+    xy, _, _ = matcher._upload_sets(kps, dev)
+    q_beg = np.array([ptr_h[i] for i, _ in pairs], dtype=np.int64); q_end = np.array([ptr_h[i + 1] for i, _ in pairs], dtype=np.int64)
+    t_beg = np.array([ptr_h[j] for _, j in pairs], dtype=np.int64); t_end = np.array([ptr_h[j + 1] for _, j in pairs], dtype=np.int64)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    n_rows, n_seg, code = int(rows.shape[0]), len(pairs), _lib.METRIC_HAMMING
+    d_F = torch.from_numpy(np.tile(F.reshape(1, 9), (n_seg, 1))).to(dev)
+    n_out, need = C.c_int64(), C.c_int64()
+    h.check(h.lib.sfm_match_batched_workspace_bytes(code, n_seg, hp(q_beg), hp(q_end), hp(t_beg), hp(t_end), n_rows, n_rows,
+                                                    C.byref(n_out), C.byref(need)), "sfm_match_batched_workspace_bytes")
+    nq = n_out.value
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    i1, i2, qi, ti, nc = (torch.empty(nq, dtype=torch.int32, device=dev) for _ in range(5))
+    e1, e2, dd = (torch.empty(nq, dtype=torch.float32, device=dev) for _ in range(3))
+    out_ptr = torch.empty(n_seg + 1, dtype=torch.int64, device=dev); seg_ptr = torch.empty(n_seg + 1, dtype=torch.int64, device=dev)
+
+    def blind():
+        h.call("sfm_match_knn2_batched", code, _p(rows), n_rows, _p(rows), n_rows, dim, n_seg, hp(q_beg), hp(q_end), hp(t_beg),
+               hp(t_end), _p(i1), _p(i2), _p(e1), _p(e2), _p(out_ptr), _p(ws), need.value)
+        h.call("sfm_match_ratio_batched", nq, n_seg, _p(out_ptr), _p(i1), _p(e1), _p(e2), C.c_double(0.75), _p(qi), _p(ti),
+               _p(dd), _p(seg_ptr), _p(ws), need.value)
+    g_out, g_need = C.c_int64(), C.c_int64()
+    h.check(h.lib.sfm_guided_workspace_bytes(code, n_seg, hp(q_beg), hp(q_end), hp(t_beg), hp(t_end), C.byref(g_out), C.byref(g_need)),
+            "sfm_guided_workspace_bytes")
+    assert g_out.value == nq
+    g_ws = torch.empty(g_need.value, dtype=torch.uint8, device=dev)
+
+    def guided(cross, gate=3.0):
+        h.call("sfm_guided_match", code, _p(rows), n_rows, dim, _p(xy), n_seg, hp(q_beg), hp(q_end), hp(t_beg), hp(t_end), _p(d_F),
+               C.c_double(gate), C.c_double(0.75), C.c_double(-1.0), cross, _p(qi), _p(ti), _p(dd), _p(nc), _p(seg_ptr), _p(g_ws),
+               g_need.value)
+    for _ in range(3):
+        blind(); guided(0); guided(1)
+    ms_blind = timed(blind, reps) * 1e3
+    n_blind = int(seg_ptr[-1].item())
+    ms_fwd = timed(lambda: guided(0), reps) * 1e3
+    n_fwd, cand = int(seg_ptr[-1].item()), float(nc.sum().item())
+    ms_cross = timed(lambda: guided(1), reps) * 1e3
+    n_cross = int(seg_ptr[-1].item())
+    ms_gate = timed(lambda: guided(0, 0.0), reps) * 1e3
+    combos = float(n_seg) * n_kp * n_kp
+    r = {"kernel": "guided_match", "pairs": n_seg, "images": n_img, "keypoints_per_image": n_kp, "descriptor_bytes": dim,
+         "gate_px": 3.0, "ratio": 0.75, "ms_blind_match_pairs": ms_blind, "ms_guided": ms_fwd, "ms_guided_cross_check": ms_cross,
+         "guided_over_blind": ms_fwd / ms_blind, "guided_cross_check_over_blind": ms_cross / ms_blind,
+         "ms_guided_gate_0px": ms_gate, "gate_tests_per_s": combos / (ms_gate * 1e-3), "share_of_combinations_passing": cand / combos,
+         "matches_blind": n_blind, "matches_guided": n_fwd, "matches_guided_cross_check": n_cross,
+         "note": "whole calls by device events, descriptors / keypoints / F resident; random descriptors, so the match counts say nothing"}
+    if emit:
+        emit(r)
+    return [r]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -819,10 +894,11 @@ def main():
     ap.add_argument("--triangulate-only", action="store_true", help="only the N-view track triangulation rows")
     ap.add_argument("--incremental-only", action="store_true", help="only the resection / evaluation / incremental-loop rows")
     ap.add_argument("--features-only", action="store_true", help="only the feature detection / description row")
+    ap.add_argument("--guided-only", action="store_true", help="only the guided-matching row (beside the blind matcher)")
     a = ap.parse_args()
     emit = lambda d: print(json.dumps(d), flush=True)
     only = a.fundamental_only or a.essential_only or a.pnp_only or a.pose_only or a.tracks_only or a.triangulate_only or a.incremental_only or \
-        a.features_only
+        a.features_only or a.guided_only
     if not only:
         measure(a.reps, a.tracks, a.corr, emit=emit)
     if a.fundamental_only or not only:
@@ -841,6 +917,8 @@ def main():
         measure_incremental(a.reps, emit=emit)
     if a.features_only or not only:
         measure_features(a.reps, emit=emit)
+    if a.guided_only or not only:
+        measure_guided(a.reps, emit=emit)
 
 
 if __name__ == "__main__":

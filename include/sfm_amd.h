@@ -66,7 +66,8 @@ enum { SFM_PROF_LIN_OBS = 0,   /* k_lin_obs: residual + Jacobian + Huber scaling
        SFM_PROF_FEAT_DESCRIBE = 17, /* k_feat_describe */
        SFM_PROF_ESS_SOLVE = 18,     /* k_ess_solve alone (inside sfm_ess_ransac) */
        SFM_PROF_ESS_SCORE = 19,     /* k_ess_score alone (inside sfm_ess_ransac) */
-       SFM_PROF_COUNT = 20 };
+       SFM_PROF_HOM_HYP = 20,       /* k_hom_hypotheses alone (inside sfm_hom_ransac) */
+       SFM_PROF_COUNT = 21 };
 int sfm_set_profiling(sfm_handle h, int enabled);
 int sfm_profile_read(sfm_handle h, int slot, double* total_ms_host, int64_t* count_host);
 
@@ -525,6 +526,45 @@ int sfm_ess_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, const fl
                    double threshold /* pixels */, int32_t refine, double* E /* [n_seg][9] */, uint8_t* mask,
                    int32_t* n_inliers, int32_t* status, int32_t* hyp_count /* may be NULL */,
                    int32_t* refined /* may be NULL */, void* workspace, int64_t workspace_bytes);
+
+/* ------------------------------------------------------------------ homography RANSAC, batched over pairs
+ * cv2.findHomography(pts1, pts2, cv2.RANSAC, threshold) for every pair of a step in one call: x2 ~ H x1.  A pair whose
+ * matches lie on a plane, or whose cameras share a centre, has no defined F, and an H explains nearly all of its
+ * matches: the ratio of this call's inlier count to sfm_fund_ransac's (or sfm_ess_ransac's) tells such a pair apart.
+ * Structure as OpenCV's is recalled (not pinned): samples of 4, a subset check, the DLT on normalised coordinates, the
+ * forward transfer error against threshold^2, most inliers wins (ties: lowest hypothesis index), H scaled to
+ * H[2][2] = 1.  Deviations, on purpose: every one of the n_hyp hypotheses runs; the samples are data, drawn by the
+ * stateless integer hash of sfm_fund_draw_samples with 4 slots, or supplied by the caller; the refit is linear and NO
+ * Levenberg-Marquardt step follows it.  The result is a function of (points, samples) alone, bitwise, run to run and
+ * independent of the batch.
+ * All arithmetic float64.  seg_ptr [n_seg+1] device int64; pts1 / pts2 [n][2] float32 pixels.
+ * Sample rule, on the float32 pixels widened to double: for each of the triples (i, j, k) = (0,1,2), (0,1,3), (0,2,3),
+ * (1,2,3) and each image, a = (xj - xi)(yk - yi) - (yj - yi)(xk - xi), d1 = |pj - pi|^2, d2 = |pk - pi|^2; the sample
+ * gives no model unless a^2 > 1e-6 d1 d2 in both images (collinear or repeated points), and none if (a1 > 0) != (a2 > 0)
+ * for any triple (the sample reverses an orientation).  A sample that holds a NaN or infinite coordinate, or an index
+ * outside its segment, gives no model either.
+ * Solve: on the segment's Hartley-normalised coordinates (the transforms of sfm_fund_ransac, over the finite matches),
+ * the 8 x 9 system with the rows [x, y, 1, 0, 0, 0, -u x, -u y, -u] and [0, 0, 0, x, y, 1, -v x, -v y, -v] per match;
+ * its null vector by Givens rotations of column pairs (sfm_amd/csrc/homography_solve.h); H = T2^-1 Hn T1; a
+ * non-finite H is no model.
+ * Inlier rule, without division (sfm_amd/csrc/homography_rule.h): X = (h0 x + h1 y) + h2, Y = (h3 x + h4 y) + h5,
+ * W = (h6 x + h7 y) + h8; inlier when W != 0 and (X - u W)^2 + (Y - v W)^2 <= threshold^2 W^2.  A match with a NaN or
+ * infinite coordinate is never an inlier.
+ *
+ * samples [n_seg][n_hyp][4] int32, segment-local indices, 4 distinct per hypothesis (-1 for segments with fewer than
+ * 4 matches).  status [n_seg]: 0 ok, 1 fewer than 4 matches, 2 no hypothesis gave an inlier; status 1 / 2 segments get
+ * H = 0, an all-zero mask and count 0.  H [n_seg][9] row-major.  hyp_count [n_seg][n_hyp] (may be NULL): per hypothesis
+ * its inlier count.  refine != 0, with at least 4 inliers: the normalised DLT over the winner's inliers (smallest
+ * eigenvector of the 9 x 9 normal matrix), re-scored with the same rule; it replaces the winner only if its count is not
+ * lower (refined[s] = 1 then; refined may be NULL).  Argument checks and return codes are those of sfm_fund_ransac.
+ * Everything runs on the handle's stream without host synchronisation. */
+int sfm_hom_workspace_bytes(int64_t n_points, int32_t n_seg, int32_t n_hyp, int64_t* bytes_host);
+int sfm_hom_draw_samples(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, int32_t n_hyp, uint64_t seed,
+                         int32_t* samples);
+int sfm_hom_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_seg, const float* pts1, const float* pts2,
+                   int64_t n, const int32_t* samples, int32_t n_hyp, double threshold, int32_t refine,
+                   double* H, uint8_t* mask, int32_t* n_inliers, int32_t* status, int32_t* hyp_count,
+                   int32_t* refined, void* workspace, int64_t workspace_bytes);
 
 /* ------------------------------------------------------------- relative-pose recovery, batched over image pairs
  * The cv2.recoverPose(E, pts1, pts2, K) call of the reference's find_best_initial_pair / initialize_reconstruction, for

@@ -2,6 +2,7 @@
 
 from .twoview import FundamentalMixin, estimate_fundamental_batched, find_fundamental  # noqa: F401
 from .essential import EssentialMixin, estimate_essential_batched, find_essential  # noqa: F401
+from .homography import HomographyMixin, estimate_homography_batched, find_homography  # noqa: F401
 from .pose import InitialPairMixin, recover_pose, recover_pose_batched  # noqa: F401
 from .tracks import Tracks, build_tracks, tracks_from_pair_files  # noqa: F401
 from .triangulate import Triangulation, triangulate_tracks, triangulate_tracks_raw  # noqa: F401

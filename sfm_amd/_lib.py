@@ -15,7 +15,7 @@ METRIC_L2_U8, METRIC_L2_F32, METRIC_HAMMING = 0, 1, 2
 SC_COUNT = 16
 PROF_SLOTS = ("lin_obs", "lin_rest", "build_G", "schur", "chol", "trsv", "backsub", "step", "knn", "schur_items",
               "fund_hyp", "pnp_hyp", "pose_vote", "feat_score", "feat_select", "feat_scatter", "feat_blur", "feat_describe",
-              "ess_solve", "ess_score")
+              "ess_solve", "ess_score", "hom_hyp")
 
 i32, i64, f64, vp = C.c_int32, C.c_int64, C.c_double, C.c_void_p
 
@@ -142,6 +142,9 @@ SIGNATURES = {
     "sfm_ess_workspace_bytes": (C.c_int, [i64, i32, i32, C.POINTER(i64)]),
     "sfm_ess_draw_samples": (C.c_int, [vp, vp, i32, i32, C.c_uint64, vp]),
     "sfm_ess_ransac": (C.c_int, [vp, vp, i32, vp, vp, i64, vp, vp, i32, f64, i32, vp, vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_hom_workspace_bytes": (C.c_int, [i64, i32, i32, C.POINTER(i64)]),
+    "sfm_hom_draw_samples": (C.c_int, [vp, vp, i32, i32, C.c_uint64, vp]),
+    "sfm_hom_ransac": (C.c_int, [vp, vp, i32, vp, vp, i64, vp, i32, f64, i32, vp, vp, vp, vp, vp, vp, vp, i64]),
     "sfm_pose_workspace_bytes": (C.c_int, [i64, i32, C.POINTER(i64)]),
     "sfm_pose_recover": (C.c_int, [vp, vp, i32, vp, vp, i64, vp, i32, vp, vp, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64]),
     "sfm_tracks_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),

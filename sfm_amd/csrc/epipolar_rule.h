@@ -2,13 +2,9 @@
 // twoview.hip (fundamental matrix) and essential.hip (essential matrix), so that both count an inlier alike, bit for bit.
 // Included by .hip files only.
 #pragma once
-#include "common.h"
+#include "ransac_kernels.h"
 
 constexpr int FUND_CHUNK = 512;      // points per LDS stage of the scoring loop: 512 x 4 doubles = 16 KiB
-
-__device__ __forceinline__ bool finite4(float2 p, float2 q) {
-  return isfinite(p.x) && isfinite(p.y) && isfinite(q.x) && isfinite(q.y);
-}
 
 // the error rule without its divisions: max(s^2/den2, s^2/den1) <= thr2  <=>  s^2 <= thr2 * min(den1, den2), with
 // min > 0 required so that a zero line (or F = 0, the empty candidate slot) never counts.  NaN fails every test.

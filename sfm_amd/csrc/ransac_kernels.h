@@ -1,6 +1,6 @@
-// The device side of a batched, replayable RANSAC, shared by twoview.hip and pnp.hip (and, for load_k4, pose.hip): the
-// sample kernel, the block sums, the whole-segment inlier count, the winner rule and the 9 x 9 Jacobi of the refits, for
-// workgroups of 256 threads.
+// The device side of a batched, replayable RANSAC, shared by twoview.hip, homography.hip and pnp.hip (and, for load_k4,
+// pose.hip): the sample kernel, the block sums, the Hartley normalisation of the two-view stages, the whole-segment
+// inlier count, the winner rule and the 9 x 9 Jacobi of the refits, for workgroups of 256 threads.
 // Included by .hip files only; what also compiles for the host stays in ransac_common.h.
 #pragma once
 #include "common.h"
@@ -85,7 +85,61 @@ __device__ __forceinline__ double block_total(const double (*s_red)[K], int k) {
   return (s_red[0][k] + s_red[1][k]) + (s_red[2][k] + s_red[3][k]);
 }
 
+__device__ __forceinline__ bool finite4(float2 p, float2 q) {
+  return isfinite(p.x) && isfinite(p.y) && isfinite(q.x) && isfinite(q.y);
+}
+
+// ------------------------------------------------------------------------------------------ normalisation
+// Hartley transform per segment and image, over the finite matches (twoview.hip and homography.hip): x' = sc * (x - c),
+// centroid c, mean distance sqrt(2) after scaling.
+// T[s] = {sc1, cx1, cy1, sc2, cx2, cy2}: the 2 x 3 upper rows [sc 0 -sc*cx; 0 sc -sc*cy] in factored form.  A template
+// only so that the kernel exists in the files that launch it; BLOCK is the workgroup size, 256.
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_hartley_normalise(const int64_t* __restrict__ seg_ptr, int64_t n,
+                                                             const float2* __restrict__ pts1, const float2* __restrict__ pts2,
+                                                             double* __restrict__ T) {
+  static_assert(BLOCK == 256, "block_sum adds four waves");
+  const int s = blockIdx.x, tid = threadIdx.x;
+  int64_t b; int M;
+  seg_range(seg_ptr, s, n, b, M);
+  double sx1 = 0, sy1 = 0, sx2 = 0, sy2 = 0, cnt = 0;
+  for (int i = tid; i < M; i += 256) {
+    const float2 p = pts1[b + i], q = pts2[b + i];
+    if (finite4(p, q)) { sx1 += p.x; sy1 += p.y; sx2 += q.x; sy2 += q.y; cnt += 1.0; }
+  }
+  cnt = block_sum(cnt);
+  const double inv = cnt > 0 ? 1.0 / cnt : 0.0;
+  const double cx1 = block_sum(sx1) * inv, cy1 = block_sum(sy1) * inv;
+  const double cx2 = block_sum(sx2) * inv, cy2 = block_sum(sy2) * inv;
+  double d1 = 0, d2 = 0;
+  for (int i = tid; i < M; i += 256) {
+    const float2 p = pts1[b + i], q = pts2[b + i];
+    if (finite4(p, q)) {
+      const double ax = p.x - cx1, ay = p.y - cy1, bx = q.x - cx2, by = q.y - cy2;
+      d1 += sqrt(ax * ax + ay * ay); d2 += sqrt(bx * bx + by * by);
+    }
+  }
+  d1 = block_sum(d1) * inv; d2 = block_sum(d2) * inv;
+  if (tid == 0) {
+    double* t = T + 6 * (int64_t)s;
+    t[0] = d1 > 0 ? sqrt(2.0) / d1 : 1.0; t[1] = cx1; t[2] = cy1;
+    t[3] = d2 > 0 ? sqrt(2.0) / d2 : 1.0; t[4] = cx2; t[5] = cy2;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- selection
+// a 3 x 3 model m as m / m[8] when that is finite (m[8] / m[8] == 1 exactly), m as it is otherwise: F[2][2] = 1 of
+// k_fund_select, H[2][2] = 1 of k_hom_select
+__device__ __forceinline__ void scale_last_to_one(double (&f)[9]) {
+  const double d = f[8];
+  bool ok = d != 0.0;
+  double g[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) { g[e] = f[e] / d; ok = ok && isfinite(g[e]); }
+#pragma unroll
+  for (int e = 0; e < 9; ++e) f[e] = ok ? g[e] : f[e];
+}
+
 // inliers of a model over the whole segment [b, b + M), counted by the workgroup (every thread takes its own points);
 // inlier(i) is the stage's rule for point i of the batch.  Writes the mask when `mask` is not null.
 template <typename Inlier>

@@ -9,8 +9,8 @@
 // own, stateless sample generator, so that the result is a function of (points, seed) alone and a NumPy reference
 // can follow the device hypothesis by hypothesis (tests/fundamental_reference.py).
 //
-// The sample kernel (k_ransac_samples<7, 7>), the block sums, the whole-segment count and the winner rule are shared with
-// pnp.hip (ransac_kernels.h).  The generator's rule stands above draw_distinct<N> in ransac_common.h and is restated in
+// The sample kernel (k_ransac_samples<7, 7>), the Hartley normalisation (with homography.hip), the block sums, the
+// whole-segment count and the winner rule are shared with pnp.hip (ransac_kernels.h).  The generator's rule stands above draw_distinct<N> in ransac_common.h and is restated in
 // NumPy by the tests (tests/ransac_reference.py); its fallback after 256 draws is never reached in practice:
 // 7 * (6/7)^256 = 5e-17 at M = 7.
 //
@@ -22,40 +22,6 @@
 #include "epipolar_rule.h"
 
 namespace {
-
-// ------------------------------------------------------------------------------------------ normalisation
-// Hartley transform per segment and image: x' = sc * (x - c), centroid c, mean distance sqrt(2) after scaling.
-// T[s] = {sc1, cx1, cy1, sc2, cx2, cy2}: the 2 x 3 upper rows [sc 0 -sc*cx; 0 sc -sc*cy] in factored form.
-__global__ __launch_bounds__(256) void k_fund_normalise(const int64_t* __restrict__ seg_ptr, int64_t n,
-                                                        const float2* __restrict__ pts1, const float2* __restrict__ pts2,
-                                                        double* __restrict__ T) {
-  const int s = blockIdx.x, tid = threadIdx.x;
-  int64_t b; int M;
-  seg_range(seg_ptr, s, n, b, M);
-  double sx1 = 0, sy1 = 0, sx2 = 0, sy2 = 0, cnt = 0;
-  for (int i = tid; i < M; i += 256) {
-    const float2 p = pts1[b + i], q = pts2[b + i];
-    if (finite4(p, q)) { sx1 += p.x; sy1 += p.y; sx2 += q.x; sy2 += q.y; cnt += 1.0; }
-  }
-  cnt = block_sum(cnt);
-  const double inv = cnt > 0 ? 1.0 / cnt : 0.0;
-  const double cx1 = block_sum(sx1) * inv, cy1 = block_sum(sy1) * inv;
-  const double cx2 = block_sum(sx2) * inv, cy2 = block_sum(sy2) * inv;
-  double d1 = 0, d2 = 0;
-  for (int i = tid; i < M; i += 256) {
-    const float2 p = pts1[b + i], q = pts2[b + i];
-    if (finite4(p, q)) {
-      const double ax = p.x - cx1, ay = p.y - cy1, bx = q.x - cx2, by = q.y - cy2;
-      d1 += sqrt(ax * ax + ay * ay); d2 += sqrt(bx * bx + by * by);
-    }
-  }
-  d1 = block_sum(d1) * inv; d2 = block_sum(d2) * inv;
-  if (tid == 0) {
-    double* t = T + 6 * (int64_t)s;
-    t[0] = d1 > 0 ? sqrt(2.0) / d1 : 1.0; t[1] = cx1; t[2] = cy1;
-    t[3] = d2 > 0 ? sqrt(2.0) / d2 : 1.0; t[4] = cx2; t[5] = cy2;
-  }
-}
 
 // --------------------------------------------------------------------------------------------- the models
 __device__ __forceinline__ double det3(double a0, double a1, double a2, double a3, double a4, double a5, double a6,
@@ -228,17 +194,6 @@ __global__ __launch_bounds__(256) void k_fund_hypotheses(const int64_t* __restri
 }
 
 // ---------------------------------------------------------------------------------------------- selection
-// F / F[8] when that is finite (F[8] / F[8] == 1 exactly), F as it is otherwise
-__device__ __forceinline__ void scale_f22(double (&f)[9]) {
-  const double d = f[8];
-  bool ok = d != 0.0;
-  double g[9];
-#pragma unroll
-  for (int e = 0; e < 9; ++e) { g[e] = f[e] / d; ok = ok && isfinite(g[e]); }
-#pragma unroll
-  for (int e = 0; e < 9; ++e) f[e] = ok ? g[e] : f[e];
-}
-
 // inliers of f over the whole segment (staged through LDS like the scoring loop is not needed here: every thread takes
 // its own points); writes the mask when `mask` is not null
 __device__ __forceinline__ int fund_count(const double (&f)[9], const float2* __restrict__ pts1,
@@ -269,7 +224,7 @@ __global__ __launch_bounds__(256) void k_fund_select(const int64_t* __restrict__
   if (st == 0) {                                         // uniform over the workgroup
 #pragma unroll
     for (int e = 0; e < 9; ++e) f[e] = hyp_F[((int64_t)s * H + hp) * 9 + e];
-    scale_f22(f);
+    scale_last_to_one(f);
     count = fund_count(f, pts1, pts2, b, M, thr2, mask);
   }
   ransac_store_winner(s, st, b, M, f, count, F, mask, n_inliers, status, refined);
@@ -379,7 +334,7 @@ __global__ __launch_bounds__(256) void k_fund_refit(const int64_t* __restrict__ 
 #pragma unroll
   for (int e = 0; e < 9; ++e) good = good && isfinite(f[e]);
   if (!good) return;                                     // uniform: every thread computed the same f
-  scale_f22(f);
+  scale_last_to_one(f);
   const int count = fund_count(f, pts1, pts2, b, M, thr2, nullptr);
   if (count < have) return;
   (void)fund_count(f, pts1, pts2, b, M, thr2, mask);
@@ -439,7 +394,7 @@ extern "C" int sfm_fund_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_s
   const float2* p2 = (const float2*)pts2;
   const int nblk = (n_hyp + 255) / 256;
   SFM_HIP(h, hipMemsetAsync(mask, 0, (size_t)n, h->stream));    // matches outside every segment
-  hipLaunchKernelGGL(k_fund_normalise, dim3(n_seg), dim3(256), 0, h->stream, seg_ptr, n, p1, p2, w.T);
+  hipLaunchKernelGGL(k_hartley_normalise<256>, dim3(n_seg), dim3(256), 0, h->stream, seg_ptr, n, p1, p2, w.T);
   sfm_prof_begin(h, SFM_PROF_FUND_HYP);
   hipLaunchKernelGGL(k_fund_hypotheses, dim3((unsigned)n_seg * nblk), dim3(256), 0, h->stream, seg_ptr, n, p1, p2,
                      samples, n_hyp, nblk, thr2, (const double*)w.T, counts, w.hyp_F);

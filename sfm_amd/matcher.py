@@ -367,7 +367,7 @@ class ImageMatcher(VerificationMixin, FundamentalMixin):
             out.append(DMatchList(*res))
         return out
 
-    def process_pairs(self, keypoints, descs, pairs, min_matches=5, guided=False, **guided_options):
+    def process_pairs(self, keypoints, descs, pairs, min_matches=5, guided=False, homography=False, **guided_options):
         """process_image_pair (find_matches.py:246-310) for every (i, j) of `pairs`, minus the image I/O and the visualisation,
         in three batched device steps: match_pairs (:272) -> the float32 pts1 / pts2 gathers (:278-279), pairs under
         `min_matches` dropped (:274) -> estimate_fundamental_batched (:282) -> verify_pairs (:288).
@@ -377,9 +377,15 @@ class ImageMatcher(VerificationMixin, FundamentalMixin):
         {'matches': DMatchList, 'pts1', 'pts2' [M,2] float32, 'F' [3,3], 'inlier_mask' [M] bool, 'symmetric_errors',
         'metrics': the dictionary of geometric_verification, 'quality_ok': verify_match_quality of it}.
         guided=True passes the result through `guided_pairs` (with `guided_options`): every pair with a model is matched again
-        under its F."""
+        under its F.
+        homography=True runs one more batched call, `estimate_homography_batched` with the threshold, hypothesis count and
+        seed of the F stage, over the pairs that have a result: each of those entries gains 'H' ([3,3] with x2 ~ H x1, or
+        None) and 'n_homography', the inlier count of H over the entry's matches - set against the inliers of F it tells a
+        planar or rotation-only pair from a general one."""
         import logging
         pairs = [(int(i), int(j)) for i, j in pairs]
+        if homography:
+            return self._with_homographies(self.process_pairs(keypoints, descs, pairs, min_matches, guided=guided, **guided_options))
         if guided:
             return self.guided_pairs(keypoints, descs, pairs, self.process_pairs(keypoints, descs, pairs, min_matches), **guided_options)
         if guided_options:
@@ -412,6 +418,19 @@ class ImageMatcher(VerificationMixin, FundamentalMixin):
                             "inlier_mask": v["inlier_mask"], "symmetric_errors": v["symmetric_errors"],
                             "metrics": v["metrics"], "quality_ok": self.verify_match_quality(v)}
         return out
+
+    def _with_homographies(self, results):
+        """`results` of process_pairs with 'H' and 'n_homography' added to every entry that is not None: one batched call."""
+        from .homography import estimate_homography_batched
+        live = [s for s, r in enumerate(results) if r is not None]
+        if live:
+            hom = estimate_homography_batched([results[s]["pts1"] for s in live], [results[s]["pts2"] for s in live],
+                                              self.fund_threshold, n_hypotheses=self.fund_hypotheses, seed=self.fund_seed,
+                                              device=self.device)
+            for s, (H, mask) in zip(live, hom):
+                results[s]["H"] = H
+                results[s]["n_homography"] = 0 if mask is None else int(np.count_nonzero(mask))
+        return results
 
     def guided_pairs(self, keypoints, descs, pairs, results, gate=3.0, ratio=None, max_distance=None, cross_check=False):
         """Guided matching on top of what `process_pairs(keypoints, descs, pairs)` returned: every pair with a result is matched
@@ -455,17 +474,17 @@ class ImageMatcher(VerificationMixin, FundamentalMixin):
         from .features import detect_features
         return detect_features(image, mask, device=self.device)
 
-    def process_images(self, images, pairs, masks=None, min_matches=5, guided=False, **guided_options):
+    def process_images(self, images, pairs, masks=None, min_matches=5, guided=False, homography=False, **guided_options):
         """From pixel arrays to verified pairs: detect_and_describe_batched over all images, then process_pairs with the
         Hamming metric.  Returns (features, results): one sfm_amd.features.Features per image and what
         process_pairs([f.xy ...], [f.descriptors ...], pairs) gives; `self.build_tracks([f.xy for f in features], pairs,
-        results)` joins them into Tracks.  guided / guided_options: as in process_pairs."""
+        results)` joins them into Tracks.  guided / guided_options / homography: as in process_pairs."""
         from .features import detect_and_describe_batched
         feats = detect_and_describe_batched(images, masks, device=self.device)
         metric, self.metric = self.metric, "hamming"
         try:
             results = self.process_pairs([f.xy for f in feats], [f.descriptors for f in feats], pairs, min_matches, guided=guided,
-                                         **guided_options)
+                                         homography=homography, **guided_options)
         finally:
             self.metric = metric
         return feats, results

@@ -2,12 +2,12 @@
 """Device-time measurement of the driver-row kernels with inputs resident in HBM:
 association (pair tests/s), two-view triangulation (tracks/s), epipolar verification (matches/s), and the batched
 fundamental-matrix RANSAC beside the batched matcher it follows in the pair loop, the batched essential-matrix RANSAC
-beside it on the same pairs, the batched PnP RANSAC of the
+beside it on the same pairs, the batched homography RANSAC beside it as well, the batched PnP RANSAC of the
 camera registration, the batched relative-pose recovery of the initial-pair scan, the track building, the N-view
 triangulation of the tracks, the resection lists, the gate evaluation and the incremental loop on top of them, and the
 feature detection / description stage in front of them all.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
 functions to time on a bounded sample of the same inputs (this tool itself never imports oracle/).
-usage: python tools/bench_driver.py [--reps 20] [--fundamental-only | --essential-only | --pnp-only | --pose-only | --tracks-only | --triangulate-only |
+usage: python tools/bench_driver.py [--reps 20] [--fundamental-only | --essential-only | --homography-only | --pnp-only | --pose-only | --tracks-only | --triangulate-only |
        --incremental-only | --features-only | --guided-only]"""
 import argparse
 import ctypes as C
@@ -287,6 +287,60 @@ def measure_essential(reps=20, n_hyp=1024, emit=None):
     if emit:
         emit(row)
     return [row]
+
+
+def measure_homography(reps=20, n_hyp=1024, emit=None):
+    """sfm_hom_ransac on the cases of measure_fundamental - the 148 shipped pairs and 630 synthetic pairs of 300 matches -
+    inputs resident in HBM: the whole call with and without the refit and k_hom_hypotheses alone (the handle's event
+    slot), beside sfm_fund_ransac on the same pairs with the same number of hypotheses in the same run."""
+    import torch
+    from sfm_amd import _lib
+    from sfm_amd.driver import _p, _ptr_array
+    h = _lib.get_handle(0)
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0)
+    g = np.load(os.path.join(ROOT, "tests", "golden", "bunny_pairs.npz"), allow_pickle=False)
+    off = g["offsets"]
+    shipped = ([g["pts1"][off[s]:off[s + 1]] for s in range(len(off) - 1)], [g["pts2"][off[s]:off[s + 1]] for s in range(len(off) - 1)])
+    results = []
+    for name, (p1, p2) in (("shipped_148_pairs", shipped), ("synthetic_630_pairs_x_300", _synthetic_pairs(rng, 630, 300))):
+        n_seg = len(p1)
+        lengths = [len(a) for a in p1]
+        n = int(sum(lengths))
+        _, ptr = _ptr_array(lengths, dev)
+        d1 = torch.from_numpy(np.concatenate(p1).astype(np.float32)).to(dev)
+        d2 = torch.from_numpy(np.concatenate(p2).astype(np.float32)).to(dev)
+        model = torch.empty((n_seg, 9), dtype=torch.float64, device=dev)
+        mask = torch.empty(n, dtype=torch.uint8, device=dev)
+        meta = torch.empty((3, n_seg), dtype=torch.int32, device=dev)
+        row = {"kernel": "hom_ransac", "case": name, "pairs": n_seg, "matches": n, "hypotheses": n_hyp}
+        for stage, size in (("hom", 4), ("fund", 7)):
+            smp = torch.empty((n_seg, n_hyp, size), dtype=torch.int32, device=dev)
+            h.call(f"sfm_{stage}_draw_samples", _p(ptr), n_seg, n_hyp, C.c_uint64(0), _p(smp))
+            need = C.c_int64()
+            h.check(getattr(h.lib, f"sfm_{stage}_workspace_bytes")(n, n_seg, n_hyp, C.byref(need)), f"sfm_{stage}_workspace_bytes")
+            ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+
+            def ransac(refine=1):
+                h.call(f"sfm_{stage}_ransac", _p(ptr), n_seg, _p(d1), _p(d2), n, _p(smp), n_hyp, C.c_double(3.0), refine,
+                       _p(model), _p(mask), _p(meta[0]), _p(meta[1]), C.c_void_p(0), _p(meta[2]), _p(ws), need.value)
+            for _ in range(3):
+                ransac()
+            row[f"ms_{stage}_call_with_refit"] = timed(ransac, reps) * 1e3
+            row[f"ms_{stage}_call_without_refit"] = timed(lambda: ransac(0), reps) * 1e3
+            h.set_profiling(True); h.profile()
+            for _ in range(reps):
+                ransac()
+            ms, launches = h.profile()[f"{stage}_hyp"]
+            h.set_profiling(False)
+            row[f"ms_k_{stage}_hypotheses"] = ms / max(launches, 1)
+            row[f"{stage}_pairs_with_model"] = int((meta[1] == 0).sum().item())
+            row[f"{stage}_refit_kept"] = int(meta[2].sum().item())
+            row[f"{stage}_inliers"] = int(meta[0].sum().item())
+        results.append(row)
+        if emit:
+            emit(row)
+    return results
 
 
 PNP_FLOP_PER_TEST = 30       # 9 fma for p = P [X; 1], 2 fma + 1 fma + 1 mul for the error, 2 mul for thr^2 p2^2 (fma = 2)
@@ -888,6 +942,7 @@ def main():
     ap.add_argument("--corr", type=int, default=20000)
     ap.add_argument("--fundamental-only", action="store_true", help="only the fundamental-matrix RANSAC rows")
     ap.add_argument("--essential-only", action="store_true", help="only the essential-matrix RANSAC row")
+    ap.add_argument("--homography-only", action="store_true", help="only the homography RANSAC rows (beside the fundamental-matrix RANSAC)")
     ap.add_argument("--pnp-only", action="store_true", help="only the PnP RANSAC rows")
     ap.add_argument("--pose-only", action="store_true", help="only the relative-pose recovery rows")
     ap.add_argument("--tracks-only", action="store_true", help="only the track-building rows")
@@ -897,7 +952,7 @@ def main():
     ap.add_argument("--guided-only", action="store_true", help="only the guided-matching row (beside the blind matcher)")
     a = ap.parse_args()
     emit = lambda d: print(json.dumps(d), flush=True)
-    only = a.fundamental_only or a.essential_only or a.pnp_only or a.pose_only or a.tracks_only or a.triangulate_only or a.incremental_only or \
+    only = a.fundamental_only or a.essential_only or a.homography_only or a.pnp_only or a.pose_only or a.tracks_only or a.triangulate_only or a.incremental_only or \
         a.features_only or a.guided_only
     if not only:
         measure(a.reps, a.tracks, a.corr, emit=emit)
@@ -905,6 +960,8 @@ def main():
         measure_fundamental(a.reps, emit=emit)
     if a.essential_only or not only:
         measure_essential(a.reps, emit=emit)
+    if a.homography_only or not only:
+        measure_homography(a.reps, emit=emit)
     if a.pnp_only or not only:
         measure_pnp(a.reps, emit=emit)
     if a.pose_only or not only:

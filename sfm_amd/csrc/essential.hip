@@ -22,7 +22,7 @@
 //                 of a hypothesis is the largest of its slots, ties to the lowest slot.
 //   k_ess_select  per segment the winner (ransac_winner: most inliers, ties to the lowest hypothesis), its mask and count.
 //   k_ess_refit   refine != 0: the same solver over ALL inliers of the winner.  The 45 entries of A^T A are summed in a
-//                 fixed order, the four eigenvectors of its smallest eigenvalues (jacobi9_lds, shared with
+//                 fixed order, the four eigenvectors of its smallest eigenvalues (normal9_eigen, shared with
 //                 k_fund_refit) stand in for the null space, lane 0 runs steps 4 to 7, every candidate is scored
 //                 over the whole segment by the workgroup, and the best (ties: the first) replaces the winner only if
 //                 its count is not lower; refined[s] = 1 then.
@@ -78,20 +78,8 @@ __global__ __launch_bounds__(64) void k_ess_solve(const int64_t* __restrict__ se
   double Bs[4][9];
   int nc = 0;
   if (M >= 5) {
-    bool ok = true;
-    int idx[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      idx[k] = samples[g * 5 + k];
-      ok = ok && idx[k] >= 0 && idx[k] < M;
-    }
     float px[5][4];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      const int id = ok ? idx[k] : 0;
-      const float2 p = pts1[b + id], q = pts2[b + id];
-      px[k][0] = p.x; px[k][1] = p.y; px[k][2] = q.x; px[k][3] = q.y;
-    }
+    const bool ok = load_sample<5>(samples, g, true, M, b, pts1, pts2, px);
     const auto [fx, fy, cx, cy] = load_k4(Kseg, s);
     if (ok) nc = fivept::solve_sample(px, fx, fy, cx, cy, ws, Bs);
   }
@@ -136,16 +124,9 @@ __global__ __launch_bounds__(256) void k_ess_score(const int64_t* __restrict__ s
     make_F(fx, fy, cx, cy, E, F);
   }
   int cnt = 0;
-  for (int base = 0; base < M; base += FUND_CHUNK) {
-    const int c = (M - base < FUND_CHUNK) ? (M - base) : FUND_CHUNK;
-    __syncthreads();
-    stage_points(s_pt, pts1, pts2, b + base, c, 256);
-    __syncthreads();
-    for (int i = 0; i < c; ++i) {
-      const double2 p = s_pt[2 * i], q = s_pt[2 * i + 1];
-      cnt += fund_inlier(F, p.x, p.y, q.x, q.y, thr2) ? 1 : 0;
-    }
-  }
+  for_each_staged_point(s_pt, pts1, pts2, b, M, [&](double2 p, double2 q) {
+    cnt += fund_inlier(F, p.x, p.y, q.x, q.y, thr2) ? 1 : 0;
+  });
   s_cnt[tid] = cnt;
   __syncthreads();
   if (lane && slot == 0) {
@@ -160,16 +141,6 @@ __global__ __launch_bounds__(256) void k_ess_score(const int64_t* __restrict__ s
 }
 
 // ---------------------------------------------------------------------------------------------- selection
-// inliers of F over the whole segment; writes the mask when `mask` is not null
-__device__ __forceinline__ int ess_count(const double (&F)[9], const float2* __restrict__ pts1,
-                                         const float2* __restrict__ pts2, int64_t b, int M, double thr2,
-                                         uint8_t* __restrict__ mask) {
-  return segment_count(b, M, mask, [&](int64_t i) {
-    const float2 p = pts1[i], q = pts2[i];
-    return finite4(p, q) && fund_inlier(F, (double)p.x, (double)p.y, (double)q.x, (double)q.y, thr2);
-  });
-}
-
 __global__ __launch_bounds__(256) void k_ess_select(const int64_t* __restrict__ seg_ptr, int64_t n,
                                                     const float2* __restrict__ pts1, const float2* __restrict__ pts2,
                                                     const double* __restrict__ Kseg, int H, double thr2,
@@ -194,7 +165,7 @@ __global__ __launch_bounds__(256) void k_ess_select(const int64_t* __restrict__ 
     const auto [fx, fy, cx, cy] = load_k4(Kseg, s);
     double F[9];
     make_F(fx, fy, cx, cy, E, F);
-    count = ess_count(F, pts1, pts2, b, M, thr2, mask);
+    count = fund_count(F, pts1, pts2, b, M, thr2, mask);
   }
   ransac_store_winner(s, st, b, M, E, count, E_out, mask, n_inliers, status, refined);
 }
@@ -231,16 +202,7 @@ __global__ __launch_bounds__(256) void k_ess_refit(const int64_t* __restrict__ s
 #pragma unroll
       for (int v = u; v < 9; ++v) acc[k++] += r[u] * r[v];
   }
-  block_sum_wide(acc, s_red);
-  if (tid < 81) {
-    const int u = tid / 9, v = tid % 9;
-    const int lo = u < v ? u : v, hi = u < v ? v : u;
-    const int k = lo * 9 - lo * (lo - 1) / 2 + (hi - lo);
-    s_A[u][v] = block_total(s_red, k);
-    s_V[u][v] = (u == v) ? 1.0 : 0.0;
-  }
-  __syncthreads();
-  jacobi9_lds(s_A, s_V);
+  normal9_eigen(acc, s_red, s_A, s_V);
   if (tid == 0) {
     // the eigenvectors of the four smallest eigenvalues (ties: the lowest index), then steps 4 to 7 on one lane
     double Bs[4][9];
@@ -274,20 +236,15 @@ __global__ __launch_bounds__(256) void k_ess_refit(const int64_t* __restrict__ s
 #pragma unroll
     for (int e = 0; e < 9; ++e) E[e] = s_E[k][e];
     make_F(fx, fy, cx, cy, E, F);
-    const int c = ess_count(F, pts1, pts2, b, M, thr2, nullptr);
+    const int c = fund_count(F, pts1, pts2, b, M, thr2, nullptr);
     if (c > best) { best = c; bk = k; }
   }
   if (best < have) return;
 #pragma unroll
   for (int e = 0; e < 9; ++e) E[e] = s_E[bk][e];
   make_F(fx, fy, cx, cy, E, F);
-  (void)ess_count(F, pts1, pts2, b, M, thr2, mask);
-  if (tid == 0) {
-#pragma unroll
-    for (int e = 0; e < 9; ++e) E_out[9 * (int64_t)s + e] = E[e];
-    n_inliers[s] = best;
-    if (refined) refined[s] = 1;
-  }
+  (void)fund_count(F, pts1, pts2, b, M, thr2, mask);
+  ransac_store_refit(s, E, best, E_out, n_inliers, refined);
 }
 
 struct ess_ws {

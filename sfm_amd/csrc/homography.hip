@@ -16,11 +16,11 @@
 //   k_hartley_normalise  (ransac_kernels.h, shared with sfm_fund_ransac) the segment's transforms over its finite matches
 //   k_hom_hypotheses     one lane per (segment, hypothesis), 256 hypotheses of ONE segment per workgroup: the sample
 //                        rule and the solver of homography_solve.h, one candidate per lane in registers, the segment's
-//                        matches staged through LDS in FUND_CHUNK pieces (stage_points) and read back as broadcasts
+//                        matches staged through LDS and read back as broadcasts (for_each_staged_point, epipolar_rule.h)
 //   k_hom_select         the winner (ransac_winner, 4 minimum points), scaled, its mask and count
 //   k_hom_refit          refine != 0 and at least 4 inliers: both rows of every inlier go into the 45 unique entries of
-//                        the 9 x 9 normal matrix (block_sum_wide), smallest eigenvector by jacobi9_lds, denormalised,
-//                        scaled, re-scored with the same rule; it replaces the winner only if its count is not lower
+//                        the 9 x 9 normal matrix, smallest eigenvector (normal9_eigen), denormalised, scaled,
+//                        re-scored with the same rule; it replaces the winner only if its count is not lower
 //
 // All arithmetic in float64.  Points arrive as float32 pixels [n][2] with a device seg_ptr[n_seg+1] (int64).  A match
 // with a NaN or infinite coordinate is left out of the Hartley statistics and is staged as NaN for the scoring, so it
@@ -57,20 +57,8 @@ __global__ __launch_bounds__(256) void k_hom_hypotheses(const int64_t* __restric
   }
   double Hc[9];
   {
-    bool ok = active;
-    int idx[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      idx[k] = active ? samples[slot * 4 + k] : 0;
-      ok = ok && idx[k] >= 0 && idx[k] < M;
-    }
     float px[4][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int id = ok ? idx[k] : 0;
-      const float2 p = pts1[b + id], q = pts2[b + id];
-      px[k][0] = p.x; px[k][1] = p.y; px[k][2] = q.x; px[k][3] = q.y;
-    }
+    const bool ok = load_sample<4>(samples, slot, active, M, b, pts1, pts2, px);
     double h[9];
     const bool good = homog::solve_sample(px, T + 6 * (int64_t)s, h) && ok;
 #pragma unroll
@@ -78,16 +66,9 @@ __global__ __launch_bounds__(256) void k_hom_hypotheses(const int64_t* __restric
   }
   // scoring: every lane walks all points of the segment with its candidate in registers
   int count = 0;
-  for (int base = 0; base < M; base += FUND_CHUNK) {
-    const int cnt = (M - base < FUND_CHUNK) ? (M - base) : FUND_CHUNK;
-    __syncthreads();
-    stage_points(s_pt, pts1, pts2, b + base, cnt, 256);
-    __syncthreads();
-    for (int i = 0; i < cnt; ++i) {
-      const double2 p = s_pt[2 * i], q = s_pt[2 * i + 1];
-      count += hom_inlier(Hc, p.x, p.y, q.x, q.y, thr2) ? 1 : 0;
-    }
-  }
+  for_each_staged_point(s_pt, pts1, pts2, b, M, [&](double2 p, double2 q) {
+    count += hom_inlier(Hc, p.x, p.y, q.x, q.y, thr2) ? 1 : 0;
+  });
   if (!active) return;
   hyp_count[slot] = count;
 #pragma unroll
@@ -164,18 +145,8 @@ __global__ __launch_bounds__(256) void k_hom_refit(const int64_t* __restrict__ s
 #pragma unroll
       for (int v = u; v < 9; ++v) acc[k++] += r0[u] * r0[v] + r1[u] * r1[v];
   }
-  block_sum_wide(acc, s_red);
-  if (tid < 81) {
-    const int u = tid / 9, v = tid % 9;
-    const int lo = u < v ? u : v, hi = u < v ? v : u;
-    const int k = lo * 9 - lo * (lo - 1) / 2 + (hi - lo);
-    s_A[u][v] = block_total(s_red, k);
-    s_V[u][v] = (u == v) ? 1.0 : 0.0;
-  }
-  __syncthreads();
-  jacobi9_lds(s_A, s_V);
-  int kmin = 0;
-  for (int k = 1; k < 9; ++k) if (s_A[k][k] < s_A[kmin][kmin]) kmin = k;
+  normal9_eigen(acc, s_red, s_A, s_V);
+  const int kmin = smallest_diagonal9(s_A);
   double hn[9], h[9];
 #pragma unroll
   for (int e = 0; e < 9; ++e) hn[e] = s_V[e][kmin];
@@ -185,32 +156,8 @@ __global__ __launch_bounds__(256) void k_hom_refit(const int64_t* __restrict__ s
   for (int e = 0; e < 9; ++e) good = good && isfinite(h[e]);
   if (!good) return;                                     // uniform: every thread computed the same h
   scale_last_to_one(h);
-  const int count = hom_count(h, pts1, pts2, b, M, thr2, nullptr);
-  if (count < have) return;
-  (void)hom_count(h, pts1, pts2, b, M, thr2, mask);
-  if (tid == 0) {
-#pragma unroll
-    for (int e = 0; e < 9; ++e) Hout[9 * (int64_t)s + e] = h[e];
-    n_inliers[s] = count;
-    if (refined) refined[s] = 1;
-  }
-}
-
-struct hom_ws {
-  double* T;
-  double* hyp_H;
-  int* hyp_count;
-  int64_t bytes;
-};
-
-hom_ws hom_layout(void* workspace, int32_t n_seg, int32_t n_hyp) {
-  ws_carve c{(char*)workspace};
-  hom_ws w;
-  w.T = c.take<double>((int64_t)n_seg * 6);
-  w.hyp_H = c.take<double>((int64_t)n_seg * n_hyp * 9);
-  w.hyp_count = c.take<int>((int64_t)n_seg * n_hyp);
-  w.bytes = c.bytes();
-  return w;
+  ransac_keep_refit(s, have, h, [&](uint8_t* m) { return hom_count(h, pts1, pts2, b, M, thr2, m); }, Hout, mask,
+                    n_inliers, refined);
 }
 
 }  // namespace
@@ -218,7 +165,7 @@ hom_ws hom_layout(void* workspace, int32_t n_seg, int32_t n_hyp) {
 // ================================================================================================ C ABI
 extern "C" int sfm_hom_workspace_bytes(int64_t n_points, int32_t n_seg, int32_t n_hyp, int64_t* bytes_host) {
   if (!bytes_host || n_points < 0 || n_seg < 0 || n_hyp < 1) return SFM_ERR_ARG;
-  *bytes_host = hom_layout(nullptr, n_seg, n_hyp).bytes;
+  *bytes_host = model9_layout(nullptr, n_seg, n_hyp).bytes;
   return SFM_OK;
 }
 
@@ -236,7 +183,7 @@ extern "C" int sfm_hom_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_se
   if (n == 0 || n_seg == 0) return SFM_OK;
   if (!seg_ptr || !pts1 || !pts2 || !samples || !H || !mask || !n_inliers || !status || !workspace)
     return sfm_fail(h, SFM_ERR_ARG, "sfm_hom_ransac", "null pointer");
-  const hom_ws w = hom_layout(workspace, n_seg, n_hyp);
+  const model9_ws w = model9_layout(workspace, n_seg, n_hyp);
   if (workspace_bytes < w.bytes) return sfm_fail(h, SFM_ERR_WORKSPACE, "sfm_hom_ransac", "workspace too small");
   int* counts = hyp_count ? hyp_count : w.hyp_count;
   const double thr2 = threshold * threshold;
@@ -247,10 +194,10 @@ extern "C" int sfm_hom_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_se
   hipLaunchKernelGGL(k_hartley_normalise<256>, dim3(n_seg), dim3(256), 0, h->stream, seg_ptr, n, p1, p2, w.T);
   sfm_prof_begin(h, SFM_PROF_HOM_HYP);
   hipLaunchKernelGGL(k_hom_hypotheses, dim3((unsigned)n_seg * nblk), dim3(256), 0, h->stream, seg_ptr, n, p1, p2,
-                     samples, n_hyp, nblk, thr2, (const double*)w.T, counts, w.hyp_H);
+                     samples, n_hyp, nblk, thr2, (const double*)w.T, counts, w.hyp_model);
   sfm_prof_end(h, SFM_PROF_HOM_HYP);
   hipLaunchKernelGGL(k_hom_select, dim3(n_seg), dim3(256), 0, h->stream, seg_ptr, n, p1, p2, n_hyp, thr2,
-                     (const int*)counts, (const double*)w.hyp_H, H, mask, n_inliers, status, refined);
+                     (const int*)counts, (const double*)w.hyp_model, H, mask, n_inliers, status, refined);
   if (refine)
     hipLaunchKernelGGL(k_hom_refit, dim3(n_seg), dim3(256), 0, h->stream, seg_ptr, n, p1, p2, thr2,
                        (const double*)w.T, H, mask, n_inliers, (const int*)status, refined);

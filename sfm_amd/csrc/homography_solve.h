@@ -10,18 +10,15 @@
 //
 // Solve, on the segment's Hartley-normalised coordinates (t = {sc1, cx1, cy1, sc2, cx2, cy2}, x' = sc (x - c)): the
 // 8 x 9 system with the rows [x, y, 1, 0, 0, 0, -u x, -u y, -u] and [0, 0, 0, x, y, 1, -v x, -v y, -v] per match
-// (x, y) -> (u, v).  Its null vector without pivoting, as k_fund_hypotheses finds its two: Givens rotations of column
+// (x, y) -> (u, v).  Its null vector without pivoting, as fundamental_solve.h finds its two: Givens rotations of column
 // pairs from the right, A G = [L 0] with L lower triangular, one row at a time (row i: apply the rotations so far, then
 // zero its entries i+1..8), so only the 36 (c, s) pairs are live and every array index is a compile-time constant
-// after unrolling.  The last column of G = G_1 ... G_36 is the null vector Hn;  H = T2^-1 Hn T1.  A non-finite H is no
-// model.
+// after unrolling (rot_index, ransac_common.h, numbers them).  The last column of G = G_1 ... G_36 is the null vector
+// Hn;  H = T2^-1 Hn T1.  A non-finite H is no model.
 #pragma once
 #include "ransac_common.h"
 
 namespace homog {
-
-// rotation k of the elimination acts on columns (i, j), j > i: k = i*8 - i*(i-1)/2 + (j - i - 1), 36 in all
-SFM_HD constexpr int rot_index(int i, int j) { return i * 8 - i * (i - 1) / 2 + (j - i - 1); }
 
 // one triple of the sample rule; px[m] = (x, y, u, v) of match m
 SFM_HD bool triple_ok(const float (&px)[4][4], int i, int j, int k) {

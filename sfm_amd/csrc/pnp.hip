@@ -344,15 +344,8 @@ __global__ __launch_bounds__(256) void k_pnp_refine(const int64_t* __restrict__ 
   }
   if (!good) return;                                     // uniform: every thread holds the same pose
   make_P(fx, fy, cx, cy, Rt, P);
-  const int count = pnp_count(P, X, uv, b, M, thr2, nullptr);
-  if (count < have) return;
-  (void)pnp_count(P, X, uv, b, M, thr2, mask);
-  if (tid == 0) {
-#pragma unroll
-    for (int e = 0; e < 12; ++e) Rt_out[12 * (int64_t)s + e] = Rt[e];
-    n_inliers[s] = count;
-    if (refined) refined[s] = 1;
-  }
+  ransac_keep_refit(s, have, Rt, [&](uint8_t* m) { return pnp_count(P, X, uv, b, M, thr2, m); }, Rt_out, mask, n_inliers,
+                    refined);
 }
 
 struct pnp_ws {

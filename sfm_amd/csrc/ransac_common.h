@@ -1,7 +1,8 @@
-// What the batched RANSAC stages (twoview.hip, pnp.hip, pose.hip) share and the host can compile too: the segment
-// convention, the stateless sample generator and the closed-form cubic.  The functions marked SFM_HD build with g++, so
-// that the generator and the minimal solvers built on them can be checked on a CPU (tests/native/).  The device-only
-// part - kernels, block sums, the winner rule - is in ransac_kernels.h.
+// What the batched RANSAC stages (twoview.hip, essential.hip, homography.hip, pnp.hip, pose.hip) and their solver
+// headers share and the host can compile too: the segment convention, the stateless sample generator, the closed-form
+// cubic and the numbering of the Givens rotations.  The functions marked SFM_HD build with g++, so that the generator
+// and the minimal solvers built on them can be checked on a CPU (tests/native/).  The device-only part - kernels, block
+// sums, the winner rule - is in ransac_kernels.h.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -96,3 +97,7 @@ SFM_HD double cubic_newton2(double x, double A, double B, double Cc) {
   }
   return x;
 }
+
+// The Givens eliminations of fundamental_solve.h (7 x 9, 35 rotations) and homography_solve.h (8 x 9, 36) number their
+// rotations alike: rotation k acts on columns (i, j), j > i, with k = i*8 - i*(i-1)/2 + (j - i - 1)
+SFM_HD constexpr int rot_index(int i, int j) { return i * 8 - i * (i - 1) / 2 + (j - i - 1); }

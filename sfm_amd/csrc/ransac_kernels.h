@@ -1,6 +1,7 @@
-// The device side of a batched, replayable RANSAC, shared by twoview.hip, homography.hip and pnp.hip (and, for load_k4,
-// pose.hip): the sample kernel, the block sums, the Hartley normalisation of the two-view stages, the whole-segment
-// inlier count, the winner rule and the 9 x 9 Jacobi of the refits, for workgroups of 256 threads.
+// The device side of a batched, replayable RANSAC, shared by twoview.hip, essential.hip, homography.hip and pnp.hip
+// (and, for load_k4, pose.hip): the sample kernel and the gather of a sample's matches, the block sums, the Hartley
+// normalisation of twoview.hip and homography.hip, the whole-segment inlier count, the winner rule, the rule by which a
+// refit replaces the winner and the 9 x 9 normal matrix and Jacobi of the two-view refits, for workgroups of 256 threads.
 // Included by .hip files only; what also compiles for the host stays in ransac_common.h.
 #pragma once
 #include "common.h"
@@ -24,7 +25,7 @@ __global__ __launch_bounds__(256) void k_ransac_samples(const int64_t* __restric
   for (int k = 0; k < N; ++k) samples[g * N + k] = idx[k];
 }
 
-// what stands behind sfm_fund_draw_samples and sfm_pnp_draw_samples; `what` names the entry point in the error string
+// what stands behind every sfm_*_draw_samples; `what` names the entry point in the error string
 template <int N, int MIN_POINTS>
 int ransac_draw_samples(sfm_handle h, const char* what, const int64_t* seg_ptr, int32_t n_seg, int32_t n_hyp,
                         uint64_t seed, int32_t* samples) {
@@ -40,10 +41,29 @@ int ransac_draw_samples(sfm_handle h, const char* what, const int64_t* seg_ptr, 
   return SFM_OK;
 }
 
-// the scalar arguments sfm_fund_ransac and sfm_pnp_ransac turn down (the grid is n_seg x ceil(n_hyp / 256) workgroups)
+// the scalar arguments every sfm_*_ransac turns down (the grid is n_seg x ceil(n_hyp / 256) workgroups)
 inline bool ransac_bad_args(int64_t n, int32_t n_seg, int32_t n_hyp, double threshold) {
   return n < 0 || n_seg < 0 || n_hyp < 1 || !(threshold >= 0.0) || !(threshold < DBL_MAX) ||
          (int64_t)n_seg * ((n_hyp + 255) / 256) > 0x7fffffffLL;
+}
+
+// the workspace of twoview.hip and homography.hip: the segments' Hartley transforms, one 3 x 3 model and one count per
+// hypothesis
+struct model9_ws {
+  double* T;
+  double* hyp_model;
+  int* hyp_count;
+  int64_t bytes;
+};
+
+inline model9_ws model9_layout(void* workspace, int32_t n_seg, int32_t n_hyp) {
+  ws_carve c{(char*)workspace};
+  model9_ws w;
+  w.T = c.take<double>((int64_t)n_seg * 6);
+  w.hyp_model = c.take<double>((int64_t)n_seg * n_hyp * 9);
+  w.hyp_count = c.take<int>((int64_t)n_seg * n_hyp);
+  w.bytes = c.bytes();
+  return w;
 }
 
 // --------------------------------------------------------------------------------------------- block sums
@@ -87,6 +107,29 @@ __device__ __forceinline__ double block_total(const double (*s_red)[K], int k) {
 
 __device__ __forceinline__ bool finite4(float2 p, float2 q) {
   return isfinite(p.x) && isfinite(p.y) && isfinite(q.x) && isfinite(q.y);
+}
+
+// The sample of hypothesis `slot` of a two-view stage as px[k] = (x1, y1, x2, y2), float32 pixels.  False, with match 0
+// (M >= 1) in every px[k], for an idle lane or an index outside [0, M): checked before anything is indexed.  Not for
+// k_fund_hypotheses: 28 floats live across its elimination cost 32 VGPRs, so its solver is handed one match per row.
+template <int N>
+__device__ __forceinline__ bool load_sample(const int* __restrict__ samples, int64_t slot, bool active, int M, int64_t b,
+                                            const float2* __restrict__ pts1, const float2* __restrict__ pts2,
+                                            float (&px)[N][4]) {
+  bool ok = active;
+  int idx[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    idx[k] = active ? samples[slot * N + k] : 0;
+    ok = ok && idx[k] >= 0 && idx[k] < M;
+  }
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const int id = ok ? idx[k] : 0;
+    const float2 p = pts1[b + id], q = pts2[b + id];
+    px[k][0] = p.x; px[k][1] = p.y; px[k][2] = q.x; px[k][3] = q.y;
+  }
+  return ok;
 }
 
 // ------------------------------------------------------------------------------------------ normalisation
@@ -196,11 +239,35 @@ __device__ __forceinline__ void ransac_store_winner(int s, int st, int64_t b, in
   }
 }
 
+// what a refit leaves for segment s when its model is kept: the model's W doubles, its count, refined = 1
+template <int W>
+__device__ __forceinline__ void ransac_store_refit(int s, const double (&model)[W], int count, double* __restrict__ out,
+                                                   int* __restrict__ n_inliers, int* __restrict__ refined) {
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int e = 0; e < W; ++e) out[W * (int64_t)s + e] = model[e];
+    n_inliers[s] = count;
+    if (refined) refined[s] = 1;
+  }
+}
+
+// A refit replaces the winner only if its inlier count is not lower than `have`, the winner's.  count(mask) is the
+// stage's whole-segment count of the refitted model (segment_count behind it): first without a mask, and only a model
+// that is kept writes its mask.
+template <int W, typename Count>
+__device__ __forceinline__ void ransac_keep_refit(int s, int have, const double (&model)[W], Count count,
+                                                  double* __restrict__ out, uint8_t* __restrict__ mask,
+                                                  int* __restrict__ n_inliers, int* __restrict__ refined) {
+  const int c = count((uint8_t*)nullptr);
+  if (c < have) return;
+  (void)count(mask);
+  ransac_store_refit(s, model, c, out, n_inliers, refined);
+}
+
 // ------------------------------------------------------------------------------------------- 9 x 9 Jacobi
 // Cyclic Jacobi on the symmetric s_A [9][9] in LDS, run by a whole workgroup (lanes 0..8 rotate one row / column entry
 // each): on return the diagonal of s_A holds the eigenvalues and the columns of s_V, which must enter as the identity,
-// the eigenvectors.  Every thread reads the same values, so the control flow is uniform.  Shared by k_fund_refit and
-// k_ess_refit.
+// the eigenvectors.  Every thread reads the same values, so the control flow is uniform.
 __device__ __forceinline__ void jacobi9_lds(double (*s_A)[9], double (*s_V)[9]) {
   const int tid = threadIdx.x;
   for (int sweep = 0; sweep < 30; ++sweep) {
@@ -232,6 +299,30 @@ __device__ __forceinline__ void jacobi9_lds(double (*s_A)[9], double (*s_V)[9]) 
         __syncthreads();
       }
   }
+}
+
+// The refits of twoview.hip, essential.hip and homography.hip: acc holds a thread's share of the 45 unique entries
+// (upper triangle, row by row) of a 9 x 9 normal matrix.  Summed by the workgroup in a fixed order into s_A, then
+// jacobi9_lds: on return s_A's diagonal holds the eigenvalues and s_V's columns the eigenvectors, for every thread.
+__device__ __forceinline__ void normal9_eigen(double (&acc)[45], double (*s_red)[45], double (*s_A)[9], double (*s_V)[9]) {
+  const int tid = threadIdx.x;
+  block_sum_wide(acc, s_red);
+  if (tid < 81) {
+    const int u = tid / 9, v = tid % 9;
+    const int lo = u < v ? u : v, hi = u < v ? v : u;
+    const int k = lo * 9 - lo * (lo - 1) / 2 + (hi - lo);
+    s_A[u][v] = block_total(s_red, k);
+    s_V[u][v] = (u == v) ? 1.0 : 0.0;
+  }
+  __syncthreads();
+  jacobi9_lds(s_A, s_V);
+}
+
+// index of the smallest eigenvalue (ties: the lowest index)
+__device__ __forceinline__ int smallest_diagonal9(const double (*s_A)[9]) {
+  int kmin = 0;
+  for (int k = 1; k < 9; ++k) if (s_A[k][k] < s_A[kmin][kmin]) kmin = k;
+  return kmin;
 }
 
 // Kseg [n_seg][4] = (fx, fy, cx, cy) of segment s

@@ -9,10 +9,12 @@
 // own, stateless sample generator, so that the result is a function of (points, seed) alone and a NumPy reference
 // can follow the device hypothesis by hypothesis (tests/fundamental_reference.py).
 //
-// The sample kernel (k_ransac_samples<7, 7>), the Hartley normalisation (with homography.hip), the block sums, the
-// whole-segment count and the winner rule are shared with pnp.hip (ransac_kernels.h).  The generator's rule stands above draw_distinct<N> in ransac_common.h and is restated in
-// NumPy by the tests (tests/ransac_reference.py); its fallback after 256 draws is never reached in practice:
-// 7 * (6/7)^256 = 5e-17 at M = 7.
+// The 7-point solver is in fundamental_solve.h and the error rule in fundamental_rule.h; both compile for the host too.
+// The sample kernel (k_ransac_samples<7, 7>), the Hartley normalisation, the workspace layout, the block sums, the
+// whole-segment count, the winner rule and the refit's normal matrix and keep rule are shared with the other stages
+// (ransac_kernels.h), the scoring loop with essential.hip and homography.hip (epipolar_rule.h).  The generator's rule
+// stands above draw_distinct<N> in ransac_common.h and is restated in NumPy by the tests (tests/ransac_reference.py);
+// its fallback after 256 draws is never reached in practice: 7 * (6/7)^256 = 5e-17 at M = 7.
 //
 // All arithmetic in float64.  Points arrive as float32 pixels [n][2] with a device seg_ptr[n_seg+1] (int64), the
 // convention of sfm_epipolar_errors.  A match with a NaN or infinite coordinate is left out of the Hartley
@@ -20,44 +22,13 @@
 // model.  Sample indices are range-checked on the device before they index anything.
 #include "ransac_kernels.h"
 #include "epipolar_rule.h"
+#include "fundamental_solve.h"
 
 namespace {
 
-// --------------------------------------------------------------------------------------------- the models
-__device__ __forceinline__ double det3(double a0, double a1, double a2, double a3, double a4, double a5, double a6,
-                                       double a7, double a8) {
-  return a0 * (a4 * a8 - a5 * a7) - a1 * (a3 * a8 - a5 * a6) + a2 * (a3 * a7 - a4 * a6);
-}
-
-// F = T2^T Fn T1 with T = [sc 0 -sc*cx; 0 sc -sc*cy; 0 0 1]
-__device__ __forceinline__ void denormalise(const double (&fn)[9], const double* __restrict__ t, double (&f)[9]) {
-  const double s1 = t[0], tx1 = -t[0] * t[1], ty1 = -t[0] * t[2];
-  const double s2 = t[3], tx2 = -t[3] * t[4], ty2 = -t[3] * t[5];
-  double g[9];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    g[3 * r] = s1 * fn[3 * r];
-    g[3 * r + 1] = s1 * fn[3 * r + 1];
-    g[3 * r + 2] = fn[3 * r] * tx1 + fn[3 * r + 1] * ty1 + fn[3 * r + 2];
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    f[c] = s2 * g[c];
-    f[3 + c] = s2 * g[3 + c];
-    f[6 + c] = tx2 * g[c] + ty2 * g[3 + c] + g[6 + c];
-  }
-}
-
-// rotation k of the elimination acts on columns (i, j), j > i: k = i*8 - i*(i-1)/2 + (j - i - 1), 35 in all
-__device__ __forceinline__ constexpr int rot_index(int i, int j) { return i * 8 - i * (i - 1) / 2 + (j - i - 1); }
-
+// --------------------------------------------------------------------------------------------- hypotheses
 // One lane per (segment, hypothesis); a workgroup covers 256 hypotheses of ONE segment, so the scoring loop's points
 // are wave-uniform: fetched from global memory once per workgroup and chunk into LDS, read back as broadcasts.
-//
-// Null space of the 7 x 9 system without pivoting: Givens rotations of column pairs from the right, A G = [L 0] with
-// L lower triangular; the last two columns of G = G_1 ... G_35 span the null space.  Rows are formed one at a time
-// (row i: apply the rotations so far, then zero its entries i+1..8), so only the 35 (c, s) pairs are live, and every
-// array index is a compile-time constant after unrolling: nothing is indexed at run time, nothing goes to scratch.
 __global__ __launch_bounds__(256) void k_fund_hypotheses(const int64_t* __restrict__ seg_ptr, int64_t n,
                                                          const float2* __restrict__ pts1, const float2* __restrict__ pts2,
                                                          const int* __restrict__ samples, int H, int nblk, double thr2,
@@ -80,108 +51,28 @@ __global__ __launch_bounds__(256) void k_fund_hypotheses(const int64_t* __restri
   }
   const double* t = T + 6 * (int64_t)s;
   double Fc[3][9];
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-#pragma unroll
-    for (int e = 0; e < 9; ++e) Fc[k][e] = 0.0;
   {
-    bool ok = active;
+    bool in_range = active;
     int idx[7];
 #pragma unroll
     for (int k = 0; k < 7; ++k) {
       idx[k] = active ? samples[slot * 7 + k] : 0;
-      ok = ok && idx[k] >= 0 && idx[k] < M;
+      in_range = in_range && idx[k] >= 0 && idx[k] < M;
     }
-    double rc[35], rs[35];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      const int id = ok ? idx[i] : 0;
+    sevenpt::solve_matches([&](int i, bool ok, float (&m)[4]) {
+      const int id = (ok && in_range) ? idx[i] : 0;
       const float2 p = pts1[b + id], q = pts2[b + id];
-      const double xa = ((double)p.x - t[1]) * t[0], xb = ((double)p.y - t[2]) * t[0];
-      const double xc = ((double)q.x - t[4]) * t[3], xd = ((double)q.y - t[5]) * t[3];
-      double r[9] = {xc * xa, xc * xb, xc, xd * xa, xd * xb, xd, xa, xb, 1.0};
-#pragma unroll
-      for (int ii = 0; ii < i; ++ii)
-#pragma unroll
-        for (int j = ii + 1; j < 9; ++j) {
-          const double c = rc[rot_index(ii, j)], sn = rs[rot_index(ii, j)];
-          const double u = r[ii], v = r[j];
-          r[ii] = c * u + sn * v; r[j] = c * v - sn * u;
-        }
-#pragma unroll
-      for (int j = i + 1; j < 9; ++j) {
-        const double u = r[i], v = r[j];
-        const double hh = sqrt(u * u + v * v);
-        const bool nz = hh > 0.0;                          // NaN: (1, 0), and the NaN travels on in r
-        const double c = nz ? u / hh : 1.0, sn = nz ? v / hh : 0.0;
-        rc[rot_index(i, j)] = c; rs[rot_index(i, j)] = sn;
-        r[i] = nz ? hh : u; r[j] = nz ? 0.0 : v;
-      }
-      ok = ok && (r[i] == r[i]);
-    }
-    // null vectors G e7, G e8: the rotations applied in reverse order to the unit vectors
-    double f1[9], f2[9];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) { f1[e] = (e == 7) ? 1.0 : 0.0; f2[e] = (e == 8) ? 1.0 : 0.0; }
-#pragma unroll
-    for (int i = 6; i >= 0; --i)
-#pragma unroll
-      for (int j = 8; j > i; --j) {
-        const double c = rc[rot_index(i, j)], sn = rs[rot_index(i, j)];
-        double u = f1[i], v = f1[j];
-        f1[i] = c * u - sn * v; f1[j] = sn * u + c * v;
-        u = f2[i]; v = f2[j];
-        f2[i] = c * u - sn * v; f2[j] = sn * u + c * v;
-      }
-    // det(l f1 + (1 - l) f2) is a cubic in l: its values at l = -1, 0, 1, 2 give the coefficients
-    double pv[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const double l = (double)(k - 1);
-      double m[9];
-#pragma unroll
-      for (int e = 0; e < 9; ++e) m[e] = l * f1[e] + (1.0 - l) * f2[e];
-      pv[k] = det3(m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8]);
-    }
-    const double c0 = pv[1];
-    const double c3 = (pv[3] - 3.0 * pv[2] + 3.0 * pv[1] - pv[0]) / 6.0;
-    const double c2 = 0.5 * (pv[2] + pv[0]) - pv[1];
-    const double c1 = pv[2] - c0 - c2 - c3;
-    const double cmax = fmax(fmax(fabs(c0), fabs(c1)), fmax(fabs(c2), fabs(c3)));
-    ok = ok && isfinite(cmax) && (c0 == c0) && (c1 == c1) && (c2 == c2) && (c3 == c3) && !(fabs(c3) < 1e-14 * cmax);
-    // monic x^3 + A x^2 + B x + C: closed form (trigonometric / Cardano), then two Newton steps on the monic cubic
-    const double A = c2 / c3, B = c1 / c3, Cc = c0 / c3;
-    double root[3];
-    int nr = cubic_roots_monic(A, B, Cc, root);
-    if (!ok) nr = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const double x = cubic_newton2(root[k], A, B, Cc);
-      double fn[9], f[9];
-#pragma unroll
-      for (int e = 0; e < 9; ++e) fn[e] = x * f1[e] + (1.0 - x) * f2[e];
-      denormalise(fn, t, f);
-      bool good = k < nr;
-#pragma unroll
-      for (int e = 0; e < 9; ++e) good = good && isfinite(f[e]);
-#pragma unroll
-      for (int e = 0; e < 9; ++e) Fc[k][e] = good ? f[e] : 0.0;
-    }
+      m[0] = p.x; m[1] = p.y; m[2] = q.x; m[3] = q.y;
+      return in_range;
+    }, t, Fc);
   }
   // scoring: every lane walks all points of the segment with its (up to) three candidates in registers
   int cnt0 = 0, cnt1 = 0, cnt2 = 0;
-  for (int base = 0; base < M; base += FUND_CHUNK) {
-    const int cnt = (M - base < FUND_CHUNK) ? (M - base) : FUND_CHUNK;
-    __syncthreads();
-    stage_points(s_pt, pts1, pts2, b + base, cnt, 256);
-    __syncthreads();
-    for (int i = 0; i < cnt; ++i) {
-      const double2 p = s_pt[2 * i], q = s_pt[2 * i + 1];
-      cnt0 += fund_inlier(Fc[0], p.x, p.y, q.x, q.y, thr2) ? 1 : 0;
-      cnt1 += fund_inlier(Fc[1], p.x, p.y, q.x, q.y, thr2) ? 1 : 0;
-      cnt2 += fund_inlier(Fc[2], p.x, p.y, q.x, q.y, thr2) ? 1 : 0;
-    }
-  }
+  for_each_staged_point(s_pt, pts1, pts2, b, M, [&](double2 p, double2 q) {
+    cnt0 += fund_inlier(Fc[0], p.x, p.y, q.x, q.y, thr2) ? 1 : 0;
+    cnt1 += fund_inlier(Fc[1], p.x, p.y, q.x, q.y, thr2) ? 1 : 0;
+    cnt2 += fund_inlier(Fc[2], p.x, p.y, q.x, q.y, thr2) ? 1 : 0;
+  });
   if (!active) return;
   int best = cnt0;
   const bool use1 = cnt1 > best;
@@ -194,17 +85,6 @@ __global__ __launch_bounds__(256) void k_fund_hypotheses(const int64_t* __restri
 }
 
 // ---------------------------------------------------------------------------------------------- selection
-// inliers of f over the whole segment (staged through LDS like the scoring loop is not needed here: every thread takes
-// its own points); writes the mask when `mask` is not null
-__device__ __forceinline__ int fund_count(const double (&f)[9], const float2* __restrict__ pts1,
-                                          const float2* __restrict__ pts2, int64_t b, int M, double thr2,
-                                          uint8_t* __restrict__ mask) {
-  return segment_count(b, M, mask, [&](int64_t i) {
-    const float2 p = pts1[i], q = pts2[i];
-    return finite4(p, q) && fund_inlier(f, (double)p.x, (double)p.y, (double)q.x, (double)q.y, thr2);
-  });
-}
-
 // winner per segment (ransac_winner): its F scaled to F[2][2] = 1, its mask and its count
 __global__ __launch_bounds__(256) void k_fund_select(const int64_t* __restrict__ seg_ptr, int64_t n,
                                                      const float2* __restrict__ pts1, const float2* __restrict__ pts2,
@@ -264,18 +144,8 @@ __global__ __launch_bounds__(256) void k_fund_refit(const int64_t* __restrict__ 
 #pragma unroll
       for (int v = u; v < 9; ++v) acc[k++] += r[u] * r[v];
   }
-  block_sum_wide(acc, s_red);
-  if (tid < 81) {
-    const int u = tid / 9, v = tid % 9;
-    const int lo = u < v ? u : v, hi = u < v ? v : u;
-    const int k = lo * 9 - lo * (lo - 1) / 2 + (hi - lo);
-    s_A[u][v] = block_total(s_red, k);
-    s_V[u][v] = (u == v) ? 1.0 : 0.0;
-  }
-  __syncthreads();
-  jacobi9_lds(s_A, s_V);
-  int kmin = 0;
-  for (int k = 1; k < 9; ++k) if (s_A[k][k] < s_A[kmin][kmin]) kmin = k;
+  normal9_eigen(acc, s_red, s_A, s_V);
+  const int kmin = smallest_diagonal9(s_A);
   double U[3][3], V[3][3];
 #pragma unroll
   for (int r = 0; r < 3; ++r)
@@ -329,38 +199,14 @@ __global__ __launch_bounds__(256) void k_fund_refit(const int64_t* __restrict__ 
     }
   }
   double f[9];
-  denormalise(fn, t, f);
+  sevenpt::denormalise(fn, t, f);
   bool good = true;
 #pragma unroll
   for (int e = 0; e < 9; ++e) good = good && isfinite(f[e]);
   if (!good) return;                                     // uniform: every thread computed the same f
   scale_last_to_one(f);
-  const int count = fund_count(f, pts1, pts2, b, M, thr2, nullptr);
-  if (count < have) return;
-  (void)fund_count(f, pts1, pts2, b, M, thr2, mask);
-  if (tid == 0) {
-#pragma unroll
-    for (int e = 0; e < 9; ++e) F[9 * (int64_t)s + e] = f[e];
-    n_inliers[s] = count;
-    if (refined) refined[s] = 1;
-  }
-}
-
-struct fund_ws {
-  double* T;
-  double* hyp_F;
-  int* hyp_count;
-  int64_t bytes;
-};
-
-fund_ws fund_layout(void* workspace, int32_t n_seg, int32_t n_hyp) {
-  ws_carve c{(char*)workspace};
-  fund_ws w;
-  w.T = c.take<double>((int64_t)n_seg * 6);
-  w.hyp_F = c.take<double>((int64_t)n_seg * n_hyp * 9);
-  w.hyp_count = c.take<int>((int64_t)n_seg * n_hyp);
-  w.bytes = c.bytes();
-  return w;
+  ransac_keep_refit(s, have, f, [&](uint8_t* m) { return fund_count(f, pts1, pts2, b, M, thr2, m); }, F, mask, n_inliers,
+                    refined);
 }
 
 }  // namespace
@@ -368,7 +214,7 @@ fund_ws fund_layout(void* workspace, int32_t n_seg, int32_t n_hyp) {
 // ================================================================================================ C ABI
 extern "C" int sfm_fund_workspace_bytes(int64_t n_points, int32_t n_seg, int32_t n_hyp, int64_t* bytes_host) {
   if (!bytes_host || n_points < 0 || n_seg < 0 || n_hyp < 1) return SFM_ERR_ARG;
-  *bytes_host = fund_layout(nullptr, n_seg, n_hyp).bytes;
+  *bytes_host = model9_layout(nullptr, n_seg, n_hyp).bytes;
   return SFM_OK;
 }
 
@@ -386,7 +232,7 @@ extern "C" int sfm_fund_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_s
   if (n == 0 || n_seg == 0) return SFM_OK;
   if (!seg_ptr || !pts1 || !pts2 || !samples || !F || !mask || !n_inliers || !status || !workspace)
     return sfm_fail(h, SFM_ERR_ARG, "sfm_fund_ransac", "null pointer");
-  const fund_ws w = fund_layout(workspace, n_seg, n_hyp);
+  const model9_ws w = model9_layout(workspace, n_seg, n_hyp);
   if (workspace_bytes < w.bytes) return sfm_fail(h, SFM_ERR_WORKSPACE, "sfm_fund_ransac", "workspace too small");
   int* counts = hyp_count ? hyp_count : w.hyp_count;
   const double thr2 = threshold * threshold;
@@ -397,10 +243,10 @@ extern "C" int sfm_fund_ransac(sfm_handle h, const int64_t* seg_ptr, int32_t n_s
   hipLaunchKernelGGL(k_hartley_normalise<256>, dim3(n_seg), dim3(256), 0, h->stream, seg_ptr, n, p1, p2, w.T);
   sfm_prof_begin(h, SFM_PROF_FUND_HYP);
   hipLaunchKernelGGL(k_fund_hypotheses, dim3((unsigned)n_seg * nblk), dim3(256), 0, h->stream, seg_ptr, n, p1, p2,
-                     samples, n_hyp, nblk, thr2, (const double*)w.T, counts, w.hyp_F);
+                     samples, n_hyp, nblk, thr2, (const double*)w.T, counts, w.hyp_model);
   sfm_prof_end(h, SFM_PROF_FUND_HYP);
   hipLaunchKernelGGL(k_fund_select, dim3(n_seg), dim3(256), 0, h->stream, seg_ptr, n, p1, p2, n_hyp, thr2,
-                     (const int*)counts, (const double*)w.hyp_F, F, mask, n_inliers, status, refined);
+                     (const int*)counts, (const double*)w.hyp_model, F, mask, n_inliers, status, refined);
   if (refine)
     hipLaunchKernelGGL(k_fund_refit, dim3(n_seg), dim3(256), 0, h->stream, seg_ptr, n, p1, p2, thr2,
                        (const double*)w.T, F, mask, n_inliers, (const int*)status, refined);

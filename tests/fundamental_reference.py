@@ -7,6 +7,8 @@ through four determinant evaluations and np.roots, where the kernel rotates colu
     row of the system for x1=(a,b), x2=(c,d):  [c*a, c*b, c, d*a, d*b, d, a, b, 1]
     err(F, x1, x2) = max( s^2/((F x1)_0^2 + (F x1)_1^2), s^2/((F^T x2)_0^2 + (F^T x2)_1^2) ),  s = x2^T F x1
 """
+import functools
+
 import numpy as np
 
 import ransac_reference
@@ -186,3 +188,16 @@ def synth_pair(rng, M, outlier_share=0.0, noise=0.5, float32=True, yaw=0.25, t=(
     if float32:
         x1, x2 = x1.astype(np.float32), x2.astype(np.float32)
     return x1, x2, true_fundamental(R, t)
+
+
+CASES = [(7, 0.0), (8, 0.0), (40, 0.3), (300, 0.3), (300, 0.6), (2000, 0.5)]       # (M, outlier share), ONE batch
+
+
+@functools.lru_cache(maxsize=None)
+def synth_batch():
+    """(pts1 list, pts2 list, true F list) of CASES - computed once, never modified."""
+    out = []
+    for M, share in CASES:
+        rng = np.random.default_rng(1000 * M + int(100 * share))
+        out.append(synth_pair(rng, M, share, noise=0.5))
+    return [o[0] for o in out], [o[1] for o in out], [o[2] for o in out]

@@ -12,17 +12,8 @@ import fundamental_reference as fr
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CASES = [(7, 0.0), (8, 0.0), (40, 0.3), (300, 0.3), (300, 0.6), (2000, 0.5)]       # (M, outlier share), ONE batch
+CASES, synth_batch = fr.CASES, fr.synth_batch
 THR = 3.0
-
-
-@functools.lru_cache(maxsize=None)
-def synth_batch():
-    out = []
-    for M, share in CASES:
-        rng = np.random.default_rng(1000 * M + int(100 * share))
-        out.append(fr.synth_pair(rng, M, share, noise=0.5))
-    return [o[0] for o in out], [o[1] for o in out], [o[2] for o in out]
 
 
 @functools.lru_cache(maxsize=None)

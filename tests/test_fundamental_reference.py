@@ -1,21 +1,51 @@
 """CPU tests of the fundamental-matrix RANSAC's NumPy reference (tests/fundamental_reference.py), of the restated
-sample generator, of the reference on the 148 pairs the reference project ships, and of the Python glue of
-sfm_amd.twoview / ImageMatcher.process_pairs with the library calls stubbed.  No GPU."""
+sample generator, of the reference on the 148 pairs the reference project ships, of the kernel's solver and error rule
+(sfm_amd/csrc/fundamental_solve.h, fundamental_rule.h) compiled for the host against the reference, hypothesis by
+hypothesis, and of the Python glue of sfm_amd.twoview / ImageMatcher.process_pairs with the library calls stubbed.
+No GPU."""
+import functools
 import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
 
 import fundamental_reference as fr
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+THR = 3.0
 
 
+@functools.lru_cache(maxsize=None)
 def bunny_pairs():
     g = np.load(os.path.join(GOLDEN, "bunny_pairs.npz"), allow_pickle=False)
     off = g["offsets"]
     return [(g["pts1"][off[s]:off[s + 1]], g["pts2"][off[s]:off[s + 1]], g["F"][s], g["mask"][off[s]:off[s + 1]])
             for s in range(len(g["F"]))]
+
+
+@functools.lru_cache(maxsize=None)
+def bunny_replay():
+    """[(samples, reference result)] of the 148 shipped pairs at seed 0, 1,024 hypotheses, no refit - computed once,
+    never modified."""
+    out = []
+    for s, (p1, p2, _, _) in enumerate(bunny_pairs()):
+        smp = fr.draw_samples(0, s, len(p1), 1024)
+        out.append((smp, fr.ransac(p1, p2, smp, THR)))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def synthetic_replay():
+    """[(samples, reference result)] of fr.CASES at seed 1, 512 hypotheses - computed once, never modified."""
+    p1s, p2s, _ = fr.synth_batch()
+    out = []
+    for s, (M, _) in enumerate(fr.CASES):
+        smp = fr.draw_samples(1, s, M, 512)
+        out.append((smp, fr.ransac(p1s[s], p2s[s], smp, THR)))
+    return out
 
 
 # ---------------------------------------------------------------------------------------- noise-free scenes
@@ -79,10 +109,9 @@ def test_shipped_pairs_winner_is_as_good_as_the_shipped_model():
     many inliers under the reference's verification rule (symmetric distance < 3, the shipped mask) as the shipped F.
     Measured: minimum ratio 1.000, median 1.030 (the bound is set by the issue's three-seed survey, minimum 0.953)."""
     ratios = []
-    for s, (p1, p2, Fs, mk) in enumerate(bunny_pairs()):
+    for s, ((p1, p2, Fs, mk), (_, r)) in enumerate(zip(bunny_pairs(), bunny_replay())):
         p1 = p1.astype(np.float64)
         p2 = p2.astype(np.float64)
-        r = fr.ransac(p1, p2, fr.draw_samples(0, s, len(p1), 1024), threshold=3.0)
         assert r["status"] == 0, s
         mine = int((fr.sym_err(r["F"], p1, p2) < 3.0).sum())
         ship = int((fr.sym_err(Fs, p1, p2) < 3.0).sum())
@@ -104,6 +133,112 @@ def test_refit_keeps_or_improves_the_count():
     assert b["n_inliers"] >= a["n_inliers"] and b["n_inliers"] == b["mask"].sum()
     sv = np.linalg.svd(b["F"], compute_uv=False)
     assert sv[2] < 1e-12 * sv[0] and b["F"][2, 2] == 1.0
+
+
+# ------------------------------------------------------- the kernel's solver and rule built for the host
+def build_native(tmp, extra=()):
+    exe = os.path.join(tmp, "fundamental_solve_check" + ("_san" if extra else ""))
+    subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", *extra, "-I" + os.path.join(ROOT, "sfm_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "native", "fundamental_solve_check.cpp"), "-o", exe], check=True)
+    return exe
+
+
+def transforms(p1, p2):
+    """The segment's {sc1, cx1, cy1, sc2, cx2, cy2} as the reference forms them: over the finite matches."""
+    a, b = np.asarray(p1, np.float64).reshape(-1, 2), np.asarray(p2, np.float64).reshape(-1, 2)
+    fin = np.isfinite(a).all(1) & np.isfinite(b).all(1)
+    T1, T2 = (fr.hartley(a[fin]), fr.hartley(b[fin])) if fin.any() else (np.eye(3), np.eye(3))
+    return [T1[0, 0], -T1[0, 2] / T1[0, 0], -T1[1, 2] / T1[0, 0], T2[0, 0], -T2[0, 2] / T2[0, 0], -T2[1, 2] / T2[0, 0]]
+
+
+def run_native(exe, p1, p2, smp, t=None):
+    """(model [H,3] bool, F [H,3,3,3], count [H,3]) of the host build for samples smp of one pair, under transforms t
+    (the reference's for this pair when None)."""
+    a = np.asarray(p1, np.float32).astype(np.float64).reshape(-1, 2)
+    b = np.asarray(p2, np.float32).astype(np.float64).reshape(-1, 2)
+    t = transforms(a, b) if t is None else t
+    np.concatenate([[len(a), len(smp), THR], t, np.c_[a, b].ravel(), np.asarray(smp, np.float64).ravel()]).tofile(exe + ".in")
+    subprocess.run([exe, exe + ".in", exe + ".out"], check=True)
+    o = np.fromfile(exe + ".out").reshape(-1, 33)
+    return o[:, :3] != 0, o[:, 3:30].reshape(-1, 3, 3, 3), o[:, 30:].astype(int)
+
+
+def check_rules(exe, p1, p2):
+    """The rule cases on one pair of M >= 7 matches (copies are modified, never p1 / p2)."""
+    M = len(p1)
+    plain = np.arange(7)[None]
+    model, Fs, cnt = run_native(exe, p1, p2, plain)
+    assert model[0].any() and cnt[0].max() >= 7                       # a plain sample fits at least its own seven
+    # a NaN and an infinity in a sampled match void all three candidates.  Match 0 with a bad y is the case the
+    # pivot test alone does not see: row 0 meets no earlier rotation, its pivot xc * xa stays finite, and a rotation
+    # that treated a NaN length as zero, (c, s) = (1, 0), would drop the NaN that stands in the row's other entries.
+    for row, img, col, bad in [(0, 0, 1, np.nan), (0, 1, 1, np.nan), (0, 1, 1, np.inf), (1, 0, 0, np.nan), (3, 1, 1, np.inf),
+                               (5, 0, 1, -np.inf), (6, 1, 0, np.nan), (6, 1, 1, np.inf)]:
+        q = [p1.copy(), p2.copy()]
+        q[img][row, col] = bad
+        model, Fs, cnt = run_native(exe, q[0], q[1], plain)
+        assert not model.any() and (cnt == 0).all(), (M, row, img, col, bad)
+    # an index of -1 and an index of M void the sample and read nothing
+    model, Fs, cnt = run_native(exe, p1, p2, np.array([[0, 1, 2, 3, 4, 5, M], [0, 1, 2, -1, 4, 5, 6]]))
+    assert not model.any() and (cnt == 0).all(), M
+    # a non-finite match that is not sampled is never counted: the last match made non-finite, against the same
+    # samples on the pair without it, under the same transforms (they leave non-finite matches out).  At M = 7 a sample
+    # of the other six repeats one of them - neither the kernel nor this program asks for distinct indices.
+    smp = fr.draw_samples(2, 0, M - 1, 64) if M > 7 else np.array([[0, 1, 2, 3, 4, 5, 5], [3, 0, 1, 2, 3, 4, 5]])
+    for bad in (np.nan, np.inf):
+        q1, q2 = p1.copy(), p2.copy()
+        q1[M - 1, 1] = bad
+        t = transforms(q1, q2)
+        with_it, F_with, cnt_with = run_native(exe, q1, q2, smp, t)
+        without, F_without, cnt_without = run_native(exe, q1[:M - 1], q2[:M - 1], smp, t)
+        assert np.array_equal(cnt_with, cnt_without) and np.array_equal(F_with, F_without), M
+        assert (cnt_with <= M - 1).all() and (M == 7 or cnt_with.max() >= 7)
+
+
+def check_native(exe):
+    p1s, p2s, _ = fr.synth_batch()
+    for s, ((M, share), (smp, ref)) in enumerate(zip(fr.CASES, synthetic_replay())):
+        model, Fs, cnt = run_native(exe, p1s[s], p2s[s], smp)
+        hyp = cnt.max(1)
+        agree = float(np.mean(hyp == ref["hyp_count"]))
+        cand = float(np.mean(np.sort(cnt, 1) == np.sort(ref["cand_count"], 1)))     # the slot order is the basis's
+        print(f"segment {s} (M {M}, outliers {share}): hyp_count equal on {agree:.4%} of 512, per candidate {cand:.4%}, "
+              f"winner {hyp.max()} / reference {ref['n_inliers']}")
+        assert agree >= 0.99, s
+        assert hyp.max() == ref["n_inliers"], s
+        assert (cnt[~model] == 0).all(), s            # the program's model flag is "F != 0": the empty slot never counts
+    check_rules(exe, p1s[2], p2s[2])          # M = 40
+    check_rules(exe, p1s[0], p2s[0])          # M = 7
+    # the shipped pairs: printed, nothing asserted.  The reference takes its null space from np.linalg.svd and this
+    # build rotates columns (with the fmas the solver writes out, nothing else contracted); on the ill-conditioned
+    # samples of real matches the two round apart.
+    agree, winners = [], 0
+    for (p1, p2, _, _), (smp, ref) in zip(bunny_pairs(), bunny_replay()):
+        _, _, cnt = run_native(exe, p1, p2, smp)
+        agree.append(float(np.mean(cnt.max(1) == ref["hyp_count"])))
+        winners += int(cnt.max() == ref["hyp_count"].max())
+    print("shipped pairs: per-hypothesis agreement min %.4f median %.4f max %.4f; winner count equal on %d of %d"
+          % (min(agree), float(np.median(agree)), max(agree), winners, len(agree)))
+
+
+def test_kernel_solver_and_rule_on_the_host_equal_the_reference(tmp_path):
+    """fundamental_solve.h + fundamental_rule.h compiled by g++ -ffp-contract=off (the fmas the solver writes out stay
+    fmas): hyp_count equals the reference's on at
+    least 99 % of the 512 hypotheses of every case of the GPU test's batch - the cap the GPU replay test sets for the
+    kernels, here for their solver and rule alone - and the winner's count equals the reference's; then the rule cases
+    at M = 40 and M = 7.  Measured: 100 % in all six cases, per candidate too.  On the 148 shipped pairs the agreement is
+    printed only: between 0.73 and 1.00 per pair (median 0.95), one winner count of 148 differs."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    check_native(build_native(str(tmp_path)))
+
+
+def test_kernel_solver_and_rule_on_the_host_under_sanitizers(tmp_path):
+    """The same program built with -fsanitize=address,undefined and run as the stand-alone program it is: every index of
+    the 35 rotations and of the rows stays inside its array, and nothing undefined happens on the way."""
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    check_native(build_native(str(tmp_path), ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g")))
 
 
 # ----------------------------------------------------------------------------- Python glue, library stubbed

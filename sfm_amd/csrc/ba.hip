@@ -1,5 +1,7 @@
 // Bundle-adjustment stages for gfx950 (MI355X): residual + analytic Jacobian + Huber row
-// scaling, block accumulation, damped Schur-complement solve.  fp64 throughout.
+// scaling, block accumulation, damped Schur-complement solve.  fp64 throughout.  Here: the workspace layout, the Schur stage, shared
+// vector kernels, the scalar read-back; ba_model.hip: the camera model (linearise, step, cost); ba_camera_cg.hip: the formed camera
+// system; ba_pcg.hip: the implicit-Schur PCG; ba_device.h: device helpers; ba_stages.h: what one unit calls in another.
 //
 // What is computed (and for which reference lines) is documented in include/sfm_amd.h and
 // DESIGN.md; the arithmetic mirrors oracle/ba_oracle.py statement by statement where the
@@ -19,35 +21,15 @@
 //   S | r  [(n+1)][n] reduced camera system with its right-hand side as a bordered row
 // Observations of one point (a track) are contiguous; cameras are reached through cam_obs.
 #include "ba_internal.h"
-#include <cstdlib>
-#include <type_traits>
-#include <cmath>
+#include "ba_device.h"
 #include <atomic>
-#include <chrono>
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
-// a ticket into a pinned host word, BEHIND everything this thread has written before (the host spins on the word); seq 0: none
-__device__ __forceinline__ void publish_word(double* word, double seq) {
-  if (seq > 0.0) {
-    __threadfence_system();
-    *(volatile double*)word = seq;
-  }
-}
-// the ticket of a finished stage into the problem's pinned page, behind the scalars (sfm_ba_read_scalars)
-__device__ __forceinline__ void publish_ticket(double* hsc, double seq) { publish_word(hsc + SFM_HSC_SEQ, seq); }
-
-#define EPS_D 2.220446049250313e-16
-#define SQRT_EPS_D 1.4901161193847656e-08
-#define CAMPRE 16   // r[3] t[3] fx fy cx cy  a b a1 b1 (Rodrigues coefficients)  |r|^2 pad
-
+// ------------------------------------------------------------------------------------ layout
 // Stride of a G block in doubles.  D = 10: 32 = 256 bytes, so that a block is exactly two whole 128-byte lines - the Schur
 // gather is bound by the lines it pulls through the fabric, and a 240-byte block at 16-byte alignment straddles 2.75 on
 // average: k_schur_items 357 -> 305 us, fabric traffic 2.34 -> 1.94 GB per launch (round 3, profiles/).  D = 6: 18 doubles =
 // 144 bytes straddle exactly two lines at any 16-byte offset already.  The strides DISPATCH_DT instantiates (GG) must match.
 static int64_t g_stride(int64_t D) { return D == 10 ? 32 : 3 * D; }
-
-// ------------------------------------------------------------------------------------ layout
 Lay ba_layout(int64_t C, int64_t P, int64_t N, int64_t D, int64_t n_items, int64_t n_cchunks, int precision) {
   Lay L;
   int64_t o = 0, n = C * D;
@@ -121,482 +103,6 @@ extern "C" int sfm_ba_get_layout(sfm_ba_problem p, sfm_ba_layout* out) {
   out->G_off = L.G * 8;
   out->cg_Ap_off = L.cg_Ap * 8; out->cg_M_off = L.cg_M * 8;
   return SFM_OK;
-}
-
-// ------------------------------------------------------------------------------------ helpers
-// The same sums without a trip through LDS per step (__shfl_* is ds_bpermute: ~100 cycles each, six in a row per wave_sum - in
-// the persistent CG, one wave per SIMD, that latency is the iteration): quad permutes and row mirrors (DPP) inside a row of 16
-// lanes, v_permlane16_swap / v_permlane32_swap across rows.  Every step adds a value and its partner's in the same order on both
-// sides, so ALL lanes end with bit-identical totals.  Measured (cfg4, 20 outer iterations after 5): camera-solve slots 155 + 123
-// -> 140 + 104 us per damped solve, 310 -> 322 LM-iterations/s.
-template <int CTRL> __device__ __forceinline__ double dpp_f64(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-// {a, b} -> (swap16: rows 1, 3 of a <-> rows 0, 2 of b; swap32: upper half of a <-> lower half of b), then a + b: with a = b = v
-// the sum of v over the two rows / halves in every lane, with two different registers one step of a halving exchange (the
-// even rows / lower half end with a's sum, the odd rows / upper half with b's)
-__device__ __forceinline__ double swap16_add(double a, double b) {
-  const auto rlo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
-  const auto rhi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-  return __hiloint2double((int)rhi[0], (int)rlo[0]) + __hiloint2double((int)rhi[1], (int)rlo[1]);
-}
-__device__ __forceinline__ double swap32_add(double a, double b) {
-  const auto rlo = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(a), (unsigned)__double2loint(b), false, false);
-  const auto rhi = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(a), (unsigned)__double2hiint(b), false, false);
-  return __hiloint2double((int)rhi[0], (int)rlo[0]) + __hiloint2double((int)rhi[1], (int)rlo[1]);
-}
-__device__ __forceinline__ double wave_sum_all(double v) {
-  v += dpp_f64<0xB1>(v);          // quad_perm [1,0,3,2]
-  v += dpp_f64<0x4E>(v);          // quad_perm [2,3,0,1]
-  v += dpp_f64<0x141>(v);         // row_half_mirror
-  v += dpp_f64<0x140>(v);         // row_mirror: every lane of a row holds the row's sum
-  v = swap16_add(v, v);           // rows 0 + 1, rows 2 + 3
-  return swap32_add(v, v);        // both halves
-}
-// (every lane gets the total; the callers that say "valid in lane 0" predate the DPP form)
-__device__ __forceinline__ double wave_sum(double v) { return wave_sum_all(v); }
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
-  return v;
-}
-// v[q] = this lane's part of the sum of row q (8 rows); returns, in every lane, the sum over the 64 lanes of row
-// 4 (lane >> 5) + 2 ((lane >> 4) & 1) + ((lane >> 3) & 1): the halves of the wave, then neighbouring rows of 16 lanes, then the two
-// halves of a row of 16 each pass HALF of what they hold to their partner and keep the other half (4 + 2 + 1 additions), the
-// last eight lanes are summed by mirrors / quad permutes (3 additions).  Fixed order: the same bits on every workgroup.
-__device__ __forceinline__ double lane_rows8_sum(double (&v)[8], int lane) {
-  double u[4], x[2];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) u[k] = swap32_add(v[k], v[k + 4]);        // upper half keeps rows + 4
-#pragma unroll
-  for (int k = 0; k < 2; ++k) x[k] = swap16_add(u[k], u[k + 2]);        // odd rows of 16 lanes keep rows + 2
-  const bool hi = (lane & 8) != 0;                                      // lanes 8..15 of a row keep rows + 1
-  const double send = hi ? x[0] : x[1], keep = hi ? x[1] : x[0];
-  double t = keep + dpp_f64<0x140>(send);                               // row_mirror: lane i <-> lane 15 - i
-  t += dpp_f64<0x141>(t);                                               // row_half_mirror: lane i <-> lane 7 - i of its eight
-  t += dpp_f64<0xB1>(t);                                                // the four lanes of a quad
-  t += dpp_f64<0x4E>(t);
-  return t;
-}
-// Sum over a 256-thread block, fixed order, in every thread.  s: >= 4 doubles of LDS.
-__device__ __forceinline__ double block_sum256_fast(double v, double* s) {
-  v = wave_sum_all(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (s[0] + s[1]) + (s[2] + s[3]);
-}
-// Sum over a 256-thread block, fixed order; result valid in thread 0.  s: >= 4 doubles of LDS.
-__device__ __forceinline__ double block_sum256(double v, double* s) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return s[0] + s[1] + s[2] + s[3];
-}
-__device__ __forceinline__ double block_max256(double v, double* s) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmax(fmax(s[0], s[1]), fmax(s[2], s[3]));
-}
-
-// Huber, per scalar residual, exactly as scipy least_squares.py:169-178 + common.py:720-731:
-// returns rho0; scale = sqrt(max(rho1 + 2 rho2 f^2, EPS)); ft = f * rho1 / scale.
-__device__ __forceinline__ double huber_row(double f, double& scale, double& ft) {
-  double z = f * f;
-  if (z <= 1.0) { scale = 1.0; ft = f; return z; }
-  double sz = sqrt(z);
-  double rho1 = 1.0 / sz;
-  // rho1 + 2*rho2*z with rho2 = -0.5 z^-1.5 is 0 up to rounding -> clamped to EPS
-  scale = SQRT_EPS_D;
-  ft = f * rho1 / SQRT_EPS_D;
-  return 2.0 * sz - 1.0;
-}
-__device__ __forceinline__ double huber_rho0(double f) {
-  double z = f * f;
-  return z <= 1.0 ? z : 2.0 * sqrt(z) - 1.0;
-}
-
-__device__ __forceinline__ void mat3_mul(const double* A, const double* Bm, double* Cm) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      Cm[i * 3 + j] = A[i * 3] * Bm[j] + A[i * 3 + 1] * Bm[3 + j] + A[i * 3 + 2] * Bm[6 + j];
-}
-
-// ------------------------------------------------------------------------------------ per-camera precompute
-// Rodrigues coefficients of R = I + a[r]x + b[r]x^2 and of dR/dr_i (same series / closed-form split as the
-// oracle's _rod_coeffs).  Only 14 doubles per camera are kept; R X and (dR/dr_i) X are rebuilt per observation
-// from cross products (cam_apply below) - gathering a 3x3 R and three 3x3 dR per observation cost more L1/TA
-// traffic than the kernel's whole HBM stream.
-template <int D>
-__global__ void k_campre(const double* __restrict__ cams, int C, double fx0, double fy0, double cx0,
-                         double cy0, double* __restrict__ out) {
-  int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const double* p = cams + (size_t)c * D;
-  const double th2 = p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
-  double a, b, a1, b1;
-  if (th2 < 1e-4) {
-    double z = th2;
-    a = 1.0 - z / 6.0 + z * z / 120.0;
-    b = 0.5 - z / 24.0 + z * z / 720.0;
-    a1 = -1.0 / 3.0 + z / 30.0 - z * z / 840.0;
-    b1 = -1.0 / 12.0 + z / 180.0 - z * z / 6720.0;
-  } else {
-    double t = sqrt(th2), s, co;
-    sincos(t, &s, &co);
-    a = s / t;
-    b = (1.0 - co) / th2;
-    a1 = (t * co - s) / (th2 * t);
-    b1 = (t * s - 2.0 * (1.0 - co)) / (th2 * th2);
-  }
-  double* o = out + (size_t)c * CAMPRE;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) o[i] = p[i];
-  if (D == 10) { o[6] = p[6]; o[7] = p[7]; o[8] = p[8]; o[9] = p[9]; }
-  else { o[6] = fx0; o[7] = fy0; o[8] = cx0; o[9] = cy0; }
-  o[10] = a; o[11] = b; o[12] = a1; o[13] = b1; o[14] = th2; o[15] = 0.0;
-}
-
-// Y = R X + t  with  R X = X + a (r x X) + b (r x (r x X))
-__device__ __forceinline__ void cam_project(const double* __restrict__ cp, double X0, double X1, double X2,
-                                            double& Y0, double& Y1, double& Y2) {
-  const double r0 = cp[0], r1 = cp[1], r2 = cp[2], a = cp[10], b = cp[11];
-  const double c0 = r1 * X2 - r2 * X1, c1 = r2 * X0 - r0 * X2, c2 = r0 * X1 - r1 * X0;       // r x X
-  const double e0 = r1 * c2 - r2 * c1, e1 = r2 * c0 - r0 * c2, e2 = r0 * c1 - r1 * c0;       // r x (r x X)
-  Y0 = X0 + a * c0 + b * e0 + cp[3];
-  Y1 = X1 + a * c1 + b * e1 + cp[4];
-  Y2 = X2 + a * c2 + b * e2 + cp[5];
-}
-
-// ------------------------------------------------------------------------------------ linearise: per observation
-// One thread per observation (point-major).  Residual (sfm_reconstruction.py:453-470,486), analytic
-// 2x(D+3) Jacobian, Huber row scaling.  The two record arrays are transposed through
-// LDS one after the other (43 KB instead of 59 KB: 3 workgroups per CU) so the doubles of 256 observations
-// leave the CU as contiguous, fully coalesced streams.
-template <int D, typename T>
-__global__ __launch_bounds__(256) void k_lin_obs(int64_t N, const int* __restrict__ cam_idx,
-                                                 const int* __restrict__ pt_idx,
-                                                 const double* __restrict__ uv,
-                                                 const double* __restrict__ pts,
-                                                 const double* __restrict__ campre,
-                                                 T* __restrict__ recA, T* __restrict__ recB,
-                                                 double* __restrict__ part) {
-  constexpr int WA = 2 * D, LDA = WA + 1, WB = 8, LDB = WB + 1;
-  __shared__ double s_rec[256 * LDA];
-  __shared__ double s_red[4];
-  const int tid = threadIdx.x;
-  const int64_t k0 = (int64_t)blockIdx.x * 256;
-  const int64_t k = k0 + tid;
-  double cost = 0.0;
-  double jb[8];
-#pragma unroll
-  for (int q = 0; q < 8; ++q) jb[q] = 0.0;
-  if (k < N) {
-    const int c = cam_idx[k], j = pt_idx[k];
-    const double* cp = campre + (size_t)c * CAMPRE;
-    const double X0 = pts[3 * (size_t)j], X1 = pts[3 * (size_t)j + 1], X2 = pts[3 * (size_t)j + 2];
-    const double r0 = cp[0], r1 = cp[1], r2 = cp[2];
-    const double fx = cp[6], fy = cp[7], cx = cp[8], cy = cp[9];
-    const double a = cp[10], b = cp[11], a1 = cp[12], b1 = cp[13], th2 = cp[14];
-    const double c0 = r1 * X2 - r2 * X1, c1 = r2 * X0 - r0 * X2, c2 = r0 * X1 - r1 * X0;       // r x X
-    const double e0 = r1 * c2 - r2 * c1, e1 = r2 * c0 - r0 * c2, e2 = r0 * c1 - r1 * c0;       // r x (r x X)
-    const double Y0 = X0 + a * c0 + b * e0 + cp[3], Y1 = X1 + a * c1 + b * e1 + cp[4], Y2 = X2 + a * c2 + b * e2 + cp[5];
-    const double iz = 1.0 / Y2, xn = Y0 * iz, yn = Y1 * iz;
-    const double f0 = fx * xn + cx - uv[2 * k], f1 = fy * yn + cy - uv[2 * k + 1];
-    double s0, s1, ft0, ft1;
-    cost = 0.5 * (huber_row(f0, s0, ft0) + huber_row(f1, s1, ft1));
-    // Pi = d(u,v)/d(x,y,z), already multiplied by the robust row scale
-    const double p00 = s0 * fx * iz, p02 = -s0 * fx * xn * iz;
-    const double p11 = s1 * fy * iz, p12 = -s1 * fy * yn * iz;
-    double* my = &s_rec[tid * LDA];
-    // (dR/dr_i) X = a (e_i x X) + b (r X_i + e_i (r.X) - 2 r_i X) + r_i (a1 (r x X) + b1 (r x (r x X)))
-    const double rx = r0 * X0 + r1 * X1 + r2 * X2;
-    const double w0 = a1 * c0 + b1 * e0, w1 = a1 * c1 + b1 * e1, w2 = a1 * c2 + b1 * e2;
-    {
-      const double d0 = b * (r0 * X0 + rx - 2.0 * r0 * X0) + r0 * w0;
-      const double d1 = a * (-X2) + b * (r1 * X0 - 2.0 * r0 * X1) + r0 * w1;
-      const double d2 = a * (X1) + b * (r2 * X0 - 2.0 * r0 * X2) + r0 * w2;
-      my[0] = p00 * d0 + p02 * d2; my[D] = p11 * d1 + p12 * d2;
-    }
-    {
-      const double d0 = a * (X2) + b * (r0 * X1 - 2.0 * r1 * X0) + r1 * w0;
-      const double d1 = b * (r1 * X1 + rx - 2.0 * r1 * X1) + r1 * w1;
-      const double d2 = a * (-X0) + b * (r2 * X1 - 2.0 * r1 * X2) + r1 * w2;
-      my[1] = p00 * d0 + p02 * d2; my[D + 1] = p11 * d1 + p12 * d2;
-    }
-    {
-      const double d0 = a * (-X1) + b * (r0 * X2 - 2.0 * r2 * X0) + r2 * w0;
-      const double d1 = a * (X0) + b * (r1 * X2 - 2.0 * r2 * X1) + r2 * w1;
-      const double d2 = b * (r2 * X2 + rx - 2.0 * r2 * X2) + r2 * w2;
-      my[2] = p00 * d0 + p02 * d2; my[D + 2] = p11 * d1 + p12 * d2;
-    }
-    my[3] = p00; my[4] = 0.0; my[5] = p02;
-    my[D + 3] = 0.0; my[D + 4] = p11; my[D + 5] = p12;
-    if (D == 10) {
-      my[6] = s0 * xn; my[7] = 0.0; my[8] = s0; my[9] = 0.0;
-      my[D + 6] = 0.0; my[D + 7] = s1 * yn; my[D + 8] = 0.0; my[D + 9] = s1;
-    }
-    // R[p][q] = delta_pq + a (r x e_q)[p] + b (r_p r_q - delta_pq |r|^2);  Jp = Pi R needs rows 0, 1, 2
-    const double R00 = 1.0 + b * (r0 * r0 - th2), R01 = -a * r2 + b * r0 * r1, R02 = a * r1 + b * r0 * r2;
-    const double R10 = a * r2 + b * r1 * r0, R11 = 1.0 + b * (r1 * r1 - th2), R12 = -a * r0 + b * r1 * r2;
-    const double R20 = -a * r1 + b * r2 * r0, R21 = a * r0 + b * r2 * r1, R22 = 1.0 + b * (r2 * r2 - th2);
-    jb[0] = p00 * R00 + p02 * R20; jb[1] = p00 * R01 + p02 * R21; jb[2] = p00 * R02 + p02 * R22;
-    jb[3] = p11 * R10 + p12 * R20; jb[4] = p11 * R11 + p12 * R21; jb[5] = p11 * R12 + p12 * R22;
-    jb[6] = ft0; jb[7] = ft1;
-  }
-  double tot = block_sum256(cost, s_red);   // contains the barrier that publishes s_rec
-  if (tid == 0) part[blockIdx.x] = tot;
-  const int nvalid = (int)((N - k0) < 256 ? (N - k0) : 256);
-  {
-    T* outp = recA + (size_t)k0 * WA;
-    for (int i = tid; i < nvalid * WA; i += 256) {
-      const int t = i / WA, q = i - t * WA;
-      outp[i] = (T)s_rec[t * LDA + q];
-    }
-  }
-  __syncthreads();
-  {
-    double* my = &s_rec[tid * LDB];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) my[q] = jb[q];
-  }
-  __syncthreads();
-  {
-    T* outp = recB + (size_t)k0 * WB;
-    for (int i = tid; i < nvalid * WB; i += 256) {
-      const int t = i >> 3, q = i & 7;
-      outp[i] = (T)s_rec[t * LDB + q];
-    }
-  }
-}
-
-// per point: C_j = sum Jp~^T Jp~ (packed xx,xy,xz,yy,yz,zz), g_pj = sum Jp~^T f~ ; block partials of
-// ||g_p||^2 and max|g_p|.
-template <typename T>
-__global__ __launch_bounds__(256) void k_point_blocks(int P, const int* __restrict__ pt_ptr,
-                                                      const T* __restrict__ recB,
-                                                      double* __restrict__ Cp, double* __restrict__ gp,
-                                                      double* __restrict__ part) {
-  __shared__ double s_red[4];
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  double g2 = 0.0, gm = 0.0, cm = 0.0;
-  if (j < P) {
-    double c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, g0 = 0, g1 = 0, g2v = 0;
-    for (int k = pt_ptr[j]; k < pt_ptr[j + 1]; ++k) {       // (`#pragma unroll 5`, which pays in k_backsub: 17.5 -> 19.9 us here)
-      const T* r = recB + (size_t)k * 8;
-      const double a0 = r[0], a1 = r[1], a2 = r[2], b0 = r[3], b1 = r[4], b2 = r[5], f0 = r[6], f1 = r[7];
-      c0 += a0 * a0 + b0 * b0; c1 += a0 * a1 + b0 * b1; c2 += a0 * a2 + b0 * b2;
-      c3 += a1 * a1 + b1 * b1; c4 += a1 * a2 + b1 * b2; c5 += a2 * a2 + b2 * b2;
-      g0 += a0 * f0 + b0 * f1; g1 += a1 * f0 + b1 * f1; g2v += a2 * f0 + b2 * f1;
-    }
-    double* co = Cp + (size_t)j * 6;
-    co[0] = c0; co[1] = c1; co[2] = c2; co[3] = c3; co[4] = c4; co[5] = c5;
-    gp[(size_t)j * 3] = g0; gp[(size_t)j * 3 + 1] = g1; gp[(size_t)j * 3 + 2] = g2v;
-    g2 = g0 * g0 + g1 * g1 + g2v * g2v;
-    gm = fmax(fabs(g0), fmax(fabs(g1), fabs(g2v)));
-    cm = fmax(c0, fmax(c3, c5));
-  }
-  double t2 = block_sum256(g2, s_red);
-  double tm = block_max256(gm, s_red);
-  double tc = block_max256(cm, s_red);
-  if (threadIdx.x == 0) { part[blockIdx.x * 4] = t2; part[blockIdx.x * 4 + 1] = tm; part[blockIdx.x * 4 + 2] = tc; }
-}
-
-// per camera: B_c = sum Jc~^T Jc~ (DxD), g_c = sum Jc~^T f~ over the camera's observations.
-// One workgroup per chunk of <= 256 observations of one camera: the chunk's Jc~ rows and f~ are gathered into
-// LDS and contracted on the matrix cores; the chunks of a camera are added in fixed order (k_cam_blocks_final).
-template <int D, typename T>
-__global__ __launch_bounds__(256) void k_cam_blocks_chunks(const int* __restrict__ cch_beg, const int* __restrict__ cch_end,
-                                                           const int* __restrict__ cam_obs,
-                                                           const T* __restrict__ recA,
-                                                           const T* __restrict__ recB, double* __restrict__ part) {
-  // [B | g] = M^T M restricted to rows < D, with M = [Jc~ | f~] (2 rows per observation, D + 1 columns): one 16x16
-  // tile of v_mfma_f64_16x16x4_f64 per wavefront, K = (observation, residual row), both operands the same LDS rows.
-  // Each wavefront takes a quarter of the chunk; the four partial tiles are added in fixed order.
-  constexpr int W = 2 * D + 2, LDW = W + 1, NE = D * D + D;
-  __shared__ double s[256 * LDW];
-  __shared__ double s_tile[4][16 * 17];
-  const int ch = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int beg = cch_beg[ch], cnt = cch_end[ch] - beg;
-  // gather of the chunk's rows: 16 lanes per observation, each one PAIR of values (16 bytes in float64) - the D pairs of the
-  // Jc~ rows and the pair f~ - so a row arrives in one load instruction per wavefront of four observations, and the loads of
-  // four trips are in flight together.  (One value per thread, 22 threads per observation: 150 us per linearisation at cfg4
-  // for 176 MB - a quarter of the rate of the other passes over the records.)
-  {
-    typedef T pair_t __attribute__((ext_vector_type(2)));
-    const int slot = tid >> 4, l16 = tid & 15;
-    const bool live = l16 <= D;                              // pairs 0 .. D-1: Jc~, pair D: f~
-    // all 16 trips of a full chunk in flight: first the 16 observation ids, then the 16 row pieces
-    int kk[16];
-#pragma unroll
-    for (int it = 0; it < 16; ++it) {
-      const int o = it * 16 + slot;
-      kk[it] = (live && o < cnt) ? cam_obs[beg + o] : -1;
-    }
-    pair_t v[16];
-#pragma unroll
-    for (int it = 0; it < 16; ++it) {
-      v[it] = (pair_t)(T)0;
-      if (kk[it] >= 0)
-        v[it] = l16 < D ? *(const pair_t*)(recA + (size_t)kk[it] * (2 * D) + 2 * l16) : *(const pair_t*)(recB + (size_t)kk[it] * 8 + 6);
-    }
-#pragma unroll
-    for (int it = 0; it < 16; ++it) {
-      const int o = it * 16 + slot;
-      if (kk[it] >= 0) { s[o * LDW + 2 * l16] = (double)v[it].x; s[o * LDW + 2 * l16 + 1] = (double)v[it].y; }
-    }
-  }
-  __syncthreads();
-  const int col = lane & 15, kq = lane >> 4;             // operand column (0..D-1: Jc~, D: f~), k slot
-  const int rrow = kq & 1;                               // residual row of this k slot
-  const int q = col < D ? rrow * D + col : 2 * D + rrow; // position inside an observation's staged record
-  const bool live = col <= D;
-  const int per = (cnt + 3) / 4;
-  // (the wave's range in SGPRs - w comes from threadIdx, so the compiler kept the trip count in a VGPR and wrapped every MFMA
-  // in an exec-mask save / restore - and four steps' operands read ahead of their MFMAs: one LDS wait per four, not per one)
-  const int wu = __builtin_amdgcn_readfirstlane(w);
-  const int o0 = wu * per, o1 = (o0 + per) < cnt ? (o0 + per) : cnt;
-  v4d acc = {0.0, 0.0, 0.0, 0.0};
-  for (int o = o0; o < o1; o += 8) {                     // k slots of a step: (o, row 0), (o, row 1), (o + 1, row 0), (o + 1, row 1)
-    double v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int oo = o + 2 * u + (kq >> 1);
-      v[u] = (live && oo < o1) ? s[oo * LDW + q] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (o + 2 * u >= o1) break;                          // wave-uniform
-      acc = __builtin_amdgcn_mfma_f64_16x16x4f64(v[u], v[u], acc, 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) s_tile[w][(kq + 4 * i) * 17 + col] = acc[i];      // C/D: row = kq + 4 i, column = col
-  __syncthreads();
-  if (tid < NE) {
-    const int a = tid < D * D ? tid / D : tid - D * D;
-    const int b = tid < D * D ? tid - a * D : D;
-    part[(size_t)ch * NE + tid] = ((s_tile[0][a * 17 + b] + s_tile[1][a * 17 + b]) + s_tile[2][a * 17 + b]) + s_tile[3][a * 17 + b];
-  }
-}
-template <int D>
-__global__ void k_cam_blocks_final(int C, const int* __restrict__ cch_ptr, const double* __restrict__ part,
-                                   double* __restrict__ B, double* __restrict__ gc) {
-  constexpr int NE = D * D + D;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= C * NE) return;
-  const int c = i / NE, e = i - c * NE;
-  double t = 0.0;
-  for (int ch = cch_ptr[c]; ch < cch_ptr[c + 1]; ++ch) t += part[(size_t)ch * NE + e];
-  if (e < D * D) B[(size_t)c * D * D + e] = t;
-  else gc[(size_t)c * D + (e - D * D)] = t;
-}
-
-// Regulariser rows of sfm_reconstruction.py:489-499 (cam_dim 10): residual, Jacobian w.r.t.
-// (fx,fy,cx,cy), Huber scaling; adds into B_c / g_c, keeps the scaled rows for the step stage.
-__global__ void k_cam_reg(int C, const double* __restrict__ cams, double fx0, double cx0, double cy0,
-                          double width, double height, double w, double* __restrict__ B,
-                          double* __restrict__ gc, double* __restrict__ cost_reg,
-                          double* __restrict__ regrec) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const double* p = cams + (size_t)c * 10;
-  const double fx = p[6], fy = p[7], cx = p[8], cy = p[9];
-  double f[4] = {(fx - fx0) / fx0 * w, (fy - fx) / fx * w, (cx - cx0) / width * w, (cy - cy0) / height * w};
-  double J[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) J[i] = 0.0;
-  J[0] = w / fx0;
-  J[4] = -w * fy / (fx * fx); J[5] = w / fx;
-  J[10] = w / width;
-  J[15] = w / height;
-  double cost = 0.0, ft[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    double sc;
-    cost += huber_row(f[r], sc, ft[r]);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) J[r * 4 + q] *= sc;
-  }
-  cost_reg[c] = 0.5 * cost;
-  double* Bc = B + (size_t)c * 100;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    double g = 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) g += J[r * 4 + i] * ft[r];
-    gc[(size_t)c * 10 + 6 + i] += g;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      double hsum = 0.0;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) hsum += J[r * 4 + i] * J[r * 4 + q];
-      Bc[(6 + i) * 10 + 6 + q] += hsum;
-    }
-  }
-  double* rr = regrec + (size_t)c * 20;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) rr[i] = J[i];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) rr[16 + r] = ft[r];
-}
-
-// Fixed-order sum of block partials -> reduce_lin = [gc copy | cost | ||gp||^2 | diag(B)], gmax = [max|gp|, max diag C].
-__global__ __launch_bounds__(256) void k_lin_finalize(int n, int D, const double* __restrict__ gc,
-                                                      const double* __restrict__ B,
-                                                      const double* __restrict__ part_obs, int nblk_obs,
-                                                      const double* __restrict__ part_pt, int nblk_pt,
-                                                      const double* __restrict__ cost_reg, int n_reg,
-                                                      double* __restrict__ red_lin, double* __restrict__ gmax) {
-  __shared__ double s_red[4];
-  const int tid = threadIdx.x;
-  #pragma unroll 8
-  for (int i = tid; i < n; i += 256) {
-    red_lin[i] = gc[i];
-    const int cam = i / D, a = i - cam * D;
-    red_lin[n + 2 + i] = B[(size_t)cam * D * D + a * D + a];
-  }
-  double c = 0.0, g2 = 0.0, gm = 0.0, cm = 0.0;
-  #pragma unroll 8
-  for (int i = tid; i < nblk_obs; i += 256) c += part_obs[i];
-  #pragma unroll 8
-  for (int i = tid; i < n_reg; i += 256) c += cost_reg[i];
-  #pragma unroll 8
-  for (int i = tid; i < nblk_pt; i += 256) { g2 += part_pt[4 * i]; gm = fmax(gm, part_pt[4 * i + 1]); cm = fmax(cm, part_pt[4 * i + 2]); }
-  double ct = block_sum256(c, s_red);
-  double g2t = block_sum256(g2, s_red);
-  double gmt = block_max256(gm, s_red);
-  double cmt = block_max256(cm, s_red);
-  if (tid == 0) { red_lin[n] = ct; red_lin[n + 1] = g2t; gmax[0] = gmt; gmax[1] = cmt; }
-}
-
-__global__ __launch_bounds__(256) void k_finish_linearize(int n, const double* __restrict__ red_lin,
-                                                          const double* __restrict__ gmax,
-                                                          double* __restrict__ sc, double* __restrict__ hsc, double seq) {
-  __shared__ double s_red[4];
-  double g2 = 0.0, gm = 0.0, hm = 0.0;
-  #pragma unroll 8
-  for (int i = threadIdx.x; i < n; i += 256) {
-    double v = red_lin[i]; g2 += v * v; gm = fmax(gm, fabs(v));
-    hm = fmax(hm, red_lin[n + 2 + i]);
-  }
-  double g2t = block_sum256(g2, s_red);
-  double gmt = block_max256(gm, s_red);
-  double hmt = block_max256(hm, s_red);
-  if (threadIdx.x == 0) {
-    sc[SFM_SC_COST] = hsc[SFM_SC_COST] = red_lin[n];
-    sc[SFM_SC_GNORM2] = hsc[SFM_SC_GNORM2] = g2t + red_lin[n + 1];
-    sc[SFM_SC_GINF] = hsc[SFM_SC_GINF] = fmax(gmt, gmax[0]);
-    sc[SFM_SC_HDIAG] = hsc[SFM_SC_HDIAG] = fmax(hmt, gmax[1]);
-    publish_ticket(hsc, seq);
-  }
 }
 
 // ------------------------------------------------------------------------------------ damped solve: point side
@@ -998,7 +504,6 @@ __global__ __launch_bounds__(64 * SFM_SCHUR_WG_WAVES) __attribute__((amdgpu_wave
 // exchange sfm_ba_pack_system, the factorisation: test_upper_triangle_of_S_is_never_read poisons the rest), so nothing else is
 // written; the items hold the UPPER blocks (c, r), c <= r, so element (rr, col) of block (r, c) is the transposed element of the
 // item tiles.  (The first form wrote each block by itself, and its mirror: 80-byte row segments, 0.42 ms at 1000 cameras.)
-constexpr int CGS_FAIL_WORD = 3;      // = CGS_FAIL (the camera CG's status words are declared with the CG, further down)
 // E_r = chol(S_rr + alpha I) and E_r^-1 by the first D lanes of a wave: lane i owns row i of L and, afterwards, column i of L^-1;
 // what another lane holds comes by shuffle.  blk: the block's element (0, 0) in LDS (row stride ld; only its lower triangle is
 // read).  The same operations in the same order as small_chol_inverse: bit for bit the factors k_diag_einv produces.
@@ -1041,7 +546,7 @@ __device__ __forceinline__ void diag_block_factor_lanes(const double* blk, int l
     Efac[(size_t)r * D * D + i * D + k] = k <= i ? Lr[k] : 0.0;
     Einv[(size_t)r * D * D + k * D + i] = Xc[k];
   }
-  if (!ok) cg_scal[CGS_FAIL_WORD] = 1.0;
+  if (!ok) cg_scal[CGS_FAIL] = 1.0;
 }
 // v[j] = -(sum of the item tiles of block (r, c_0 + j)) (+ B_r on the diagonal block), j < nv, for element e of the block (the
 // transposed element of the tiles for c < r: the items hold the upper blocks).  The item ranges of all blocks are fetched first and
@@ -1437,6 +942,15 @@ __global__ __launch_bounds__(256) void k_backsub(int P, const int* __restrict__ 
   if (threadIdx.x == 0) { part[blockIdx.x * 2] = a; part[blockIdx.x * 2 + 1] = b; }
 }
 
+// ------------------------------------------------------------------------------------ small vector helpers
+__global__ void k_copy_neg(const double* __restrict__ src, double* __restrict__ dst, int n, double sgn) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = sgn * src[i];
+}
+__global__ void k_add_vec(const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ dst, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = a[i] + b[i];
+}
 // dst[0..cnt) = fixed-order sums of `cnt` interleaved partial columns (stride = cnt).
 __global__ __launch_bounds__(256) void k_sum_partials(const double* __restrict__ part, int nblk, int cnt,
                                                       double* __restrict__ dst) {
@@ -1448,205 +962,21 @@ __global__ __launch_bounds__(256) void k_sum_partials(const double* __restrict__
     if (threadIdx.x == 0) dst[q] = tt;
   }
 }
-
-// ------------------------------------------------------------------------------------ small vector helpers
-__global__ void k_add_diag(double* __restrict__ A, int n, double alpha) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) A[(size_t)i * n + i] += alpha;
+__global__ __launch_bounds__(1024) void k_dot(int n, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ out) {
+  __shared__ double s_red[17];
+  double t = 0.0;
+  for (int i = threadIdx.x; i < n; i += 1024) t += a[i] * b[i];
+  t = block_sum1024(t, s_red);
+  if (threadIdx.x == 0) *out = t;
 }
-__global__ void k_copy_neg(const double* __restrict__ src, double* __restrict__ dst, int n, double sgn) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = sgn * src[i];
-}
-__global__ void k_add_vec(const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ dst, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = a[i] + b[i];
-}
-
-// scalars after the solve: PNORM2 = ||p_c||^2 + sum ||p_p||^2 ; PQ = sum ||v||^2 + ||y||^2
-__global__ __launch_bounds__(256) void k_finish_solve(int n, const double* __restrict__ pc,
-                                                      const double* __restrict__ red_q,
-                                                      const double* __restrict__ y, int want_q,
-                                                      const int* __restrict__ flag, double* __restrict__ sc, double* __restrict__ hsc,
-                                                      double seq) {
-  __shared__ double s_red[4];
-  double a = 0.0, b = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    a += pc[i] * pc[i];
-    if (want_q) b += y[i] * y[i];
-  }
-  double at = block_sum256(a, s_red);
-  double bt = block_sum256(b, s_red);
-  if (threadIdx.x == 0) {
-    const double pn2 = at + red_q[n], pq = want_q ? (bt + red_q[n + 1]) : 0.0;
-    sc[SFM_SC_PNORM2] = hsc[SFM_SC_PNORM2] = pn2;
-    sc[SFM_SC_PQ] = hsc[SFM_SC_PQ] = pq;
-    // 1: non-positive pivot, 2: a triangular solve stalled, 3: the step is not finite (NaN/Inf in the system)
-    int f = *flag;
-    if (f == 0 && !(isfinite(pn2) && isfinite(pq))) f = 3;
-    sc[SFM_SC_CHOL_FAIL] = hsc[SFM_SC_CHOL_FAIL] = (double)f;
-    publish_ticket(hsc, seq);
-  }
-}
-
-// ------------------------------------------------------------------------------------ step + cost
-__global__ __launch_bounds__(256) void k_axpy_step(int64_t n_c, int64_t n_total, const double* __restrict__ x,
-                                                   const double* __restrict__ pc, const double* __restrict__ pp,
-                                                   double scale, double* __restrict__ x_new,
-                                                   double* __restrict__ part) {
-  __shared__ double s_red[4];
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  double s2 = 0.0, x2 = 0.0;
-  if (i < n_total) {
-    const bool is_cam = i < n_c;
-    const double s = scale * (is_cam ? pc[i] : pp[i - n_c]);
-    const double xn = x[i] + s;
-    x_new[i] = xn;
-    if (!is_cam) { s2 = s * s; x2 = xn * xn; }
-  }
-  double a = block_sum256(s2, s_red);
-  double b = block_sum256(x2, s_red);
-  if (threadIdx.x == 0) { part[blockIdx.x * 2] = a; part[blockIdx.x * 2 + 1] = b; }
-}
-
-// per observation: (J~ s) for both rows -> partial sums of (J~ s)^2 and f~ (J~ s)
-template <int D, typename T>
-__global__ __launch_bounds__(256) void k_step_obs(int64_t N, const int* __restrict__ cam_idx,
-                                                  const int* __restrict__ pt_idx,
-                                                  const T* __restrict__ recA, const T* __restrict__ recB,
-                                                  const double* __restrict__ pc, const double* __restrict__ pp,
-                                                  double scale, double* __restrict__ part) {
-  __shared__ double s_red[4];
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;   // (obs, row)
-  double j2 = 0.0, gt = 0.0;
-  if (i < 2 * N) {
-    const int64_t k = i >> 1;
-    const int row = (int)(i & 1);
-    const T* jc = recA + (size_t)k * (2 * D) + row * D;
-    const T* rb = recB + (size_t)k * 8;
-    const T* jp = rb + row * 3;
-    const double* c = pc + (size_t)cam_idx[k] * D;
-    const double* q = pp + (size_t)pt_idx[k] * 3;
-    double t = (double)jp[0] * q[0] + (double)jp[1] * q[1] + (double)jp[2] * q[2];
-#pragma unroll
-    for (int a = 0; a < D; ++a) t += (double)jc[a] * c[a];
-    t *= scale;
-    j2 = t * t;
-    gt = (double)rb[6 + row] * t;
-  }
-  double a = block_sum256(j2, s_red);
-  double b = block_sum256(gt, s_red);
-  if (threadIdx.x == 0) { part[blockIdx.x * 4] = a; part[blockIdx.x * 4 + 1] = b; }
-}
-
-// Huber cost of the reprojection rows at the parameters behind `campre` / `pts`.
-__global__ __launch_bounds__(256) void k_cost_obs(int64_t N, const int* __restrict__ cam_idx,
-                                                  const int* __restrict__ pt_idx,
-                                                  const double* __restrict__ uv, const double* __restrict__ pts,
-                                                  const double* __restrict__ campre,
-                                                  double* __restrict__ part, int part_stride, int part_col,
-                                                  double* __restrict__ err_out) {
-  __shared__ double s_red[4];
-  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  double cost = 0.0;
-  if (k < N) {
-    const double* cp = campre + (size_t)cam_idx[k] * CAMPRE;
-    const size_t j = (size_t)pt_idx[k] * 3;
-    const double X0 = pts[j], X1 = pts[j + 1], X2 = pts[j + 2];
-    double Y0, Y1, Y2;
-    cam_project(cp, X0, X1, X2, Y0, Y1, Y2);
-    const double iz = 1.0 / Y2;
-    const double f0 = cp[6] * (Y0 * iz) + cp[8] - uv[2 * k];
-    const double f1 = cp[7] * (Y1 * iz) + cp[9] - uv[2 * k + 1];
-    cost = 0.5 * (huber_rho0(f0) + huber_rho0(f1));
-    if (err_out) err_out[k] = sqrt(f0 * f0 + f1 * f1);
-  }
-  double t = block_sum256(cost, s_red);
-  if (threadIdx.x == 0 && part) part[(size_t)blockIdx.x * part_stride + part_col] = t;
-}
-
-// regulariser rows at x_new (cost) and their share of J~ s, f~ J~ s
-__global__ void k_reg_step(int C, const double* __restrict__ cams_new, const double* __restrict__ pc,
-                           double scale, const double* __restrict__ regrec, double fx0, double cx0, double cy0,
-                           double width, double height, double w, int with_lin,
-                           double* __restrict__ cost_reg /*[C][4]: cost, js2, gts*/) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const double* p = cams_new + (size_t)c * 10;
-  const double fx = p[6], fy = p[7], cx = p[8], cy = p[9];
-  const double f[4] = {(fx - fx0) / fx0 * w, (fy - fx) / fx * w, (cx - cx0) / width * w, (cy - cy0) / height * w};
-  double cost = 0.0;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) cost += huber_rho0(f[r]);
-  double js2 = 0.0, gts = 0.0;
-  if (with_lin) {
-    const double* rr = regrec + (size_t)c * 20;
-    const double* s = pc + (size_t)c * 10 + 6;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const double t = scale * (rr[r * 4] * s[0] + rr[r * 4 + 1] * s[1] + rr[r * 4 + 2] * s[2] + rr[r * 4 + 3] * s[3]);
-      js2 += t * t;
-      gts += rr[16 + r] * t;
-    }
-  }
-  cost_reg[(size_t)c * 4] = 0.5 * cost;
-  cost_reg[(size_t)c * 4 + 1] = js2;
-  cost_reg[(size_t)c * 4 + 2] = gts;
-}
-
-// red_step = [ js2, gts, cost_new, s_pts2, xnew_pts2 ] (this rank's partial sums, fixed order).
-// The single-workgroup sums of this kernel and of k_lin_finalize / k_finish_step / k_finish_linearize walk ~4,000 block partials,
-// 16 per thread: with a run-time trip count the loop waited for every load before issuing the next (12-14 us per kernel);
-// `#pragma unroll 8` lets eight loads be in flight while the additions keep their order (the same bits).
-__global__ __launch_bounds__(256) void k_step_finalize(const double* __restrict__ part_obs, int nblk_obs,
-                                                       int nblk_rows, const double* __restrict__ part_x, int nblk_x,
-                                                       const double* __restrict__ cost_reg, int n_reg,
-                                                       int with_lin, double* __restrict__ red_step) {
-  __shared__ double s_red[4];
-  double v[5] = {0, 0, 0, 0, 0};
-  #pragma unroll 8
-  for (int i = threadIdx.x; i < nblk_obs; i += 256) v[2] += part_obs[(size_t)i * 4 + 2];
-  if (with_lin)
-    #pragma unroll 8
-    for (int i = threadIdx.x; i < nblk_rows; i += 256) { v[0] += part_obs[(size_t)i * 4]; v[1] += part_obs[(size_t)i * 4 + 1]; }
-  #pragma unroll 8
-  for (int i = threadIdx.x; i < n_reg; i += 256) {
-    v[2] += cost_reg[(size_t)i * 4]; v[0] += cost_reg[(size_t)i * 4 + 1]; v[1] += cost_reg[(size_t)i * 4 + 2];
-  }
-  if (with_lin)
-    #pragma unroll 8
-    for (int i = threadIdx.x; i < nblk_x; i += 256) { v[3] += part_x[(size_t)i * 2]; v[4] += part_x[(size_t)i * 2 + 1]; }
-#pragma unroll
-  for (int q = 0; q < 5; ++q) {
-    double t = block_sum256(v[q], s_red);
-    if (threadIdx.x == 0) red_step[q] = t;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_finish_step(int n_c, const double* __restrict__ pc, double scale,
-                                                     const double* __restrict__ x_new,
-                                                     const double* __restrict__ red_step,
-                                                     double* __restrict__ sc, double* __restrict__ hsc, double seq) {
-  __shared__ double s_red[4];
-  double s2 = 0.0, x2 = 0.0;
-  #pragma unroll 8
-  for (int i = threadIdx.x; i < n_c; i += 256) {
-    const double s = scale * pc[i];
-    s2 += s * s;
-    x2 += x_new[i] * x_new[i];
-  }
-  double a = block_sum256(s2, s_red);
-  double b = block_sum256(x2, s_red);
-  if (threadIdx.x == 0) {
-    sc[SFM_SC_JS2] = hsc[SFM_SC_JS2] = red_step[0]; sc[SFM_SC_GTS] = hsc[SFM_SC_GTS] = red_step[1];
-    sc[SFM_SC_COST_NEW] = hsc[SFM_SC_COST_NEW] = red_step[2];
-    sc[SFM_SC_SNORM2] = hsc[SFM_SC_SNORM2] = a + red_step[3]; sc[SFM_SC_XNEW_NORM2] = hsc[SFM_SC_XNEW_NORM2] = b + red_step[4];
-    publish_ticket(hsc, seq);
-  }
-}
+// (the launches the other units make of these: ba_stages.h)
+void ba_copy_neg(sfm_ctx* h, const double* src, double* dst, int n, double sgn) { hipLaunchKernelGGL(k_copy_neg, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, src, dst, n, sgn); }
+void ba_add_vec(sfm_ctx* h, const double* a, const double* b, double* dst, int n) { hipLaunchKernelGGL(k_add_vec, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, a, b, dst, n); }
+void ba_dot(sfm_ctx* h, int n, const double* a, const double* b, double* out) { hipLaunchKernelGGL(k_dot, dim3(1), dim3(1024), 0, h->stream, n, a, b, out); }
+void ba_sum_partials(sfm_ctx* h, const double* part, int nblk, int cnt, double* dst) { hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, h->stream, part, nblk, cnt, dst); }
 
 // ------------------------------------------------------------------------------------ host stages
-static int check_problem(sfm_ctx* h, sfm_ba_problem p, Lay* L) {
+int check_problem(sfm_ctx* h, sfm_ba_problem p, Lay* L) {
   if (!h) return SFM_ERR_ARG;
   if (!p) return sfm_fail(h, SFM_ERR_ARG, "sfm_ba", "null problem");
   if (!p->workspace) return sfm_fail(h, SFM_ERR_WORKSPACE, "sfm_ba", "no workspace bound (sfm_ba_bind_workspace)");
@@ -1654,170 +984,42 @@ static int check_problem(sfm_ctx* h, sfm_ba_problem p, Lay* L) {
   return SFM_OK;
 }
 
-#define WS(L, field) (ws + (L).field)
-#define DISPATCH_D(D, ...)            \
-  do {                                \
-    if ((D) == 10) { constexpr int DD = 10; __VA_ARGS__; } \
-    else { constexpr int DD = 6; __VA_ARGS__; }            \
-  } while (0)
-// camera block width DD, storage type TT of the Jacobian records, G block stride GG (doubles; G is always float64)
-#define DISPATCH_DT(D, PREC, ...)                                                                 \
-  do {                                                                                            \
-    if ((PREC) == SFM_BA_MIXED) {                                                                 \
-      if ((D) == 10) { constexpr int DD = 10; constexpr int GG = 32; typedef float TT; __VA_ARGS__; }  \
-      else { constexpr int DD = 6; constexpr int GG = 18; typedef float TT; __VA_ARGS__; }             \
-    } else {                                                                                      \
-      if ((D) == 10) { constexpr int DD = 10; constexpr int GG = 32; typedef double TT; __VA_ARGS__; } \
-      else { constexpr int DD = 6; constexpr int GG = 18; typedef double TT; __VA_ARGS__; }            \
-    }                                                                                             \
-  } while (0)
-#define WST(L, field) ((TT*)(ws + (L).field))
-
-static int launch_cost(sfm_ctx* h, sfm_ba_problem p, const Lay& L, double* ws, const double* x,
-                       const double* pc_for_reg, double scale, int with_lin, double* err_out) {
-  const int C = p->n_cams, D = p->cam_dim;
-  const int64_t N = p->n_obs;
-  const double* cams = x;
-  const double* pts = x + (size_t)C * D;
-  DISPATCH_D(D, hipLaunchKernelGGL(k_campre<DD>, dim3(cdiv(C, 64)), dim3(64), 0, h->stream, cams, C, p->fx0,
-                                   p->fy0, p->cx0, p->cy0, WS(L, campre2)));
-  hipLaunchKernelGGL(k_cost_obs, dim3((unsigned)L.nblk_obs), dim3(256), 0, h->stream, N, p->cam_idx, p->pt_idx,
-                     p->uv, pts, WS(L, campre2), WS(L, part_obs), 4, 2, err_out);
-  if (D == 10 && p->apply_reg)
-    hipLaunchKernelGGL(k_reg_step, dim3(cdiv(C, 64)), dim3(64), 0, h->stream, C, cams, pc_for_reg, scale,
-                       WS(L, regrec), p->fx0, p->cx0, p->cy0, p->width, p->height, p->reg_weight, with_lin,
-                       WS(L, cost_reg));
-  SFM_LAUNCH_CHECK(h, "launch_cost");
-  return SFM_OK;
-}
-
-extern "C" int sfm_ba_cost(sfm_handle h, sfm_ba_problem p, const double* x) {
-  Lay L; int rc = check_problem(h, p, &L); if (rc) return rc;
-  double* ws = (double*)p->workspace;
-  rc = launch_cost(h, p, L, ws, x, nullptr, 0.0, 0, nullptr); if (rc) return rc;
-  const int nreg = (p->cam_dim == 10 && p->apply_reg) ? p->n_cams : 0;
-  hipLaunchKernelGGL(k_step_finalize, dim3(1), dim3(256), 0, h->stream, WS(L, part_obs), (int)L.nblk_obs, 0,
-                     (const double*)nullptr, 0, WS(L, cost_reg), nreg, 0, WS(L, red_step));
-  SFM_LAUNCH_CHECK(h, "sfm_ba_cost");
-  return SFM_OK;
-}
-
-__global__ void k_set_intrinsics(int C, double fx, double fy, double cx, double cy, double* __restrict__ cp) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  double* o = cp + (size_t)c * CAMPRE;
-  o[6] = fx; o[7] = fy; o[8] = cx; o[9] = cy;
-}
-
-extern "C" int sfm_ba_reproj_errors(sfm_handle h, sfm_ba_problem p, const double* x, int shared_k,
-                                    double* err_out) {
-  Lay L; int rc = check_problem(h, p, &L); if (rc) return rc;
-  if (!err_out) return sfm_fail(h, SFM_ERR_ARG, "sfm_ba_reproj_errors", "null output");
-  double* ws = (double*)p->workspace;
-  const int C = p->n_cams, D = p->cam_dim;
-  DISPATCH_D(D, hipLaunchKernelGGL(k_campre<DD>, dim3(cdiv(C, 64)), dim3(64), 0, h->stream, x, C, p->fx0,
-                                   p->fy0, p->cx0, p->cy0, WS(L, campre2)));
-  // compute_reconstruction_stats projects with the ONE shared self.K (sfm_reconstruction.py:601)
-  if (shared_k)
-    hipLaunchKernelGGL(k_set_intrinsics, dim3(cdiv(C, 64)), dim3(64), 0, h->stream, C, p->fx0, p->fy0, p->cx0,
-                       p->cy0, WS(L, campre2));
-  hipLaunchKernelGGL(k_cost_obs, dim3((unsigned)L.nblk_obs), dim3(256), 0, h->stream, p->n_obs, p->cam_idx,
-                     p->pt_idx, p->uv, x + (size_t)C * D, WS(L, campre2), (double*)nullptr, 0, 0, err_out);
-  SFM_LAUNCH_CHECK(h, "sfm_ba_reproj_errors");
-  return SFM_OK;
-}
-
-__global__ void k_sq_partials(int64_t n, const double* __restrict__ v, double* __restrict__ part);     // (defined with the loop's ||x|| helpers)
-
-// sum over this problem's observations of ||proj - uv||^2 at x, to the host: what bundle_adjust logs before and after the
-// solve (sfm_reconstruction.py:522-524 prints ||objective(x)||_2).  In the library so that the drop-in's write-back needs no
-// torch kernel: on a fresh box the first use of a torch elementwise / reduction kernel pages its code object in from disk,
-// ~0.1 s of the 0.15 s the round-2 driver run saw in `log_norms_and_write_back`.
-extern "C" int sfm_ba_residual_norm2(sfm_handle h, sfm_ba_problem p, const double* x, int shared_k, double* out_host) {
-  Lay L; int rc = check_problem(h, p, &L); if (rc) return rc;
-  if (!x || !out_host) return sfm_fail(h, SFM_ERR_ARG, "sfm_ba_residual_norm2", "null argument");
-  double* ws = (double*)p->workspace;
-  const int C = p->n_cams, D = p->cam_dim;
-  const int64_t N = p->n_obs;
-  DISPATCH_D(D, hipLaunchKernelGGL(k_campre<DD>, dim3(cdiv(C, 64)), dim3(64), 0, h->stream, x, C, p->fx0,
-                                   p->fy0, p->cx0, p->cy0, WS(L, campre2)));
-  if (shared_k)
-    hipLaunchKernelGGL(k_set_intrinsics, dim3(cdiv(C, 64)), dim3(64), 0, h->stream, C, p->fx0, p->fy0, p->cx0,
-                       p->cy0, WS(L, campre2));
-  hipLaunchKernelGGL(k_cost_obs, dim3((unsigned)L.nblk_obs), dim3(256), 0, h->stream, N, p->cam_idx,
-                     p->pt_idx, p->uv, x + (size_t)C * D, WS(L, campre2), (double*)nullptr, 0, 0, WS(L, tmp3));
-  hipLaunchKernelGGL(k_sq_partials, dim3((unsigned)L.nblk_obs), dim3(256), 0, h->stream, N, WS(L, tmp3), WS(L, part_obs));
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, h->stream, WS(L, part_obs), (int)L.nblk_obs, 1, WS(L, red_step) + 6);
-  SFM_HIP(h, hipMemcpyAsync(h->pinned + 48, WS(L, red_step) + 6, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  SFM_HIP(h, hipStreamSynchronize(h->stream));
-  SFM_LAUNCH_CHECK(h, "sfm_ba_residual_norm2");
-  *out_host = h->pinned[48];
-  return SFM_OK;
-}
-
-extern "C" int sfm_reproj_errors(sfm_handle h, int32_t n_cams, int32_t cam_dim, int64_t n_obs, const int32_t* cam_idx,
-                                 const int32_t* pt_idx, const double* uv, const double* x, double fx, double fy, double cx,
-                                 double cy, int shared_k, double* err_out) {
+extern "C" int sfm_ba_set_sharded(sfm_handle h, sfm_ba_problem p, int sharded) {
   if (!h) return SFM_ERR_ARG;
-  if (n_cams < 1 || n_obs < 1 || (cam_dim != 6 && cam_dim != 10) || !cam_idx || !pt_idx || !uv || !x || !err_out)
-    return sfm_fail(h, SFM_ERR_ARG, "sfm_reproj_errors", "bad argument");
-  double* campre = (double*)sfm_scratch(h, (size_t)n_cams * CAMPRE * sizeof(double));
-  if (!campre) return sfm_fail(h, SFM_ERR_HIP, "sfm_reproj_errors", "scratch allocation failed");
-  const int C = n_cams;
-  DISPATCH_D(cam_dim, hipLaunchKernelGGL(k_campre<DD>, dim3(cdiv(C, 64)), dim3(64), 0, h->stream, x, C, fx, fy, cx, cy, campre));
-  if (shared_k)
-    hipLaunchKernelGGL(k_set_intrinsics, dim3(cdiv(C, 64)), dim3(64), 0, h->stream, C, fx, fy, cx, cy, campre);
-  hipLaunchKernelGGL(k_cost_obs, dim3(cdiv(n_obs, 256)), dim3(256), 0, h->stream, n_obs, cam_idx, pt_idx, uv,
-                     x + (size_t)C * cam_dim, campre, (double*)nullptr, 0, 0, err_out);
-  SFM_LAUNCH_CHECK(h, "sfm_reproj_errors");
+  if (!p) return sfm_fail(h, SFM_ERR_ARG, "sfm_ba_set_sharded", "null problem");
+  p->sharded = sharded ? 1 : 0;
   return SFM_OK;
 }
 
-extern "C" int sfm_ba_linearize(sfm_handle h, sfm_ba_problem p, const double* x) {
-  Lay L; int rc = check_problem(h, p, &L); if (rc) return rc;
-  double* ws = (double*)p->workspace;
-  const int C = p->n_cams, P = p->n_pts, D = p->cam_dim, n = C * D;
-  const int64_t N = p->n_obs;
-  const double* pts = x + (size_t)n;
-  p->cgp.fail_rel *= 0.8;                             // a new linearisation: what was hopeless for the camera CG may not be here, let it try lower again
-  DISPATCH_DT(D, p->precision, {
-    hipLaunchKernelGGL(k_campre<DD>, dim3(cdiv(C, 64)), dim3(64), 0, h->stream, x, C, p->fx0, p->fy0, p->cx0,
-                       p->cy0, WS(L, campre));
-    sfm_prof_begin(h, SFM_PROF_LIN_OBS);
-    hipLaunchKernelGGL((k_lin_obs<DD, TT>), dim3((unsigned)L.nblk_obs), dim3(256), 0, h->stream, N, p->cam_idx,
-                       p->pt_idx, p->uv, pts, WS(L, campre), WST(L, recA), WST(L, recB), WS(L, part_obs));
-    sfm_prof_end(h, SFM_PROF_LIN_OBS);
-    sfm_prof_begin(h, SFM_PROF_LIN_REST);
-    hipLaunchKernelGGL(k_point_blocks<TT>, dim3((unsigned)L.nblk_pt), dim3(256), 0, h->stream, P, p->pt_ptr,
-                       WST(L, recB), WS(L, Cp), WS(L, gp), WS(L, part_pt));
-    if (p->n_cchunks > 0)
-      hipLaunchKernelGGL((k_cam_blocks_chunks<DD, TT>), dim3((unsigned)p->n_cchunks), dim3(256), 0, h->stream, p->cch_beg,
-                         p->cch_end, p->cam_obs, WST(L, recA), WST(L, recB), WS(L, cbl_part));
-    hipLaunchKernelGGL(k_cam_blocks_final<DD>, dim3(cdiv((int64_t)C * (DD * DD + DD), 256)), dim3(256), 0, h->stream, C,
-                       p->cch_ptr, WS(L, cbl_part), WS(L, B), WS(L, gc));
-  });
-  int nreg = 0;
-  if (D == 10 && p->apply_reg) {
-    nreg = C;
-    hipLaunchKernelGGL(k_cam_reg, dim3(cdiv(C, 64)), dim3(64), 0, h->stream, C, x, p->fx0, p->cx0, p->cy0,
-                       p->width, p->height, p->reg_weight, WS(L, B), WS(L, gc), WS(L, cost_reg), WS(L, regrec));
-  }
-  // cost_reg is [C][4] in the step stage and [C] here: use stride 1 in both by writing column 0 only
-  hipLaunchKernelGGL(k_lin_finalize, dim3(1), dim3(256), 0, h->stream, n, D, WS(L, gc), WS(L, B), WS(L, part_obs),
-                     (int)L.nblk_obs, WS(L, part_pt), (int)L.nblk_pt, WS(L, cost_reg), nreg, WS(L, red_lin),
-                     WS(L, gmax));
-  sfm_prof_end(h, SFM_PROF_LIN_REST);
-  SFM_LAUNCH_CHECK(h, "sfm_ba_linearize");
-  return SFM_OK;
+// the launches of the Schur stage that other units make too (what they enqueue: ba_stages.h)
+void launch_build_G(sfm_ctx* h, sfm_ba_problem p, const Lay& L, double alpha, double* cg_scal) {
+  double* ws = (double*)p->workspace; const int64_t N = p->n_obs, P = p->n_pts;
+  DISPATCH_DT(p->cam_dim, p->precision,
+    hipLaunchKernelGGL((k_build_G<DD, TT, double, GG>), dim3(cdiv(N, 256) + cdiv(P, 256)), dim3(256), 0, h->stream, N, p->pt_idx, WST(L, recA),
+                       WST(L, recB), WS(L, Linv), WS(L, G), WS(L, e), WS(L, eobs), WS(L, Cp), WS(L, gp), alpha, (int)P, (unsigned)cdiv(N, 256),
+                       cg_scal));
 }
-
-extern "C" int sfm_ba_finish_linearize(sfm_handle h, sfm_ba_problem p) {
-  Lay L; int rc = check_problem(h, p, &L); if (rc) return rc;
+void launch_obs_Gtp(sfm_ctx* h, sfm_ba_problem p, const Lay& L, const double* vc) {
+  double* ws = (double*)p->workspace; const int64_t N = p->n_obs;
+  DISPATCH_D(p->cam_dim, hipLaunchKernelGGL((k_obs_Gtp<DD, double, GG>), dim3(cdiv(N, GTP_OBS)), dim3(256), 0, h->stream, N, p->cam_idx, WS(L, G), vc, WS(L, tmp3)));
+}
+void launch_backsub_points(sfm_ctx* h, sfm_ba_problem p, const Lay& L) {
   double* ws = (double*)p->workspace;
-  hipLaunchKernelGGL(k_finish_linearize, dim3(1), dim3(256), 0, h->stream, p->n_cams * p->cam_dim,
-                     WS(L, red_lin), WS(L, gmax), WS(L, scalars), p->host_sc, next_ticket(p));
-  SFM_LAUNCH_CHECK(h, "sfm_ba_finish_linearize");
-  return SFM_OK;
+  hipLaunchKernelGGL(k_backsub, dim3((unsigned)L.nblk_pt), dim3(256), 0, h->stream, p->n_pts, p->pt_ptr, WS(L, tmp3),
+                     WS(L, Linv), WS(L, e), WS(L, pp), WS(L, v), WS(L, part_pt));
+}
+void launch_cam_reduce_chunks(sfm_ctx* h, sfm_ba_problem p, const Lay& L, const double* vec) {
+  double* ws = (double*)p->workspace;
+  if (p->n_cchunks > 0)
+    DISPATCH_D(p->cam_dim, hipLaunchKernelGGL((k_cam_reduce_chunks<DD, double, GG>), dim3((unsigned)p->n_cchunks), dim3(256), 0, h->stream, p->cch_beg,
+                                              p->cch_end, p->cam_obs, p->cam_pt, WS(L, G), vec, WS(L, cch_part)));
+}
+void launch_cam_reduce_final(sfm_ctx* h, sfm_ba_problem p, const Lay& L, const double* base, double* out, bool point_sums) {
+  double* ws = (double*)p->workspace; const int C = p->n_cams, s = point_sums ? 1 : 0;
+  // (+ 1 workgroup: the two sums over the point pass's per-block partials, sum ||p_p||^2 and sum ||v||^2; else the kernel's defaults)
+  DISPATCH_D(p->cam_dim, hipLaunchKernelGGL(k_cam_reduce_final<DD>, dim3(cdiv(C, 4) + s), dim3(256), 0, h->stream, C, p->cch_ptr, WS(L, cch_part),
+                                            base, out, s ? WS(L, part_pt) : (const double*)nullptr, s ? (int)L.nblk_pt : 0, s ? 2 : 0,
+                                            s ? WS(L, red_q) + C * p->cam_dim : (double*)nullptr));
 }
 
 // S (red_S) and its right-hand side from the item tiles; einv_out / m_out: the diagonal blocks' factors of S + alpha I for the
@@ -1858,17 +1060,14 @@ extern "C" int sfm_ba_schur_build(sfm_handle h, sfm_ba_problem p, double alpha) 
   Lay L; int rc = check_problem(h, p, &L); if (rc) return rc;
   if (!(alpha > 0.0)) return sfm_fail(h, SFM_ERR_ARG, "sfm_ba_schur_build", "alpha must be > 0");
   double* ws = (double*)p->workspace;
-  const int C = p->n_cams, P = p->n_pts, D = p->cam_dim, n = C * D;
-  const int64_t N = p->n_obs;
+  const int C = p->n_cams, D = p->cam_dim, n = C * D;
   const BaSwitches sw = ba_switches_from_env();
   const CamPlan plan = cam_plan(n, p->camera_solver, h->cgs_persist_off != 0, sw);
   sfm_prof_begin(h, SFM_PROF_BUILD_G);
+  launch_build_G(h, p, L, alpha, WS(L, cg_scal));
+  sfm_prof_end(h, SFM_PROF_BUILD_G);
+  sfm_prof_begin(h, SFM_PROF_SCHUR);
   DISPATCH_DT(D, p->precision, {
-    hipLaunchKernelGGL((k_build_G<DD, TT, double, GG>), dim3(cdiv(N, 256) + cdiv(P, 256)), dim3(256), 0, h->stream, N, p->pt_idx, WST(L, recA),
-                       WST(L, recB), WS(L, Linv), WS(L, G), WS(L, e), WS(L, eobs), WS(L, Cp), WS(L, gp), alpha, P, (unsigned)cdiv(N, 256),
-                       WS(L, cg_scal));
-    sfm_prof_end(h, SFM_PROF_BUILD_G);
-    sfm_prof_begin(h, SFM_PROF_SCHUR);
     if (p->n_items > 0) { // 8 groups x ceil(largest group / 4) workgroups
       sfm_prof_begin(h, SFM_PROF_SCHUR_ITEMS);
       hipLaunchKernelGGL((k_schur_items<DD, double, GG>), dim3(8 * cdiv(p->xcd_max_items, SFM_SCHUR_WG_WAVES)),
@@ -1877,10 +1076,8 @@ extern "C" int sfm_ba_schur_build(sfm_handle h, sfm_ba_problem p, double alpha) 
                          p->cam_idx, p->item_ptr, p->cch_ptr, C, WS(L, eobs), WS(L, cch_part), p->has_dup ? 0 : 1);
       sfm_prof_end(h, SFM_PROF_SCHUR_ITEMS);
     }
-    if (p->has_dup && p->n_cchunks > 0)        // the chunk partials of sum_k G_k e_j by the camera-wise pass over G
-      hipLaunchKernelGGL((k_cam_reduce_chunks<DD, double, GG>), dim3((unsigned)p->n_cchunks), dim3(256), 0, h->stream, p->cch_beg,
-                         p->cch_end, p->cam_obs, p->cam_pt, WS(L, G), WS(L, e), WS(L, cch_part));
   });
+  if (p->has_dup) launch_cam_reduce_chunks(h, p, L, WS(L, e));      // the chunk partials of sum_k G_k e_j by the camera-wise pass over G
   // what the solve of this system will consume decides what is left for it: S (with the diagonal blocks' factors), or S~ alone
   // (S is then formed on demand only: schur_materialise_S)
   const BuildFusion fuse = build_fusion(plan, p->sharded != 0, p->camera_solver, n, sw);
@@ -1901,7 +1098,7 @@ extern "C" int sfm_ba_schur_build(sfm_handle h, sfm_ba_problem p, double alpha) 
 
 // S (red_S) from the item tiles of the last sfm_ba_schur_build, for the consumers that need the unscaled system after a build
 // that formed S~ only: the factorisation (a system the CG is not given, or did not finish) and sfm_ba_pack_system.
-static int schur_materialise_S(sfm_ctx* h, sfm_ba_problem p, const Lay& L) {
+int schur_materialise_S(sfm_ctx* h, sfm_ba_problem p, const Lay& L) {
   if (p->s_valid) return SFM_OK;
   launch_schur_assemble(h, p, L, 0.0, nullptr, nullptr);
   p->s_valid = 1;
@@ -1935,1726 +1132,46 @@ static int pack_S(sfm_handle h, sfm_ba_problem p, int unpack_dir, const char* wh
 extern "C" int sfm_ba_pack_system(sfm_handle h, sfm_ba_problem p) { return pack_S(h, p, 0, "sfm_ba_pack_system"); }
 extern "C" int sfm_ba_unpack_system(sfm_handle h, sfm_ba_problem p) { return pack_S(h, p, 1, "sfm_ba_unpack_system"); }
 
-// In-register Cholesky of a small SPD block and the inverse of its factor (one thread per block; D <= 10):
-// L (lower part valid on entry) <- chol(L), X <- L^-1 (lower, zeros above).  Returns false on a non-positive pivot.
-template <int D>
-__device__ __forceinline__ bool small_chol_inverse(double (&L)[D][D], double (&X)[D][D]) {
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < D; ++j) {
-    // (explicit fused multiply-adds: the cooperative form of this routine in k_schur_assemble must round exactly alike, and what
-    // the compiler contracts on its own depends on the code around it)
-    double sum = L[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) sum = fma(-L[j][k], L[j][k], sum);
-    if (!(sum > 0.0)) { ok = false; sum = 1.0; }
-    const double l = sqrt(sum);
-    L[j][j] = l;
-#pragma unroll
-    for (int i = j + 1; i < D; ++i) {
-      double t = L[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) t = fma(-L[i][k], L[j][k], t);
-      L[i][j] = t / l;
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < D; ++t)
-#pragma unroll
-    for (int r = 0; r < D; ++r) {
-      double sum = (r == t) ? 1.0 : 0.0;
-#pragma unroll
-      for (int k = 0; k < r; ++k) sum = (k >= t) ? fma(-L[r][k], X[k][t], sum) : sum;
-      X[r][t] = (r >= t) ? sum / L[r][r] : 0.0;
-    }
-  return ok;
-}
-
-// (defined with the implicit-Schur PCG further down)
-__global__ void k_dot(int n, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ out);
-__global__ void k_finish_solve_pcg(int n, const double* __restrict__ pc, const double* __restrict__ red_q, int want_q,
-                                   const double* __restrict__ dotp, const double* __restrict__ failp, double* __restrict__ sc,
-                                   double* __restrict__ hsc, double seq);
-
-// ------------------------------------------------------------------------------------ CG on the explicit reduced system
-// Once S has been formed (and, multi-rank, all-reduced) the replicated camera solve is a latency chain in the dense
-// Cholesky (n / 64 dependent steps, 0.9 ms at n = 2000) - but with its own d x d diagonal blocks as preconditioner
-// S needs only ~25 conjugate-gradient iterations to a relative residual of 1e-13, each ONE launch that streams S once
-// from L2.  The system is scaled symmetrically with the Cholesky factors E_c of its diagonal blocks,
-// S~ = E^-1 (S + alpha I) E^-T (unit diagonal blocks), so that plain CG on S~ IS block-Jacobi PCG on S and the
-// recurrences need no preconditioner application.  k_cgs_iter: every workgroup first repeats the vector
-// recurrences of the previous iteration from r, p and the full S~ p (3 n doubles from L2, fixed-order block sums:
-// all workgroups obtain bit-identical scalars and vectors, so no grid-wide reduction or second launch is needed),
-// keeps the new direction in LDS and multiplies its own rows of S~ with it.  r, p, S~ p are double-buffered
-// (workgroup 0 publishes iteration k's vectors while others may still read iteration k-1's).  Rows are dealt to
-// workgroups so that one XCD owns a contiguous eighth of S~ (4 MB at n = 2000: stays in its L2 across iterations).
-// The host reads ||r||^2 every few launches.  If CG has not converged after CGS_MAX_ITER iterations, or meets a
-// direction of non-positive curvature, the caller falls back to the Cholesky route: S itself is left untouched.
-// (CGS_MAX_N, CGS_MAX_ITER and the budget of the tile-streaming route: ba_plan.h)
-// ||r|| <= CGS_RTOL ||r_0|| on the scaled system.  SFM_CGS_RTOL overrides it - a DIAGNOSTIC knob (tools/exp_cg_fixed_cost.py
-// sets 1.0: zero iterations, what remains is the fixed cost of a system), never set by the product
-static double cgs_rtol() { static const double v = getenv("SFM_CGS_RTOL") ? atof(getenv("SFM_CGS_RTOL")) : 1e-13; return v; }
-#define CGS_RTOL cgs_rtol()
-enum { CGS_RR0 = 0, CGS_RR = 1, CGS_ITER = 2, CGS_FAIL = 3, CGS_DONE = 4,
-       CGS_RR_SLOT = 5 };   // [5], [6]: ||r||^2 handed from launch to launch; launch `it` reads slot (it + 1) & 1, writes slot it & 1
-
-// E_c = chol(S_cc + alpha I); Einv[c] = E_c^-1 (lower, zeros above).  One thread per camera.
-template <int D>
-__global__ __launch_bounds__(64) void k_diag_einv(int C, const double* __restrict__ S, int n, double alpha, double* __restrict__ Einv,
-                            double* __restrict__ Efac /* E_c itself (lower) */, double* __restrict__ scal) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  double L[D][D], X[D][D];
-  const double* blk = S + (size_t)c * D * n + c * D;
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-#pragma unroll
-    for (int j = 0; j < D; ++j) L[i][j] = (j <= i) ? blk[(size_t)i * n + j] + (i == j ? alpha : 0.0) : 0.0;
-  const bool bad = !small_chol_inverse<D>(L, X);
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-      Einv[(size_t)c * D * D + i * D + j] = X[i][j];
-      Efac[(size_t)c * D * D + i * D + j] = j <= i ? L[i][j] : 0.0;
-    }
-  if (bad) scal[CGS_FAIL] = 1.0;
-}
-// St[c][c2] = Einv_c (S[c][c2] + alpha [c == c2]) Einv_c2^T.  One workgroup (128 threads, thread e < D*D owns element e of a
-// block) per block row c and SCALE_NB consecutive columns c2; only the blocks c2 >= c are computed, each is written twice
-// (St is symmetric: the block and its transpose).  All blocks of a workgroup move through each stage together: three
-// barriers per workgroup, not per block.  (One workgroup per block pair, 40,000 at 200 cameras: 22 us, dispatch-bound.)
-// (blocks per workgroup, us per launch at 200 cameras: 16: 29.9, 8: 21.8, 4: 18.4, 2: 18.0)
-constexpr int SCALE_NB = 4;
-template <int D>
-__global__ __launch_bounds__(128) void k_scale_system(int n, int C, const double* __restrict__ S, double alpha,
-                                                      const double* __restrict__ Einv, double* __restrict__ St,
-                                                      const double* __restrict__ rhs, double* __restrict__ rhs_t) {
-  __shared__ double sB[SCALE_NB][D * D], sT[SCALE_NB][D * D], sE2[SCALE_NB][D * D], sE1[D * D];
-  const int c = blockIdx.x, e = threadIdx.x;
-  const int a = e / D, b = e - a * D;
-  const int c2_0 = blockIdx.y * SCALE_NB;
-  // rhs~_c = E_c^-1 rhs_c for the CG that follows (the first workgroup of the block row does it, once for everybody: the
-  // persistent kernel used to form all of rhs~ in every one of its workgroups)
-  if (rhs_t && blockIdx.y == 0 && e < D) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < D; ++k) t += Einv[(size_t)c * D * D + e * D + k] * rhs[c * D + k];     // E^-1 lower: stored zeros above
-    rhs_t[c * D + e] = t;
-  }
-  if (c2_0 + SCALE_NB <= c) return;                      // (workgroup-uniform) nothing at or right of the diagonal here
-  const int nb = (C - c2_0) < SCALE_NB ? (C - c2_0) : SCALE_NB;
-  if (e < D * D) {
-    sE1[e] = Einv[(size_t)c * D * D + e];
-#pragma unroll
-    for (int j = 0; j < SCALE_NB; ++j)
-      if (j < nb && c2_0 + j >= c) {
-        // block (c, c2 >= c) of S from its LOWER triangle - the part the multi-rank exchange carries (sfm_ba_pack_system):
-        // S[c][c2][a][b] = S[c2 D + b][c D + a]
-        const int c2 = c2_0 + j, row = c * D + a, col = c2 * D + b;
-        sB[j][e] = (col <= row ? S[(size_t)row * n + col] : S[(size_t)col * n + row]) + ((c == c2 && a == b) ? alpha : 0.0);
-        sE2[j][e] = Einv[(size_t)c2 * D * D + e];
-      }
-  }
-  __syncthreads();
-  if (e < D * D) {
-#pragma unroll
-    for (int j = 0; j < SCALE_NB; ++j)
-      if (j < nb && c2_0 + j >= c) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) t += sE1[a * D + k] * sB[j][k * D + b];    // Einv_c is lower: entries k > a are stored zeros
-        sT[j][e] = t;
-      }
-  }
-  __syncthreads();
-  if (e < D * D) {
-#pragma unroll
-    for (int j = 0; j < SCALE_NB; ++j)
-      if (j < nb && c2_0 + j >= c) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) t += sT[j][a * D + k] * sE2[j][b * D + k];
-        const int c2 = c2_0 + j;
-        St[(size_t)(c * D + a) * n + c2 * D + b] = t;
-        if (c2 != c) St[(size_t)(c2 * D + b) * n + c * D + a] = t;
-      }
-  }
-}
-// The same for the tile-streaming CG (n > 2,048), which reads the 128 x 128 tiles (I, J <= I) of St only - the lower triangle
-// plus, inside the diagonal tiles, the entries above the diagonal: blocks (c, c2) with c2 <= c and the band c < c2 <= c + BAND
-// (a 128-wide tile spans at most 128 / D + 2 cameras).  Every block is read from the lower triangle of S and written ONCE, in
-// its own rows (80-byte row segments): half the bytes of k_scale_system and none of its column-strided mirror writes
-// (0.53 -> 0.35 ms at 1000 cameras).  A form that moves whole 640-byte rows of the strip through LDS (every workgroup computing all
-// its blocks, the transposes bit-identical) was built and measured SLOWER: 35 against 21 us at 200 cameras, +0.1 ms at 1000 - the
-// kernel is bound by the latency of its few dependent stages per workgroup, not by the width of its accesses.
-template <int D>
-__global__ __launch_bounds__(128) void k_scale_system_lower(int n, int C, const double* __restrict__ S, double alpha,
-                                                            const double* __restrict__ Einv, double* __restrict__ St,
-                                                            const double* __restrict__ rhs, double* __restrict__ rhs_t) {
-  constexpr int BAND = 128 / D + 2;
-  __shared__ double sB[SCALE_NB][D * D], sT[SCALE_NB][D * D], sE2[SCALE_NB][D * D], sE1[D * D];
-  // descending strips and rows: what k_schur_assemble wrote last is read first - still in the memory-side cache at 1000 cameras
-  const int c = (int)(gridDim.x - 1u - blockIdx.x), e = threadIdx.x;
-  const int a = e / D, b = e - a * D;
-  const int by = (int)(gridDim.y - 1u - blockIdx.y);
-  const int c2_0 = by * SCALE_NB;
-  if (rhs_t && by == 0 && e < D) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < D; ++k) t += Einv[(size_t)c * D * D + e * D + k] * rhs[c * D + k];
-    rhs_t[c * D + e] = t;
-  }
-  if (c2_0 > c + BAND) return;                           // (workgroup-uniform) nothing left of the band's end here
-  const int last = (c + BAND) < (C - 1) ? (c + BAND) : (C - 1);
-  if (e < D * D) {
-    sE1[e] = Einv[(size_t)c * D * D + e];
-#pragma unroll
-    for (int j = 0; j < SCALE_NB; ++j)
-      if (c2_0 + j <= last) {
-        const int c2 = c2_0 + j, row = c * D + a, col = c2 * D + b;
-        sB[j][e] = (col <= row ? S[(size_t)row * n + col] : S[(size_t)col * n + row]) + ((c == c2 && a == b) ? alpha : 0.0);
-        sE2[j][e] = Einv[(size_t)c2 * D * D + e];
-      }
-  }
-  __syncthreads();
-  if (e < D * D) {
-#pragma unroll
-    for (int j = 0; j < SCALE_NB; ++j)
-      if (c2_0 + j <= last) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) t += sE1[a * D + k] * sB[j][k * D + b];
-        sT[j][e] = t;
-      }
-  }
-  __syncthreads();
-  if (e < D * D) {
-#pragma unroll
-    for (int j = 0; j < SCALE_NB; ++j)
-      if (c2_0 + j <= last) {
-        double t = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) t += sT[j][a * D + k] * sE2[j][b * D + k];
-        St[(size_t)(c * D + a) * n + (c2_0 + j) * D + b] = t;
-      }
-  }
-}
-// out_c = Einv_c v_c (transpose 0) or Einv_c^T v_c (transpose 1), optionally negated
-template <int D>
-__global__ void k_block_mv(int C, const double* __restrict__ Einv, const double* __restrict__ v, double* __restrict__ out,
-                           int transpose, double sgn, const double* __restrict__ v2 = nullptr /* added to v when given */) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= C * D) return;
-  const int c = i / D, a = i - c * D;
-  const double* E = Einv + (size_t)c * D * D;
-  double t = 0.0;
-#pragma unroll
-  for (int k = 0; k < D; ++k) t += (transpose ? E[k * D + a] : E[a * D + k]) * (v[c * D + k] + (v2 ? v2[c * D + k] : 0.0));
-  out[i] = sgn * t;
-}
-// state 0 of the recurrence: x = 0, r = p = rhs; rr0
-__global__ __launch_bounds__(256) void k_cgs_init(int n, const double* __restrict__ rhs, double* __restrict__ x,
-                                                  double* __restrict__ r0, double* __restrict__ p0, double* __restrict__ scal) {
-  __shared__ double s_red[4];
-  double rr = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) { const double v = rhs[i]; x[i] = 0.0; r0[i] = v; p0[i] = v; rr += v * v; }
-  rr = block_sum256(rr, s_red);
-  if (threadIdx.x == 0) {
-    scal[CGS_RR0] = rr; scal[CGS_RR] = rr; scal[CGS_ITER] = 0.0; scal[CGS_DONE] = 0.0;
-    scal[CGS_RR_SLOT] = rr; scal[CGS_RR_SLOT + 1] = rr;
-  }
-}
-// One CG iteration on S~ per launch.  it == 0: only the product S~ p_0.  vec: [2 states][r | p | Ap], n doubles each.
-// NC = ceil(n / 512) column chunks per thread, ROWS rows of S~ per workgroup.  The workgroup's slice of S~ does not
-// depend on the recurrences, so it is fetched into registers FIRST (ROWS x NC 16-byte loads per thread in flight)
-// and the vector recurrences run in the shadow of that latency; measured 12.8 -> ... us per launch.
-template <int NC, int ROWS>
-__global__ __launch_bounds__(256) void k_cgs_iter(int n, int it, double rtol2, const double* __restrict__ St,
-                                                  double* __restrict__ vec, double* __restrict__ x, double* __restrict__ scal) {
-  __shared__ double s_p[NC * 512];
-  __shared__ double s_red[4];
-  __shared__ double s_row[ROWS][4];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  // rows of this workgroup: XCD x = blockIdx % 8 owns rows [x * per_xcd, (x + 1) * per_xcd)
-  const int per_xcd = (int)(gridDim.x / 8) * ROWS;
-  const int row0 = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3) * ROWS;
-  double2 sv[ROWS][NC];
-#pragma unroll
-  for (int q = 0; q < ROWS; ++q)
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int row = row0 + q, jc = 2 * tid + 512 * c;            // n is even: jc < n implies jc + 1 < n
-      sv[q][c] = (row < n && jc < n) ? *(const double2*)(St + (size_t)row * n + jc) : make_double2(0.0, 0.0);
-    }
-  const size_t sz = (size_t)3 * n;
-  const double* in = vec + (size_t)((it + 1) & 1) * sz;        // state written by launch it - 1 (it == 0: state 0 below)
-  double* out = vec + (size_t)(it & 1) * sz;
-  if (it == 0) {
-    in = vec;                                                  // k_cgs_init left r_0 = p_0 in state 0
-    for (int i = tid; i < NC * 512; i += 256) s_p[i] = i < n ? in[n + i] : 0.0;
-  } else {
-    const double *r = in, *pv = in + n, *Ap = in + 2 * n;
-    constexpr int PER = 2 * NC;
-    double rv[PER], pvv[PER], av[PER];
-    double pAp = 0.0;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int i = tid + 256 * q;
-      rv[q] = i < n ? r[i] : 0.0; pvv[q] = i < n ? pv[i] : 0.0; av[q] = i < n ? Ap[i] : 0.0;
-      pAp += pvv[q] * av[q];
-    }
-    pAp = block_sum256(pAp, s_red);
-    // ||r||^2 as workgroup 0 of the previous launch left it.  It writes the new value to the OTHER slot: workgroups of
-    // this launch that run later must still find the old one
-    const double rr_old = scal[CGS_RR_SLOT + ((it + 1) & 1)], rr0 = scal[CGS_RR0];
-    const bool done = rr_old <= rtol2 * rr0;
-    const bool broken = !done && !(pAp > 0.0);                 // non-positive curvature (or NaN): S~ is not positive definite
-    if (done || broken) {
-      // carry the state forward unchanged so that later launches of this batch see it again (and stop again)
-      if (blockIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < PER; ++q) { const int i = tid + 256 * q; if (i < n) { out[i] = rv[q]; out[n + i] = pvv[q]; out[2 * n + i] = av[q]; } }
-        if (tid == 0) { scal[CGS_RR_SLOT + (it & 1)] = rr_old; scal[CGS_DONE] = 1.0; if (broken) scal[CGS_FAIL] = 2.0; }
-      }
-      return;
-    }
-    const double a = rr_old / pAp;
-    double rr_new = 0.0;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) { rv[q] -= a * av[q]; rr_new += rv[q] * rv[q]; }
-    rr_new = block_sum256(rr_new, s_red);
-    const double beta = rr_new / rr_old;
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-      const int i = tid + 256 * q;
-      const double pn = rv[q] + beta * pvv[q];
-      s_p[i] = i < n ? pn : 0.0;
-      if (i < n && blockIdx.x == 0) { x[i] += a * pvv[q]; out[i] = rv[q]; out[n + i] = pn; }
-    }
-    if (blockIdx.x == 0 && tid == 0) { scal[CGS_RR_SLOT + (it & 1)] = rr_new; scal[CGS_RR] = rr_new; scal[CGS_ITER] = (double)it; }
-  }
-  __syncthreads();
-  double acc[ROWS];
-#pragma unroll
-  for (int q = 0; q < ROWS; ++q) acc[q] = 0.0;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const double p0 = s_p[2 * tid + 512 * c], p1 = s_p[2 * tid + 512 * c + 1];
-#pragma unroll
-    for (int q = 0; q < ROWS; ++q) acc[q] += sv[q][c].x * p0 + sv[q][c].y * p1;
-  }
-#pragma unroll
-  for (int q = 0; q < ROWS; ++q) {
-    const double t = wave_sum(acc[q]);
-    if (lane == 0) s_row[q][w] = t;
-  }
-  __syncthreads();
-  if (tid < ROWS && row0 + tid < n) out[2 * n + row0 + tid] = (s_row[tid][0] + s_row[tid][1]) + (s_row[tid][2] + s_row[tid][3]);
-}
-
-// ------------------------------------------------------------------------------------ persistent form of the same CG
-// ONE launch per system instead of one per iteration (k_cgs_iter above: ~7 us per iteration, of which the kernel boundary
-// and the re-read of S~ from L2 are most).  Workgroup b owns the PR_ROWS rows [8 b, 8 b + 8) of S~ and holds them IN
-// REGISTERS for the whole solve (thread t: the columns 2t + 512 c, c < NC -> 8 x NC x 2 doubles = 128 VGPRs at n = 2048:
-// the kernel runs one wave per SIMD), together with its columns of x, r, p.  Per iteration a workgroup multiplies its rows
-// with p (64 FMAs per thread, wave sums, four partials through LDS: fixed order), PUBLISHES its 8 entries of S~ p and
-// GATHERS all n of them: the all-gather is the only exchange between workgroups.  It uses self-validating 8-byte granules
-// (cdna_hip_programming.md, Guideline 16, form R2: {tag, 32-bit half of the double} written by ONE relaxed agent-scope
-// atomic store = global_store_dwordx2 sc1, polled with relaxed agent-scope atomic loads = sc1: no flag, no fence; a double
-// is two granules).  tag = salt (a per-launch counter: no hipGraph replay here) * 256 + iteration + 1, two slots by
-// iteration parity: a workgroup can be at most one iteration ahead of the slowest (its product of iteration i + 1 needs
-// every entry of iteration i), so when it overwrites slot i & 1 with iteration i + 2 everybody has read iteration i.
-// The vector recurrences and the two dot products are then computed REDUNDANTLY by every workgroup from identical data in
-// identical order (block sums), so all take the same branch at the same iteration and no second exchange is needed.
-// Placement-independent: nothing assumes a dispatch order or a workgroup -> XCD map; every spin is bounded, a workgroup that
-// gives up posts the launch's salt in the abort word, which the others poll beside their granules, and the host then takes
-// the per-launch kernel (and stops using this one for the handle: a grid that is not co-resident - CUs taken by another
-// process - would pay the timeout on every solve otherwise).
-// Diagnostic build only (-DSFM_CGS_STAMPS=1, tools/exp_cgs_phases.sh): per-iteration phase stamps of workgroup 0 / thread 0 of
-// k_cgs_persist on the 100 MHz constant clock.  The shipped library executes no stamp.
-#ifndef SFM_CGS_STAMPS
-#define SFM_CGS_STAMPS 0
-#endif
-#if SFM_CGS_STAMPS
-constexpr int CGS_STAMP_SLOTS = 1 << 16;
-__device__ unsigned long long g_cgs_stamps[CGS_STAMP_SLOTS];
-__device__ unsigned int g_cgs_stamp_pos;
-extern "C" int sfm_debug_cgs_stamps(unsigned long long* dst, int n_words, unsigned int* n_used) {
-  if (hipMemcpyFromSymbol(n_used, HIP_SYMBOL(g_cgs_stamp_pos), 4, 0, hipMemcpyDeviceToHost) != hipSuccess) return 1;
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_cgs_stamps), (size_t)n_words * 8, 0, hipMemcpyDeviceToHost);
-}
-// record (tag, time): tag 0 = launch start, 1 = rows in registers, 2 = product + wave sums done (publish), 3 = gather complete,
-// 4 = recurrences done (end of iteration), 5 = epilogue done
-#define CGS_STAMP(tag) do { if (stamp_on) { const unsigned q_ = atomicAdd(&g_cgs_stamp_pos, 2u); \
-    if (q_ + 1 < CGS_STAMP_SLOTS) { g_cgs_stamps[q_] = (tag); g_cgs_stamps[q_ + 1] = __builtin_amdgcn_s_memrealtime(); } } } while (0)
-#else
-#define CGS_STAMP(tag) do {} while (0)
-#endif
-constexpr int PR_ROWS = 8;
-constexpr unsigned PR_SPIN_LIMIT = 1u << 17;      // passes over a thread's granules (~1 us each) before giving up
-typedef unsigned long long pr_u64;
-#define PR_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-// What used to be separate 4-us launches around a system, folded into the persistent kernel (all optional):
-struct PrFuse {
-  const double* Einv;      // non-null: the right-hand side arrives UNSCALED and rhs~ = E^-1 (rhs + rhs_b) is formed in the prologue
-  const double* rhs_b;     //   second summand (system of the q term: p_c + W C_a^-1 p_p pieces), may be null
-  double* pc_out;          // non-null (step system): p_c = -E^-T x~ is written here by workgroup 0 on convergence
-  const double* fin_pc;    // non-null (q system): the scalars of the damped solve are finished here on convergence
-  const double* fin_redq;  //   [n + 2]: ... | sum ||p_p||^2 | sum ||v||^2
-  double* fin_sc;          //   SFM_SC_PNORM2, SFM_SC_PQ, SFM_SC_CHOL_FAIL
-  double* fin_hsc;         //   the same three in the problem's pinned host mirror of the scalars (sfm_ba_read_scalars)
-  int rhs_scaled;          // 1: `rhs` is rhs~ already (k_scale_system / k_block_mv formed it; Einv then only serves the epilogue).  Forming
-                           //    it in the prologue - every workgroup all n entries, ~200 eight-byte loads per thread - took 17-19 us per
-                           //    launch by in-kernel stamps, more than seven iterations
-  double fin_seq;          // (q system) the ticket sfm_ba_read_scalars waits for - published whatever the verdict: the host then looks at it
-};
-
-template <int NC, int D>
-__global__ __launch_bounds__(256, 1) void k_cgs_persist(int n, double rtol2, int max_iter, unsigned salt,
-                                                        const double* __restrict__ St, const double* __restrict__ rhs,
-                                                        double* __restrict__ x_out, pr_u64* mail /* [2][n][2] granules */,
-                                                        pr_u64* abort_w, double* __restrict__ scal, PrFuse f, int sabotage,
-                                                        double* __restrict__ host_status /* pinned host memory, device-mapped: 8 words */) {
-  __shared__ double s_part[PR_ROWS][4];
-  __shared__ double s_red[4];
-  __shared__ int s_ok[4];
-  __shared__ double s_x[PR_MAX_N];                  // workgroup 0, epilogue: x~ for the block-wise back-transformation
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int blk = (int)blockIdx.x;
-  // test hook (SFM_CGS_SABOTAGE=1): workgroup 1 never publishes, as if it had not become resident - the others must run into
-  // their spin bound, post the abort word and leave; the host then takes the launch-per-iteration route
-  if (sabotage > 0 && blk == 1) return;
-  const int row0 = blk * PR_ROWS;
-#if SFM_CGS_STAMPS
-  const bool stamp_on = blk == 0 && tid == 0;
-#endif
-  CGS_STAMP(0);
-  // this thread's slice of the workgroup's rows: registers for the whole solve
-  double2 sv[PR_ROWS][NC];
-#pragma unroll
-  for (int q = 0; q < PR_ROWS; ++q)
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int row = row0 + q, col = 2 * tid + 512 * c;            // n is even: col < n implies col + 1 < n
-      sv[q][c] = (row < n && col < n) ? *(const double2*)(St + (size_t)row * n + col) : make_double2(0.0, 0.0);
-    }
-  double xv[2 * NC], rv[2 * NC], pv[2 * NC], bv[2 * NC];     // bv: the right-hand side itself (the q system's r~ . x~)
-#if SFM_CGS_STAMPS
-  { double keep_ = 0.0;
-#pragma unroll
-    for (int q = 0; q < PR_ROWS; ++q) keep_ += sv[q][0].x;
-    asm volatile("" :: "v"(keep_)); }      // (the stamp below must not be scheduled ahead of the row loads)
-#endif
-  CGS_STAMP(1);
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int col = 2 * tid + 512 * c;
-    const bool in = col < n;
-    if (f.Einv && !f.rhs_scaled) {
-      // rhs~_i = sum_k E^-1[cam][a][k] (rhs + rhs_b)[cam D + k]   (E^-1 lower triangular: the stored zeros above cost nothing here)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        double t = 0.0;
-        if (in) {
-          const int i = col + u, cam = i / D, a = i - cam * D;
-          const double* e = f.Einv + (size_t)cam * D * D + a * D;
-          const double* r = rhs + cam * D;
-#pragma unroll
-          for (int k = 0; k < D; ++k) t += e[k] * (r[k] + (f.rhs_b ? f.rhs_b[cam * D + k] : 0.0));
-        }
-        rv[2 * c + u] = t;
-      }
-    } else {
-      rv[2 * c] = in ? rhs[col] : 0.0; rv[2 * c + 1] = in ? rhs[col + 1] : 0.0;
-    }
-    bv[2 * c] = rv[2 * c]; bv[2 * c + 1] = rv[2 * c + 1];
-    xv[2 * c] = 0.0; xv[2 * c + 1] = 0.0;
-  }
-  double rr0;
-  {
-    double t = 0.0;
-#pragma unroll
-    for (int i = 0; i < 2 * NC; ++i) t += rv[i] * rv[i];
-    rr0 = block_sum256_fast(t, s_red);                 // ||rhs||^2 (every thread gets it): the tolerance is relative to the right-hand side
-  }
-
-  // one round: y = S~ v for this workgroup's rows, published and gathered; returns false when the launch is abandoned
-  double yv[2 * NC];
-  // (dot: v . y over the whole vector, in every thread - its four wave parts travel through LDS together with the waves'
-  // verdicts on the gather, one barrier pair for both; meaningless when the round is abandoned)
-  auto exchange = [&](const double (&v)[2 * NC], int round, double& dot) -> bool {
-    double acc[PR_ROWS];
-#pragma unroll
-    for (int q = 0; q < PR_ROWS; ++q) {
-      double t = 0.0;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) t += sv[q][c].x * v[2 * c] + sv[q][c].y * v[2 * c + 1];
-      acc[q] = t;
-    }
-    // the eight row sums over the wave by ONE halving exchange (lane_rows8_sum: 10 additions and 22 cross-lane moves) instead of
-    // eight full wave sums (48 and 96): in-kernel stamps put "product + wave sums" at 1.8 us of a 5.1-us iteration at n = 2,000
-    // (one wave per SIMD: every dependent step of the reduction is exposed)
-    {
-      const double t = lane_rows8_sum(acc, lane);
-      if ((lane & 7) == 0) s_part[((lane >> 5) << 2) | (((lane >> 4) & 1) << 1) | ((lane >> 3) & 1)][w] = t;
-    }
-    __syncthreads();
-    CGS_STAMP(2);
-    const unsigned tag = salt * 256u + (unsigned)round + 1u;
-    pr_u64* slot = mail + (size_t)(round & 1) * 2 * n;
-    if (tid < PR_ROWS && row0 + tid < n) {
-      const double y = (s_part[tid][0] + s_part[tid][1]) + (s_part[tid][2] + s_part[tid][3]);
-      const pr_u64 bits = (pr_u64)__double_as_longlong(y);
-      // the two granules of the entry in ONE 16-byte device-scope store (the workgroup's eight entries = one whole 128-byte line
-      // from one instruction); each 8-byte half carries its own tag, so the store need not be atomic as a whole
-      typedef unsigned pr_st4 __attribute__((ext_vector_type(4)));
-      const pr_st4 pk = {(unsigned)(bits & 0xFFFFFFFFull), tag, (unsigned)(bits >> 32), tag};
-      asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(slot + 2 * (size_t)(row0 + tid)), "v"(pk) : "memory");
-    }
-    // gather this thread's columns: 4 granules per chunk (two doubles), re-read until every tag matches
-    // ... but not at once: nothing can have arrived before the slowest workgroup's store has crossed the fabric, and a pass that
-    // comes too early is not free - 250 workgroups x 32 KB of L1-bypassing loads compete with the very stores they wait for,
-    // and the lines they pull are invalidated again a moment later.  In-kernel stamps (tools/exp_cgs_phases.sh, n = 2,000):
-    // publish -> gather complete 2.83 us polling at once, 1.78 with s_sleep 8 (x 64 clocks) in front, 1.56-1.59 with 24, 1.91
-    // with 40, 2.57 with 64; n = 500 (63 workgroups, one chunk per thread): 0.98 at once, 1.08 with 8, 1.31 with 24.
-    constexpr int FIRST_SLEEP = NC == 1 ? 0 : 6 * NC - 4;          // 8 / 14 / 20 for two / three / four chunks per thread
-    if (FIRST_SLEEP > 0) __builtin_amdgcn_s_sleep(FIRST_SLEEP);
-    bool ok = false;
-    for (unsigned spins = 0; spins < PR_SPIN_LIMIT; ++spins) {
-      pr_u64 g[4 * NC];
-      // a thread's four granules of a chunk (two doubles) are 32 contiguous, 32-byte aligned bytes: TWO 16-byte device-scope loads
-      // instead of four 8-byte ones (8-byte accesses run at 0.54-0.70 of the 16-byte rate, MI355X_MICROARCH.md).  Every 8-byte
-      // half carries its own tag, so a 16-byte load that saw its two halves at different times is still read correctly.  The
-      // compiler does not see these loads: the wait below is theirs.
-      typedef unsigned pr_u32x4 __attribute__((ext_vector_type(4)));
-      pr_u32x4 q[2 * NC];
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int col = 2 * tid + 512 * c;
-        const pr_u64* gp = slot + 2 * (size_t)(col < n ? col : 0);
-        asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(q[2 * c]) : "v"(gp) : "memory");
-        asm volatile("global_load_dwordx4 %0, %1, off offset:16 sc1" : "=v"(q[2 * c + 1]) : "v"(gp) : "memory");
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int c = 0; c < 2 * NC; ++c) {
-        // (the wait must sit between the loads and the first use of ANY of their registers: tie them to it)
-        asm volatile("" : "+v"(q[c]));
-        g[2 * c] = (pr_u64)q[c].x | ((pr_u64)q[c].y << 32);
-        g[2 * c + 1] = (pr_u64)q[c].z | ((pr_u64)q[c].w << 32);
-      }
-      bool all = true;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const bool in = 2 * tid + 512 * c < n;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) all &= !in || (unsigned)(g[4 * c + i] >> 32) == tag;
-        yv[2 * c] = in ? __longlong_as_double((long long)((g[4 * c] & 0xFFFFFFFFull) | (g[4 * c + 1] << 32))) : 0.0;
-        yv[2 * c + 1] = in ? __longlong_as_double((long long)((g[4 * c + 2] & 0xFFFFFFFFull) | (g[4 * c + 3] << 32))) : 0.0;
-      }
-      if (__all(all)) { ok = true; break; }
-      if ((spins & 31u) == 31u && __hip_atomic_load(abort_w, PR_RLX_AGENT) == (pr_u64)salt) break;     // somebody gave up
-      __builtin_amdgcn_s_sleep(2);                    // (polling without the sleep measured the same: 135.1 / 100.1 us per system)
-    }
-    CGS_STAMP(3);
-    double td = 0.0;
-#pragma unroll
-    for (int i = 0; i < 2 * NC; ++i) td += v[i] * yv[i];
-    td = wave_sum_all(td);
-    // (s_red / s_ok were last READ before the barrier above - the one behind the s_part writes - so they can be written here
-    // without another one in front; their next writer, the block sum of r . r, starts with a barrier of its own)
-    if (lane == 0) { s_red[w] = td; s_ok[w] = ok ? 1 : 0; }
-    __syncthreads();
-    const bool all_ok = (s_ok[0] & s_ok[1] & s_ok[2] & s_ok[3]) != 0;
-    dot = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-    if (!all_ok && tid == 0) __hip_atomic_store(abort_w, (pr_u64)salt, PR_RLX_AGENT);
-    return all_ok;
-  };
-  // done: 1 = the recurrence ended (converged, or broken: fail 2), 0 = out of iterations, -1 = the launch was abandoned.
-  // CGS_FAIL may already hold k_diag_einv's 1 (a diagonal block is not positive definite): it is only ever raised here.
-  auto finish = [&](double rr, int it, double done, double fail) {
-    if (blk != 0) return;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const int col = 2 * tid + 512 * c;
-      if (col < n) { x_out[col] = xv[2 * c]; x_out[col + 1] = xv[2 * c + 1]; }
-    }
-    if (tid == 0) {
-      scal[CGS_RR0] = rr0; scal[CGS_RR] = rr; scal[CGS_ITER] = (double)it; scal[CGS_DONE] = done;
-      const double fail_now = scal[CGS_FAIL] != 0.0 ? scal[CGS_FAIL] : fail;
-      if (fail != 0.0 && scal[CGS_FAIL] == 0.0) scal[CGS_FAIL] = fail;
-      // the host's copy of the verdict, written straight into its pinned page (visible when the launch has ended: an event
-      // behind the launch is all the host waits for) - a separate 64-byte device-to-host copy is a blit kernel of its own, ~4 us
-      // plus two kernel boundaries between this system and the back-substitution that waits behind it
-      host_status[CGS_RR0] = rr0; host_status[CGS_RR] = rr; host_status[CGS_ITER] = (double)it;
-      host_status[CGS_FAIL] = fail_now; host_status[CGS_DONE] = done;
-    }
-    const bool converged = done == 1.0 && fail == 0.0 && rr <= rtol2 * rr0;
-    if (!converged && f.fin_sc && tid == 0) publish_ticket(f.fin_hsc, f.fin_seq);      // (no scalars: the verdict is what the host finds)
-    if (!converged || !(f.pc_out || f.fin_sc)) return;          // (workgroup-uniform)
-    if (f.pc_out) {
-      // p_c = -E^-T x~: entry (cam, a) needs the whole x~ block of its camera -> through LDS
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int col = 2 * tid + 512 * c;
-        if (col < n) { s_x[col] = xv[2 * c]; s_x[col + 1] = xv[2 * c + 1]; }
-      }
-      __syncthreads();
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int col = 2 * tid + 512 * c;
-        if (col < n) {
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            const int i = col + u, cam = i / D, a = i - cam * D;
-            const double* e = f.Einv + (size_t)cam * D * D;
-            double t = 0.0;
-#pragma unroll
-            for (int k = 0; k < D; ++k) t += e[k * D + a] * s_x[cam * D + k];
-            f.pc_out[i] = -t;
-          }
-        }
-      }
-    }
-    if (f.fin_sc) {
-      // the scalars of the damped solve (k_finish_solve_pcg): p^T (H + alpha I)^-1 p = rhs2~ . x~2 + sum ||v||^2
-      double t = 0.0, t2 = 0.0;
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int col = 2 * tid + 512 * c;
-        if (col < n) {
-          t += bv[2 * c] * xv[2 * c] + bv[2 * c + 1] * xv[2 * c + 1];
-          const double p0 = f.fin_pc[col], p1 = f.fin_pc[col + 1];
-          t2 += p0 * p0 + p1 * p1;
-        }
-      }
-      const double dot = block_sum256_fast(t, s_red);
-      const double pc2 = block_sum256_fast(t2, s_red);
-      if (tid == 0) {
-        const double pn2 = pc2 + f.fin_redq[n], pq = dot + f.fin_redq[n + 1];
-        f.fin_sc[SFM_SC_PNORM2] = f.fin_hsc[SFM_SC_PNORM2] = pn2; f.fin_sc[SFM_SC_PQ] = f.fin_hsc[SFM_SC_PQ] = pq;
-        double fl = scal[CGS_FAIL] != 0.0 ? 1.0 : 0.0;
-        if (fl == 0.0 && !(isfinite(pn2) && isfinite(pq))) fl = 3.0;
-        f.fin_sc[SFM_SC_CHOL_FAIL] = f.fin_hsc[SFM_SC_CHOL_FAIL] = fl;
-        publish_ticket(f.fin_hsc, f.fin_seq);
-      }
-    }
-  };
-
-  int round = 0;
-  double rr = rr0;                                  // x = 0: r = p = rhs
-#pragma unroll
-  for (int i = 0; i < 2 * NC; ++i) pv[i] = rv[i];
-  if (!(rr0 > 0.0)) {                               // zero right-hand side: x = 0; NaN / Inf in it: not a system CG can solve (fail 2 ->
-    if (rr0 == 0.0) finish(0.0, 0, 1.0, 0.0);       // the caller's factorisation route reports the non-finite step)
-    else finish(rr0, 0, 1.0, 2.0);
-    return;
-  }
-  int it = 0;
-  for (; it < max_iter; ++it) {
-    if (rr <= rtol2 * rr0) { finish(rr, it, 1.0, 0.0); return; }
-    double pAp;
-    if (!exchange(pv, round++, pAp)) { finish(rr, it, -1.0, 0.0); return; }
-    if (!(pAp > 0.0)) { finish(rr, it, 1.0, 2.0); return; }       // non-positive curvature (or NaN): S~ is not positive definite
-    const double a = rr / pAp;
-    double t2 = 0.0;
-#pragma unroll
-    for (int i = 0; i < 2 * NC; ++i) { xv[i] += a * pv[i]; rv[i] -= a * yv[i]; t2 += rv[i] * rv[i]; }
-    const double rr_new = block_sum256_fast(t2, s_red);
-    const double beta = rr_new / rr;
-#pragma unroll
-    for (int i = 0; i < 2 * NC; ++i) pv[i] = rv[i] + beta * pv[i];
-    rr = rr_new;
-    CGS_STAMP(4);
-  }
-  finish(rr, it, rr <= rtol2 * rr0 ? 1.0 : 0.0, 0.0);
-}
-
-// One persistent launch for a system (k_cgs_persist), in two halves so that the host never idles the GPU on its status:
-// cgs_persist_launch enqueues the kernel and the copy of its 8 status words into pinned memory (slot pin: SFM_PIN_CG1 /
-// the problem's own slot for the second system) (which systems take it: cam_plan);
-// cgs_persist_status interprets the copy once the caller knows it has arrived (an event behind it, or a later stream
-// synchronisation).  *ran = 0: the launch was abandoned - the caller takes the launch-per-iteration route (cgs_solve) with its
-// separate pre / post kernels; *status = 0: converged (and whatever `fuse` asked for has been done by workgroup 0).
-// The salt of a launch's granule tags comes from ONE process-wide counter (24 bits, never 0 = what cleared memory reads as),
-// started from the clock: a handle that is destroyed and created again, or two handles sharing a workspace over time, can never
-// replay a salt whose granules still sit in a mailbox (a per-handle counter restarting at 1 could: the reader would then take
-// stale entries for fresh ones - silently).  sfm_ba_bind_workspace clears the mailbox of a caller-owned workspace besides.
-static unsigned cgs_next_salt() {
-  static std::atomic<unsigned> seq{(unsigned)(std::chrono::steady_clock::now().time_since_epoch().count() >> 10)};
-  unsigned s;
-  do { s = (seq.fetch_add(1u, std::memory_order_relaxed) + 1u) & 0xFFFFFFu; } while (s == 0u);
-  return s;
-}
-struct PrLaunch {      // everything a (re)launch of one system needs
-  int n, D; const double* St; const double* rhs; double* x_t; double* mail; double* scal; double rtol; PrFuse fuse;
-  double* pin;         // pinned host words the kernel writes its verdict to
-};
-static int cgs_persist_launch(sfm_ctx* h, const PrLaunch& a) {
-  const int n = a.n, D = a.D;
-  const unsigned grid = (unsigned)cdiv(n, PR_ROWS);
-  const int nc = (int)cdiv(n, 512);
-  pr_u64* abort_w = (pr_u64*)(a.scal + 12);
-  const unsigned salt = cgs_next_salt();
-  const double rtol2 = a.rtol * a.rtol;
-  const int sabotage = (getenv("SFM_CGS_SABOTAGE") && getenv("SFM_CGS_SABOTAGE")[0] == '1' && grid > 1) ? 1 : 0;
-  a.pin[CGS_DONE] = -1.0;                          // what a launch that never wrote its verdict reads as: abandoned
-#define PR_LAUNCH(NC, DD_) hipLaunchKernelGGL((k_cgs_persist<NC, DD_>), dim3(grid), dim3(256), 0, h->stream, n, rtol2, CGS_MAX_ITER, salt, a.St, a.rhs, a.x_t, (pr_u64*)a.mail, abort_w, a.scal, a.fuse, sabotage, a.pin)
-  if (D == 10) { if (nc <= 1) PR_LAUNCH(1, 10); else if (nc == 2) PR_LAUNCH(2, 10); else if (nc == 3) PR_LAUNCH(3, 10); else PR_LAUNCH(4, 10); }
-  else { if (nc <= 1) PR_LAUNCH(1, 6); else if (nc == 2) PR_LAUNCH(2, 6); else if (nc == 3) PR_LAUNCH(3, 6); else PR_LAUNCH(4, 6); }
-#undef PR_LAUNCH
-  SFM_LAUNCH_CHECK(h, "cgs_persist_launch");
-  return SFM_OK;
-}
-static void cgs_persist_read(const double* st, int* iters_out, int* status, int* ran) {
-  *ran = 0; *status = 1;
-  if (st[CGS_DONE] == -1.0) return;                 // the launch was abandoned (a spin ran out)
-  *ran = 1;
-  *iters_out += (int)st[CGS_ITER];
-  if (st[CGS_FAIL] == 0.0 && st[CGS_DONE] != 0.0) *status = 0;
-}
-// The verdict of a launch has arrived (an event or a stream synchronisation behind it).  An abandoned launch is dealt with here:
-//   * `sharded` (the problem is one rank's shard): every rank must take the SAME route through the camera solve - the
-//     launch-per-iteration kernel sums in another order, and a rank that switched on its own would hold a replicated camera step
-//     that differs from its peers' in the last bits and, sooner or later, a different trial history and a different sequence of
-//     collectives.  So: the same kernel again, up to CGS_SHARDED_RETRIES times, then the solve fails loudly;
-//   * otherwise: *ran = 0, the handle stops using the persistent kernel and the caller takes the launch-per-iteration route.
-// *relaunched tells the caller that work enqueued behind the first launch on the assumption that it converged must be redone.
-constexpr int CGS_SHARDED_RETRIES = 3;
-static int cgs_persist_verdict(sfm_ctx* h, const PrLaunch& a, int sharded, int* iters_out, int* status, int* ran, int* relaunched) {
-  *relaunched = 0;
-  cgs_persist_read(a.pin, iters_out, status, ran);
-  if (*ran) return SFM_OK;
-  auto again = [&]() -> int {
-    *relaunched = 1;
-    SFM_HIP(h, hipMemsetAsync(a.scal, 0, CG_SCAL_WORDS * sizeof(double), h->stream));
-    int rc = cgs_persist_launch(h, a); if (rc) return rc;
-    SFM_HIP(h, hipStreamSynchronize(h->stream));
-    cgs_persist_read(a.pin, iters_out, status, ran);
-    return SFM_OK;
-  };
-  if (sharded) {
-    for (int attempt = 1; attempt <= CGS_SHARDED_RETRIES && !*ran; ++attempt) {
-      fprintf(stderr, "sfm_amd: the persistent CG launch of a sharded solve was abandoned; launching it again (%d of %d)\n", attempt, CGS_SHARDED_RETRIES);
-      int rc = again(); if (rc) return rc;
-    }
-    if (!*ran)
-      return sfm_fail(h, SFM_ERR_HIP, "camera CG",
-                      "the persistent kernel could not run on this rank (its grid was not co-resident) and a sharded solve must take the "
-                      "same route on every rank: set SFM_CGS_PERSIST=0 on ALL ranks");
-    return SFM_OK;
-  }
-  h->cgs_persist_off = 1;
-  fprintf(stderr, "sfm_amd: the persistent CG launch was abandoned (grid not co-resident?); using one launch per iteration from now on\n");
-  return SFM_OK;
-}
-
-// x~ = S~^-1 rhs~ by CG, one launch per iteration (k_cgs_iter); returns 0 converged / 1 not converged or broken (caller falls
-// back to the factorisation)
-static int cgs_solve(sfm_ctx* h, int n, const double* St, const double* rhs_t, double* x_t, double* vec, double* scal,
-                     double rtol, int* iters_out, int* status) {
-  const double rtol2 = rtol * rtol;
-  *status = 1;
-  // (column chunks per thread, rows per workgroup): 128 registers of prefetched matrix per thread in the two larger shapes
-  // four rows per workgroup: at n = 2000 that is 512 workgroups (two per CU) - 8 rows / 256 workgroups measured 6 % slower per
-  // iteration, 2 rows / 1,024 workgroups 9 % slower (twice the redundant vector work).
-  constexpr int ROWS = 4;
-  const unsigned grid = 8u * (unsigned)cdiv(cdiv(n, 8), ROWS);
-  hipLaunchKernelGGL(k_cgs_init, dim3(1), dim3(256), 0, h->stream, n, rhs_t, x_t, vec, vec + n, scal);
-  int it = 0;
-  int batch = 13;                                                  // launch 0 only multiplies: first look after 12 iterations
-  while (it <= CGS_MAX_ITER) {
-    for (int b = 0; b < batch; ++b, ++it)
-      if (n <= 1024) hipLaunchKernelGGL((k_cgs_iter<2, ROWS>), dim3(grid), dim3(256), 0, h->stream, n, it, rtol2, St, vec, x_t, scal);
-      else if (n <= 2048) hipLaunchKernelGGL((k_cgs_iter<4, ROWS>), dim3(grid), dim3(256), 0, h->stream, n, it, rtol2, St, vec, x_t, scal);
-      else hipLaunchKernelGGL((k_cgs_iter<8, ROWS>), dim3(grid), dim3(256), 0, h->stream, n, it, rtol2, St, vec, x_t, scal);
-    SFM_HIP(h, hipMemcpyAsync(h->pinned, scal, 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    SFM_HIP(h, hipStreamSynchronize(h->stream));
-    if (h->pinned[CGS_FAIL] != 0.0) break;
-    const double rr = h->pinned[CGS_RR], rr0 = h->pinned[CGS_RR0];
-    if (h->pinned[CGS_DONE] != 0.0 || rr <= rtol2 * rr0) { *status = 0; break; }
-    // next look where the residual should be small enough, from the average rate so far (CG on these systems converges
-    // close to linearly): every look costs a stream synchronisation, every launch past convergence ~4 us
-    const double done_its = h->pinned[CGS_ITER] > 1.0 ? h->pinned[CGS_ITER] : 1.0;
-    const double rate = std::log(rr / rr0) / done_its;               // < 0 when converging
-    batch = 8;
-    if (rate < -1e-3 && rr > 0.0) {
-      const double need = std::log(rtol2 * rr0 / rr) / rate;
-      batch = need < 2.0 ? 2 : (need > 32.0 ? 32 : (int)need + 2);
-    }
-  }
-  *iters_out += (int)h->pinned[CGS_ITER];
-  SFM_LAUNCH_CHECK(h, "cgs_solve");
-  return SFM_OK;
-}
-
-// ------------------------------------------------------------------------------------ the same CG for large systems
-// n > 2,048 (1000 cameras: n = 10,000, S~ = 800 MB).  Little of S~ stays in a cache between iterations, so an iteration is
-// a stream over the matrix and what counts is how many bytes of it are read: S~ is symmetric, and a 128 x 128 tile (I, J),
-// J < I, of its lower triangle serves BOTH products it takes part in - rows I of S~ p get A_IJ p_J, rows J get A_IJ^T p_I -
-// so an iteration reads n^2 / 2 entries (414 MB at n = 10,000 against 800 MB; the factorisation it replaces: 14 ms per damped
-// solve, ~50 iterations of this per system).  One workgroup per tile (3,160 at n = 10,000); wave w owns 32 of its rows, a lane
-// two of its columns (one 16-byte load per row and lane: a row of the tile is one contiguous KiB).  The column sums stay in
-// the lane (two accumulators over the wave's rows, the four waves added in fixed order through LDS); the row sums of 16 rows
-// at a time are reduced over the 64 lanes by a halving exchange (lane_rows16_sum: 15 + 2 shuffles instead of 16 x 6).  Every
-// tile writes its partial sums to a slot of its own, P[k][i] with k = J for the row sums of (I, J) and k = I for its column
-// sums - each (k, i) is written exactly once per iteration - and k_cgs_big_reduce adds the nb = ceil(n / 128) slots of an
-// entry in fixed order: no atomics, bitwise reproducible.  The recurrences run in ONE workgroup (k_cgs_big_update: 5 vectors
-// of n doubles, ~6 us); three launches per iteration, ~15 us of them around the ~75 us stream.  State in the factor's
-// transposed-copy buffer (free on this route): r | p | S~p | dots[nb] | P[nb][n].
-constexpr int SY_T = 128;
-
-// v[q] = this lane's part of the sum of row q; returns (in every lane) the sum over the 64 lanes of row (lane >> 2)
-__device__ __forceinline__ double lane_rows16_sum(double (&v)[16], int lane) {
-  // halving exchanges without LDS round trips (the ds_bpermute form of this function, 17 dependent shuffles per call, was
-  // ~0.8 us at the end of every 16-row batch of a tile): across the half-waves and across neighbouring rows by
-  // v_permlane32_swap / v_permlane16_swap, inside a row of 16 lanes by row / half-row mirrors (DPP)
-  double u[8], x[4];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) u[k] = swap32_add(v[k], v[k + 8]);        // upper half keeps rows + 8
-#pragma unroll
-  for (int k = 0; k < 4; ++k) x[k] = swap16_add(u[k], u[k + 4]);        // odd rows of 16 lanes keep rows + 4
-  double y[2];
-  {
-    const bool hi = (lane & 8) != 0;                                    // lanes 8..15 of a row keep rows + 2
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const double send = hi ? x[k] : x[k + 2], keep = hi ? x[k + 2] : x[k];
-      y[k] = keep + dpp_f64<0x140>(send);                               // row_mirror: lane i <-> lane 15 - i
-    }
-  }
-  double t;
-  {
-    const bool hi = (lane & 4) != 0;                                    // bit 2 keeps rows + 1
-    const double send = hi ? y[0] : y[1], keep = hi ? y[1] : y[0];
-    t = keep + dpp_f64<0x141>(send);                                    // row_half_mirror: lane i <-> lane 7 - i of its eight
-  }
-  t += dpp_f64<0xB1>(t);                                                // the four lanes of a quad
-  t += dpp_f64<0x4E>(t);
-  return t;
-}
-
-// The recurrences in the Chronopoulos - Gear arrangement, which needs ONE global reduction point per iteration (gamma = r.r and
-// delta = (S~ r).r, both from the product that has just been formed) where the textbook form has two (p.S~p, then r'.r'):
-//     beta = gamma / gamma_prev;  alpha = gamma / (delta - beta gamma / alpha_prev)
-//     p = r + beta p;  s = w + beta s  (= S~ p);  x += alpha p;  r -= alpha s;  w = S~ r
-// So an iteration is TWO launches: the tile kernel - whose prologue sums the per-block dot products of the previous launch (every
-// tile the same 2 nb numbers in the same order: identical scalars everywhere, no broadcast), forms the new r on its own two
-// 128-entry ranges in LDS and multiplies - and the slot reduction, which also leaves the two dot products per block.  The third
-// launch of the first form (a single workgroup running the vector updates over all n entries: 13 us of a ~100-us iteration at
-// n = 10,000, plus its boundary) is gone: the DIAGONAL tile of a range writes that range's r, p, s, x, into the other of two
-// buffer sets (the off-diagonal tiles of the same launch still read the old ones).  Convergence is seen one launch late - the
-// launch whose prologue finds gamma <= rtol^2 gamma_0 copies x out and multiplies nothing.
-// State in the factor's transposed-copy buffer (free on this route): [2][r | p | s | x] | w | dots[2][nbp] | P[nb][n].
-enum { CGB_PAIR = 5 };     // scal[5 + 2 (it & 1)], scal[6 + 2 (it & 1)]: alpha and gamma of launch `it`, read by launch it + 1
-__global__ __launch_bounds__(256) void k_cgb_init(int n, int nbp, const double* __restrict__ rhs, double* __restrict__ vec,
-                                                  double* __restrict__ dots, double* __restrict__ scal) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) {
-    vec[i] = rhs[i];                                                                  // r_0 (set 0)
-    vec[(size_t)1 * n + i] = 0.0; vec[(size_t)2 * n + i] = 0.0; vec[(size_t)3 * n + i] = 0.0;     // p, s (times beta = 0 in launch 1), x_0
-  }
-  if (i < 2 * nbp) dots[i] = 0.0;
-  if (i == 0) { scal[CGS_RR0] = 0.0; scal[CGS_RR] = 0.0; scal[CGS_ITER] = 0.0; scal[CGS_DONE] = 0.0; scal[5] = scal[6] = scal[7] = scal[8] = 0.0; }
-}
-__global__ __launch_bounds__(256) void k_cgb_symv(int n, int nb, int nbp, int it, double rtol2, const double* __restrict__ St,
-                                                  double* __restrict__ vec, const double* __restrict__ wv, const double* __restrict__ dots,
-                                                  double* __restrict__ P, double* __restrict__ scal, double* __restrict__ x_out, int flip,
-                                                  double* __restrict__ hst /* pinned host words */, double seq) {
-  // CGS_DONE holds 1 + the index of the launch that saw the end (converged or broken).  Only an EARLIER launch's verdict stops
-  // this one: the tiles of the deciding launch itself all reach the same verdict from the same numbers, and each still has its
-  // range of x to copy out - a tile that started late must not take tile 0's freshly written flag for yesterday's
-  { const double dn = scal[CGS_DONE]; if (dn != 0.0 && dn <= (double)it) return; }
-  __shared__ double s_r[2][SY_T];                   // the new r on the tile's row range (I) and column range (J)
-  __shared__ double s_col[4][SY_T];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  // t -> (I, J), J <= I: I = floor((sqrt(8 t + 1) - 1) / 2), corrected for the rounding of the root
-  const int t = flip ? (int)(gridDim.x - 1u - blockIdx.x) : (int)blockIdx.x;
-  int I = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-  while ((I + 1) * (I + 2) / 2 <= t) ++I;
-  while (I * (I + 1) / 2 > t) --I;
-  const int J = t - I * (I + 1) / 2;
-  const int r0 = I * SY_T, c0 = J * SY_T;
-  const size_t N4 = (size_t)4 * n;
-  double* cur = vec + (size_t)((it + 1) & 1) * N4;     // launch it - 1 left r_{it-1}, p_{it-2}, s_{it-2}, x_{it-1} here (it = 0: unused)
-  double* nxt = vec + (size_t)(it & 1) * N4;           // launch 0 reads r_0 from set 0
-  // Loads return in issue order.  The few small ones the prologue needs (the dot products, the scalars, this thread's entries of
-  // r, s, w, p, x) therefore go FIRST and the 32 matrix loads per thread behind them: the prologue's arithmetic then runs while
-  // the tile streams in.  (With the matrix loads in front, every small load waited for all of them and the launch was 10 us
-  // longer than the plain product it replaces: 70.8 against 61.2 us at n = 10,000.)
-  const int half = tid >> 7, li = tid & 127;        // threads 0..127: range I, 128..255: range J
-  const int gi = (half ? c0 : r0) + li;
-  const bool own = I == J && half == 0;             // the range's diagonal tile keeps the vectors
-  double g = 0.0, dl = 0.0, g_prev = 0.0, a_prev = 0.0, g0s = 0.0;
-  double v_r = 0.0, v_s = 0.0, v_w = 0.0, v_p = 0.0, v_x = 0.0;
-  if (it == 0) {
-    v_r = gi < n ? nxt[gi] : 0.0;
-  } else {
-    for (int bb = lane; bb < nb; bb += 64) { g += dots[bb]; dl += dots[nbp + bb]; }
-    g_prev = scal[CGB_PAIR + 1 + 2 * ((it + 1) & 1)]; a_prev = scal[CGB_PAIR + 2 * ((it + 1) & 1)]; g0s = scal[CGS_RR0];
-    if (gi < n) {
-      v_r = cur[gi]; v_s = cur[(size_t)2 * n + gi]; v_w = wv[gi];
-      if (own) { v_p = cur[(size_t)n + gi]; v_x = cur[(size_t)3 * n + gi]; }
-    }
-  }
-  const int jc = c0 + 2 * lane;                     // n is even: jc < n implies jc + 1 < n
-  const bool col_ok = jc < n;
-  double2 a[2][16];
-#pragma unroll
-  for (int b = 0; b < 2; ++b)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const int row = r0 + w * 32 + b * 16 + q;
-      a[b][q] = (col_ok && row < n) ? *(const double2*)(St + (size_t)row * n + jc) : make_double2(0.0, 0.0);
-    }
-  if (it == 0) {
-    s_r[half][li] = v_r;
-  } else {
-    // gamma_{it-1}, delta_{it-1}: the per-block parts, summed by every wave of every tile in the same order
-    g = wave_sum_all(g); dl = wave_sum_all(dl);
-    const double g0 = it == 1 ? g : g0s;
-    const bool converged = g <= rtol2 * g0;          // (a zero right-hand side: 0 <= 0, x = 0)
-    const double beta = it == 1 ? 0.0 : g / g_prev;
-    const double den = it == 1 ? dl : dl - beta * g / a_prev;
-    const bool broken = !converged && !(den > 0.0);  // non-positive curvature, or NaN anywhere: S~ is not positive definite
-    if (t == 0 && tid == 0) {
-      if (it == 1) scal[CGS_RR0] = g;
-      scal[CGS_RR] = g; scal[CGS_ITER] = (double)(it - 1);
-      if (converged || broken) scal[CGS_DONE] = (double)(it + 1);
-      if (broken) scal[CGS_FAIL] = 2.0;
-      // the host's copy, straight into its pinned page: where the solve stands (every launch) and, from the launch that sees the
-      // end, the verdict with the system's ticket behind it - cgs_solve_big spins on the ticket and goes on enqueuing while the
-      // launches it had queued blind behind this one are still returning
-      const double fl = broken ? 2.0 : scal[CGS_FAIL];
-      hst[CGS_RR0] = g0; hst[CGS_RR] = g; hst[CGS_ITER] = (double)(it - 1); hst[CGS_FAIL] = fl;
-      if (converged || broken) {
-        hst[CGS_DONE] = (double)(it + 1);
-        publish_word(hst + 7, seq);
-      }
-    }
-    if (converged) {                                 // (uniform over the whole grid) x_{it-1} is the answer
-      if (own && gi < n) x_out[gi] = v_x;
-      return;
-    }
-    if (broken) return;
-    const double al = g / den;
-    if (t == 0 && tid == 0) { scal[CGB_PAIR + 2 * (it & 1)] = al; scal[CGB_PAIR + 1 + 2 * (it & 1)] = g; }
-    double rn = 0.0;
-    if (gi < n) {
-      const double sn = v_w + beta * v_s;
-      rn = v_r - al * sn;
-      if (own) {
-        const double pn = v_r + beta * v_p;
-        nxt[gi] = rn; nxt[(size_t)n + gi] = pn; nxt[(size_t)2 * n + gi] = sn; nxt[(size_t)3 * n + gi] = v_x + al * pn;
-      }
-    }
-    s_r[half][li] = rn;
-  }
-  __syncthreads();
-  const double pj0 = col_ok ? s_r[1][2 * lane] : 0.0, pj1 = col_ok ? s_r[1][2 * lane + 1] : 0.0;
-  double cs0 = 0.0, cs1 = 0.0;
-#pragma unroll
-  for (int b = 0; b < 2; ++b) {
-    double v[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      const double pi = s_r[0][w * 32 + b * 16 + q];
-      v[q] = a[b][q].x * pj0 + a[b][q].y * pj1;
-      cs0 += a[b][q].x * pi; cs1 += a[b][q].y * pi;
-    }
-    const double rs = lane_rows16_sum(v, lane);
-    const int row = r0 + w * 32 + b * 16 + (lane >> 2);
-    if ((lane & 3) == 0 && row < n) P[(size_t)J * n + row] = rs;
-  }
-  if (I != J) {                                      // (workgroup-uniform) the diagonal tile is stored whole: row sums only
-    s_col[w][2 * lane] = cs0; s_col[w][2 * lane + 1] = cs1;
-    __syncthreads();
-    if (tid < SY_T && c0 + tid < n) P[(size_t)I * n + c0 + tid] = (s_col[0][tid] + s_col[1][tid]) + (s_col[2][tid] + s_col[3][tid]);
-  }
-}
-// w = S~ r = sum over the nb slots (fixed order); the block's parts of gamma = r.r and delta = w.r.  One workgroup of 128 per
-// block of 128 entries.  r is the one launch `it` of the tile kernel has just formed (set it & 1).
-__global__ __launch_bounds__(128) void k_cgb_reduce(int n, int nb, int nbp, int it, const double* __restrict__ P, const double* __restrict__ vec,
-                                                    double* __restrict__ wv, double* __restrict__ dots, const double* __restrict__ scal) {
-  if (scal[CGS_DONE] != 0.0) return;
-  __shared__ double s_w[2][2];
-  const int i = (int)blockIdx.x * SY_T + threadIdx.x;
-  const double* r = vec + (size_t)(it & 1) * 4 * n;
-  double sum = 0.0, ri = 0.0;
-  if (i < n) {
-    ri = r[i];
-    // 79 slots at n = 10,000 and only 79 workgroups: the launch is as long as a thread's chain of loads.  32 of them in flight
-    // at a time (the additions in slot order all the same): 8.9 -> 6.0 us per launch
-    for (int k0 = 0; k0 < nb; k0 += 32) {
-      double t[32];
-#pragma unroll
-      for (int q = 0; q < 32; ++q) t[q] = (k0 + q < nb) ? P[(size_t)(k0 + q) * n + i] : 0.0;
-#pragma unroll
-      for (int q = 0; q < 32; ++q) sum = (k0 + q < nb) ? sum + t[q] : sum;
-    }
-    wv[i] = sum;
-  }
-  const double g = wave_sum_all(ri * ri), d = wave_sum_all(sum * ri);
-  if ((threadIdx.x & 63) == 0) { s_w[0][threadIdx.x >> 6] = g; s_w[1][threadIdx.x >> 6] = d; }
-  __syncthreads();
-  if (threadIdx.x == 0) { dots[blockIdx.x] = s_w[0][0] + s_w[0][1]; dots[nbp + blockIdx.x] = s_w[1][0] + s_w[1][1]; }
-}
-
-// its_hint: iterations the last converged system of this problem took (0: unknown) - the first batch of launches is sized for it
-// (a batch is enqueued blind and the host looks at the residual behind it; launches past convergence return at once but still
-// cost ~3 us each: at 14 iterations per system, 30 of the fixed first batch of 72 launches were such)
-static int cgs_solve_big(sfm_ctx* h, int n, const double* St, const double* rhs_t, double* x_t, double* buf, double* scal,
-                         double rtol, int budget, int* iters_out, int* status, int its_hint) {
-  const double rtol2 = rtol * rtol;
-  *status = 1;
-  const int nb = (int)cdiv(n, SY_T), nbp = (nb + 127) & ~127;
-  const unsigned n_tiles = (unsigned)((int64_t)nb * (nb + 1) / 2);
-  double *vec = buf, *wv = buf + 8 * (size_t)n, *dots = wv + n, *P = dots + 2 * (size_t)nbp;
-  hipLaunchKernelGGL(k_cgb_init, dim3(cdiv(n > 2 * nbp ? n : 2 * nbp, 256)), dim3(256), 0, h->stream, n, nbp, rhs_t, vec, dots, scal);
-  // launch `it` forms r_it (it >= 1: from the dot products launch it - 1 left) and multiplies; launch it = k + 1 is the one that
-  // sees iterate k converged and copies it out, so a system of k iterations takes k + 2 launch pairs
-  // The triangle (405 MB at n = 10,000) is larger than the memory-side cache (256 MB): walked in the same direction every
-  // iteration, nothing of it is ever found there (a cyclic walk is LRU's worst case); walked back and forth, the tail of the
-  // previous pass is.  Odd launches therefore take the tiles in descending order: 1,361 -> 1,215 us per second system at cfg5
-  // (tools/experiments/README.md).  Which tile a workgroup takes changes nothing in the arithmetic: every tile's partial sums go
-  // to its own slot.
-  int it = 0;
-  int batch = its_hint > 0 ? (its_hint + 4 > 48 ? 48 : its_hint + 4) : 24;
-  // The verdict comes through the pinned page (k_cgb_symv): the host spins on this system's ticket and, every SPIN_QUERY spins,
-  // asks whether the stream has drained (a batch that ended without a verdict).  No status copy, no stream synchronisation
-  // on the way of a system that converges within its batch - and the caller's next launches queue up behind the blind launches
-  // still returning.  (No launch of an earlier system can write here: all of them return at their first instruction.)
-  volatile double* hst = h->pinned + SFM_PIN_CGB;
-  h->cgb_seq += 1.0;
-  const double seq = h->cgb_seq;
-  for (int q = 0; q < 7; ++q) hst[q] = 0.0;
-  constexpr unsigned SPIN_QUERY = 4096;
-  while (it < budget + 2) {
-    for (int b = 0; b < batch && it < budget + 2; ++b, ++it) {
-      hipLaunchKernelGGL(k_cgb_symv, dim3(n_tiles), dim3(256), 0, h->stream, n, nb, nbp, it, rtol2, St, vec, wv, dots, P, scal, x_t, it & 1,
-                         h->pinned + SFM_PIN_CGB, seq);
-      hipLaunchKernelGGL(k_cgb_reduce, dim3(nb), dim3(128), 0, h->stream, n, nb, nbp, it, P, vec, wv, dots, scal);
-    }
-    bool seen = false;
-    for (unsigned spins = 1; ; ++spins) {
-      if (hst[7] == seq) { seen = true; break; }
-      if ((spins % SPIN_QUERY) == 0 && hipStreamQuery(h->stream) != hipErrorNotReady) break;
-#if defined(__x86_64__)
-      __builtin_ia32_pause();
-#endif
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (!seen) {
-      SFM_HIP(h, hipStreamSynchronize(h->stream));
-      seen = hst[7] == seq;                           // (the verdict of the batch's last launches)
-    }
-    if (seen && hst[CGS_FAIL] != 0.0) break;
-    if (seen) { *status = 0; break; }                 // (the launch that saw the end has copied x out)
-    if (hst[CGS_FAIL] != 0.0) break;                  // a diagonal block was not positive definite (raised before the first launch)
-    const double rr = hst[CGS_RR], rr0 = hst[CGS_RR0];
-    // next look where the residual should be small enough, from the average rate so far (as cgs_solve)
-    const double done_its = hst[CGS_ITER] > 1.0 ? hst[CGS_ITER] : 1.0;
-    const double rate = rr0 > 0.0 ? std::log(rr / rr0) / done_its : 0.0;
-    batch = 8;
-    if (rate < -1e-3 && rr > 0.0) {
-      const double need = std::log(rtol2 * rr0 / rr) / rate;
-      batch = need < 2.0 ? 3 : (need > 48.0 ? 48 : (int)need + 3);
-    }
-  }
-  *iters_out += (int)hst[CGS_ITER];
-  SFM_LAUNCH_CHECK(h, "cgs_solve_big");
-  return SFM_OK;
-}
-
-// S~ x~ = r~ (r~ in cg_r, x~ into cg_z) by the plan's launch-per-iteration CG
-static int cgs_solve_per_launch(sfm_ctx* h, sfm_ba_problem p, const Lay& L, const DenseWs& dw, const CamPlan& plan, int* status, int its_hint) {
-  double* ws = (double*)p->workspace;
-  const int n = p->n_cams * p->cam_dim;
-  if (plan.per_launch == CAM_CG_TILES)
-    return cgs_solve_big(h, n, dw.Lm, WS(L, cg_r), WS(L, cg_z), dw.LmT, WS(L, cg_scal), CGS_RTOL, plan.budget, &p->cg_iters, status, its_hint);
-  return cgs_solve(h, n, dw.Lm, WS(L, cg_r), WS(L, cg_z), dw.LmT, WS(L, cg_scal), CGS_RTOL, &p->cg_iters, status);
-}
-
-// S + alpha I = L L^T into the factor's buffer, where S~ was (S is formed from the item tiles first if the build left S~ only);
-// row n of [S | r]: r -> L^-1 r
-static int factor_system(sfm_ctx* h, sfm_ba_problem p, const Lay& L, const DenseWs& dw, double alpha) {
-  double* ws = (double*)p->workspace;
-  const int n = p->n_cams * p->cam_dim;
-  int rc = schur_materialise_S(h, p, L); if (rc) return rc;
-  p->st_alpha = -1.0;
-  SFM_HIP(h, hipMemsetAsync(dw.flag, 0, sizeof(int), h->stream));       // the factorisation's failure flag (k_finish_solve reads it)
-  hipLaunchKernelGGL(k_add_diag, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, WS(L, red_S), n, alpha);
-  return dense_cholesky(h, WS(L, red_S), n, n + 1, dw);
-}
-
 // point back-substitution for the p_c in the workspace, and (want_q) the pieces of rhs2 = p_c - W C_a^-1 p_p
-static void launch_backsub(sfm_ctx* h, sfm_ba_problem p, const Lay& L, double* ws, int want_q) {
-  const int C = p->n_cams, P = p->n_pts, D = p->cam_dim, n = C * D;
-  const int64_t N = p->n_obs;
+void launch_backsub(sfm_ctx* h, sfm_ba_problem p, const Lay& L, int want_q) {
+  double* ws = (double*)p->workspace;
   sfm_prof_begin(h, SFM_PROF_BACKSUB);
-  DISPATCH_DT(D, p->precision, hipLaunchKernelGGL((k_obs_Gtp<DD, double, GG>), dim3(cdiv(N, GTP_OBS)), dim3(256), 0, h->stream, N,
-                                                  p->cam_idx, WS(L, G), WS(L, pc), WS(L, tmp3)));
-  hipLaunchKernelGGL(k_backsub, dim3((unsigned)L.nblk_pt), dim3(256), 0, h->stream, P, p->pt_ptr, WS(L, tmp3),
-                     WS(L, Linv), WS(L, e), WS(L, pp), WS(L, v), WS(L, part_pt));
-  if (want_q) {
-    DISPATCH_DT(D, p->precision, {
-      if (p->n_cchunks > 0)
-        hipLaunchKernelGGL((k_cam_reduce_chunks<DD, double, GG>), dim3((unsigned)p->n_cchunks), dim3(256), 0, h->stream, p->cch_beg,
-                           p->cch_end, p->cam_obs, p->cam_pt, WS(L, G), WS(L, v), WS(L, cch_part));
-      // (+ 1 workgroup: the two sums over the point pass's per-block partials, sum ||p_p||^2 and sum ||v||^2)
-      hipLaunchKernelGGL(k_cam_reduce_final<DD>, dim3(cdiv(C, 4) + 1), dim3(256), 0, h->stream, C, p->cch_ptr,
-                         WS(L, cch_part), (const double*)nullptr, WS(L, red_q), WS(L, part_pt), (int)L.nblk_pt, 2, WS(L, red_q) + n);
-    });
-  } else {
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, h->stream, WS(L, part_pt), (int)L.nblk_pt, 2,
-                       WS(L, red_q) + n);
-  }
+  launch_obs_Gtp(h, p, L, WS(L, pc));
+  launch_backsub_points(h, p, L);
+  if (want_q) launch_cam_reduce_chunks(h, p, L, WS(L, v));
+  if (want_q) launch_cam_reduce_final(h, p, L, nullptr, WS(L, red_q), true);
+  else ba_sum_partials(h, WS(L, part_pt), (int)L.nblk_pt, 2, WS(L, red_q) + p->n_cams * p->cam_dim);
   sfm_prof_end(h, SFM_PROF_BACKSUB);
 }
 
-extern "C" int sfm_ba_set_sharded(sfm_handle h, sfm_ba_problem p, int sharded) {
-  if (!h) return SFM_ERR_ARG;
-  if (!p) return sfm_fail(h, SFM_ERR_ARG, "sfm_ba_set_sharded", "null problem");
-  p->sharded = sharded ? 1 : 0;
-  return SFM_OK;
-}
-
-extern "C" int sfm_ba_schur_solve(sfm_handle h, sfm_ba_problem p, double alpha, int want_q) {
-  Lay L; int rc = check_problem(h, p, &L); if (rc) return rc;
-  double* ws = (double*)p->workspace;
-  const int C = p->n_cams, D = p->cam_dim, n = C * D;
-  double* S = WS(L, red_S);
-  DenseWs dw; dense_ws_carve(WS(L, dense), n, &dw);
-  p->cg_state = 0;
-  p->cg2_pending = 0;
-  p->cg_alpha = alpha;
-  const BaSwitches sw = ba_switches_from_env();
-  const CamPlan plan = cam_plan(n, p->camera_solver, h->cgs_persist_off != 0, sw);
-  // AUTO only: a system predicted to exhaust the CG's budget goes to the factorisation at once (CgPredictor)
-  const double hdiag = p->host_sc[SFM_SC_HDIAG];
-  const double arel = hdiag > 0.0 ? alpha / hdiag : 0.0;
-  const bool hopeless = p->camera_solver == SFM_CAMERA_SOLVER_AUTO && arel > 0.0 && sw.predict && p->cgp.hopeless(arel, plan.budget);
-  if (hopeless) p->cg_fallbacks++;
-  if (plan.route != CAM_FACTOR && !hopeless) {
-    const int its_before = p->cg_iters;
-    // S~ = E^-1 (S + alpha I) E^-T into the factor's buffer (S stays as it is: the fallback below needs it), r~ = E^-1 r
-    sfm_prof_begin(h, SFM_PROF_CHOL);
-    // (cleared by k_schur_assemble when this solve follows its own sfm_ba_schur_build, as it does in every loop of this library)
-    if (!p->cg_scal_clean) { SFM_HIP(h, hipMemsetAsync(WS(L, cg_scal), 0, CG_SCAL_WORDS * sizeof(double), h->stream)); p->einv_alpha = -1.0; }
-    p->cg_scal_clean = 0;
-    const bool have_einv = p->einv_alpha == alpha && !p->sharded;      // k_schur_assemble of THIS system left them
-    p->einv_alpha = -1.0;
-    // ... or the scaled system itself (tile-streaming route: k_schur_assemble_scaled)
-    const bool have_st = have_einv && p->st_alpha == alpha && plan.lower_only;
-    if (!have_st && (rc = schur_materialise_S(h, p, L))) return rc;
-    if (!have_st) DISPATCH_D(D, {
-      if (!have_einv)
-        hipLaunchKernelGGL(k_diag_einv<DD>, dim3(cdiv(C, 64)), dim3(64), 0, h->stream, C, S, n, alpha, WS(L, cg_Minv), WS(L, cg_M), WS(L, cg_scal));
-      if (plan.lower_only)
-        hipLaunchKernelGGL(k_scale_system_lower<DD>, dim3(C, cdiv(C, SCALE_NB)), dim3(128), 0, h->stream, n, C, S, alpha, WS(L, cg_Minv), dw.Lm,
-                           S + (size_t)n * n, WS(L, cg_r));
-      else
-        hipLaunchKernelGGL(k_scale_system<DD>, dim3(C, cdiv(C, SCALE_NB)), dim3(128), 0, h->stream, n, C, S, alpha, WS(L, cg_Minv), dw.Lm,
-                           S + (size_t)n * n, WS(L, cg_r));
-    });
-    int status = 1, ran = 0;
-    if (plan.route == CAM_CG_PERSIST) {
-      // ONE persistent launch: r~ = E^-1 r in its prologue, p_c = -E^-T x~ in its epilogue.  The host needs its verdict
-      // (converged / fall back) but must not idle the GPU for it: the status words are copied to pinned memory, an event is
-      // recorded behind the copy, the back-substitution is enqueued on the assumption that the solve converged (it does: 0
-      // fallbacks in the bench schedules), and only then the host waits - for the event, not for the stream.
-      PrFuse fuse = {WS(L, cg_Minv), nullptr, WS(L, pc), nullptr, nullptr, nullptr, nullptr, 1, 0.0};      // rhs~ = cg_r (k_scale_system)
-      const PrLaunch pl = {n, D, dw.Lm, WS(L, cg_r), WS(L, cg_z), WS(L, cg_mail), WS(L, cg_scal), CGS_RTOL, fuse, h->pinned + SFM_PIN_CG1};
-      rc = cgs_persist_launch(h, pl);
-      if (rc) return rc;
-      SFM_HIP(h, hipEventRecord(h->cg_event, h->stream));
-      sfm_prof_end(h, SFM_PROF_CHOL);
-      launch_backsub(h, p, L, ws, want_q);
-      SFM_HIP(h, hipEventSynchronize(h->cg_event));
-      int relaunched = 0;
-      rc = cgs_persist_verdict(h, pl, p->sharded, &p->cg_iters, &status, &ran, &relaunched);
-      if (rc) return rc;
-      if (relaunched && ran && status == 0) launch_backsub(h, p, L, ws, want_q);      // the first one ran on an unfinished p_c
-      if (ran && status == 0) {
-        p->cg_state = 1;
-        p->cgp.note_ok(arel, p->cg_iters - its_before);
-        SFM_LAUNCH_CHECK(h, "sfm_ba_schur_solve");
-        return SFM_OK;
-      }
-      sfm_prof_begin(h, SFM_PROF_CHOL);             // not converged or abandoned: the routes below, then the back-substitution again
-    }
-    if (!ran) {                                       // plan.per_launch: one launch (pair) per iteration, with the scaling of r and of the solution as kernels of their own
-      DISPATCH_D(D, hipLaunchKernelGGL(k_block_mv<DD>, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, C, WS(L, cg_Minv), S + (size_t)n * n, WS(L, cg_r), 0, 1.0));
-      rc = cgs_solve_per_launch(h, p, L, dw, plan, &status, p->cgp.ok_its[0]);
-      if (rc) return rc;
-      p->cg_its_sys1 = p->cg_iters - its_before;
-      if (status == 0)
-        DISPATCH_D(D, hipLaunchKernelGGL(k_block_mv<DD>, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, C, WS(L, cg_Minv), WS(L, cg_z),
-                                         WS(L, pc), 1, -1.0));                      // p_c = -E^-T x~
-    }
-    if (status == 0) {
-      p->cg_state = 1;
-      p->cgp.note_ok(arel, p->cg_iters - its_before);
-    } else {
-      p->cg_fallbacks++;
-      p->cgp.note_out_of_budget(arel, p->cg_iters - its_before, plan.budget);
-    }
-    sfm_prof_end(h, SFM_PROF_CHOL);
+// The host's wait for a ticket in pinned memory (sfm_ba_read_scalars, cgs_solve_big).  Every few thousand spins the stream is asked as
+// well: a drained stream ends the wait whatever was published (a path that publishes nothing, or a failure the caller's synchronisation reports)
+bool ba_wait_for_word(sfm_ctx* h, const volatile double* word, double want) {
+  constexpr unsigned SPIN_QUERY = 4096;
+  bool seen = false;
+  for (unsigned spins = 1; ; ++spins) {
+    if (*word == want) { seen = true; break; }
+    if ((spins % SPIN_QUERY) == 0 && hipStreamQuery(h->stream) != hipErrorNotReady) break;
+#if defined(__x86_64__)
+    __builtin_ia32_pause();
+#endif
   }
-  if (p->cg_state == 0) {
-    sfm_prof_begin(h, SFM_PROF_CHOL);
-    rc = factor_system(h, p, L, dw, alpha); if (rc) return rc;
-    sfm_prof_end(h, SFM_PROF_CHOL);
-    sfm_prof_begin(h, SFM_PROF_TRSV);
-    // p_c = -L^-T (L^-1 r)
-    hipLaunchKernelGGL(k_copy_neg, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, dw.Lm + (size_t)n * n, WS(L, tvec), n, -1.0);
-    rc = dense_trsv(h, n, dw, WS(L, tvec), WS(L, pc), 1); if (rc) return rc;
-    sfm_prof_end(h, SFM_PROF_TRSV);
-  }
-  launch_backsub(h, p, L, ws, want_q);
-  SFM_LAUNCH_CHECK(h, "sfm_ba_schur_solve");
-  return SFM_OK;
-}
-
-// the q term from the factorisation (S intact in red_S): used when the CG on the second system did not converge
-static int finish_solve_by_factor(sfm_ctx* h, sfm_ba_problem p, const Lay& L, double* ws, int want_q, bool factor_first) {
-  const int n = p->n_cams * p->cam_dim;
-  DenseWs dw; dense_ws_carve(WS(L, dense), n, &dw);
-  int rc;
-  if (factor_first) {
-    p->cg_fallbacks++;
-    p->cg_state = 0;
-    rc = factor_system(h, p, L, dw, p->cg_alpha); if (rc) return rc;
-  }
-  if (want_q) {
-    // rhs2 = p_c - W C_a^-1 p_p ;  y = L^-1 rhs2
-    sfm_prof_begin(h, SFM_PROF_TRSV);
-    hipLaunchKernelGGL(k_add_vec, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, WS(L, pc), WS(L, red_q), WS(L, tvec), n);
-    rc = dense_trsv(h, n, dw, WS(L, tvec), WS(L, y), 0); if (rc) return rc;
-    sfm_prof_end(h, SFM_PROF_TRSV);
-  }
-  hipLaunchKernelGGL(k_finish_solve, dim3(1), dim3(256), 0, h->stream, n, WS(L, pc), WS(L, red_q), WS(L, y),
-                     want_q, (const int*)dw.flag, WS(L, scalars), p->host_sc, next_ticket(p));
-  SFM_LAUNCH_CHECK(h, "sfm_ba_finish_solve");
-  return SFM_OK;
-}
-
-extern "C" int sfm_ba_finish_solve(sfm_handle h, sfm_ba_problem p, int want_q) {
-  Lay L; int rc = check_problem(h, p, &L); if (rc) return rc;
-  double* ws = (double*)p->workspace;
-  const int n = p->n_cams * p->cam_dim;
-  DenseWs dw; dense_ws_carve(WS(L, dense), n, &dw);
-  const CamPlan plan = cam_plan(n, p->camera_solver, h->cgs_persist_off != 0, ba_switches_from_env());
-  if (p->cg_state == 1) {
-    // the camera system was solved by CG on the scaled system S~ (still in dw.Lm): p^T (H + alpha I)^-1 p needs
-    // rhs2^T S^-1 rhs2 = r~2^T x~2 with r~2 = E^-1 rhs2, S~ x~2 = r~2
-    const int C = p->n_cams, D = p->cam_dim;
-    int status = 0;
-    if (want_q) {
-      sfm_prof_begin(h, SFM_PROF_TRSV);
-      if (plan.route == CAM_CG_PERSIST) {
-        // ONE persistent launch: r~2 = E^-1 (p_c + rhs2 pieces) in its prologue, r~2 . x~2 and the scalars of the solve in its
-        // epilogue.  Its verdict travels to pinned memory with the copy enqueued behind it and is looked at where the host
-        // synchronises anyway: in sfm_ba_read_scalars, which redoes this step from the factorisation if it has to.
-        // rhs~2 = E^-1 (p_c + rhs2 pieces) by one small launch (in the CG kernel's prologue every workgroup formed all of it)
-        DISPATCH_D(D, hipLaunchKernelGGL(k_block_mv<DD>, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, C, WS(L, cg_Minv), WS(L, pc),
-                                         WS(L, cg_r), 0, 1.0, WS(L, red_q)));
-        PrFuse fuse = {WS(L, cg_Minv), nullptr, nullptr, WS(L, pc), WS(L, red_q), WS(L, scalars), p->host_sc, 1, next_ticket(p)};
-        const PrLaunch pl = {n, D, dw.Lm, WS(L, cg_r), WS(L, cg_z), WS(L, cg_mail), WS(L, cg_scal), CGS_RTOL, fuse, p->host_sc + SFM_HSC_CG2};
-        rc = cgs_persist_launch(h, pl);
-        if (rc) return rc;
-        p->cg2_pending = 1;
-        sfm_prof_end(h, SFM_PROF_TRSV);
-        return SFM_OK;
-      }
-      hipLaunchKernelGGL(k_add_vec, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, WS(L, pc), WS(L, red_q), WS(L, tvec), n);
-      DISPATCH_D(D, hipLaunchKernelGGL(k_block_mv<DD>, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, C, WS(L, cg_Minv), WS(L, tvec),
-                                       WS(L, cg_r), 0, 1.0));
-      // (the q system of a damped solve takes about as many iterations as its step system just did)
-      rc = cgs_solve_per_launch(h, p, L, dw, plan, &status, p->cg_its_sys1);
-      if (rc) return rc;
-      if (status == 0)
-        hipLaunchKernelGGL(k_dot, dim3(1), dim3(1024), 0, h->stream, n, WS(L, cg_r), WS(L, cg_z), WS(L, cg_scal) + 8);
-      sfm_prof_end(h, SFM_PROF_TRSV);
-    }
-    if (status == 0) {
-      hipLaunchKernelGGL(k_finish_solve_pcg, dim3(1), dim3(256), 0, h->stream, n, WS(L, pc), WS(L, red_q), want_q, WS(L, cg_scal) + 8,
-                         WS(L, cg_scal) + CGS_FAIL, WS(L, scalars), p->host_sc, next_ticket(p));
-      SFM_LAUNCH_CHECK(h, "sfm_ba_finish_solve");
-      return SFM_OK;
-    }
-    // the second system did not converge: factor after all (S is intact) and take the q term from the factor
-    return finish_solve_by_factor(h, p, L, ws, want_q, true);
-  }
-  return finish_solve_by_factor(h, p, L, ws, want_q, false);
-}
-
-// ------------------------------------------------------------------------------------ implicit-Schur PCG
-// The damped camera system S y = r,  S = B + alpha I - W (C + alpha I)^-1 W^T, WITHOUT forming or factoring S
-// (SURVEY.md section 7 hard part 4 / 4b): for systems of many cameras (1000 cameras: S is 800 MB and its replicated
-// factorisation 13.8 ms per damped solve) and for the multi-rank split, where the dense route all-reduces n^2/2
-// doubles per solve and factors on every rank while this route exchanges ONE vector of n doubles per iteration.
-//   S v = (B + alpha I) v - sum_{k in camera} G_k u_{pt(k)},   u_j = sum_{k in track j} G_k^T v_{cam(k)}
-// (the same two passes over G the back-substitution makes), preconditioned with the exact diagonal blocks
-// M_c = B_c + alpha I - sum_{k in c} G_k G_k^T (d x d per camera, inverted explicitly).  All CG scalars live on the
-// device (one fused single-workgroup kernel per iteration: alpha, x, r, z = M^-1 r, beta, p); the host only reads
-// ||r||^2 every few iterations.  Vectors of length n are replicated on every rank, sums over observations are
-// rank-local and reduced through the caller's hook - so every rank runs the identical recurrence.
-enum { CG_RZ = 0, CG_RR = 1, CG_RR0 = 2, CG_ITER = 3, CG_FAIL = 4, CG_DOT = 5 };
-
-__global__ __launch_bounds__(256) void k_track_sum(int P, const int* __restrict__ pt_ptr, const double* __restrict__ tmp3,
-                                                   double* __restrict__ u) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= P) return;
-  double u0 = 0.0, u1 = 0.0, u2 = 0.0;
-#pragma unroll 5
-  for (int k = pt_ptr[j]; k < pt_ptr[j + 1]; ++k) { u0 += tmp3[(size_t)k * 3]; u1 += tmp3[(size_t)k * 3 + 1]; u2 += tmp3[(size_t)k * 3 + 2]; }
-  u[(size_t)j * 3] = u0; u[(size_t)j * 3 + 1] = u1; u[(size_t)j * 3 + 2] = u2;
-}
-// out[c] = B_c v_c - sum over the camera's chunks of the partial sums of k_cam_reduce_chunks (this rank's part of S v - alpha v)
-template <int D>
-__global__ void k_cam_reduce_final_bv(int C, const int* __restrict__ cch_ptr, const double* __restrict__ part,
-                                      const double* __restrict__ B, const double* __restrict__ v, double* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= C * D) return;
-  const int c = i / D, a = i - c * D;
-  double t = 0.0;
-  for (int ch = cch_ptr[c]; ch < cch_ptr[c + 1]; ++ch) t += part[(size_t)ch * 16 + a];
-  double bv = 0.0;
-#pragma unroll
-  for (int b = 0; b < D; ++b) bv += B[(size_t)c * D * D + a * D + b] * v[c * D + b];
-  out[i] = bv - t;
-}
-// per chunk of one camera's observations: sum_k G_k G_k^T (D x D), thread (a, b) per entry, fixed order
-template <int D, typename TG, int GS>
-__global__ __launch_bounds__(128) void k_cam_gg_chunks(const int* __restrict__ cch_beg, const int* __restrict__ cch_end,
-                                                       const int* __restrict__ cam_obs, const TG* __restrict__ G,
-                                                       double* __restrict__ part) {
-  const int ch = blockIdx.x, e = threadIdx.x;
-  if (e >= D * D) return;
-  const int a = e / D, b = e - a * D;
-  double acc = 0.0;
-  for (int i = cch_beg[ch]; i < cch_end[ch]; ++i) {
-    const TG* g = G + (size_t)cam_obs[i] * GS;
-    acc += (double)g[a] * (double)g[b] + (double)g[D + a] * (double)g[D + b] + (double)g[2 * D + a] * (double)g[2 * D + b];
-  }
-  part[(size_t)ch * (D * D) + e] = acc;
-}
-template <int D>
-__global__ void k_cam_gg_final(int C, const int* __restrict__ cch_ptr, const double* __restrict__ part,
-                               const double* __restrict__ B, double* __restrict__ M) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= C * D * D) return;
-  const int c = i / (D * D), e = i - c * D * D;
-  double t = 0.0;
-  for (int ch = cch_ptr[c]; ch < cch_ptr[c + 1]; ++ch) t += part[(size_t)ch * (D * D) + e];
-  M[i] = B[i] - t;
-}
-// Minv_c = (M_c + alpha I)^-1 by Cholesky, one thread per camera (D <= 10: 100 doubles of registers / scratch)
-template <int D>
-__global__ __launch_bounds__(64) void k_precond_invert(int C, const double* __restrict__ M, double alpha, double* __restrict__ Minv,
-                                 double* __restrict__ scal) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  double L[D][D], X[D][D];
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-#pragma unroll
-    for (int j = 0; j < D; ++j) L[i][j] = 0.5 * (M[(size_t)c * D * D + i * D + j] + M[(size_t)c * D * D + j * D + i]) + (i == j ? alpha : 0.0);
-  const bool bad = !small_chol_inverse<D>(L, X);      // X = L^-1, then Minv = X^T X
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-      double sum = 0.0;
-#pragma unroll
-      for (int k = 0; k < D; ++k) sum += X[k][i] * X[k][j];
-      Minv[(size_t)c * D * D + i * D + j] = sum;
-    }
-  if (bad) scal[CG_FAIL] = 1.0;
-}
-
-// Sum over a 1024-thread block, fixed order; every thread gets the result.  s: >= 17 doubles of LDS.
-__device__ __forceinline__ double block_sum1024(double v, double* s) {
-  v = wave_sum_all(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < 16; ++w) t += s[w];
-  return t;
-}
-// z = Minv r per camera block (thread i owns row i of its block)
-template <int D>
-__device__ __forceinline__ double precond_row(const double* __restrict__ Minv, const double* __restrict__ r, int i) {
-  const int c = i / D, a = i - c * D;
-  const double* m = Minv + (size_t)c * D * D + a * D;
-  double z = 0.0;
-#pragma unroll
-  for (int b = 0; b < D; ++b) z += m[b] * r[c * D + b];
-  return z;
-}
-// start: x = 0, r = rhs, z = M^-1 r, p = z; scalars rz, rr, rr0
-template <int D>
-__global__ __launch_bounds__(1024) void k_cg_init(int n, const double* __restrict__ rhs, const double* __restrict__ Minv,
-                                                  double* __restrict__ x, double* __restrict__ r, double* __restrict__ z,
-                                                  double* __restrict__ pv, double* __restrict__ scal) {
-  __shared__ double s_red[17];
-  double rz = 0.0, rr = 0.0;
-  for (int i = threadIdx.x; i < n; i += 1024) { x[i] = 0.0; r[i] = rhs[i]; }
-  __syncthreads();
-  for (int i = threadIdx.x; i < n; i += 1024) {
-    const double zi = precond_row<D>(Minv, rhs, i);
-    z[i] = zi; pv[i] = zi;
-    rz += rhs[i] * zi; rr += rhs[i] * rhs[i];
-  }
-  rz = block_sum1024(rz, s_red);
-  rr = block_sum1024(rr, s_red);
-  if (threadIdx.x == 0) { scal[CG_RZ] = rz; scal[CG_RR] = rr; scal[CG_RR0] = rr; scal[CG_ITER] = 0.0; }
-}
-// one CG iteration after the product: Ap = (reduced B p - W C^-1 W^T p) + alpha p
-template <int D>
-__global__ __launch_bounds__(1024) void k_cg_step(int n, double alpha, double* __restrict__ Ap, double* __restrict__ pv,
-                                                  double* __restrict__ x, double* __restrict__ r, double* __restrict__ z,
-                                                  const double* __restrict__ Minv, double* __restrict__ scal) {
-  __shared__ double s_red[17];
-  const double rz = scal[CG_RZ];
-  double pAp = 0.0;
-  for (int i = threadIdx.x; i < n; i += 1024) { const double ap = Ap[i] + alpha * pv[i]; Ap[i] = ap; pAp += pv[i] * ap; }
-  pAp = block_sum1024(pAp, s_red);
-  if (!(pAp > 0.0) || rz == 0.0) {            // S is not positive definite (or the residual vanished exactly): stop moving
-    if (threadIdx.x == 0) { if (!(pAp > 0.0) && rz != 0.0) scal[CG_FAIL] = 2.0; scal[CG_RR] = (rz == 0.0) ? 0.0 : scal[CG_RR]; }
-    return;
-  }
-  const double a = rz / pAp;
-  for (int i = threadIdx.x; i < n; i += 1024) { x[i] += a * pv[i]; r[i] -= a * Ap[i]; }
-  __syncthreads();                              // r complete before the block-wise preconditioner reads it
-  double rz_new = 0.0, rr = 0.0;
-  for (int i = threadIdx.x; i < n; i += 1024) {
-    const double zi = precond_row<D>(Minv, r, i);
-    z[i] = zi;
-    rz_new += r[i] * zi; rr += r[i] * r[i];
-  }
-  rz_new = block_sum1024(rz_new, s_red);
-  rr = block_sum1024(rr, s_red);
-  const double beta = rz_new / rz;
-  for (int i = threadIdx.x; i < n; i += 1024) pv[i] = z[i] + beta * pv[i];
-  if (threadIdx.x == 0) { scal[CG_RZ] = rz_new; scal[CG_RR] = rr; scal[CG_ITER] += 1.0; }
-}
-__global__ __launch_bounds__(1024) void k_dot(int n, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ out) {
-  __shared__ double s_red[17];
-  double t = 0.0;
-  for (int i = threadIdx.x; i < n; i += 1024) t += a[i] * b[i];
-  t = block_sum1024(t, s_red);
-  if (threadIdx.x == 0) *out = t;
-}
-// scalars after a PCG solve: PNORM2 = ||p_c||^2 + sum ||p_p||^2, PQ = rhs2^T S^-1 rhs2 + sum ||v||^2, failure code
-__global__ __launch_bounds__(256) void k_finish_solve_pcg(int n, const double* __restrict__ pc, const double* __restrict__ red_q,
-                                                          int want_q, const double* __restrict__ dotp, const double* __restrict__ failp,
-                                                          double* __restrict__ sc, double* __restrict__ hsc, double seq) {
-  __shared__ double s_red[4];
-  double a = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) a += pc[i] * pc[i];
-  const double at = block_sum256(a, s_red);
-  if (threadIdx.x == 0) {
-    const double pn2 = at + red_q[n], pq = want_q ? (*dotp + red_q[n + 1]) : 0.0;
-    sc[SFM_SC_PNORM2] = hsc[SFM_SC_PNORM2] = pn2; sc[SFM_SC_PQ] = hsc[SFM_SC_PQ] = pq;
-    double f = *failp != 0.0 ? 1.0 : 0.0;                   // 1: a block or S itself is not positive definite
-    if (f == 0.0 && !(isfinite(pn2) && isfinite(pq))) f = 3.0;
-    sc[SFM_SC_CHOL_FAIL] = hsc[SFM_SC_CHOL_FAIL] = f;
-    publish_ticket(hsc, seq);
-  }
-}
-
-
-
-namespace {
-struct Pcg {
-  sfm_ctx* h; sfm_ba_problem p; Lay L; double* ws; double alpha, rtol; int max_iter;
-  sfm_reduce_fn reduce; void* user;
-  int iters;
-  bool stalled = false;      // a system ran out of iterations above rtol
-
-  int red(double* ptr, int64_t count) {
-    if (!reduce) return SFM_OK;
-    return reduce(user, ptr, count, 0) ? sfm_fail(h, SFM_ERR_HIP, "sfm_ba_solve_pcg", "the reduce hook failed") : SFM_OK;
-  }
-  // this rank's part of (S - alpha I) v -> cg_Ap, reduced over the ranks
-  int matvec(const double* v) {
-    const int C = p->n_cams, P = p->n_pts, D = p->cam_dim, n = C * D;
-    const int64_t N = p->n_obs;
-    DISPATCH_DT(D, p->precision, {
-      hipLaunchKernelGGL((k_obs_Gtp<DD, double, GG>), dim3(cdiv(N, GTP_OBS)), dim3(256), 0, h->stream, N, p->cam_idx, WS(L, G), v, WS(L, tmp3));
-      hipLaunchKernelGGL(k_track_sum, dim3(cdiv(P, 256)), dim3(256), 0, h->stream, P, p->pt_ptr, WS(L, tmp3), WS(L, v));
-      if (p->n_cchunks > 0)
-        hipLaunchKernelGGL((k_cam_reduce_chunks<DD, double, GG>), dim3((unsigned)p->n_cchunks), dim3(256), 0, h->stream, p->cch_beg,
-                           p->cch_end, p->cam_obs, p->cam_pt, WS(L, G), WS(L, v), WS(L, cch_part));
-      hipLaunchKernelGGL(k_cam_reduce_final_bv<DD>, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, C, p->cch_ptr, WS(L, cch_part), WS(L, B),
-                         v, WS(L, cg_Ap));
-    });
-    return red(WS(L, cg_Ap), n);
-  }
-  // x = S^-1 rhs (x, rhs: device vectors of n doubles, distinct from the cg_* work vectors)
-  int solve(const double* rhs, double* x) {
-    const int D = p->cam_dim, n = p->n_cams * D;
-    DISPATCH_D(D, hipLaunchKernelGGL(k_cg_init<DD>, dim3(1), dim3(1024), 0, h->stream, n, rhs, WS(L, cg_Minv), x, WS(L, cg_r), WS(L, cg_z),
-                                     WS(L, cg_p), WS(L, cg_scal)));
-    const int check_every = 8;
-    bool settled = false;                            // converged, or a failure the scalars already carry
-    for (int it = 0; it < max_iter; ++it) {
-      int rc = matvec(WS(L, cg_p)); if (rc) return rc;
-      DISPATCH_D(D, hipLaunchKernelGGL(k_cg_step<DD>, dim3(1), dim3(1024), 0, h->stream, n, alpha, WS(L, cg_Ap), WS(L, cg_p), x, WS(L, cg_r),
-                                       WS(L, cg_z), WS(L, cg_Minv), WS(L, cg_scal)));
-      ++iters;
-      if ((it + 1) % check_every == 0 || it + 1 == max_iter) {
-        SFM_HIP(h, hipMemcpyAsync(h->pinned, WS(L, cg_scal), 8 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        SFM_HIP(h, hipStreamSynchronize(h->stream));
-        const double rr = h->pinned[CG_RR], rr0 = h->pinned[CG_RR0];
-        if (h->pinned[CG_FAIL] != 0.0 || !(rr == rr)) { settled = true; break; }     // reported through the scalars
-        if (rr <= rtol * rtol * rr0) { settled = true; break; }
-      }
-    }
-    // max_iter iterations without reaching rtol (the last look above was at it + 1 == max_iter): an inexact p and
-    // p^T (H + alpha I)^-1 p would silently steer More's alpha update.  Measured on the goldens: near convergence of the
-    // outer loop (alpha ~ 1e-3, S nearly singular along the 7 gauge directions) block-Jacobi PCG stalls at a relative
-    // residual of 1e-2 .. 1e-4.  The caller (sfm_ba_solve_pcg) then solves THIS damped system by the formed-S route, as the
-    // explicit-S CG falls back to its factorisation.
-    if (!settled) {
-      const double rr = h->pinned[CG_RR], rr0 = h->pinned[CG_RR0];
-      const double rel = rr0 > 0.0 ? std::sqrt(rr / rr0) : 0.0;
-      if (rel > p->pcg_worst_relres) p->pcg_worst_relres = rel;
-      if (getenv("SFM_PCG_DEBUG")) fprintf(stderr, "sfm_amd pcg: alpha %.3e: %d iterations, relative residual %.3e (rtol %.1e): formed-S fallback\n", alpha, max_iter, rel, rtol);
-      stalled = true;
-    }
-    SFM_LAUNCH_CHECK(h, "sfm_ba_solve_pcg");
-    return SFM_OK;
-  }
-};
-}  // namespace
-
-// The damped system by the formed-S route (what the trust-region loop does with SFM_SOLVER_DENSE), for a system the
-// implicit-Schur PCG could not bring to its tolerance.
-static int pcg_fallback_dense(sfm_ctx* h, sfm_ba_problem p, const Lay& L, double alpha, int want_q, sfm_reduce_fn reduce, void* user) {
-  char* base = (char*)p->workspace;
-  sfm_ba_layout lay; sfm_ba_get_layout(p, &lay);
-  auto red = [&](int64_t off, int64_t count) -> int {
-    if (!reduce) return SFM_OK;
-    return reduce(user, base + off, count, 0) ? sfm_fail(h, SFM_ERR_HIP, "sfm_ba_solve_pcg", "the reduce hook failed") : SFM_OK;
-  };
-  int rc;
-  p->pcg_fallbacks++;
-  if ((rc = sfm_ba_schur_build(h, p, alpha))) return rc;
-  if (reduce) {
-    if ((rc = sfm_ba_pack_system(h, p))) return rc;
-    if ((rc = red(lay.reduce_Sp_off, lay.reduce_Sp_count))) return rc;
-    if ((rc = sfm_ba_unpack_system(h, p))) return rc;
-  }
-  if ((rc = sfm_ba_schur_solve(h, p, alpha, want_q))) return rc;
-  if ((rc = red(lay.reduce_q_off, lay.reduce_q_count))) return rc;
-  return sfm_ba_finish_solve(h, p, want_q);
-}
-
-extern "C" int sfm_ba_solve_pcg(sfm_handle h, sfm_ba_problem p, double alpha, int want_q, double rtol, int32_t max_iter,
-                                sfm_reduce_fn reduce, void* reduce_user, int32_t* iters_host) {
-  Lay L; int rc = check_problem(h, p, &L); if (rc) return rc;
-  if (!(alpha > 0.0) || !(rtol > 0.0) || max_iter < 1) return sfm_fail(h, SFM_ERR_ARG, "sfm_ba_solve_pcg", "alpha, rtol > 0 and max_iter >= 1");
-  double* ws = (double*)p->workspace;
-  const int C = p->n_cams, P = p->n_pts, D = p->cam_dim, n = C * D;
-  const int64_t N = p->n_obs;
-  Pcg cg{h, p, L, ws, alpha, rtol, max_iter, reduce, reduce_user, 0};
-  if (reduce) p->sharded = 1;          // the formed-S fallback below solves a replicated camera system: same route on every rank
-  SFM_HIP(h, hipMemsetAsync(WS(L, cg_scal), 0, CG_SCAL_WORDS * sizeof(double), h->stream));
-  // point factors, G, and this rank's part of the right-hand side r = g_c - W C_a^-1 g_p and of the diagonal blocks
-  sfm_prof_begin(h, SFM_PROF_BUILD_G);
-  DISPATCH_DT(D, p->precision, {
-    hipLaunchKernelGGL((k_build_G<DD, TT, double, GG>), dim3(cdiv(N, 256) + cdiv(P, 256)), dim3(256), 0, h->stream, N, p->pt_idx, WST(L, recA),
-                       WST(L, recB), WS(L, Linv), WS(L, G), WS(L, e), WS(L, eobs), WS(L, Cp), WS(L, gp), alpha, P, (unsigned)cdiv(N, 256),
-                       (double*)nullptr);
-    sfm_prof_end(h, SFM_PROF_BUILD_G);
-    sfm_prof_begin(h, SFM_PROF_SCHUR);
-    if (p->n_cchunks > 0) {
-      hipLaunchKernelGGL((k_cam_reduce_chunks<DD, double, GG>), dim3((unsigned)p->n_cchunks), dim3(256), 0, h->stream, p->cch_beg,
-                         p->cch_end, p->cam_obs, p->cam_pt, WS(L, G), WS(L, e), WS(L, cch_part));
-      hipLaunchKernelGGL((k_cam_gg_chunks<DD, double, GG>), dim3((unsigned)p->n_cchunks), dim3(128), 0, h->stream, p->cch_beg, p->cch_end,
-                         p->cam_obs, WS(L, G), WS(L, cbl_part));
-    }
-    hipLaunchKernelGGL(k_cam_reduce_final<DD>, dim3(cdiv(C, 4)), dim3(256), 0, h->stream, C, p->cch_ptr, WS(L, cch_part), WS(L, gc),
-                       WS(L, tvec));
-    hipLaunchKernelGGL(k_cam_gg_final<DD>, dim3(cdiv((int64_t)n * DD, 256)), dim3(256), 0, h->stream, C, p->cch_ptr, WS(L, cbl_part),
-                       WS(L, B), WS(L, cg_M));
-    sfm_prof_end(h, SFM_PROF_SCHUR);
-  });
-  if ((rc = cg.red(WS(L, tvec), n))) return rc;
-  if ((rc = cg.red(WS(L, cg_M), (int64_t)n * D))) return rc;
-  sfm_prof_begin(h, SFM_PROF_CHOL);            // the slot of the camera solve: here the CG iterations
-  DISPATCH_D(D, hipLaunchKernelGGL(k_precond_invert<DD>, dim3(cdiv(C, 64)), dim3(64), 0, h->stream, C, WS(L, cg_M), alpha, WS(L, cg_Minv),
-                                   WS(L, cg_scal)));
-  // y = S^-1 r ; p_c = -y
-  if ((rc = cg.solve(WS(L, tvec), WS(L, y)))) return rc;
-  if (cg.stalled) {
-    sfm_prof_end(h, SFM_PROF_CHOL);
-    if (iters_host) *iters_host = cg.iters;
-    return pcg_fallback_dense(h, p, L, alpha, want_q, reduce, reduce_user);
-  }
-  hipLaunchKernelGGL(k_copy_neg, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, WS(L, y), WS(L, pc), n, -1.0);
-  sfm_prof_end(h, SFM_PROF_CHOL);
-  sfm_prof_begin(h, SFM_PROF_BACKSUB);
-  DISPATCH_DT(D, p->precision, hipLaunchKernelGGL((k_obs_Gtp<DD, double, GG>), dim3(cdiv(N, GTP_OBS)), dim3(256), 0, h->stream, N,
-                                                  p->cam_idx, WS(L, G), WS(L, pc), WS(L, tmp3)));
-  hipLaunchKernelGGL(k_backsub, dim3((unsigned)L.nblk_pt), dim3(256), 0, h->stream, P, p->pt_ptr, WS(L, tmp3), WS(L, Linv), WS(L, e),
-                     WS(L, pp), WS(L, v), WS(L, part_pt));
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, h->stream, WS(L, part_pt), (int)L.nblk_pt, 2, WS(L, red_q) + n);
-  if (want_q) {
-    DISPATCH_DT(D, p->precision, {
-      if (p->n_cchunks > 0)
-        hipLaunchKernelGGL((k_cam_reduce_chunks<DD, double, GG>), dim3((unsigned)p->n_cchunks), dim3(256), 0, h->stream, p->cch_beg,
-                           p->cch_end, p->cam_obs, p->cam_pt, WS(L, G), WS(L, v), WS(L, cch_part));
-      hipLaunchKernelGGL(k_cam_reduce_final<DD>, dim3(cdiv(C, 4)), dim3(256), 0, h->stream, C, p->cch_ptr, WS(L, cch_part),
-                         (const double*)nullptr, WS(L, red_q));
-    });
-  }
-  sfm_prof_end(h, SFM_PROF_BACKSUB);
-  if ((rc = cg.red(WS(L, red_q), n + 2))) return rc;
-  if (want_q) {
-    // rhs2 = p_c - W C_a^-1 p_p ;  p^T (H + alpha I)^-1 p = rhs2^T S^-1 rhs2 + sum ||v||^2
-    sfm_prof_begin(h, SFM_PROF_TRSV);
-    hipLaunchKernelGGL(k_add_vec, dim3(cdiv(n, 256)), dim3(256), 0, h->stream, WS(L, pc), WS(L, red_q), WS(L, tvec), n);
-    if ((rc = cg.solve(WS(L, tvec), WS(L, y)))) return rc;
-    if (cg.stalled) {
-      sfm_prof_end(h, SFM_PROF_TRSV);
-      if (iters_host) *iters_host = cg.iters;
-      return pcg_fallback_dense(h, p, L, alpha, want_q, reduce, reduce_user);
-    }
-    hipLaunchKernelGGL(k_dot, dim3(1), dim3(1024), 0, h->stream, n, WS(L, tvec), WS(L, y), WS(L, cg_scal) + CG_DOT);
-    sfm_prof_end(h, SFM_PROF_TRSV);
-  }
-  hipLaunchKernelGGL(k_finish_solve_pcg, dim3(1), dim3(256), 0, h->stream, n, WS(L, pc), WS(L, red_q), want_q, WS(L, cg_scal) + CG_DOT,
-                     WS(L, cg_scal) + CG_FAIL, WS(L, scalars), p->host_sc, next_ticket(p));
-  SFM_LAUNCH_CHECK(h, "sfm_ba_solve_pcg");
-  if (iters_host) *iters_host = cg.iters;
-  return SFM_OK;
-}
-
-extern "C" int sfm_ba_step(sfm_handle h, sfm_ba_problem p, const double* x, double scale, double* x_new) {
-  Lay L; int rc = check_problem(h, p, &L); if (rc) return rc;
-  double* ws = (double*)p->workspace;
-  const int C = p->n_cams, P = p->n_pts, D = p->cam_dim, n = C * D;
-  const int64_t N = p->n_obs, ntot = (int64_t)n + 3 * (int64_t)P;
-  double* part_x = WS(L, part_x);
-  sfm_prof_begin(h, SFM_PROF_STEP);
-  const unsigned nblk_x = cdiv(ntot, 256), nblk_rows = cdiv(2 * N, 256);
-  hipLaunchKernelGGL(k_axpy_step, dim3(nblk_x), dim3(256), 0, h->stream, (int64_t)n, ntot, x, WS(L, pc), WS(L, pp),
-                     scale, x_new, part_x);
-  DISPATCH_DT(D, p->precision, hipLaunchKernelGGL((k_step_obs<DD, TT>), dim3(nblk_rows), dim3(256), 0, h->stream, N, p->cam_idx,
-                                                  p->pt_idx, WST(L, recA), WST(L, recB), WS(L, pc), WS(L, pp), scale, WS(L, part_obs)));
-  rc = launch_cost(h, p, L, ws, x_new, WS(L, pc), scale, 1, nullptr); if (rc) return rc;
-  const int nreg = (D == 10 && p->apply_reg) ? C : 0;
-  hipLaunchKernelGGL(k_step_finalize, dim3(1), dim3(256), 0, h->stream, WS(L, part_obs), (int)L.nblk_obs,
-                     (int)nblk_rows, part_x, (int)nblk_x, WS(L, cost_reg), nreg, 1, WS(L, red_step));
-  sfm_prof_end(h, SFM_PROF_STEP);
-  SFM_LAUNCH_CHECK(h, "sfm_ba_step");
-  return SFM_OK;
-}
-
-extern "C" int sfm_ba_finish_step(sfm_handle h, sfm_ba_problem p, const double* x, double scale,
-                                  const double* x_new) {
-  Lay L; int rc = check_problem(h, p, &L); if (rc) return rc;
-  double* ws = (double*)p->workspace;
-  (void)x;
-  hipLaunchKernelGGL(k_finish_step, dim3(1), dim3(256), 0, h->stream, p->n_cams * p->cam_dim, WS(L, pc), scale,
-                     x_new, WS(L, red_step), WS(L, scalars), p->host_sc, next_ticket(p));
-  SFM_LAUNCH_CHECK(h, "sfm_ba_finish_step");
-  return SFM_OK;
-}
-
-// ---- ||x||^2 for the trust-region loop's initial radius (Delta_0 = ||x_0||, scipy trf.py:422-430)
-__global__ __launch_bounds__(256) void k_sq_partials(int64_t n, const double* __restrict__ v, double* __restrict__ part) {
-  __shared__ double s_red[4];
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const double t = i < n ? v[i] * v[i] : 0.0;
-  const double a = block_sum256(t, s_red);
-  if (threadIdx.x == 0) part[blockIdx.x] = a;
-}
-__global__ __launch_bounds__(256) void k_xnorm_finish(int n_c, const double* __restrict__ x, const double* __restrict__ red_step,
-                                                      double* __restrict__ sc, double* __restrict__ hsc, double seq) {
-  __shared__ double s_red[4];
-  double a = 0.0;
-  for (int i = threadIdx.x; i < n_c; i += 256) a += x[i] * x[i];
-  const double t = block_sum256(a, s_red);
-  if (threadIdx.x == 0) { sc[SFM_SC_XNEW_NORM2] = hsc[SFM_SC_XNEW_NORM2] = t + red_step[4]; publish_ticket(hsc, seq); }
-}
-int ba_xnorm_partial(sfm_ctx* h, sfm_ba_problem p, const double* x) {
-  Lay L; int rc = check_problem(h, p, &L); if (rc) return rc;
-  double* ws = (double*)p->workspace;
-  const int64_t n = (int64_t)p->n_cams * p->cam_dim, np3 = 3 * (int64_t)p->n_pts;
-  const unsigned nb = cdiv(np3, 256);       // part_x holds ((n + 3P + 255) / 256) * 2 + 2 doubles: enough
-  hipLaunchKernelGGL(k_sq_partials, dim3(nb), dim3(256), 0, h->stream, np3, x + n, WS(L, part_x));
-  hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, h->stream, WS(L, part_x), (int)nb, 1, WS(L, red_step) + 4);
-  SFM_LAUNCH_CHECK(h, "ba_xnorm_partial");
-  return SFM_OK;
-}
-int ba_xnorm_finish(sfm_ctx* h, sfm_ba_problem p, const double* x) {
-  Lay L; int rc = check_problem(h, p, &L); if (rc) return rc;
-  double* ws = (double*)p->workspace;
-  hipLaunchKernelGGL(k_xnorm_finish, dim3(1), dim3(256), 0, h->stream, p->n_cams * p->cam_dim, x, WS(L, red_step), WS(L, scalars), p->host_sc, next_ticket(p));
-  SFM_LAUNCH_CHECK(h, "ba_xnorm_finish");
-  return SFM_OK;
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return seen;
 }
 
 extern "C" int sfm_ba_read_scalars(sfm_handle h, sfm_ba_problem p, double* out_host) {
   Lay L; int rc = check_problem(h, p, &L); if (rc) return rc;
-  double* ws = (double*)p->workspace;
-  // every kernel that writes one of the scalars writes it into the problem's pinned host mirror too (p->host_sc): waiting for
-  // the stream is all that is left to do here - the 128-byte device-to-host copy was a blit kernel of its own in front of every
-  // one of these waits
-  // ... and not even that: the finishing kernel of the stage publishes its ticket behind the scalars, and the host spins on the
-  // ticket word of the pinned page - it sees the scalars ~1 us after the kernel's last store, where a stream synchronisation
-  // returns only after the kernel has been retired and its completion signal processed.  Every SPIN_QUERY spins the
-  // stream is asked as well: a drained stream ends the wait whatever was published (a path that publishes nothing).
+  // every kernel that writes one of the scalars writes it into the problem's pinned host mirror too (p->host_sc; the 128-byte
+  // device-to-host copy was a blit kernel of its own in front of every wait), and the finishing kernel of a stage publishes its
+  // ticket behind them: the host spins on the ticket word (ba_wait_for_word) and sees the scalars ~1 us after the kernel's last store,
+  // where a stream synchronisation returns only after the kernel has been retired and its completion signal processed.
   // SFM_POLL_SCALARS=0: wait for the stream.
-  {
-    static const bool poll_on = !(getenv("SFM_POLL_SCALARS") && getenv("SFM_POLL_SCALARS")[0] == '0');
-    bool seen = false;
-    if (poll_on && p->look_pending) {
-      volatile double* seq = p->host_sc + SFM_HSC_SEQ;
-      const double want = p->look_seq;
-      constexpr unsigned SPIN_QUERY = 4096;
-      for (unsigned spins = 1; ; ++spins) {
-        if (*seq == want) { seen = true; break; }
-        if ((spins % SPIN_QUERY) == 0 && hipStreamQuery(h->stream) != hipErrorNotReady) break;     // drained, or failed: the synchronisation below reports it
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-    }
-    p->look_pending = 0;
-    if (!seen) SFM_HIP(h, hipStreamSynchronize(h->stream));
-  }
-  if (p->cg2_pending) {
-    // the verdict of the persistent CG on the second system of the last damped solve (sfm_ba_finish_solve) arrived with this
-    // synchronisation; if that system did not converge - or its launch was abandoned - the q term is redone from the
-    // factorisation now (no exchange between ranks is involved: red_q has been reduced already)
-    p->cg2_pending = 0;
-    int status = 1, ran = 0, relaunched = 0;
-    {
-      // (a relaunch finds the same inputs: r~2 is still in cg_r, S~ in the factor's buffer)
-      const int C = p->n_cams, D = p->cam_dim, n = C * D;
-      DenseWs dw; dense_ws_carve(WS(L, dense), n, &dw);
-      PrFuse fuse = {WS(L, cg_Minv), nullptr, nullptr, WS(L, pc), WS(L, red_q), WS(L, scalars), p->host_sc, 1, p->look_seq};
-      const PrLaunch pl = {n, D, dw.Lm, WS(L, cg_r), WS(L, cg_z), WS(L, cg_mail), WS(L, cg_scal), CGS_RTOL, fuse, p->host_sc + SFM_HSC_CG2};
-      rc = cgs_persist_verdict(h, pl, p->sharded, &p->cg_iters, &status, &ran, &relaunched);
-      if (rc) return rc;
-    }
-    if (!(ran && status == 0)) {
-      if ((rc = finish_solve_by_factor(h, p, L, ws, 1, true))) return rc;
-      SFM_HIP(h, hipStreamSynchronize(h->stream));
-    }
-  }
+  static const bool poll_on = !(getenv("SFM_POLL_SCALARS") && getenv("SFM_POLL_SCALARS")[0] == '0');
+  const bool seen = poll_on && p->look_pending && ba_wait_for_word(h, p->host_sc + SFM_HSC_SEQ, p->look_seq);
+  p->look_pending = 0;
+  if (!seen) SFM_HIP(h, hipStreamSynchronize(h->stream));
+  if (p->cg2_pending && (rc = cgs_second_system_verdict(h, p, L))) return rc;
   memcpy(out_host, p->host_sc, SFM_SC_COUNT * sizeof(double));
   return SFM_OK;
 }
-

@@ -81,6 +81,7 @@ Lay ba_layout(int64_t C, int64_t P, int64_t N, int64_t D, int64_t n_items, int64
 void* sfm_scratch(sfm_ctx* h, size_t bytes);
 
 // ||x||^2 in two stages around the multi-rank reduction: the point part of this rank -> reduce_step[4], then
-// camera part + reduced point part -> scalar SFM_SC_XNEW_NORM2 (ba.hip; used by the trust-region loop's start)
+// camera part + reduced point part -> scalar SFM_SC_XNEW_NORM2 (ba_model.hip; used by the trust-region loop's start)
 int ba_xnorm_partial(sfm_ctx* h, sfm_ba_problem p, const double* x);
 int ba_xnorm_finish(sfm_ctx* h, sfm_ba_problem p, const double* x);
+#include "ba_stages.h"

@@ -1,6 +1,6 @@
 // Host-side planning of the bundle adjustment's camera solve: which route forms and solves the reduced camera system of a
 // damped solve, which assembler shape a camera count takes, and the prediction of systems the CG cannot finish.  Plain C++
-// (no HIP): included by ba_internal.h, executed by sfm_ba_schur_build / sfm_ba_schur_solve / sfm_ba_finish_solve (ba.hip), and
+// (no HIP): included by ba_internal.h, executed by sfm_ba_schur_build (ba.hip) / sfm_ba_schur_solve / sfm_ba_finish_solve (ba_camera_cg.hip), and
 // compiled on its own with the address and undefined-behaviour sanitizers by tests/test_host_logic.py
 // (tests/native/ba_plan_check.cpp, which defines SFM_BA_PLAN_STANDALONE).
 #pragma once

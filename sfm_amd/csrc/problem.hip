@@ -1,6 +1,6 @@
 // Construction of a bundle-adjustment problem on the device (gfx950): from the three arrays the reference packs
 // (camera index, point index, pixel per observation; /root/reference/utils/sfm_reconstruction.py:409-451) to the
-// index structure the kernels of ba.hip walk:
+// index structure the kernels of ba*.hip walk:
 //   pt_ptr            track (observation range) of every point            - boundaries of the point-major order
 //   cam_ptr, cam_obs  observations grouped by camera, ascending            - stable sort by camera id
 //   blk_ptr, pair_k, pair_k2   for every upper-triangular camera pair (c <= c2) the observation pairs (k, k2) that
@@ -11,7 +11,7 @@
 //   cch_*             the camera lists cut into chunks of <= 256 observations (one workgroup each)
 // sfm_amd/structure.py is the host-side mirror (NumPy); tests/test_ba_gpu.py checks the arrays bit for bit.
 // The two global stable sorts and the prefix sums are rocPRIM device primitives (set-up plumbing, once per
-// problem); everything per-iteration is hand-written in ba.hip / dense.hip.
+// problem); everything per-iteration is hand-written in ba*.hip / dense.hip.
 #include <cstdlib>
 #include <cstring>
 #include <vector>

@@ -2,7 +2,7 @@
 // scipy.optimize.least_squares(method='trf', loss='huber', ...) does at
 // /root/reference/utils/sfm_reconstruction.py:506-514, as trf_no_bounds (scipy _lsq/trf.py:401-560) with the
 // More' root finder for the Levenberg-Marquardt parameter (scipy _lsq/common.py:57-168), update_tr_radius and
-// check_termination (common.py:222-248, 705-717).  Every data-parallel stage runs on the device (ba.hip); the
+// check_termination (common.py:222-248, 705-717).  Every data-parallel stage runs on the device (ba*.hip); the
 // host only sees a handful of scalars per stage.  sfm_amd/trf.py is the same state machine in the host language
 // of the drop-in (it drives any backend, including the CPU stand-in of the multi-rank tests); the two are held
 // together by tests/test_ba_gpu.py::test_c_loop_equals_python_loop.

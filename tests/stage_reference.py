@@ -7,7 +7,7 @@ STAGE WAS GIVEN - on the GPU the device's own workspace regions - so a stage's b
 the conditioning of everything before it.  The same formulas run in float64 (dt=np.float64) are the "transcription" the CPU
 tests hold to the bounds and seed defects into; its worst ratios are where the non-derivable constants below come from.
 
-Formulas: the kernel comments of sfm_amd/csrc/ba.hip and SURVEY.md Appendix D.
+Formulas: the kernel comments of sfm_amd/csrc/ba.hip, ba_model.hip, ba_camera_cg.hip and SURVEY.md Appendix D.
   M_j = chol(C_j + alpha I)^-1 (packed m00 m10 m11 m20 m21 m22),  e_j = M_j g_pj
   G_k[m][a] = sum_r Jc~_k[r][a] (Jp~_k M_j^T)[r][m]
   S(c, c2) = [c == c2] B_c - sum_{pairs (k, k2) of the block} G_k^T G_k2      (alpha is NOT in the stored diagonal)

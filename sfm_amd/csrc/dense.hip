@@ -19,8 +19,9 @@
 //   k_inv64_fix / k_inv_merge : explicit inverses of the 128x128 diagonal blocks of L (both layouts), so that
 //   k_trsv_flow    : a whole triangular solve is one launch of n/128 workgroups handing their 128 unknowns
 //                    on through the output vector itself (k_trsv_step: one launch per block, for n > 16384).
+// Workspace layout, grids, tile decode, the launch schedule and the switches: dense_plan.h (checked on the CPU).
 #include "dense.h"
-#include <cstdlib>
+#include "dense_plan.h"
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 
@@ -51,24 +52,11 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   return v;
 }
 
-int64_t dense_ws_doubles(int n) {
-  const int64_t nb = (n + 127) / 128;
-  return 2 * 64 * 64 + 2 * nb * 128 * 128 + nb * 2 * 64 * 64 + 32 + align_up((int64_t)(n + 1) * n, 32) + (int64_t)n * n;
-}
-int64_t dense_ws_lm_offset(int n) {
-  const int64_t nb = (n + 127) / 128;
-  return 2 * 64 * 64 + 2 * nb * 128 * 128 + nb * 2 * 64 * 64 + 32;
-}
+int64_t dense_ws_doubles(int n) { return dense_ws_layout(n).total; }
+int64_t dense_ws_lm_offset(int n) { return dense_ws_layout(n).Lm; }
 void dense_ws_carve(double* base, int n, DenseWs* w) {
-  const int64_t nb = (n + 127) / 128;
-  double* p = base;
-  w->Ld = p; p += 2 * 64 * 64;
-  w->Dinv = p; p += nb * 128 * 128;
-  w->DinvT = p; p += nb * 128 * 128;
-  w->inv64 = p; p += nb * 2 * 64 * 64;
-  w->flag = (int*)p; p += 32;
-  w->Lm = p; p += align_up((int64_t)(n + 1) * n, 32);      // = base + dense_ws_lm_offset(n)
-  w->LmT = p;
+  const DenseWsLayout l = dense_ws_layout(n);
+  *w = DenseWs{base + l.Ld, base + l.Dinv, base + l.DinvT, base + l.inv64, (int*)(base + l.flag), base + l.Lm, base + l.LmT};
 }
 
 // ------------------------------------------------------------------------------------ Cholesky
@@ -386,7 +374,6 @@ __device__ __forceinline__ void trsm_rows16(const TrsmIn& in, const double* __re
 //      publishes its step data to Dn for the next launch, so the serial chain never waits for a kernel of its own.
 // A's panel columns are only read here (never overwritten), which is what makes step 1 race-free.
 constexpr int CHOL_STEP_SMEM = CRIT64_DOUBLES + 6 + 64 * LDM;     // 102.5 KB static (gfx950 allows up to 160 KB)
-constexpr int CHOL_STRIP_MIN_N = 4096;       // systems at least this large use the two-level (strip + rank-256 update) scheme
 // tile b of the step at panel j0 (see k_chol_step); all 256 threads of the workgroup, smem = CHOL_STEP_SMEM doubles
 // col_end < n (two-level scheme): only the trailing columns [j1, col_end) of the current 256-column strip are
 // updated (tiles enumerated column by column); the rest waits for the strip's rank-256 update (k_syrk_lower).
@@ -397,26 +384,10 @@ __device__ __forceinline__ void chol_tile(double* smem, int b, bool stage_d, dou
   double* sJ = smem + 64 * LDM;      // [64][LDM]   (the factor's buffers later reuse sI/sJ)
   double* sD = smem + CRIT64_DOUBLES + 6;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int nb = (n - j0) < 64 ? (n - j0) : 64;
-  const int j1 = j0 + nb;
-  const int rem_r = nrows - j1, rem_c = col_end - j1;
-  int ti, tj;
-  if (rem_c <= 0) {                     // no columns to update: one tile per 64 rows, panel solve only
-    ti = b; tj = 0;
-  } else if (col_end >= n) {
-    // 1-D order over the lower-triangular tiles only: b -> (ti, tj), tj <= ti, b = ti (ti + 1) / 2 + tj
-    ti = (int)((sqrtf(8.0f * (float)b + 1.0f) - 1.0f) * 0.5f);
-    while ((ti + 1) * (ti + 2) / 2 <= b) ++ti;
-    while (ti * (ti + 1) / 2 > b) --ti;
-    tj = b - ti * (ti + 1) / 2;
-  } else {
-    // strip: column tj holds the tiles ti = tj .. T - 1, columns one after the other (at most 4 of them)
-    const int T = (rem_r + 63) / 64;
-    tj = 0;
-    int rest = b;
-    while (rest >= T - tj) { rest -= T - tj; ++tj; }
-    ti = tj + rest;
-  }
+  const CholStep s = chol_step(n, nrows, j0, col_end);
+  const int nb = s.nb, j1 = s.j1, rem_r = s.rem_r, rem_c = s.rem_c;
+  const TileIJ t_ = chol_step_tile(b, s);
+  const int ti = t_.ti, tj = t_.tj;
   const int I0 = ti * 64, J0 = tj * 64;
   const int col16 = lane & 15, rq = lane >> 4;
   // prefetch the C tile this lane updates (rows 16 w + (lane>>4) + 4 i, cols 16 t + (lane&15))
@@ -447,11 +418,8 @@ __device__ __forceinline__ void chol_tile(double* smem, int b, bool stage_d, dou
         if (gr < nrows && col < nb) Lm[(size_t)gr * n + j0 + col] = xi[t][i];
       }
   }
-  const bool has_tile10 = rem_c > 0 && rem_r > 64;         // tile (1,0) exists in this launch
-  if (tj == 0 && !(ti == 0 && has_tile10)) {
-    // transposed copy for the forward solve, from the LDS tile so that the stores run along rows of LmT.  The
-    // rows of tile (0,0) - the workgroup that carries the serial chain - are written by tile (1,0), which has
-    // the same rows as its X_J
+  if (chol_tile_writes_own_lmt(s, ti, tj)) {
+    // transposed copy for the forward solve, from the LDS tile so that the stores run along rows of LmT
     for (int e = tid; e < 64 * 64; e += 256) {
       const int col = e >> 6, r = e & 63;
       const int gr = j1 + I0 + r;
@@ -459,12 +427,12 @@ __device__ __forceinline__ void chol_tile(double* smem, int b, bool stage_d, dou
     }
   }
   PHASE_T(2);
-  if (rem_c <= 0) return;                          // only the bordered row was left: nothing to update
+  if (!chol_step_looks_ahead(s)) return;           // strip end / only the bordered row was left: nothing to update, no next block
   const double* sJr = sI;
   if (ti != tj) {
     trsm_rows16(inJ, sD, sJ + w * 16 * LDM, lane, xj);
     sJr = sJ;
-    if (ti == 1 && tj == 0) {
+    if (chol_tile_writes_lmt_of_tile00(ti, tj)) {
       for (int e = tid; e < 64 * 64; e += 256) {
         const int col = e >> 6, r = e & 63;
         const int gr = j1 + r;
@@ -540,10 +508,8 @@ __device__ __forceinline__ void syrk_lower_body(double* __restrict__ C, int ldc,
   __shared__ double sA[128 * LDK], sB[128 * LDK];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wr = w >> 1, wc = w & 1;
-  int ti = (int)((sqrtf(8.0f * (float)blockIdx.x + 1.0f) - 1.0f) * 0.5f);
-  while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.x) ++ti;
-  while (ti * (ti + 1) / 2 > (int)blockIdx.x) --ti;
-  const int tj = (int)blockIdx.x - ti * (ti + 1) / 2;
+  const TileIJ t_ = tri_tile((int)blockIdx.x);
+  const int ti = t_.ti, tj = t_.tj;
   const int I0 = ti * 128, J0 = tj * 128;
   const bool diag = ti == tj;
   constexpr int TPR = NT / 128;                           // threads per staged row
@@ -796,11 +762,9 @@ __global__ __launch_bounds__(256) void k_trsv_step(const double* __restrict__ L,
 // solution with agent-scope atomic stores and each consumer thread polls ITS element with agent-scope atomic
 // loads, so a hand-off is one L2 round trip.  After its last dependency a block only has one 128x128
 // product (from registers) + the Dinv product (from LDS) left: the chain is n/128 hand-offs, not n/128 launches.
-// Every working workgroup must be resident at once: one per CU (134 KB of LDS).  Placement: workgroups go
-// round-robin over the 8 XCDs, so worker p sits at blockIdx 8 p + xcd(p) with 32 consecutive workers per XCD
-// (32 CUs each): hand-offs between neighbours stay inside one L2.  Progress: block g only waits for blocks that
-// never wait for g, the first block waits for none, and the idle workgroups of the grid exit at once.
-constexpr int TRSV_FLOW_MAX_BLOCKS = 128;
+// Every working workgroup must be resident at once: one per CU (134 KB of LDS); trsv_flow_worker (dense_plan.h)
+// places them.  Progress: block g only waits for blocks that never wait for g, the first block waits for none, and
+// the idle workgroups of the grid exit at once.
 __device__ __forceinline__ bool trsv_pending(double v) { return __double_as_longlong(v) == -1LL; }
 template <bool TRANSPOSE>
 __global__ __launch_bounds__(256) void k_trsv_flow(const double* __restrict__ L, const double* __restrict__ LT, int n,
@@ -811,9 +775,9 @@ __global__ __launch_bounds__(256) void k_trsv_flow(const double* __restrict__ L,
   __shared__ double sacc[128], sx[128], shalf[128];
   const int tid = threadIdx.x;
   const int nblk = (n + 127) / 128;
-  const int p = (int)blockIdx.x >> 3;                                          // position in the dependency order
-  if (((int)blockIdx.x & 7) != ((p >> 5) & 7)) return;
-  const int g = TRANSPOSE ? nblk - 1 - p : p;
+  int p;                                                                       // position in the dependency order
+  if (!trsv_flow_worker((int)blockIdx.x, p)) return;
+  const int g = trsv_flow_block(p, nblk, TRANSPOSE);
   const int r0 = g * 128;
   const int nbg = (n - r0) < 128 ? (n - r0) : 128;
   {
@@ -890,43 +854,32 @@ int dense_cholesky(sfm_ctx* h, double* A, int n, int nrows, const DenseWs& w) {
   // Two-level scheme from CHOL_STRIP_MIN_N on: inside a 256-column strip the 64-column steps only touch the
   // strip's own columns, the rest of the trailing matrix gets ONE rank-256 update per strip (k_syrk_lower) - 4x the
   // flops per byte streamed from HBM.  Small systems are a pure latency chain and keep the one-level scheme.
-  const char* strip_env = getenv("SFM_CHOL_STRIP_MIN_N");       // test knob
-  const int strip_min_n = strip_env ? atoi(strip_env) : CHOL_STRIP_MIN_N;
-  const int strip = n >= strip_min_n ? 256 : n;
-  int step = 0;
-  for (int jb = 0; jb < n; jb += strip) {
-    const int je = (jb + strip) < n ? (jb + strip) : n;            // columns [jb, je) form this strip
-    hipLaunchKernelGGL(k_chol_diag, dim3(1), dim3(256), 0, h->stream, A, w.Lm, n, jb, w.Ld + (size_t)(step & 1) * 64 * 64,
-                       w.inv64 + (size_t)(jb / 64) * 64 * 64, w.flag);
-    for (int j0 = jb; j0 < je; j0 += 64, ++step) {
-      const int nb = (n - j0) < 64 ? (n - j0) : 64;
-      const int j1 = j0 + nb;
-      const int below = nrows - j1;
-      if (below <= 0) break;
-      const unsigned T = cdiv(below, 64);
-      double* D = w.Ld + (size_t)(step & 1) * 64 * 64;
-      double* Dn = w.Ld + (size_t)((step + 1) & 1) * 64 * 64;
-      const int tcols = (int)cdiv(je - j1 > 0 ? je - j1 : 0, 64);  // tile columns still inside the strip
-      unsigned grid;
-      if (tcols == 0) grid = T;                                    // panel solve only (strip end / bordered row)
-      else if (je >= n) grid = T * (T + 1) / 2;                    // last (or only) strip: the whole trailing triangle
-      else { grid = 0; for (int c = 0; c < tcols; ++c) grid += T - c; }
-      hipLaunchKernelGGL(k_chol_step, dim3(grid), dim3(256), 0, h->stream, A, w.Lm, w.LmT, n, nrows, j0, je, D, Dn,
-                         w.inv64 + (size_t)(j1 / 64) * 64 * 64, w.flag);
+  for_each_chol_launch(n, nrows, dense_switches_from_env().strip_min_n, [&](const CholLaunch& l) {
+    const auto ld = [&](int slot) { return w.Ld + (size_t)slot * 64 * 64; };
+    const auto inv64 = [&](int block) { return w.inv64 + (size_t)block * 64 * 64; };
+    switch (l.kind) {
+      case CHOL_DIAG:
+        hipLaunchKernelGGL(k_chol_diag, dim3(l.grid), dim3(256), 0, h->stream, A, w.Lm, n, l.j0, ld(l.ld_write),
+                           inv64(l.inv64_block), w.flag);
+        break;
+      case CHOL_STEP:
+        hipLaunchKernelGGL(k_chol_step, dim3(l.grid), dim3(256), 0, h->stream, A, w.Lm, w.LmT, n, nrows, l.j0, l.col_end,
+                           ld(l.ld_read), ld(l.ld_write), inv64(l.inv64_block), w.flag);
+        break;
+      case CHOL_SYRK:
+        hipLaunchKernelGGL(k_syrk_lower, dim3(l.grid), dim3(512), 0, h->stream, A + l.c_off, n, w.Lm + l.x_off, n, l.R, l.Cn, l.K);
+        break;
+      case CHOL_INV64_FIX:
+        hipLaunchKernelGGL(k_inv64_fix, dim3(l.grid), dim3(256), 0, h->stream, w.Lm, n, w.inv64);
+        break;
+      case CHOL_IDENTITY:
+        hipLaunchKernelGGL(k_set_identity64, dim3(l.grid), dim3(256), 0, h->stream, inv64(l.inv64_block));
+        break;
+      case CHOL_MERGE:
+        hipLaunchKernelGGL(k_inv_merge, dim3(l.grid), dim3(256), 0, h->stream, w.Lm, n, w.inv64, w.Dinv, w.DinvT);
+        break;
     }
-    if (je < n) {
-      const int R = nrows - je, Cn = n - je;
-      const unsigned T2 = cdiv(R, 128);
-      hipLaunchKernelGGL(k_syrk_lower, dim3(T2 * (T2 + 1) / 2), dim3(512), 0, h->stream, A + (size_t)je * n + je, n,
-                         w.Lm + (size_t)je * n + jb, n, R, Cn, je - jb);
-    }
-  }
-  // 64x64 and then 128x128 diagonal-block inverses for the triangular solves
-  const unsigned nb64 = cdiv(n, 64), nb128 = cdiv(n, 128);
-  hipLaunchKernelGGL(k_inv64_fix, dim3(nb64), dim3(256), 0, h->stream, w.Lm, n, w.inv64);
-  if ((nb64 & 1u) != 0)             // odd number of 64-blocks: the partner of the last one is an identity block
-    hipLaunchKernelGGL(k_set_identity64, dim3(1), dim3(256), 0, h->stream, w.inv64 + (size_t)nb64 * 64 * 64);
-  hipLaunchKernelGGL(k_inv_merge, dim3(nb128), dim3(256), 0, h->stream, w.Lm, n, w.inv64, w.Dinv, w.DinvT);
+  });
   SFM_LAUNCH_CHECK(h, "dense_cholesky");
   return SFM_OK;
 }
@@ -934,28 +887,23 @@ int dense_cholesky(sfm_ctx* h, double* A, int n, int nrows, const DenseWs& w) {
 int dense_trsv(sfm_ctx* h, int n, const DenseWs& w, double* b, double* xout, int transpose) {
   const double* L = w.Lm;
   const int nblk = (n + 127) / 128;
-  const char* flow = getenv("SFM_TRSV_FLOW");       // "0": one launch per block (the path taken for n > 16384)
-  if (nblk <= TRSV_FLOW_MAX_BLOCKS && !(flow && flow[0] == '0')) {
+  if (trsv_takes_flow(nblk, dense_switches_from_env())) {
     if (hipMemsetAsync(xout, 0xFF, (size_t)n * sizeof(double), h->stream) != hipSuccess)     // "not published yet"
       return sfm_fail(h, SFM_ERR_HIP, "dense_trsv", "memset");
     if (transpose)
-      hipLaunchKernelGGL(k_trsv_flow<true>, dim3(8 * nblk), dim3(256), 0, h->stream, L, w.LmT, n, w.Dinv, w.DinvT, b, xout, w.flag);
+      hipLaunchKernelGGL(k_trsv_flow<true>, dim3(trsv_flow_grid(nblk)), dim3(256), 0, h->stream, L, w.LmT, n, w.Dinv, w.DinvT, b, xout, w.flag);
     else
-      hipLaunchKernelGGL(k_trsv_flow<false>, dim3(8 * nblk), dim3(256), 0, h->stream, L, w.LmT, n, w.Dinv, w.DinvT, b, xout, w.flag);
+      hipLaunchKernelGGL(k_trsv_flow<false>, dim3(trsv_flow_grid(nblk)), dim3(256), 0, h->stream, L, w.LmT, n, w.Dinv, w.DinvT, b, xout, w.flag);
     SFM_LAUNCH_CHECK(h, "dense_trsv");
     return SFM_OK;
   }
   if (!transpose) {
     for (int blk = 0; blk < nblk; ++blk) {
-      const int after = n - (blk * 128 + 128);
-      const unsigned g = after > 0 ? cdiv(after, 32) : 1;
-      hipLaunchKernelGGL(k_trsv_step, dim3(g), dim3(256), 0, h->stream, L, n, w.Dinv, w.DinvT, b, xout, blk, 0);
+      hipLaunchKernelGGL(k_trsv_step, dim3(trsv_step_grid_forward(n, blk)), dim3(256), 0, h->stream, L, n, w.Dinv, w.DinvT, b, xout, blk, 0);
     }
   } else {
     for (int blk = nblk - 1; blk >= 0; --blk) {
-      const int before = blk * 128;
-      const unsigned g = before > 0 ? cdiv(before, 256) : 1;
-      hipLaunchKernelGGL(k_trsv_step, dim3(g), dim3(256), 0, h->stream, L, n, w.Dinv, w.DinvT, b, xout, blk, 1);
+      hipLaunchKernelGGL(k_trsv_step, dim3(trsv_step_grid_backward(blk)), dim3(256), 0, h->stream, L, n, w.Dinv, w.DinvT, b, xout, blk, 1);
     }
   }
   SFM_LAUNCH_CHECK(h, "dense_trsv");
@@ -963,10 +911,19 @@ int dense_trsv(sfm_ctx* h, int n, const DenseWs& w, double* b, double* xout, int
 }
 
 // ------------------------------------------------------------------------------------ exported helpers (tests)
+namespace {
+struct ScratchWs {      // the helpers' own workspace: freed on every return, checked where the call succeeded
+  double* p = nullptr;
+  ~ScratchWs() { if (p) (void)hipFree(p); }
+  hipError_t release() { double* q = p; p = nullptr; return hipFree(q); }
+};
+}  // namespace
+
 extern "C" int sfm_dense_cholesky(sfm_handle h, double* a, int32_t n, int32_t* fail_flag) {
   if (!h || !a || n < 1 || !fail_flag) return SFM_ERR_ARG;
-  double* base = nullptr;
-  SFM_HIP(h, hipMalloc(&base, (size_t)dense_ws_doubles(n) * sizeof(double)));
+  ScratchWs ws;
+  SFM_HIP(h, hipMalloc(&ws.p, (size_t)dense_ws_doubles(n) * sizeof(double)));
+  double* const base = ws.p;
   DenseWs w; dense_ws_carve(base, n, &w);
   w.flag = fail_flag;
   SFM_HIP(h, hipMemsetAsync(fail_flag, 0, sizeof(int), h->stream));
@@ -974,7 +931,7 @@ extern "C" int sfm_dense_cholesky(sfm_handle h, double* a, int32_t n, int32_t* f
   int rc = dense_cholesky(h, a, n, n, w);
   SFM_HIP(h, hipMemcpyAsync(a, w.Lm, (size_t)n * n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
   SFM_HIP(h, hipStreamSynchronize(h->stream));
-  SFM_HIP(h, hipFree(base));
+  SFM_HIP(h, ws.release());
   return rc;
 }
 
@@ -988,8 +945,9 @@ __global__ __launch_bounds__(256) void k_transpose_copy(const double* __restrict
 
 extern "C" int sfm_dense_trsv(sfm_handle h, const double* l, int32_t n, double* b, int transpose) {
   if (!h || !l || !b || n < 1) return SFM_ERR_ARG;
-  double* base = nullptr;
-  SFM_HIP(h, hipMalloc(&base, ((size_t)dense_ws_doubles(n) + n) * sizeof(double)));
+  ScratchWs ws;
+  SFM_HIP(h, hipMalloc(&ws.p, ((size_t)dense_ws_doubles(n) + n) * sizeof(double)));
+  double* const base = ws.p;
   DenseWs w; dense_ws_carve(base, n, &w);          // w.flag points into the workspace
   SFM_HIP(h, hipMemsetAsync(w.flag, 0, sizeof(int), h->stream));
   double* xout = base + dense_ws_doubles(n);
@@ -1003,6 +961,6 @@ extern "C" int sfm_dense_trsv(sfm_handle h, const double* l, int32_t n, double* 
     SFM_HIP(h, hipMemcpyAsync(b, xout, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     SFM_HIP(h, hipStreamSynchronize(h->stream));
   }
-  SFM_HIP(h, hipFree(base));
+  SFM_HIP(h, ws.release());
   return rc;
 }

@@ -383,6 +383,29 @@ def test_ba_plan_under_address_and_ub_sanitizers(tmp_path):
     assert run.returncode == 0 and run.stdout.startswith("ok "), (run.stdout, run.stderr[-2000:])
 
 
+def test_dense_plan_under_address_and_ub_sanitizers(tmp_path):
+    """sfm_amd/csrc/dense_plan.h (the dense solver's workspace layout, the map between a workgroup and its tile, the
+    schedule of a factorisation launch by launch, the placement of the triangular solves, the two switches) is plain
+    C++: built here with g++ -fsanitize=address,undefined and replayed tile by tile for n = 1 ... 1,400, with and without the
+    bordered row, one-level and in strips (tests/native/dense_plan_check.cpp lists what it asserts).  It prints the tiles
+    visited and the workgroups whose column range is empty (270 over that sweep, all on bordered systems)."""
+    import shutil, subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = tmp_path / "dense_plan_check"
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-fno-omit-frame-pointer", "-I" + os.path.join(root, "sfm_amd", "csrc"),
+           os.path.join(root, "tests", "native", "dense_plan_check.cpp"), "-o", str(exe)]
+    build = subprocess.run(cmd, capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True,
+                         env={k: v for k, v in os.environ.items()
+                              if not k.startswith("SFM_CHOL_") and not k.startswith("SFM_TRSV_")})
+    print(run.stdout, end="")
+    assert run.returncode == 0 and run.stdout.startswith("ok "), (run.stdout, run.stderr[-2000:])
+
+
 class _DenseFitBackend:
     """The problem of tests/native/trf_loop_check.cpp in NumPy, behind the backend protocol of sfm_amd/trf.py."""
 

@@ -678,6 +678,66 @@ int sfm_tracks_evaluate(sfm_handle h, const double* proj, int32_t n_cams, const 
                         double* obs_err /* [n_obs], may be NULL */, int64_t* counts /* [6] */,
                         void* workspace, int64_t workspace_bytes);
 
+/* ------------------------------------------------------------------- robust triangulation: drop observations, not points
+ * Tracks are connected components of pairwise matches, so one wrong match puts a foreign keypoint into a good track, and
+ * sfm_triangulate_tracks then fails the whole track.  sfm_triangulate_tracks_robust takes the arguments of
+ * sfm_triangulate_tracks and adds a per-observation inlier flag (sfm_amd/csrc/triangulate_robust.h).  For one track, with
+ * its used observations in track order: an observation is sound when its pixel, P and C are finite; it agrees with a
+ * point X when it is sound, its depth P[2].(X,1) > 0 and its reprojection error e <= max_error.
+ *   Step 1: the rule of sfm_triangulate_tracks over all used observations.  Status 0 is returned as it is - X, max_err
+ *   and n_views are the bits of sfm_triangulate_tracks - with obs_inlier = 1 for every used observation and n_inliers =
+ *   n_views.  A failing track with fewer than 4 sound observations is returned as it is too, with obs_inlier = 0
+ *   everywhere and n_inliers = 0: two or three views cannot tell which one is wrong, a pair always fits itself and a
+ *   consensus needs a third, confirming view.
+ *   Step 2: with s sound observations and M = s (s - 1) / 2 pairs (a, b), a < b, over them in lexicographic order,
+ *   hypothesis h (0 <= h < min(M, H), H = SFM_TRI_ROBUST_PAIRS) uses pair number h when M <= H and pair number
+ *   (h * M) / H in 64-bit integers otherwise.  Its point is the DLT of sfm_triangulate2 of the two observations.  It is
+ *   void when v[3] == 0, the point is not finite, either depth is <= 0, or min_angle_deg > 0 and the two rays do not pass
+ *   the angle gate.  Its score is the number of used observations that agree with its point.  The winner has the highest
+ *   score; ties go to the lowest h.  When no hypothesis scores at least max(min_views, 3) the failing result of step 1
+ *   is returned as above.
+ *   Step 3: the rule of sfm_triangulate_tracks over the observations that agree with the winner's point, with min_views
+ *   = max(min_views, 3) and the caller's refine_iters and gates.  A status other than 0 returns the failing result of
+ *   step 1.  Otherwise status is 0, X is the refit point, obs_inlier [n_obs] uint8 is 1 exactly for the used observations
+ *   that agree with X (a superset of the refit's own set), n_inliers counts them, max_err is their largest error and
+ *   n_views stays the number of used observations.
+ * obs_inlier is 0 for unused observations, for tracks without a point and for an observation that no track covers (the
+ * call zeroes the array first).  counts [6] int64: tracks by status.  Two passes: one thread per track runs step 1 and
+ * appends the failing tracks with at least 4 sound observations to a work list in the workspace (a wavefront ballot and
+ * one integer atomic add per wavefront); then one wavefront per entry runs hypothesis h on lane h, takes the winner by an integer wave
+ * reduction on (score, -lane) and refits once.  The second launch does not depend on the length of the list, nothing is
+ * read back and the outputs do not depend on the order of the list: a track's outputs depend on its used observations
+ * in their order and on nothing else.  Argument checks, return codes and n_tracks == 0 as sfm_triangulate_tracks.
+ * The workspace holds, each rounded up to 256 bytes: the camera centres [n_cams][3] float64, the work list [n_tracks]
+ * int32 (track indices in no particular order) and its length, one int32 - after the call the number of tracks that went
+ * through the second pass, which a caller may read.
+ *
+ * sfm_tracks_classify is sfm_tracks_evaluate over the observations that agree with the given X: same arguments, the
+ * workspace of sfm_triangulate_tracks_workspace_bytes, one thread per track.  A track with has_point == 0 gets
+ * SFM_EVAL_NO_POINT, its n_views is still counted, n_inliers = 0, max_err NaN, and it is left out of counts.  Every other
+ * track: n_views used observations, n_inliers of them agree with X, obs_inlier flags them, and status is
+ * SFM_TRI_TOO_FEW_VIEWS (n_inliers < min_views; a non-finite X lands here; max_err NaN), SFM_TRI_LOW_ANGLE (no pair of
+ * inliers passes the angle gate) or 0; max_err is the largest error of an inlier.  obs_err as sfm_tracks_evaluate.  Fed
+ * the X of sfm_triangulate_tracks_robust with the same cameras and gates, a track of status 0 gets status 0, the same
+ * flags, the same n_inliers and the same max_err bits.  obs_inlier is zeroed first here too.  Both calls run on the
+ * handle's stream without host synchronisation. */
+enum { SFM_TRI_ROBUST_PAIRS = 64 };
+int sfm_triangulate_tracks_robust_workspace_bytes(int32_t n_cams, int64_t n_tracks, int64_t* bytes_host);
+int sfm_triangulate_tracks_robust(sfm_handle h, const double* proj, int32_t n_cams, const int32_t* cam_of_image,
+                                  int32_t n_img, const int64_t* kp_ptr, const double* kp_xy, int64_t n_nodes,
+                                  const int64_t* track_ptr, int64_t n_tracks, const int32_t* obs_image,
+                                  const int32_t* obs_kp, int64_t n_obs, int32_t min_views, int32_t refine_iters,
+                                  double max_error, double min_angle_deg, double* X, int32_t* status, int32_t* n_views,
+                                  int32_t* n_inliers, double* max_err, uint8_t* obs_inlier /* [n_obs] */,
+                                  int64_t* counts /* [6] by status */, void* workspace, int64_t workspace_bytes);
+int sfm_tracks_classify(sfm_handle h, const double* proj, int32_t n_cams, const int32_t* cam_of_image, int32_t n_img,
+                        const int64_t* kp_ptr, const double* kp_xy, int64_t n_nodes, const int64_t* track_ptr,
+                        int64_t n_tracks, const int32_t* obs_image, const int32_t* obs_kp, int64_t n_obs,
+                        const double* X, const uint8_t* has_point, int32_t min_views, double max_error,
+                        double min_angle_deg, int32_t* status, int32_t* n_views, int32_t* n_inliers, double* max_err,
+                        uint8_t* obs_inlier /* [n_obs] */, double* obs_err /* [n_obs], may be NULL */,
+                        int64_t* counts /* [6] */, void* workspace, int64_t workspace_bytes);
+
 /* ------------------------------------------------------------------- 2D-3D correspondences of the unregistered images
  * What sfm_pnp_ransac consumes, taken from the tracks by index.  Node n of image i (kp_ptr[i] <= n < kp_ptr[i+1]) is
  * listed when cam_of_image[i] < 0, 0 <= node_track[n] < n_tracks and has_point[node_track[n]] != 0: integers only, so a

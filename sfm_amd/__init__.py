@@ -6,7 +6,7 @@ from .homography import HomographyMixin, estimate_homography_batched, find_homog
 from .pose import InitialPairMixin, recover_pose, recover_pose_batched  # noqa: F401
 from .tracks import Tracks, build_tracks, tracks_from_pair_files  # noqa: F401
 from .triangulate import Triangulation, triangulate_tracks, triangulate_tracks_raw  # noqa: F401
-from .incremental import Reconstruction, evaluate_tracks, reconstruct_tracks, resection_lists  # noqa: F401
+from .incremental import Reconstruction, classify_tracks, evaluate_tracks, reconstruct_tracks, resection_lists  # noqa: F401
 from .features import Features, detect_and_describe_batched, detect_features  # noqa: F401
 from .interchange import read_pnm, write_pnm  # noqa: F401
 from .guided import guided_match_pairs  # noqa: F401

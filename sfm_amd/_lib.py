@@ -154,6 +154,11 @@ SIGNATURES = {
                                          vp, vp, vp, vp, vp, vp, i64]),
     "sfm_tracks_evaluate": (C.c_int, [vp, vp, i32, vp, i32, vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, i32, f64, f64,
                                       vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_triangulate_tracks_robust_workspace_bytes": (C.c_int, [i32, i64, C.POINTER(i64)]),
+    "sfm_triangulate_tracks_robust": (C.c_int, [vp, vp, i32, vp, i32, vp, vp, i64, vp, i64, vp, vp, i64, i32, i32, f64, f64,
+                                                vp, vp, vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_tracks_classify": (C.c_int, [vp, vp, i32, vp, i32, vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, i32, f64, f64,
+                                      vp, vp, vp, vp, vp, vp, vp, vp, i64]),
     "sfm_resection_workspace_bytes": (C.c_int, [i64, C.POINTER(i64)]),
     "sfm_tracks_resection": (C.c_int, [vp, vp, i32, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64]),
     "sfm_orb_default_pattern": (C.c_int, [vp]),

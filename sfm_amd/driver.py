@@ -278,10 +278,12 @@ class DriverMixin:
     def triangulate_tracks(self, tracks, keypoints, **options):
         """N-view triangulation of a `Tracks` object against `self.poses` / `self.K` (sfm_amd.triangulate): sets
         `self.points3D` and `self.point_tracks` ({image_id: [x, y]} over the registered images only) to the valid tracks
-        and returns the `Triangulation`."""
+        and returns the `Triangulation`.  `robust=True` drops outlier observations instead of points; the rejected
+        observations are left out of `self.point_tracks`."""
         from .triangulate import triangulate_tracks
         options.setdefault("device", getattr(self, "ba_device", 0))
-        tri = triangulate_tracks(tracks, keypoints, dict(self.poses), K=self.K, **options)
+        robust = bool(options.pop("robust", False))
+        tri = triangulate_tracks(tracks, keypoints, dict(self.poses), K=self.K, robust=robust, **options)
         ids = tracks.image_ids if tracks.image_ids is not None else list(range(len(tracks.kp_ptr) - 1))
         sel, pt = tri._valid_observations()
         point_tracks = [dict() for _ in range(int(tri.valid.sum()))]

@@ -5,6 +5,8 @@
                       image, taken from the tracks by index - what PnP consumes, and their counts rank the next view
   `evaluate_tracks`   sfm_tracks_evaluate (sfm_amd/csrc/triangulate.hip): the triangulation gates at points that are
                       given - what a bundle adjustment leaves behind
+  `classify_tracks`   sfm_tracks_classify (sfm_amd/csrc/triangulate_robust.hip): the same gates over the observations
+                      that agree with the point, and a flag per observation - the loop's `robust_tracks` mode
 
 For the life of a `reconstruct_tracks` call the CSR arrays, kp_ptr, kp_xy, node_track, X and has_point live in device
 tensors uploaded once; per step only the cameras go up and only the correspondence lists, statuses and counts come
@@ -36,7 +38,7 @@ class _Scene:
     """The device-resident arrays of one data set and the three device calls on them.  Everything stays on the device
     between calls; the methods return only what the host loop decides on."""
 
-    def __init__(self, kp_ptr, kp_xy, node_track, track_ptr, obs_image, obs_kp, device):
+    def __init__(self, kp_ptr, kp_xy, node_track, track_ptr, obs_image, obs_kp, device, robust=False):
         import torch
         self.torch = torch
         self.h = _lib.get_handle(device)
@@ -57,6 +59,14 @@ class _Scene:
         self.counts = torch.empty(6, dtype=torch.int64, device=dev)
         self.proj = self.cam_of_image = self.ws_tri = None
         self.n_cams = 0
+        self.robust = bool(robust)
+        if self.robust:
+            # per observation: the flag of the loop's state, the flags of the last robust triangulation, its track
+            self.obs_inlier = torch.zeros(max(self.n_obs, 1), dtype=torch.uint8, device=dev)
+            self.obs_inlier_tri = torch.zeros(max(self.n_obs, 1), dtype=torch.uint8, device=dev)
+            self.n_inliers = torch.empty(T, dtype=torch.int32, device=dev)
+            self.obs_track = torch.zeros(max(self.n_obs, 1), dtype=torch.int64, device=dev)
+            self.obs_track[:self.n_obs] = torch.repeat_interleave(torch.arange(T, device=dev), self.track_ptr[1:] - self.track_ptr[:-1])
         need = C.c_int64()
         self.h.check(self.h.lib.sfm_resection_workspace_bytes(self.n_nodes, C.byref(need)), "sfm_resection_workspace_bytes")
         self.ws_res, self.ws_res_bytes = torch.empty(need.value, dtype=torch.uint8, device=dev), need.value
@@ -89,6 +99,10 @@ class _Scene:
         self.h.check(self.h.lib.sfm_triangulate_tracks_workspace_bytes(self.n_cams, C.byref(need)),
                      "sfm_triangulate_tracks_workspace_bytes")
         self.ws_tri, self.ws_tri_bytes = torch.empty(need.value, dtype=torch.uint8, device=self.dev), need.value
+        if self.robust:
+            self.h.check(self.h.lib.sfm_triangulate_tracks_robust_workspace_bytes(self.n_cams, self.n_tracks, C.byref(need)),
+                         "sfm_triangulate_tracks_robust_workspace_bytes")
+            self.ws_rob, self.ws_rob_bytes = torch.empty(need.value, dtype=torch.uint8, device=self.dev), need.value
 
     def resection(self):
         """(seg_ptr [n_img+1] int64, corr_node, corr_track int32, corr_X [n,3] float64, corr_uv [n,2] float32) on the host."""
@@ -114,12 +128,27 @@ class _Scene:
                     _p(self.X_tri), _p(self.status), _p(self.n_views), _p(self.max_err), _p(self.counts), _p(self.ws_tri),
                     self.ws_tri_bytes)
 
+    def triangulate_robust(self, min_views, refine_iters, max_error, min_angle_deg):
+        """sfm_triangulate_tracks_robust over all tracks into X_tri / status / n_views / n_inliers / max_err / counts and
+        obs_inlier_tri (device)."""
+        from .driver import _p
+        self.h.call("sfm_triangulate_tracks_robust", _p(self.proj), self.n_cams, _p(self.cam_of_image), self.n_img,
+                    _p(self.kp_ptr), _p(self.kp_xy), self.n_nodes, _p(self.track_ptr), self.n_tracks, _p(self.obs_image),
+                    _p(self.obs_kp), self.n_obs, int(min_views), int(refine_iters), C.c_double(max_error),
+                    C.c_double(min_angle_deg), _p(self.X_tri), _p(self.status), _p(self.n_views), _p(self.n_inliers),
+                    _p(self.max_err), _p(self.obs_inlier_tri), _p(self.counts), _p(self.ws_rob), self.ws_rob_bytes)
+
     def adopt_new_points(self, **gates):
         """Triangulate, then adopt the points of status 0 for tracks without a point; existing points stay.  Returns the
-        number adopted (one integer comes down)."""
+        number adopted (one integer comes down).  In the robust mode the adopted tracks take their flags with them."""
         torch = self.torch
-        self.triangulate(**gates)
+        if self.robust:
+            self.triangulate_robust(**gates)
+        else:
+            self.triangulate(**gates)
         new = (self.has_point == 0) & (self.status == _lib.TRI_OK)
+        if self.robust:
+            self.obs_inlier = torch.where(new[self.obs_track], self.obs_inlier_tri, self.obs_inlier)
         self.X = torch.where(new[:, None], self.X_tri, self.X)
         self.has_point |= new.to(torch.uint8)
         return int(new.sum().item())
@@ -135,11 +164,36 @@ class _Scene:
                     _p(self.counts), _p(self.ws_tri), self.ws_tri_bytes)
         return obs_err[:self.n_obs] if want_obs_err else None
 
+    def classify(self, min_views, max_error, min_angle_deg, want_obs_err=False):
+        """sfm_tracks_classify at X / has_point into status / n_views / n_inliers / max_err / counts and obs_inlier, the
+        flags of the loop's state: those of every track that has a point are refreshed, the others are 0."""
+        from .driver import _p
+        obs_err = self.torch.empty(max(self.n_obs, 1), dtype=self.torch.float64, device=self.dev) if want_obs_err else None
+        self.h.call("sfm_tracks_classify", _p(self.proj), self.n_cams, _p(self.cam_of_image), self.n_img, _p(self.kp_ptr),
+                    _p(self.kp_xy), self.n_nodes, _p(self.track_ptr), self.n_tracks, _p(self.obs_image), _p(self.obs_kp),
+                    self.n_obs, _p(self.X), _p(self.has_point), int(min_views), C.c_double(max_error),
+                    C.c_double(min_angle_deg), _p(self.status), _p(self.n_views), _p(self.n_inliers), _p(self.max_err),
+                    _p(self.obs_inlier), _p(obs_err), _p(self.counts), _p(self.ws_tri), self.ws_tri_bytes)
+        return obs_err[:self.n_obs] if want_obs_err else None
+
+    def observations_rejected(self):
+        """The observations in registered images, of tracks that have a point, whose flag is 0 (one integer comes down)."""
+        if self.n_obs == 0:
+            return 0
+        used = self.cam_of_image[self.obs_image.long()] >= 0
+        return int((used & (self.has_point[self.obs_track[:self.n_obs]] != 0) & (self.obs_inlier[:self.n_obs] == 0)).sum().item())
+
     def drop_failing_points(self, **gates):
-        """Evaluate, then every point whose status is not 0 loses has_point.  Returns the number dropped."""
-        self.evaluate(**gates)
+        """Evaluate - in the robust mode: classify - then every point whose status is not 0 loses has_point (and its
+        flags).  Returns the number dropped."""
+        if self.robust:
+            self.classify(**gates)
+        else:
+            self.evaluate(**gates)
         bad = (self.has_point != 0) & (self.status != _lib.TRI_OK)
         self.has_point &= ~bad.to(self.torch.uint8) & 1
+        if self.robust:
+            self.obs_inlier &= ~bad[self.obs_track].to(self.torch.uint8) & 1
         return int(bad.sum().item())
 
 
@@ -201,12 +255,41 @@ def evaluate_tracks(tracks, keypoints, proj_or_poses, X, has_point, K=None, regi
             "obs_err": obs_err.cpu().numpy(), "counts": sc.counts.cpu().numpy()}
 
 
+def classify_tracks(tracks, keypoints, proj_or_poses, X, has_point, K=None, registered=None, min_views=2,
+                    max_error=TRIANGULATION_MAX_ERROR, min_angle_deg=0.0, device=0):
+    """`evaluate_tracks` over the observations that agree with the given points (sfm_tracks_classify): an observation is
+    an inlier when it is finite, lies in front of its camera and reprojects within max_error.  Same arguments.  Returns
+    {status [n] int32 (0, TRI_TOO_FEW_VIEWS: fewer than min_views inliers, TRI_LOW_ANGLE, or EVAL_NO_POINT = -1 where
+    has_point is 0), n_views [n] int32, n_inliers [n] int32, max_err [n] (the largest error of an inlier), obs_inlier
+    [n_obs] bool, obs_err [n_obs] (NaN: image not registered or no point), counts [6] int64 (the tracks that have a point,
+    by status)}."""
+    _check_options(min_views, 0, max_error, min_angle_deg)
+    _check_tracks(tracks, keypoints)
+    X = np.asarray(X, dtype=np.float64).reshape(-1, 3)
+    has_point = np.asarray(has_point).reshape(-1)
+    if len(X) != len(tracks) or len(has_point) != len(tracks):
+        raise ValueError("X / has_point need one entry per track")
+    proj, cam_of_image = _cameras(tracks, proj_or_poses, K, registered)
+    kp_xy = keypoint_table(tracks, keypoints)
+    if len(tracks) == 0:
+        return {"status": np.zeros(0, np.int32), "n_views": np.zeros(0, np.int32), "n_inliers": np.zeros(0, np.int32),
+                "max_err": np.zeros(0), "obs_inlier": np.zeros(0, bool), "obs_err": np.zeros(0), "counts": np.zeros(6, np.int64)}
+    sc = _Scene(tracks.kp_ptr, kp_xy, np.zeros(0, np.int32), tracks.track_ptr, tracks.image, tracks.keypoint, device, robust=True)
+    sc.set_points(X, has_point)
+    sc.set_cameras(proj, cam_of_image)
+    obs_err = sc.classify(min_views, max_error, min_angle_deg, want_obs_err=True)
+    return {"status": sc.status.cpu().numpy(), "n_views": sc.n_views.cpu().numpy(), "n_inliers": sc.n_inliers.cpu().numpy(),
+            "max_err": sc.max_err.cpu().numpy(), "obs_inlier": sc.obs_inlier[:sc.n_obs].cpu().numpy() != 0,
+            "obs_err": obs_err.cpu().numpy(), "counts": sc.counts.cpu().numpy()}
+
+
 # ------------------------------------------------------------------------------------------------------------ the loop
 class Reconstruction:
     """What `reconstruct_tracks` returns.  poses {image position: (R [3,3], t [3])}, order (registration order), K (the
     intrinsics the cameras were last evaluated with), X [n_tracks,3] (NaN without a point), has_point [n_tracks] bool,
     status [n_tracks] int32 from the last evaluation (-1 without a point), unregistered (image positions), log (one dict
-    per step)."""
+    per step), obs_inlier ([n_obs] bool from `robust_tracks=True`: the observations a point is kept with - the others are
+    left out of `ba_inputs()` and `as_state()`; None otherwise)."""
 
     def __init__(self, tracks, kp_xy, K):
         self.tracks, self._kp_xy = tracks, kp_xy
@@ -216,6 +299,7 @@ class Reconstruction:
         self.X = np.full((n, 3), np.nan)
         self.has_point = np.zeros(n, bool)
         self.status = np.full(n, _lib.EVAL_NO_POINT, np.int32)
+        self.obs_inlier = None
 
     def cam_of_image(self):
         cam = np.full(len(self.tracks.kp_ptr) - 1, -1, dtype=np.int32)
@@ -227,11 +311,14 @@ class Reconstruction:
         return np.asarray([projection_matrix(self.K, *self.poses[i]) for i in self.order], dtype=np.float64).reshape(-1, 3, 4)
 
     def _observations(self):
-        """(observation indices, point index of each) over the tracks with a point and the registered images."""
+        """(observation indices, point index of each) over the tracks with a point and the registered images; with
+        obs_inlier, over the inlier observations only."""
         tr = self.tracks
         new_id = np.cumsum(self.has_point) - 1
         trk = np.repeat(np.arange(len(tr)), tr.lengths())
         sel = np.flatnonzero(self.has_point[trk] & (self.cam_of_image()[tr.image] >= 0)) if tr.n_obs else np.zeros(0, np.int64)
+        if self.obs_inlier is not None:
+            sel = sel[self.obs_inlier[sel]]
         return sel, new_id[trk[sel]]
 
     def ba_inputs(self, cam_dim=6):
@@ -352,7 +439,8 @@ def _initial_pair(tracks, kp_xy, K, initial_pair, o, device):
 DEFAULTS = dict(initial_candidates=32, min_initial_points=50, min_visible=15, candidates_per_step=8, pnp_threshold=8.0,
                 pnp_hypotheses=1024, pnp_min_inliers=15, seed=0, ba_every=7, cam_dim=6, max_error=TRIANGULATION_MAX_ERROR,
                 min_angle_deg=1.0, refine_iters=5, min_views=2, fund_threshold=3.0, fund_hypotheses=1024,
-                refine_initial_pair=True, image_size=(1024, 768), initial_model="fundamental", max_homography_ratio=None)
+                refine_initial_pair=True, image_size=(1024, 768), initial_model="fundamental", max_homography_ratio=None,
+                robust_tracks=False)
 
 
 def reconstruct_tracks(tracks, keypoints, K, initial_pair=None, device=0, **options):
@@ -370,6 +458,13 @@ def reconstruct_tracks(tracks, keypoints, K, initial_pair=None, device=0, **opti
     left out (SfmError if that leaves none).  0.8 is the customary value (COLMAP's, recalled).  The NumPy reference
     (tests/test_homography_reference.py: 512 hypotheses at 3 px, 40 and 300 matches, 0 % and 30 % outliers) gives
     n_H / n_F of 0.07 to 0.19 on a general scene and 0.90 to 1.00 on a pure rotation and on a plane.
+    `robust_tracks` (default False) drops outlier observations instead of points: tracks are triangulated by
+    sfm_triangulate_tracks_robust (a failing track of at least 4 views is searched for a consensus of at least 3), every
+    observation carries an inlier flag that sfm_tracks_classify refreshes after every registration and every bundle
+    adjustment, the bundle adjustment sees the inlier observations only, a point is dropped when fewer than `min_views`
+    observations agree with it or those fail the angle gate, and the log entries gain `observations_rejected` (the result of a bundle
+    adjustment in the log also `observations_newest_camera`, what it saw of the camera registered last).  PnP is
+    robust by itself and sees every point as before.
     Options and their defaults: `DEFAULTS`.  keypoints: per image position an [n,2] array or cv2.KeyPoints.  Image
     positions are those of `tracks.kp_ptr`.  Validates on the host first (ValueError); raises SfmError when no initial pair
     has `min_initial_points` good points; a data set that falls apart returns the part that registered and lists the
@@ -409,7 +504,8 @@ def reconstruct_tracks(tracks, keypoints, K, initial_pair=None, device=0, **opti
     rec.poses = {i0: (np.eye(3), np.zeros(3)), j0: (R, t)}
     rec.order = [i0, j0]
     node_track = tracks.node_track if tracks.node_track is not None else node_track_of(tracks)
-    sc = _Scene(tracks.kp_ptr, kp_xy, node_track, tracks.track_ptr, tracks.image, tracks.keypoint, device)
+    robust = bool(o["robust_tracks"])
+    sc = _Scene(tracks.kp_ptr, kp_xy, node_track, tracks.track_ptr, tracks.image, tracks.keypoint, device, robust=robust)
     tri_gates = dict(min_views=o["min_views"], refine_iters=o["refine_iters"], max_error=o["max_error"],
                      min_angle_deg=o["min_angle_deg"])
     eval_gates = dict(min_views=o["min_views"], max_error=o["max_error"], min_angle_deg=o["min_angle_deg"])
@@ -464,7 +560,12 @@ def reconstruct_tracks(tracks, keypoints, K, initial_pair=None, device=0, **opti
         """The BA result for the log.  On success the cameras and points are adopted, failing points dropped and
         triangulated again; otherwise the state stays as it was."""
         rec.X, rec.has_point = sc.X.cpu().numpy(), sc.has_point.cpu().numpy() != 0
+        if robust:
+            rec.obs_inlier = sc.obs_inlier[:sc.n_obs].cpu().numpy() != 0
         out, cams, pts = run_ba(o["cam_dim"])
+        if robust:
+            # what the adjustment saw of the camera registered last: its inliers on old points and on the ones just adopted
+            out["observations_newest_camera"] = int((tracks.image[rec._observations()[0]] == rec.order[-1]).sum())
         if not out["success"]:
             return out
         if o["cam_dim"] == 10:
@@ -478,6 +579,14 @@ def reconstruct_tracks(tracks, keypoints, K, initial_pair=None, device=0, **opti
         out["points_added"] = sc.adopt_new_points(**tri_gates)
         return out
 
+    def refresh_flags(entry):
+        """Robust mode, after a registration and before anything uses the flags: the new camera's observations are
+        classified at the current points (until then they are 0, as those of every unregistered image; nothing is dropped
+        here); the entry gets the number of rejected observations."""
+        if robust:
+            sc.classify(**eval_gates)
+            entry["observations_rejected"] = sc.observations_rejected()
+
     cameras_up()
     refined = refine_pair() if o["refine_initial_pair"] else None
     if refined is not None and refined["success"]:
@@ -485,6 +594,7 @@ def reconstruct_tracks(tracks, keypoints, K, initial_pair=None, device=0, **opti
     added = sc.adopt_new_points(**tri_gates)
     rec.log.append({"step": 0, "initial_pair": (i0, j0), "initial_model": o["initial_model"], "n_good": n_good, "candidates": rows, "pair_refinement": refined,
                     "points_added": added})
+    refresh_flags(rec.log[-1])
     since_ba = 0
     while unregistered:
         seg_ptr, _, _, corr_X, corr_uv = sc.resection()
@@ -493,6 +603,8 @@ def reconstruct_tracks(tracks, keypoints, K, initial_pair=None, device=0, **opti
         cands = cands[:o["candidates_per_step"]]
         entry = {"step": len(rec.log), "candidates": cands, "visible": [int(visible[i]) for i in cands], "inliers": [],
                  "chosen": None, "points_added": 0, "points_removed": 0, "ba": None}
+        if robust:
+            entry["observations_rejected"] = sc.observations_rejected()       # also for an entry that ends the loop below
         rec.log.append(entry)
         if not cands:
             break
@@ -512,11 +624,14 @@ def reconstruct_tracks(tracks, keypoints, K, initial_pair=None, device=0, **opti
         unregistered.remove(i)
         cameras_up()
         entry["points_added"] = sc.adopt_new_points(**tri_gates)
+        refresh_flags(entry)                                 # before the adjustment, which sees the inliers only
         since_ba += 1
         if since_ba >= o["ba_every"] and len(rec.order) > 2:
             entry["ba"] = bundle_adjust()
             entry["points_removed"] = entry["ba"].get("points_removed", 0)
             since_ba = 0
+            if robust:                                       # the adjustment's own classify and adoption left the flags current
+                entry["observations_rejected"] = sc.observations_rejected()
     # the end: a bundle adjustment when cameras were registered since the last one; then the gates once more, so that
     # every point that is returned passes them under the cameras that are returned
     final = {"step": len(rec.log), "final": True, "ba": None, "points_removed": 0, "points_added": 0}
@@ -525,7 +640,12 @@ def reconstruct_tracks(tracks, keypoints, K, initial_pair=None, device=0, **opti
     final["points_removed"] = sc.drop_failing_points(**eval_gates)
     if final["points_removed"]:
         final["points_added"] = sc.adopt_new_points(**tri_gates)
-    sc.evaluate(**eval_gates)
+    if robust:
+        sc.classify(**eval_gates)
+        final["observations_rejected"] = sc.observations_rejected()
+        rec.obs_inlier = sc.obs_inlier[:sc.n_obs].cpu().numpy() != 0
+    else:
+        sc.evaluate(**eval_gates)
     rec.log.append(final)
     rec.has_point = sc.has_point.cpu().numpy() != 0
     rec.X = np.where(rec.has_point[:, None], sc.X.cpu().numpy(), np.nan)

@@ -26,11 +26,13 @@ def _check_options(min_views, refine_iters, max_error, min_angle_deg):
 
 
 def triangulate_tracks_raw(proj, cam_of_image, kp_ptr, kp_xy, track_ptr, obs_image, obs_kp, min_views=2, refine_iters=5,
-                           max_error=TRIANGULATION_MAX_ERROR, min_angle_deg=0.0, device=0):
+                           max_error=TRIANGULATION_MAX_ERROR, min_angle_deg=0.0, device=0, robust=False):
     """sfm_triangulate_tracks on flat host arrays, nothing validated but the options (the device treats an image or camera
     index out of range as not registered and a keypoint outside its image as a NaN pixel).  proj [n_cams,12] or [n_cams,3,4]
     K[R|t]; cam_of_image [n_img] (-1: not registered); kp_ptr [n_img+1]; kp_xy [n_nodes,2] pixels by node id; track_ptr,
-    obs_image, obs_kp: the CSR arrays of the tracks.  Returns {X [n,3], status int32, n_views int32, max_err, counts [6]}."""
+    obs_image, obs_kp: the CSR arrays of the tracks.  Returns {X [n,3], status int32, n_views int32, max_err, counts [6]}.
+    robust=True: sfm_triangulate_tracks_robust (an outlier observation is dropped, not the point); the result gains
+    n_inliers [n] int32 and obs_inlier [n_obs] uint8."""
     import torch
     from .driver import _p
     _check_options(min_views, refine_iters, max_error, min_angle_deg)
@@ -45,13 +47,27 @@ def triangulate_tracks_raw(proj, cam_of_image, kp_ptr, kp_xy, track_ptr, obs_ima
     d_kp, d_xy = _dev(kp_ptr, np.int64), _dev(kp_xy, np.float64)
     d_tp, d_img, d_okp = _dev(track_ptr, np.int64), _dev(obs_image, np.int32), _dev(obs_kp, np.int32)
     need = C.c_int64()
-    h.check(h.lib.sfm_triangulate_tracks_workspace_bytes(n_cams, C.byref(need)), "sfm_triangulate_tracks_workspace_bytes")
+    if robust:
+        h.check(h.lib.sfm_triangulate_tracks_robust_workspace_bytes(n_cams, n_tracks, C.byref(need)),
+                "sfm_triangulate_tracks_robust_workspace_bytes")
+    else:
+        h.check(h.lib.sfm_triangulate_tracks_workspace_bytes(n_cams, C.byref(need)), "sfm_triangulate_tracks_workspace_bytes")
     ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
     X = torch.empty((n_tracks, 3), dtype=torch.float64, device=dev)
     status = torch.empty(n_tracks, dtype=torch.int32, device=dev)
     n_views = torch.empty(n_tracks, dtype=torch.int32, device=dev)
     max_err = torch.empty(n_tracks, dtype=torch.float64, device=dev)
     counts = torch.empty(6, dtype=torch.int64, device=dev)
+    if robust:
+        n_inliers = torch.empty(n_tracks, dtype=torch.int32, device=dev)
+        obs_inlier = torch.zeros(max(n_obs, 1), dtype=torch.uint8, device=dev)
+        h.call("sfm_triangulate_tracks_robust", _p(d_proj), n_cams, _p(d_cam), n_img, _p(d_kp), _p(d_xy), n_nodes, _p(d_tp),
+               n_tracks, _p(d_img), _p(d_okp), n_obs, int(min_views), int(refine_iters), C.c_double(max_error),
+               C.c_double(min_angle_deg), _p(X), _p(status), _p(n_views), _p(n_inliers), _p(max_err), _p(obs_inlier), _p(counts),
+               _p(ws), need.value)
+        return {"X": X.cpu().numpy(), "status": status.cpu().numpy(), "n_views": n_views.cpu().numpy(),
+                "n_inliers": n_inliers.cpu().numpy(), "max_err": max_err.cpu().numpy(),
+                "obs_inlier": obs_inlier[:n_obs].cpu().numpy(), "counts": counts.cpu().numpy()}
     h.call("sfm_triangulate_tracks", _p(d_proj), n_cams, _p(d_cam), n_img, _p(d_kp), _p(d_xy), n_nodes, _p(d_tp), n_tracks,
            _p(d_img), _p(d_okp), n_obs, int(min_views), int(refine_iters), C.c_double(max_error), C.c_double(min_angle_deg),
            _p(X), _p(status), _p(n_views), _p(max_err), _p(counts), _p(ws), need.value)
@@ -62,13 +78,17 @@ def triangulate_tracks_raw(proj, cam_of_image, kp_ptr, kp_xy, track_ptr, obs_ima
 class Triangulation:
     """The points of a `Tracks` object.  X [n,3] (NaN where there is no point), status [n] (sfm_amd._lib.TRI_*), n_views [n]
     observations in registered images, max_err [n] the largest reprojection error in pixels, counts [6] tracks by status,
-    valid = status == 0."""
+    valid = status == 0.  From a robust call: obs_inlier [n_obs] bool, the observations the point was kept with, and
+    n_inliers [n] their number per track (max_err is then the largest error of an inlier); otherwise obs_inlier is None and
+    n_inliers equals n_views on the valid tracks and is 0 elsewhere."""
 
     def __init__(self, tracks, uv, cam_of_image, out):
         self.tracks = tracks
         self.cam_of_image = cam_of_image
         self.X, self.status, self.n_views = out["X"], out["status"], out["n_views"]
         self.max_err, self.counts = out["max_err"], out["counts"]
+        self.obs_inlier = out["obs_inlier"] != 0 if "obs_inlier" in out else None
+        self.n_inliers = out["n_inliers"] if "n_inliers" in out else np.where(self.status == _lib.TRI_OK, self.n_views, 0).astype(np.int32)
         self._uv = uv                                     # [n_obs,2] float64 pixels of the observations
 
     @property
@@ -76,16 +96,21 @@ class Triangulation:
         return self.status == _lib.TRI_OK
 
     def _valid_observations(self):
-        """(selected observation indices, point index of each) over the valid tracks and the registered images."""
+        """(selected observation indices, point index of each) over the valid tracks and the registered images; after a
+        robust call, over the inlier observations only."""
         tr = self.tracks
         new_id = np.cumsum(self.valid) - 1
         trk = np.repeat(np.arange(len(tr)), tr.lengths())
-        sel = np.flatnonzero(self.valid[trk] & (self.cam_of_image[tr.image] >= 0))
+        keep = self.valid[trk] & (self.cam_of_image[tr.image] >= 0)
+        if self.obs_inlier is not None:
+            keep &= self.obs_inlier
+        sel = np.flatnonzero(keep)
         return sel, new_id[trk[sel]]
 
     def ba_inputs(self):
-        """(pts [m,3], cam_idx int32, pt_idx int32, uv [k,2]) of the valid tracks, restricted to registered cameras and
-        point-major: what `GpuBA` and `reproj_errors` take beside the camera parameters."""
+        """(pts [m,3], cam_idx int32, pt_idx int32, uv [k,2]) of the valid tracks, restricted to registered cameras - and to
+        the inlier observations after a robust call - and point-major: what `GpuBA` and `reproj_errors` take beside the
+        camera parameters."""
         sel, pt = self._valid_observations()
         return (self.X[self.valid].copy(), self.cam_of_image[self.tracks.image[sel]].astype(np.int32), pt.astype(np.int32),
                 self._uv[sel].copy())
@@ -156,11 +181,13 @@ def keypoint_table(tracks, keypoints):
 
 
 def triangulate_tracks(tracks, keypoints, proj_or_poses, K=None, registered=None, min_views=2, refine_iters=5,
-                       max_error=TRIANGULATION_MAX_ERROR, min_angle_deg=0.0, device=0):
+                       max_error=TRIANGULATION_MAX_ERROR, min_angle_deg=0.0, device=0, robust=False):
     """Triangulate every track.  keypoints: per image position what `twoview.keypoints_xy` accepts ([n,2] array or
     cv2.KeyPoints); cameras: [n,3,4] projections K[R|t] with `registered` (the image position of each; default: one per
     image, in order) or a {image_id: (R, t)} dict with K, mapped to positions through `tracks.image_ids`.  An observation in
-    an image without a camera is ignored.  Everything is validated on the host first (ValueError); returns a Triangulation."""
+    an image without a camera is ignored.  robust=True drops outlier observations instead of points (a track that fails is
+    searched for a consensus of at least 3 views, see sfm_triangulate_tracks_robust in include/sfm_amd.h) and the
+    Triangulation carries obs_inlier.  Everything is validated on the host first (ValueError); returns a Triangulation."""
     _check_options(min_views, refine_iters, max_error, min_angle_deg)
     n_img = len(tracks.kp_ptr) - 1
     if len(keypoints) != n_img:
@@ -170,6 +197,6 @@ def triangulate_tracks(tracks, keypoints, proj_or_poses, K=None, registered=None
     proj, cam_of_image = _cameras(tracks, proj_or_poses, K, registered)
     kp_xy = keypoint_table(tracks, keypoints)
     out = triangulate_tracks_raw(proj, cam_of_image, tracks.kp_ptr, kp_xy, tracks.track_ptr, tracks.image, tracks.keypoint,
-                                 min_views, refine_iters, max_error, min_angle_deg, device)
+                                 min_views, refine_iters, max_error, min_angle_deg, device, robust=bool(robust))
     uv = kp_xy[tracks.kp_ptr[tracks.image] + tracks.keypoint] if tracks.n_obs else np.zeros((0, 2))
     return Triangulation(tracks, uv, cam_of_image, out)

@@ -617,7 +617,9 @@ def measure_triangulate(reps=20, emit=None):
     images, 1,641 tracks of 2 to 12 views, 4 on average: launch-bound) and (b) 200 cameras / 100,000 points / 10 views
     each from sfm_amd.synth with both visibility patterns of bench.py, for refine_iters 0 and 5.  Per row: ms,
     observations per second and the share of the HBM stream floor (every input array read once and every output written
-    once, over HBM_STREAM_BPS); beside it the time of sfm_triangulate2 on as many two-view tracks as an anchor."""
+    once, over HBM_STREAM_BPS); beside it the time of sfm_triangulate2 on as many two-view tracks as an anchor.  Then, per
+    case, rows for sfm_triangulate_tracks_robust beside sfm_triangulate_tracks on the same inputs (refine_iters 5), with
+    the observations as they are and with 5 % of them moved by 30 to 100 px, and the share of tracks in the second pass."""
     import torch
     from sfm_amd import _lib
     from sfm_amd.driver import _dev, _p
@@ -670,6 +672,49 @@ def measure_triangulate(reps=20, emit=None):
         results.append(row)
         if emit:
             emit(row)
+        # the robust call beside the plain one on the same inputs in the same run (refine_iters 5), once with the
+        # observations as they are and once with 5 % of them moved by 30 to 100 px
+        need_r = C.c_int64(); h.lib.sfm_triangulate_tracks_robust_workspace_bytes(n_cams, n_tracks, C.byref(need_r))
+        ws_r = torch.empty(need_r.value, dtype=torch.uint8, device=dev)
+        ni = torch.empty(n_tracks, dtype=torch.int32, device=dev)
+        flags = torch.empty(max(n_obs, 1), dtype=torch.uint8, device=dev)              # the call zeroes it
+        rng = np.random.default_rng(7)
+        moved = rng.random(n_obs) < 0.05
+        ang, rad = rng.uniform(0, 2 * np.pi, int(moved.sum())), rng.uniform(30, 100, int(moved.sum()))
+        xy_moved = c["kp_xy"].copy()
+        xy_moved[node[moved]] += np.stack([rad * np.cos(ang), rad * np.sin(ang)], axis=1)
+        for what, xy in (("as they are", d["kp_xy"]), ("5 % moved by 30 to 100 px", _dev(xy_moved, np.float64, dev))):
+            def run_plain():
+                h.call("sfm_triangulate_tracks", _p(d["proj"]), n_cams, _p(d["cam_of_image"]), n_cams, _p(d["kp_ptr"]),
+                       _p(xy), n_obs, _p(d["track_ptr"]), n_tracks, _p(d["obs_image"]), _p(d["obs_kp"]), n_obs, 2, 5,
+                       C.c_double(4.0), C.c_double(1.0), _p(X), _p(st), _p(nv), _p(me), _p(counts), _p(ws), need.value)
+
+            def run_robust():
+                h.call("sfm_triangulate_tracks_robust", _p(d["proj"]), n_cams, _p(d["cam_of_image"]), n_cams, _p(d["kp_ptr"]),
+                       _p(xy), n_obs, _p(d["track_ptr"]), n_tracks, _p(d["obs_image"]), _p(d["obs_kp"]), n_obs, 2, 5,
+                       C.c_double(4.0), C.c_double(1.0), _p(X), _p(st), _p(nv), _p(ni), _p(me), _p(flags), _p(counts), _p(ws_r),
+                       need_r.value)
+            for _ in range(3):
+                run_plain()
+            sec_plain = timed(run_plain, reps)
+            ok_plain = int(counts.cpu().numpy()[0])
+            for _ in range(3):
+                run_robust()
+            sec_robust = timed(run_robust, reps)
+            # the length of the device work list, which the header documents as the last of the workspace's three arrays
+            up256 = lambda v: (v + 255) // 256 * 256
+            at = up256(24 * n_cams) + up256(4 * n_tracks)
+            second_pass = int(ws_r[at:at + 4].view(torch.int32).item())
+            rrow = {"kernel": "triangulate_tracks_robust", "case": c["name"], "observations_are": what, "cameras": n_cams,
+                    "tracks": n_tracks, "observations": n_obs, "ms_triangulate_tracks_refine5": sec_plain * 1e3,
+                    "ms_robust_refine5": sec_robust * 1e3, "robust_over_plain": sec_robust / sec_plain,
+                    "ok_tracks_plain": ok_plain, "ok_tracks_robust": int(counts.cpu().numpy()[0]),
+                    "tracks_in_second_pass": second_pass, "share_of_tracks_in_second_pass": second_pass / max(n_tracks, 1),
+                    "observations_rejected": int(((flags[:n_obs] == 0) & (st == 0)[torch.repeat_interleave(
+                        torch.arange(n_tracks, device=dev), d["track_ptr"][1:] - d["track_ptr"][:-1])]).sum().item())}
+            results.append(rrow)
+            if emit:
+                emit(rrow)
     return results
 
 

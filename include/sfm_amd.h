@@ -824,6 +824,66 @@ int sfm_features_describe(sfm_handle h, const uint8_t* images, const int64_t* im
                           uint8_t* desc /* uint8 [n_kp][32] */, uint8_t* blurred_out /* may be NULL */, void* workspace,
                           int64_t workspace_bytes);
 
+/* ---- dense depth maps by plane-sweep stereo (sfm_amd/csrc/depth.hip, depth_rule.h, depth_plan.h) ----
+ * From n_img gray uint8 images in the layout of sfm_features_detect (one device buffer, img_off [n_img+1] int64, heights /
+ * widths [n_img] int32 as HOST arrays), registered cameras and a list of plane depths per reference view: per reference
+ * pixel the plane with the lowest aggregated census cost, that cost, a depth refined between planes, and after a
+ * cross-view check a keep flag and the 3-D point.  Fronto-parallel planes of the reference camera only.  All floating
+ * point is float64 without FMA contraction; everything else is integer: the output bytes are a function of the inputs
+ * alone, the same from run to run, and independent of the launch geometry and of the other views of the batch.
+ *
+ * Views: n_ref reference views, ref_image [n_ref] (each image at most once); view r has the sources
+ *   src_image[src_ptr[r] .. src_ptr[r+1]) (at most 8, none equal to ref_image[r]; ref_image, src_ptr, src_image are HOST
+ *   arrays) and the plane depths plane_depth[plane_ptr[r] .. plane_ptr[r+1]) (plane_ptr a HOST array, plane_depth float64 on
+ *   the device; 1 .. 1024 planes, every depth finite and > 0).  Entry e of src_image has the warp warps[e] = [A | b], 12
+ *   float64 row-major 3 x 4 on the device; the caller forms A = K_s R_s R_r^T K_r^-1, b = K_s (t_s - R_s R_r^T t_r), so
+ *   that with the last row of K_s = (0, 0, 1) q2 below is the depth along the source's optical axis.  The maps of view r
+ *   are the elements out_off[r] .. out_off[r] + h w (row-major) of every output, out_off[r] = sum over r' < r of h w.
+ * Census: cen(p) is 48 bits in a uint64; for the offsets (dy, dx), dy, dx in -3 .. 3 in row-major order with the centre
+ *   skipped, bit k = I(clamp(p + o_k)) < I(p), coordinates clamped to the image.  census has img_off[n_img] elements, the
+ *   word of pixel (x, y) of image i at img_off[i] + y w + x; elements of a slot behind h w are not written.
+ * Sample: for the reference pixel (x, y), a depth d and a source of w_s x h_s pixels with warp [A | b]:
+ *   a_i = (A_i0 * x + A_i1 * y) + A_i2,  q_i = d * a_i + b_i,  u = q0 / q2,  v = q1 / q2;  valid iff q2 > 0 and
+ *   u >= -0.5 and u < w_s - 0.5 and v >= -0.5 and v < h_s - 0.5, each comparison false on NaN;  xi = (int)floor(u + 0.5),
+ *   yi likewise (never above w_s - 1, h_s - 1: the rounded sum can reach the size only for a size of 1, and is then cut).
+ *   c = popcount(cen_r(p) ^ cen_s(yi, xi)); an invalid sample costs 24, what two unrelated census words are expected to give.
+ * Aggregate: c_k(p) = sum of c over the sources at plane k;  S_k(p) = sum of c_k(clamp(p + o)) over the (2 radius + 1)^2
+ *   window, 0 <= radius <= 4, coordinates clamped to the reference image.  S <= 48 * 8 * 81 = 31,104.
+ * Winner: best = the lowest k that minimises S_k.  plane (int32) = best, cost (uint16) = S_best, depth (float32): with D
+ *   planes, if 0 < best < D - 1 and den = S_{best-1} - 2 S_best + S_{best+1} > 0 (integers), off = (double)(S_{best-1} -
+ *   S_{best+1}) / (double)(2 * den), j = best + 1 if off >= 0 else best - 1, f = fabs(off),
+ *   w = 1 / d_best + f * (1 / d_j - 1 / d_best), depth = (float)(1 / w); otherwise depth = (float)d_best.  A view without a
+ *   source still gets its maps: S_k = 0, best = 0.
+ * Filter: for a reference pixel whose depth is finite, d = that float32 widened to double goes through the sample rule
+ *   against every source that has a depth map of its own (it is itself a reference view of the call); the pixel agrees
+ *   with the source iff the sample is valid, ds = depth_s(yi, xi) is finite and fabs(ds - q2) <= rel_tol * q2.
+ *   n_consistent (uint8) counts the agreeing sources; keep (uint8) = 1 iff cost <= max_cost[r] (a HOST int32 [n_ref], NULL:
+ *   no limit) and n_consistent >= min_consistent.  xyz (float64 x 3) for every pixel: with backproj[r] = [M | c], 12 float64
+ *   row-major 3 x 4 on the device, M = R_r^T K_r^-1, c = -R_r^T t_r: xyz_i = d * ((M_i0 * x + M_i1 * y) + M_i2) + c_i.
+ *   A pixel whose depth is not finite has n_consistent = 0, keep = 0 and xyz = NaN.
+ * The workspace (sfm_depth_workspace_bytes; n_entries = src_ptr[n_ref]) holds the tables of a call only; one workspace
+ * sized for the sweep serves the census and the filter of the same images too.  SFM_ERR_ARG before any device work for a
+ * null handle, an img_off that does not ascend, an image larger than its slot, a reference or source index out of range, a
+ * reference listed twice, a source equal to its reference, more than 8 sources, a radius above 4, fewer than 1 or more than
+ * 1024 planes, or a workspace that is missing or too small.  No kernel reads outside an image. */
+int sfm_depth_workspace_bytes(int32_t n_img, int32_t n_ref, int64_t n_entries, int64_t* bytes_host);
+int sfm_depth_census(sfm_handle h, const uint8_t* images, const int64_t* img_off /* host */, const int32_t* heights /* host */,
+                     const int32_t* widths /* host */, int32_t n_img, uint64_t* census /* device [img_off[n_img]] */,
+                     void* workspace, int64_t workspace_bytes);
+int sfm_depth_sweep(sfm_handle h, const uint64_t* census, const int64_t* img_off /* host */, const int32_t* heights /* host */,
+                    const int32_t* widths /* host */, int32_t n_img, int32_t n_ref, const int32_t* ref_image /* host */,
+                    const int64_t* src_ptr /* host [n_ref+1] */, const int32_t* src_image /* host */,
+                    const double* warps /* device [n_entries][12] */, const int64_t* plane_ptr /* host [n_ref+1] */,
+                    const double* plane_depth /* device */, int32_t radius, int32_t* plane, uint16_t* cost, float* depth,
+                    void* workspace, int64_t workspace_bytes);
+int sfm_depth_filter(sfm_handle h, const int64_t* img_off /* host */, const int32_t* heights /* host */,
+                     const int32_t* widths /* host */, int32_t n_img, int32_t n_ref, const int32_t* ref_image /* host */,
+                     const int64_t* src_ptr /* host [n_ref+1] */, const int32_t* src_image /* host */,
+                     const double* warps /* device [n_entries][12] */, const double* backproj /* device [n_ref][12] */,
+                     const float* depth, const uint16_t* cost, const int32_t* max_cost /* host [n_ref] or NULL */,
+                     double rel_tol, int32_t min_consistent, uint8_t* n_consistent, uint8_t* keep,
+                     double* xyz /* device [n_out][3] */, void* workspace, int64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,29 @@ def save_ply(points3D, filepath):
         f.writelines(f"{p[0]} {p[1]} {p[2]}\n" for p in pts)
 
 
+def save_ply_points(points, colors, path):
+    """A dense cloud as binary little-endian PLY: points [n,3] as float32 x, y, z; colors None, [n] gray or [n,3] uint8 in
+    cv2's channel order (BGR), written as red, green, blue."""
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(pts)}",
+            "property float x", "property float y", "property float z"]
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if colors is not None:
+        col = np.asarray(colors)
+        if col.dtype != np.uint8 or col.shape not in ((len(pts),), (len(pts), 3)):
+            raise ValueError("colors must be uint8 [n] or [n,3], one per point")
+        col = np.repeat(col[:, None], 3, axis=1) if col.ndim == 1 else col[:, ::-1]
+        head += ["property uchar red", "property uchar green", "property uchar blue"]
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    body = np.zeros(len(pts), dtype=np.dtype(fields))
+    body["x"], body["y"], body["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
+    if colors is not None:
+        body["red"], body["green"], body["blue"] = col[:, 0], col[:, 1], col[:, 2]
+    with open(path, "wb") as f:
+        f.write(("\n".join(head + ["end_header"]) + "\n").encode("ascii"))
+        f.write(body.tobytes())
+
+
 def save_reconstruction(poses, points3D, point_tracks, output_dir):
     """poses.json, points3D.json (points + tracks, image ids as strings) and reconstruction.ply."""
     output_dir = Path(output_dir)

@@ -4,11 +4,11 @@ association (pair tests/s), two-view triangulation (tracks/s), epipolar verifica
 fundamental-matrix RANSAC beside the batched matcher it follows in the pair loop, the batched essential-matrix RANSAC
 beside it on the same pairs, the batched homography RANSAC beside it as well, the batched PnP RANSAC of the
 camera registration, the batched relative-pose recovery of the initial-pair scan, the track building, the N-view
-triangulation of the tracks, the resection lists, the gate evaluation and the incremental loop on top of them, and the
-feature detection / description stage in front of them all.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
+triangulation of the tracks, the resection lists, the gate evaluation and the incremental loop on top of them, the
+feature detection / description stage in front of them all, and the dense-depth stage behind them.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
 functions to time on a bounded sample of the same inputs (this tool itself never imports oracle/).
 usage: python tools/bench_driver.py [--reps 20] [--fundamental-only | --essential-only | --homography-only | --pnp-only | --pose-only | --tracks-only | --triangulate-only |
-       --incremental-only | --features-only | --guided-only]"""
+       --incremental-only | --features-only | --guided-only | --depth-only]"""
 import argparse
 import ctypes as C
 import json
@@ -980,6 +980,93 @@ def measure_guided(reps=20, emit=None):
     return [r]
 
 
+def measure_depth(reps=20, emit=None):
+    """sfm_depth_census, sfm_depth_sweep and sfm_depth_filter on 36 synthetic 1024 x 768 views (the scene generator of
+    tests/depth_reference.py: cameras on a line, baseline 0.1, f = 1228), every view a reference with its 4 nearest cameras
+    as sources, planes from sfm_amd.depth.plane_depths over 2.5 .. 5, radius 2, inputs resident in HBM: device time of each
+    call by HIP events around `reps` calls, per reference view, and the samples (pixels x planes x sources) per second of
+    the sweep.  In the same run sfm_features_detect + sfm_features_describe on the same images, as a known quantity."""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from depth_reference import make_scene
+    from sfm_amd import _lib, depth as dm, features
+    from sfm_amd.driver import _p
+    h = _lib.get_handle(0)
+    dev = torch.device("cuda", 0)
+    n_img, W, H, radius, n_src = 36, 1024, 768, 2, 4
+    sc = make_scene(n_cams=n_img, width=W, height=H, f=1228.0, baseline=0.1)
+    refs = list(range(n_img))
+    sources = {r: sorted(sorted((s for s in refs if s != r), key=lambda s: (abs(s - r), s))[:n_src]) for r in refs}
+    planes = {r: dm.plane_depths(sc.d_min, sc.d_max, dm.view_warps(sc.K, sc.poses, r, sources[r]), sc.size) for r in refs}
+    imgs, refs, src_ptr, src_image, warps, backproj, plane_ptr, depths = dm.check_arguments(sc.images, sc.K, sc.poses, sources, planes, radius)
+    off = np.arange(n_img + 1, dtype=np.int64) * (H * W)
+    heights, widths = np.full(n_img, H, np.int32), np.full(n_img, W, np.int32)
+    ref_image = np.array(refs, dtype=np.int32)
+    d_img = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).to(dev)
+    d_warps, d_back, d_planes = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (warps, backproj, depths))
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    need = C.c_int64()
+    h.check(h.lib.sfm_depth_workspace_bytes(n_img, n_img, len(src_image), C.byref(need)), "sfm_depth_workspace_bytes")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    n_out = n_img * H * W
+    census = torch.empty(n_out, dtype=torch.int64, device=dev)
+    plane = torch.empty(n_out, dtype=torch.int32, device=dev)
+    cost = torch.empty(n_out, dtype=torch.int16, device=dev)
+    depth = torch.empty(n_out, dtype=torch.float32, device=dev)
+    ncons = torch.empty(n_out, dtype=torch.uint8, device=dev)
+    keep = torch.empty(n_out, dtype=torch.uint8, device=dev)
+    xyz = torch.empty((n_out, 3), dtype=torch.float64, device=dev)
+    limit = np.array([12 * (src_ptr[v + 1] - src_ptr[v]) * (2 * radius + 1) ** 2 for v in range(n_img)], dtype=np.int32)
+
+    def run_census():
+        h.call("sfm_depth_census", _p(d_img), hp(off), hp(heights), hp(widths), n_img, _p(census), _p(ws), need.value)
+
+    def run_sweep():
+        h.call("sfm_depth_sweep", _p(census), hp(off), hp(heights), hp(widths), n_img, n_img, hp(ref_image), hp(src_ptr), hp(src_image),
+               _p(d_warps), hp(plane_ptr), _p(d_planes), radius, _p(plane), _p(cost), _p(depth), _p(ws), need.value)
+
+    def run_filter():
+        h.call("sfm_depth_filter", hp(off), hp(heights), hp(widths), n_img, n_img, hp(ref_image), hp(src_ptr), hp(src_image),
+               _p(d_warps), _p(d_back), _p(depth), _p(cost), hp(limit), C.c_double(0.02), 2, _p(ncons), _p(keep), _p(xyz), _p(ws), need.value)
+    run_census(); run_sweep(); run_filter()
+    samples = int(sum(H * W * (plane_ptr[v + 1] - plane_ptr[v]) * (src_ptr[v + 1] - src_ptr[v]) for v in range(n_img)))
+    truth = np.stack(sc.depth)
+    z = depth.cpu().numpy().reshape(n_img, H, W)
+    kept = keep.cpu().numpy().reshape(n_img, H, W).astype(bool)
+    row = {"kernel": "depth", "views": n_img, "height": H, "width": W, "radius": radius, "sources_per_view": n_src,
+           "planes_min": int(np.diff(plane_ptr).min()), "planes_max": int(np.diff(plane_ptr).max()), "samples": samples,
+           "share_kept": float(kept.mean()), "share_of_kept_within_2_percent_of_truth": float((np.abs(z - truth) <= 0.02 * truth)[kept].mean()),
+           "ms_census_per_view": timed(run_census, reps) * 1e3 / n_img, "ms_sweep_per_view": timed(run_sweep, reps) * 1e3 / n_img,
+           "ms_filter_per_view": timed(run_filter, reps) * 1e3 / n_img}
+    row["samples_per_s_sweep"] = samples / (row["ms_sweep_per_view"] * n_img * 1e-3)
+    # the known quantity beside it: the feature stage on the same images
+    threshold, edge, max_features = 20, 31, 10000
+    h.check(h.lib.sfm_features_workspace_bytes(n_img, hp(off), C.byref(need)), "sfm_features_workspace_bytes")
+    fws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    kp_ptr = torch.empty(n_img + 1, dtype=torch.int64, device=dev)
+    rot = features._rot_table(None, 0)
+
+    def detect():
+        h.call("sfm_features_detect", _p(d_img), None, hp(off), hp(heights), hp(widths), n_img, threshold, edge, max_features,
+               _p(kp_ptr), _p(fws), need.value)
+    detect()
+    n = int(kp_ptr.cpu().numpy()[-1])
+    xy = torch.empty((max(n, 1), 2), dtype=torch.int32, device=dev)
+    score = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    abin = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    desc = torch.empty((max(n, 1), 32), dtype=torch.uint8, device=dev)
+
+    def both():
+        detect()
+        h.call("sfm_features_describe", _p(d_img), hp(off), hp(heights), hp(widths), n_img, _p(kp_ptr), n, _p(rot), _p(xy),
+               _p(score), _p(abin), _p(desc), None, _p(fws), need.value)
+    row["keypoints"] = n
+    row["ms_features_detect_plus_describe_per_view"] = timed(both, reps) * 1e3 / n_img
+    if emit:
+        emit(row)
+    return [row]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -995,10 +1082,11 @@ def main():
     ap.add_argument("--incremental-only", action="store_true", help="only the resection / evaluation / incremental-loop rows")
     ap.add_argument("--features-only", action="store_true", help="only the feature detection / description row")
     ap.add_argument("--guided-only", action="store_true", help="only the guided-matching row (beside the blind matcher)")
+    ap.add_argument("--depth-only", action="store_true", help="only the dense-depth row (beside the feature stage on the same images)")
     a = ap.parse_args()
     emit = lambda d: print(json.dumps(d), flush=True)
     only = a.fundamental_only or a.essential_only or a.homography_only or a.pnp_only or a.pose_only or a.tracks_only or a.triangulate_only or a.incremental_only or \
-        a.features_only or a.guided_only
+        a.features_only or a.guided_only or a.depth_only
     if not only:
         measure(a.reps, a.tracks, a.corr, emit=emit)
     if a.fundamental_only or not only:
@@ -1021,6 +1109,8 @@ def main():
         measure_features(a.reps, emit=emit)
     if a.guided_only or not only:
         measure_guided(a.reps, emit=emit)
+    if a.depth_only or not only:
+        measure_depth(a.reps, emit=emit)
 
 
 if __name__ == "__main__":

@@ -68,6 +68,10 @@ class BALayout(C.Structure):
         "pc_off", "pp_off", "scalars_off", "G_off", "cg_Ap_off", "cg_M_off")]
 
 
+# the cameras and the tracks as the four track-judging entry points take them after the handle: proj, n_cams, cam_of_image,
+# n_img, kp_ptr, kp_xy, n_nodes, track_ptr, n_tracks, obs_image, obs_kp, n_obs
+TRACK_SOURCE = (vp, i32, vp, i32, vp, vp, i64, vp, i64, vp, vp, i64)
+
 # name -> (restype, argtypes); every symbol include/sfm_amd.h declares
 SIGNATURES = {
     "sfm_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
@@ -150,15 +154,11 @@ SIGNATURES = {
     "sfm_tracks_workspace_bytes": (C.c_int, [i64, i64, C.POINTER(i64)]),
     "sfm_tracks_build": (C.c_int, [vp, vp, i32, i64, vp, i32, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp, i64, i64, vp, i64]),
     "sfm_triangulate_tracks_workspace_bytes": (C.c_int, [i32, C.POINTER(i64)]),
-    "sfm_triangulate_tracks": (C.c_int, [vp, vp, i32, vp, i32, vp, vp, i64, vp, i64, vp, vp, i64, i32, i32, f64, f64,
-                                         vp, vp, vp, vp, vp, vp, i64]),
-    "sfm_tracks_evaluate": (C.c_int, [vp, vp, i32, vp, i32, vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, i32, f64, f64,
-                                      vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_triangulate_tracks": (C.c_int, [vp, *TRACK_SOURCE, i32, i32, f64, f64, vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_tracks_evaluate": (C.c_int, [vp, *TRACK_SOURCE, vp, vp, i32, f64, f64, vp, vp, vp, vp, vp, vp, i64]),
     "sfm_triangulate_tracks_robust_workspace_bytes": (C.c_int, [i32, i64, C.POINTER(i64)]),
-    "sfm_triangulate_tracks_robust": (C.c_int, [vp, vp, i32, vp, i32, vp, vp, i64, vp, i64, vp, vp, i64, i32, i32, f64, f64,
-                                                vp, vp, vp, vp, vp, vp, vp, vp, i64]),
-    "sfm_tracks_classify": (C.c_int, [vp, vp, i32, vp, i32, vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, i32, f64, f64,
-                                      vp, vp, vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_triangulate_tracks_robust": (C.c_int, [vp, *TRACK_SOURCE, i32, i32, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_tracks_classify": (C.c_int, [vp, *TRACK_SOURCE, vp, vp, i32, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp, i64]),
     "sfm_resection_workspace_bytes": (C.c_int, [i64, C.POINTER(i64)]),
     "sfm_tracks_resection": (C.c_int, [vp, vp, i32, i64, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, vp, i64]),
     "sfm_orb_default_pattern": (C.c_int, [vp]),

@@ -1,5 +1,5 @@
 // Robust N-view triangulation of one track: an outlier observation is dropped, not the point.  For the device
-// (triangulate_robust.hip) and - SFM_HD - for the host, so that the CPU tests can set it against the NumPy restatement
+// (triangulate.hip) and - SFM_HD - for the host, so that the CPU tests can set it against the NumPy restatement
 // (tests/triangulate_robust_reference.py, tests/native/triangulate_robust_check.cpp).  tri::solve of triangulate_solve.h
 // is used as it is.  For one track, with u_0..u_{m-1} its used observations in track order:
 //   sound        the pixel, P and C of the observation are finite

@@ -5,7 +5,7 @@
                       image, taken from the tracks by index - what PnP consumes, and their counts rank the next view
   `evaluate_tracks`   sfm_tracks_evaluate (sfm_amd/csrc/triangulate.hip): the triangulation gates at points that are
                       given - what a bundle adjustment leaves behind
-  `classify_tracks`   sfm_tracks_classify (sfm_amd/csrc/triangulate_robust.hip): the same gates over the observations
+  `classify_tracks`   sfm_tracks_classify (sfm_amd/csrc/triangulate.hip): the same gates over the observations
                       that agree with the point, and a flag per observation - the loop's `robust_tracks` mode
 
 For the life of a `reconstruct_tracks` call the CSR arrays, kp_ptr, kp_xy, node_track, X and has_point live in device
@@ -15,13 +15,12 @@ points.  No CPU fallback: without the library or a GPU these raise.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
+from ._track_scene import _Scene
 from .driver import TRIANGULATION_MAX_ERROR, projection_matrix
-from .triangulate import _cameras, _check_options, keypoint_table
+from .triangulate import _cameras, _check_options, _check_tracks, keypoint_table
 
 
 def node_track_of(tracks):
@@ -32,178 +31,6 @@ def node_track_of(tracks):
         node = tracks.kp_ptr[tracks.image] + tracks.keypoint
         node_track[node] = np.repeat(np.arange(len(tracks), dtype=np.int32), tracks.lengths())
     return node_track
-
-
-class _Scene:
-    """The device-resident arrays of one data set and the three device calls on them.  Everything stays on the device
-    between calls; the methods return only what the host loop decides on."""
-
-    def __init__(self, kp_ptr, kp_xy, node_track, track_ptr, obs_image, obs_kp, device, robust=False):
-        import torch
-        self.torch = torch
-        self.h = _lib.get_handle(device)
-        self.dev = dev = torch.device("cuda", device)
-        up = lambda a, dtype: torch.from_numpy(np.array(a, dtype=dtype, order="C")).to(dev)      # a copy: inputs may be read-only
-        self.n_img, self.n_nodes = len(kp_ptr) - 1, int(np.asarray(kp_xy).reshape(-1, 2).shape[0])
-        self.n_tracks, self.n_obs = len(track_ptr) - 1, len(obs_image)
-        self.kp_ptr, self.kp_xy = up(kp_ptr, np.int64), up(np.asarray(kp_xy).reshape(-1, 2), np.float64)
-        self.node_track = up(node_track, np.int32)
-        self.track_ptr, self.obs_image, self.obs_kp = up(track_ptr, np.int64), up(obs_image, np.int32), up(obs_kp, np.int32)
-        T = self.n_tracks
-        self.X = torch.full((T, 3), float("nan"), dtype=torch.float64, device=dev)
-        self.has_point = torch.zeros(T, dtype=torch.uint8, device=dev)
-        self.X_tri = torch.empty((T, 3), dtype=torch.float64, device=dev)
-        self.status = torch.empty(T, dtype=torch.int32, device=dev)
-        self.n_views = torch.empty(T, dtype=torch.int32, device=dev)
-        self.max_err = torch.empty(T, dtype=torch.float64, device=dev)
-        self.counts = torch.empty(6, dtype=torch.int64, device=dev)
-        self.proj = self.cam_of_image = self.ws_tri = None
-        self.n_cams = 0
-        self.robust = bool(robust)
-        if self.robust:
-            # per observation: the flag of the loop's state, the flags of the last robust triangulation, its track
-            self.obs_inlier = torch.zeros(max(self.n_obs, 1), dtype=torch.uint8, device=dev)
-            self.obs_inlier_tri = torch.zeros(max(self.n_obs, 1), dtype=torch.uint8, device=dev)
-            self.n_inliers = torch.empty(T, dtype=torch.int32, device=dev)
-            self.obs_track = torch.zeros(max(self.n_obs, 1), dtype=torch.int64, device=dev)
-            self.obs_track[:self.n_obs] = torch.repeat_interleave(torch.arange(T, device=dev), self.track_ptr[1:] - self.track_ptr[:-1])
-        need = C.c_int64()
-        self.h.check(self.h.lib.sfm_resection_workspace_bytes(self.n_nodes, C.byref(need)), "sfm_resection_workspace_bytes")
-        self.ws_res, self.ws_res_bytes = torch.empty(need.value, dtype=torch.uint8, device=dev), need.value
-        self.seg_ptr = torch.empty(self.n_img + 1, dtype=torch.int64, device=dev)
-        self.total = torch.empty(1, dtype=torch.int64, device=dev)
-        self.cap = 0
-        self._corr(int((np.asarray(node_track) >= 0).sum()))
-
-    def _corr(self, cap):
-        torch, dev = self.torch, self.dev
-        self.cap = cap
-        self.corr_node = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-        self.corr_track = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-        self.corr_X = torch.empty((max(cap, 1), 3), dtype=torch.float64, device=dev)
-        self.corr_uv = torch.empty((max(cap, 1), 2), dtype=torch.float32, device=dev)
-
-    def set_points(self, X, has_point):
-        torch = self.torch
-        self.X.copy_(torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 3)))
-        self.has_point.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(has_point) != 0, dtype=np.uint8)))
-
-    def set_cameras(self, proj, cam_of_image):
-        """Per step the only upload: proj [n_cams,12] and cam_of_image [n_img]."""
-        torch = self.torch
-        proj = np.ascontiguousarray(proj, dtype=np.float64).reshape(-1, 12)
-        self.n_cams = proj.shape[0]
-        self.proj = torch.from_numpy(proj.copy()).to(self.dev)
-        self.cam_of_image = torch.from_numpy(np.array(cam_of_image, dtype=np.int32, order="C")).to(self.dev)
-        need = C.c_int64()
-        self.h.check(self.h.lib.sfm_triangulate_tracks_workspace_bytes(self.n_cams, C.byref(need)),
-                     "sfm_triangulate_tracks_workspace_bytes")
-        self.ws_tri, self.ws_tri_bytes = torch.empty(need.value, dtype=torch.uint8, device=self.dev), need.value
-        if self.robust:
-            self.h.check(self.h.lib.sfm_triangulate_tracks_robust_workspace_bytes(self.n_cams, self.n_tracks, C.byref(need)),
-                         "sfm_triangulate_tracks_robust_workspace_bytes")
-            self.ws_rob, self.ws_rob_bytes = torch.empty(need.value, dtype=torch.uint8, device=self.dev), need.value
-
-    def resection(self):
-        """(seg_ptr [n_img+1] int64, corr_node, corr_track int32, corr_X [n,3] float64, corr_uv [n,2] float32) on the host."""
-        from .driver import _p
-        while True:
-            self.h.call("sfm_tracks_resection", _p(self.kp_ptr), self.n_img, self.n_nodes, _p(self.kp_xy), _p(self.node_track),
-                        _p(self.cam_of_image), _p(self.X), _p(self.has_point), self.n_tracks, _p(self.seg_ptr),
-                        _p(self.corr_node), _p(self.corr_track), _p(self.corr_X), _p(self.corr_uv), self.cap, _p(self.total),
-                        _p(self.ws_res), self.ws_res_bytes)
-            n = int(self.total.item())
-            if n <= self.cap:
-                break
-            self._corr(n)                                   # cannot happen with cap = every node of a track; kept as a guard
-        return (self.seg_ptr.cpu().numpy(), self.corr_node[:n].cpu().numpy(), self.corr_track[:n].cpu().numpy(),
-                self.corr_X[:n].cpu().numpy(), self.corr_uv[:n].cpu().numpy())
-
-    def triangulate(self, min_views, refine_iters, max_error, min_angle_deg):
-        """sfm_triangulate_tracks over all tracks into X_tri / status / n_views / max_err / counts (device)."""
-        from .driver import _p
-        self.h.call("sfm_triangulate_tracks", _p(self.proj), self.n_cams, _p(self.cam_of_image), self.n_img, _p(self.kp_ptr),
-                    _p(self.kp_xy), self.n_nodes, _p(self.track_ptr), self.n_tracks, _p(self.obs_image), _p(self.obs_kp),
-                    self.n_obs, int(min_views), int(refine_iters), C.c_double(max_error), C.c_double(min_angle_deg),
-                    _p(self.X_tri), _p(self.status), _p(self.n_views), _p(self.max_err), _p(self.counts), _p(self.ws_tri),
-                    self.ws_tri_bytes)
-
-    def triangulate_robust(self, min_views, refine_iters, max_error, min_angle_deg):
-        """sfm_triangulate_tracks_robust over all tracks into X_tri / status / n_views / n_inliers / max_err / counts and
-        obs_inlier_tri (device)."""
-        from .driver import _p
-        self.h.call("sfm_triangulate_tracks_robust", _p(self.proj), self.n_cams, _p(self.cam_of_image), self.n_img,
-                    _p(self.kp_ptr), _p(self.kp_xy), self.n_nodes, _p(self.track_ptr), self.n_tracks, _p(self.obs_image),
-                    _p(self.obs_kp), self.n_obs, int(min_views), int(refine_iters), C.c_double(max_error),
-                    C.c_double(min_angle_deg), _p(self.X_tri), _p(self.status), _p(self.n_views), _p(self.n_inliers),
-                    _p(self.max_err), _p(self.obs_inlier_tri), _p(self.counts), _p(self.ws_rob), self.ws_rob_bytes)
-
-    def adopt_new_points(self, **gates):
-        """Triangulate, then adopt the points of status 0 for tracks without a point; existing points stay.  Returns the
-        number adopted (one integer comes down).  In the robust mode the adopted tracks take their flags with them."""
-        torch = self.torch
-        if self.robust:
-            self.triangulate_robust(**gates)
-        else:
-            self.triangulate(**gates)
-        new = (self.has_point == 0) & (self.status == _lib.TRI_OK)
-        if self.robust:
-            self.obs_inlier = torch.where(new[self.obs_track], self.obs_inlier_tri, self.obs_inlier)
-        self.X = torch.where(new[:, None], self.X_tri, self.X)
-        self.has_point |= new.to(torch.uint8)
-        return int(new.sum().item())
-
-    def evaluate(self, min_views, max_error, min_angle_deg, want_obs_err=False):
-        """sfm_tracks_evaluate at X / has_point into status / n_views / max_err / counts (device); obs_err or None."""
-        from .driver import _p
-        obs_err = self.torch.empty(max(self.n_obs, 1), dtype=self.torch.float64, device=self.dev) if want_obs_err else None
-        self.h.call("sfm_tracks_evaluate", _p(self.proj), self.n_cams, _p(self.cam_of_image), self.n_img, _p(self.kp_ptr),
-                    _p(self.kp_xy), self.n_nodes, _p(self.track_ptr), self.n_tracks, _p(self.obs_image), _p(self.obs_kp),
-                    self.n_obs, _p(self.X), _p(self.has_point), int(min_views), C.c_double(max_error),
-                    C.c_double(min_angle_deg), _p(self.status), _p(self.n_views), _p(self.max_err), _p(obs_err),
-                    _p(self.counts), _p(self.ws_tri), self.ws_tri_bytes)
-        return obs_err[:self.n_obs] if want_obs_err else None
-
-    def classify(self, min_views, max_error, min_angle_deg, want_obs_err=False):
-        """sfm_tracks_classify at X / has_point into status / n_views / n_inliers / max_err / counts and obs_inlier, the
-        flags of the loop's state: those of every track that has a point are refreshed, the others are 0."""
-        from .driver import _p
-        obs_err = self.torch.empty(max(self.n_obs, 1), dtype=self.torch.float64, device=self.dev) if want_obs_err else None
-        self.h.call("sfm_tracks_classify", _p(self.proj), self.n_cams, _p(self.cam_of_image), self.n_img, _p(self.kp_ptr),
-                    _p(self.kp_xy), self.n_nodes, _p(self.track_ptr), self.n_tracks, _p(self.obs_image), _p(self.obs_kp),
-                    self.n_obs, _p(self.X), _p(self.has_point), int(min_views), C.c_double(max_error),
-                    C.c_double(min_angle_deg), _p(self.status), _p(self.n_views), _p(self.n_inliers), _p(self.max_err),
-                    _p(self.obs_inlier), _p(obs_err), _p(self.counts), _p(self.ws_tri), self.ws_tri_bytes)
-        return obs_err[:self.n_obs] if want_obs_err else None
-
-    def observations_rejected(self):
-        """The observations in registered images, of tracks that have a point, whose flag is 0 (one integer comes down)."""
-        if self.n_obs == 0:
-            return 0
-        used = self.cam_of_image[self.obs_image.long()] >= 0
-        return int((used & (self.has_point[self.obs_track[:self.n_obs]] != 0) & (self.obs_inlier[:self.n_obs] == 0)).sum().item())
-
-    def drop_failing_points(self, **gates):
-        """Evaluate - in the robust mode: classify - then every point whose status is not 0 loses has_point (and its
-        flags).  Returns the number dropped."""
-        if self.robust:
-            self.classify(**gates)
-        else:
-            self.evaluate(**gates)
-        bad = (self.has_point != 0) & (self.status != _lib.TRI_OK)
-        self.has_point &= ~bad.to(self.torch.uint8) & 1
-        if self.robust:
-            self.obs_inlier &= ~bad[self.obs_track].to(self.torch.uint8) & 1
-        return int(bad.sum().item())
-
-
-def _check_tracks(tracks, keypoints):
-    n_img = len(tracks.kp_ptr) - 1
-    if len(keypoints) != n_img:
-        raise ValueError(f"{len(keypoints)} keypoint lists for {n_img} images")
-    if tracks.n_obs and (tracks.image.min() < 0 or tracks.image.max() >= n_img):
-        raise ValueError("an observation names an image out of range")
-    return n_img
 
 
 def resection_lists(tracks, keypoints, X, has_point, cam_of_image, device=0):
@@ -230,12 +57,9 @@ def resection_lists(tracks, keypoints, X, has_point, cam_of_image, device=0):
     return seg_ptr, corr_track, corr_X, corr_uv
 
 
-def evaluate_tracks(tracks, keypoints, proj_or_poses, X, has_point, K=None, registered=None, min_views=2,
-                    max_error=TRIANGULATION_MAX_ERROR, min_angle_deg=0.0, device=0):
-    """The gates of `triangulate_tracks` at points that are given (after a bundle adjustment, say).  Cameras as
-    `triangulate_tracks` takes them.  Returns {status [n] int32 (sfm_amd._lib.TRI_*, or EVAL_NO_POINT = -1 where has_point
-    is 0), n_views [n] int32, max_err [n], obs_err [n_obs] (NaN: image not registered or no point), counts [6] int64 (the
-    tracks that have a point, by status)}."""
+def _judge_tracks(robust, tracks, keypoints, proj_or_poses, X, has_point, K, registered, min_views, max_error, min_angle_deg,
+                  device):
+    """`evaluate_tracks` (robust False) and `classify_tracks` (True): the host checks, one scene, one call, the download."""
     _check_options(min_views, 0, max_error, min_angle_deg)
     _check_tracks(tracks, keypoints)
     X = np.asarray(X, dtype=np.float64).reshape(-1, 3)
@@ -245,14 +69,30 @@ def evaluate_tracks(tracks, keypoints, proj_or_poses, X, has_point, K=None, regi
     proj, cam_of_image = _cameras(tracks, proj_or_poses, K, registered)
     kp_xy = keypoint_table(tracks, keypoints)
     if len(tracks) == 0:
-        return {"status": np.zeros(0, np.int32), "n_views": np.zeros(0, np.int32), "max_err": np.zeros(0),
-                "obs_err": np.zeros(0), "counts": np.zeros(6, np.int64)}
-    sc = _Scene(tracks.kp_ptr, kp_xy, np.zeros(0, np.int32), tracks.track_ptr, tracks.image, tracks.keypoint, device)
+        out = {"status": np.zeros(0, np.int32), "n_views": np.zeros(0, np.int32), "max_err": np.zeros(0),
+               "obs_err": np.zeros(0), "counts": np.zeros(6, np.int64)}
+        if robust:
+            out.update(n_inliers=np.zeros(0, np.int32), obs_inlier=np.zeros(0, bool))
+        return out
+    sc = _Scene(tracks.kp_ptr, kp_xy, np.zeros(0, np.int32), tracks.track_ptr, tracks.image, tracks.keypoint, device, robust=robust)
     sc.set_points(X, has_point)
     sc.set_cameras(proj, cam_of_image)
-    obs_err = sc.evaluate(min_views, max_error, min_angle_deg, want_obs_err=True)
-    return {"status": sc.status.cpu().numpy(), "n_views": sc.n_views.cpu().numpy(), "max_err": sc.max_err.cpu().numpy(),
-            "obs_err": obs_err.cpu().numpy(), "counts": sc.counts.cpu().numpy()}
+    obs_err = (sc.classify if robust else sc.evaluate)(min_views, max_error, min_angle_deg, want_obs_err=True)
+    out = {"status": sc.status.cpu().numpy(), "n_views": sc.n_views.cpu().numpy(), "max_err": sc.max_err.cpu().numpy(),
+           "obs_err": obs_err.cpu().numpy(), "counts": sc.counts.cpu().numpy()}
+    if robust:
+        out.update(n_inliers=sc.n_inliers.cpu().numpy(), obs_inlier=sc.obs_inlier[:sc.n_obs].cpu().numpy() != 0)
+    return out
+
+
+def evaluate_tracks(tracks, keypoints, proj_or_poses, X, has_point, K=None, registered=None, min_views=2,
+                    max_error=TRIANGULATION_MAX_ERROR, min_angle_deg=0.0, device=0):
+    """The gates of `triangulate_tracks` at points that are given (after a bundle adjustment, say).  Cameras as
+    `triangulate_tracks` takes them.  Returns {status [n] int32 (sfm_amd._lib.TRI_*, or EVAL_NO_POINT = -1 where has_point
+    is 0), n_views [n] int32, max_err [n], obs_err [n_obs] (NaN: image not registered or no point), counts [6] int64 (the
+    tracks that have a point, by status)}."""
+    return _judge_tracks(False, tracks, keypoints, proj_or_poses, X, has_point, K, registered, min_views, max_error,
+                         min_angle_deg, device)
 
 
 def classify_tracks(tracks, keypoints, proj_or_poses, X, has_point, K=None, registered=None, min_views=2,
@@ -263,24 +103,8 @@ def classify_tracks(tracks, keypoints, proj_or_poses, X, has_point, K=None, regi
     has_point is 0), n_views [n] int32, n_inliers [n] int32, max_err [n] (the largest error of an inlier), obs_inlier
     [n_obs] bool, obs_err [n_obs] (NaN: image not registered or no point), counts [6] int64 (the tracks that have a point,
     by status)}."""
-    _check_options(min_views, 0, max_error, min_angle_deg)
-    _check_tracks(tracks, keypoints)
-    X = np.asarray(X, dtype=np.float64).reshape(-1, 3)
-    has_point = np.asarray(has_point).reshape(-1)
-    if len(X) != len(tracks) or len(has_point) != len(tracks):
-        raise ValueError("X / has_point need one entry per track")
-    proj, cam_of_image = _cameras(tracks, proj_or_poses, K, registered)
-    kp_xy = keypoint_table(tracks, keypoints)
-    if len(tracks) == 0:
-        return {"status": np.zeros(0, np.int32), "n_views": np.zeros(0, np.int32), "n_inliers": np.zeros(0, np.int32),
-                "max_err": np.zeros(0), "obs_inlier": np.zeros(0, bool), "obs_err": np.zeros(0), "counts": np.zeros(6, np.int64)}
-    sc = _Scene(tracks.kp_ptr, kp_xy, np.zeros(0, np.int32), tracks.track_ptr, tracks.image, tracks.keypoint, device, robust=True)
-    sc.set_points(X, has_point)
-    sc.set_cameras(proj, cam_of_image)
-    obs_err = sc.classify(min_views, max_error, min_angle_deg, want_obs_err=True)
-    return {"status": sc.status.cpu().numpy(), "n_views": sc.n_views.cpu().numpy(), "n_inliers": sc.n_inliers.cpu().numpy(),
-            "max_err": sc.max_err.cpu().numpy(), "obs_inlier": sc.obs_inlier[:sc.n_obs].cpu().numpy() != 0,
-            "obs_err": obs_err.cpu().numpy(), "counts": sc.counts.cpu().numpy()}
+    return _judge_tracks(True, tracks, keypoints, proj_or_poses, X, has_point, K, registered, min_views, max_error,
+                         min_angle_deg, device)
 
 
 # ------------------------------------------------------------------------------------------------------------ the loop

@@ -6,8 +6,6 @@ No CPU fallback: without the library or a GPU these raise.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
@@ -25,6 +23,15 @@ def _check_options(min_views, refine_iters, max_error, min_angle_deg):
         raise ValueError("min_angle_deg must lie in [0, 180]")
 
 
+def _check_tracks(tracks, keypoints):
+    n_img = len(tracks.kp_ptr) - 1
+    if len(keypoints) != n_img:
+        raise ValueError(f"{len(keypoints)} keypoint lists for {n_img} images")
+    if tracks.n_obs and (tracks.image.min() < 0 or tracks.image.max() >= n_img):
+        raise ValueError("an observation names an image out of range")
+    return n_img
+
+
 def triangulate_tracks_raw(proj, cam_of_image, kp_ptr, kp_xy, track_ptr, obs_image, obs_kp, min_views=2, refine_iters=5,
                            max_error=TRIANGULATION_MAX_ERROR, min_angle_deg=0.0, device=0, robust=False):
     """sfm_triangulate_tracks on flat host arrays, nothing validated but the options (the device treats an image or camera
@@ -33,46 +40,16 @@ def triangulate_tracks_raw(proj, cam_of_image, kp_ptr, kp_xy, track_ptr, obs_ima
     obs_image, obs_kp: the CSR arrays of the tracks.  Returns {X [n,3], status int32, n_views int32, max_err, counts [6]}.
     robust=True: sfm_triangulate_tracks_robust (an outlier observation is dropped, not the point); the result gains
     n_inliers [n] int32 and obs_inlier [n_obs] uint8."""
-    import torch
-    from .driver import _p
+    from ._track_scene import _Scene
     _check_options(min_views, refine_iters, max_error, min_angle_deg)
-    h = _lib.get_handle(device)
-    dev = torch.device("cuda", device)
-    _dev = lambda a, dtype: torch.from_numpy(np.array(a, dtype=dtype, order="C")).to(dev)    # a copy: inputs may be read-only
-    proj = np.asarray(proj, dtype=np.float64).reshape(-1, 12)
-    kp_xy = np.asarray(kp_xy, dtype=np.float64).reshape(-1, 2)
-    n_cams, n_img, n_nodes = proj.shape[0], len(cam_of_image), kp_xy.shape[0]
-    n_tracks, n_obs = len(track_ptr) - 1, len(obs_image)
-    d_proj, d_cam = _dev(proj, np.float64), _dev(cam_of_image, np.int32)
-    d_kp, d_xy = _dev(kp_ptr, np.int64), _dev(kp_xy, np.float64)
-    d_tp, d_img, d_okp = _dev(track_ptr, np.int64), _dev(obs_image, np.int32), _dev(obs_kp, np.int32)
-    need = C.c_int64()
+    sc = _Scene(kp_ptr, kp_xy, np.zeros(0, np.int32), track_ptr, obs_image, obs_kp, device, robust=robust)
+    sc.set_cameras(proj, cam_of_image)
+    (sc.triangulate_robust if robust else sc.triangulate)(min_views, refine_iters, max_error, min_angle_deg)
+    out = {"X": sc.X_tri.cpu().numpy(), "status": sc.status.cpu().numpy(), "n_views": sc.n_views.cpu().numpy(),
+           "max_err": sc.max_err.cpu().numpy(), "counts": sc.counts.cpu().numpy()}
     if robust:
-        h.check(h.lib.sfm_triangulate_tracks_robust_workspace_bytes(n_cams, n_tracks, C.byref(need)),
-                "sfm_triangulate_tracks_robust_workspace_bytes")
-    else:
-        h.check(h.lib.sfm_triangulate_tracks_workspace_bytes(n_cams, C.byref(need)), "sfm_triangulate_tracks_workspace_bytes")
-    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-    X = torch.empty((n_tracks, 3), dtype=torch.float64, device=dev)
-    status = torch.empty(n_tracks, dtype=torch.int32, device=dev)
-    n_views = torch.empty(n_tracks, dtype=torch.int32, device=dev)
-    max_err = torch.empty(n_tracks, dtype=torch.float64, device=dev)
-    counts = torch.empty(6, dtype=torch.int64, device=dev)
-    if robust:
-        n_inliers = torch.empty(n_tracks, dtype=torch.int32, device=dev)
-        obs_inlier = torch.zeros(max(n_obs, 1), dtype=torch.uint8, device=dev)
-        h.call("sfm_triangulate_tracks_robust", _p(d_proj), n_cams, _p(d_cam), n_img, _p(d_kp), _p(d_xy), n_nodes, _p(d_tp),
-               n_tracks, _p(d_img), _p(d_okp), n_obs, int(min_views), int(refine_iters), C.c_double(max_error),
-               C.c_double(min_angle_deg), _p(X), _p(status), _p(n_views), _p(n_inliers), _p(max_err), _p(obs_inlier), _p(counts),
-               _p(ws), need.value)
-        return {"X": X.cpu().numpy(), "status": status.cpu().numpy(), "n_views": n_views.cpu().numpy(),
-                "n_inliers": n_inliers.cpu().numpy(), "max_err": max_err.cpu().numpy(),
-                "obs_inlier": obs_inlier[:n_obs].cpu().numpy(), "counts": counts.cpu().numpy()}
-    h.call("sfm_triangulate_tracks", _p(d_proj), n_cams, _p(d_cam), n_img, _p(d_kp), _p(d_xy), n_nodes, _p(d_tp), n_tracks,
-           _p(d_img), _p(d_okp), n_obs, int(min_views), int(refine_iters), C.c_double(max_error), C.c_double(min_angle_deg),
-           _p(X), _p(status), _p(n_views), _p(max_err), _p(counts), _p(ws), need.value)
-    return {"X": X.cpu().numpy(), "status": status.cpu().numpy(), "n_views": n_views.cpu().numpy(),
-            "max_err": max_err.cpu().numpy(), "counts": counts.cpu().numpy()}
+        out.update(n_inliers=sc.n_inliers.cpu().numpy(), obs_inlier=sc.obs_inlier_tri[:sc.n_obs].cpu().numpy())
+    return out
 
 
 class Triangulation:
@@ -189,11 +166,7 @@ def triangulate_tracks(tracks, keypoints, proj_or_poses, K=None, registered=None
     searched for a consensus of at least 3 views, see sfm_triangulate_tracks_robust in include/sfm_amd.h) and the
     Triangulation carries obs_inlier.  Everything is validated on the host first (ValueError); returns a Triangulation."""
     _check_options(min_views, refine_iters, max_error, min_angle_deg)
-    n_img = len(tracks.kp_ptr) - 1
-    if len(keypoints) != n_img:
-        raise ValueError(f"{len(keypoints)} keypoint lists for {n_img} images")
-    if tracks.n_obs and (tracks.image.min() < 0 or tracks.image.max() >= n_img):
-        raise ValueError("an observation names an image out of range")
+    _check_tracks(tracks, keypoints)
     proj, cam_of_image = _cameras(tracks, proj_or_poses, K, registered)
     kp_xy = keypoint_table(tracks, keypoints)
     out = triangulate_tracks_raw(proj, cam_of_image, tracks.kp_ptr, kp_xy, tracks.track_ptr, tracks.image, tracks.keypoint,

@@ -173,6 +173,15 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.sfm_version()
 
 
+def test_track_calls_share_one_source_prefix():
+    """The four track-judging entry points take the handle and then the same 12 source arguments, spelled once."""
+    from sfm_amd import _lib
+    prefix = [_lib.vp] + list(_lib.TRACK_SOURCE)
+    assert len(prefix) == 13
+    shared = {name for name, (_, args) in _lib.SIGNATURES.items() if args[:13] == prefix}
+    assert shared == {"sfm_triangulate_tracks", "sfm_triangulate_tracks_robust", "sfm_tracks_evaluate", "sfm_tracks_classify"}
+
+
 def test_argument_checks_without_gpu():
     """Entry points reject null handles / problems before touching a device (no compute without a GPU)."""
     from sfm_amd import _lib

@@ -18,6 +18,7 @@ import triangulate_reference as tr
 from test_triangulate_gpu import GATES, gate_scene, take_tracks
 from test_triangulate_reference import flat, rel_dev_scalars, status_cases
 from test_tracks_reference import shipped
+from track_calls import judge_raw
 
 pytestmark = pytest.mark.gpu
 
@@ -151,35 +152,7 @@ def test_public_resection_lists(gpu_ready):
 
 
 # ----------------------------------------------------------------------------------------------------------- evaluate
-def device_evaluate(args, X, has_point, want_obs_err=True, **opts):
-    """sfm_tracks_evaluate on flat host arrays: {status, n_views, max_err, obs_err, counts}."""
-    import torch
-    from sfm_amd import _lib
-    from sfm_amd.driver import _p
-    o = dict(min_views=2, max_error=4.0, min_angle_deg=0.0)
-    o.update(opts)
-    h = _lib.get_handle(0)
-    dev = torch.device("cuda", 0)
-    up = lambda a, dt: torch.from_numpy(np.array(a, dtype=dt, order="C")).to(dev)
-    proj, cam, kp_ptr, kp_xy, track_ptr, obs_image, obs_kp = args
-    proj = np.asarray(proj, dtype=np.float64).reshape(-1, 12)
-    n_tracks, n_obs = len(track_ptr) - 1, len(obs_image)
-    d = [up(proj, np.float64), up(cam, np.int32), up(kp_ptr, np.int64), up(np.asarray(kp_xy).reshape(-1, 2), np.float64),
-         up(track_ptr, np.int64), up(obs_image, np.int32), up(obs_kp, np.int32), up(np.asarray(X).reshape(-1, 3), np.float64),
-         up(np.asarray(has_point) != 0, np.uint8)]
-    need = C.c_int64()
-    assert h.lib.sfm_triangulate_tracks_workspace_bytes(len(proj), C.byref(need)) == 0
-    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-    status = torch.full((n_tracks,), 77, dtype=torch.int32, device=dev)
-    n_views = torch.full((n_tracks,), 77, dtype=torch.int32, device=dev)
-    max_err = torch.zeros(n_tracks, dtype=torch.float64, device=dev)
-    obs_err = torch.zeros(max(n_obs, 1), dtype=torch.float64, device=dev) if want_obs_err else None
-    counts = torch.full((6,), 7, dtype=torch.int64, device=dev)
-    h.call("sfm_tracks_evaluate", _p(d[0]), len(proj), _p(d[1]), len(cam), _p(d[2]), _p(d[3]), len(d[3]), _p(d[4]), n_tracks,
-           _p(d[5]), _p(d[6]), n_obs, _p(d[7]), _p(d[8]), int(o["min_views"]), C.c_double(o["max_error"]),
-           C.c_double(o["min_angle_deg"]), _p(status), _p(n_views), _p(max_err), _p(obs_err), _p(counts), _p(ws), need.value)
-    return {"status": status.cpu().numpy(), "n_views": n_views.cpu().numpy(), "max_err": max_err.cpu().numpy(),
-            "obs_err": obs_err[:n_obs].cpu().numpy() if want_obs_err else None, "counts": counts.cpu().numpy()}
+device_evaluate = functools.partial(judge_raw, "sfm_tracks_evaluate")       # {status, n_views, max_err, obs_err, counts}
 
 
 def assert_evaluate_parity(args, X, has, what, **opts):

@@ -15,6 +15,7 @@ import triangulate_robust_reference as rr
 from test_triangulate_gpu import GATES as PLAIN_GATES, parity_device, parity_scene, take_tracks
 from test_triangulate_reference import flat, rel_dev_points, rel_dev_scalars
 from test_triangulate_robust_reference import EDGE_OPTIONS, GATES, edge_reference, outlier_reference
+from track_calls import judge_raw
 
 pytestmark = pytest.mark.gpu
 
@@ -219,39 +220,7 @@ def test_a_track_does_not_depend_on_its_batch(gpu_ready):
 
 
 # ----------------------------------------------------------------------------------------------------------- classify
-def device_classify(args, X, has_point, want_obs_err=True, **opts):
-    """sfm_tracks_classify on flat host arrays."""
-    import torch
-    from sfm_amd import _lib
-    from sfm_amd.driver import _p
-    o = dict(min_views=2, max_error=4.0, min_angle_deg=0.0)
-    o.update(opts)
-    h = _lib.get_handle(0)
-    dev = torch.device("cuda", 0)
-    up = lambda a, dt: torch.from_numpy(np.array(a, dtype=dt, order="C")).to(dev)
-    proj, cam, kp_ptr, kp_xy, track_ptr, obs_image, obs_kp = args
-    proj = np.asarray(proj, dtype=np.float64).reshape(-1, 12)
-    n_tracks, n_obs = len(track_ptr) - 1, len(obs_image)
-    d = [up(proj, np.float64), up(cam, np.int32), up(kp_ptr, np.int64), up(np.asarray(kp_xy).reshape(-1, 2), np.float64),
-         up(track_ptr, np.int64), up(obs_image, np.int32), up(obs_kp, np.int32), up(np.asarray(X).reshape(-1, 3), np.float64),
-         up(np.asarray(has_point) != 0, np.uint8)]
-    need = C.c_int64()
-    assert h.lib.sfm_triangulate_tracks_workspace_bytes(len(proj), C.byref(need)) == 0
-    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-    status = torch.full((n_tracks,), 77, dtype=torch.int32, device=dev)
-    n_views = torch.full((n_tracks,), 77, dtype=torch.int32, device=dev)
-    n_inliers = torch.full((n_tracks,), 77, dtype=torch.int32, device=dev)
-    max_err = torch.zeros(n_tracks, dtype=torch.float64, device=dev)
-    flags = torch.full((max(n_obs, 1),), 77, dtype=torch.uint8, device=dev)
-    obs_err = torch.zeros(max(n_obs, 1), dtype=torch.float64, device=dev) if want_obs_err else None
-    counts = torch.full((6,), 7, dtype=torch.int64, device=dev)
-    h.call("sfm_tracks_classify", _p(d[0]), len(proj), _p(d[1]), len(cam), _p(d[2]), _p(d[3]), len(d[3]), _p(d[4]), n_tracks,
-           _p(d[5]), _p(d[6]), n_obs, _p(d[7]), _p(d[8]), int(o["min_views"]), C.c_double(o["max_error"]),
-           C.c_double(o["min_angle_deg"]), _p(status), _p(n_views), _p(n_inliers), _p(max_err), _p(flags), _p(obs_err),
-           _p(counts), _p(ws), need.value)
-    return {"status": status.cpu().numpy(), "n_views": n_views.cpu().numpy(), "n_inliers": n_inliers.cpu().numpy(),
-            "max_err": max_err.cpu().numpy(), "obs_inlier": flags[:n_obs].cpu().numpy(),
-            "obs_err": obs_err[:n_obs].cpu().numpy() if want_obs_err else None, "counts": counts.cpu().numpy()}
+device_classify = functools.partial(judge_raw, "sfm_tracks_classify")       # evaluate's keys and {n_inliers, obs_inlier}
 
 
 def test_classify_at_perturbed_points_equals_the_restatement(gpu_ready):

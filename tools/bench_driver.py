@@ -611,6 +611,14 @@ def _triangulate_cases():
     return cases
 
 
+def _track_source(d, n_cams, n_tracks, n_obs, kp_xy=None):
+    """The 12 arguments the four track calls share after the handle (include/sfm_amd.h), from the device tensors of one
+    workload of _triangulate_case: every camera an image, every observation a node; kp_xy replaces the workload's pixels."""
+    from sfm_amd.driver import _p
+    return (_p(d["proj"]), n_cams, _p(d["cam_of_image"]), n_cams, _p(d["kp_ptr"]), _p(d["kp_xy"] if kp_xy is None else kp_xy),
+            n_obs, _p(d["track_ptr"]), n_tracks, _p(d["obs_image"]), _p(d["obs_kp"]), n_obs)
+
+
 def measure_triangulate(reps=20, emit=None):
     """sfm_triangulate_tracks, inputs resident in HBM, device time of the whole call (camera-centre prologue, counter reset
     and the track kernel) by HIP events around `reps` calls after warm-up, on (a) a set shaped like the shipped tracks (35
@@ -632,6 +640,7 @@ def measure_triangulate(reps=20, emit=None):
         d = {k: _dev(c[k], t, dev) for k, t in (("proj", np.float64), ("cam_of_image", np.int32), ("kp_ptr", np.int64),
                                                 ("kp_xy", np.float64), ("track_ptr", np.int64), ("obs_image", np.int32),
                                                 ("obs_kp", np.int32))}
+        src = _track_source(d, n_cams, n_tracks, n_obs)
         need = C.c_int64(); h.lib.sfm_triangulate_tracks_workspace_bytes(n_cams, C.byref(need))
         ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
         X = torch.empty((n_tracks, 3), dtype=torch.float64, device=dev); me = torch.empty(n_tracks, dtype=torch.float64, device=dev)
@@ -644,9 +653,8 @@ def measure_triangulate(reps=20, emit=None):
                "stream_bytes": int(stream_bytes), "hbm_stream_floor_ms": floor_s * 1e3, "hbm_stream_Bps_assumed": HBM_STREAM_BPS}
         for iters in (0, 5):
             def run():
-                h.call("sfm_triangulate_tracks", _p(d["proj"]), n_cams, _p(d["cam_of_image"]), n_cams, _p(d["kp_ptr"]),
-                       _p(d["kp_xy"]), n_obs, _p(d["track_ptr"]), n_tracks, _p(d["obs_image"]), _p(d["obs_kp"]), n_obs, 2, iters,
-                       C.c_double(4.0), C.c_double(1.0), _p(X), _p(st), _p(nv), _p(me), _p(counts), _p(ws), need.value)
+                h.call("sfm_triangulate_tracks", *src, 2, iters, C.c_double(4.0), C.c_double(1.0), _p(X), _p(st), _p(nv), _p(me),
+                       _p(counts), _p(ws), need.value)
             for _ in range(3):
                 run()
             sec = timed(run, reps)
@@ -684,16 +692,15 @@ def measure_triangulate(reps=20, emit=None):
         xy_moved = c["kp_xy"].copy()
         xy_moved[node[moved]] += np.stack([rad * np.cos(ang), rad * np.sin(ang)], axis=1)
         for what, xy in (("as they are", d["kp_xy"]), ("5 % moved by 30 to 100 px", _dev(xy_moved, np.float64, dev))):
+            src_xy = _track_source(d, n_cams, n_tracks, n_obs, kp_xy=xy)
+
             def run_plain():
-                h.call("sfm_triangulate_tracks", _p(d["proj"]), n_cams, _p(d["cam_of_image"]), n_cams, _p(d["kp_ptr"]),
-                       _p(xy), n_obs, _p(d["track_ptr"]), n_tracks, _p(d["obs_image"]), _p(d["obs_kp"]), n_obs, 2, 5,
-                       C.c_double(4.0), C.c_double(1.0), _p(X), _p(st), _p(nv), _p(me), _p(counts), _p(ws), need.value)
+                h.call("sfm_triangulate_tracks", *src_xy, 2, 5, C.c_double(4.0), C.c_double(1.0), _p(X), _p(st), _p(nv), _p(me),
+                       _p(counts), _p(ws), need.value)
 
             def run_robust():
-                h.call("sfm_triangulate_tracks_robust", _p(d["proj"]), n_cams, _p(d["cam_of_image"]), n_cams, _p(d["kp_ptr"]),
-                       _p(xy), n_obs, _p(d["track_ptr"]), n_tracks, _p(d["obs_image"]), _p(d["obs_kp"]), n_obs, 2, 5,
-                       C.c_double(4.0), C.c_double(1.0), _p(X), _p(st), _p(nv), _p(ni), _p(me), _p(flags), _p(counts), _p(ws_r),
-                       need_r.value)
+                h.call("sfm_triangulate_tracks_robust", *src_xy, 2, 5, C.c_double(4.0), C.c_double(1.0), _p(X), _p(st), _p(nv),
+                       _p(ni), _p(me), _p(flags), _p(counts), _p(ws_r), need_r.value)
             for _ in range(3):
                 run_plain()
             sec_plain = timed(run_plain, reps)
@@ -767,22 +774,21 @@ def measure_incremental(reps=20, emit=None):
         d = {k: _dev(c[k], t, dev) for k, t in (("proj", np.float64), ("cam_of_image", np.int32), ("kp_ptr", np.int64),
                                                 ("kp_xy", np.float64), ("track_ptr", np.int64), ("obs_image", np.int32),
                                                 ("obs_kp", np.int32))}
+        src = _track_source(d, n_cams, n_tracks, n_obs)
         need = C.c_int64(); h.lib.sfm_triangulate_tracks_workspace_bytes(n_cams, C.byref(need))
         ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
         X = torch.empty((n_tracks, 3), dtype=torch.float64, device=dev); me = torch.empty(n_tracks, dtype=torch.float64, device=dev)
         st = torch.empty(n_tracks, dtype=torch.int32, device=dev); nv = torch.empty(n_tracks, dtype=torch.int32, device=dev)
         counts = torch.empty(6, dtype=torch.int64, device=dev)
-        h.call("sfm_triangulate_tracks", _p(d["proj"]), n_cams, _p(d["cam_of_image"]), n_cams, _p(d["kp_ptr"]), _p(d["kp_xy"]),
-               n_obs, _p(d["track_ptr"]), n_tracks, _p(d["obs_image"]), _p(d["obs_kp"]), n_obs, 2, 5, C.c_double(4.0),
-               C.c_double(1.0), _p(X), _p(st), _p(nv), _p(me), _p(counts), _p(ws), need.value)
+        h.call("sfm_triangulate_tracks", *src, 2, 5, C.c_double(4.0), C.c_double(1.0), _p(X), _p(st), _p(nv), _p(me), _p(counts),
+               _p(ws), need.value)
         has = (st == 0).to(torch.uint8)
         X_h, has_h = X.cpu().numpy(), has.cpu().numpy()
         obs_err = torch.empty(n_obs, dtype=torch.float64, device=dev)
 
         def evaluate():
-            h.call("sfm_tracks_evaluate", _p(d["proj"]), n_cams, _p(d["cam_of_image"]), n_cams, _p(d["kp_ptr"]), _p(d["kp_xy"]),
-                   n_obs, _p(d["track_ptr"]), n_tracks, _p(d["obs_image"]), _p(d["obs_kp"]), n_obs, _p(X), _p(has), 2,
-                   C.c_double(4.0), C.c_double(1.0), _p(st), _p(nv), _p(me), _p(obs_err), _p(counts), _p(ws), need.value)
+            h.call("sfm_tracks_evaluate", *src, _p(X), _p(has), 2, C.c_double(4.0), C.c_double(1.0), _p(st), _p(nv), _p(me),
+                   _p(obs_err), _p(counts), _p(ws), need.value)
         for _ in range(3):
             evaluate()
         sec = timed(evaluate, reps)

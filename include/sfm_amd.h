@@ -884,6 +884,64 @@ int sfm_depth_filter(sfm_handle h, const int64_t* img_off /* host */, const int3
                      double rel_tol, int32_t min_consistent, uint8_t* n_consistent, uint8_t* keep,
                      double* xyz /* device [n_out][3] */, void* workspace, int64_t workspace_bytes);
 
+/* ---- fusion of the depth maps into one cloud with normals (sfm_amd/csrc/depth_fuse.hip, depth_rule.h, depth_plan.h) ----
+ * From the inputs of sfm_depth_filter and its outputs depth, keep and xyz (on the device): every surface point once, as
+ * the mean of the views that agree on it, with a normal.  A pure function of those arrays: no visit order, no atomics on
+ * memory, no randomness.  All floating point is float64 without FMA contraction, everything else is integer, so the
+ * output bytes are the same from run to run.  Parameters: rel_tol >= 0, normal_step t in 1 .. 4, normal_jump j >= 0.
+ * "Position" of a view is its index in ref_image.  X(x, y) is the xyz of a pixel, d its float32 depth widened to double.
+ *
+ * 1. Normal map per view (normal_map, float32 [n_out][3]; keep plays no part).  With the neighbours at clamp(x +- t) and
+ *    clamp(y +- t), coordinates clamped to the view's image:  a = X(x+t, y) - X(x-t, y),  b = X(x, y+t) - X(x, y-t),
+ *    n = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0),  l2 = (n0*n0 + n1*n1) + n2*n2.  The normal is valid iff the centre
+ *    depth d is finite, each of the four neighbour depths dn is finite with fabs(dn - d) <= j * d, and l2 is finite and
+ *    > 0.  Then n_i = n_i / sqrt(l2), and n is negated when ((n0*c0 + n1*c1) + n2*c2) < 0 with c = C - X, C the view's
+ *    centre (elements 3, 7, 11 of backproj[r]).  Rounded to float32; an invalid normal is (0, 0, 0).  An image one pixel
+ *    wide or high has no valid normal (a or b is zero).
+ * 2. Partners.  For a pixel p of view v with keep = 1, entry s (0 .. 7) of the view's sources agrees iff the source has
+ *    maps of its own, the sample rule at the pixel's depth d is valid, ds = the source's depth at (yi, xi) is finite,
+ *    fabs(ds - q2) <= rel_tol * q2, and keep of that source pixel is 1.  agree_mask (uint8 [n_out]) has bit s set for
+ *    each agreeing entry and is 0 where keep = 0;  n_views = 1 + popcount(agree_mask).
+ * 3. Owner (uint8 [n_out]) = keep and no agreeing partner lies in a view of lower position.  A pixel is dropped only in
+ *    favour of a kept pixel of an earlier view: by induction over the positions every kept pixel is an owner or reaches
+ *    one through a chain of agreeing partners, and view 0 loses nothing.
+ * 4. Fused point and normal, owners only.  acc = X(p); for the agreeing entries in entry order acc_i = acc_i + X_s_i with
+ *    X_s the xyz of the partner pixel; point_i = acc_i / (double)n_views.  The normal is the same sum over the float32
+ *    normals of the normal maps widened to double, the pixel's own first, invalid ones adding zero; l2 as above; when l2
+ *    is finite and > 0 each sum is divided by sqrt(l2), otherwise the normal is (0, 0, 0); rounded to float32.
+ * 5. Output order: the owners in (view position, row-major) order.  points float64 [m][3], normals float32 [m][3],
+ *    n_views uint8 [m], index int32 [m][3] as (view position, y, x); pt_ptr int64 [n_ref+1] on the device, the owners of
+ *    view v are the points pt_ptr[v] .. pt_ptr[v+1], m = pt_ptr[n_ref].
+ * Limits.  Agreement is not transitive: several pixels of a close view can fall on one pixel of a farther, earlier view
+ *    and are all dropped, so the earlier view's resolution wins.  No forward-backward check is added: the partner need
+ *    not project back onto p.  Sources without maps of their own never count.
+ * Two calls.  sfm_depth_fuse_mark writes normal_map, agree_mask, owner and pt_ptr and leaves the first output slot of
+ *    every block of 256 pixels in the workspace; the caller reads pt_ptr[n_ref] (after a synchronisation of the stream),
+ *    allocates the outputs and hands the same workspace, untouched, with the same views to sfm_depth_fuse_gather, which
+ *    returns at once for n_points == 0.  n_points is the capacity of the outputs: a value between 0 and the number of
+ *    pixels cannot be checked against the device's count on the host and is NOT checked; the gather writes no slot at or
+ *    above it, nor outside pt_ptr's range of the pixel's view, so a wrong value loses points but writes nothing outside.
+ * The workspace (sfm_depth_fuse_workspace_bytes; n_out = the pixels of all views) is larger than that of
+ *    sfm_depth_workspace_bytes and may be the same buffer.  SFM_ERR_ARG before any device work for what
+ *    sfm_depth_filter refuses, a normal_step outside 1 .. 4, a negative or NaN normal_jump or rel_tol, a negative n_points
+ *    or one above the number of pixels.  No kernel reads outside a map. */
+int sfm_depth_fuse_workspace_bytes(int32_t n_img, int32_t n_ref, int64_t n_entries, int64_t n_out, int64_t* bytes_host);
+int sfm_depth_fuse_mark(sfm_handle h, const int64_t* img_off /* host */, const int32_t* heights /* host */,
+                        const int32_t* widths /* host */, int32_t n_img, int32_t n_ref, const int32_t* ref_image /* host */,
+                        const int64_t* src_ptr /* host [n_ref+1] */, const int32_t* src_image /* host */,
+                        const double* warps /* device [n_entries][12] */, const double* backproj /* device [n_ref][12] */,
+                        const float* depth, const uint8_t* keep, const double* xyz, double rel_tol, int32_t normal_step,
+                        double normal_jump, float* normal_map /* device [n_out][3] */, uint8_t* agree_mask, uint8_t* owner,
+                        int64_t* pt_ptr /* device [n_ref+1] */, void* workspace, int64_t workspace_bytes);
+int sfm_depth_fuse_gather(sfm_handle h, const int64_t* img_off /* host */, const int32_t* heights /* host */,
+                          const int32_t* widths /* host */, int32_t n_img, int32_t n_ref, const int32_t* ref_image /* host */,
+                          const int64_t* src_ptr /* host [n_ref+1] */, const int32_t* src_image /* host */,
+                          const double* warps /* device [n_entries][12] */, const float* depth, const double* xyz,
+                          const float* normal_map, const uint8_t* agree_mask, const uint8_t* owner,
+                          const int64_t* pt_ptr /* device [n_ref+1] */, int64_t n_points, double* points /* [n_points][3] */,
+                          float* normals /* [n_points][3] */, uint8_t* n_views, int32_t* index /* [n_points][3] */,
+                          void* workspace, int64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,5 +10,5 @@ from .incremental import Reconstruction, classify_tracks, evaluate_tracks, recon
 from .features import Features, detect_and_describe_batched, detect_features  # noqa: F401
 from .interchange import read_pnm, save_ply_points, write_pnm  # noqa: F401
 from .guided import guided_match_pairs  # noqa: F401
-from .depth import (DepthMaps, dense_from_reconstruction, depth_maps, depth_ranges, plane_depths, select_sources,  # noqa: F401
+from .depth import (DepthMaps, FusedCloud, dense_from_reconstruction, depth_maps, depth_maps_from_arrays, depth_ranges, plane_depths, select_sources,  # noqa: F401
                     view_backprojection, view_warps)

@@ -170,6 +170,9 @@ SIGNATURES = {
     "sfm_depth_census": (C.c_int, [vp, vp, vp, vp, vp, i32, vp, vp, i64]),
     "sfm_depth_sweep": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64]),
     "sfm_depth_filter": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f64, i32, vp, vp, vp, vp, i64]),
+    "sfm_depth_fuse_workspace_bytes": (C.c_int, [i32, i32, i64, i64, C.POINTER(i64)]),
+    "sfm_depth_fuse_mark": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f64, i32, f64, vp, vp, vp, vp, vp, i64]),
+    "sfm_depth_fuse_gather": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64]),
 }
 
 _lib = None

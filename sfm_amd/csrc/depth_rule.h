@@ -87,4 +87,63 @@ DEPTH_HD double backproject(const double* row, double x, double y, double d) {
   return d * ((row[0] * x + row[1] * y) + row[2]) + row[3];
 }
 
+// ---- fusion (depth_fuse.hip; include/sfm_amd.h, "fusion of the depth maps"; tests/depth_fuse_reference.py) ----
+// whether a number is finite: false on NaN and on +-inf
+DEPTH_HD int is_finite(double v) { return v - v == 0.0; }
+
+// the neighbour depth dn belongs to the surface of the centre depth d: finite and within jump * d of it
+DEPTH_HD int near_depth(double dn, double d, double jump) { return is_finite(dn) && (fabs(dn - d) <= jump * d); }
+
+// n = (xp - xm) x (yp - ym) of four points, every product and difference rounded on its own
+DEPTH_HD void cross_of_differences(const double* xp, const double* xm, const double* yp, const double* ym, double* n) {
+  const double a0 = xp[0] - xm[0], a1 = xp[1] - xm[1], a2 = xp[2] - xm[2];
+  const double b0 = yp[0] - ym[0], b1 = yp[1] - ym[1], b2 = yp[2] - ym[2];
+  n[0] = a1 * b2 - a2 * b1;
+  n[1] = a2 * b0 - a0 * b2;
+  n[2] = a0 * b1 - a1 * b0;
+}
+
+DEPTH_HD double norm2(const double* n) { return (n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]; }
+
+// n / sqrt(l2) in place when l2 is finite and > 0 (returns 1); otherwise n = 0 (returns 0)
+DEPTH_HD int normalise(double* n, double l2) {
+  if (!(is_finite(l2) && l2 > 0.0)) { n[0] = 0.0; n[1] = 0.0; n[2] = 0.0; return 0; }
+  const double l = sqrt(l2);
+  n[0] = n[0] / l; n[1] = n[1] / l; n[2] = n[2] / l;
+  return 1;
+}
+
+// turn n towards the camera centre C seen from the point X
+DEPTH_HD void orient(double* n, const double* C, const double* X) {
+  const double c0 = C[0] - X[0], c1 = C[1] - X[1], c2 = C[2] - X[2];
+  if (((n[0] * c0 + n[1] * c1) + n[2] * c2) < 0.0) { n[0] = -n[0]; n[1] = -n[1]; n[2] = -n[2]; }
+}
+
+// the normal of a pixel of a view's map: d the centre depth and X its point, dn[4] the depths of the neighbours in the
+// order (x+t, x-t, y+t, y-t) and xp / xm / yp / ym their points, C the view's centre.  out = (0, 0, 0) when the normal is
+// not valid.
+DEPTH_HD int view_normal(double d, const double* X, const double* dn, const double* xp, const double* xm, const double* yp,
+                         const double* ym, const double* C, double jump, float* out) {
+  double n[3] = {0.0, 0.0, 0.0};
+  int valid = is_finite(d);
+  for (int k = 0; k < 4; ++k) valid = valid && near_depth(dn[k], d, jump);
+  if (valid) {
+    cross_of_differences(xp, xm, yp, ym, n);
+    valid = normalise(n, norm2(n));
+    if (valid) orient(n, C, X);
+  }
+  out[0] = (float)n[0]; out[1] = (float)n[1]; out[2] = (float)n[2];
+  return valid;
+}
+
+// one coordinate of the fused point: the sum of the agreeing views' coordinates over their number
+DEPTH_HD double fused_mean(double acc, int n_views) { return acc / (double)n_views; }
+
+// the fused normal from the sum of the views' float32 normals: unit length, or zeros when the sum has no length
+DEPTH_HD void fused_normal(const double* acc, float* out) {
+  double n[3] = {acc[0], acc[1], acc[2]};
+  normalise(n, norm2(n));
+  out[0] = (float)n[0]; out[1] = (float)n[1]; out[2] = (float)n[2];
+}
+
 }  // namespace depth

@@ -14,6 +14,7 @@ import numpy as np
 from . import _lib
 
 MAX_SOURCES, MAX_RADIUS, MAX_PLANES = 8, 4, 1024
+MAX_NORMAL_STEP = 4
 
 
 def _K_of(K, image):
@@ -252,7 +253,53 @@ class DepthMaps:
             self._host.pop(name, None)
         self.n_consistent, self.keep = self._split("n_consistent"), self._split("keep")
         self.xyz = self._split("xyz", (3,))
+        self._rel_tol = float(rel_tol)
         return self
+
+    def fuse(self, rel_tol=None, normal_step=2, normal_jump=0.05):
+        """The kept pixels of all views fused into one cloud with normals on the device (`sfm_depth_fuse_mark` /
+        `sfm_depth_fuse_gather`; include/sfm_amd.h states the rule): a surface point is kept once, by the earliest view that
+        sees it, as the mean of the views that agree on it.  rel_tol: the agreement of two views' depths, None for the value
+        of the last `.filter()`; normal_step: the normal of a pixel comes from its neighbours this many pixels away, 1 .. 4;
+        normal_jump: a neighbour whose depth differs by more than this share of the pixel's is across an edge, and the pixel
+        gets no normal.  Needs `.filter()` first.  Returns a `FusedCloud`."""
+        import torch
+        if self.keep is None:
+            raise ValueError("fuse() needs filter() first")
+        rel_tol = self._rel_tol if rel_tol is None else rel_tol
+        if not (isinstance(rel_tol, Real) and rel_tol >= 0):
+            raise ValueError("rel_tol must be None or a number >= 0")
+        if not (isinstance(normal_step, (int, np.integer)) and 1 <= normal_step <= MAX_NORMAL_STEP):
+            raise ValueError(f"normal_step must be an integer 1 .. {MAX_NORMAL_STEP}")
+        if not (isinstance(normal_jump, Real) and normal_jump >= 0):
+            raise ValueError("normal_jump must be a number >= 0")
+        s = self._s
+        n, n_ref, n_img = max(s["n_out"], 1), len(self.views), len(s["imgs"])
+        dev = s["depth"].device
+        h = _lib.get_handle(dev.index)
+        need = C.c_int64()
+        h.check(h.lib.sfm_depth_fuse_workspace_bytes(n_img, n_ref, len(s["src_image"]), s["n_out"], C.byref(need)),
+                "sfm_depth_fuse_workspace_bytes")
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        f = {"view_normals": torch.empty((n, 3), dtype=torch.float32, device=dev),
+             "agree_mask": torch.empty(n, dtype=torch.uint8, device=dev), "owner": torch.empty(n, dtype=torch.uint8, device=dev),
+             "pt_ptr": torch.empty(n_ref + 1, dtype=torch.int64, device=dev)}
+        dp = lambda t: C.c_void_p(t.data_ptr())
+        hp = lambda a: C.c_void_p(a.ctypes.data)
+        views = (hp(s["off"]), hp(s["heights"]), hp(s["widths"]), n_img, n_ref, hp(s["ref_image"]), hp(s["src_ptr"]), hp(s["src_image"]),
+                 dp(s["warps"]))
+        h.call("sfm_depth_fuse_mark", *views, dp(s["backproj"]), dp(s["depth"]), dp(s["keep"]), dp(s["xyz"]), C.c_double(float(rel_tol)),
+               int(normal_step), C.c_double(float(normal_jump)), dp(f["view_normals"]), dp(f["agree_mask"]), dp(f["owner"]),
+               dp(f["pt_ptr"]), dp(ws), need.value)
+        pt_ptr = f["pt_ptr"].cpu().numpy()                       # waits for the mark call: the number of points sizes the outputs
+        m = int(pt_ptr[-1])
+        f["points"] = torch.empty((max(m, 1), 3), dtype=torch.float64, device=dev)
+        f["normals"] = torch.empty((max(m, 1), 3), dtype=torch.float32, device=dev)
+        f["n_views"] = torch.empty(max(m, 1), dtype=torch.uint8, device=dev)
+        f["index"] = torch.empty((max(m, 1), 3), dtype=torch.int32, device=dev)
+        h.call("sfm_depth_fuse_gather", *views, dp(s["depth"]), dp(s["xyz"]), dp(f["view_normals"]), dp(f["agree_mask"]), dp(f["owner"]),
+               dp(f["pt_ptr"]), m, dp(f["points"]), dp(f["normals"]), dp(f["n_views"]), dp(f["index"]), dp(ws), need.value)
+        return FusedCloud(f, pt_ptr, self)
 
     def cost_limits(self, max_cost):
         """int32 per view: floor(max_cost * sources * window), what `filter(max_cost=...)` hands to the device."""
@@ -287,6 +334,58 @@ class DepthMaps:
             m = index[:, 0] == v
             out[m] = col[v][index[m, 1], index[m, 2]]
         return pts, index, out
+
+
+class FusedCloud:
+    """What `DepthMaps.fuse` returns; the arrays stay on the device until they are asked for.  points float64 [m,3], normals
+    float32 [m,3] (zeros where no agreeing view has a normal), n_views uint8 [m] (the views a point is the mean of), index
+    int32 [m,3] as (view position, y, x) of the owning pixel, in (view, row-major) order; pt_ptr int64 [views + 1]: the points
+    of view v are pt_ptr[v] .. pt_ptr[v+1]; view_normals (float32 [h,w,3]), owner and agree_mask (uint8 [h,w]): one per view."""
+
+    def __init__(self, state, pt_ptr, maps):
+        self._f = state
+        self._maps = maps
+        self.pt_ptr = pt_ptr
+        self._host = {}
+
+    def __len__(self):
+        return int(self.pt_ptr[-1])
+
+    def _flat(self, name):
+        if name not in self._host:
+            self._host[name] = self._f[name].cpu().numpy()[:len(self)]
+        return self._host[name]
+
+    def _per_view(self, name, tail=()):
+        if name not in self._host:
+            flat, out, o = self._f[name].cpu().numpy(), [], 0
+            for h, w in self._maps.shapes:
+                out.append(flat[o:o + h * w].reshape((h, w) + tail))
+                o += h * w
+            self._host[name] = out
+        return self._host[name]
+
+    points = property(lambda self: self._flat("points"))
+    normals = property(lambda self: self._flat("normals"))
+    n_views = property(lambda self: self._flat("n_views"))
+    index = property(lambda self: self._flat("index"))
+    view_normals = property(lambda self: self._per_view("view_normals", (3,)))
+    owner = property(lambda self: self._per_view("owner"))
+    agree_mask = property(lambda self: self._per_view("agree_mask"))
+
+    def colors(self, images):
+        """The colour of every point from its owning pixel: images is one [h,w] or [h,w,3] array per IMAGE of the set."""
+        maps = self._maps
+        if len(images) != len(maps._s["imgs"]):
+            raise ValueError("colors: one array per image")
+        col = [np.asarray(images[r]) for r in maps.views]
+        index = self.index
+        tail = col[0].shape[2:] if col else ()
+        out = np.zeros((len(index),) + tail, dtype=col[0].dtype if col else np.uint8)
+        for v in range(len(col)):
+            m = index[:, 0] == v
+            out[m] = col[v][index[m, 1], index[m, 2]]
+        return out
 
 
 def depth_maps(images, K, poses, sources, planes, radius=2, device=0):
@@ -333,12 +432,65 @@ def depth_maps_raw(imgs, refs, src_ptr, src_image, warps, backproj, plane_ptr, d
     return DepthMaps(st)
 
 
+def depth_maps_from_arrays(shapes, refs, src_ptr, src_image, warps, backproj, depth, keep, xyz, rel_tol=0.01, device=0):
+    """A `DepthMaps` around maps that were made and filtered elsewhere, for `.fuse()`: shapes is the (height, width) of every
+    image of the set, refs / src_ptr / src_image / warps / backproj are as `check_arguments` returns them, and depth
+    (float32 [h,w]), keep (uint8 [h,w]) and xyz (float64 [h,w,3]) hold one array per view in the order of refs.  plane, cost
+    and n_consistent are zeros.  rel_tol is what `.fuse(rel_tol=None)` takes."""
+    import torch
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    refs = [int(r) for r in refs]
+    if len(set(refs)) != len(refs) or any(not 0 <= r < len(shapes) for r in refs):
+        raise ValueError("refs must name different images of the set")
+    if not (len(depth) == len(keep) == len(xyz) == len(refs)):
+        raise ValueError("depth, keep and xyz need one array per view")
+    for v, r in enumerate(refs):
+        if np.shape(depth[v]) != shapes[r] or np.shape(keep[v]) != shapes[r] or np.shape(xyz[v]) != shapes[r] + (3,):
+            raise ValueError(f"view {v}: the maps must have the shape of image {r}")
+    h = _lib.get_handle(device)
+    dev = torch.device("cuda", device)
+    n_img, n_ref = len(shapes), len(refs)
+    src_ptr, src_image = np.ascontiguousarray(src_ptr, dtype=np.int64), np.ascontiguousarray(src_image, dtype=np.int32)
+    off = np.zeros(n_img + 1, dtype=np.int64)
+    np.cumsum([hh * ww for hh, ww in shapes], out=off[1:])
+    need = C.c_int64()
+    h.check(h.lib.sfm_depth_workspace_bytes(n_img, n_ref, len(src_image), C.byref(need)), "sfm_depth_workspace_bytes")
+    n_out = int(sum(shapes[r][0] * shapes[r][1] for r in refs))
+
+    def up(arrays, dtype, tail=()):
+        """The views' arrays back to back on the device (one element where there is no pixel: a pointer must exist)."""
+        if not n_out:
+            return torch.from_numpy(np.zeros((1,) + tail, dtype)).to(dev)
+        flat = np.concatenate([np.asarray(a, dtype=dtype).reshape((-1,) + tail) for a in arrays])
+        return torch.from_numpy(np.ascontiguousarray(flat)).to(dev)
+
+    def table(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev) if len(a) else torch.zeros((1, 12), dtype=torch.float64, device=dev)
+
+    warps = np.asarray(warps, dtype=np.float64).reshape(-1, 12)
+    backproj = np.asarray(backproj, dtype=np.float64).reshape(-1, 12)
+    st = {"imgs": [np.zeros(sh, np.uint8) for sh in shapes], "refs": refs, "radius": 0, "off": off,
+          "heights": np.array([sh[0] for sh in shapes], dtype=np.int32), "widths": np.array([sh[1] for sh in shapes], dtype=np.int32),
+          "ref_image": np.array(refs, dtype=np.int32), "src_ptr": src_ptr, "src_image": src_image, "n_out": n_out,
+          "ws": torch.empty(need.value, dtype=torch.uint8, device=dev),
+          "warps": table(warps), "backproj": table(backproj),
+          "plane": torch.zeros(max(n_out, 1), dtype=torch.int32, device=dev),
+          "cost": torch.zeros(max(n_out, 1), dtype=torch.int16, device=dev),
+          "n_consistent": torch.zeros(max(n_out, 1), dtype=torch.uint8, device=dev),
+          "depth": up(depth, np.float32), "keep": up(keep, np.uint8), "xyz": up(xyz, np.float64, (3,))}
+    maps = DepthMaps(st)
+    maps.n_consistent, maps.keep, maps.xyz = maps._split("n_consistent"), maps._split("keep"), maps._split("xyz", (3,))
+    maps._rel_tol = float(rel_tol)
+    return maps
+
+
 def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=256, radius=2, rel_tol=0.01, max_cost=None,
-                              min_consistent=2, colors=None, device=0):
+                              min_consistent=2, colors=None, device=0, fuse=False):
     """The chain on a `Reconstruction`: sources by shared points (`select_sources`), the depth interval of every view from
     its sparse points (`depth_ranges`), planes at most one pixel apart (`plane_depths`), `depth_maps`, `.filter`,
     `.point_cloud`.  images: one per image position of rec.tracks.  Returns (points, index, DepthMaps) - or (points, index,
-    colours, DepthMaps) with colors."""
+    colours, DepthMaps) with colors.  With fuse=True the last step is `.fuse()` in place of `.point_cloud`, and the result
+    is (FusedCloud, DepthMaps); the colours are then `FusedCloud.colors(colors)`."""
     n_img = len(rec.tracks.kp_ptr) - 1
     if len(images) != n_img:
         raise ValueError(f"{len(images)} images for {n_img} image positions")
@@ -351,4 +503,6 @@ def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=2
         planes[r] = plane_depths(rng[r][0], rng[r][1], view_warps(rec.K, rec.poses, r, s), size, max_planes)
     maps = depth_maps(images, rec.K, rec.poses, src, planes, radius, device)
     maps.filter(rel_tol, max_cost, min_consistent)
+    if fuse:
+        return maps.fuse(), maps
     return maps.point_cloud(colors) + (maps,)

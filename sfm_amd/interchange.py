@@ -73,13 +73,20 @@ def save_ply(points3D, filepath):
         f.writelines(f"{p[0]} {p[1]} {p[2]}\n" for p in pts)
 
 
-def save_ply_points(points, colors, path):
-    """A dense cloud as binary little-endian PLY: points [n,3] as float32 x, y, z; colors None, [n] gray or [n,3] uint8 in
-    cv2's channel order (BGR), written as red, green, blue."""
+def save_ply_points(points, colors, path, normals=None):
+    """A dense cloud as binary little-endian PLY: points [n,3] as float32 x, y, z; normals None or [n,3], written as float32
+    nx, ny, nz after the coordinates; colors None, [n] gray or [n,3] uint8 in cv2's channel order (BGR), written as red,
+    green, blue."""
     pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
     head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(pts)}",
             "property float x", "property float y", "property float z"]
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        nrm = np.asarray(normals)
+        if nrm.shape != (len(pts), 3):
+            raise ValueError("normals must be [n,3], one per point")
+        head += ["property float nx", "property float ny", "property float nz"]
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
     if colors is not None:
         col = np.asarray(colors)
         if col.dtype != np.uint8 or col.shape not in ((len(pts),), (len(pts), 3)):
@@ -89,6 +96,8 @@ def save_ply_points(points, colors, path):
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
     body = np.zeros(len(pts), dtype=np.dtype(fields))
     body["x"], body["y"], body["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
+    if normals is not None:
+        body["nx"], body["ny"], body["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
     if colors is not None:
         body["red"], body["green"], body["blue"] = col[:, 0], col[:, 1], col[:, 2]
     with open(path, "wb") as f:

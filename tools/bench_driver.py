@@ -991,7 +991,9 @@ def measure_depth(reps=20, emit=None):
     tests/depth_reference.py: cameras on a line, baseline 0.1, f = 1228), every view a reference with its 4 nearest cameras
     as sources, planes from sfm_amd.depth.plane_depths over 2.5 .. 5, radius 2, inputs resident in HBM: device time of each
     call by HIP events around `reps` calls, per reference view, and the samples (pixels x planes x sources) per second of
-    the sweep.  In the same run sfm_features_detect + sfm_features_describe on the same images, as a known quantity."""
+    the sweep.  Behind them sfm_depth_fuse_mark and sfm_depth_fuse_gather (rel_tol 0.02, step 2, jump 0.05) on the filter's
+    outputs, beside the compaction they replace: torch.nonzero + gather as in DepthMaps.point_cloud().  In the same run
+    sfm_features_detect + sfm_features_describe on the same images, as a known quantity."""
     import torch
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from depth_reference import make_scene
@@ -1045,6 +1047,41 @@ def measure_depth(reps=20, emit=None):
            "ms_census_per_view": timed(run_census, reps) * 1e3 / n_img, "ms_sweep_per_view": timed(run_sweep, reps) * 1e3 / n_img,
            "ms_filter_per_view": timed(run_filter, reps) * 1e3 / n_img}
     row["samples_per_s_sweep"] = samples / (row["ms_sweep_per_view"] * n_img * 1e-3)
+    # the fusion behind the filter; beside it what it replaces: the compaction of point_cloud() (torch.nonzero + gather)
+    h.check(h.lib.sfm_depth_fuse_workspace_bytes(n_img, n_img, len(src_image), n_out, C.byref(need)), "sfm_depth_fuse_workspace_bytes")
+    fuse_ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    normal_map = torch.empty((n_out, 3), dtype=torch.float32, device=dev)
+    agree_mask = torch.empty(n_out, dtype=torch.uint8, device=dev)
+    owner = torch.empty(n_out, dtype=torch.uint8, device=dev)
+    pt_ptr = torch.empty(n_img + 1, dtype=torch.int64, device=dev)
+    views = (hp(off), hp(heights), hp(widths), n_img, n_img, hp(ref_image), hp(src_ptr), hp(src_image), _p(d_warps))
+
+    def run_mark():
+        h.call("sfm_depth_fuse_mark", *views, _p(d_back), _p(depth), _p(keep), _p(xyz), C.c_double(0.02), 2, C.c_double(0.05),
+               _p(normal_map), _p(agree_mask), _p(owner), _p(pt_ptr), _p(fuse_ws), need.value)
+    run_mark()
+    m = int(pt_ptr.cpu().numpy()[-1])
+    points = torch.empty((max(m, 1), 3), dtype=torch.float64, device=dev)
+    normals = torch.empty((max(m, 1), 3), dtype=torch.float32, device=dev)
+    n_views = torch.empty(max(m, 1), dtype=torch.uint8, device=dev)
+    index = torch.empty((max(m, 1), 3), dtype=torch.int32, device=dev)
+
+    def run_gather():
+        h.call("sfm_depth_fuse_gather", *views, _p(depth), _p(xyz), _p(normal_map), _p(agree_mask), _p(owner), _p(pt_ptr), m,
+               _p(points), _p(normals), _p(n_views), _p(index), _p(fuse_ws), need.value)
+
+    def run_point_cloud():
+        return xyz[torch.nonzero(keep, as_tuple=False).reshape(-1)]
+    run_gather()
+    z_fused = points[:m, 2].cpu().numpy()
+    idx = index[:m].cpu().numpy()
+    t_fused = truth[idx[:, 0], idx[:, 1], idx[:, 2]]
+    row.update({"fused_points": m, "fused_share_of_kept": m / max(int(kept.sum()), 1),
+                "share_of_fused_with_normal": float((normals[:m] != 0).any(dim=1).float().mean().item()) if m else 0.0,
+                "share_of_fused_within_2_percent_of_truth": float((np.abs(z_fused - t_fused) <= 0.02 * t_fused).mean()) if m else 0.0,
+                "ms_fuse_mark_per_view": timed(run_mark, reps) * 1e3 / n_img, "ms_fuse_gather_per_view": timed(run_gather, reps) * 1e3 / n_img,
+                "ms_point_cloud_nonzero_gather_per_view": timed(run_point_cloud, reps) * 1e3 / n_img})
+    del normal_map, agree_mask, owner, points, normals, n_views, index, fuse_ws
     # the known quantity beside it: the feature stage on the same images
     threshold, edge, max_features = 20, 31, 10000
     h.check(h.lib.sfm_features_workspace_bytes(n_img, hp(off), C.byref(need)), "sfm_features_workspace_bytes")

@@ -249,6 +249,11 @@ typedef struct {
   const int32_t* cch_end;    /* [n_cchunks] */
 } sfm_ba_structure;
 int sfm_ba_get_structure(sfm_ba_problem p, sfm_ba_structure* out_host);
+/* How the Schur kernel walks a work item (device pointers, int32 [n_items]; inspection and tests): item i of block b takes
+ * pairs first[i] + j * stride[i], j < count[i] <= 256.  The n items of a block partition its range of pair_k / pair_k2: blocks
+ * of n <= 2 items by the contiguous stretches item_beg / item_end (stride 1), blocks of n >= 3 items interleaved - item i takes
+ * pairs blk_ptr[b] + i + j n (stride n), so that every item of a block row walks its camera's observation list at one pace. */
+int sfm_ba_get_item_descriptors(sfm_ba_problem p, const int32_t** first, const int32_t** stride, const int32_t** count);
 
 /* Byte offsets into the workspace of the regions the host reads or all-reduces. */
 typedef struct {

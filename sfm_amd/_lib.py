@@ -105,6 +105,7 @@ SIGNATURES = {
     "sfm_ba_create_problem": (C.c_int, [vp, C.POINTER(BADesc), C.POINTER(vp)]),
     "sfm_ba_destroy_problem": (None, [vp]),
     "sfm_ba_get_structure": (C.c_int, [vp, C.POINTER(BAStructureView)]),
+    "sfm_ba_get_item_descriptors": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
     "sfm_ba_get_layout": (C.c_int, [vp, C.POINTER(BALayout)]),
     "sfm_ba_set_sharded": (C.c_int, [vp, vp, C.c_int]),
     "sfm_ba_solver_stats": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),

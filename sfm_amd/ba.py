@@ -157,6 +157,19 @@ class GpuBA:
             out[name] = a
         return out
 
+    def item_descriptors(self):
+        """How k_schur_items walks each work item: dict of int32 arrays item_first / item_stride / item_cnt
+        (sfm_ba_get_item_descriptors; sfm_amd.structure.item_descriptors is the host-side mirror)."""
+        ptrs = [_lib.vp() for _ in range(3)]
+        self.h.check(self.h.lib.sfm_ba_get_item_descriptors(self._pp, *[C.byref(q) for q in ptrs]), "sfm_ba_get_item_descriptors")
+        out = {}
+        for name, q in zip(("item_first", "item_stride", "item_cnt"), ptrs):
+            a = np.empty(self.n_items, dtype=np.int32)
+            if self.n_items:
+                self.h.call("sfm_copy_to_host", C.c_void_p(a.ctypes.data), q, self.n_items * 4)
+            out[name] = a
+        return out
+
     # ---- workspace views
     def view(self, off, count, dtype=None):
         dtype = dtype or self.torch.float64

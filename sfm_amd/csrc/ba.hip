@@ -246,7 +246,8 @@ __global__ __launch_bounds__(256) void k_build_G(int64_t N, const int* __restric
 }
 
 // Reduced camera system  S[c][c2] = [c == c2] B_c - sum_{(k,k2) on a shared track} G_k G_k2^T  (c <= c2, mirrored).
-// The pair list of a block is cut into work items of <= 256 pairs (sfm_amd/structure.py); ONE wavefront per
+// The pair list of a block is cut into work items of <= 256 pairs (sfm_amd/structure.py; the items of a block of >= 3 items
+// interleaved pair by pair, so that all items of a block row walk the row camera's observation list in step: k_item_desc); ONE wavefront per
 // item accumulates its 16x16 tile on v_mfma_f64_16x16x4_f64 as a K = 4 (3 used) x n_pairs contraction:
 // lane l feeds A[row l&15][k l>>4] = G_k[m = l>>4][row], B likewise from G_k2; C/D: col = l&15,
 // row = (l>>4) + 4*reg.  Pair ids are loaded 64 at a time (coalesced) and broadcast with v_readlane so the
@@ -298,14 +299,14 @@ extern "C" int sfm_debug_schur_stamps(unsigned long long* dst, int n_words) {
   return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_schur_stamps), (size_t)n_words * 8, 0, hipMemcpyDeviceToHost);
 }
 #define SCHUR_STAMP_BEGIN() const unsigned long long stamp_t0 = __builtin_amdgcn_s_memrealtime()
-#define SCHUR_STAMP_END(npairs) do { const unsigned wv = blockIdx.x * SFM_SCHUR_WG_WAVES + (threadIdx.x >> 6); if ((threadIdx.x & 63) == 0 && wv < SCHUR_STAMP_WAVES) { \
+#define SCHUR_STAMP_END(npairs, isdiag) do { const unsigned wv = blockIdx.x * SFM_SCHUR_WG_WAVES + (threadIdx.x >> 6); if ((threadIdx.x & 63) == 0 && wv < SCHUR_STAMP_WAVES) { \
     unsigned long long* o = g_schur_stamps + (size_t)wv * 4; \
     o[0] = stamp_t0; o[1] = __builtin_amdgcn_s_memrealtime(); \
     o[2] = ((unsigned long long)(unsigned)(npairs) << 32) | (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4); \
-    o[3] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 20); } } while (0)
+    o[3] = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 20) | ((unsigned long long)((isdiag) ? 1 : 0) << 32); } } while (0)
 #else
 #define SCHUR_STAMP_BEGIN() do {} while (0)
-#define SCHUR_STAMP_END(npairs) do {} while (0)
+#define SCHUR_STAMP_END(npairs, isdiag) do {} while (0)
 #endif
 // waves per workgroup of k_schur_items (its waves never meet: no barrier, wave-private LDS).  ONE: a wave slot is handed back
 // when its wave ends, not when the slowest of four does.  Wave begin / end stamps (tools/exp_schur_lifetimes.sh, cfg4): with
@@ -316,8 +317,9 @@ extern "C" int sfm_debug_schur_stamps(unsigned long long* dst, int n_words) {
 #endif
 template <int D, typename T, int GS>
 __global__ __launch_bounds__(64 * SFM_SCHUR_WG_WAVES) __attribute__((amdgpu_waves_per_eu(D == 6 ? SFM_SCHUR_WAVES_D6 : SFM_SCHUR_WAVES_D10, D == 6 ? SFM_SCHUR_WAVES_D6 : SFM_SCHUR_WAVES_D10))) void k_schur_items(const int* __restrict__ xcd_ptr, const int* __restrict__ xcd_items,
-                                                     const int* __restrict__ item_beg,
-                                                     const int* __restrict__ item_end,
+                                                     const int* __restrict__ it_first,
+                                                     const int* __restrict__ it_stride,
+                                                     const int* __restrict__ it_cnt,
                                                      const int* __restrict__ pair_k, const int* __restrict__ pair_k2,
                                                      const T* __restrict__ G, double* __restrict__ part,
                                                      const int* __restrict__ cam_idx,
@@ -359,7 +361,10 @@ __global__ __launch_bounds__(64 * SFM_SCHUR_WG_WAVES) __attribute__((amdgpu_wave
   // (the item and its bounds are the same for the whole wave: in SGPRs, so that every loop bound below is scalar - as per-lane
   // loads they put the trip count of the MFMA loop into a VGPR and an exec-mask dance around every MFMA)
   const int it = __builtin_amdgcn_readfirstlane(xcd_items[pos]);
-  const int beg = __builtin_amdgcn_readfirstlane(item_beg[it]), end = __builtin_amdgcn_readfirstlane(item_end[it]);
+  // the item walks pairs first + j * stride, j < n (problem.hip, k_item_desc: stride 1, or the item count of an interleaved block -
+  // then the lanes' id loads are strided, over lines the block's other items ask for at the same time)
+  const int first = __builtin_amdgcn_readfirstlane(it_first[it]), stride = __builtin_amdgcn_readfirstlane(it_stride[it]);
+  const int n = __builtin_amdgcn_readfirstlane(it_cnt[it]);
   const int row = lane & 15, m = lane >> 4;
   const int lb = lane / CH, lc = lane - lb * CH;          // this lane's block / chunk within a load
   const bool loader = lb < BPL;
@@ -367,7 +372,7 @@ __global__ __launch_bounds__(64 * SFM_SCHUR_WG_WAVES) __attribute__((amdgpu_wave
   char* sB = s_stage[w][1];
   const char* Gb = (const char*)G;
   v4d acc = {0.0, 0.0, 0.0, 0.0};
-  const int k_first = __builtin_amdgcn_readfirstlane(pair_k[beg]), k2_first = __builtin_amdgcn_readfirstlane(pair_k2[beg]);
+  const int k_first = __builtin_amdgcn_readfirstlane(pair_k[first]), k2_first = __builtin_amdgcn_readfirstlane(pair_k2[first]);
   // wave-uniform.  A diagonal block holds nothing but self-pairs UNLESS a camera appears twice on a track (fuse_rhs == 0,
   // sfm_ba_prob::has_dup): then it is processed like any other block and the right-hand side comes from k_cam_reduce_chunks
   const bool diag = fuse_rhs && k_first == k2_first;
@@ -388,16 +393,16 @@ __global__ __launch_bounds__(64 * SFM_SCHUR_WG_WAVES) __attribute__((amdgpu_wave
   auto run = [&](auto diag_c) __attribute__((always_inline)) {
     constexpr bool DIAG = decltype(diag_c)::value;
     // (the pair ids of the NEXT 64 pairs are asked for while the present 64 are worked on)
-    int kk_n = (beg + lane) < end ? pair_k[beg + lane] : 0;
-    int kk2_n = DIAG ? kk_n : ((beg + lane) < end ? pair_k2[beg + lane] : 0);
-    for (int base = beg; base < end; base += 64) {
+    int kk_n = lane < n ? pair_k[first + lane * stride] : 0;
+    int kk2_n = DIAG ? kk_n : (lane < n ? pair_k2[first + lane * stride] : 0);
+    for (int base = 0; base < n; base += 64) {
       const int kk = kk_n, kk2 = kk2_n;
-      if (base + 64 < end) {                               // wave-uniform
-        const int idn = base + 64 + lane;
-        kk_n = idn < end ? pair_k[idn] : 0;
-        kk2_n = DIAG ? kk_n : (idn < end ? pair_k2[idn] : 0);
+      if (base + 64 < n) {                                 // wave-uniform
+        const int jn = base + 64 + lane;
+        kk_n = jn < n ? pair_k[first + jn * stride] : 0;
+        kk2_n = DIAG ? kk_n : (jn < n ? pair_k2[first + jn * stride] : 0);
       }
-      const int cnt = (end - base) < 64 ? (end - base) : 64;
+      const int cnt = (n - base) < 64 ? (n - base) : 64;
       if (DIAG) {
         // e_j of this lane's pair (the per-observation copy k_build_G leaves) -> LDS, in flight together with the G loads
         // of the batch below
@@ -495,7 +500,7 @@ __global__ __launch_bounds__(64 * SFM_SCHUR_WG_WAVES) __attribute__((amdgpu_wave
       if (rr < D) cch_part[(size_t)ch * 16 + rr] = acc[i];
     }
   }
-  SCHUR_STAMP_END(end - beg);
+  SCHUR_STAMP_END(n, diag);
 }
 
 // grid (C, ceil(C / ASM_NB)), 128 threads: workgroup (r, y) sums the item tiles of the blocks (r, c), c = ASM_NB y .. <= r, of the
@@ -1072,7 +1077,7 @@ extern "C" int sfm_ba_schur_build(sfm_handle h, sfm_ba_problem p, double alpha) 
       sfm_prof_begin(h, SFM_PROF_SCHUR_ITEMS);
       hipLaunchKernelGGL((k_schur_items<DD, double, GG>), dim3(8 * cdiv(p->xcd_max_items, SFM_SCHUR_WG_WAVES)),
                          dim3(64 * SFM_SCHUR_WG_WAVES), 0, h->stream,
-                         p->xcd_ptr, p->xcd_items, p->item_beg, p->item_end, p->pair_k, p->pair_k2, WS(L, G), WS(L, sch_part),
+                         p->xcd_ptr, p->xcd_items, p->it_first, p->it_stride, p->it_cnt, p->pair_k, p->pair_k2, WS(L, G), WS(L, sch_part),
                          p->cam_idx, p->item_ptr, p->cch_ptr, C, WS(L, eobs), WS(L, cch_part), p->has_dup ? 0 : 1);
       sfm_prof_end(h, SFM_PROF_SCHUR_ITEMS);
     }

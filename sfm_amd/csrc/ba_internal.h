@@ -26,6 +26,7 @@ struct sfm_ba_prob {
 
   int64_t n_pairs;
   int32_t *item_ptr, *item_beg, *item_end;
+  int32_t *it_first, *it_stride, *it_cnt;   // [n_items] the pairs item i walks: it_first[i] + j * it_stride[i], j < it_cnt[i] (problem.hip)
   int64_t n_items;
   int32_t *xcd_ptr, *xcd_items;
   int64_t xcd_max_items;

@@ -7,6 +7,8 @@
 //                     share a track: every (k, k2) with cam(k) <= cam(k2), ordered by (block, k, k2)
 //                                                                          - enumerate per observation, stable sort by block id
 //   item_*            the pair list of a block cut into work items of <= 256 pairs (one wavefront each)
+//   it_first, it_stride, it_cnt   the pairs an item WALKS (internal: k_schur_items reads these, not item_beg / item_end):
+//                     first + j * stride, j < cnt.  The items of a block of n >= 3 items are interleaved (stride n)
 //   xcd_*             work items grouped by block row mod 8 (one XCD serves one group: L2 reuse of G)
 //   cch_*             the camera lists cut into chunks of <= 256 observations (one workgroup each)
 // sfm_amd/structure.py is the host-side mirror (NumPy); tests/test_ba_gpu.py checks the arrays bit for bit.
@@ -121,6 +123,24 @@ __global__ __launch_bounds__(256) void k_piece_fill(int64_t n, const int* __rest
   for (int s = lo; s < hi; s += size, ++o) { beg[o] = s; end[o] = (s + size) < hi ? (s + size) : hi; }
 }
 
+// What item i of block b walks.  item_beg / item_end cut the block's pair list [lo, hi) into contiguous stretches; a block of
+// n >= 3 items is walked INTERLEAVED instead: item i takes pairs lo + i, lo + i + n, lo + i + 2 n, ...  The pair list of a block
+// is ordered by k, the observation of the row's camera c, so every item of an interleaved block walks camera c's observation
+// list from end to end at the pace of the row's single-item blocks (which span it in one item): a G block one item loads is found
+// in the XCD's L2 by the row's other items.  A contiguous stretch i only ever visits stretch i of the list - where none of the
+// row's other items are.  Blocks of 2 items stay contiguous: two interleaved halves would walk the list at TWICE the row's pace
+// (tools/l2sim, tools/experiments/README.md).  n = ceil(m / size) items of ceil or floor (m / n) <= size pairs each.
+__global__ __launch_bounds__(256) void k_item_desc(int64_t n_blk, const int* __restrict__ blk_ptr, const int* __restrict__ item_ptr,
+                                                   int size, int* __restrict__ first, int* __restrict__ stride, int* __restrict__ cnt) {
+  const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (b >= n_blk) return;
+  const int lo = blk_ptr[b], hi = blk_ptr[b + 1], o = item_ptr[b], n = item_ptr[b + 1] - o;
+  for (int i = 0; i < n; ++i) {
+    if (n >= 3) { first[o + i] = lo + i; stride[o + i] = n; cnt[o + i] = (hi - lo - i + n - 1) / n; }
+    else { const int s = lo + i * size; first[o + i] = s; stride[o + i] = 1; cnt[o + i] = (hi - s) < size ? (hi - s) : size; }
+  }
+}
+
 // items of block row r = item_ptr[rowstart(r + 1)] - item_ptr[rowstart(r)]
 // how far from the diagonal the blocks with work lie: stat[0] += number of non-empty blocks (c, c2 > c), stat[1] += sum of c2 - c
 // over them (integer sums: the order of the atomics does not matter).  One thread per block row.
@@ -184,7 +204,7 @@ __global__ void k_pair_uv(int64_t N, const int* __restrict__ cam_obs, const doub
 extern "C" void sfm_ba_destroy_problem(sfm_ba_problem p) {
   if (!p) return;
   void* owned[] = {p->cam_idx, p->pt_idx, p->uv, p->pt_ptr, p->cam_ptr, p->cam_obs, p->cam_pt, p->blk_ptr, p->pair_k, p->pair_k2,
-                   p->item_ptr, p->item_beg, p->item_end, p->xcd_ptr, p->xcd_items, p->cch_ptr, p->cch_beg, p->cch_end};
+                   p->item_ptr, p->item_beg, p->item_end, p->it_first, p->it_stride, p->it_cnt, p->xcd_ptr, p->xcd_items, p->cch_ptr, p->cch_beg, p->cch_end};
   for (void* q : owned)
     if (q) (void)hipFree(q);
   if (p->owns_workspace && p->workspace) (void)hipFree(p->workspace);
@@ -352,10 +372,15 @@ extern "C" int sfm_ba_create_problem(sfm_handle h, const sfm_ba_desc* d, sfm_ba_
   p->n_items = n_items;
   PB_HIP(hipMalloc((void**)&p->item_beg, ((int64_t)n_items + 1) * 4));
   PB_HIP(hipMalloc((void**)&p->item_end, ((int64_t)n_items + 1) * 4));
+  PB_HIP(hipMalloc((void**)&p->it_first, ((int64_t)n_items + 1) * 4));
+  PB_HIP(hipMalloc((void**)&p->it_stride, ((int64_t)n_items + 1) * 4));
+  PB_HIP(hipMalloc((void**)&p->it_cnt, ((int64_t)n_items + 1) * 4));
   PB_HIP(hipMalloc((void**)&p->xcd_items, ((int64_t)n_items + 1) * 4));
   PB_HIP(hipMalloc((void**)&p->xcd_ptr, 9 * 4));
   hipLaunchKernelGGL(k_piece_fill, dim3(cdiv(n_blk, 256)), dim3(256), 0, st, n_blk, p->blk_ptr, p->item_ptr, ITEM_PAIRS,
                      p->item_beg, p->item_end);
+  hipLaunchKernelGGL(k_item_desc, dim3(cdiv(n_blk, 256)), dim3(256), 0, st, n_blk, p->blk_ptr, p->item_ptr, ITEM_PAIRS,
+                     p->it_first, p->it_stride, p->it_cnt);
   // items grouped by block row: 8 groups, one per XCD (workgroup b of the Schur kernel serves group b % 8); rows (and the
   // items inside a row) stay in ascending order inside a group: C numbers, on the host.  Default: rows dealt back and forth over the groups.
   // SFM_XCD_GROUP=contig: contiguous row ranges balanced by item count - neighbouring block rows share their partner
@@ -458,6 +483,12 @@ extern "C" int sfm_ba_get_structure(sfm_ba_problem p, sfm_ba_structure* o) {
   o->item_ptr = p->item_ptr; o->item_beg = p->item_beg; o->item_end = p->item_end;
   o->xcd_ptr = p->xcd_ptr; o->xcd_items = p->xcd_items;
   o->cch_ptr = p->cch_ptr; o->cch_beg = p->cch_beg; o->cch_end = p->cch_end;
+  return SFM_OK;
+}
+
+extern "C" int sfm_ba_get_item_descriptors(sfm_ba_problem p, const int32_t** first, const int32_t** stride, const int32_t** count) {
+  if (!p || !first || !stride || !count) return SFM_ERR_ARG;
+  *first = p->it_first; *stride = p->it_stride; *count = p->it_cnt;
   return SFM_OK;
 }
 

@@ -32,6 +32,10 @@ class BAStructure:
     cch_ptr: np.ndarray     # [C+1] int32: chunks (<= CHUNK_OBS entries of cam_obs of ONE camera) per camera
     cch_beg: np.ndarray     # [n_cchunks] int32 ranges into cam_obs
     cch_end: np.ndarray     # [n_cchunks] int32
+    # how the Schur kernel walks item i: pairs item_first[i] + j * item_stride[i], j < item_cnt[i] (sfm_ba_get_item_descriptors)
+    item_first: np.ndarray = None    # [n_items] int32
+    item_stride: np.ndarray = None   # [n_items] int32: 1, or the item count n >= 3 of an interleaved block
+    item_cnt: np.ndarray = None      # [n_items] int32, <= ITEM_PAIRS
 
     @property
     def n_obs(self):
@@ -68,6 +72,24 @@ def _split_ranges(ptr, size):
     beg = ptr[owner] + within * size
     end = np.minimum(beg + size, ptr[owner + 1])
     return piece_ptr, beg, end
+
+
+def item_descriptors(blk_ptr, item_ptr, size=ITEM_PAIRS):
+    """(first, stride, count) per work item - the rule of k_item_desc (sfm_amd/csrc/problem.hip): item i of a block [lo, hi) of
+    n items walks pairs first + j * stride, j < count.  n <= 2: the contiguous stretches of _split_ranges (stride 1); n >= 3:
+    interleaved, first = lo + i, stride = n - every item of the block then walks the whole of the row camera's observation list
+    (the block's pairs are ordered by it) at the pace of the row's single-item blocks."""
+    blk_ptr = np.asarray(blk_ptr, dtype=np.int64)
+    item_ptr = np.asarray(item_ptr, dtype=np.int64)
+    n = np.diff(item_ptr)
+    owner = np.repeat(np.arange(len(n), dtype=np.int64), n)
+    i = np.arange(int(item_ptr[-1]), dtype=np.int64) - item_ptr[owner]
+    lo, hi, n = blk_ptr[owner], blk_ptr[owner + 1], n[owner]
+    inter = n >= 3
+    first = np.where(inter, lo + i, lo + i * size)
+    stride = np.where(inter, n, 1)
+    cnt = np.where(inter, (hi - lo - i + n - 1) // np.maximum(n, 1), np.minimum(size, hi - first))
+    return first, stride, cnt
 
 
 def block_index(c, c2, n_cams):
@@ -112,6 +134,7 @@ def build_structure(cam_idx, pt_idx, n_cams, n_pts):
     i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
     item_ptr, item_beg, item_end = _split_ranges(blk_ptr, ITEM_PAIRS)
     cch_ptr, cch_beg, cch_end = _split_ranges(cam_ptr, CHUNK_OBS)
+    item_first, item_stride, item_cnt = item_descriptors(blk_ptr, item_ptr)
     # block row of every item -> 8 groups (stable: rows, then blocks, stay in order inside a group): rows dealt back and forth, or with
     # SFM_XCD_GROUP=contig contiguous row ranges balanced by item count (the same rule as sfm_amd/csrc/problem.hip)
     n_blk_row = np.arange(n_cams, 0, -1, dtype=np.int64)                 # row c holds blocks (c, c..C-1)
@@ -141,7 +164,7 @@ def build_structure(cam_idx, pt_idx, n_cams, n_pts):
     return BAStructure(int(n_cams), int(n_pts), i32(cam_idx), i32(pt_idx), i32(pt_ptr), i32(cam_ptr),
                        i32(cam_obs), i32(blk_ptr), i32(k[order]), i32(k2[order]),
                        i32(item_ptr), i32(item_beg), i32(item_end), i32(xcd_ptr), i32(xcd_items),
-                       i32(cch_ptr), i32(cch_beg), i32(cch_end))
+                       i32(cch_ptr), i32(cch_beg), i32(cch_end), i32(item_first), i32(item_stride), i32(item_cnt))
 
 
 def partition_points(pt_ptr, world_size):

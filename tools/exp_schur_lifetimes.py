@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Wave lifetimes of k_schur_items at cfg4 (needs a library built with -DSFM_SCHUR_STAMPS=1: tools/exp_schur_lifetimes.sh).
-Prints how full the chip is over the span of ONE launch (resident waves over time) and how wave time depends on item size."""
+Prints how full the chip is over the span of ONE launch (resident waves over time), how wave time depends on item size, and the
+pace (us per pair) of the self-pair items of the diagonal blocks against the off-diagonal ones."""
 import ctypes, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -40,6 +41,18 @@ for lo, hi in ((1, 64), (65, 128), (129, 192), (193, 240), (241, 256)):
     m = (npairs >= lo) & (npairs <= hi)
     if m.any():
         print("items of %3d-%3d pairs: %6d waves, lifetime mean %.1f us, %.3f us per pair" % (lo, hi, m.sum(), life[m].mean(), (life[m] / npairs[m]).mean()))
+# pace of the self-pair items of the diagonal blocks (one gather per pair) against the others: the interleaved items of a block
+# row keep their camera's G blocks in the L2 for each other only while they walk its observation list in step
+isdiag = ((st[:, 3] >> np.uint64(32)) & np.uint64(1)).astype(bool)
+big = npairs >= 128
+for name, m in (("diagonal (self-pair)", isdiag & big), ("off-diagonal", ~isdiag & big)):
+    if m.any():
+        per = life[m] / npairs[m]
+        print("%-21s items of >= 128 pairs: %6d waves, mean %4d pairs, lifetime mean %.1f us, per pair mean %.4f us, median %.4f us" %
+              (name, m.sum(), npairs[m].mean(), life[m].mean(), per.mean(), np.median(per)))
+if (isdiag & big).any() and (~isdiag & big).any():
+    print("diagonal items walk %.3f x as fast as off-diagonal ones (ratio of the median us per pair)" %
+          (np.median((life / npairs)[~isdiag & big]) / np.median((life / npairs)[isdiag & big])))
 hw = st[:, 2].astype(np.int64) & 0xFFFFFFFF
 xcc = st[:, 3].astype(np.int64) & 0xF
 for x in range(8):

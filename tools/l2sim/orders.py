@@ -32,7 +32,7 @@ def run(name, grp_of_row, key):
     out = "/tmp/l2sim_o.bin"
     with open(out, "wb") as f:
         np.array([st.n_pairs, n_items, 2, 0], dtype=np.int64).tofile(f)
-        for a in (st.pair_k, st.pair_k2, st.item_beg, st.item_end, xp, order):
+        for a in (st.pair_k, st.pair_k2, st.item_first, st.item_stride, st.item_cnt, xp, order):
             np.ascontiguousarray(a, dtype=np.int32).tofile(f)
     print("%-46s" % name, end=" ", flush=True)
     subprocess.run([exe, out, "640", "4"], check=True)

@@ -947,6 +947,73 @@ int sfm_depth_fuse_gather(sfm_handle h, const int64_t* img_off /* host */, const
                           float* normals /* [n_points][3] */, uint8_t* n_views, int32_t* index /* [n_points][3] */,
                           void* workspace, int64_t workspace_bytes);
 
+/* ---- a surface from the depth maps: TSDF volume and marching tetrahedra (sfm_amd/csrc/tsdf.hip, mesh.hip, tsdf_rule.h,
+ *      mesh_rule.h, mesh_plan.h) ----
+ * Two stages, each a pure function of its inputs: float64 without FMA contraction, everything else integer, no visit
+ * order, no atomics on memory, so the output bytes are the same from run to run.
+ * Grid: nx x ny x nz NODES, each dimension 2 .. 1024; node (i, j, k) has the index n = (k ny + j) nx + i and the position
+ *   X_a = origin_a + voxel * (double)index_a, origin (3 float64, HOST) finite, voxel finite and > 0.  tsdf is float32
+ *   [n_nodes], weight uint16 [n_nodes], both on the device.
+ *
+ * sfm_tsdf_integrate.  The depth maps in the layout of sfm_depth_filter: heights / widths per image and ref_image per view
+ *   (HOST), view r at out_off[r] = sum over r' < r of h w in depth (float32) and keep (uint8, or NULL: every finite depth
+ *   counts).  proj (device, float64 [n_ref][12]) is the row-major [P | p] of a view, P = K R, p = K t; with the last row of
+ *   K = (0, 0, 1) q2 below is the depth along the optical axis.  For the node X and the views in position order:
+ *   q_i = ((P_i0 * X0 + P_i1 * X1) + P_i2 * X2) + p_i,  u = q0 / q2,  v = q1 / q2;  validity and the nearest pixel (xi, yi)
+ *   are those of the sample rule above (q2 > 0, the half-open bounds, floor(u + 0.5) with the cut);  ds = the float32 depth
+ *   at (yi, xi) widened.  The view is skipped unless the projection is valid, ds is finite and keep != 0;  sdf = ds - q2,
+ *   and the view is skipped if sdf < -trunc;  otherwise acc = acc + (sdf < trunc ? sdf : trunc) / trunc and w = w + 1.
+ *   After all views weight = w and tsdf = (float)(acc / (double)w); for w = 0 tsdf has the bit pattern 0x7FC00000.
+ *   Every view weighs the same.  A pixel without a depth carries no evidence, so free space outside every silhouette stays
+ *   unknown (w = 0).  The workspace (sfm_tsdf_workspace_bytes) holds the view table.  SFM_ERR_ARG before any device work
+ *   for a null handle, a negative image size, a reference index out of range, a reference listed twice, n_ref > n_img or
+ *   > 65,535, a dimension out of range, a non-finite origin or voxel, voxel <= 0, trunc not > 0, a null pointer, or a
+ *   workspace that is missing or too small.  No kernel reads outside a map.
+ *
+ * sfm_mesh_mark / sfm_mesh_emit.  Marching tetrahedra over the Kuhn split of every cell.
+ *   Known, inside, active: a node is known iff weight >= min_weight and tsdf is finite, and inside iff tsdf < 0.  Cell
+ *   (i, j, k), each index below its dimension - 1, is active iff its 8 corners are known; its index is that of its node.
+ *   Split: every cell has 6 tetrahedra, numbered by the permutations of the axes in lexicographic order xyz, xzy, yxz, yzx,
+ *   zxy, zyx; the tetrahedron of (a, b, c) has the local nodes v0 = (0,0,0), v1 = v0 + e_a, v2 = v1 + e_b, v3 = (1,1,1).
+ *   Every edge of every tetrahedron runs from a node in one of the directions 0 .. 6 = (1,0,0), (0,1,0), (0,0,1), (1,1,0),
+ *   (1,0,1), (0,1,1), (1,1,1) and is owned by that node.  The split is the same in every cell: faces match.
+ *   Vertices: direction d of node N carries a vertex iff B = N + d is in the grid, N and B differ in "inside", and at least
+ *   one active cell contains the edge (the cells N - (a, b, c), each component 0 where that of d is 1 and 0 or 1 otherwise).
+ *   Vertices come in (node index, direction) order.  With fa, fb the values at N and B widened, t = fa / (fa - fb) and
+ *   V_a = XA_a + t * (XB_a - XA_a), float64.  Normal: per node and axis the gradient is 0.5 * (f(+) - f(-)) when both
+ *   neighbours are in the grid and known, else f(+) - f or f - f(-) with the usable one, else 0;  g_a = gA_a + t * (gB_a -
+ *   gA_a), l2 = (g0*g0 + g1*g1) + g2*g2; when l2 is finite and > 0 each g_a is divided by sqrt(l2), otherwise the normal
+ *   is (0, 0, 0); rounded to float32.  It points to the outside.
+ *   Triangles: in (cell index, tetrahedron number) order, active cells only.  Name an edge by its two local nodes.  One
+ *   node p on one side and a < b < c on the other (either way round): (pa, pb, pc).  Inside p < q and outside r < s:
+ *   (pr, ps, qs), then (pr, qs, qr).  Orientation: with m(e) the sum of the two local node offsets of edge e,
+ *   n = (m1 - m0) x (m2 - m0) and D = |I| * sum(outside offsets) - |O| * sum(inside offsets), all integers and n . D never
+ *   0, the second and third vertex are exchanged iff n . D < 0: the normal of a triangle points from inside to outside.
+ *   Zero-area triangles (a node that holds exactly 0) are kept.  mesh_rule.h has the 6 x 16 cases as a table.
+ *   Limits: no colour or texture, no hole filling; about 2.3 x the triangles of marching cubes.
+ * Two calls.  sfm_mesh_mark writes counts (device int64 [2]: vertices, triangles) and leaves in the workspace
+ *    (sfm_mesh_workspace_bytes) per node its flags and one record - the 7-bit vertex mask, the node's first vertex slot and
+ *    the cell's first triangle slot relative to its block of 256 nodes, the cell's activity - and the first slots of every
+ *    block through a two-level scan.  The caller reads counts (after a synchronisation of the stream), allocates and hands
+ *    the same workspace, untouched, with the same grid to sfm_mesh_emit, which writes vertices float64 [nv][3], normals
+ *    float32 [nv][3] and triangles int32 [nt][3]; a triangle finds a vertex as the slot of the owning node plus the
+ *    popcount of the mask below the direction.  n_vertices / n_triangles are the capacities of the outputs: emit writes
+ *    nothing at or above them and returns at once when both are 0.  SFM_ERR_ARG before any device work for a null handle,
+ *    a dimension out of range, a negative min_weight, a non-finite origin or voxel, voxel <= 0, a capacity below 0 or above
+ *    2^31 - 1, a null pointer, or a workspace that is missing or too small. */
+int sfm_tsdf_workspace_bytes(int32_t n_ref, int64_t* bytes_host);
+int sfm_tsdf_integrate(sfm_handle h, const int32_t* heights /* host */, const int32_t* widths /* host */, int32_t n_img,
+                       int32_t n_ref, const int32_t* ref_image /* host */, const double* proj /* device [n_ref][12] */,
+                       const float* depth, const uint8_t* keep /* or NULL */, const double* origin /* host [3] */,
+                       double voxel, int32_t nx, int32_t ny, int32_t nz, double trunc, float* tsdf, uint16_t* weight,
+                       void* workspace, int64_t workspace_bytes);
+int sfm_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, int64_t* bytes_host);
+int sfm_mesh_mark(sfm_handle h, const float* tsdf, const uint16_t* weight, int32_t nx, int32_t ny, int32_t nz,
+                  int32_t min_weight, int64_t* counts /* device [2] */, void* workspace, int64_t workspace_bytes);
+int sfm_mesh_emit(sfm_handle h, const float* tsdf, int32_t nx, int32_t ny, int32_t nz, const double* origin /* host [3] */,
+                  double voxel, int64_t n_vertices, int64_t n_triangles, double* vertices, float* normals,
+                  int32_t* triangles, void* workspace, int64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

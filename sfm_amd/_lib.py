@@ -174,6 +174,11 @@ SIGNATURES = {
     "sfm_depth_fuse_workspace_bytes": (C.c_int, [i32, i32, i64, i64, C.POINTER(i64)]),
     "sfm_depth_fuse_mark": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f64, i32, f64, vp, vp, vp, vp, vp, i64]),
     "sfm_depth_fuse_gather": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64]),
+    "sfm_tsdf_workspace_bytes": (C.c_int, [i32, C.POINTER(i64)]),
+    "sfm_tsdf_integrate": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, f64, i32, i32, i32, f64, vp, vp, vp, i64]),
+    "sfm_mesh_workspace_bytes": (C.c_int, [i32, i32, i32, C.POINTER(i64)]),
+    "sfm_mesh_mark": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, vp, i64]),
+    "sfm_mesh_emit": (C.c_int, [vp, vp, i32, i32, i32, vp, f64, i64, i64, vp, vp, vp, vp, i64]),
 }
 
 _lib = None

@@ -301,6 +301,17 @@ class DepthMaps:
                dp(f["pt_ptr"]), m, dp(f["points"]), dp(f["normals"]), dp(f["n_views"]), dp(f["index"]), dp(ws), need.value)
         return FusedCloud(f, pt_ptr, self)
 
+    def tsdf(self, origin=None, voxel=None, shape=None, resolution=256, margin=0.05, trunc=None, min_weight=1):
+        """The kept pixels of all views integrated into a truncated signed distance volume on the device
+        (`sfm_tsdf_integrate`; include/sfm_amd.h states the rule).  origin (3 numbers), voxel and shape = (nx, ny, nz) nodes,
+        each 2 .. 1024, come together; without them the box is, per axis, the 1st to 99th percentile of the kept pixels' xyz
+        widened by margin of its length on both sides, with cubic voxels so that the longest side has `resolution` nodes.
+        trunc: the truncation distance, None for 3 voxels; min_weight: what `.mesh()` of the volume takes by default.  Every
+        view weighs the same, and space that no kept pixel looks through stays unknown.  Needs `.filter()` first.  Returns a
+        `TsdfVolume`."""
+        from .mesh import integrate_depth_maps
+        return integrate_depth_maps(self, origin, voxel, shape, resolution, margin, trunc, min_weight)
+
     def cost_limits(self, max_cost):
         """int32 per view: floor(max_cost * sources * window), what `filter(max_cost=...)` hands to the device."""
         win = (2 * self.radius + 1) ** 2
@@ -485,12 +496,13 @@ def depth_maps_from_arrays(shapes, refs, src_ptr, src_image, warps, backproj, de
 
 
 def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=256, radius=2, rel_tol=0.01, max_cost=None,
-                              min_consistent=2, colors=None, device=0, fuse=False):
+                              min_consistent=2, colors=None, device=0, fuse=False, mesh=False):
     """The chain on a `Reconstruction`: sources by shared points (`select_sources`), the depth interval of every view from
     its sparse points (`depth_ranges`), planes at most one pixel apart (`plane_depths`), `depth_maps`, `.filter`,
     `.point_cloud`.  images: one per image position of rec.tracks.  Returns (points, index, DepthMaps) - or (points, index,
     colours, DepthMaps) with colors.  With fuse=True the last step is `.fuse()` in place of `.point_cloud`, and the result
-    is (FusedCloud, DepthMaps); the colours are then `FusedCloud.colors(colors)`."""
+    is (FusedCloud, DepthMaps); the colours are then `FusedCloud.colors(colors)`.  With mesh=True the surface of the kept
+    pixels, `maps.tsdf().mesh()`, is appended to whichever of those is returned."""
     n_img = len(rec.tracks.kp_ptr) - 1
     if len(images) != n_img:
         raise ValueError(f"{len(images)} images for {n_img} image positions")
@@ -503,6 +515,7 @@ def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=2
         planes[r] = plane_depths(rng[r][0], rng[r][1], view_warps(rec.K, rec.poses, r, s), size, max_planes)
     maps = depth_maps(images, rec.K, rec.poses, src, planes, radius, device)
     maps.filter(rel_tol, max_cost, min_consistent)
+    surface = (maps.tsdf().mesh(),) if mesh else ()
     if fuse:
-        return maps.fuse(), maps
-    return maps.point_cloud(colors) + (maps,)
+        return (maps.fuse(), maps) + surface
+    return maps.point_cloud(colors) + (maps,) + surface

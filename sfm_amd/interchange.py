@@ -105,6 +105,49 @@ def save_ply_points(points, colors, path, normals=None):
         f.write(body.tobytes())
 
 
+def save_ply_mesh(vertices, triangles, path, normals=None, colors=None):
+    """A triangle mesh as binary little-endian PLY: the vertex element as `save_ply_points` writes it (float32 x, y, z, then
+    nx, ny, nz with normals, then red, green, blue with colors), then `element face` with one `list uchar int vertex_indices`
+    of three int32 per triangle.  triangles: [m,3] integers, every index below the number of vertices."""
+    pts = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    tri = np.asarray(triangles)
+    if tri.size == 0:
+        tri = np.zeros((0, 3), dtype=np.int32)
+    if tri.ndim != 2 or tri.shape[1] != 3 or tri.dtype.kind not in "iu":
+        raise ValueError("triangles must be integers [m,3]")
+    if len(tri) and (tri.min() < 0 or tri.max() >= len(pts)):
+        raise ValueError("a triangle names a vertex that does not exist")
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(pts)}",
+            "property float x", "property float y", "property float z"]
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        nrm = np.asarray(normals)
+        if nrm.shape != (len(pts), 3):
+            raise ValueError("normals must be [n,3], one per vertex")
+        head += ["property float nx", "property float ny", "property float nz"]
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    if colors is not None:
+        col = np.asarray(colors)
+        if col.dtype != np.uint8 or col.shape not in ((len(pts),), (len(pts), 3)):
+            raise ValueError("colors must be uint8 [n] or [n,3], one per vertex")
+        col = np.repeat(col[:, None], 3, axis=1) if col.ndim == 1 else col[:, ::-1]
+        head += ["property uchar red", "property uchar green", "property uchar blue"]
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    head += [f"element face {len(tri)}", "property list uchar int vertex_indices"]
+    body = np.zeros(len(pts), dtype=np.dtype(fields))
+    body["x"], body["y"], body["z"] = pts[:, 0], pts[:, 1], pts[:, 2]
+    if normals is not None:
+        body["nx"], body["ny"], body["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
+    if colors is not None:
+        body["red"], body["green"], body["blue"] = col[:, 0], col[:, 1], col[:, 2]
+    faces = np.zeros(len(tri), dtype=np.dtype([("n", "u1"), ("v", "<i4", 3)]))
+    faces["n"], faces["v"] = 3, tri
+    with open(path, "wb") as f:
+        f.write(("\n".join(head + ["end_header"]) + "\n").encode("ascii"))
+        f.write(body.tobytes())
+        f.write(faces.tobytes())
+
+
 def save_reconstruction(poses, points3D, point_tracks, output_dir):
     """poses.json, points3D.json (points + tracks, image ids as strings) and reconstruction.ply."""
     output_dir = Path(output_dir)

@@ -1,0 +1,229 @@
+"""A surface from the depth maps on the device: `sfm_tsdf_integrate` (sfm_amd/csrc/tsdf.hip) fills a truncated signed
+distance volume from filtered depth maps, `sfm_mesh_mark` / `sfm_mesh_emit` (sfm_amd/csrc/mesh.hip) turn its zero level into
+a triangle mesh by marching tetrahedra; include/sfm_amd.h states both rules completely.  Every view weighs the same, a pixel
+without a depth carries no evidence (free space outside every silhouette stays unknown and the mesh is open there), holes
+are not filled and zero-area triangles are kept.  No CPU fallback: without the library or a GPU the calls raise.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from numbers import Real
+
+import numpy as np
+
+from . import _lib
+
+MIN_DIM, MAX_DIM, MAX_VIEWS = 2, 1024, 65535
+
+
+def check_grid(origin, voxel, shape):
+    """(origin float64 [3], voxel float, (nx, ny, nz)) or ValueError."""
+    origin = np.asarray(origin, dtype=np.float64).reshape(-1)
+    if origin.shape != (3,) or not np.isfinite(origin).all():
+        raise ValueError("origin must be 3 finite numbers")
+    if not (isinstance(voxel, Real) and np.isfinite(voxel) and voxel > 0):
+        raise ValueError("voxel must be a finite number > 0")
+    try:
+        shape = tuple(shape)
+    except TypeError:
+        raise ValueError("shape must be (nx, ny, nz)") from None
+    if len(shape) != 3 or any(not (isinstance(n, (int, np.integer)) and MIN_DIM <= n <= MAX_DIM) for n in shape):
+        raise ValueError(f"shape must be (nx, ny, nz), integers {MIN_DIM} .. {MAX_DIM}")
+    return origin, float(voxel), tuple(int(n) for n in shape)
+
+
+class Mesh:
+    """What `TsdfVolume.mesh` returns; the arrays stay on the device until they are asked for.  vertices float64 [nv,3] in
+    (node index, direction) order, normals float32 [nv,3] (unit, pointing to the outside; zeros where the gradient has no
+    length), triangles int32 [nt,3] in (cell index, tetrahedron) order, their normals pointing from inside to outside."""
+
+    def __init__(self, state, n_vertices, n_triangles):
+        self._m = state
+        self.n_vertices, self.n_triangles = int(n_vertices), int(n_triangles)
+        self._host = {}
+
+    def _get(self, name, n):
+        if name not in self._host:
+            self._host[name] = self._m[name].cpu().numpy()[:n]
+        return self._host[name]
+
+    vertices = property(lambda self: self._get("vertices", self.n_vertices))
+    normals = property(lambda self: self._get("normals", self.n_vertices))
+    triangles = property(lambda self: self._get("triangles", self.n_triangles))
+
+    def save(self, path, colors=None):
+        """Binary PLY with normals (`save_ply_mesh`)."""
+        from .interchange import save_ply_mesh
+        save_ply_mesh(self.vertices, self.triangles, path, normals=self.normals, colors=colors)
+
+
+class TsdfVolume:
+    """A truncated signed distance field on a grid of nx x ny x nz nodes, node (i, j, k) at origin + voxel * (i, j, k).
+    tsdf float32 and weight uint16, both [nz,ny,nx], stay on the device until they are asked for; origin float64 [3], voxel,
+    shape = (nx, ny, nz).  A node without evidence has weight 0 and a NaN tsdf."""
+
+    def __init__(self, tsdf, weight, origin, voxel, shape, min_weight=1):
+        self._tsdf, self._weight = tsdf, weight                    # device: float32 [n], int16 [n] holding the uint16 bits
+        self.origin, self.voxel, self.shape = origin, voxel, shape
+        self.min_weight = min_weight
+        self._host = {}
+
+    @property
+    def tsdf(self):
+        if "tsdf" not in self._host:
+            self._host["tsdf"] = self._tsdf.cpu().numpy().reshape(self.shape[::-1])
+        return self._host["tsdf"]
+
+    @property
+    def weight(self):
+        if "weight" not in self._host:
+            self._host["weight"] = self._weight.cpu().numpy().view(np.uint16).reshape(self.shape[::-1])
+        return self._host["weight"]
+
+    def mesh(self, min_weight=None):
+        """The zero level as a `Mesh`.  min_weight: a node counts when at least this many views saw it (None: the volume's
+        own, 1 unless `DepthMaps.tsdf` was given another); cells with a node that does not count give no triangle."""
+        import torch
+        min_weight = self.min_weight if min_weight is None else min_weight
+        if not (isinstance(min_weight, (int, np.integer)) and 0 <= min_weight <= 0x7FFFFFFF):
+            raise ValueError("min_weight must be an integer >= 0")
+        dev = self._tsdf.device
+        h = _lib.get_handle(dev.index)
+        nx, ny, nz = self.shape
+        need = C.c_int64()
+        h.check(h.lib.sfm_mesh_workspace_bytes(nx, ny, nz, C.byref(need)), "sfm_mesh_workspace_bytes")
+        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        dp = lambda t: C.c_void_p(t.data_ptr())
+        origin = np.ascontiguousarray(self.origin, dtype=np.float64)
+        h.call("sfm_mesh_mark", dp(self._tsdf), dp(self._weight), nx, ny, nz, int(min_weight), dp(counts), dp(ws), need.value)
+        nv, nt = (int(c) for c in counts.cpu().numpy())            # waits for the mark call: the counts size the outputs
+        m = {"vertices": torch.empty((max(nv, 1), 3), dtype=torch.float64, device=dev),
+             "normals": torch.empty((max(nv, 1), 3), dtype=torch.float32, device=dev),
+             "triangles": torch.empty((max(nt, 1), 3), dtype=torch.int32, device=dev)}
+        h.call("sfm_mesh_emit", dp(self._tsdf), nx, ny, nz, C.c_void_p(origin.ctypes.data), C.c_double(self.voxel), nv, nt,
+               dp(m["vertices"]), dp(m["normals"]), dp(m["triangles"]), dp(ws), need.value)
+        m["ws"] = ws                                               # alive until the outputs are: the emit call may still run
+        return Mesh(m, nv, nt)
+
+
+def tsdf_volume_from_arrays(tsdf, weight, origin, voxel, device=0):
+    """A `TsdfVolume` around a field that was made elsewhere: tsdf (float32) and weight (uint16) are [nz,ny,nx]."""
+    import torch
+    tsdf = np.ascontiguousarray(tsdf, dtype=np.float32)
+    weight = np.ascontiguousarray(weight)
+    if tsdf.ndim != 3 or weight.shape != tsdf.shape:
+        raise ValueError("tsdf and weight must be [nz,ny,nx] arrays of one shape")
+    if weight.dtype.kind not in "iu" or (weight.size and (weight.min() < 0 or weight.max() > 65535)):
+        raise ValueError("weight must hold integers 0 .. 65535")
+    origin, voxel, shape = check_grid(origin, voxel, tsdf.shape[::-1])
+    _lib.get_handle(device)
+    dev = torch.device("cuda", device)
+    return TsdfVolume(torch.from_numpy(tsdf.reshape(-1)).to(dev), torch.from_numpy(weight.astype(np.uint16).view(np.int16).reshape(-1)).to(dev),
+                      origin, voxel, shape)
+
+
+def projections_from_backprojections(backproj):
+    """[n,12] [P | p] = [K R | K t] from the [M | c] = [R^T K^-1 | -R^T t] that `view_backprojection` makes: P = M^-1, p = -P c."""
+    B = np.asarray(backproj, dtype=np.float64).reshape(-1, 3, 4)
+    out = np.zeros((len(B), 12))
+    for v, b in enumerate(B):
+        P = np.linalg.inv(b[:, :3])
+        out[v] = np.c_[P, -P @ b[:, 3]].reshape(12)
+    return out
+
+
+def bounding_grid(points, resolution=256, margin=0.05):
+    """(origin, voxel, shape) of a box around points [n,3]: per axis the 1st to 99th percentile, widened on both sides by
+    margin of its length, with cubic voxels so that the longest side has `resolution` nodes."""
+    if not (isinstance(resolution, (int, np.integer)) and MIN_DIM <= resolution <= MAX_DIM):
+        raise ValueError(f"resolution must be an integer {MIN_DIM} .. {MAX_DIM}")
+    if not (isinstance(margin, Real) and margin >= 0):
+        raise ValueError("margin must be a number >= 0")
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    pts = pts[np.isfinite(pts).all(axis=1)]
+    if len(pts) == 0:
+        raise ValueError("no kept pixel to put a box around")
+    lo, hi = np.percentile(pts, 1, axis=0), np.percentile(pts, 99, axis=0)
+    ext = hi - lo
+    lo, hi = lo - margin * ext, hi + margin * ext
+    longest = float((hi - lo).max())
+    if not longest > 0:
+        raise ValueError("the kept pixels have no extent")
+    voxel = longest / (resolution - 1)
+    shape = tuple(int(min(max(np.ceil((hi[a] - lo[a]) / voxel - 1e-9) + 1, MIN_DIM), MAX_DIM)) for a in range(3))
+    return lo, voxel, shape
+
+
+def integrate_depth_maps(maps, origin=None, voxel=None, shape=None, resolution=256, margin=0.05, trunc=None, min_weight=1):
+    """What `DepthMaps.tsdf` does."""
+    if maps.keep is None:
+        raise ValueError("tsdf() needs filter() first")
+    given = [a is not None for a in (origin, voxel, shape)]
+    if any(given) and not all(given):
+        raise ValueError("origin, voxel and shape come together or not at all")
+    if not (isinstance(min_weight, (int, np.integer)) and min_weight >= 0):
+        raise ValueError("min_weight must be an integer >= 0")
+    s = maps._s
+    if len(maps.views) > MAX_VIEWS:
+        raise ValueError(f"at most {MAX_VIEWS} views")
+    if not all(given):
+        kept = [x[k != 0] for x, k in zip(maps.xyz, maps.keep)]
+        origin, voxel, shape = bounding_grid(np.concatenate(kept) if kept else np.zeros((0, 3)), resolution, margin)
+    origin, voxel, shape = check_grid(origin, voxel, shape)
+    trunc = 3.0 * voxel if trunc is None else trunc
+    if not (isinstance(trunc, Real) and trunc > 0):
+        raise ValueError("trunc must be None or a number > 0")
+    n_ref = len(maps.views)
+    proj = projections_from_backprojections(s["backproj"].cpu().numpy()[:n_ref])
+    vol = _integrate(s["depth"].device, s["heights"], s["widths"], s["ref_image"], proj, s["depth"], s["keep"], origin, voxel, shape, trunc)
+    vol.min_weight = int(min_weight)
+    return vol
+
+
+def _integrate(dev, heights, widths, ref_image, proj, d_depth, d_keep, origin, voxel, shape, trunc):
+    """The device call: heights / widths (int32 per image) and ref_image (int32 per view) on the host, proj float64 [n_ref,12]
+    on the host, the maps of the views back to back on the device (d_keep may be None)."""
+    import torch
+    h = _lib.get_handle(dev.index)
+    n_ref, n_img = len(ref_image), len(heights)
+    proj = np.ascontiguousarray(proj, dtype=np.float64).reshape(-1, 12)
+    d_proj = torch.from_numpy(proj).to(dev) if n_ref else torch.zeros((1, 12), dtype=torch.float64, device=dev)
+    need = C.c_int64()
+    h.check(h.lib.sfm_tsdf_workspace_bytes(n_ref, C.byref(need)), "sfm_tsdf_workspace_bytes")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    n = shape[0] * shape[1] * shape[2]
+    tsdf = torch.empty(n, dtype=torch.float32, device=dev)
+    weight = torch.empty(n, dtype=torch.int16, device=dev)
+    dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    h.call("sfm_tsdf_integrate", hp(heights), hp(widths), n_img, n_ref, hp(ref_image), dp(d_proj), dp(d_depth), dp(d_keep), hp(origin),
+           C.c_double(voxel), shape[0], shape[1], shape[2], C.c_double(float(trunc)), dp(tsdf), dp(weight), dp(ws), need.value)
+    vol = TsdfVolume(tsdf, weight, origin, voxel, shape)
+    vol.trunc, vol.proj, vol._ws = float(trunc), proj, (ws, d_proj, d_depth, d_keep)       # alive while the call may still run
+    return vol
+
+
+def tsdf_volume_from_depth_arrays(proj, depth, keep, origin, voxel, shape, trunc, device=0):
+    """A `TsdfVolume` integrated from maps that were made elsewhere: proj float64 [n,12] (row-major [K R | K t]), depth one
+    float32 [h,w] per view, keep one uint8 [h,w] per view or None (every finite depth counts)."""
+    import torch
+    origin, voxel, shape = check_grid(origin, voxel, shape)
+    if not (isinstance(trunc, Real) and trunc > 0):
+        raise ValueError("trunc must be a number > 0")
+    depth = [np.ascontiguousarray(d, dtype=np.float32) for d in depth]
+    if any(d.ndim != 2 for d in depth) or np.shape(proj) != (len(depth), 12) or len(depth) > MAX_VIEWS:
+        raise ValueError(f"depth: at most {MAX_VIEWS} [h,w] maps; proj: 12 numbers for each")
+    if keep is not None and [np.shape(k) for k in keep] != [d.shape for d in depth]:
+        raise ValueError("keep must be None or one [h,w] array per view, shaped like its depth map")
+    _lib.get_handle(device)
+    dev = torch.device("cuda", device)
+
+    def up(arrays, dtype):
+        flat = np.concatenate([np.asarray(a, dtype=dtype).reshape(-1) for a in arrays] + [np.zeros(1, dtype)])
+        return torch.from_numpy(flat).to(dev)
+
+    heights = np.array([d.shape[0] for d in depth], dtype=np.int32)
+    widths = np.array([d.shape[1] for d in depth], dtype=np.int32)
+    return _integrate(dev, heights, widths, np.arange(len(depth), dtype=np.int32), proj, up(depth, np.float32),
+                      None if keep is None else up(keep, np.uint8), origin, voxel, shape, trunc)

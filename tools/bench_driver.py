@@ -8,7 +8,7 @@ triangulation of the tracks, the resection lists, the gate evaluation and the in
 feature detection / description stage in front of them all, and the dense-depth stage behind them.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
 functions to time on a bounded sample of the same inputs (this tool itself never imports oracle/).
 usage: python tools/bench_driver.py [--reps 20] [--fundamental-only | --essential-only | --homography-only | --pnp-only | --pose-only | --tracks-only | --triangulate-only |
-       --incremental-only | --features-only | --guided-only | --depth-only]"""
+       --incremental-only | --features-only | --guided-only | --depth-only | --mesh-only]"""
 import argparse
 import ctypes as C
 import json
@@ -986,14 +986,16 @@ def measure_guided(reps=20, emit=None):
     return [r]
 
 
-def measure_depth(reps=20, emit=None):
+def measure_depth(reps=20, emit=None, mesh=False):
     """sfm_depth_census, sfm_depth_sweep and sfm_depth_filter on 36 synthetic 1024 x 768 views (the scene generator of
     tests/depth_reference.py: cameras on a line, baseline 0.1, f = 1228), every view a reference with its 4 nearest cameras
     as sources, planes from sfm_amd.depth.plane_depths over 2.5 .. 5, radius 2, inputs resident in HBM: device time of each
     call by HIP events around `reps` calls, per reference view, and the samples (pixels x planes x sources) per second of
     the sweep.  Behind them sfm_depth_fuse_mark and sfm_depth_fuse_gather (rel_tol 0.02, step 2, jump 0.05) on the filter's
     outputs, beside the compaction they replace: torch.nonzero + gather as in DepthMaps.point_cloud().  In the same run
-    sfm_features_detect + sfm_features_describe on the same images, as a known quantity."""
+    sfm_features_detect + sfm_features_describe on the same images, as a known quantity.  With mesh=True also the surface
+    of the same run: sfm_tsdf_integrate of the 36 filtered maps into 256^3 nodes (a cube around the kept pixels, truncation 3
+    voxels), sfm_mesh_mark and sfm_mesh_emit (min_weight 1), whole calls by HIP events; the row is then named "mesh"."""
     import torch
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from depth_reference import make_scene
@@ -1082,6 +1084,49 @@ def measure_depth(reps=20, emit=None):
                 "ms_fuse_mark_per_view": timed(run_mark, reps) * 1e3 / n_img, "ms_fuse_gather_per_view": timed(run_gather, reps) * 1e3 / n_img,
                 "ms_point_cloud_nonzero_gather_per_view": timed(run_point_cloud, reps) * 1e3 / n_img})
     del normal_map, agree_mask, owner, points, normals, n_views, index, fuse_ws
+    if mesh:
+        from sfm_amd import mesh as mm
+        row["kernel"] = "mesh"
+        sub = xyz[torch.nonzero(keep, as_tuple=False).reshape(-1)[::64]].cpu().numpy()
+        lo, voxel, box = mm.bounding_grid(sub, 256, 0.05)
+        nx = ny = nz = 256                                         # a cube: the shorter sides of the box are centred in it
+        origin = np.ascontiguousarray(lo + 0.5 * voxel * (np.array(box) - 1) - 0.5 * voxel * 255, dtype=np.float64)
+        d_proj = torch.from_numpy(mm.projections_from_backprojections(backproj)).to(dev)
+        h.check(h.lib.sfm_tsdf_workspace_bytes(n_img, C.byref(need)), "sfm_tsdf_workspace_bytes")
+        tsdf_need = need.value
+        tsdf_ws = torch.empty(tsdf_need, dtype=torch.uint8, device=dev)
+        h.check(h.lib.sfm_mesh_workspace_bytes(nx, ny, nz, C.byref(need)), "sfm_mesh_workspace_bytes")
+        mesh_need = need.value
+        mesh_ws = torch.empty(mesh_need, dtype=torch.uint8, device=dev)
+        tsdf = torch.empty(nx * ny * nz, dtype=torch.float32, device=dev)
+        weight = torch.empty(nx * ny * nz, dtype=torch.int16, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+
+        def run_integrate():
+            h.call("sfm_tsdf_integrate", hp(heights), hp(widths), n_img, n_img, hp(ref_image), _p(d_proj), _p(depth), _p(keep), hp(origin),
+                   C.c_double(voxel), nx, ny, nz, C.c_double(3.0 * voxel), _p(tsdf), _p(weight), _p(tsdf_ws), tsdf_need)
+
+        def run_mesh_mark():
+            h.call("sfm_mesh_mark", _p(tsdf), _p(weight), nx, ny, nz, 1, _p(counts), _p(mesh_ws), mesh_need)
+        run_integrate(); run_mesh_mark()
+        nv, nt = (int(c) for c in counts.cpu().numpy())
+        vertices = torch.empty((max(nv, 1), 3), dtype=torch.float64, device=dev)
+        vnormals = torch.empty((max(nv, 1), 3), dtype=torch.float32, device=dev)
+        triangles = torch.empty((max(nt, 1), 3), dtype=torch.int32, device=dev)
+
+        def run_mesh_emit():
+            h.call("sfm_mesh_emit", _p(tsdf), nx, ny, nz, hp(origin), C.c_double(voxel), nv, nt, _p(vertices), _p(vnormals), _p(triangles),
+                   _p(mesh_ws), mesh_need)
+        run_mesh_emit()
+        zv = vertices[:nv, 2].cpu().numpy()
+        seen = int((weight != 0).sum().item())
+        row.update({"grid_nodes": [nx, ny, nz], "voxel": float(voxel), "nodes_seen": seen, "projections": nx * ny * nz * n_img,
+                    "mesh_vertices": nv, "mesh_triangles": nt,
+                    "share_of_vertices_within_one_voxel_of_a_plane": float((np.minimum(np.abs(zv - sc.z_front), np.abs(zv - sc.z_back)) <= voxel).mean()) if nv else 0.0,
+                    "ms_tsdf_integrate": timed(run_integrate, reps) * 1e3, "ms_mesh_mark": timed(run_mesh_mark, reps) * 1e3,
+                    "ms_mesh_emit": timed(run_mesh_emit, reps) * 1e3})
+        row["projections_per_s"] = row["projections"] / (row["ms_tsdf_integrate"] * 1e-3)
+        del tsdf, weight, vertices, vnormals, triangles, mesh_ws
     # the known quantity beside it: the feature stage on the same images
     threshold, edge, max_features = 20, 31, 10000
     h.check(h.lib.sfm_features_workspace_bytes(n_img, hp(off), C.byref(need)), "sfm_features_workspace_bytes")
@@ -1126,10 +1171,11 @@ def main():
     ap.add_argument("--features-only", action="store_true", help="only the feature detection / description row")
     ap.add_argument("--guided-only", action="store_true", help="only the guided-matching row (beside the blind matcher)")
     ap.add_argument("--depth-only", action="store_true", help="only the dense-depth row (beside the feature stage on the same images)")
+    ap.add_argument("--mesh-only", action="store_true", help="only the meshing row: TSDF integration, mark and emit beside the sweep and the fusion of the same run")
     a = ap.parse_args()
     emit = lambda d: print(json.dumps(d), flush=True)
     only = a.fundamental_only or a.essential_only or a.homography_only or a.pnp_only or a.pose_only or a.tracks_only or a.triangulate_only or a.incremental_only or \
-        a.features_only or a.guided_only or a.depth_only
+        a.features_only or a.guided_only or a.depth_only or a.mesh_only
     if not only:
         measure(a.reps, a.tracks, a.corr, emit=emit)
     if a.fundamental_only or not only:
@@ -1154,6 +1200,8 @@ def main():
         measure_guided(a.reps, emit=emit)
     if a.depth_only or not only:
         measure_depth(a.reps, emit=emit)
+    if a.mesh_only:
+        measure_depth(a.reps, emit=emit, mesh=True)
 
 
 if __name__ == "__main__":

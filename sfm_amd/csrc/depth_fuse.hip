@@ -1,17 +1,18 @@
 // Fusion of the depth maps of a call into one cloud with normals for gfx950 (MI355X): a normal map per view, the agreeing
 // partners and the owner of every kept pixel, a two-level exclusive scan of the owner counts, and the gather of the fused
 // points.  include/sfm_amd.h states the rule; depth_rule.h holds its floating-point pieces (float64, no FMA contraction),
-// depth_plan.h the block counts, the scan plan and the workspace layout.
+// depth_plan.h the block counts and the workspace layout; count, scan and rank are those of block_scan.h / scan_plan.h.
 //
 // Every kernel is one thread per pixel over the pixel blocks of the filter (DEPTH_PIXEL_BLOCK pixels of one view).  The
 // rule is a pure function of the filter's outputs: no visit order, no global atomics, nothing waits on another workgroup.
-// k_depth_fuse_mark counts the owners of its block with one ballot and one LDS add per wavefront; the scan turns the
+// k_depth_fuse_mark counts the owners of its block with one ballot per wavefront; the scan turns the
 // counts into the first output slot of every block; k_depth_fuse_gather ranks an owner inside its block by the ballots
 // of the wavefronts in front of it and the lanes below it, and re-reads the partners that agree_mask names through the
 // sample rule: partner coordinates are never stored.
 #include "common.h"
 #include "depth_rule.h"
 #include "depth_plan.h"
+#include "block_scan.h"
 
 #pragma clang fp contract(off)
 
@@ -86,9 +87,7 @@ __global__ __launch_bounds__(DEPTH_PIXEL_BLOCK) void k_depth_fuse_mark(const Dep
                                                                        const float* __restrict__ depth_in, const uint8_t* __restrict__ keep,
                                                                        double rel_tol, uint8_t* __restrict__ agree_mask,
                                                                        uint8_t* __restrict__ owner, uint32_t* __restrict__ blk) {
-  __shared__ unsigned s_count;
-  if (threadIdx.x == 0) s_count = 0;
-  __syncthreads();
+  __shared__ int s_wave[FUSE_WAVES];
   DepthView view; DepthImage ref;
   const FusePixel q = fuse_pixel(images, views, n_ref, &view, &ref);
   unsigned mask = 0;
@@ -106,53 +105,13 @@ __global__ __launch_bounds__(DEPTH_PIXEL_BLOCK) void k_depth_fuse_mark(const Dep
     }
   }
   if (q.in) { agree_mask[q.o] = (uint8_t)mask; owner[q.o] = own ? 1 : 0; }
-  const unsigned long long owners = __ballot(own);
-  if ((threadIdx.x & 63) == 0) atomicAdd(&s_count, (unsigned)__popcll(owners));      // LDS, one add per wavefront
-  __syncthreads();
-  if (threadIdx.x == 0) blk[blockIdx.x] = s_count;
-}
-
-// exclusive prefix of v over the workgroup, and the workgroup's total; s_wave has FUSE_WAVES elements and is free again on return
-__device__ __forceinline__ int64_t fuse_block_scan(int64_t v, int64_t* s_wave, int64_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int64_t inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int64_t t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  int64_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < FUSE_WAVES; ++w) {
-    const int64_t t = s_wave[w];
-    if (w < wave) before += t;
-    all += t;
-  }
-  __syncthreads();
-  *total = all;
-  return before + inc - v;
+  const int owners = block_flag_count<DEPTH_PIXEL_BLOCK>(own, s_wave);
+  if (threadIdx.x == 0) blk[blockIdx.x] = (uint32_t)owners;
 }
 
 __global__ __launch_bounds__(DEPTH_THREADS) void k_depth_fuse_scan_chunks(uint32_t* __restrict__ blk, int64_t n_blocks, int64_t* __restrict__ chunk_sum) {
   __shared__ int64_t s_wave[FUSE_WAVES];
-  uint32_t c[DEPTH_SCAN_ITEMS];
-  int64_t sum = 0;
-#pragma unroll
-  for (int j = 0; j < DEPTH_SCAN_ITEMS; ++j) {
-    const int64_t i = depth_scan_item(blockIdx.x, threadIdx.x, j);
-    c[j] = i < n_blocks ? blk[i] : 0u;
-    sum += c[j];
-  }
-  int64_t total;
-  int64_t run = fuse_block_scan(sum, s_wave, &total);
-#pragma unroll
-  for (int j = 0; j < DEPTH_SCAN_ITEMS; ++j) {
-    const int64_t i = depth_scan_item(blockIdx.x, threadIdx.x, j);
-    if (i < n_blocks) blk[i] = (uint32_t)run;
-    run += c[j];
-  }
+  const int64_t total = scan_chunk_counts(blk, n_blocks, s_wave);
   if (threadIdx.x == 0) chunk_sum[blockIdx.x] = total;
 }
 
@@ -160,19 +119,11 @@ __global__ __launch_bounds__(DEPTH_THREADS) void k_depth_fuse_scan_top(int64_t* 
                                                                        int64_t n_blocks, const DepthView* __restrict__ views, int n_ref,
                                                                        int64_t* __restrict__ pt_ptr) {
   __shared__ int64_t s_wave[FUSE_WAVES];
-  int64_t carry = 0;
-  for (int64_t first = 0; first < n_chunks; first += DEPTH_THREADS) {
-    const int64_t i = first + threadIdx.x;
-    const int64_t v = i < n_chunks ? chunk_sum[i] : 0;
-    int64_t total;
-    const int64_t before = fuse_block_scan(v, s_wave, &total);
-    if (i < n_chunks) chunk_sum[i] = carry + before;
-    carry += total;
-  }
+  const int64_t all = scan_chunk_totals(chunk_sum, n_chunks, 1, s_wave);
   __syncthreads();                                             // the bases of this workgroup's own stores, read below
   for (int v = threadIdx.x; v <= n_ref; v += DEPTH_THREADS) {
     const int64_t b = views[v].pix_block_first;
-    pt_ptr[v] = b < n_blocks ? depth_scan_base(chunk_sum, blk, b) : carry;
+    pt_ptr[v] = b < n_blocks ? depth_scan_base(chunk_sum, blk, b) : all;
   }
 }
 
@@ -189,14 +140,8 @@ __global__ __launch_bounds__(DEPTH_PIXEL_BLOCK) void k_depth_fuse_gather(const D
   DepthView view; DepthImage ref;
   const FusePixel q = fuse_pixel(images, views, n_ref, &view, &ref);
   const bool own = q.in && owner[q.o] != 0;
-  const unsigned long long owners = __ballot(own);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) s_wave[wave] = __popcll(owners);
-  __syncthreads();
+  const int rank = block_flag_rank<DEPTH_PIXEL_BLOCK>(own, s_wave);
   if (!own) return;
-  int rank = __popcll(owners & ((1ull << lane) - 1ull));
-#pragma unroll
-  for (int w = 0; w < FUSE_WAVES; ++w) rank += w < wave ? s_wave[w] : 0;
   const int64_t slot = depth_scan_base(chunk_base, blk, blockIdx.x) + rank;
   // a workspace or a pt_ptr that is not the mark call's, or an n_points below the truth, writes nothing outside the outputs
   if (slot < pt_ptr[q.v] || slot >= pt_ptr[q.v + 1] || slot >= n_points) return;
@@ -285,7 +230,7 @@ extern "C" int sfm_depth_fuse_mark(sfm_handle h, const int64_t* img_off, const i
   const DepthView* d_view = (const DepthView*)(ws + T.views);
   uint32_t* d_blk = (uint32_t*)(ws + L.blk);
   int64_t* d_chunk = (int64_t*)(ws + L.chunk_base);
-  const int64_t n_chunks = depth_scan_chunks(nb);
+  const int64_t n_chunks = scan_chunks(nb);
   hipLaunchKernelGGL(k_depth_normals, dim3((unsigned)nb), dim3(DEPTH_PIXEL_BLOCK), 0, h->stream, d_img, d_view, n_ref, backproj, depth, xyz,
                      normal_step, normal_jump, normal_map);
   SFM_LAUNCH_CHECK(h, "sfm_depth_fuse_mark");

@@ -10,6 +10,7 @@
 #pragma once
 #include <cstdint>
 #include <vector>
+#include "scan_plan.h"
 
 #if defined(__HIPCC__)
 #define DEPTH_PLAN_HD __host__ __device__ __forceinline__
@@ -177,25 +178,18 @@ inline DepthLayout depth_layout(int64_t n_img, int64_t n_ref, int64_t n_entries)
 
 // ---- fusion (depth_fuse.hip): the owner counts of the pixel blocks and their two-level exclusive scan ----
 // k_depth_fuse_mark leaves one owner count per pixel block (the blocks of the filter: DEPTH_PIXEL_BLOCK pixels of one view,
-// views back to back, block b of the call at blk[b]).  A chunk is DEPTH_SCAN_CHUNK consecutive blocks.  Level one
-// (k_depth_fuse_scan_chunks, one workgroup of DEPTH_THREADS threads per chunk) replaces every count by the owners in front
-// of it within its chunk and writes the chunk's total; thread t holds the DEPTH_SCAN_ITEMS consecutive counts from
-// depth_scan_item(chunk, t, 0).  Level two (k_depth_fuse_scan_top, ONE workgroup) walks the chunk totals in tiles of
-// DEPTH_THREADS with a running carry, replaces every total by the owners in front of its chunk, and writes
+// views back to back, block b of the call at blk[b]).  The two-level scan of scan_plan.h runs over them: level one
+// (k_depth_fuse_scan_chunks) writes one total per chunk, level two (k_depth_fuse_scan_top) walks the totals and writes
 // pt_ptr[v] = depth_scan_base(...) of the first block of view v (the grand total where no block follows).  The first
 // output slot of block b is depth_scan_base(chunk_base, blk, b).  Nothing waits on another workgroup: three launches.
-#define DEPTH_SCAN_ITEMS 4
-#define DEPTH_SCAN_CHUNK (DEPTH_THREADS * DEPTH_SCAN_ITEMS)
 #define DEPTH_MAX_NORMAL_STEP 4
 
-static_assert(DEPTH_PIXEL_BLOCK == DEPTH_THREADS && DEPTH_THREADS % 64 == 0, "a pixel block is a workgroup of whole wavefronts");
-// a chunk holds at most DEPTH_SCAN_CHUNK * DEPTH_PIXEL_BLOCK owners: the counts and the bases within a chunk fit 32 bits
-static_assert((int64_t)DEPTH_SCAN_CHUNK * DEPTH_PIXEL_BLOCK < 0x7FFFFFFFLL, "bases within a chunk fit 32 bits");
+static_assert(DEPTH_PIXEL_BLOCK == DEPTH_THREADS && DEPTH_THREADS == SCAN_THREADS, "a pixel block is a workgroup of the scan");
+// a chunk holds at most SCAN_CHUNK * DEPTH_PIXEL_BLOCK owners: the counts and the bases within a chunk fit 32 bits
+static_assert((int64_t)SCAN_CHUNK * DEPTH_PIXEL_BLOCK < 0x7FFFFFFFLL, "bases within a chunk fit 32 bits");
 
-DEPTH_PLAN_HD int64_t depth_scan_chunks(int64_t n_blocks) { return (n_blocks + DEPTH_SCAN_CHUNK - 1) / DEPTH_SCAN_CHUNK; }
-DEPTH_PLAN_HD int64_t depth_scan_item(int64_t chunk, int tid, int j) { return chunk * DEPTH_SCAN_CHUNK + (int64_t)tid * DEPTH_SCAN_ITEMS + j; }
 DEPTH_PLAN_HD int64_t depth_scan_base(const int64_t* chunk_base, const uint32_t* blk, int64_t b) {
-  return chunk_base[b / DEPTH_SCAN_CHUNK] + (int64_t)blk[b];
+  return scan_base(chunk_base, 1, 0, b, (int64_t)blk[b]);
 }
 // the most pixel blocks a call with n_out output elements in n_ref views can have: every view ends in one partial block
 DEPTH_PLAN_HD int64_t depth_max_pixel_blocks(int64_t n_out, int64_t n_ref) { return n_out / DEPTH_PIXEL_BLOCK + n_ref; }
@@ -207,7 +201,7 @@ inline DepthFuseLayout depth_fuse_layout(int64_t n_img, int64_t n_ref, int64_t n
   L.tables = depth_layout(n_img, n_ref, n_entries);
   int64_t off = depth_align(L.tables.bytes);
   L.blk = off;        off += depth_align(n_blocks * 4);
-  L.chunk_base = off; off += depth_align(depth_scan_chunks(n_blocks) * 8);
+  L.chunk_base = off; off += depth_align(scan_chunks(n_blocks) * 8);
   L.bytes = off + 256;
   return L;
 }

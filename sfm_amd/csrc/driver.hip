@@ -7,6 +7,7 @@
 // no FMA contraction anywhere in this file (NumPy / OpenCV's generic x86 code do not fuse).
 #include "common.h"
 #include "pose_solve.h"
+#include "block_scan.h"
 #include <cfloat>
 
 #pragma clang fp contract(off)
@@ -21,25 +22,6 @@ __device__ __forceinline__ int seg_of(const int64_t* __restrict__ ptr, int n_seg
     if (ptr[mid] <= i) lo = mid; else hi = mid;
   }
   return lo;
-}
-
-// exclusive scan of one int per thread over a 256-thread block; total = block sum
-__device__ __forceinline__ int block_excl_scan(int v, int* s_w, int& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(incl, d);
-    if (lane >= d) incl += t;
-  }
-  __syncthreads();
-  if (lane == 63) s_w[w] = incl;
-  __syncthreads();
-  int off = 0;
-  total = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { if (k < w) off += s_w[k]; total += s_w[k]; }
-  return off + incl - v;
 }
 
 // ------------------------------------------------------------------------------------------ association
@@ -79,7 +61,7 @@ __global__ __launch_bounds__(256) void k_assoc(const double2* __restrict__ tp, c
         if (y < split) before += c;
       }
     int total;
-    off = (int64_t)blk_off[blockIdx.x] + block_excl_scan(row_total, s_w, total) + before;
+    off = (int64_t)blk_off[blockIdx.x] + block_exclusive_scan<256, int>(row_total, s_w, &total) + before;
   }
   int cnt = 0;
   for (int s = seg_first; s <= seg_last; ++s) {
@@ -132,30 +114,18 @@ __global__ __launch_bounds__(256) void k_assoc(const double2* __restrict__ tp, c
   if (!FILL) {
     if (active) cnt_rs[i * nsplit + split] = cnt;
     int total;
-    (void)block_excl_scan(cnt, s_w, total);
+    (void)block_exclusive_scan<256, int>(cnt, s_w, &total);
     if (tid == 0 && total) atomicAdd(&blk_cnt[blockIdx.x], total);
   }
 }
 
-// exclusive scan of n ints by one 256-thread block (n = number of 256-row blocks, a few thousand at most)
+// exclusive scan of the n block counts by one workgroup (n = number of 256-row blocks, a few thousand at most)
 __global__ __launch_bounds__(256) void k_scan_blocks(int n, const int* __restrict__ in, int* __restrict__ out,
                                                      int64_t* __restrict__ total_out) {
-  __shared__ long long s_sum[256];
-  const int tid = threadIdx.x;
-  const int per = (n + 255) / 256;
-  const int b = tid * per, e = (b + per < n ? b + per : n);
-  long long local = 0;
-  for (int k = b; k < e; ++k) local += in[k];
-  s_sum[tid] = local;
-  __syncthreads();
-  if (tid == 0) {
-    long long run = 0;
-    for (int k = 0; k < 256; ++k) { const long long v = s_sum[k]; s_sum[k] = run; run += v; }
-    *total_out = run;
-  }
-  __syncthreads();
-  long long run = s_sum[tid];
-  for (int k = b; k < e; ++k) { out[k] = (int)run; run += in[k]; }
+  __shared__ int64_t s_wave[4];
+  int64_t total;
+  scan_counts<256>(n, in, out, s_wave, &total);
+  if (threadIdx.x == 0) *total_out = total;
 }
 
 // ---------------------------------------------------------------------------------------- triangulation

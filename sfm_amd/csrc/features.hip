@@ -17,6 +17,7 @@
 //   k_feat_describe  one wavefront per keypoint: moments -> angle bin, 256 comparisons -> four ballots = the 32 bytes
 #include "common.h"
 #include "features_plan.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -227,27 +228,6 @@ __global__ __launch_bounds__(256) void k_feat_ties(feat_dev w, int n_img, int n_
   if (lane == 0) { w.row_cnt[R] = above; w.row_tie[R] = ties; }
 }
 
-// exclusive scan of one value per thread over the workgroup; `total` is the sum of all
-template <int NT> __device__ __forceinline__ int block_scan(int v, int* part, int& total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int inc = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
-  if (lane == 63) part[wv] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-  for (int k = 0; k < NT / 64; ++k) {
-    const int p = part[k];
-    if (k < wv) base += p;
-    tot += p;
-  }
-  __syncthreads();
-  total = tot;
-  return base + inc - v;
-}
-
 // row_tie[R]: ties of the image before row R; row_cnt[R] += the ties of the row that stay
 __global__ __launch_bounds__(256) void k_feat_tie_scan(feat_dev w) {
   __shared__ int part[4];
@@ -260,7 +240,7 @@ __global__ __launch_bounds__(256) void k_feat_tie_scan(feat_dev w) {
     const int r = base + threadIdx.x;
     const int ties = r < m.rows ? w.row_tie[m.row0 + r] : 0;
     int total;
-    const int before = carry + block_scan<256>(ties, part, total);
+    const int before = carry + block_exclusive_scan<256, int>(ties, part, &total);
     if (r < m.rows) {
       w.row_tie[m.row0 + r] = before;
       w.row_cnt[m.row0 + r] += min(max(quota - before, 0), ties);
@@ -279,7 +259,7 @@ __global__ __launch_bounds__(1024) void k_feat_scan(feat_dev w, int n_img, int n
     int c[4], sum = 0;
     for (int k = 0; k < 4; ++k) { c[k] = r + k < n_rows ? w.row_cnt[r + k] : 0; sum += c[k]; }
     int total;
-    int at = carry + block_scan<1024>(sum, part, total);
+    int at = carry + block_exclusive_scan<1024, int>(sum, part, &total);
     for (int k = 0; k < 4; ++k) {
       if (r + k < n_rows) w.row_off[r + k] = at;
       at += c[k];

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "guided_rule.h"
 #include "guided_plan.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -209,31 +210,16 @@ __global__ __launch_bounds__(256) void k_guided_count(int64_t n_out, const Guide
   const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const bool k = o < n_out && guided_keeps(o, segs, n_seg, idx1, d1, d2, ncand, rev, ratio, max_distance, cross_check);
   if (o < n_out) keep[o] = k ? 1 : 0;
-  const unsigned long long b = __ballot(k);
-  if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = __popcll(b);
-  __syncthreads();
-  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = s_c[0] + s_c[1] + s_c[2] + s_c[3];
+  const int kept = block_flag_count(k, s_c);
+  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = kept;
 }
 
-// exclusive scan of the per-block counts: one workgroup, every thread a contiguous run of blocks (as k_ratio_scan of match.hip)
+// exclusive scan of the per-block counts by one workgroup; one entry past the last block: the total
 __global__ __launch_bounds__(256) void k_guided_scan(int nblk, const int* __restrict__ blk_cnt, int* __restrict__ blk_off) {
-  __shared__ int64_t s_sum[256];
-  const int tid = threadIdx.x;
-  const int per = (nblk + 255) / 256;
-  const int beg = tid * per < nblk ? tid * per : nblk, end = (beg + per) < nblk ? (beg + per) : nblk;
-  int64_t mine = 0;
-  for (int i = beg; i < end; ++i) mine += blk_cnt[i];
-  s_sum[tid] = mine;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {
-    const int64_t v = tid >= o ? s_sum[tid - o] : 0;
-    __syncthreads();
-    s_sum[tid] += v;
-    __syncthreads();
-  }
-  int64_t run = s_sum[tid] - mine;
-  for (int i = beg; i < end; ++i) { blk_off[i] = (int)run; run += blk_cnt[i]; }
-  if (tid == 255) blk_off[nblk] = (int)s_sum[255];          // one entry past the last block: the total
+  __shared__ int64_t s_wave[4];
+  int64_t total;
+  scan_counts<256>(nblk, blk_cnt, blk_off, s_wave, &total);
+  if (threadIdx.x == 0) blk_off[nblk] = (int)total;
 }
 
 __global__ __launch_bounds__(256) void k_guided_scatter(int64_t n_out, const GuidedSeg* __restrict__ segs, int n_seg,
@@ -242,14 +228,8 @@ __global__ __launch_bounds__(256) void k_guided_scatter(int64_t n_out, const Gui
                                                         int* __restrict__ query_idx, int* __restrict__ train_idx, float* __restrict__ dist) {
   __shared__ int s_c[4];
   const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const bool k = o < n_out && keep[o] != 0;
-  const unsigned long long b = __ballot(k);
-  if (lane == 0) s_c[w] = __popcll(b);
-  __syncthreads();
-  int off = blk_off[blockIdx.x];
-  for (int i = 0; i < w; ++i) off += s_c[i];
-  off += __popcll(b & ((1ull << lane) - 1ull));
+  const int off = blk_off[blockIdx.x] + block_flag_rank(k, s_c);
   if (k) {
     const int s = guided_find(segs, n_seg, o, GUIDED_BY_OUT);
     query_idx[off] = (int)(o - segs[s].out_first);

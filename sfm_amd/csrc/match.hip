@@ -22,6 +22,7 @@
 // float32 value over the whole train set by k_knn2_u8_rerank (k_merge_splits_u8 lists them).
 #include "common.h"
 #include "match_plan.h"
+#include "block_scan.h"
 #include <vector>
 #include <type_traits>
 
@@ -946,33 +947,18 @@ __global__ __launch_bounds__(256) void k_ratio_count(int64_t nq, const float* __
   __shared__ int s_c[4];
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const bool keep = (i < nq) && ((double)d1[i] < ratio * (double)d2[i]);
-  const unsigned long long b = __ballot(keep);
-  if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = __popcll(b);
-  __syncthreads();
-  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = s_c[0] + s_c[1] + s_c[2] + s_c[3];
+  const int kept = block_flag_count(keep, s_c);
+  if (threadIdx.x == 0) blk_cnt[blockIdx.x] = kept;
 }
 // exclusive scan of the per-block match counts: ONE workgroup, every thread a contiguous run of blocks (a single thread
 // walking all of them took 42-67 us of dependent loads per call - more than any other kernel of a batched call but the
-// distances)
+// distances).  blk_off has nblk entries: the total goes to *total only.
 __global__ __launch_bounds__(256) void k_ratio_scan(int nblk, const int* __restrict__ blk_cnt, int* __restrict__ blk_off,
                                                     int64_t* __restrict__ total) {
-  __shared__ int64_t s_sum[256];
-  const int tid = threadIdx.x;
-  const int per = (nblk + 255) / 256;
-  const int beg = tid * per, end = (beg + per) < nblk ? (beg + per) : nblk;
-  int64_t mine = 0;
-  for (int i = beg; i < end; ++i) mine += blk_cnt[i];
-  s_sum[tid] = mine;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {                       // inclusive Hillis-Steele scan of the 256 run sums
-    const int64_t v = tid >= o ? s_sum[tid - o] : 0;
-    __syncthreads();
-    s_sum[tid] += v;
-    __syncthreads();
-  }
-  int64_t run = s_sum[tid] - mine;
-  for (int i = beg; i < end; ++i) { blk_off[i] = (int)run; run += blk_cnt[i]; }
-  if (tid == 255) *total = s_sum[255];
+  __shared__ int64_t s_wave[4];
+  int64_t sum;
+  scan_counts<256>(nblk, blk_cnt, blk_off, s_wave, &sum);
+  if (threadIdx.x == 0) *total = sum;
 }
 __global__ __launch_bounds__(256) void k_ratio_scatter(int64_t nq, const int* __restrict__ idx1,
                                                        const float* __restrict__ d1, const float* __restrict__ d2,
@@ -981,14 +967,8 @@ __global__ __launch_bounds__(256) void k_ratio_scatter(int64_t nq, const int* __
                                                        float* __restrict__ dist) {
   __shared__ int s_c[4];
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const bool keep = (i < nq) && ((double)d1[i] < ratio * (double)d2[i]);
-  const unsigned long long b = __ballot(keep);
-  if (lane == 0) s_c[w] = __popcll(b);
-  __syncthreads();
-  int off = blk_off[blockIdx.x];
-  for (int k = 0; k < w; ++k) off += s_c[k];
-  off += __popcll(b & ((1ull << lane) - 1ull));
+  const int off = blk_off[blockIdx.x] + block_flag_rank(keep, s_c);
   if (keep) { query_idx[off] = (int)i; train_idx[off] = idx1[i]; dist[off] = d1[i]; }
 }
 

@@ -2,7 +2,7 @@
 // the flags of every node, the vertex mask of every node and the triangle count of every cell with their ranks inside
 // the block, a two-level exclusive scan of the block counts, and the two emitting kernels.  include/sfm_amd.h states the
 // rule; mesh_rule.h holds the case table and the floating point (float64, no FMA contraction), mesh_plan.h the node
-// record, the scan plan and the workspace layout.
+// record, the packed counts and the workspace layout; the scans are those of block_scan.h / scan_plan.h.
 //
 // Every kernel is one thread per node, x fastest, MESH_BLOCK consecutive nodes per workgroup; the thread of a node also
 // handles the cell whose lowest node it is.  The rule is a pure function of the field: no visit order, no global atomics,
@@ -13,6 +13,7 @@
 #include "tsdf_rule.h"
 #include "mesh_rule.h"
 #include "mesh_plan.h"
+#include "block_scan.h"
 
 #pragma clang fp contract(off)
 
@@ -43,29 +44,6 @@ __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_classify(const float* __res
                                                               int64_t n_nodes, int min_weight, uint8_t* __restrict__ flags) {
   const int64_t n = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
   if (n < n_nodes) flags[n] = (uint8_t)mesh::node_flags(tsdf[n], (int)weight[n], min_weight);
-}
-
-// exclusive prefix of v over the workgroup, and the workgroup's total; s_wave has MESH_WAVES elements and is free again on return
-__device__ __forceinline__ int64_t mesh_block_scan(int64_t v, int64_t* s_wave, int64_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int64_t inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int64_t t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  int64_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < MESH_WAVES; ++w) {
-    const int64_t t = s_wave[w];
-    if (w < wave) before += t;
-    all += t;
-  }
-  __syncthreads();
-  *total = all;
-  return before + inc - v;
 }
 
 __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_mark(const uint8_t* __restrict__ flags, Grid g, uint32_t* __restrict__ record,
@@ -108,45 +86,15 @@ __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_mark(const uint8_t* __restr
   }
   // both counts of a block stay below 2^16: one scan of the packed pair
   const int v = __popc((unsigned)mask) | (triangles << 16);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < MESH_WAVES; ++w) {
-    const int t = s_wave[w];
-    if (w < wave) before += t;
-    all += t;
-  }
-  const int rank = before + inc - v;
+  int all;
+  const int rank = block_exclusive_scan<MESH_BLOCK, int>(v, s_wave, &all);
   if (q.in) record[q.n] = mesh_record(mask, rank & 0xFFFF, rank >> 16, active);
   if (threadIdx.x == 0) blk[blockIdx.x] = mesh_count_pack((uint32_t)(all & 0xFFFF), (uint32_t)(all >> 16));
 }
 
 __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_scan_chunks(uint64_t* __restrict__ blk, int64_t n_blocks, int64_t* __restrict__ chunk_sum) {
   __shared__ int64_t s_wave[MESH_WAVES];
-  uint64_t c[MESH_SCAN_ITEMS];
-  int64_t sum = 0;
-#pragma unroll
-  for (int j = 0; j < MESH_SCAN_ITEMS; ++j) {
-    const int64_t i = mesh_scan_item(blockIdx.x, threadIdx.x, j);
-    c[j] = i < n_blocks ? blk[i] : 0ull;
-    sum += (int64_t)c[j];
-  }
-  int64_t total;
-  int64_t run = mesh_block_scan(sum, s_wave, &total);           // neither half leaves its 32 bits within a chunk
-#pragma unroll
-  for (int j = 0; j < MESH_SCAN_ITEMS; ++j) {
-    const int64_t i = mesh_scan_item(blockIdx.x, threadIdx.x, j);
-    if (i < n_blocks) blk[i] = (uint64_t)run;
-    run += (int64_t)c[j];
-  }
+  const int64_t total = scan_chunk_counts(blk, n_blocks, s_wave);   // neither half leaves its 32 bits within a chunk
   if (threadIdx.x == 0) {
     chunk_sum[2 * (int64_t)blockIdx.x] = total & 0xFFFFFFFFll;
     chunk_sum[2 * (int64_t)blockIdx.x + 1] = total >> 32;
@@ -156,16 +104,8 @@ __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_scan_chunks(uint64_t* __res
 __global__ __launch_bounds__(MESH_BLOCK) void k_mesh_scan_top(int64_t* __restrict__ chunk_sum, int64_t n_chunks, int64_t* __restrict__ counts) {
   __shared__ int64_t s_wave[MESH_WAVES];
   for (int half = 0; half < 2; ++half) {
-    int64_t carry = 0;
-    for (int64_t first = 0; first < n_chunks; first += MESH_BLOCK) {
-      const int64_t i = first + threadIdx.x;
-      const int64_t v = i < n_chunks ? chunk_sum[2 * i + half] : 0;
-      int64_t total;
-      const int64_t before = mesh_block_scan(v, s_wave, &total);
-      if (i < n_chunks) chunk_sum[2 * i + half] = carry + before;
-      carry += total;
-    }
-    if (threadIdx.x == 0) counts[half] = carry;
+    const int64_t all = scan_chunk_totals(chunk_sum + half, n_chunks, 2, s_wave);
+    if (threadIdx.x == 0) counts[half] = all;
   }
 }
 
@@ -263,7 +203,7 @@ extern "C" int sfm_mesh_mark(sfm_handle h, const float* tsdf, const uint16_t* we
   int bad = mesh_check_grid(nx, ny, nz);
   if (!bad && min_weight < 0) bad = 11;
   if (bad) return sfm_fail(h, SFM_ERR_ARG, what, MESH_WHY[bad]);
-  const int64_t n_nodes = mesh_nodes(nx, ny, nz), nb = mesh_blocks(n_nodes), n_chunks = mesh_scan_chunks(nb);
+  const int64_t n_nodes = mesh_nodes(nx, ny, nz), nb = mesh_blocks(n_nodes), n_chunks = scan_chunks(nb);
   const MeshLayout L = mesh_layout(n_nodes);
   if (!workspace || workspace_bytes < L.bytes) return sfm_fail(h, SFM_ERR_ARG, what, "workspace missing or too small");
   if (!tsdf || !weight || !counts) return sfm_fail(h, SFM_ERR_ARG, what, "null pointer");

@@ -5,14 +5,14 @@
 // Every kernel is one thread per node, x fastest, MESH_BLOCK consecutive nodes per workgroup; a cell is handled by the
 // thread of its lowest node.  k_mesh_mark leaves per node one 32-bit record - the 7-bit vertex mask, the vertices of the
 // block in front of the node's, the triangles of the block in front of the cell's, whether the cell is active - and per
-// block one 64-bit count, vertices in the low half and triangles in the high half.  A chunk is MESH_SCAN_CHUNK consecutive
-// blocks.  Level one (k_mesh_scan_chunks, one workgroup per chunk) replaces every count by the sums in front of it within
-// its chunk and writes the chunk's two totals; level two (k_mesh_scan_top, ONE workgroup) walks the totals in tiles of
-// MESH_BLOCK with a running carry, replaces them by the sums in front of the chunk, and writes counts.  Nothing waits on
-// another workgroup.
+// block one 64-bit count, vertices in the low half and triangles in the high half.  The two-level scan of scan_plan.h
+// runs over the packed counts: level one (k_mesh_scan_chunks) scans both halves with one add and writes the chunk's two
+// totals, level two (k_mesh_scan_top) walks each of the two (stride 2) and writes counts.  Nothing waits on another
+// workgroup.
 #pragma once
 #include <cstdint>
 #include <vector>
+#include "scan_plan.h"
 
 #if defined(__HIPCC__)
 #define MESH_PLAN_HD __host__ __device__ __forceinline__
@@ -21,8 +21,6 @@
 #endif
 
 #define MESH_BLOCK 256
-#define MESH_SCAN_ITEMS 4
-#define MESH_SCAN_CHUNK (MESH_BLOCK * MESH_SCAN_ITEMS)
 #define MESH_MIN_DIM 2
 #define MESH_MAX_DIM 1024
 #define MESH_MAX_CELL_TRIANGLES 12
@@ -31,8 +29,9 @@
 // the record of a node: mask in bits 0 .. 6, vertex rank in 7 .. 17, triangle rank in 18 .. 29, the cell's activity in 30
 static_assert((MESH_BLOCK - 1) * 7 < (1 << 11), "the vertices in front of a node within its block fit 11 bits");
 static_assert((MESH_BLOCK - 1) * MESH_MAX_CELL_TRIANGLES < (1 << 12), "the triangles in front of a cell within its block fit 12 bits");
-// a chunk holds at most MESH_SCAN_CHUNK * MESH_BLOCK * 12 triangles: both halves of a packed count stay below 2^32
-static_assert((int64_t)MESH_SCAN_CHUNK * MESH_BLOCK * MESH_MAX_CELL_TRIANGLES < 0xFFFFFFFFLL, "sums within a chunk fit 32 bits");
+static_assert(MESH_BLOCK == SCAN_THREADS, "a workgroup of the scan is a workgroup of the stage");
+// a chunk holds at most SCAN_CHUNK * MESH_BLOCK * 12 triangles: both halves of a packed count stay below 2^32
+static_assert((int64_t)SCAN_CHUNK * MESH_BLOCK * MESH_MAX_CELL_TRIANGLES < 0xFFFFFFFFLL, "sums within a chunk fit 32 bits");
 
 MESH_PLAN_HD uint32_t mesh_record(int mask, int vrank, int trank, int active) {
   return (uint32_t)mask | ((uint32_t)vrank << 7) | ((uint32_t)trank << 18) | ((uint32_t)active << 30);
@@ -45,15 +44,13 @@ MESH_PLAN_HD int mesh_record_active(uint32_t r) { return (int)((r >> 30) & 1u); 
 MESH_PLAN_HD int64_t mesh_nodes(int nx, int ny, int nz) { return (int64_t)nx * ny * nz; }
 MESH_PLAN_HD int64_t mesh_node(int i, int j, int k, int nx, int ny) { return ((int64_t)k * ny + j) * nx + i; }
 MESH_PLAN_HD int64_t mesh_blocks(int64_t n_nodes) { return (n_nodes + MESH_BLOCK - 1) / MESH_BLOCK; }
-MESH_PLAN_HD int64_t mesh_scan_chunks(int64_t n_blocks) { return (n_blocks + MESH_SCAN_CHUNK - 1) / MESH_SCAN_CHUNK; }
-MESH_PLAN_HD int64_t mesh_scan_item(int64_t chunk, int tid, int j) { return chunk * MESH_SCAN_CHUNK + (int64_t)tid * MESH_SCAN_ITEMS + j; }
 MESH_PLAN_HD uint64_t mesh_count_pack(uint32_t vertices, uint32_t triangles) { return (uint64_t)vertices | ((uint64_t)triangles << 32); }
 // the first vertex / triangle slot of block b; chunk_base holds two sums per chunk
 MESH_PLAN_HD int64_t mesh_vertex_base(const int64_t* chunk_base, const uint64_t* blk, int64_t b) {
-  return chunk_base[2 * (b / MESH_SCAN_CHUNK)] + (int64_t)(blk[b] & 0xFFFFFFFFull);
+  return scan_base(chunk_base, 2, 0, b, (int64_t)(blk[b] & 0xFFFFFFFFull));
 }
 MESH_PLAN_HD int64_t mesh_triangle_base(const int64_t* chunk_base, const uint64_t* blk, int64_t b) {
-  return chunk_base[2 * (b / MESH_SCAN_CHUNK) + 1] + (int64_t)(blk[b] >> 32);
+  return scan_base(chunk_base, 2, 1, b, (int64_t)(blk[b] >> 32));
 }
 
 // 0 = fine; otherwise an index into MESH_WHY
@@ -83,7 +80,7 @@ inline MeshLayout mesh_layout(int64_t n_nodes) {
   L.flags = off;      off += mesh_align(n_nodes);
   L.record = off;     off += mesh_align(n_nodes * 4);
   L.blk = off;        off += mesh_align(nb * 8);
-  L.chunk_base = off; off += mesh_align(mesh_scan_chunks(nb) * 16);
+  L.chunk_base = off; off += mesh_align(scan_chunks(nb) * 16);
   L.bytes = off + 256;
   return L;
 }

@@ -3,13 +3,14 @@
 // A stream compaction over the nodes, integers only, so the output has one byte pattern:
 //   k_resect_flag      one lane per node: the listing rule; the ballot of each wavefront (one 64-bit word) and the number
 //                      of listed nodes of each workgroup go to the workspace
-//   k_resect_scan      exclusive scan in place of the workgroup sums by one workgroup (as the scan of tracks.hip); the total
+//   k_resect_scan      exclusive scan in place of the workgroup sums by one workgroup (scan_counts of block_scan.h); the total
 //   k_resect_scatter   one lane per node: slot = workgroup offset + popcounts of the ballots of the wavefronts before it
 //                      + popcount of its own ballot below its lane; entries below cap_corr are written
 //   k_resect_segments  one lane per image boundary: seg_ptr[i] = listed nodes below kp_ptr[i], from the same words
 // Nothing is read back between the launches and the stream is not synchronised.
 #include "common.h"
 #include "resection_plan.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -39,48 +40,17 @@ __global__ __launch_bounds__(RESECT_BLOCK) void k_resect_flag(const int64_t* __r
     }
   }
   const unsigned long long word = __ballot(f);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    mask[(int64_t)blockIdx.x * RESECT_WAVES + w] = word;
-    s_w[w] = __popcll(word);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int sum = 0;
-#pragma unroll
-    for (int k = 0; k < RESECT_WAVES; ++k) sum += s_w[k];
-    blk[blockIdx.x] = sum;
-  }
+  if ((threadIdx.x & 63) == 0) mask[(int64_t)blockIdx.x * RESECT_WAVES + (threadIdx.x >> 6)] = word;
+  const int sum = block_flag_count<RESECT_BLOCK>(f, s_w);
+  if (threadIdx.x == 0) blk[blockIdx.x] = sum;
 }
 
 // exclusive scan in place of the n workgroup sums by one workgroup; blk[n] and *total get the sum
-__global__ __launch_bounds__(256) void k_resect_scan(int n, int* __restrict__ blk, int64_t* __restrict__ total) {
-  __shared__ long long s_a[256];
-  const int tid = threadIdx.x;
-  const int per = (n + 255) / 256;
-  const int64_t b0 = (int64_t)tid * per;
-  const int b = (int)(b0 < n ? b0 : n), e = (b + per < n ? b + per : n);
-  long long la = 0;
-  for (int k = b; k < e; ++k) la += blk[k];
-  s_a[tid] = la;
-  __syncthreads();
-  if (tid == 0) {
-    long long ra = 0;
-    for (int k = 0; k < 256; ++k) {
-      const long long va = s_a[k];
-      s_a[k] = ra;
-      ra += va;
-    }
-    blk[n] = (int)ra;
-    *total = ra;
-  }
-  __syncthreads();
-  long long ra = s_a[tid];
-  for (int k = b; k < e; ++k) {
-    const int va = blk[k];
-    blk[k] = (int)ra;
-    ra += va;
-  }
+__global__ __launch_bounds__(256) void k_resect_scan(int n, int* blk, int64_t* __restrict__ total) {
+  __shared__ int64_t s_wave[4];
+  int64_t sum;
+  scan_counts<256>(n, blk, blk, s_wave, &sum);
+  if (threadIdx.x == 0) { blk[n] = (int)sum; *total = sum; }
 }
 
 // listed nodes below node p (0 <= p <= n_nodes), from the scanned workgroup sums and the ballots

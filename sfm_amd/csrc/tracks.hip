@@ -17,6 +17,7 @@
 // Nothing is read back between the launches; the status word counts[4] is read once behind the last one.
 #include "common.h"
 #include "tracks_plan.h"
+#include "block_scan.h"
 
 namespace {
 
@@ -120,27 +121,11 @@ __global__ __launch_bounds__(256) void k_tracks_flatten(int n_nodes, const int* 
 }
 
 // ---------------------------------------------------------------------------------------------------- scans
-// Exclusive scan of a pair of ints per thread over a 256-thread block (s_w: 8 ints); ta / tb = the block's sums.
-__device__ __forceinline__ void block_scan2(int a, int b, int* s_w, int& ea, int& eb, int& ta, int& tb) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int ia = a, ib = b;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int xa = __shfl_up(ia, d), xb = __shfl_up(ib, d);
-    if (lane >= d) { ia += xa; ib += xb; }
-  }
-  __syncthreads();
-  if (lane == 63) { s_w[w] = ia; s_w[4 + w] = ib; }
-  __syncthreads();
-  int oa = 0, ob = 0;
-  ta = 0; tb = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (k < w) { oa += s_w[k]; ob += s_w[4 + k]; }
-    ta += s_w[k]; tb += s_w[4 + k];
-  }
-  ea = oa + ia - a; eb = ob + ib - b;
-}
+// A (flag, length) pair goes through block_exclusive_scan as one 64-bit value, the flag in the low half: a workgroup's
+// flags sum to at most 256 and its lengths to at most n_nodes < 2^31, so neither half leaves its 32 bits.
+__device__ __forceinline__ int64_t pair_pack(int a, int b) { return (int64_t)a | ((int64_t)b << 32); }
+__device__ __forceinline__ int pair_a(int64_t v) { return (int)(v & 0xFFFFFFFFll); }
+__device__ __forceinline__ int pair_b(int64_t v) { return (int)(v >> 32); }
 
 struct tracks_dev {
   int64_t* ctr;
@@ -153,7 +138,7 @@ struct tracks_dev {
 // the pair (flag, length) an item contributes.  MODE 0: item = node, flag = root of a component with >= min_len nodes.
 // MODE 1: item = candidate, flag = kept under the policy.
 template <int MODE>
-__device__ __forceinline__ void scan_item(const tracks_dev& w, int64_t item, int n_nodes, int min_len, int policy, int& a,
+__device__ __forceinline__ void tracks_item(const tracks_dev& w, int64_t item, int n_nodes, int min_len, int policy, int& a,
                                           int& b) {
   a = 0; b = 0;
   if (MODE == 0) {
@@ -167,41 +152,22 @@ __device__ __forceinline__ void scan_item(const tracks_dev& w, int64_t item, int
 
 template <int MODE>
 __global__ __launch_bounds__(256) void k_tracks_scan_reduce(tracks_dev w, int n_nodes, int min_len, int policy) {
-  __shared__ int s_w[8];
-  int a, b, ea, eb, ta, tb;
-  scan_item<MODE>(w, (int64_t)blockIdx.x * 256 + threadIdx.x, n_nodes, min_len, policy, a, b);
-  block_scan2(a, b, s_w, ea, eb, ta, tb);
-  if (threadIdx.x == 0) { w.blk_a[blockIdx.x] = ta; w.blk_b[blockIdx.x] = tb; }
+  __shared__ int64_t s_w[4];
+  int a, b;
+  tracks_item<MODE>(w, (int64_t)blockIdx.x * 256 + threadIdx.x, n_nodes, min_len, policy, a, b);
+  int64_t total;
+  (void)block_exclusive_scan<256, int64_t>(pair_pack(a, b), s_w, &total);
+  if (threadIdx.x == 0) { w.blk_a[blockIdx.x] = pair_a(total); w.blk_b[blockIdx.x] = pair_b(total); }
 }
 
 // exclusive scan in place of the n block sums of both quantities by one workgroup; the totals go to two counters
-__global__ __launch_bounds__(256) void k_tracks_scan_sums(int n, int* __restrict__ blk_a, int* __restrict__ blk_b,
-                                                          int64_t* __restrict__ total_a, int64_t* __restrict__ total_b) {
-  __shared__ long long s_a[256], s_b[256];
-  const int tid = threadIdx.x;
-  const int per = (n + 255) / 256;
-  const int64_t b0 = (int64_t)tid * per;
-  const int b = (int)(b0 < n ? b0 : n), e = (b + per < n ? b + per : n);
-  long long la = 0, lb = 0;
-  for (int k = b; k < e; ++k) { la += blk_a[k]; lb += blk_b[k]; }
-  s_a[tid] = la; s_b[tid] = lb;
-  __syncthreads();
-  if (tid == 0) {
-    long long ra = 0, rb = 0;
-    for (int k = 0; k < 256; ++k) {
-      const long long va = s_a[k], vb = s_b[k];
-      s_a[k] = ra; s_b[k] = rb;
-      ra += va; rb += vb;
-    }
-    *total_a = ra; *total_b = rb;
-  }
-  __syncthreads();
-  long long ra = s_a[tid], rb = s_b[tid];
-  for (int k = b; k < e; ++k) {
-    const int va = blk_a[k], vb = blk_b[k];
-    blk_a[k] = (int)ra; blk_b[k] = (int)rb;
-    ra += va; rb += vb;
-  }
+__global__ __launch_bounds__(256) void k_tracks_scan_sums(int n, int* blk_a, int* blk_b, int64_t* __restrict__ total_a,
+                                                          int64_t* __restrict__ total_b) {
+  __shared__ int64_t s_wave[4];
+  int64_t ta, tb;
+  scan_counts<256>(n, blk_a, blk_a, s_wave, &ta);
+  scan_counts<256>(n, blk_b, blk_b, s_wave, &tb);
+  if (threadIdx.x == 0) { *total_a = ta; *total_b = tb; }
 }
 
 template <int MODE>
@@ -209,12 +175,13 @@ __global__ __launch_bounds__(256) void k_tracks_scan_apply(tracks_dev w, int n_n
                                                            int64_t* __restrict__ track_ptr,
                                                            uint8_t* __restrict__ track_conflict,
                                                            int64_t* __restrict__ counts) {
-  __shared__ int s_w[8];
+  __shared__ int64_t s_w[4];
   const int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  int a, b, ea, eb, ta, tb;
-  scan_item<MODE>(w, item, n_nodes, min_len, policy, a, b);
-  block_scan2(a, b, s_w, ea, eb, ta, tb);
-  const int num = w.blk_a[blockIdx.x] + ea, off = w.blk_b[blockIdx.x] + eb;
+  int a, b;
+  tracks_item<MODE>(w, item, n_nodes, min_len, policy, a, b);
+  int64_t total;
+  const int64_t before = block_exclusive_scan<256, int64_t>(pair_pack(a, b), s_w, &total);
+  const int num = w.blk_a[blockIdx.x] + pair_a(before), off = w.blk_b[blockIdx.x] + pair_b(before);
   if (MODE == 0) {
     if (a) {
       w.cidx[item] = num;

@@ -3,7 +3,7 @@
 //                                    OUT: n records of { int32 valid; float n[3] }
 //   depth_fuse_check fused IN OUT    IN: int64 n, then n records of { double acc[3], nacc[3]; int32 n_views, pad }
 //                                    OUT: n records of { double X[3]; float n[3]; int32 pad }
-//   depth_fuse_check scan SEED       the two-level scan as the kernels walk it (depth_scan_item, chunks, tiles of the top
+//   depth_fuse_check scan SEED       the two-level scan as the kernels walk it (scan_replay.h: scan_item, chunks, tiles of the top
 //                                    level with their carry, depth_scan_base) against a running sum, for block counts
 //                                    around the chunk size and above DEPTH_THREADS chunks; pt_ptr from the views of random
 //                                    batches; the layout; the parameter checks; prints "ok <cases>"
@@ -15,6 +15,7 @@
 
 #include "depth_plan.h"
 #include "depth_rule.h"
+#include "scan_replay.h"
 
 #define REQUIRE(c) do { if (!(c)) { std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); std::exit(1); } } while (0)
 
@@ -50,57 +51,25 @@ static uint64_t rnd() {
   return z ^ (z >> 31);
 }
 
-// the two kernels of the scan on the host: blk holds the counts on entry and the bases within a chunk on return
-static int64_t scan_like_the_device(std::vector<uint32_t>& blk, std::vector<int64_t>& chunk_base) {
-  const int64_t nb = (int64_t)blk.size(), n_chunks = depth_scan_chunks(nb);
-  REQUIRE(n_chunks * DEPTH_SCAN_CHUNK >= nb && (n_chunks == 0 || (n_chunks - 1) * DEPTH_SCAN_CHUNK < nb));
-  chunk_base.assign((size_t)n_chunks, 0);
-  std::vector<char> seen((size_t)nb, 0);
-  for (int64_t c = 0; c < n_chunks; ++c) {                      // k_depth_fuse_scan_chunks: one workgroup per chunk
-    int64_t run = 0;
-    for (int tid = 0; tid < DEPTH_THREADS; ++tid) {             // the exclusive prefix over the threads, in thread order
-      for (int j = 0; j < DEPTH_SCAN_ITEMS; ++j) {
-        const int64_t i = depth_scan_item(c, tid, j);
-        REQUIRE(i >= c * DEPTH_SCAN_CHUNK && i < (c + 1) * DEPTH_SCAN_CHUNK);
-        if (i >= nb) continue;
-        REQUIRE(!seen[(size_t)i]);                             // every count belongs to one thread
-        seen[(size_t)i] = 1;
-        const uint32_t count = blk[(size_t)i];
-        REQUIRE(run <= 0xFFFFFFFFLL);
-        blk[(size_t)i] = (uint32_t)run;
-        run += count;
-      }
-    }
-    chunk_base[(size_t)c] = run;
-  }
-  for (int64_t i = 0; i < nb; ++i) REQUIRE(seen[(size_t)i]);
-  int64_t carry = 0;                                            // k_depth_fuse_scan_top: tiles of DEPTH_THREADS with a carry
-  for (int64_t first = 0; first < n_chunks; first += DEPTH_THREADS) {
-    int64_t total = 0;
-    for (int tid = 0; tid < DEPTH_THREADS; ++tid) {
-      const int64_t i = first + tid;
-      if (i >= n_chunks) continue;
-      const int64_t v = chunk_base[(size_t)i];
-      chunk_base[(size_t)i] = carry + total;
-      total += v;
-    }
-    carry += total;
-  }
-  return carry;
+// k_depth_fuse_scan_chunks and k_depth_fuse_scan_top on the host (the shared replay of scan_replay.h): blk holds the counts
+// on entry and the bases within a chunk on return, chunk_base one sum per chunk; returns the grand total
+static int64_t fuse_scan(std::vector<uint32_t>& blk, std::vector<int64_t>& chunk_base) {
+  scan_replay::chunk_counts(blk, chunk_base);
+  return scan_replay::chunk_totals(chunk_base.data(), (int64_t)chunk_base.size(), 1);
 }
 
 static int check_scan(uint64_t seed) {
   rng_state = seed;
   int cases = 0;
-  const int64_t sizes[] = {0, 1, 2, DEPTH_SCAN_CHUNK - 1, DEPTH_SCAN_CHUNK, DEPTH_SCAN_CHUNK + 1, 3 * DEPTH_SCAN_CHUNK + 7,
-                           (int64_t)DEPTH_THREADS * DEPTH_SCAN_CHUNK + 5, (int64_t)(DEPTH_THREADS + 1) * DEPTH_SCAN_CHUNK + 1};
+  const int64_t sizes[] = {0, 1, 2, SCAN_CHUNK - 1, SCAN_CHUNK, SCAN_CHUNK + 1, 3 * SCAN_CHUNK + 7,
+                           (int64_t)DEPTH_THREADS * SCAN_CHUNK + 5, (int64_t)(DEPTH_THREADS + 1) * SCAN_CHUNK + 1};
   for (int64_t nb : sizes) {
     for (int full = 0; full < 2; ++full) {
       std::vector<uint32_t> blk((size_t)nb), counts;
       for (auto& c : blk) c = full ? DEPTH_PIXEL_BLOCK : (uint32_t)(rnd() % (DEPTH_PIXEL_BLOCK + 1));
       counts = blk;
       std::vector<int64_t> chunk_base;
-      const int64_t total = scan_like_the_device(blk, chunk_base);
+      const int64_t total = fuse_scan(blk, chunk_base);
       int64_t run = 0;
       for (int64_t b = 0; b < nb; ++b) {
         REQUIRE(depth_scan_base(chunk_base.data(), blk.data(), b) == run);
@@ -143,7 +112,7 @@ static int check_scan(uint64_t seed) {
       }
       want[(size_t)r + 1] = want[(size_t)r] + owners;
     }
-    const int64_t total = scan_like_the_device(blk, chunk_base);
+    const int64_t total = fuse_scan(blk, chunk_base);
     for (int r = 0; r <= n_ref; ++r) {
       const int64_t b = p.views[(size_t)r].pix_block_first;
       REQUIRE((b < p.n_pix_blocks ? depth_scan_base(chunk_base.data(), blk.data(), b) : total) == want[(size_t)r]);
@@ -153,7 +122,7 @@ static int check_scan(uint64_t seed) {
     const DepthFuseLayout most = depth_fuse_layout(n_img, n_ref, 0, depth_max_pixel_blocks(p.n_out, n_ref));
     REQUIRE(L.blk >= L.tables.bytes && L.blk % 256 == 0 && L.chunk_base % 256 == 0);
     REQUIRE(L.chunk_base >= L.blk + p.n_pix_blocks * 4);
-    REQUIRE(L.bytes >= L.chunk_base + depth_scan_chunks(p.n_pix_blocks) * 8 && most.bytes >= L.bytes);
+    REQUIRE(L.bytes >= L.chunk_base + scan_chunks(p.n_pix_blocks) * 8 && most.bytes >= L.bytes);
     ++cases;
   }
   const double nan = std::nan("");

@@ -20,6 +20,7 @@
 #include "mesh_plan.h"
 #include "mesh_rule.h"
 #include "tsdf_rule.h"
+#include "scan_replay.h"
 
 #define REQUIRE(c) do { if (!(c)) { std::fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); std::exit(1); } } while (0)
 
@@ -134,46 +135,18 @@ static uint64_t rnd() {
   return z ^ (z >> 31);
 }
 
-// the two kernels of the scan on the host: blk holds the packed counts on entry and the packed sums within a chunk on
-// return, chunk_base two sums per chunk; totals[2] is what k_mesh_scan_top writes to counts
-static void scan_like_the_device(std::vector<uint64_t>& blk, std::vector<int64_t>& chunk_base, int64_t* totals) {
-  const int64_t nb = (int64_t)blk.size(), n_chunks = mesh_scan_chunks(nb);
-  REQUIRE(n_chunks * MESH_SCAN_CHUNK >= nb && (n_chunks == 0 || (n_chunks - 1) * MESH_SCAN_CHUNK < nb));
+// k_mesh_scan_chunks and k_mesh_scan_top on the host (the shared replay of scan_replay.h): blk holds the packed counts on
+// entry and the packed sums within a chunk on return, chunk_base two sums per chunk; totals[2] is what goes to counts
+static void mesh_scan(std::vector<uint64_t>& blk, std::vector<int64_t>& chunk_base, int64_t* totals) {
+  std::vector<int64_t> packed;
+  scan_replay::chunk_counts(blk, packed);
+  const int64_t n_chunks = (int64_t)packed.size();
   chunk_base.assign((size_t)n_chunks * 2, 0);
-  std::vector<char> seen((size_t)nb, 0);
   for (int64_t c = 0; c < n_chunks; ++c) {
-    uint64_t run = 0;
-    for (int tid = 0; tid < MESH_BLOCK; ++tid)
-      for (int j = 0; j < MESH_SCAN_ITEMS; ++j) {
-        const int64_t i = mesh_scan_item(c, tid, j);
-        REQUIRE(i >= c * MESH_SCAN_CHUNK && i < (c + 1) * MESH_SCAN_CHUNK);
-        if (i >= nb) continue;
-        REQUIRE(!seen[(size_t)i]);
-        seen[(size_t)i] = 1;
-        const uint64_t count = blk[(size_t)i];
-        blk[(size_t)i] = run;
-        REQUIRE((run & 0xFFFFFFFFull) + (count & 0xFFFFFFFFull) <= 0xFFFFFFFFull);      // the low half never carries into the high one
-        run += count;
-      }
-    chunk_base[(size_t)(2 * c)] = (int64_t)(run & 0xFFFFFFFFull);
-    chunk_base[(size_t)(2 * c + 1)] = (int64_t)(run >> 32);
+    chunk_base[(size_t)(2 * c)] = packed[(size_t)c] & 0xFFFFFFFFll;
+    chunk_base[(size_t)(2 * c + 1)] = packed[(size_t)c] >> 32;
   }
-  for (int64_t i = 0; i < nb; ++i) REQUIRE(seen[(size_t)i]);
-  for (int half = 0; half < 2; ++half) {
-    int64_t carry = 0;
-    for (int64_t first = 0; first < n_chunks; first += MESH_BLOCK) {
-      int64_t total = 0;
-      for (int tid = 0; tid < MESH_BLOCK; ++tid) {
-        const int64_t i = first + tid;
-        if (i >= n_chunks) continue;
-        const int64_t v = chunk_base[(size_t)(2 * i + half)];
-        chunk_base[(size_t)(2 * i + half)] = carry + total;
-        total += v;
-      }
-      carry += total;
-    }
-    totals[half] = carry;
-  }
+  for (int half = 0; half < 2; ++half) totals[half] = scan_replay::chunk_totals(chunk_base.data() + half, n_chunks, 2);
 }
 
 static int check_plan(uint64_t seed) {
@@ -210,7 +183,7 @@ static int check_plan(uint64_t seed) {
       }
       std::vector<int64_t> chunk_base;
       int64_t totals[2];
-      scan_like_the_device(blk, chunk_base, totals);
+      mesh_scan(blk, chunk_base, totals);
       int64_t nv = 0, nt = 0;
       for (int64_t i = 0; i < n; ++i) {
         const int64_t b = i / MESH_BLOCK;
@@ -223,13 +196,13 @@ static int check_plan(uint64_t seed) {
       // the layout: nothing overlaps, all inside
       const MeshLayout L = mesh_layout(n);
       REQUIRE(L.flags == 0 && L.record >= n && L.record % 256 == 0 && L.blk >= L.record + n * 4 && L.blk % 256 == 0);
-      REQUIRE(L.chunk_base >= L.blk + nb * 8 && L.chunk_base % 256 == 0 && L.bytes >= L.chunk_base + mesh_scan_chunks(nb) * 16);
+      REQUIRE(L.chunk_base >= L.blk + nb * 8 && L.chunk_base % 256 == 0 && L.bytes >= L.chunk_base + scan_chunks(nb) * 16);
       ++cases;
     }
   }
   // per block: block counts around the chunk size and above MESH_BLOCK chunks
-  const int64_t sizes[] = {1, MESH_SCAN_CHUNK - 1, MESH_SCAN_CHUNK, MESH_SCAN_CHUNK + 1, 3 * MESH_SCAN_CHUNK + 7,
-                           (int64_t)MESH_BLOCK * MESH_SCAN_CHUNK + 5, (int64_t)(MESH_BLOCK + 1) * MESH_SCAN_CHUNK + 1};
+  const int64_t sizes[] = {1, SCAN_CHUNK - 1, SCAN_CHUNK, SCAN_CHUNK + 1, 3 * SCAN_CHUNK + 7,
+                           (int64_t)MESH_BLOCK * SCAN_CHUNK + 5, (int64_t)(MESH_BLOCK + 1) * SCAN_CHUNK + 1};
   for (int64_t nb : sizes) {
     for (int full = 0; full < 2; ++full) {
       std::vector<uint64_t> blk((size_t)nb), counts;
@@ -239,7 +212,7 @@ static int check_plan(uint64_t seed) {
       counts = blk;
       std::vector<int64_t> chunk_base;
       int64_t totals[2], nv = 0, nt = 0;
-      scan_like_the_device(blk, chunk_base, totals);
+      mesh_scan(blk, chunk_base, totals);
       for (int64_t b = 0; b < nb; ++b) {
         REQUIRE(mesh_vertex_base(chunk_base.data(), blk.data(), b) == nv && mesh_triangle_base(chunk_base.data(), blk.data(), b) == nt);
         nv += (int64_t)(counts[(size_t)b] & 0xFFFFFFFFull);

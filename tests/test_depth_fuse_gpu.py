@@ -102,9 +102,11 @@ def test_nan_warp_and_source_behind_the_camera(gpu_ready):
 
 
 def test_the_same_call_twice_and_a_batch_of_many_blocks(gpu_ready):
-    """96 x 72 is 27 blocks a view: more than one block per view and blocks whose owners start in the middle of the output."""
+    """300 x 300 is 352 blocks a view and 1,053 in the batch: more than one chunk of 1,024 block counts for the two-level
+    scan, more than one block per view and blocks whose owners start in the middle of the output."""
     rng = np.random.default_rng(75)
-    shapes = ((72, 96), (70, 95), (60, 100))
+    shapes = ((300, 300), (296, 301), (290, 310))
+    assert sum(-(-h * w // 256) for h, w in shapes) > 1024
     refs, sources = all_to_all(3)
     case = plane_case(rng, shapes, refs, sources, ("random", "checker", "ones"))
     a, want = assert_equal_to_reference(case, what="many blocks")

@@ -25,7 +25,10 @@ def pixels(rng, n, dup_from=None, frac=0.5, jitter=1.5):
     return p
 
 
-@pytest.mark.parametrize("T,M,seed", [(1, 1, 0), (7, 300, 1), (256, 256, 2), (257, 513, 3), (3000, 229, 4), (5000, 4000, 5)])
+# the last three: 256, 257 and 514 row blocks for the one-workgroup scan of the block counts (a count per thread, empty
+# runs at the end, a ragged last run)
+@pytest.mark.parametrize("T,M,seed", [(1, 1, 0), (7, 300, 1), (256, 256, 2), (257, 513, 3), (3000, 229, 4), (5000, 4000, 5),
+                                      (65536, 40, 6), (65537, 40, 7), (131329, 24, 8)])
 def test_associate_matches_oracle(gpu_ready, T, M, seed):
     from oracle import driver_oracle as do
     from sfm_amd import driver

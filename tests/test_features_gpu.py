@@ -83,6 +83,19 @@ def test_batch_against_the_reference(gpu_ready, edge):
     assert out["desc"].shape == (int(out["kp_ptr"][-1]), 32) and out["desc"].dtype == np.uint8
 
 
+def test_a_batch_of_more_rows_than_one_piece_of_the_row_scan(gpu_ready):
+    """69 images of 64 x 64 and one of 300 x 64: 4,716 image rows, so the one workgroup that scans the row counts walks a
+    second piece of 4,096 with its carry, and the tie scan of the tall image a second tile of 256 rows; the quota cuts
+    into the tied scores of most images."""
+    images = [fr.make_scene(64, 64, seed=100 + i) for i in range(69)]
+    images.insert(40, fr.make_scene(300, 64, seed=7, noise=20, levels=8))
+    assert sum(a.shape[0] for a in images) > 4096
+    for mf in (0, 4):
+        refs = [fr.detect_and_describe(a, default_tables()[1], edge=16, max_features=mf) for a in images]
+        assert sum(len(r["xy"]) for r in refs) > 100 and len(refs[40]["xy"]) > 0
+        assert_matches_reference(device(images, edge=16, max_features=mf), refs, mf)
+
+
 def test_threshold_is_honoured(gpu_ready):
     img = batch()[1]
     for threshold in (1, 60, 254):

@@ -132,6 +132,17 @@ def test_sizes_around_every_tile_constant(gpu_ready, edge_images, metric, dim):
     assert sum(len(w[0]) for w in want) > 50
 
 
+def test_one_pair_of_65537_queries(gpu_ready):
+    """65,537 queries against 8 train keypoints: 257 blocks of output rows, so the one workgroup that scans the block counts
+    gives two counts to a thread and leaves the last threads without any; about a third of the rows are kept."""
+    rng = np.random.default_rng(5)
+    nq = 256 * 256 + 1
+    kps = [(rng.uniform(0, 1, (n, 2)) * [1024, 768]).astype(np.float32) for n in (nq, 8)]
+    descs = [rng.integers(0, 256, (n, 32), dtype=np.uint8) for n in (nq, 8)]
+    want, nc = check(kps, descs, [(0, 1)], [gr.scene_a()["F"]], "hamming", gate=60.0, ratio=0.9, cross_check=False)
+    assert 0.2 * nq < len(want[0][0]) < 0.5 * nq
+
+
 def test_candidate_counts_drain_the_queue_zero_one_and_several_times(gpu_ready):
     """Queries with exactly 0, 1, 2, 63, 64, 65, 127, 128, 129 and 200 candidates: under a sideways translation the rule is
     |y1 - y2| <= gate, so the train keypoints of one image row are one query's candidates; they are scattered over two LDS

@@ -128,6 +128,24 @@ def test_ratio_boundary_is_strict(gpu_ready):
     assert (qi.tolist(), ti.tolist(), d.tolist()) == ([0], [0], [2.0])
 
 
+@pytest.mark.parametrize("nq", [1, 255, 256, 257, 65536, 65537, 131329])
+def test_ratio_filter_compaction_at_the_scan_seams(gpu_ready, nq):
+    """sfm_match_ratio alone on synthetic (idx1, d1, d2): 1 block, 256 and 257 blocks (one count per scanning thread, then
+    two with empty runs at the end) and 514 blocks (a ragged last run), with about half the rows kept, all and none."""
+    import torch
+    from sfm_amd import matcher
+    rng = np.random.default_rng(nq)
+    idx1 = rng.integers(0, 1 << 20, nq).astype(np.int32)
+    d2 = rng.uniform(1.0, 500.0, nq).astype(np.float32)
+    for kind in ("half", "all", "none"):
+        d1 = {"half": d2 * rng.uniform(0.5, 1.0, nq).astype(np.float32), "all": d2 * np.float32(0.5), "none": d2.copy()}[kind]
+        keep = np.nonzero(d1.astype(np.float64) < 0.75 * d2.astype(np.float64))[0]
+        assert len(keep) == {"all": nq, "none": 0}.get(kind, len(keep)) and (kind != "half" or nq < 255 or 0 < len(keep) < nq)
+        q, t, d = matcher.ratio_filter(torch.from_numpy(idx1).cuda(), torch.from_numpy(d1).cuda(), torch.from_numpy(d2).cuda(), 0.75)
+        assert np.array_equal(q.cpu().numpy(), keep.astype(np.int32)), (kind, nq)
+        assert np.array_equal(t.cpu().numpy(), idx1[keep]) and np.array_equal(d.cpu().numpy(), d1[keep]), (kind, nq)
+
+
 def far_apart_sets(nq, nt, dim, seed):
     """Every pair far apart AND closely spaced: three quarters of the bytes are 0 (query) against 255 (train),
     the rest differ by 0..2, so all d^2 sit within ~100 of 0.75 * dim * 255^2 (6.2e6 at dim 128, above 2^22),

@@ -188,6 +188,16 @@ def test_100000_two_node_components(gpu_ready):
     assert device(g, 3, "drop")["counts"].tolist() == [0, 0, 0, 0] and (device(g, 3, "drop")["node_track"] == -2).all()
 
 
+@pytest.mark.parametrize("n", [65536, 65537, 131329])
+def test_node_blocks_around_the_scan_of_the_block_sums(gpu_ready, n):
+    """256, 257 and 514 workgroups of nodes for the one workgroup that scans their sums (a sum per thread, then two with
+    the last threads empty, then a ragged last run): two-node components, and one node left over where n is odd."""
+    n2 = n // 2
+    g = tr.pack([n - n2, n2], [(0, 1)], [(np.arange(n2), np.random.default_rng(n).permutation(n2))])
+    out = check(g, n, policies=("drop",))
+    assert out["counts"].tolist() == [n2, 2 * n2, 0, 0] and int((out["node_track"] == -1).sum()) == n % 2
+
+
 @pytest.mark.parametrize("n_edges", [63, 64, 65, 255, 256, 257])
 def test_edge_counts_around_wavefronts_and_workgroups(gpu_ready, n_edges):
     rng = np.random.default_rng(n_edges)

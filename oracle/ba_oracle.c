@@ -77,7 +77,7 @@ static double huber_row(double f, double* scale, double* ft) {
   double z = f * f;
   if (z <= 1.0) { *scale = 1.0; *ft = f; return z; }
   double sz = sqrt(z);
-  *scale = SQRT_EPS_D; *ft = f * (1.0 / sz) / SQRT_EPS_D;
+  *scale = SQRT_EPS_D; *ft = f * 0.0 + copysign(1.0 / SQRT_EPS_D, f);   /* f rho1 = sign(f) exactly: +-2^26, as the kernel's huber_row */
   return 2.0 * sz - 1.0;
 }
 static double huber_rho0(double f) { double z = f * f; return z <= 1.0 ? z : 2.0 * sqrt(z) - 1.0; }

@@ -297,9 +297,9 @@ class Linearization:
 
 def linearize(x, prob):
     f, Jc, Jp, Jreg = jacobian_blocks(x, prob)
-    scale, rho1 = robust_row_scale(f)
+    scale, _ = robust_row_scale(f)
     N, C, P, d = prob.n_obs, prob.n_cams, prob.n_pts, prob.d
-    gf = (rho1 * f)                                       # gradient weights per row
+    gf = np.where(f * f <= 1.0, f, np.sign(f))            # gradient weights per row: rho1 f, exactly sign(f) on a Huber-linear row
     s_obs = scale[:2 * N].reshape(N, 2)
     gf_obs = gf[:2 * N].reshape(N, 2)
     g_c = np.zeros((C, d)); g_p = np.zeros((P, 3))

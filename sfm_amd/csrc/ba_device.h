@@ -107,10 +107,11 @@ __device__ __forceinline__ double huber_row(double f, double& scale, double& ft)
   double z = f * f;
   if (z <= 1.0) { scale = 1.0; ft = f; return z; }
   double sz = sqrt(z);
-  double rho1 = 1.0 / sz;
   // rho1 + 2*rho2*z with rho2 = -0.5 z^-1.5 is 0 up to rounding -> clamped to EPS
   scale = SQRT_EPS_D;
-  ft = f * rho1 / SQRT_EPS_D;
+  // f rho1 = f / |f| is sign(f): taken as such, ft = +-2^26 exactly.  (f * (1.0 / sz) rounds to 1 - 2^-53 for about one f in
+  // seven.)  f * 0.0 adds nothing to a finite f and keeps a non-finite one poisoning the gradient as the product did.
+  ft = f * 0.0 + copysign(1.0 / SQRT_EPS_D, f);
   return 2.0 * sz - 1.0;
 }
 __device__ __forceinline__ double huber_rho0(double f) {

@@ -17,7 +17,7 @@
 //      changes no sign and is not found: such a sample is at the edge between two counts of real roots anyway.
 //      A polynomial with a non-finite coefficient, a zero leading one or a non-finite bound gives no model.
 //   7. per root (x, y, w) = the cross product of two rows of B(z): of the pairs (k,l), (k,m), (l,m) the one with the
-//      largest |w|, the first on a tie; w == 0 gives no candidate.  (x, y, z) then take two Gauss-Newton steps on the
+//      largest |w|, the first on a tie; w == 0 gives no candidate.  (x, y, z) then take three Gauss-Newton steps on the
 //      nine cubic constraints themselves (polish() says why).  E = xX + yY + zZ + W, scaled to |E|_F = sqrt(2), the
 //      entry of largest magnitude (the first on a tie) positive.
 //
@@ -386,15 +386,15 @@ SFM_HD void combine(const double (&Bs)[4][9], double x, double y, double z, doub
 }
 
 // The root of the degree-10 polynomial carries the rounding of the elimination behind it, and (x, y) that of B(z): on
-// real pairs the two singular values of E = xX + yY + zZ + W then differ by up to 1e-8.  Two Gauss-Newton steps on the
+// real pairs the two singular values of E = xX + yY + zZ + W then differ by up to 1e-8.  Three Gauss-Newton steps on the
 // nine cubic constraints in (x, y, z) - inside the null space, so the five epipolar constraints stay exact - take that
-// out.  The Jacobian along a basis matrix D is (D E^T + E D^T - tr(D E^T)) E + (E E^T - tr(E E^T) / 2) D.  A step is
+// out (two leave a candidate in 600 at 1e-10 where 1e-14 is there to be had: tests/solver_truth.py).  The Jacobian along a basis matrix D is (D E^T + E D^T - tr(D E^T)) E + (E E^T - tr(E E^T) / 2) D.  A step is
 // kept only if it is finite and lowers |f|^2.
 SFM_HD void polish(const double (&Bs)[4][9], double& x, double& y, double& z) {
   double E[9], L[9], f[9];
   combine(Bs, x, y, z, E);
   double r2 = cubic_residual(E, L, f);
-  for (int it = 0; it < 2; ++it) {
+  for (int it = 0; it < 3; ++it) {
     double J[3][9];
 #pragma unroll
     for (int v = 0; v < 3; ++v) {

@@ -67,7 +67,11 @@ __global__ __launch_bounds__(256) void k_pnp_hypotheses(const int64_t* __restric
   int64_t b; int M;
   seg_range(seg_ptr, s, n, b, M);
   if (M < 4) {                                           // uniform over the workgroup
-    if (active) { hyp_count[slot] = 0; hyp_cand[slot] = 0; }
+    if (active) {
+      hyp_count[slot] = 0; hyp_cand[slot] = 0;
+#pragma unroll
+      for (int e = 0; e < 48; ++e) cand_Rt[slot * 48 + e] = 0.0;         // "no model", as the other stages leave it
+    }
     return;
   }
   const auto [fx, fy, cx, cy] = load_k4(Kseg, s);

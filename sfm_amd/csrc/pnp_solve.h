@@ -148,9 +148,15 @@ SFM_HD int solve(const double (&P)[3][3], const double (&f)[3][3], double (&Rt)[
       double r0 = 0.0, r1 = 0.0, r2 = 0.0;
 #pragma unroll
       for (int it = 0; it < 3; ++it) {                      // the last pass only evaluates the residuals
-        r0 = l0 * l0 + l1 * l1 - 2.0 * b01 * l0 * l1 - a01;
-        r1 = l0 * l0 + l2 * l2 - 2.0 * b02 * l0 * l2 - a02;
-        r2 = l1 * l1 + l2 * l2 - 2.0 * b12 * l1 * l2 - a12;
+        // |l_i f_i - l_j f_j|^2 - a_ij from the difference vectors: l_i^2 + l_j^2 - 2 b_ij l_i l_j cancels from the
+        // size of the squared depths down to that of the squared side, and the depths inherit that loss
+        double q01 = 0.0, q02 = 0.0, q12 = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const double u0 = l0 * f[0][k], u1 = l1 * f[1][k], u2 = l2 * f[2][k];
+          q01 += (u0 - u1) * (u0 - u1); q02 += (u0 - u2) * (u0 - u2); q12 += (u1 - u2) * (u1 - u2);
+        }
+        r0 = q01 - a01; r1 = q02 - a02; r2 = q12 - a12;
         if (it == 2) break;
         const double j00 = 2.0 * (l0 - b01 * l1), j01 = 2.0 * (l1 - b01 * l0);
         const double j10 = 2.0 * (l0 - b02 * l2), j12 = 2.0 * (l2 - b02 * l0);

@@ -83,6 +83,43 @@ def _polyval(c, z):
     return acc
 
 
+def _cubic(E):
+    """(E E^T - tr(E E^T) / 2) E for E [...,3,3]: the nine cubic constraints, halved."""
+    L = E @ np.swapaxes(E, -1, -2)
+    L = L - 0.5 * np.trace(L, axis1=-2, axis2=-1)[..., None, None] * np.eye(3)
+    return L @ E, L
+
+
+def polish(basis, x, y, z, steps=4):
+    """Step 7's Gauss-Newton on the nine cubic constraints in (x, y, z), inside the null space: basis [H,4,9], x, y, z
+    [H,R].  By np.linalg.pinv of the 9 x 3 Jacobian, all candidates at once; a candidate keeps a step only if it is
+    finite and lowers |f|^2.  Without it the roots carry the rounding of the elimination and of the companion matrix
+    (errors of 1e-7 to 1e-12 in E, measured against tests/solver_truth.py), which the kernel's polish takes out."""
+    B = basis.reshape(-1, 1, 4, 3, 3)
+    q = np.stack([x, y, z], -1)
+    with np.errstate(all="ignore"):
+        for _ in range(steps):
+            E = (q[..., None, None] * B[:, :, :3]).sum(2) + B[:, :, 3]
+            f, L = _cubic(E)
+            J = []
+            for v in range(3):
+                D = np.broadcast_to(B[:, :, v], E.shape)
+                S = D @ np.swapaxes(E, -1, -2)
+                S = S + np.swapaxes(S, -1, -2)
+                S = S - 0.5 * np.trace(S, axis1=-2, axis2=-1)[..., None, None] * np.eye(3)
+                J.append((S @ E + L @ D).reshape(E.shape[:-2] + (9,)))
+            J = np.stack(J, -1)                                          # [H,R,9,3]
+            ok = np.isfinite(J).all(axis=(-1, -2)) & np.isfinite(f).all(axis=(-1, -2))
+            step = np.zeros_like(q)
+            if ok.any():
+                step[ok] = (np.linalg.pinv(J[ok]) @ f[ok].reshape(-1, 9, 1))[..., 0]
+            qn = q - step
+            fn, _ = _cubic((qn[..., None, None] * B[:, :, :3]).sum(2) + B[:, :, 3])
+            better = ok & ((fn * fn).sum(axis=(-1, -2)) < (f * f).sum(axis=(-1, -2)))
+            q = np.where(better[..., None], qn, q)
+    return q[..., 0], q[..., 1], q[..., 2]
+
+
 def from_basis(basis):
     """Steps 4 to 7: basis [H,4,9] (X, Y, Z, W) -> E [H,10,3,3] (slot = ascending real root; scaled()) and valid [H,10]."""
     H = basis.shape[0]
@@ -144,6 +181,7 @@ def from_basis(basis):
     xyw = np.take_along_axis(cr, pick[..., None, None], 2)[:, :, 0]
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         x, y = xyw[..., 0] / xyw[..., 2], xyw[..., 1] / xyw[..., 2]
+        x, y, z = polish(basis, x, y, z)
         E = (x[..., None] * basis[:, None, 0] + y[..., None] * basis[:, None, 1] + z[..., None] * basis[:, None, 2]
              + basis[:, None, 3])
         E = scaled(E)

@@ -990,7 +990,8 @@ int sfm_depth_fuse_gather(sfm_handle h, const int64_t* img_off /* host */, const
  *   n = (m1 - m0) x (m2 - m0) and D = |I| * sum(outside offsets) - |O| * sum(inside offsets), all integers and n . D never
  *   0, the second and third vertex are exchanged iff n . D < 0: the normal of a triangle points from inside to outside.
  *   Zero-area triangles (a node that holds exactly 0) are kept.  mesh_rule.h has the 6 x 16 cases as a table.
- *   Limits: no colour or texture, no hole filling; about 2.3 x the triangles of marching cubes.
+ *   Limits: no texture (per-vertex colours come from sfm_mesh_colors below), no hole filling; about 2.3 x the triangles of
+ *   marching cubes.
  * Two calls.  sfm_mesh_mark writes counts (device int64 [2]: vertices, triangles) and leaves in the workspace
  *    (sfm_mesh_workspace_bytes) per node its flags and one record - the 7-bit vertex mask, the node's first vertex slot and
  *    the cell's first triangle slot relative to its block of 256 nodes, the cell's activity - and the first slots of every
@@ -1013,6 +1014,47 @@ int sfm_mesh_mark(sfm_handle h, const float* tsdf, const uint16_t* weight, int32
 int sfm_mesh_emit(sfm_handle h, const float* tsdf, int32_t nx, int32_t ny, int32_t nz, const double* origin /* host [3] */,
                   double voxel, int64_t n_vertices, int64_t n_triangles, double* vertices, float* normals,
                   int32_t* triangles, void* workspace, int64_t workspace_bytes);
+
+/* ---- colours of the mesh: per vertex a blend over the views that see it (sfm_amd/csrc/mesh_color.hip,
+ *      mesh_color_rule.h, mesh_color_plan.h) ----
+ * A pure function of its inputs: float64 without FMA contraction, no visit order, no atomics, no randomness, so NumPy
+ * reproduces every output byte (tests/mesh_color_reference.py).
+ * Inputs.  The vertex X (float64 [3]) and its normal n (float32 [3], widened to double) as sfm_mesh_emit wrote them.  The
+ *   views in the layout of sfm_tsdf_integrate: heights / widths per image and ref_image per view (HOST), proj (device,
+ *   float64 [n_ref][12]), depth (float32) and keep (uint8, or NULL: every finite depth counts) back to back at out_off[r].
+ *   centres (device, float64 [n_ref][3]): the camera centres.  pixels (device, uint8 [n_out][channels]): the views' images
+ *   back to back in the layout of depth, channels interleaved, channels 1 or 3, their order untouched.
+ * Per vertex acc_k = 0, W = 0, m = 0, best = -1, bw = 0, then the views in position order:
+ *   1. q_i, u = q0 / q2, v = q1 / q2, validity and the nearest pixel (yi, xi) as in sfm_tsdf_integrate; skipped unless
+ *      valid (a NaN vertex never is).
+ *   2. ds = the float32 depth at (yi, xi) widened; skipped unless ds is finite and keep there != 0; d = ds - q2; skipped
+ *      unless d >= -tol && d <= tol.  This is the occlusion test: the view's own depth map says that it sees this surface
+ *      and not one in front of it.
+ *   3. g_a = C_a - X_a, l2 = (g0 g0 + g1 g1) + g2 g2; skipped unless l2 is finite and > 0.  c = 1 when n is all zeros,
+ *      otherwise c = ((n0 g0 + n1 g1) + n2 g2) / sqrt(l2); skipped unless c >= min_cos (false on NaN).  wgt = c * c.
+ *   4. Bilinear sample at (u, v): x0 = floor(u), fx = u - x0, the columns clamp((int)x0, 0, w - 1) and
+ *      clamp((int)x0 + 1, 0, w - 1), the rows likewise from v with fy.  With the four pixel values of channel k widened to
+ *      double as a, b (upper row) and e, f (lower row): top = a + fx * (b - a), bot = e + fx * (f - e),
+ *      s_k = top + fy * (bot - top).
+ *   5. acc_k = acc_k + wgt * s_k;  W = W + wgt;  m = m + 1;  if wgt > bw then bw = wgt and best = v (ties go to the
+ *      earlier view).
+ * After the views colors[k] = (uint8) min(floor(acc_k / W + 0.5), 255) when m > 0 && W > 0, otherwise fill;
+ *   n_views = min(m, 255) (uint8); best_view = best (int32, -1 for none).  colors is uint8 [n_vertices][channels].
+ * Limits: no texture atlas, no exposure compensation; a vertex that no view sees gets fill and is not filled from its
+ *   neighbours; every view that passes weighs by its angle only.
+ * The workspace (sfm_mesh_colors_workspace_bytes) holds the view table.  Nothing is written at or above n_vertices, and
+ *   the call returns at once for n_vertices == 0.  SFM_ERR_ARG before any device work for a null handle, what
+ *   sfm_tsdf_integrate refuses about the views, channels not 1 or 3, n_vertices below 0 or above 2^31 - 1, tol not finite or
+ *   below 0, min_cos not finite, not > 0 or above 1, fill outside 0 .. 255, a null pointer (keep excepted; depth / pixels
+ *   may be null only when there is no pixel, vertices / normals / the outputs only when n_vertices is 0), or a workspace
+ *   that is missing or too small.  No kernel reads outside a map or an image. */
+int sfm_mesh_colors_workspace_bytes(int32_t n_ref, int64_t* bytes_host);
+int sfm_mesh_colors(sfm_handle h, const int32_t* heights /* host */, const int32_t* widths /* host */, int32_t n_img,
+                    int32_t n_ref, const int32_t* ref_image /* host */, const double* proj /* device [n_ref][12] */,
+                    const double* centres /* device [n_ref][3] */, const float* depth, const uint8_t* keep /* or NULL */,
+                    const uint8_t* pixels, int32_t channels, int64_t n_vertices, const double* vertices, const float* normals,
+                    double tol, double min_cos, int32_t fill, uint8_t* colors, uint8_t* n_views, int32_t* best_view,
+                    void* workspace, int64_t workspace_bytes);
 
 #ifdef __cplusplus
 }

@@ -12,4 +12,4 @@ from .interchange import read_pnm, save_ply_mesh, save_ply_points, write_pnm  # 
 from .guided import guided_match_pairs  # noqa: F401
 from .depth import (DepthMaps, FusedCloud, dense_from_reconstruction, depth_maps, depth_maps_from_arrays, depth_ranges, plane_depths, select_sources,  # noqa: F401
                     view_backprojection, view_warps)
-from .mesh import Mesh, TsdfVolume, tsdf_volume_from_arrays  # noqa: F401
+from .mesh import Mesh, TsdfVolume, mesh_vertex_colors, tsdf_volume_from_arrays  # noqa: F401

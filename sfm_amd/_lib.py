@@ -179,6 +179,8 @@ SIGNATURES = {
     "sfm_mesh_workspace_bytes": (C.c_int, [i32, i32, i32, C.POINTER(i64)]),
     "sfm_mesh_mark": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, vp, i64]),
     "sfm_mesh_emit": (C.c_int, [vp, vp, i32, i32, i32, vp, f64, i64, i64, vp, vp, vp, vp, i64]),
+    "sfm_mesh_colors_workspace_bytes": (C.c_int, [i32, C.POINTER(i64)]),
+    "sfm_mesh_colors": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i64, vp, vp, f64, f64, i32, vp, vp, vp, vp, i64]),
 }
 
 _lib = None

@@ -502,7 +502,8 @@ def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=2
     `.point_cloud`.  images: one per image position of rec.tracks.  Returns (points, index, DepthMaps) - or (points, index,
     colours, DepthMaps) with colors.  With fuse=True the last step is `.fuse()` in place of `.point_cloud`, and the result
     is (FusedCloud, DepthMaps); the colours are then `FusedCloud.colors(colors)`.  With mesh=True the surface of the kept
-    pixels, `maps.tsdf().mesh()`, is appended to whichever of those is returned."""
+    pixels, `maps.tsdf().mesh()`, is appended to whichever of those is returned; with colors (uint8 images) it is coloured
+    by `Mesh.colors(colors)`."""
     n_img = len(rec.tracks.kp_ptr) - 1
     if len(images) != n_img:
         raise ValueError(f"{len(images)} images for {n_img} image positions")
@@ -516,6 +517,8 @@ def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=2
     maps = depth_maps(images, rec.K, rec.poses, src, planes, radius, device)
     maps.filter(rel_tol, max_cost, min_consistent)
     surface = (maps.tsdf().mesh(),) if mesh else ()
+    if mesh and colors is not None:
+        surface[0].colors(colors)
     if fuse:
         return (maps.fuse(), maps) + surface
     return maps.point_cloud(colors) + (maps,) + surface

@@ -2,7 +2,8 @@
 distance volume from filtered depth maps, `sfm_mesh_mark` / `sfm_mesh_emit` (sfm_amd/csrc/mesh.hip) turn its zero level into
 a triangle mesh by marching tetrahedra; include/sfm_amd.h states both rules completely.  Every view weighs the same, a pixel
 without a depth carries no evidence (free space outside every silhouette stays unknown and the mesh is open there), holes
-are not filled and zero-area triangles are kept.  No CPU fallback: without the library or a GPU the calls raise.
+are not filled and zero-area triangles are kept.  `sfm_mesh_colors` (sfm_amd/csrc/mesh_color.hip) gives every vertex a colour
+blended over the views whose own depth maps see it.  No CPU fallback: without the library or a GPU the calls raise.
 """
 from __future__ import annotations
 
@@ -37,12 +38,15 @@ class Mesh:
     (node index, direction) order, normals float32 [nv,3] (unit, pointing to the outside; zeros where the gradient has no
     length), triangles int32 [nt,3] in (cell index, tetrahedron) order, their normals pointing from inside to outside."""
 
-    def __init__(self, state, n_vertices, n_triangles):
+    def __init__(self, state, n_vertices, n_triangles, volume=None):
         self._m = state
         self.n_vertices, self.n_triangles = int(n_vertices), int(n_triangles)
+        self._volume = volume                                      # for the defaults of colors(): its truncation, its maps
         self._host = {}
 
     def _get(self, name, n):
+        if name not in self._m:
+            return None
         if name not in self._host:
             self._host[name] = self._m[name].cpu().numpy()[:n]
         return self._host[name]
@@ -50,10 +54,52 @@ class Mesh:
     vertices = property(lambda self: self._get("vertices", self.n_vertices))
     normals = property(lambda self: self._get("normals", self.n_vertices))
     triangles = property(lambda self: self._get("triangles", self.n_triangles))
+    # after colors(): uint8 [nv] or [nv,3], uint8 [nv] (the views blended, at most 255), int32 [nv] (-1: no view); None before
+    vertex_colors = property(lambda self: self._get("vertex_colors", self.n_vertices))
+    n_views = property(lambda self: self._get("n_views", self.n_vertices))
+    best_view = property(lambda self: self._get("best_view", self.n_vertices))
+
+    def colors(self, images, maps=None, tol=None, min_cos=0.35, fill=0):
+        """A colour per vertex on the device (`sfm_mesh_colors`; include/sfm_amd.h states the rule): the vertex is projected
+        into every view, a view counts when its own depth at the nearest pixel is within tol of the vertex's depth and the
+        cosine between the vertex normal and the direction to the camera is at least min_cos, and the bilinear samples of
+        the views that count are blended with the weight cos^2.  images: one [h,w] or [h,w,3] uint8 array per IMAGE of the
+        set, all with the same channel count, each shaped like its view's maps, channel order untouched; maps: a filtered
+        `DepthMaps`, None for those the mesh's volume was integrated from; tol: None for the truncation of the volume
+        (3 voxels); fill: the colour of a vertex that no view sees.  Returns uint8 [nv] or [nv,3] and fills vertex_colors,
+        n_views and best_view (the position of the view with the largest weight, -1 for none)."""
+        maps = getattr(self._volume, "_maps", None) if maps is None else maps
+        if maps is None:
+            raise ValueError("colors() needs maps: the mesh's volume was not built by DepthMaps.tsdf()")
+        if getattr(maps, "keep", None) is None:
+            raise ValueError("colors() needs filter() first")
+        if tol is None:
+            vol = self._volume
+            if vol is None:
+                raise ValueError("colors() needs tol: the mesh has no volume")
+            tol = getattr(vol, "trunc", 3.0 * vol.voxel)
+        check_color_scalars(tol, min_cos, fill)
+        s = maps._s
+        if len(images) != len(s["imgs"]):
+            raise ValueError("images: one array per image of the set")
+        flat, channels = check_color_images([images[r] for r in maps.views], maps.shapes)
+        import torch
+        dev = self._m["vertices"].device
+        n_ref = len(maps.views)
+        backproj = s["backproj"].cpu().numpy()[:n_ref].reshape(-1, 3, 4)
+        proj = projections_from_backprojections(backproj)
+        centres = np.ascontiguousarray(backproj[:, :, 3])
+        out = _colors(dev, s["heights"], s["widths"], s["ref_image"], proj, centres, s["depth"], s["keep"], torch.from_numpy(flat).to(dev),
+                      channels, self.n_vertices, self._m["vertices"], self._m["normals"], tol, min_cos, fill)
+        self._m.update(out)
+        for name in ("vertex_colors", "n_views", "best_view"):
+            self._host.pop(name, None)
+        return self.vertex_colors
 
     def save(self, path, colors=None):
-        """Binary PLY with normals (`save_ply_mesh`)."""
+        """Binary PLY with normals (`save_ply_mesh`); colors: None for vertex_colors when `colors()` has made them."""
         from .interchange import save_ply_mesh
+        colors = self.vertex_colors if colors is None else colors
         save_ply_mesh(self.vertices, self.triangles, path, normals=self.normals, colors=colors)
 
 
@@ -104,7 +150,7 @@ class TsdfVolume:
         h.call("sfm_mesh_emit", dp(self._tsdf), nx, ny, nz, C.c_void_p(origin.ctypes.data), C.c_double(self.voxel), nv, nt,
                dp(m["vertices"]), dp(m["normals"]), dp(m["triangles"]), dp(ws), need.value)
         m["ws"] = ws                                               # alive until the outputs are: the emit call may still run
-        return Mesh(m, nv, nt)
+        return Mesh(m, nv, nt, self)
 
 
 def tsdf_volume_from_arrays(tsdf, weight, origin, voxel, device=0):
@@ -178,6 +224,7 @@ def integrate_depth_maps(maps, origin=None, voxel=None, shape=None, resolution=2
     proj = projections_from_backprojections(s["backproj"].cpu().numpy()[:n_ref])
     vol = _integrate(s["depth"].device, s["heights"], s["widths"], s["ref_image"], proj, s["depth"], s["keep"], origin, voxel, shape, trunc)
     vol.min_weight = int(min_weight)
+    vol._maps = maps                                               # what Mesh.colors() projects into by default
     return vol
 
 
@@ -227,3 +274,90 @@ def tsdf_volume_from_depth_arrays(proj, depth, keep, origin, voxel, shape, trunc
     widths = np.array([d.shape[1] for d in depth], dtype=np.int32)
     return _integrate(dev, heights, widths, np.arange(len(depth), dtype=np.int32), proj, up(depth, np.float32),
                       None if keep is None else up(keep, np.uint8), origin, voxel, shape, trunc)
+
+
+# ------------------------------------------------------------------------------------------- colours
+def check_color_scalars(tol, min_cos, fill):
+    if not (isinstance(tol, Real) and np.isfinite(tol) and tol >= 0):
+        raise ValueError("tol must be a finite number >= 0")
+    if not (isinstance(min_cos, Real) and np.isfinite(min_cos) and 0 < min_cos <= 1):
+        raise ValueError("min_cos must be a number > 0 and <= 1")
+    if not (isinstance(fill, (int, np.integer)) and 0 <= fill <= 255):
+        raise ValueError("fill must be an integer 0 .. 255")
+
+
+def check_color_images(images, shapes):
+    """(the views' pixels back to back as uint8 [n_out * channels + 1], channels) from one uint8 [h,w] or [h,w,3] array per
+    VIEW, shaped like shapes; ValueError says what is wrong."""
+    arrays = [np.asarray(a) for a in images]
+    if len(arrays) != len(shapes):
+        raise ValueError("images: one array per view")
+    tails = {a.shape[2:] for a in arrays if a.ndim in (2, 3)}
+    if any(a.ndim not in (2, 3) for a in arrays) or len(tails) > 1 or (tails and next(iter(tails)) not in ((), (3,))):
+        raise ValueError("images must all be [h,w] or all be [h,w,3]")
+    if any(a.dtype != np.uint8 for a in arrays):
+        raise ValueError("images must be uint8")
+    for v, (a, sh) in enumerate(zip(arrays, shapes)):
+        if a.shape[:2] != tuple(sh):
+            raise ValueError(f"view {v}: the image must have the shape of its maps, {tuple(sh)}")
+    channels = 3 if tails and next(iter(tails)) == (3,) else 1
+    flat = np.concatenate([a.reshape(-1) for a in arrays] + [np.zeros(1, np.uint8)])          # one element more: a pointer must exist
+    return np.ascontiguousarray(flat), channels
+
+
+def _colors(dev, heights, widths, ref_image, proj, centres, d_depth, d_keep, d_pixels, channels, n_vertices, d_vertices, d_normals,
+            tol, min_cos, fill):
+    """The device call: heights / widths (int32 per image), ref_image (int32 per view), proj [n_ref,12] and centres [n_ref,3]
+    on the host; the maps, the pixels, the vertices and the normals on the device (d_keep may be None)."""
+    import torch
+    h = _lib.get_handle(dev.index)
+    n_ref, n_img = len(ref_image), len(heights)
+    table = lambda a, k: (torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, k)).to(dev) if n_ref
+                          else torch.zeros((1, k), dtype=torch.float64, device=dev))
+    d_proj, d_centres = table(proj, 12), table(centres, 3)
+    need = C.c_int64()
+    h.check(h.lib.sfm_mesh_colors_workspace_bytes(n_ref, C.byref(need)), "sfm_mesh_colors_workspace_bytes")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    n = max(int(n_vertices), 1)
+    out = {"vertex_colors": torch.empty(n if channels == 1 else (n, 3), dtype=torch.uint8, device=dev),
+           "n_views": torch.empty(n, dtype=torch.uint8, device=dev), "best_view": torch.empty(n, dtype=torch.int32, device=dev)}
+    dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    h.call("sfm_mesh_colors", hp(heights), hp(widths), n_img, n_ref, hp(ref_image), dp(d_proj), dp(d_centres), dp(d_depth), dp(d_keep),
+           dp(d_pixels), int(channels), int(n_vertices), dp(d_vertices), dp(d_normals), C.c_double(float(tol)), C.c_double(float(min_cos)),
+           int(fill), dp(out["vertex_colors"]), dp(out["n_views"]), dp(out["best_view"]), dp(ws), need.value)
+    out["colors_ws"] = (ws, d_proj, d_centres, d_depth, d_keep, d_pixels)      # alive while the call may still run
+    return out
+
+
+def mesh_vertex_colors(vertices, normals, proj, centres, depth, keep, images, tol, min_cos=0.35, fill=0, device=0):
+    """`sfm_mesh_colors` on arrays that were made elsewhere: vertices float64 [nv,3], normals float32 [nv,3], proj float64
+    [n,12] (row-major [K R | K t]), centres float64 [n,3], depth one float32 [h,w] per view, keep one uint8 [h,w] per view or
+    None (every finite depth counts), images one uint8 [h,w] or [h,w,3] per VIEW.  Returns (colors uint8 [nv] or [nv,3],
+    n_views uint8 [nv], best_view int32 [nv])."""
+    import torch
+    check_color_scalars(tol, min_cos, fill)
+    vertices = np.ascontiguousarray(vertices, dtype=np.float64)
+    normals = np.ascontiguousarray(normals, dtype=np.float32)
+    if vertices.ndim != 2 or vertices.shape[1] != 3 or normals.shape != vertices.shape:
+        raise ValueError("vertices and normals must be [nv,3]")
+    depth = [np.ascontiguousarray(d, dtype=np.float32) for d in depth]
+    if any(d.ndim != 2 for d in depth) or np.shape(proj) != (len(depth), 12) or np.shape(centres) != (len(depth), 3) or len(depth) > MAX_VIEWS:
+        raise ValueError(f"depth: at most {MAX_VIEWS} [h,w] maps; proj: 12 numbers and centres: 3 numbers for each")
+    if keep is not None and [np.shape(k) for k in keep] != [d.shape for d in depth]:
+        raise ValueError("keep must be None or one [h,w] array per view, shaped like its depth map")
+    flat, channels = check_color_images(images, [d.shape for d in depth])
+    _lib.get_handle(device)
+    dev = torch.device("cuda", device)
+
+    def up(arrays, dtype):
+        return torch.from_numpy(np.concatenate([np.asarray(a, dtype=dtype).reshape(-1) for a in arrays] + [np.zeros(1, dtype)])).to(dev)
+
+    pad = lambda a: np.concatenate([a, np.zeros((1, 3), a.dtype)])           # one row more: a pointer must exist
+    heights = np.array([d.shape[0] for d in depth], dtype=np.int32)
+    widths = np.array([d.shape[1] for d in depth], dtype=np.int32)
+    nv = len(vertices)
+    out = _colors(dev, heights, widths, np.arange(len(depth), dtype=np.int32), proj, centres, up(depth, np.float32),
+                  None if keep is None else up(keep, np.uint8), torch.from_numpy(flat).to(dev), channels, nv,
+                  torch.from_numpy(pad(vertices)).to(dev), torch.from_numpy(pad(normals)).to(dev), tol, min_cos, fill)
+    return tuple(out[name].cpu().numpy()[:nv] for name in ("vertex_colors", "n_views", "best_view"))

@@ -995,7 +995,8 @@ def measure_depth(reps=20, emit=None, mesh=False):
     outputs, beside the compaction they replace: torch.nonzero + gather as in DepthMaps.point_cloud().  In the same run
     sfm_features_detect + sfm_features_describe on the same images, as a known quantity.  With mesh=True also the surface
     of the same run: sfm_tsdf_integrate of the 36 filtered maps into 256^3 nodes (a cube around the kept pixels, truncation 3
-    voxels), sfm_mesh_mark and sfm_mesh_emit (min_weight 1), whole calls by HIP events; the row is then named "mesh"."""
+    voxels), sfm_mesh_mark and sfm_mesh_emit (min_weight 1), then sfm_mesh_colors of that mesh from the 36 views (BGR, tol 3
+    voxels, min_cos 0.35) with its vertex-view projections per second, whole calls by HIP events; the row is then named "mesh"."""
     import torch
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from depth_reference import make_scene
@@ -1118,15 +1119,33 @@ def measure_depth(reps=20, emit=None, mesh=False):
             h.call("sfm_mesh_emit", _p(tsdf), nx, ny, nz, hp(origin), C.c_double(voxel), nv, nt, _p(vertices), _p(vnormals), _p(triangles),
                    _p(mesh_ws), mesh_need)
         run_mesh_emit()
+        # the colours of the same mesh: BGR images (the gray ones in three channels), the defaults of Mesh.colors
+        d_bgr = d_img[:, None].expand(-1, 3).contiguous()
+        d_centres = torch.from_numpy(np.ascontiguousarray(np.asarray(backproj).reshape(-1, 3, 4)[:, :, 3])).to(dev)
+        h.check(h.lib.sfm_mesh_colors_workspace_bytes(n_img, C.byref(need)), "sfm_mesh_colors_workspace_bytes")
+        colors_need = need.value
+        colors_ws = torch.empty(colors_need, dtype=torch.uint8, device=dev)
+        vcolors = torch.empty((max(nv, 1), 3), dtype=torch.uint8, device=dev)
+        vviews = torch.empty(max(nv, 1), dtype=torch.uint8, device=dev)
+        vbest = torch.empty(max(nv, 1), dtype=torch.int32, device=dev)
+
+        def run_mesh_colors():
+            h.call("sfm_mesh_colors", hp(heights), hp(widths), n_img, n_img, hp(ref_image), _p(d_proj), _p(d_centres), _p(depth), _p(keep),
+                   _p(d_bgr), 3, nv, _p(vertices), _p(vnormals), C.c_double(3.0 * voxel), C.c_double(0.35), 0, _p(vcolors), _p(vviews),
+                   _p(vbest), _p(colors_ws), colors_need)
+        run_mesh_colors()
         zv = vertices[:nv, 2].cpu().numpy()
         seen = int((weight != 0).sum().item())
         row.update({"grid_nodes": [nx, ny, nz], "voxel": float(voxel), "nodes_seen": seen, "projections": nx * ny * nz * n_img,
                     "mesh_vertices": nv, "mesh_triangles": nt,
                     "share_of_vertices_within_one_voxel_of_a_plane": float((np.minimum(np.abs(zv - sc.z_front), np.abs(zv - sc.z_back)) <= voxel).mean()) if nv else 0.0,
                     "ms_tsdf_integrate": timed(run_integrate, reps) * 1e3, "ms_mesh_mark": timed(run_mesh_mark, reps) * 1e3,
-                    "ms_mesh_emit": timed(run_mesh_emit, reps) * 1e3})
+                    "ms_mesh_emit": timed(run_mesh_emit, reps) * 1e3, "ms_mesh_colors": timed(run_mesh_colors, reps) * 1e3,
+                    "color_projections": nv * n_img, "share_of_vertices_with_a_view": float((vviews[:nv] != 0).float().mean().item()) if nv else 0.0,
+                    "mean_views_per_vertex": float(vviews[:nv].float().mean().item()) if nv else 0.0})
         row["projections_per_s"] = row["projections"] / (row["ms_tsdf_integrate"] * 1e-3)
-        del tsdf, weight, vertices, vnormals, triangles, mesh_ws
+        row["color_projections_per_s"] = row["color_projections"] / (row["ms_mesh_colors"] * 1e-3)
+        del tsdf, weight, vertices, vnormals, triangles, mesh_ws, d_bgr, vcolors, vviews, vbest, colors_ws
     # the known quantity beside it: the feature stage on the same images
     threshold, edge, max_features = 20, 31, 10000
     h.check(h.lib.sfm_features_workspace_bytes(n_img, hp(off), C.byref(need)), "sfm_features_workspace_bytes")

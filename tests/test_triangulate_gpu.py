@@ -6,6 +6,9 @@ from its np.longdouble run on the same inputs and allows the device 100 times th
 of operations; the 80-bit run stands in for the exact value).  The reference's side of that pair on the parity scene of 2,000
 tracks (largest relative deviation, float64 against 80-bit): refine_iters=0: X 2.0e-15, max_err 5.1e-11; refine_iters=5: X 9.1e-15,
 max_err 1.8e-11.  Every test prints both sides of its pair.
+
+This is parity with a restatement: a weakness of the algorithm itself passes, because the reference has it too.  The sharper
+statement - the device against a 60-digit truth of the problem, on scenes beyond this arc - is tests/test_geometry_truth_gpu.py.
 """
 import functools
 

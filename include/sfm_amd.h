@@ -829,6 +829,76 @@ int sfm_features_describe(sfm_handle h, const uint8_t* images, const int64_t* im
                           uint8_t* desc /* uint8 [n_kp][32] */, uint8_t* blurred_out /* may be NULL */, void* workspace,
                           int64_t workspace_bytes);
 
+/* ---- multi-scale features: an image pyramid in front of detect and describe (sfm_amd/csrc/features_pyramid.hip,
+ * features_pyramid_plan.h) ----
+ * The two calls above take a batch of images of different sizes, so a pyramid is such a batch with n_img * n_levels
+ * entries, and they run on it unchanged.  The calls here build that batch and join the keypoints of an image's levels
+ * into one list in level-0 coordinates under one max_features budget.  Every byte is integer arithmetic (the coordinate
+ * map is one double division, rounded once); the outputs are the same from run to run and do not depend on the launch
+ * geometry or on the other images of the batch.
+ *
+ * Scale and levels: the scale is a rational num / den with den < num <= 2 den, num <= 16 and 8 num >= 9 den (default
+ *   6/5); 2 <= n_levels <= 16.
+ * Level sizes, chained, heights and widths alike: n_l = max(1, (2 n_{l-1} den + num) / (2 num)) in integer division (the
+ *   half-up rounding of n_{l-1} den / num); a side of 0 stays 0.  n_l <= n_{l-1} always, and a side of at least 33
+ *   strictly shrinks; a small side may repeat - such an image is not eligible for keypoints anyway.
+ * Level batch: image-major; slot i * n_levels + l holds level l of image i in exactly h_l * w_l bytes, the slots back to
+ *   back from offset 0 (lvl_off ascends).  Level 0 is a copy of the image; its mask a copy of the mask.
+ * Resampling level l from level l - 1: for the destination pixel x of a row of wd pixels over a source row of ws, in int64
+ *   ux = (2x + 1) ws - wd,  x0 = ux / (2 wd),  fx = ((ux % (2 wd)) * 256) / (2 wd),  x1 = min(x0 + 1, ws - 1); the same in
+ *   y.  The value is ((256-fx)(256-fy) I[y0,x0] + fx (256-fy) I[y0,x1] + (256-fx) fy I[y1,x0] + fx fy I[y1,x1] + 32768)
+ *   >> 16: pixel-centre aligned, 8-bit weights, exact in int32, rounded once.
+ * Masks: the mask of a level is 1 exactly where all four of those source mask pixels are > 0, else 0 - whatever their
+ *   weights.  Conservative: a keypoint of a coarse level never sits on a pixel that drew on a masked one.
+ * Each level is detected and described by the rule above, with the call's threshold, edge and pattern.
+ * Joining: the keypoints of image i are those of its levels in (level ascending, row-major) order - the segment
+ *   lvl_kp_ptr[i n_levels] .. lvl_kp_ptr[(i + 1) n_levels] of the level batch's list.  With max_features = M > 0 and more
+ *   than M of them the cut is the one above, over the union: the score s with #(score > s) < M <= #(score >= s) from a
+ *   256-bin histogram; all above s stay, of those equal to s the first M - #(score > s) in that order.  Nothing is
+ *   sorted; the survivors keep their order.  The level batch may be detected with the same M per level first: a keypoint
+ *   in the union's top M is in its level's top M, and both tie rules take prefixes of the same order, so the result is
+ *   the same.
+ * Outputs per kept keypoint: xy float32 in level-0 pixels, X = ((double)(2x + 1) * (double)w0) / (double)(2 w_l) - 0.5 and
+ *   Y likewise with the heights, without FMA contraction, rounded once to float32 - exactly (x, y) at level 0; level
+ *   uint8; score, angle_bin and desc copied; src int32, its index in the level batch's keypoint list.
+ * Limits: a keypoint of level l is located to about (num/den)^l / 2 pixels of level 0; one global score cut, not a quota
+ *   per level; the levels are chained bilinear resamplings, not area averages, and each is blurred by the fixed 7-tap rule.
+ *
+ * sfm_features_pyramid_sizes (host only): the tables of the level batch - lvl_off int64 [n_img n_levels + 1], lvl_heights
+ *   / lvl_widths int32 [n_img n_levels] - which go straight into sfm_features_workspace_bytes / _detect / _describe with
+ *   n_img n_levels images.  SFM_ERR_ARG for an option out of range, a negative size or more than 2^32 pixels.
+ * sfm_features_pyramid: builds the level batch into lvl_images (and lvl_masks; NULL iff masks is NULL) on the handle's
+ *   stream: one launch copies level 0, then one launch per level (and one more for the masks) resamples level l from
+ *   level l - 1.  img_off / heights / widths are HOST arrays as above.  No kernel reads outside an image or writes outside
+ *   a level's slot.  The workspace holds the tile table.
+ * sfm_features_merge_count: from lvl_kp_ptr (device, what detect wrote for the level batch) and lvl_score (what describe
+ *   wrote), writes kp_ptr (device int64 [n_img+1]) on the stream.  The caller reads kp_ptr[n_img] back - one more
+ *   read-back, as between detect and describe.
+ * sfm_features_merge_gather: with the same workspace, untouched since merge_count, writes xy float32 [n_kp][2], level,
+ *   score, angle_bin, desc [n_kp][32] (4-byte aligned) and src; nothing at or beyond n_kp.  lvl_heights / lvl_widths are
+ *   the HOST tables of sfm_features_pyramid_sizes.
+ * SFM_ERR_ARG before any device work, with the rule's text in sfm_last_error, for a null handle, an option out of range,
+ * a null pointer, masks without lvl_masks or the reverse, or a workspace that is too small. */
+int sfm_features_pyramid_sizes(int32_t n_img, const int32_t* heights, const int32_t* widths, int32_t n_levels, int32_t num,
+                               int32_t den, int64_t* lvl_off /* [n_img n_levels + 1] */, int32_t* lvl_heights,
+                               int32_t* lvl_widths);
+int sfm_features_pyramid_workspace_bytes(int32_t n_img, int32_t n_levels, int64_t* bytes_host);
+int sfm_features_pyramid(sfm_handle h, const uint8_t* images, const uint8_t* masks /* may be NULL */,
+                         const int64_t* img_off /* host */, const int32_t* heights /* host */,
+                         const int32_t* widths /* host */, int32_t n_img, int32_t n_levels, int32_t num, int32_t den,
+                         uint8_t* lvl_images, uint8_t* lvl_masks /* NULL iff masks is */, void* workspace,
+                         int64_t workspace_bytes);
+int sfm_features_merge_workspace_bytes(int32_t n_img, int32_t n_levels, int64_t* bytes_host);
+int sfm_features_merge_count(sfm_handle h, const int64_t* lvl_kp_ptr /* device [n_img n_levels + 1] */,
+                             const uint8_t* lvl_score, int32_t n_img, int32_t n_levels, int32_t max_features,
+                             int64_t* kp_ptr /* device int64 [n_img+1] */, void* workspace, int64_t workspace_bytes);
+int sfm_features_merge_gather(sfm_handle h, const int64_t* lvl_kp_ptr, const int32_t* lvl_xy, const uint8_t* lvl_score,
+                              const uint8_t* lvl_angle_bin, const uint8_t* lvl_desc, const int32_t* lvl_heights /* host */,
+                              const int32_t* lvl_widths /* host */, int32_t n_img, int32_t n_levels,
+                              const int64_t* kp_ptr /* device */, int64_t n_kp, float* xy /* float32 [n_kp][2] */,
+                              uint8_t* level, uint8_t* score, uint8_t* angle_bin, uint8_t* desc /* uint8 [n_kp][32] */,
+                              int32_t* src, void* workspace, int64_t workspace_bytes);
+
 /* ---- dense depth maps by plane-sweep stereo (sfm_amd/csrc/depth.hip, depth_rule.h, depth_plan.h) ----
  * From n_img gray uint8 images in the layout of sfm_features_detect (one device buffer, img_off [n_img+1] int64, heights /
  * widths [n_img] int32 as HOST arrays), registered cameras and a list of plane depths per reference view: per reference

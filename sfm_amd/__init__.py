@@ -7,7 +7,7 @@ from .pose import InitialPairMixin, recover_pose, recover_pose_batched  # noqa: 
 from .tracks import Tracks, build_tracks, tracks_from_pair_files  # noqa: F401
 from .triangulate import Triangulation, triangulate_tracks, triangulate_tracks_raw  # noqa: F401
 from .incremental import Reconstruction, classify_tracks, evaluate_tracks, reconstruct_tracks, resection_lists  # noqa: F401
-from .features import Features, detect_and_describe_batched, detect_features  # noqa: F401
+from .features import Features, PyramidFeatures, detect_and_describe_batched, detect_features, pyramid_levels  # noqa: F401
 from .interchange import read_pnm, save_ply_mesh, save_ply_points, write_pnm  # noqa: F401
 from .guided import guided_match_pairs  # noqa: F401
 from .depth import (DepthMaps, FusedCloud, dense_from_reconstruction, depth_maps, depth_maps_from_arrays, depth_ranges, plane_depths, select_sources,  # noqa: F401

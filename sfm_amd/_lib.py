@@ -167,7 +167,13 @@ SIGNATURES = {
     "sfm_features_workspace_bytes": (C.c_int, [i32, vp, C.POINTER(i64)]),
     "sfm_features_detect": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i64]),
     "sfm_features_describe": (C.c_int, [vp, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64]),
-    "sfm_depth_workspace_bytes": (C.c_int, [i32, i32, i64, C.POINTER(i64)]),
+    "sfm_features_pyramid_sizes": (C.c_int, [i32, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "sfm_features_pyramid_workspace_bytes": (C.c_int, [i32, i32, C.POINTER(i64)]),
+    "sfm_features_pyramid": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i64]),
+    "sfm_features_merge_workspace_bytes": (C.c_int, [i32, i32, C.POINTER(i64)]),
+    "sfm_features_merge_count": (C.c_int, [vp, vp, vp, i32, i32, i32, vp, vp, i64]),
+    "sfm_features_merge_gather": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_depth_workspace_bytes":(C.c_int, [i32, i32, i64, C.POINTER(i64)]),
     "sfm_depth_census": (C.c_int, [vp, vp, vp, vp, vp, i32, vp, vp, i64]),
     "sfm_depth_sweep": (C.c_int, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i64]),
     "sfm_depth_filter": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f64, i32, vp, vp, vp, vp, i64]),

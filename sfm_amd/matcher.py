@@ -468,19 +468,22 @@ class ImageMatcher(VerificationMixin, FundamentalMixin):
                       "n_unguided": len(results[s]["matches"])}
         return out
 
-    def detect_features(self, image, mask=None):
+    def detect_features(self, image, mask=None, n_levels=1, scale=(6, 5)):
         """detect_features of the reference (find_matches.py:74-139) for one image on the device: (keypoints [n,2] float32,
-        descriptors uint8 [n,32] or None); see sfm_amd.features for the detector, the descriptor and what differs from ORB."""
+        descriptors uint8 [n,32] or None); see sfm_amd.features for the detector, the descriptor and what differs from ORB.
+        n_levels > 1: over a pyramid of that many levels at scale = (num, den), keypoints in pixels of the image."""
         from .features import detect_features
-        return detect_features(image, mask, device=self.device)
+        return detect_features(image, mask, device=self.device, n_levels=n_levels, scale=scale)
 
-    def process_images(self, images, pairs, masks=None, min_matches=5, guided=False, homography=False, **guided_options):
+    def process_images(self, images, pairs, masks=None, min_matches=5, guided=False, homography=False, n_levels=1,
+                       scale=(6, 5), **guided_options):
         """From pixel arrays to verified pairs: detect_and_describe_batched over all images, then process_pairs with the
-        Hamming metric.  Returns (features, results): one sfm_amd.features.Features per image and what
+        Hamming metric.  Returns (features, results): one sfm_amd.features.Features per image (PyramidFeatures with
+        n_levels > 1: the multi-scale stage, which keeps images matching across a change of distance) and what
         process_pairs([f.xy ...], [f.descriptors ...], pairs) gives; `self.build_tracks([f.xy for f in features], pairs,
         results)` joins them into Tracks.  guided / guided_options / homography: as in process_pairs."""
         from .features import detect_and_describe_batched
-        feats = detect_and_describe_batched(images, masks, device=self.device)
+        feats = detect_and_describe_batched(images, masks, device=self.device, n_levels=n_levels, scale=scale)
         metric, self.metric = self.metric, "hamming"
         try:
             results = self.process_pairs([f.xy for f in feats], [f.descriptors for f in feats], pairs, min_matches, guided=guided,

@@ -8,7 +8,7 @@ triangulation of the tracks, the resection lists, the gate evaluation and the in
 feature detection / description stage in front of them all, and the dense-depth stage behind them.  Prints one JSON line per kernel.  bench.py calls measure() and, in its cpu_baseline leg, hands in the NumPy oracle's
 functions to time on a bounded sample of the same inputs (this tool itself never imports oracle/).
 usage: python tools/bench_driver.py [--reps 20] [--fundamental-only | --essential-only | --homography-only | --pnp-only | --pose-only | --tracks-only | --triangulate-only |
-       --incremental-only | --features-only | --guided-only | --depth-only | --mesh-only]"""
+       --incremental-only | --features-only | --pyramid-only | --guided-only | --depth-only | --mesh-only]"""
 import argparse
 import ctypes as C
 import json
@@ -911,6 +911,106 @@ def measure_features(reps=20, emit=None):
     return [row]
 
 
+def measure_features_pyramid(reps=20, emit=None):
+    """The multi-scale feature stage beside the single-scale one in the same run: the 36 synthetic 1600 x 1200 images of
+    measure_features, 8 levels at 6/5, threshold 20, max_features 10,000, inputs resident in HBM.  Device time by HIP events
+    around `reps` calls after 3 warm-up calls, per image: sfm_features_pyramid, detect + describe on the level batch, the
+    two merge calls, their sum, and the ratio of that sum to sfm_features_detect + sfm_features_describe on the 36 images
+    alone (the yardstick); beside them the pixel ratio of the level batch to the images, which is what detect + describe
+    are expected to scale by.  Not part of measure(): only `--pyramid-only` runs it."""
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from features_reference import make_scene
+    from sfm_amd import _lib, features
+    from sfm_amd.driver import _p
+    h = _lib.get_handle(0)
+    dev = torch.device("cuda", 0)
+    H, W, n_img, threshold, edge, max_features, n_levels, num, den = 1200, 1600, 36, 20, 31, 10000, 8, 6, 5
+    imgs = [make_scene(H, W, seed=100 + k) for k in range(n_img)]
+    off = np.arange(n_img + 1, dtype=np.int64) * (H * W)
+    heights, widths = np.full(n_img, H, np.int32), np.full(n_img, W, np.int32)
+    d_img = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).to(dev)
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    rot = features._rot_table(None, 0)
+    e = lambda *shape, dt=torch.uint8: torch.empty(shape, dtype=dt, device=dev)
+
+    def stage(images, offs, hs, ws, n):
+        """(detect, describe, kp_ptr, n_kp, outputs) of the single-scale calls on a batch"""
+        need = C.c_int64()
+        h.check(h.lib.sfm_features_workspace_bytes(n, hp(offs), C.byref(need)), "sfm_features_workspace_bytes")
+        wsp, kp_ptr = e(need.value), e(n + 1, dt=torch.int64)
+
+        def detect():
+            h.call("sfm_features_detect", _p(images), None, hp(offs), hp(hs), hp(ws), n, threshold, edge, max_features,
+                   _p(kp_ptr), _p(wsp), need.value)
+        detect()
+        n_kp = int(kp_ptr.cpu().numpy()[-1])
+        o = (e(n_kp, 2, dt=torch.int32), e(n_kp), e(n_kp), e(n_kp, 32))
+
+        def describe():
+            h.call("sfm_features_describe", _p(images), hp(offs), hp(hs), hp(ws), n, _p(kp_ptr), n_kp, _p(rot), _p(o[0]),
+                   _p(o[1]), _p(o[2]), _p(o[3]), None, _p(wsp), need.value)
+        return detect, describe, kp_ptr, n_kp, o
+
+    n_slot = n_img * n_levels
+    lvl_off, lvl_h, lvl_w = np.zeros(n_slot + 1, np.int64), np.zeros(n_slot, np.int32), np.zeros(n_slot, np.int32)
+    h.check(h.lib.sfm_features_pyramid_sizes(n_img, hp(heights), hp(widths), n_levels, num, den, hp(lvl_off), hp(lvl_h),
+                                             hp(lvl_w)), "sfm_features_pyramid_sizes")
+    need = C.c_int64()
+    h.check(h.lib.sfm_features_pyramid_workspace_bytes(n_img, n_levels, C.byref(need)), "sfm_features_pyramid_workspace_bytes")
+    pws, lvl_images = e(need.value), e(int(lvl_off[-1]))
+
+    def pyramid():
+        h.call("sfm_features_pyramid", _p(d_img), None, hp(off), hp(heights), hp(widths), n_img, n_levels, num, den,
+               _p(lvl_images), None, _p(pws), need.value)
+    pyramid()
+    one_detect, one_describe, _, n_one, _ = stage(d_img, off, heights, widths, n_img)
+    lvl_detect, lvl_describe, lvl_kp_ptr, n_lvl, lo = stage(lvl_images, lvl_off, lvl_h, lvl_w, n_slot)
+    lvl_describe()
+    mneed = C.c_int64()
+    h.check(h.lib.sfm_features_merge_workspace_bytes(n_img, n_levels, C.byref(mneed)), "sfm_features_merge_workspace_bytes")
+    mws, kp_ptr = e(mneed.value), e(n_img + 1, dt=torch.int64)
+
+    def count():
+        h.call("sfm_features_merge_count", _p(lvl_kp_ptr), _p(lo[1]), n_img, n_levels, max_features, _p(kp_ptr), _p(mws),
+               mneed.value)
+    count()
+    kp = kp_ptr.cpu().numpy()
+    n = int(kp[-1])
+    xy, level, score, abin = e(n, 2, dt=torch.float32), e(n), e(n), e(n)
+    desc, src = e(n, 32), e(n, dt=torch.int32)
+
+    def merge():
+        count()
+        h.call("sfm_features_merge_gather", _p(lvl_kp_ptr), _p(lo[0]), _p(lo[1]), _p(lo[2]), _p(lo[3]), hp(lvl_h), hp(lvl_w),
+               n_img, n_levels, _p(kp_ptr), n, _p(xy), _p(level), _p(score), _p(abin), _p(desc), _p(src), _p(mws), mneed.value)
+
+    def lvl_both():
+        lvl_detect(); lvl_describe()
+
+    def one_both():
+        one_detect(); one_describe()
+    for _ in range(3):
+        pyramid(); lvl_both(); merge(); one_both()
+    per = lambda fn: timed(fn, reps) * 1e3 / n_img
+    row = {"kernel": "features_pyramid", "images": n_img, "height": H, "width": W, "n_levels": n_levels, "scale": [num, den],
+           "threshold": threshold, "edge": edge, "max_features": max_features, "reps": reps,
+           "keypoints_single_scale": n_one, "keypoints_level_batch": n_lvl, "keypoints": n,
+           "keypoints_per_level": np.bincount(level.cpu().numpy(), minlength=n_levels).tolist(),
+           "pixel_ratio_level_batch": float(lvl_off[-1]) / float(off[-1]),
+           "ms_per_image_single_scale": per(one_both), "ms_per_image_pyramid": per(pyramid),
+           "ms_per_image_detect_describe_levels": per(lvl_both), "ms_per_image_merge": per(merge)}
+    row["ms_per_image_single_scale_again"] = per(one_both)          # the yardstick once more, after the others: its spread
+    row["ms_per_image_multi_scale"] = (row["ms_per_image_pyramid"] + row["ms_per_image_detect_describe_levels"] +
+                                       row["ms_per_image_merge"])
+    row["ratio_multi_scale_to_single_scale"] = row["ms_per_image_multi_scale"] / row["ms_per_image_single_scale"]
+    row["ratio_detect_describe_levels_to_single_scale"] = (row["ms_per_image_detect_describe_levels"] /
+                                                           row["ms_per_image_single_scale"])
+    if emit:
+        emit(row)
+    return [row]
+
+
 def measure_guided(reps=20, emit=None):
     """sfm_guided_match with and without cross_check beside the blind batched matcher (knn2_batched + ratio_batched) on
     the same batch in the same run, inputs resident in HBM: the sizes of the matcher row of measure_fundamental (36 images
@@ -1188,13 +1288,14 @@ def main():
     ap.add_argument("--triangulate-only", action="store_true", help="only the N-view track triangulation rows")
     ap.add_argument("--incremental-only", action="store_true", help="only the resection / evaluation / incremental-loop rows")
     ap.add_argument("--features-only", action="store_true", help="only the feature detection / description row")
+    ap.add_argument("--pyramid-only", action="store_true", help="only the multi-scale feature row (beside the single-scale stage on the same images); no other selection runs it")
     ap.add_argument("--guided-only", action="store_true", help="only the guided-matching row (beside the blind matcher)")
     ap.add_argument("--depth-only", action="store_true", help="only the dense-depth row (beside the feature stage on the same images)")
     ap.add_argument("--mesh-only", action="store_true", help="only the meshing row: TSDF integration, mark and emit beside the sweep and the fusion of the same run")
     a = ap.parse_args()
     emit = lambda d: print(json.dumps(d), flush=True)
     only = a.fundamental_only or a.essential_only or a.homography_only or a.pnp_only or a.pose_only or a.tracks_only or a.triangulate_only or a.incremental_only or \
-        a.features_only or a.guided_only or a.depth_only or a.mesh_only
+        a.features_only or a.guided_only or a.depth_only or a.mesh_only or a.pyramid_only
     if not only:
         measure(a.reps, a.tracks, a.corr, emit=emit)
     if a.fundamental_only or not only:
@@ -1215,6 +1316,8 @@ def main():
         measure_incremental(a.reps, emit=emit)
     if a.features_only or not only:
         measure_features(a.reps, emit=emit)
+    if a.pyramid_only:
+        measure_features_pyramid(a.reps, emit=emit)
     if a.guided_only or not only:
         measure_guided(a.reps, emit=emit)
     if a.depth_only or not only:

@@ -1060,8 +1060,8 @@ int sfm_depth_fuse_gather(sfm_handle h, const int64_t* img_off /* host */, const
  *   n = (m1 - m0) x (m2 - m0) and D = |I| * sum(outside offsets) - |O| * sum(inside offsets), all integers and n . D never
  *   0, the second and third vertex are exchanged iff n . D < 0: the normal of a triangle points from inside to outside.
  *   Zero-area triangles (a node that holds exactly 0) are kept.  mesh_rule.h has the 6 x 16 cases as a table.
- *   Limits: no texture (per-vertex colours come from sfm_mesh_colors below), no hole filling; about 2.3 x the triangles of
- *   marching cubes.
+ *   Limits: no hole filling; about 2.3 x the triangles of marching cubes.  Colour comes afterwards: one per vertex from
+ *   sfm_mesh_colors, a texture atlas from sfm_mesh_texture, both below.
  * Two calls.  sfm_mesh_mark writes counts (device int64 [2]: vertices, triangles) and leaves in the workspace
  *    (sfm_mesh_workspace_bytes) per node its flags and one record - the 7-bit vertex mask, the node's first vertex slot and
  *    the cell's first triangle slot relative to its block of 256 nodes, the cell's activity - and the first slots of every
@@ -1110,8 +1110,9 @@ int sfm_mesh_emit(sfm_handle h, const float* tsdf, int32_t nx, int32_t ny, int32
  *      earlier view).
  * After the views colors[k] = (uint8) min(floor(acc_k / W + 0.5), 255) when m > 0 && W > 0, otherwise fill;
  *   n_views = min(m, 255) (uint8); best_view = best (int32, -1 for none).  colors is uint8 [n_vertices][channels].
- * Limits: no texture atlas, no exposure compensation; a vertex that no view sees gets fill and is not filled from its
- *   neighbours; every view that passes weighs by its angle only.
+ * Limits: one colour per vertex (sfm_mesh_texture below gives every triangle a patch of texels by the same rule), no
+ *   exposure compensation; a vertex that no view sees gets fill and is not filled from its neighbours; every view that
+ *   passes weighs by its angle only.
  * The workspace (sfm_mesh_colors_workspace_bytes) holds the view table.  Nothing is written at or above n_vertices, and
  *   the call returns at once for n_vertices == 0.  SFM_ERR_ARG before any device work for a null handle, what
  *   sfm_tsdf_integrate refuses about the views, channels not 1 or 3, n_vertices below 0 or above 2^31 - 1, tol not finite or
@@ -1125,6 +1126,54 @@ int sfm_mesh_colors(sfm_handle h, const int32_t* heights /* host */, const int32
                     const uint8_t* pixels, int32_t channels, int64_t n_vertices, const double* vertices, const float* normals,
                     double tol, double min_cos, int32_t fill, uint8_t* colors, uint8_t* n_views, int32_t* best_view,
                     void* workspace, int64_t workspace_bytes);
+
+/* ---- texture of the mesh: a patch of texels per triangle in one atlas, every texel blended over the views that see it
+ *      (sfm_amd/csrc/mesh_texture.hip, mesh_texture_rule.h, mesh_texture_plan.h) ----
+ * A pure function of its inputs: float64 without FMA contraction and integers, no visit order, no atomics, no randomness,
+ * so NumPy reproduces every output byte (tests/mesh_texture_reference.py).
+ * Layout, a pure function of (n_triangles, texels, cells_per_row).  s = texels, 1 <= s <= 64, and P = s + 3.  Triangle t
+ *   lives in cell c = t >> 1, half t & 1; cell c starts at texel (x0, y0) = ((c % cells_per_row) * P, (c / cells_per_row) * P).
+ *   The atlas is W = cells_per_row * P wide and H = ceil(ceil(n_triangles / 2) / cells_per_row) * P high, W, H <= 32768
+ *   (sfm_mesh_texture_size).  Local coordinates (i, j) of a triangle run over i, j >= 0, i + j <= s + 1; half 0 puts (i, j)
+ *   at texel (x0 + i, y0 + j), half 1 at (x0 + P - 1 - i, y0 + P - 1 - j): a point reflection, so the orientation is kept.
+ *   The corners sit on texel centres: corner 0 at (0, 0), corner 1 at (s, 0), corner 2 at (0, s).
+ *   The inverse map takes a texel (x, y) with lx = x % P, ly = y % P: lx + ly <= s + 1 is half 0 with (i, j) = (lx, ly);
+ *   lx + ly >= s + 3 is half 1 with (i, j) = (P - 1 - lx, P - 1 - ly); lx + ly == s + 2 belongs to no triangle, and so does
+ *   a half whose t >= n_triangles.
+ * Barycentric numerators over 2 s.  Interior texels (i + j <= s): n1 = 2 i, n2 = 2 j, n0 = 2 s - n1 - n2.  The diagonal
+ *   i + j == s + 1 is the gutter: n1 = clamp(2 i - 1, 0, 2 s), n2 = 2 s - n1, n0 = 0 - the texel centre moved onto the
+ *   hypotenuse.  With the corners on texel centres and this gutter a bilinear lookup at any point inside a triangle takes
+ *   non-zero weight only from that triangle's own texels; the sides i = -1 and j = -1 need no gutter.
+ * Point and normal of a texel.  V0, V1, V2 the triangle's vertices (float64), m0, m1, m2 their normals (float32 widened),
+ *   the numerators converted to double:  X_a = ((n0 * V0_a + n1 * V1_a) + n2 * V2_a) / (double)(2 s), g_a the same expression
+ *   of the normals, l2 = (g0 g0 + g1 g1) + g2 g2; the normal is g_a / sqrt(l2) when l2 is finite and > 0, else zeros.  It is
+ *   used in double and not rounded to float32.
+ * Colour.  Steps 1 to 5 of sfm_mesh_colors and its finish, applied to (X, normal) with the same views, tol, min_cos and
+ *   fill: texture[y][x][k] is that colour, views[y][x] = min(m, 255).  A triangle with a vertex index outside
+ *   [0, n_vertices) is seen by no view - fill and 0, and nothing is read through the bad index.  Texels that belong to no
+ *   triangle get fill and 0.  Every texel of the H x W atlas is written and nothing outside it.
+ * uv (float32 [n_triangles][3][2]): for corner k at texel (x, y) it is ((x + 0.5) / W, (y + 0.5) / H), computed in double
+ *   and rounded once; v counts downwards from the top row (writers flip it where a format wants that).  Written for every
+ *   triangle, those with bad indices included.
+ * Limits: one patch size for all triangles (the triangles of marching tetrahedra are all voxel-sized; slivers waste
+ *   texels), no chart merging (triangles that share an edge share no texel), no view culling per triangle, no exposure
+ *   compensation, no fill-in of unseen texels, no mip levels.
+ * The workspace (sfm_mesh_texture_workspace_bytes) holds the view table.  The call returns at once for n_triangles == 0.
+ *   SFM_ERR_ARG before any device work for a null handle, what sfm_mesh_colors refuses about the views and the scalars
+ *   (channels, n_vertices, tol, min_cos, fill), texels outside 1 .. 64, cells_per_row < 1, W or H above 32768, n_triangles
+ *   below 0 or above 2^31 - 1, a null pointer (keep excepted; depth / pixels may be null only when there is no pixel,
+ *   vertices / normals only when n_vertices is 0, triangles and the outputs only when n_triangles is 0), or a workspace that
+ *   is missing or too small.  sfm_mesh_texture_size refuses the same layouts and a null output.  No kernel reads outside a
+ *   map, an image or the mesh. */
+int sfm_mesh_texture_size(int64_t n_triangles, int32_t texels, int32_t cells_per_row, int32_t* width_host, int32_t* height_host);
+int sfm_mesh_texture_workspace_bytes(int32_t n_ref, int64_t* bytes_host);
+int sfm_mesh_texture(sfm_handle h, const int32_t* heights /* host */, const int32_t* widths /* host */, int32_t n_img,
+                     int32_t n_ref, const int32_t* ref_image /* host */, const double* proj /* device [n_ref][12] */,
+                     const double* centres /* device [n_ref][3] */, const float* depth, const uint8_t* keep /* or NULL */,
+                     const uint8_t* pixels, int32_t channels, int64_t n_vertices, const double* vertices, const float* normals,
+                     int64_t n_triangles, const int32_t* triangles, int32_t texels, int32_t cells_per_row, double tol,
+                     double min_cos, int32_t fill, uint8_t* texture /* [H][W][channels] */, uint8_t* views /* [H][W] */,
+                     float* uv /* [n_triangles][3][2] */, void* workspace, int64_t workspace_bytes);
 
 #ifdef __cplusplus
 }

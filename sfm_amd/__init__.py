@@ -8,8 +8,8 @@ from .tracks import Tracks, build_tracks, tracks_from_pair_files  # noqa: F401
 from .triangulate import Triangulation, triangulate_tracks, triangulate_tracks_raw  # noqa: F401
 from .incremental import Reconstruction, classify_tracks, evaluate_tracks, reconstruct_tracks, resection_lists  # noqa: F401
 from .features import Features, PyramidFeatures, detect_and_describe_batched, detect_features, pyramid_levels  # noqa: F401
-from .interchange import read_pnm, save_ply_mesh, save_ply_points, write_pnm  # noqa: F401
+from .interchange import read_pnm, save_obj_mesh, save_ply_mesh, save_ply_points, write_png, write_pnm  # noqa: F401
 from .guided import guided_match_pairs  # noqa: F401
 from .depth import (DepthMaps, FusedCloud, dense_from_reconstruction, depth_maps, depth_maps_from_arrays, depth_ranges, plane_depths, select_sources,  # noqa: F401
                     view_backprojection, view_warps)
-from .mesh import Mesh, TsdfVolume, mesh_vertex_colors, tsdf_volume_from_arrays  # noqa: F401
+from .mesh import Mesh, MeshTexture, TsdfVolume, mesh_texture, mesh_vertex_colors, tsdf_volume_from_arrays  # noqa: F401

@@ -496,14 +496,20 @@ def depth_maps_from_arrays(shapes, refs, src_ptr, src_image, warps, backproj, de
 
 
 def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=256, radius=2, rel_tol=0.01, max_cost=None,
-                              min_consistent=2, colors=None, device=0, fuse=False, mesh=False):
+                              min_consistent=2, colors=None, device=0, fuse=False, mesh=False, texture=None):
     """The chain on a `Reconstruction`: sources by shared points (`select_sources`), the depth interval of every view from
     its sparse points (`depth_ranges`), planes at most one pixel apart (`plane_depths`), `depth_maps`, `.filter`,
     `.point_cloud`.  images: one per image position of rec.tracks.  Returns (points, index, DepthMaps) - or (points, index,
     colours, DepthMaps) with colors.  With fuse=True the last step is `.fuse()` in place of `.point_cloud`, and the result
     is (FusedCloud, DepthMaps); the colours are then `FusedCloud.colors(colors)`.  With mesh=True the surface of the kept
     pixels, `maps.tsdf().mesh()`, is appended to whichever of those is returned; with colors (uint8 images) it is coloured
-    by `Mesh.colors(colors)`."""
+    by `Mesh.colors(colors)`, and with texture (an integer, the texels per triangle leg) it also gets the atlas of
+    `Mesh.texture(colors, texels=texture)` as `Mesh.atlas`; the tuple keeps its shape."""
+    if texture is not None:
+        if not (isinstance(texture, (int, np.integer)) and 1 <= texture <= 64):
+            raise ValueError("texture must be None or the texels per triangle leg, an integer 1 .. 64")
+        if not mesh or colors is None:
+            raise ValueError("texture needs mesh=True and colors: the images the atlas is blended from")
     n_img = len(rec.tracks.kp_ptr) - 1
     if len(images) != n_img:
         raise ValueError(f"{len(images)} images for {n_img} image positions")
@@ -519,6 +525,8 @@ def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=2
     surface = (maps.tsdf().mesh(),) if mesh else ()
     if mesh and colors is not None:
         surface[0].colors(colors)
+        if texture is not None:
+            surface[0].texture(colors, texels=int(texture))
     if fuse:
         return (maps.fuse(), maps) + surface
     return maps.point_cloud(colors) + (maps,) + surface

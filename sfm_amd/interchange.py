@@ -148,6 +148,72 @@ def save_ply_mesh(vertices, triangles, path, normals=None, colors=None):
         f.write(faces.tobytes())
 
 
+def write_png(path, image):
+    """An 8-bit gray [h,w] or RGB [h,w,3] uint8 array as a PNG file: one zlib stream of the rows, each with filter type 0,
+    through the standard library alone.  The channels are written in the order they have."""
+    import struct
+    import zlib
+    img = np.asarray(image)
+    if img.dtype != np.uint8 or img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] != 3) or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError("image must be uint8 [h,w] or [h,w,3] with at least one pixel")
+    h, w = img.shape[:2]
+    rows = np.zeros((h, 1 + w * (3 if img.ndim == 3 else 1)), np.uint8)         # column 0: the filter type of the row, none
+    rows[:, 1:] = img.reshape(h, -1)
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n")
+        f.write(chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2 if img.ndim == 3 else 0, 0, 0, 0)))
+        f.write(chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)))
+        f.write(chunk(b"IEND", b""))
+
+
+def save_obj_mesh(vertices, triangles, path, normals=None, uv=None, texture=None, bgr=True):
+    """A triangle mesh as Wavefront OBJ text: `v` per vertex, `vn` per vertex with normals, and with uv (float32 [m,3,2],
+    per triangle corner (u, v) with v counted downwards from the top row, as `MeshTexture.uv` is) one `vt u (1 - v)` per
+    corner - the format counts v upwards - and faces `f a/ta/a` (1-based; `a//a` without uv, `a/ta` without normals).  With
+    texture (uint8 [h,w] or [h,w,3]) the image goes to <stem>.png and a material with `map_Kd` to <stem>.mtl, both beside
+    path; bgr=True reverses the channels of a three-channel texture on the way, because the project's images are BGR."""
+    path = Path(path)
+    pts = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
+    tri = np.asarray(triangles)
+    if tri.size == 0:
+        tri = np.zeros((0, 3), dtype=np.int32)
+    if tri.ndim != 2 or tri.shape[1] != 3 or tri.dtype.kind not in "iu":
+        raise ValueError("triangles must be integers [m,3]")
+    if len(tri) and (tri.min() < 0 or tri.max() >= len(pts)):
+        raise ValueError("a triangle names a vertex that does not exist")
+    if normals is not None and np.shape(normals) != (len(pts), 3):
+        raise ValueError("normals must be [n,3], one per vertex")
+    if uv is not None and np.shape(uv) != (len(tri), 3, 2):
+        raise ValueError("uv must be [m,3,2], one pair per triangle corner")
+    if texture is not None and uv is None:
+        raise ValueError("a texture needs uv")
+    lines = ["# sfm_amd mesh"]
+    if texture is not None:
+        img = np.asarray(texture)
+        write_png(path.with_suffix(".png"), img[:, :, ::-1] if (bgr and img.ndim == 3) else img)
+        with open(path.with_suffix(".mtl"), "w") as f:
+            f.write(f"newmtl atlas\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {path.with_suffix('.png').name}\n")
+        lines += [f"mtllib {path.with_suffix('.mtl').name}", "usemtl atlas"]
+    lines += ["v %.17g %.17g %.17g" % tuple(p) for p in pts]
+    if normals is not None:
+        lines += ["vn %.9g %.9g %.9g" % tuple(n) for n in np.asarray(normals, dtype=np.float64)]
+    if uv is not None:
+        q = np.asarray(uv, dtype=np.float64).reshape(-1, 2)
+        lines += ["vt %.9g %.9g" % (u, 1.0 - v) for u, v in q]
+    for t, (a, b, c) in enumerate(tri + 1):
+        if uv is not None:
+            ref = (lambda i, k: f"{i}/{3 * t + k + 1}/{i}") if normals is not None else (lambda i, k: f"{i}/{3 * t + k + 1}")
+        else:
+            ref = (lambda i, k: f"{i}//{i}") if normals is not None else (lambda i, k: f"{i}")
+        lines.append(f"f {ref(a, 0)} {ref(b, 1)} {ref(c, 2)}")
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def save_reconstruction(poses, points3D, point_tracks, output_dir):
     """poses.json, points3D.json (points + tracks, image ids as strings) and reconstruction.ply."""
     output_dir = Path(output_dir)

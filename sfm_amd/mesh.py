@@ -3,7 +3,8 @@ distance volume from filtered depth maps, `sfm_mesh_mark` / `sfm_mesh_emit` (sfm
 a triangle mesh by marching tetrahedra; include/sfm_amd.h states both rules completely.  Every view weighs the same, a pixel
 without a depth carries no evidence (free space outside every silhouette stays unknown and the mesh is open there), holes
 are not filled and zero-area triangles are kept.  `sfm_mesh_colors` (sfm_amd/csrc/mesh_color.hip) gives every vertex a colour
-blended over the views whose own depth maps see it.  No CPU fallback: without the library or a GPU the calls raise.
+blended over the views whose own depth maps see it, `sfm_mesh_texture` (sfm_amd/csrc/mesh_texture.hip) every triangle a
+patch of texels in an atlas by the same blend.  No CPU fallback: without the library or a GPU the calls raise.
 """
 from __future__ import annotations
 
@@ -59,6 +60,28 @@ class Mesh:
     n_views = property(lambda self: self._get("n_views", self.n_vertices))
     best_view = property(lambda self: self._get("best_view", self.n_vertices))
 
+    def _view_inputs(self, what, images, maps, tol, min_cos, fill):
+        """What colors() and texture() share: the maps and tol with their defaults, the checked scalars, the views' pixels
+        back to back with their channel count, and proj / centres of the views on the host."""
+        maps = getattr(self._volume, "_maps", None) if maps is None else maps
+        if maps is None:
+            raise ValueError(f"{what}() needs maps: the mesh's volume was not built by DepthMaps.tsdf()")
+        if getattr(maps, "keep", None) is None:
+            raise ValueError(f"{what}() needs filter() first")
+        if tol is None:
+            vol = self._volume
+            if vol is None:
+                raise ValueError(f"{what}() needs tol: the mesh has no volume")
+            tol = getattr(vol, "trunc", 3.0 * vol.voxel)
+        check_color_scalars(tol, min_cos, fill)
+        s = maps._s
+        if len(images) != len(s["imgs"]):
+            raise ValueError("images: one array per image of the set")
+        flat, channels = check_color_images([images[r] for r in maps.views], maps.shapes)
+        n_ref = len(maps.views)
+        backproj = s["backproj"].cpu().numpy()[:n_ref].reshape(-1, 3, 4)
+        return maps, tol, flat, channels, projections_from_backprojections(backproj), np.ascontiguousarray(backproj[:, :, 3])
+
     def colors(self, images, maps=None, tol=None, min_cos=0.35, fill=0):
         """A colour per vertex on the device (`sfm_mesh_colors`; include/sfm_amd.h states the rule): the vertex is projected
         into every view, a view counts when its own depth at the nearest pixel is within tol of the vertex's depth and the
@@ -68,27 +91,10 @@ class Mesh:
         `DepthMaps`, None for those the mesh's volume was integrated from; tol: None for the truncation of the volume
         (3 voxels); fill: the colour of a vertex that no view sees.  Returns uint8 [nv] or [nv,3] and fills vertex_colors,
         n_views and best_view (the position of the view with the largest weight, -1 for none)."""
-        maps = getattr(self._volume, "_maps", None) if maps is None else maps
-        if maps is None:
-            raise ValueError("colors() needs maps: the mesh's volume was not built by DepthMaps.tsdf()")
-        if getattr(maps, "keep", None) is None:
-            raise ValueError("colors() needs filter() first")
-        if tol is None:
-            vol = self._volume
-            if vol is None:
-                raise ValueError("colors() needs tol: the mesh has no volume")
-            tol = getattr(vol, "trunc", 3.0 * vol.voxel)
-        check_color_scalars(tol, min_cos, fill)
+        maps, tol, flat, channels, proj, centres = self._view_inputs("colors", images, maps, tol, min_cos, fill)
         s = maps._s
-        if len(images) != len(s["imgs"]):
-            raise ValueError("images: one array per image of the set")
-        flat, channels = check_color_images([images[r] for r in maps.views], maps.shapes)
         import torch
         dev = self._m["vertices"].device
-        n_ref = len(maps.views)
-        backproj = s["backproj"].cpu().numpy()[:n_ref].reshape(-1, 3, 4)
-        proj = projections_from_backprojections(backproj)
-        centres = np.ascontiguousarray(backproj[:, :, 3])
         out = _colors(dev, s["heights"], s["widths"], s["ref_image"], proj, centres, s["depth"], s["keep"], torch.from_numpy(flat).to(dev),
                       channels, self.n_vertices, self._m["vertices"], self._m["normals"], tol, min_cos, fill)
         self._m.update(out)
@@ -96,11 +102,70 @@ class Mesh:
             self._host.pop(name, None)
         return self.vertex_colors
 
+    atlas = None                                                   # the `MeshTexture` of the last texture(); None before
+
+    def texture(self, images, texels=8, maps=None, tol=None, min_cos=0.35, fill=0, cells_per_row=None):
+        """A texture atlas on the device (`sfm_mesh_texture`; include/sfm_amd.h states the rule): every triangle gets a patch
+        with texels + 1 texel centres along each leg, two triangles to a cell of (texels + 3)^2 texels, cells_per_row cells
+        in a row (None: ceil(sqrt(ceil(nt / 2))), a square atlas), and every texel is the blend of `colors()` at the texel's
+        point on the triangle, with the normal interpolated from the corners'.  images, maps, tol, min_cos and fill are those
+        of `colors()`; fill is also the colour of the texels that belong to no triangle.  Returns a `MeshTexture` and keeps
+        it as `atlas`."""
+        cells_per_row = check_texture_layout(self.n_triangles, texels, cells_per_row)[0]
+        maps, tol, flat, channels, proj, centres = self._view_inputs("texture", images, maps, tol, min_cos, fill)
+        s = maps._s
+        import torch
+        dev = self._m["vertices"].device
+        self.atlas = _texture(dev, s["heights"], s["widths"], s["ref_image"], proj, centres, s["depth"], s["keep"], torch.from_numpy(flat).to(dev),
+                              channels, self.n_vertices, self._m["vertices"], self._m["normals"], self.n_triangles, self._m["triangles"],
+                              texels, cells_per_row, tol, min_cos, fill)
+        return self.atlas
+
     def save(self, path, colors=None):
         """Binary PLY with normals (`save_ply_mesh`); colors: None for vertex_colors when `colors()` has made them."""
         from .interchange import save_ply_mesh
         colors = self.vertex_colors if colors is None else colors
         save_ply_mesh(self.vertices, self.triangles, path, normals=self.normals, colors=colors)
+
+    def save_obj(self, path, texture=None):
+        """Wavefront OBJ with normals, texture coordinates, a .mtl and the atlas as a .png beside it (`save_obj_mesh`);
+        texture: a `MeshTexture`, None for `atlas`.  Three-channel atlases are taken as BGR, like the project's images."""
+        from .interchange import save_obj_mesh
+        texture = self.atlas if texture is None else texture
+        if texture is None:
+            raise ValueError("save_obj() needs a texture: call texture() first")
+        save_obj_mesh(self.vertices, self.triangles, path, normals=self.normals, uv=texture.uv, texture=texture.image)
+
+
+class MeshTexture:
+    """What `Mesh.texture` returns; the arrays stay on the device until they are asked for.  image uint8 [H,W] or [H,W,3]
+    (the channel order of the images), views uint8 [H,W] (the views blended into a texel, at most 255; 0 where no view sees
+    it or it belongs to no triangle), uv float32 [nt,3,2]: per triangle corner the centre of its texel as (column, row) over
+    (W, H), the row counted downwards from the top; size = (W, H)."""
+
+    def __init__(self, state, size, texels, cells_per_row, channels, n_triangles):
+        self._m, self.size, self.texels, self.cells_per_row = state, tuple(size), int(texels), int(cells_per_row)
+        self.channels, self.n_triangles = int(channels), int(n_triangles)
+        self._host = {}
+
+    def _get(self, name, n, shape):
+        if name not in self._host:
+            self._host[name] = self._m[name].cpu().numpy().reshape(-1)[:n].reshape(shape)
+        return self._host[name]
+
+    @property
+    def image(self):
+        W, H = self.size
+        return self._get("image", H * W * self.channels, (H, W) if self.channels == 1 else (H, W, 3))
+
+    @property
+    def views(self):
+        W, H = self.size
+        return self._get("views", H * W, (H, W))
+
+    @property
+    def uv(self):
+        return self._get("uv", self.n_triangles * 6, (self.n_triangles, 3, 2))
 
 
 class TsdfVolume:
@@ -361,3 +426,93 @@ def mesh_vertex_colors(vertices, normals, proj, centres, depth, keep, images, to
                   None if keep is None else up(keep, np.uint8), torch.from_numpy(flat).to(dev), channels, nv,
                   torch.from_numpy(pad(vertices)).to(dev), torch.from_numpy(pad(normals)).to(dev), tol, min_cos, fill)
     return tuple(out[name].cpu().numpy()[:nv] for name in ("vertex_colors", "n_views", "best_view"))
+
+
+# ------------------------------------------------------------------------------------------- texture
+MAX_TEXELS, MAX_ATLAS_SIDE = 64, 32768
+
+
+def check_texture_layout(n_triangles, texels, cells_per_row):
+    """(cells_per_row with None resolved, W, H) of the atlas or ValueError: what `sfm_mesh_texture_size` computes."""
+    if not (isinstance(texels, (int, np.integer)) and 1 <= texels <= MAX_TEXELS):
+        raise ValueError(f"texels must be an integer 1 .. {MAX_TEXELS}")
+    if not 0 <= n_triangles <= 0x7FFFFFFF:
+        raise ValueError("at most 2^31 - 1 triangles")
+    cells = (int(n_triangles) + 1) // 2
+    if cells_per_row is None:
+        import math
+        r = math.isqrt(cells)
+        cells_per_row = max(r + (r * r < cells), 1)
+    if not (isinstance(cells_per_row, (int, np.integer)) and cells_per_row >= 1):
+        raise ValueError("cells_per_row must be None or an integer >= 1")
+    P = int(texels) + 3
+    W, H = int(cells_per_row) * P, -(-cells // int(cells_per_row)) * P
+    if W > MAX_ATLAS_SIDE or H > MAX_ATLAS_SIDE:
+        raise ValueError(f"the atlas would be {W} x {H}: at most {MAX_ATLAS_SIDE} either way (fewer texels, or another cells_per_row)")
+    return int(cells_per_row), W, H
+
+
+def _texture(dev, heights, widths, ref_image, proj, centres, d_depth, d_keep, d_pixels, channels, n_vertices, d_vertices, d_normals,
+             n_triangles, d_triangles, texels, cells_per_row, tol, min_cos, fill):
+    """The device call: the views as `_colors` takes them; the vertices, the normals and the triangles on the device."""
+    import torch
+    h = _lib.get_handle(dev.index)
+    n_ref, n_img = len(ref_image), len(heights)
+    table = lambda a, k: (torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, k)).to(dev) if n_ref
+                          else torch.zeros((1, k), dtype=torch.float64, device=dev))
+    d_proj, d_centres = table(proj, 12), table(centres, 3)
+    W, H = C.c_int32(), C.c_int32()
+    if h.lib.sfm_mesh_texture_size(int(n_triangles), int(texels), int(cells_per_row), C.byref(W), C.byref(H)) != 0:
+        raise ValueError("sfm_mesh_texture_size refuses this layout")
+    W, H = W.value, H.value
+    need = C.c_int64()
+    h.check(h.lib.sfm_mesh_texture_workspace_bytes(n_ref, C.byref(need)), "sfm_mesh_texture_workspace_bytes")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    out = {"image": torch.empty(max(H * W * channels, 1), dtype=torch.uint8, device=dev),
+           "views": torch.empty(max(H * W, 1), dtype=torch.uint8, device=dev),
+           "uv": torch.empty(max(int(n_triangles) * 6, 1), dtype=torch.float32, device=dev)}
+    dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    h.call("sfm_mesh_texture", hp(heights), hp(widths), n_img, n_ref, hp(ref_image), dp(d_proj), dp(d_centres), dp(d_depth), dp(d_keep),
+           dp(d_pixels), int(channels), int(n_vertices), dp(d_vertices), dp(d_normals), int(n_triangles), dp(d_triangles), int(texels),
+           int(cells_per_row), C.c_double(float(tol)), C.c_double(float(min_cos)), int(fill), dp(out["image"]), dp(out["views"]), dp(out["uv"]),
+           dp(ws), need.value)
+    out["ws"] = (ws, d_proj, d_centres, d_depth, d_keep, d_pixels, d_vertices, d_normals, d_triangles)      # alive while the call may still run
+    return MeshTexture(out, (W, H), texels, cells_per_row, channels, n_triangles)
+
+
+def mesh_texture(vertices, normals, triangles, proj, centres, depth, keep, images, tol, texels=8, min_cos=0.35, fill=0, cells_per_row=None,
+                 device=0):
+    """`sfm_mesh_texture` on arrays that were made elsewhere: vertices float64 [nv,3], normals float32 [nv,3], triangles int32
+    [nt,3] (a triangle with an index outside 0 .. nv - 1 is seen by no view), the views as `mesh_vertex_colors` takes them,
+    images one uint8 [h,w] or [h,w,3] per VIEW.  Returns a `MeshTexture`."""
+    import torch
+    check_color_scalars(tol, min_cos, fill)
+    vertices = np.ascontiguousarray(vertices, dtype=np.float64)
+    normals = np.ascontiguousarray(normals, dtype=np.float32)
+    if vertices.ndim != 2 or vertices.shape[1] != 3 or normals.shape != vertices.shape:
+        raise ValueError("vertices and normals must be [nv,3]")
+    tri = np.asarray(triangles)
+    if tri.ndim != 2 or tri.shape[1] != 3 or tri.dtype.kind not in "iu" or (tri.size and (tri.min() < -0x80000000 or tri.max() > 0x7FFFFFFF)):
+        raise ValueError("triangles must be [nt,3] integers that fit int32")
+    tri = np.ascontiguousarray(tri, dtype=np.int32)
+    cells_per_row = check_texture_layout(len(tri), texels, cells_per_row)[0]
+    depth = [np.ascontiguousarray(d, dtype=np.float32) for d in depth]
+    if any(d.ndim != 2 for d in depth) or np.shape(proj) != (len(depth), 12) or np.shape(centres) != (len(depth), 3) or len(depth) > MAX_VIEWS:
+        raise ValueError(f"depth: at most {MAX_VIEWS} [h,w] maps; proj: 12 numbers and centres: 3 numbers for each")
+    if keep is not None and [np.shape(k) for k in keep] != [d.shape for d in depth]:
+        raise ValueError("keep must be None or one [h,w] array per view, shaped like its depth map")
+    flat, channels = check_color_images(images, [d.shape for d in depth])
+    _lib.get_handle(device)
+    dev = torch.device("cuda", device)
+
+    def up(arrays, dtype):
+        return torch.from_numpy(np.concatenate([np.asarray(a, dtype=dtype).reshape(-1) for a in arrays] + [np.zeros(1, dtype)])).to(dev)
+
+    pad = lambda a: np.concatenate([a, np.zeros((1, 3), a.dtype)])           # one row more: a pointer must exist
+    heights = np.array([d.shape[0] for d in depth], dtype=np.int32)
+    widths = np.array([d.shape[1] for d in depth], dtype=np.int32)
+    return _texture(dev, heights, widths, np.arange(len(depth), dtype=np.int32), proj, centres, up(depth, np.float32),
+                    None if keep is None else up(keep, np.uint8), torch.from_numpy(flat).to(dev), channels, len(vertices),
+                    torch.from_numpy(pad(vertices)).to(dev), torch.from_numpy(pad(normals)).to(dev), len(tri), torch.from_numpy(pad(tri)).to(dev),
+                    texels, cells_per_row, tol, min_cos, fill)

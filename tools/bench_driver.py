@@ -1096,7 +1096,9 @@ def measure_depth(reps=20, emit=None, mesh=False):
     sfm_features_detect + sfm_features_describe on the same images, as a known quantity.  With mesh=True also the surface
     of the same run: sfm_tsdf_integrate of the 36 filtered maps into 256^3 nodes (a cube around the kept pixels, truncation 3
     voxels), sfm_mesh_mark and sfm_mesh_emit (min_weight 1), then sfm_mesh_colors of that mesh from the 36 views (BGR, tol 3
-    voxels, min_cos 0.35) with its vertex-view projections per second, whole calls by HIP events; the row is then named "mesh"."""
+    voxels, min_cos 0.35) with its vertex-view projections per second, and sfm_mesh_texture of the same mesh from the same views
+    at texels 8 with its texel-view projections per second (the texels of the triangles' patches x views), whole calls by HIP
+    events; the row is then named "mesh"."""
     import torch
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from depth_reference import make_scene
@@ -1234,6 +1236,30 @@ def measure_depth(reps=20, emit=None, mesh=False):
                    _p(d_bgr), 3, nv, _p(vertices), _p(vnormals), C.c_double(3.0 * voxel), C.c_double(0.35), 0, _p(vcolors), _p(vviews),
                    _p(vbest), _p(colors_ws), colors_need)
         run_mesh_colors()
+        # the texture of the same mesh from the same views: texels 8, the square atlas of Mesh.texture; 20 calls after 3
+        texels, cells_per_row, aw, ah = 8, mm.check_texture_layout(nt, 8, None)[0], C.c_int32(), C.c_int32()
+        h.check(h.lib.sfm_mesh_texture_size(nt, texels, cells_per_row, C.byref(aw), C.byref(ah)), "sfm_mesh_texture_size")
+        aw, ah = aw.value, ah.value
+        h.check(h.lib.sfm_mesh_texture_workspace_bytes(n_img, C.byref(need)), "sfm_mesh_texture_workspace_bytes")
+        texture_need = need.value
+        texture_ws = torch.empty(texture_need, dtype=torch.uint8, device=dev)
+        atlas = torch.empty(max(ah * aw * 3, 1), dtype=torch.uint8, device=dev)
+        aviews = torch.empty(max(ah * aw, 1), dtype=torch.uint8, device=dev)
+        auv = torch.empty(max(nt * 6, 1), dtype=torch.float32, device=dev)
+
+        def run_mesh_texture():
+            h.call("sfm_mesh_texture", hp(heights), hp(widths), n_img, n_img, hp(ref_image), _p(d_proj), _p(d_centres), _p(depth), _p(keep),
+                   _p(d_bgr), 3, nv, _p(vertices), _p(vnormals), nt, _p(triangles), texels, cells_per_row, C.c_double(3.0 * voxel),
+                   C.c_double(0.35), 0, _p(atlas), _p(aviews), _p(auv), _p(texture_ws), texture_need)
+        for _ in range(3):
+            run_mesh_texture()
+        owned = nt * (texels + 2) * (texels + 3) // 2              # the texels that belong to a triangle: its patch with the gutter
+        with_view = int((aviews[:ah * aw] != 0).sum().item())      # only those can have a view
+        row.update({"texture_texels": texels, "texture_cells_per_row": cells_per_row, "texture_atlas": [aw, ah],
+                    "texture_share_of_texels_in_a_triangle": owned / max(aw * ah, 1), "texture_share_of_those_with_a_view": with_view / max(owned, 1),
+                    "texture_projections": owned * n_img, "ms_mesh_texture": timed(run_mesh_texture, reps) * 1e3})
+        row["texture_projections_per_s"] = row["texture_projections"] / (row["ms_mesh_texture"] * 1e-3)
+        del atlas, aviews, auv, texture_ws
         zv = vertices[:nv, 2].cpu().numpy()
         seen = int((weight != 0).sum().item())
         row.update({"grid_nodes": [nx, ny, nz], "voxel": float(voxel), "nodes_seen": seen, "projections": nx * ny * nz * n_img,

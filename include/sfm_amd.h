@@ -1175,6 +1175,60 @@ int sfm_mesh_texture(sfm_handle h, const int32_t* heights /* host */, const int3
                      double min_cos, int32_t fill, uint8_t* texture /* [H][W][channels] */, uint8_t* views /* [H][W] */,
                      float* uv /* [n_triangles][3][2] */, void* workspace, int64_t workspace_bytes);
 
+/* ---- render of the mesh: depth, triangle, barycentrics and colour per pixel of any camera (sfm_amd/csrc/mesh_render.hip,
+ *      mesh_render_rule.h, mesh_render_plan.h) ----
+ * A pure function of its inputs: float64 without FMA contraction and integers, no floating-point atomics, no randomness;
+ * the only atomic is an integer minimum, which has no order, so NumPy reproduces every output byte
+ * (tests/mesh_render_reference.py).
+ * Inputs.  n_cam cameras: heights / widths (HOST, 0 .. 32768 each; a camera with a side of 0 has no pixel) and proj (device,
+ *   float64 [n_cam][12], row-major [K R | K t], world to pixels, as sfm_tsdf_integrate takes it).  The outputs of camera c
+ *   start at pixel off[c] = sum over c' < c of heights[c'] * widths[c'].  vertices float64 [n_vertices][3] and triangles int32
+ *   [n_triangles][3] as sfm_mesh_emit wrote them.  color_mode 0: no colour; 1: vertex_colors uint8 [n_vertices][channels]
+ *   (what sfm_mesh_colors made); 2: the atlas uint8 [atlas_h][atlas_w][channels] with uv float32 [n_triangles][3][2] (what
+ *   sfm_mesh_texture made).  channels 1 or 3.
+ * Per camera P with an image of w x h pixels, pixel (x, y) having its centre at (x, y):
+ *   1. Project, per vertex: q_i = ((P_i0 X0 + P_i1 X1) + P_i2 X2) + P_i3, u = q0 / q2, v = q1 / q2.  A vertex is usable iff
+ *      q2 > 0 and u, v, q2 are finite.  A triangle with a corner that is not usable, or with an index outside [0, n_vertices),
+ *      draws nothing; it is not clipped against the near plane, and nothing is read through a bad index.
+ *   2. Bounding box, per triangle with the corners a, b, c: columns ceil(min u) .. floor(max u), rows ceil(min v) ..
+ *      floor(max v), both cut to the image.  An empty box draws nothing.
+ *   3. Inside test at (x, y): w0 = (ub - x)(vc - y) - (vb - y)(uc - x), w1 = (uc - x)(va - y) - (vc - y)(ua - x),
+ *      w2 = (ua - x)(vb - y) - (va - y)(ub - x), A = (w0 + w1) + w2.  Inside iff A != 0 and (w0, w1, w2 all >= 0 or all <= 0).
+ *      Both orientations draw (the mesh is open; no back-face culling).  A pixel on a shared edge is claimed by both
+ *      triangles, and step 5 decides.
+ *   4. Depth: r_k = w_k / q2_k, s = (r0 + r1) + r2, depth = (float)(A / s): 1 / z is linear on the screen.  The pixel is
+ *      skipped unless that float32 is finite and > 0.
+ *   5. Winner: the smallest (depth as float32, triangle index) in lexicographic order over the triangles that claim the
+ *      pixel.  A positive float32 orders like its bits, so this is the minimum of one 64-bit unsigned key per pixel, the
+ *      depth's bits in the high word and the index in the low word, whatever the visit order.
+ *   6. Outputs per pixel.  triangle (int32): the winner, -1 where nothing draws.  depth (float32): the winner's, the quiet
+ *      NaN 0x7FC00000 where nothing draws.  bary (float32 [3]): b_k = r_k / s of the winner, recomputed, kept in double for the
+ *      shading and rounded once for the output; zeros where nothing draws.  color (uint8 [channels], color_mode != 0): fill
+ *      where nothing draws, else with round(x) = min(max(floor(x + 0.5), 0), 255)
+ *      - vertex colours: round((b0 c_a + b1 c_b) + b2 c_c) per channel, c the colours of the winner's corners;
+ *      - atlas: px = ((b0 U_a + b1 U_b) + b2 U_c) * atlas_w - 0.5 with U the float32 uv column of the winner's corners
+ *        widened to double, py likewise from the uv row with atlas_h; x0 = floor(px), fx = px - x0, the columns x0 and x0 + 1
+ *        clamped to 0 .. atlas_w - 1, rows likewise; the bilinear sample of step 4 of sfm_mesh_colors over the four texels,
+ *        rounded by round.  uv is used as it is: the atlas rule keeps the taps that weigh inside the triangle's own patch.
+ * Limits: no clipping against the near plane (a triangle with a corner behind the camera is dropped whole), no culling, one
+ *   sample per pixel and so no anti-aliasing, no mip levels, the nearest depth wins alone (no blending, no transparency).
+ * The workspace (sfm_mesh_render_workspace_bytes; mesh_render_plan.h has the layout) holds at byte 0 one uint64, after the
+ *   call the number of (camera, triangle) boxes of more than 64 pixels, then the camera table, one 64-bit key per pixel, the
+ *   projected vertices of every camera and the list of those boxes.  Nothing is written at or above the sizes given.
+ *   SFM_ERR_ARG before any device work for a null handle, n_cam outside 0 .. 65535, a side outside 0 .. 32768, n_vertices or
+ *   n_triangles below 0 or above 2^31 - 1, color_mode not 0, 1 or 2, channels not 1 or 3 with a colour, fill outside
+ *   0 .. 255, an atlas side outside 1 .. 32768 when there is a triangle, a null pointer (heights / widths / proj may be null
+ *   only without a camera, vertices without a vertex, triangles without a triangle, the outputs without a pixel, color and
+ *   the colour sources where color_mode does not ask for them), or a workspace that is missing or too small. */
+int sfm_mesh_render_workspace_bytes(int32_t n_cam, const int32_t* heights /* host */, const int32_t* widths /* host */,
+                                    int64_t n_vertices, int64_t n_triangles, int64_t* bytes_host);
+int sfm_mesh_render(sfm_handle h, int32_t n_cam, const int32_t* heights /* host */, const int32_t* widths /* host */,
+                    const double* proj /* device [n_cam][12] */, int64_t n_vertices, const double* vertices, int64_t n_triangles,
+                    const int32_t* triangles, int32_t color_mode, int32_t channels, const uint8_t* vertex_colors /* or NULL */,
+                    const float* uv /* or NULL */, const uint8_t* atlas /* or NULL */, int32_t atlas_w, int32_t atlas_h,
+                    int32_t fill, float* depth /* [n_pix] */, int32_t* triangle /* [n_pix] */, float* bary /* [n_pix][3] */,
+                    uint8_t* color /* [n_pix][channels], or NULL */, void* workspace, int64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,6 +191,8 @@ SIGNATURES = {
     "sfm_mesh_texture_workspace_bytes": (C.c_int, [i32, C.POINTER(i64)]),
     "sfm_mesh_texture": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i64, vp, vp, i64, vp, i32, i32, f64, f64, i32, vp, vp, vp,
                                    vp, i64]),
+    "sfm_mesh_render_workspace_bytes": (C.c_int, [i32, vp, vp, i64, i64, C.POINTER(i64)]),
+    "sfm_mesh_render": (C.c_int, [vp, i32, vp, vp, vp, i64, vp, i64, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i64]),
 }
 
 _lib = None

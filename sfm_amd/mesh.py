@@ -4,7 +4,8 @@ a triangle mesh by marching tetrahedra; include/sfm_amd.h states both rules comp
 without a depth carries no evidence (free space outside every silhouette stays unknown and the mesh is open there), holes
 are not filled and zero-area triangles are kept.  `sfm_mesh_colors` (sfm_amd/csrc/mesh_color.hip) gives every vertex a colour
 blended over the views whose own depth maps see it, `sfm_mesh_texture` (sfm_amd/csrc/mesh_texture.hip) every triangle a
-patch of texels in an atlas by the same blend.  No CPU fallback: without the library or a GPU the calls raise.
+patch of texels in an atlas by the same blend, and `sfm_mesh_render` (sfm_amd/csrc/mesh_render.hip) draws the mesh through
+any camera: depth, triangle, barycentrics and colour per pixel.  No CPU fallback: without the library or a GPU the calls raise.
 """
 from __future__ import annotations
 
@@ -120,6 +121,37 @@ class Mesh:
                               channels, self.n_vertices, self._m["vertices"], self._m["normals"], self.n_triangles, self._m["triangles"],
                               texels, cells_per_row, tol, min_cos, fill)
         return self.atlas
+
+    def render(self, cameras, sizes, colors="auto", fill=0):
+        """The mesh drawn through cameras on the device (`sfm_mesh_render`; include/sfm_amd.h states the rule): per pixel the
+        nearest triangle under its centre, its depth, its barycentrics and a colour.  cameras: one [3,4] or [12] projection
+        (world to pixels) or a list of them; a camera may also be (K, (R, t)) or (K, R, t), taken as P = K [R | t].  sizes: one
+        (width, height) for all cameras or one per camera.  colors: "atlas" samples `atlas` bilinearly at the interpolated uv,
+        "vertex" interpolates `vertex_colors`, None draws geometry only, "auto" takes the atlas if the mesh has one, else the
+        vertex colours, else none; a source the mesh does not have is a ValueError.  fill: the colour where nothing draws.
+        Returns a `MeshRender`."""
+        proj, heights, widths = check_render_arguments(cameras, sizes, fill)[:3]
+        has_vertex = "vertex_colors" in self._m
+        mode = resolve_render_colors(colors, self.atlas is not None, has_vertex)
+        vcol = uv = image = None
+        channels, size = 1, (0, 0)
+        if mode == RENDER_ATLAS:
+            image, uv, channels, size = self.atlas._m["image"], self.atlas._m["uv"], self.atlas.channels, self.atlas.size
+        elif mode == RENDER_VERTEX:
+            vcol = self._m["vertex_colors"]
+            channels = 3 if vcol.ndim == 2 else 1
+        return _render(self._m["vertices"].device, proj, heights, widths, self.n_vertices, self._m["vertices"], self.n_triangles,
+                       self._m["triangles"], mode, channels, vcol, uv, image, size, fill)
+
+    def render_views(self, maps=None, colors="auto", fill=0):
+        """`render()` through the cameras of the views of a `DepthMaps`, each at the size of its maps: the render of every
+        input photograph that has a depth map.  maps: None for those the mesh's volume was integrated from."""
+        maps = getattr(self._volume, "_maps", None) if maps is None else maps
+        if maps is None:
+            raise ValueError("render_views() needs maps: the mesh's volume was not built by DepthMaps.tsdf()")
+        n_ref = len(maps.views)
+        proj = projections_from_backprojections(maps._s["backproj"].cpu().numpy()[:n_ref])
+        return self.render(list(proj), [(w, h) for h, w in maps.shapes], colors, fill)
 
     def save(self, path, colors=None):
         """Binary PLY with normals (`save_ply_mesh`); colors: None for vertex_colors when `colors()` has made them."""
@@ -516,3 +548,207 @@ def mesh_texture(vertices, normals, triangles, proj, centres, depth, keep, image
                     None if keep is None else up(keep, np.uint8), torch.from_numpy(flat).to(dev), channels, len(vertices),
                     torch.from_numpy(pad(vertices)).to(dev), torch.from_numpy(pad(normals)).to(dev), len(tri), torch.from_numpy(pad(tri)).to(dev),
                     texels, cells_per_row, tol, min_cos, fill)
+
+
+# ------------------------------------------------------------------------------------------- render
+RENDER_NONE, RENDER_VERTEX, RENDER_ATLAS = 0, 1, 2
+MAX_CAMERAS, MAX_IMAGE_SIDE = 65535, 32768
+
+
+def _shape(a):
+    """np.shape, None for what has none (a ragged nest)."""
+    try:
+        return np.shape(a)
+    except ValueError:
+        return None
+
+
+def _one_camera(cam):
+    """float64 [12] from a [3,4] / [12] projection or from (K, (R, t)) / (K, R, t)."""
+    if isinstance(cam, (tuple, list)) and len(cam) in (2, 3) and _shape(cam[0]) == (3, 3):
+        K = np.asarray(cam[0], dtype=np.float64)
+        R, t = cam[1] if len(cam) == 2 else cam[1:]
+        R, t = np.asarray(R, dtype=np.float64), np.asarray(t, dtype=np.float64).reshape(-1)
+        if R.shape != (3, 3) or t.shape != (3,):
+            raise ValueError("a camera given as K with (R, t) needs R [3,3] and t [3]")
+        return (K @ np.c_[R, t]).reshape(12)
+    try:
+        P = np.asarray(cam, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("a camera must be a [3,4] or [12] projection, or K with (R, t)") from None
+    if P.shape not in ((3, 4), (12,)):
+        raise ValueError("a camera must be a [3,4] or [12] projection, or K with (R, t)")
+    return P.reshape(12)
+
+
+def check_render_arguments(cameras, sizes, fill=0, vertices=None, triangles=None, vertex_colors=None, uv=None, atlas=None):
+    """What `Mesh.render` and `render_mesh` check before the device: (proj float64 [n,12], heights int32 [n], widths int32 [n],
+    mode, channels, vertices, triangles, vertex_colors, uv, atlas) or ValueError.  The arrays behind fill are those of
+    `render_mesh` and stay None where they are not given."""
+    single = (isinstance(cameras, np.ndarray) and cameras.shape in ((3, 4), (12,))) or \
+             (isinstance(cameras, (tuple, list)) and len(cameras) in (2, 3) and _shape(cameras[0]) == (3, 3)) or \
+             (isinstance(cameras, (tuple, list)) and _shape(cameras) in ((3, 4), (12,)) and _shape(cameras[0]) in ((), (4,)))
+    cams = [cameras] if single else list(cameras)
+    proj = np.array([_one_camera(c) for c in cams], dtype=np.float64).reshape(-1, 12)
+    if len(proj) > MAX_CAMERAS:
+        raise ValueError(f"at most {MAX_CAMERAS} cameras")
+    whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    try:
+        pairs = list(sizes)
+    except TypeError:
+        raise ValueError("sizes must be (width, height) or one such pair per camera") from None
+    if len(pairs) == 2 and all(whole(v) for v in pairs):
+        pairs = [tuple(pairs)] * len(proj)
+    if len(pairs) != len(proj):
+        raise ValueError("sizes: one (width, height) for all cameras or one per camera")
+    for p in pairs:
+        if not (isinstance(p, (tuple, list, np.ndarray)) and len(p) == 2 and all(whole(v) and 0 <= v <= MAX_IMAGE_SIDE for v in p)):
+            raise ValueError(f"a size must be (width, height), integers 0 .. {MAX_IMAGE_SIDE}")
+    widths = np.array([p[0] for p in pairs], dtype=np.int32)
+    heights = np.array([p[1] for p in pairs], dtype=np.int32)
+    if not (whole(fill) and 0 <= fill <= 255):
+        raise ValueError("fill must be an integer 0 .. 255")
+    mode, channels, n_vertices = RENDER_NONE, 1, None
+    if vertices is not None:
+        vertices = np.ascontiguousarray(vertices, dtype=np.float64)
+        if vertices.ndim != 2 or vertices.shape[1] != 3:
+            raise ValueError("vertices must be [nv,3]")
+        n_vertices = len(vertices)
+    if triangles is not None:
+        tri = np.asarray(triangles)
+        if tri.ndim != 2 or tri.shape[1] != 3 or tri.dtype.kind not in "iu" or (tri.size and (tri.min() < -0x80000000 or tri.max() > 0x7FFFFFFF)):
+            raise ValueError("triangles must be [nt,3] integers that fit int32")
+        triangles = np.ascontiguousarray(tri, dtype=np.int32)
+    if vertex_colors is not None and (uv is not None or atlas is not None):
+        raise ValueError("one source of colour: vertex_colors, or uv with atlas")
+    if (uv is None) != (atlas is None):
+        raise ValueError("uv and atlas come together")
+    if vertex_colors is not None:
+        vertex_colors = np.asarray(vertex_colors)
+        if vertex_colors.dtype != np.uint8 or vertex_colors.shape not in ((n_vertices,), (n_vertices, 3)):
+            raise ValueError("vertex_colors must be uint8 [nv] or [nv,3]")
+        mode, channels = RENDER_VERTEX, 3 if vertex_colors.ndim == 2 else 1
+        vertex_colors = np.ascontiguousarray(vertex_colors)
+    if atlas is not None:
+        atlas, uv = np.asarray(atlas), np.asarray(uv)
+        nt = 0 if triangles is None else len(triangles)
+        if atlas.dtype != np.uint8 or atlas.ndim not in (2, 3) or (atlas.ndim == 3 and atlas.shape[2] != 3):
+            raise ValueError("atlas must be uint8 [H,W] or [H,W,3]")
+        if nt > 0 and not (1 <= atlas.shape[0] <= MAX_ATLAS_SIDE and 1 <= atlas.shape[1] <= MAX_ATLAS_SIDE):
+            raise ValueError(f"the atlas must be 1 .. {MAX_ATLAS_SIDE} wide and high")
+        if uv.shape != (nt, 3, 2) or uv.dtype.kind != "f":
+            raise ValueError("uv must be a float array [nt,3,2]")
+        mode, channels = RENDER_ATLAS, 3 if atlas.ndim == 3 else 1
+        atlas, uv = np.ascontiguousarray(atlas), np.ascontiguousarray(uv, dtype=np.float32)
+    return proj, heights, widths, mode, channels, vertices, triangles, vertex_colors, uv, atlas
+
+
+def resolve_render_colors(colors, has_atlas, has_vertex_colors):
+    """The colour mode of `Mesh.render` from its `colors` argument and what the mesh has."""
+    if colors is None:
+        return RENDER_NONE
+    if colors == "auto":
+        return RENDER_ATLAS if has_atlas else (RENDER_VERTEX if has_vertex_colors else RENDER_NONE)
+    if colors == "atlas":
+        if not has_atlas:
+            raise ValueError('colors="atlas" needs an atlas: call texture() first')
+        return RENDER_ATLAS
+    if colors == "vertex":
+        if not has_vertex_colors:
+            raise ValueError('colors="vertex" needs vertex colours: call colors() first')
+        return RENDER_VERTEX
+    raise ValueError('colors must be "auto", "atlas", "vertex" or None')
+
+
+class MeshRender:
+    """What `Mesh.render` returns; the arrays stay on the device until they are asked for.  Per camera: depth float32 [h,w]
+    (NaN where nothing draws), triangle int32 [h,w] (-1 there), bary float32 [h,w,3] (zeros there), color uint8 [h,w] or
+    [h,w,3] in the channel order of its source (fill there; None for a render without colour).  sizes = [(width, height)]."""
+
+    def __init__(self, state, heights, widths, channels, has_color):
+        self._m, self.channels, self.has_color = state, int(channels), bool(has_color)
+        self.sizes = [(int(w), int(h)) for h, w in zip(heights, widths)]
+        self._host = {}
+
+    def _split(self, name, tail=()):
+        if name not in self._host:
+            flat = self._m[name].cpu().numpy().reshape(-1)
+            per = int(np.prod(tail, dtype=np.int64)) if tail else 1
+            out, o = [], 0
+            for w, h in self.sizes:
+                out.append(flat[o * per:(o + h * w) * per].reshape((h, w) + tail))
+                o += h * w
+            self._host[name] = out
+        return self._host[name]
+
+    depth = property(lambda self: self._split("depth"))
+    triangle = property(lambda self: self._split("triangle"))
+    bary = property(lambda self: self._split("bary", (3,)))
+
+    @property
+    def color(self):
+        if not self.has_color:
+            return None
+        return self._split("color", () if self.channels == 1 else (3,))
+
+    @property
+    def coverage(self):
+        """The share of drawn pixels per camera (0 for a camera without a pixel)."""
+        return [float((t >= 0).mean()) if t.size else 0.0 for t in self.triangle]
+
+    @property
+    def n_large(self):
+        """The (camera, triangle) boxes of more than 64 pixels, which the second raster pass drew: the workspace's first word."""
+        return int(self._m["ws"][:8].cpu().numpy().view(np.uint64)[0])
+
+    def save_png(self, path, camera=0):
+        """The colour image of one camera as a PNG (`write_png`); three channels are taken as BGR and written as RGB, like
+        the atlas."""
+        from .interchange import write_png
+        if not self.has_color:
+            raise ValueError("save_png() needs a render with colour")
+        image = self.color[camera]
+        write_png(path, image[:, :, ::-1] if image.ndim == 3 else image)
+
+
+def _render(dev, proj, heights, widths, n_vertices, d_vertices, n_triangles, d_triangles, mode, channels, d_vertex_colors, d_uv, d_atlas,
+            atlas_size, fill):
+    """The device call: proj [n_cam,12], heights and widths (int32) on the host; the mesh and the colour source on the device."""
+    import torch
+    h = _lib.get_handle(dev.index)
+    n_cam = len(heights)
+    heights, widths = np.ascontiguousarray(heights, dtype=np.int32), np.ascontiguousarray(widths, dtype=np.int32)
+    d_proj = torch.from_numpy(np.ascontiguousarray(proj, dtype=np.float64).reshape(-1, 12)).to(dev) if n_cam else torch.zeros((1, 12), dtype=torch.float64, device=dev)
+    hp = lambda a: C.c_void_p(a.ctypes.data) if len(a) else None
+    need = C.c_int64()
+    h.check(h.lib.sfm_mesh_render_workspace_bytes(n_cam, hp(heights), hp(widths), int(n_vertices), int(n_triangles), C.byref(need)),
+            "sfm_mesh_render_workspace_bytes")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    n_pix = int((heights.astype(np.int64) * widths.astype(np.int64)).sum())
+    n = max(n_pix, 1)
+    out = {"depth": torch.empty(n, dtype=torch.float32, device=dev), "triangle": torch.empty(n, dtype=torch.int32, device=dev),
+           "bary": torch.empty(n * 3, dtype=torch.float32, device=dev)}
+    if mode != RENDER_NONE:
+        out["color"] = torch.empty(n * channels, dtype=torch.uint8, device=dev)
+    dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    h.call("sfm_mesh_render", n_cam, hp(heights), hp(widths), dp(d_proj), int(n_vertices), dp(d_vertices), int(n_triangles), dp(d_triangles),
+           int(mode), int(channels), dp(d_vertex_colors), dp(d_uv), dp(d_atlas), int(atlas_size[0]), int(atlas_size[1]), int(fill),
+           dp(out["depth"]), dp(out["triangle"]), dp(out["bary"]), dp(out.get("color")), dp(ws), need.value)
+    out["ws"] = ws
+    out["held"] = (d_proj, d_vertices, d_triangles, d_vertex_colors, d_uv, d_atlas)         # alive while the call may still run
+    return MeshRender(out, heights, widths, channels, mode != RENDER_NONE)
+
+
+def render_mesh(vertices, triangles, proj, sizes, vertex_colors=None, uv=None, atlas=None, fill=0, device=0):
+    """`sfm_mesh_render` on arrays that were made elsewhere: vertices float64 [nv,3], triangles int32 [nt,3] (a triangle with
+    an index outside 0 .. nv - 1 draws nothing), proj and sizes as `Mesh.render` takes cameras and sizes, and one source of
+    colour or none: vertex_colors uint8 [nv] or [nv,3], or uv float32 [nt,3,2] with atlas uint8 [H,W] or [H,W,3].  Returns
+    a `MeshRender`."""
+    import torch
+    proj, heights, widths, mode, channels, vertices, tri, vcol, uv, atlas = check_render_arguments(
+        proj, sizes, fill, vertices, np.zeros((0, 3), np.int32) if triangles is None else triangles, vertex_colors, uv, atlas)
+    _lib.get_handle(device)
+    dev = torch.device("cuda", device)
+    up = lambda a: None if a is None else torch.from_numpy(np.concatenate([a.reshape(-1), np.zeros(1, a.dtype)])).to(dev)      # a pointer must exist
+    size = (0, 0) if atlas is None else (atlas.shape[1], atlas.shape[0])
+    return _render(dev, proj, heights, widths, len(vertices), up(vertices), len(tri), up(tri), mode, channels, up(vcol), up(uv), up(atlas), size, fill)

@@ -1097,8 +1097,9 @@ def measure_depth(reps=20, emit=None, mesh=False):
     of the same run: sfm_tsdf_integrate of the 36 filtered maps into 256^3 nodes (a cube around the kept pixels, truncation 3
     voxels), sfm_mesh_mark and sfm_mesh_emit (min_weight 1), then sfm_mesh_colors of that mesh from the 36 views (BGR, tol 3
     voxels, min_cos 0.35) with its vertex-view projections per second, and sfm_mesh_texture of the same mesh from the same views
-    at texels 8 with its texel-view projections per second (the texels of the triangles' patches x views), whole calls by HIP
-    events; the row is then named "mesh"."""
+    at texels 8 with its texel-view projections per second (the texels of the triangles' patches x views), then sfm_mesh_render
+    of that mesh into its 36 views with that atlas (ms per camera, pixels and triangle-camera pairs per second, the length of
+    the large-box list), whole calls by HIP events; the row is then named "mesh"."""
     import torch
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from depth_reference import make_scene
@@ -1259,7 +1260,28 @@ def measure_depth(reps=20, emit=None, mesh=False):
                     "texture_share_of_texels_in_a_triangle": owned / max(aw * ah, 1), "texture_share_of_those_with_a_view": with_view / max(owned, 1),
                     "texture_projections": owned * n_img, "ms_mesh_texture": timed(run_mesh_texture, reps) * 1e3})
         row["texture_projections_per_s"] = row["texture_projections"] / (row["ms_mesh_texture"] * 1e-3)
-        del atlas, aviews, auv, texture_ws
+        # the render of the same mesh into its 36 views with that atlas, beside the texture call above as its yardstick
+        h.check(h.lib.sfm_mesh_render_workspace_bytes(n_img, hp(heights), hp(widths), nv, nt, C.byref(need)), "sfm_mesh_render_workspace_bytes")
+        render_need = need.value
+        render_ws = torch.empty(render_need, dtype=torch.uint8, device=dev)
+        r_depth = torch.empty(n_out, dtype=torch.float32, device=dev)
+        r_tri = torch.empty(n_out, dtype=torch.int32, device=dev)
+        r_bary = torch.empty(n_out * 3, dtype=torch.float32, device=dev)
+        r_color = torch.empty(n_out * 3, dtype=torch.uint8, device=dev)
+
+        def run_mesh_render():
+            h.call("sfm_mesh_render", n_img, hp(heights), hp(widths), _p(d_proj), nv, _p(vertices), nt, _p(triangles), 2, 3, None, _p(auv), _p(atlas),
+                   aw, ah, 0, _p(r_depth), _p(r_tri), _p(r_bary), _p(r_color), _p(render_ws), render_need)
+        for _ in range(3):
+            run_mesh_render()
+        ms_render = timed(run_mesh_render, reps) * 1e3
+        drawn = r_tri >= 0
+        row.update({"render_cameras": n_img, "ms_mesh_render": ms_render, "ms_mesh_render_per_camera": ms_render / n_img,
+                    "render_pixels_per_s": n_out / (ms_render * 1e-3), "render_triangle_camera_pairs": nt * n_img,
+                    "render_triangle_camera_pairs_per_s": nt * n_img / (ms_render * 1e-3),
+                    "render_large_boxes": int(render_ws[:8].cpu().numpy().view(np.uint64)[0]), "render_workspace_bytes": render_need,
+                    "render_share_of_pixels_drawn": float(drawn.float().mean().item())})
+        del atlas, aviews, auv, texture_ws, render_ws, r_depth, r_tri, r_bary, r_color, drawn
         zv = vertices[:nv, 2].cpu().numpy()
         seen = int((weight != 0).sum().item())
         row.update({"grid_nodes": [nx, ny, nz], "voxel": float(voxel), "nodes_seen": seen, "projections": nx * ny * nz * n_img,

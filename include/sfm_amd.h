@@ -1229,6 +1229,58 @@ int sfm_mesh_render(sfm_handle h, int32_t n_cam, const int32_t* heights /* host 
                     int32_t fill, float* depth /* [n_pix] */, int32_t* triangle /* [n_pix] */, float* bary /* [n_pix][3] */,
                     uint8_t* color /* [n_pix][channels], or NULL */, void* workspace, int64_t workspace_bytes);
 
+/* ---- score of a render against the photographs: error, PSNR and SSIM sums and the distance to the views' own depth
+ *      (sfm_amd/csrc/render_score.hip, render_score_rule.h, render_score_plan.h) ----
+ * A pure function of its inputs.  Every statistic is an INTEGER sum, so no order of summation exists and NumPy reproduces
+ * every output byte whatever the launch geometry (tests/render_score_reference.py); the two quotients are float64 without
+ * FMA contraction.
+ * Inputs.  n_view views in the order of the render: heights / widths (HOST, 0 .. 32768 each); the arrays of view v start at
+ *   pixel off[v] = sum over v' < v of heights[v'] * widths[v'] (times channels for the colour arrays).  channels c is 1 or 3.
+ *   From the render (sfm_mesh_render): render_color uint8 [h][w][c], render_triangle int32 [h][w], render_depth float32 [h][w].
+ *   photos uint8 [h][w][c].  Optional: photo_mask uint8 [h][w]; view_depth float32 [h][w] with view_keep uint8 [h][w], the
+ *   view's own depth map and what sfm_depth_filter kept of it (both or neither).
+ * Per view of w x h pixels:
+ *   1. A pixel is covered iff triangle >= 0, and compared iff it is covered and the mask, if given, is > 0.  Per channel k
+ *      with e = render - photo in integers: sad[k] += |e| and sse[k] += e e over the compared pixels; abs_error is |e| there
+ *      and 0 elsewhere.
+ *   2. SSIM over a uniform W x W window, W = window odd in 3 .. 11, n = W W.  A pixel has a window iff all n pixels of the
+ *      window centred on it are inside the image and compared.  Per channel over the window in int64, x the render and y the
+ *      photograph: Sx, Sy, Sxx, Syy, Sxy;  a = 2 Sx Sy,  b = Sx Sx + Sy Sy,  cv = 2 (n Sxy - Sx Sy),
+ *      vr = (n Sxx - Sx Sx) + (n Syy - Sy Sy),  c1 = (double)(n n) * 6.5025,  c2 = (double)(n n) * 58.5225 (the usual
+ *      (0.01 * 255)^2 and (0.03 * 255)^2 scaled by n^2),
+ *        s_k = (((double)a + c1) * ((double)cv + c2)) / (((double)b + c1) * ((double)vr + c2)).
+ *      This is the population covariance (divisor n), not the sample covariance (n - 1).  The denominator is positive, so
+ *      no NaN arises.  s = s_0, or ((s_0 + s_1) + s_2) / 3.0 for three channels.  ssim_map = (float)s, the quiet NaN
+ *      0x7FC00000 where there is no window.  n_ssim += 1 and q_ssim += (int64)floor(s * 16777216.0 + 0.5), a signed sum.
+ *   3. Depth, only with view_depth.  A pixel is seen iff keep != 0 and dv = view_depth is finite.  n_both counts covered and
+ *      seen pixels; there r = |(double)dr - (double)dv| with dr = render_depth.  When r is a NaN nothing more is counted.
+ *      Otherwise n_agree += (r <= rel_tol * (double)dv) and q_rel += (int64)floor(t * 16777216.0 + 0.5), where
+ *      t = min(r / (double)dv, 1.0) for dv > 0; for dv <= 0, where r / dv is no relative error, t = 0.0 when r == 0 and 1.0
+ *      otherwise (such a pixel agrees only when dr == dv == 0).  n_render_only counts covered pixels that are not seen,
+ *      n_view_only seen pixels that are not covered.
+ *   4. stats int64 [n_view][16]: n_pixels (h w), n_compared, sad[3], sse[3], n_ssim, q_ssim, n_both, n_agree, q_rel,
+ *      n_render_only, n_view_only, 0.  The columns of channels that are not there are 0, and so are the depth columns
+ *      without view_depth.  The call clears the table itself.  Means, PSNR = 10 log10(255^2 n_compared c / sum sse) and the
+ *      mean SSIM q_ssim / (2^24 n_ssim) are formed by the caller in double from these integers; pooled figures come from the
+ *      summed integers.
+ * Limits: a uniform window only (no Gaussian weights), one scale, no learned metric; no exposure compensation is estimated;
+ *   pixels the mesh does not cover are counted (n_view_only) and not penalised in the error.
+ * abs_error (uint8 [h][w][c]) and ssim_map (float32 [h][w]) may each be NULL: statistics only.  The workspace
+ *   (sfm_render_score_workspace_bytes; render_score_plan.h has the layout) holds the table of the views.
+ *   sfm_render_score_tile gives the sides of the tile one workgroup takes.  Nothing is written outside the pixels of the
+ *   views and the n_view rows of stats.  SFM_ERR_ARG before any device work for a null handle, n_view outside 0 .. 65535, a
+ *   side outside 0 .. 32768, channels not 1 or 3, window even or outside 3 .. 11, rel_tol not finite or negative, view_keep
+ *   without view_depth or the reverse, a null pointer (heights / widths / stats may be null only without a view, the four
+ *   images only without a pixel), or a workspace that is missing or too small. */
+int sfm_render_score_tile(int32_t* tile_w, int32_t* tile_h);
+int sfm_render_score_workspace_bytes(int32_t n_view, const int32_t* heights /* host */, const int32_t* widths /* host */,
+                                     int64_t* bytes_host);
+int sfm_render_score(sfm_handle h, int32_t n_view, const int32_t* heights /* host */, const int32_t* widths /* host */,
+                     int32_t channels, const uint8_t* render_color, const int32_t* render_triangle, const float* render_depth,
+                     const uint8_t* photos, const uint8_t* photo_mask /* or NULL */, const float* view_depth /* or NULL */,
+                     const uint8_t* view_keep /* or NULL */, int32_t window, double rel_tol, int64_t* stats /* [n_view][16] */,
+                     uint8_t* abs_error /* or NULL */, float* ssim_map /* or NULL */, void* workspace, int64_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

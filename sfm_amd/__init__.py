@@ -12,4 +12,5 @@ from .interchange import read_pnm, save_obj_mesh, save_ply_mesh, save_ply_points
 from .guided import guided_match_pairs  # noqa: F401
 from .depth import (DepthMaps, FusedCloud, dense_from_reconstruction, depth_maps, depth_maps_from_arrays, depth_ranges, plane_depths, select_sources,  # noqa: F401
                     view_backprojection, view_warps)
-from .mesh import Mesh, MeshRender, MeshTexture, TsdfVolume, mesh_texture, mesh_vertex_colors, render_mesh, tsdf_volume_from_arrays  # noqa: F401
+from .mesh import (Mesh, MeshRender, MeshTexture, RenderScore, TsdfVolume, check_score_arguments, mesh_texture, mesh_vertex_colors, render_mesh,  # noqa: F401
+                   score_render, tsdf_volume_from_arrays)

@@ -193,6 +193,9 @@ SIGNATURES = {
                                    vp, i64]),
     "sfm_mesh_render_workspace_bytes": (C.c_int, [i32, vp, vp, i64, i64, C.POINTER(i64)]),
     "sfm_mesh_render": (C.c_int, [vp, i32, vp, vp, vp, i64, vp, i64, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i64]),
+    "sfm_render_score_tile": (C.c_int, [C.POINTER(i32), C.POINTER(i32)]),
+    "sfm_render_score_workspace_bytes": (C.c_int, [i32, vp, vp, C.POINTER(i64)]),
+    "sfm_render_score": (C.c_int, [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, f64, vp, vp, vp, vp, i64]),
 }
 
 _lib = None

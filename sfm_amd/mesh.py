@@ -5,7 +5,9 @@ without a depth carries no evidence (free space outside every silhouette stays u
 are not filled and zero-area triangles are kept.  `sfm_mesh_colors` (sfm_amd/csrc/mesh_color.hip) gives every vertex a colour
 blended over the views whose own depth maps see it, `sfm_mesh_texture` (sfm_amd/csrc/mesh_texture.hip) every triangle a
 patch of texels in an atlas by the same blend, and `sfm_mesh_render` (sfm_amd/csrc/mesh_render.hip) draws the mesh through
-any camera: depth, triangle, barycentrics and colour per pixel.  No CPU fallback: without the library or a GPU the calls raise.
+any camera: depth, triangle, barycentrics and colour per pixel; `sfm_render_score` (sfm_amd/csrc/render_score.hip) scores such a
+render against the photographs: error, PSNR and SSIM sums and the distance to the views' own depth.  No CPU fallback: without the
+library or a GPU the calls raise.
 """
 from __future__ import annotations
 
@@ -152,6 +154,18 @@ class Mesh:
         n_ref = len(maps.views)
         proj = projections_from_backprojections(maps._s["backproj"].cpu().numpy()[:n_ref])
         return self.render(list(proj), [(w, h) for h, w in maps.shapes], colors, fill)
+
+    def score(self, images, maps=None, colors="auto", **options):
+        """`render_views(maps, colors).compare(images, maps, **options)`: every view drawn again and scored against its
+        photograph and its own depth map (`sfm_render_score`).  images: one array per IMAGE of the set, as `colors()` and
+        `texture()` take them, or one per view; options: masks, window, rel_tol, keep_maps of `MeshRender.compare`.
+        Returns a `RenderScore`."""
+        maps = getattr(self._volume, "_maps", None) if maps is None else maps
+        if maps is None:
+            raise ValueError("score() needs maps: the mesh's volume was not built by DepthMaps.tsdf()")
+        if len(images) == len(maps._s["imgs"]):
+            images = [images[r] for r in maps.views]
+        return self.render_views(maps, colors).compare(images, maps, **options)
 
     def save(self, path, colors=None):
         """Binary PLY with normals (`save_ply_mesh`); colors: None for vertex_colors when `colors()` has made them."""
@@ -710,6 +724,31 @@ class MeshRender:
         image = self.color[camera]
         write_png(path, image[:, :, ::-1] if image.ndim == 3 else image)
 
+    def compare(self, images, maps=None, masks=None, window=7, rel_tol=0.02, keep_maps=True):
+        """The render scored against photographs on the device (`sfm_render_score`; include/sfm_amd.h states the rule): per
+        camera the absolute and squared error and the SSIM over a uniform window, over the pixels the mesh covers, and how
+        far the rendered depth is from the view's own.  images: one uint8 array per camera of the render, shaped like its
+        `color`; maps: a filtered `DepthMaps` whose views are the render's cameras, or None for no depth columns; masks:
+        None or one uint8 [h,w] array per camera, a pixel is compared where it is > 0; keep_maps: False for the statistics
+        alone.  Returns a `RenderScore`."""
+        if not self.has_color:
+            raise ValueError("compare() needs a render with colour")
+        heights = np.array([h for w, h in self.sizes], dtype=np.int32)
+        widths = np.array([w for w, h in self.sizes], dtype=np.int32)
+        photos, masks = check_score_arguments(heights, widths, self.channels, images, masks, window, rel_tol)
+        d_depth = d_keep = None
+        if maps is not None:
+            if getattr(maps, "keep", None) is None:
+                raise ValueError("compare() needs filter() first")
+            if [(w, h) for h, w in maps.shapes] != self.sizes:
+                raise ValueError("maps: its views must be the render's cameras, each at the size of its maps")
+            d_depth, d_keep = maps._s["depth"], maps._s["keep"]
+        import torch
+        dev = self._m["triangle"].device
+        up = lambda a: None if a is None else torch.from_numpy(np.concatenate([a, np.zeros(1, a.dtype)])).to(dev)   # a pointer must exist
+        return _score(dev, heights, widths, self.channels, self._m["color"], self._m["triangle"], self._m["depth"], up(photos), up(masks),
+                      d_depth, d_keep, window, rel_tol, keep_maps)
+
 
 def _render(dev, proj, heights, widths, n_vertices, d_vertices, n_triangles, d_triangles, mode, channels, d_vertex_colors, d_uv, d_atlas,
             atlas_size, fill):
@@ -752,3 +791,217 @@ def render_mesh(vertices, triangles, proj, sizes, vertex_colors=None, uv=None, a
     up = lambda a: None if a is None else torch.from_numpy(np.concatenate([a.reshape(-1), np.zeros(1, a.dtype)])).to(dev)      # a pointer must exist
     size = (0, 0) if atlas is None else (atlas.shape[1], atlas.shape[0])
     return _render(dev, proj, heights, widths, len(vertices), up(vertices), len(tri), up(tri), mode, channels, up(vcol), up(uv), up(atlas), size, fill)
+
+
+# ------------------------------------------------------------------------------------------- score
+SCORE_COLUMNS = 16
+(SCORE_N_PIXELS, SCORE_N_COMPARED, SCORE_SAD, SCORE_SSE, SCORE_N_SSIM, SCORE_Q_SSIM, SCORE_N_BOTH, SCORE_N_AGREE, SCORE_Q_REL,
+ SCORE_N_RENDER_ONLY, SCORE_N_VIEW_ONLY) = (0, 1, 2, 5, 8, 9, 10, 11, 12, 13, 14)
+SCORE_Q = 16777216.0                                               # q_ssim and q_rel count in units of 2^-24
+MIN_WINDOW, MAX_WINDOW = 3, 11
+
+
+def score_tile():
+    """(width, height) of the tile one workgroup of `sfm_render_score` takes, from the library."""
+    w, h = C.c_int32(), C.c_int32()
+    if _lib.load().sfm_render_score_tile(C.byref(w), C.byref(h)) != 0:
+        raise _lib.SfmError("sfm_render_score_tile failed")
+    return w.value, h.value
+
+
+def check_score_arguments(heights, widths, channels, images, masks=None, window=7, rel_tol=0.02):
+    """What `MeshRender.compare` and `score_render` check before the device: (photos uint8 flat, masks uint8 flat or None) or
+    ValueError.  heights / widths: the sizes of the render's cameras; images: one uint8 [h,w] (channels 1) or [h,w,3] array per
+    camera; masks: None or one uint8 [h,w] array per camera."""
+    whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    if channels not in (1, 3):
+        raise ValueError("channels must be 1 or 3")
+    if not (whole(window) and MIN_WINDOW <= window <= MAX_WINDOW and window % 2 == 1):
+        raise ValueError(f"window must be an odd integer {MIN_WINDOW} .. {MAX_WINDOW}")
+    if not (isinstance(rel_tol, Real) and not isinstance(rel_tol, bool) and np.isfinite(rel_tol) and rel_tol >= 0):
+        raise ValueError("rel_tol must be a finite number >= 0")
+    n = len(heights)
+    if n > MAX_CAMERAS:
+        raise ValueError(f"at most {MAX_CAMERAS} views")
+    if any(not (0 <= int(v) <= MAX_IMAGE_SIDE) for v in list(heights) + list(widths)):
+        raise ValueError(f"every image side must be 0 .. {MAX_IMAGE_SIDE}")
+
+    def flat(arrays, what, tail):
+        try:
+            arrays = list(arrays)
+        except TypeError:
+            raise ValueError(f"{what}: one array per camera of the render") from None
+        if len(arrays) != n:
+            raise ValueError(f"{what}: one array per camera of the render")
+        out = []
+        for a, h, w in zip(arrays, heights, widths):
+            a = np.asarray(a)
+            if a.dtype != np.uint8 or a.shape != (int(h), int(w)) + tail:
+                raise ValueError(f"{what}: every array must be uint8 {['h', 'w'] + list(tail)}, shaped like the render")
+            out.append(np.ascontiguousarray(a).reshape(-1))
+        return np.concatenate(out) if out else np.zeros(0, np.uint8)
+
+    photos = flat(images, "images", () if channels == 1 else (3,))
+    return photos, None if masks is None else flat(masks, "masks", ())
+
+
+def score_figures(stats, channels):
+    """The figures of one row of the table, or of the sum of several rows, formed in double from the integers: dict(n_compared,
+    mae [c], mse [c], psnr, ssim, n_ssim, depth_both, depth_agree, depth_rel, render_only, view_only).  A mean over nothing is
+    NaN; PSNR = 10 log10(255^2 n_compared c / sum sse) is inf for a squared error of 0."""
+    import math
+    s = [int(v) for v in np.asarray(stats, dtype=np.int64).reshape(-1, SCORE_COLUMNS).sum(0)]
+    n = s[SCORE_N_COMPARED]
+    div = lambda a, b: a / b if b else float("nan")
+    sse = sum(s[SCORE_SSE:SCORE_SSE + channels])
+    psnr = float("nan") if n == 0 else (float("inf") if sse == 0 else 10.0 * math.log10(65025.0 * n * channels / sse))
+    return dict(n_compared=n, mae=[div(s[SCORE_SAD + k], n) for k in range(channels)], mse=[div(s[SCORE_SSE + k], n) for k in range(channels)],
+                psnr=psnr, ssim=div(s[SCORE_Q_SSIM], SCORE_Q * s[SCORE_N_SSIM]), n_ssim=s[SCORE_N_SSIM], depth_both=s[SCORE_N_BOTH],
+                depth_agree=div(s[SCORE_N_AGREE], s[SCORE_N_BOTH]), depth_rel=div(s[SCORE_Q_REL], SCORE_Q * s[SCORE_N_BOTH]),
+                render_only=s[SCORE_N_RENDER_ONLY], view_only=s[SCORE_N_VIEW_ONLY])
+
+
+class RenderScore:
+    """What `MeshRender.compare` returns; the arrays stay on the device until they are asked for.  stats int64 [n,16] is the
+    table of `sfm_render_score`; per view from it: n_compared, mae and mse float64 [n,c], psnr, ssim (NaN without a window),
+    n_ssim, depth_both, depth_agree (the share of depth_both within rel_tol), depth_rel (the mean relative difference, each
+    capped at 1), render_only, view_only.  abs_error uint8 [h,w] or [h,w,3] and ssim_map float32 [h,w] (NaN without a window)
+    per view; None when the maps were not kept."""
+
+    def __init__(self, state, heights, widths, channels, window, rel_tol, has_maps):
+        self._m, self.channels, self.window, self.rel_tol, self.has_maps = state, int(channels), int(window), float(rel_tol), bool(has_maps)
+        self.sizes = [(int(w), int(h)) for h, w in zip(heights, widths)]
+        self._host = {}
+
+    _split = MeshRender._split
+
+    @property
+    def stats(self):
+        if "stats" not in self._host:
+            self._host["stats"] = self._m["stats"].cpu().numpy().reshape(-1)[:len(self.sizes) * SCORE_COLUMNS].reshape(-1, SCORE_COLUMNS)
+        return self._host["stats"]
+
+    @property
+    def abs_error(self):
+        return self._split("abs_error", () if self.channels == 1 else (3,)) if self.has_maps else None
+
+    @property
+    def ssim_map(self):
+        return self._split("ssim_map") if self.has_maps else None
+
+    def _figures(self):
+        if "figures" not in self._host:
+            self._host["figures"] = [score_figures(row, self.channels) for row in self.stats]
+        return self._host["figures"]
+
+    def _column(self, name, dtype):
+        return np.array([f[name] for f in self._figures()], dtype=dtype).reshape((len(self.sizes),) + ((self.channels,) if name in ("mae", "mse") else ()))
+
+    n_compared = property(lambda self: self._column("n_compared", np.int64))
+    mae = property(lambda self: self._column("mae", np.float64))
+    mse = property(lambda self: self._column("mse", np.float64))
+    psnr = property(lambda self: self._column("psnr", np.float64))
+    ssim = property(lambda self: self._column("ssim", np.float64))
+    n_ssim = property(lambda self: self._column("n_ssim", np.int64))
+    depth_both = property(lambda self: self._column("depth_both", np.int64))
+    depth_agree = property(lambda self: self._column("depth_agree", np.float64))
+    depth_rel = property(lambda self: self._column("depth_rel", np.float64))
+    render_only = property(lambda self: self._column("render_only", np.int64))
+    view_only = property(lambda self: self._column("view_only", np.int64))
+
+    def pooled(self):
+        """The figures of all views together (`score_figures` of the summed integers, not a mean of the views' figures)."""
+        return score_figures(self.stats, self.channels)
+
+    def worst(self, k=5, by="ssim"):
+        """The positions of the k worst views: the lowest ssim, psnr or depth_agree, the highest mae (mean over the channels)
+        or depth_rel; a view without a figure (NaN) comes last."""
+        if by not in ("ssim", "psnr", "mae", "depth_agree", "depth_rel"):
+            raise ValueError('by must be "ssim", "psnr", "mae", "depth_agree" or "depth_rel"')
+        v = getattr(self, by)
+        v = v.mean(axis=1) if by == "mae" else v
+        key = -v if by in ("mae", "depth_rel") else v
+        order = np.argsort(np.where(np.isnan(key), np.inf, key), kind="stable")
+        return [int(i) for i in order[:max(int(k), 0)]]
+
+    def save_png(self, path, camera=0, what="error"):
+        """One view's map as a PNG (`write_png`): what="error" writes abs_error (three channels are taken as BGR and written as
+        RGB, like the render), what="ssim" writes ssim_map mapped linearly from [-1, 1] to 0 .. 255, NaN to 0."""
+        from .interchange import write_png
+        if not self.has_maps:
+            raise ValueError("save_png() needs the maps: compare(..., keep_maps=True)")
+        if what == "error":
+            image = self.abs_error[camera]
+            write_png(path, image[:, :, ::-1] if image.ndim == 3 else image)
+        elif what == "ssim":
+            write_png(path, ssim_to_gray(self.ssim_map[camera]))
+        else:
+            raise ValueError('what must be "error" or "ssim"')
+
+
+def ssim_to_gray(ssim_map):
+    """uint8 from an SSIM map: floor((s + 1) * 127.5 + 0.5) cut to 0 .. 255, NaN to 0."""
+    s = np.asarray(ssim_map, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        g = np.clip(np.floor((s + 1.0) * 127.5 + 0.5), 0.0, 255.0)
+    return np.where(np.isnan(s), 0.0, g).astype(np.uint8)
+
+
+def _score(dev, heights, widths, channels, d_color, d_triangle, d_depth, d_photos, d_masks, d_view_depth, d_view_keep, window, rel_tol, keep_maps):
+    """The device call: heights and widths (int32) on the host, everything else on the device, views back to back."""
+    import torch
+    h = _lib.get_handle(dev.index)
+    n_view = len(heights)
+    heights, widths = np.ascontiguousarray(heights, dtype=np.int32), np.ascontiguousarray(widths, dtype=np.int32)
+    hp = lambda a: C.c_void_p(a.ctypes.data) if len(a) else None
+    dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    need = C.c_int64()
+    h.check(h.lib.sfm_render_score_workspace_bytes(n_view, hp(heights), hp(widths), C.byref(need)), "sfm_render_score_workspace_bytes")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    n = max(int((heights.astype(np.int64) * widths.astype(np.int64)).sum()), 1)
+    out = {"stats": torch.empty(max(n_view, 1) * SCORE_COLUMNS, dtype=torch.int64, device=dev)}
+    if keep_maps:
+        out["abs_error"] = torch.empty(n * channels, dtype=torch.uint8, device=dev)
+        out["ssim_map"] = torch.empty(n, dtype=torch.float32, device=dev)
+    h.call("sfm_render_score", n_view, hp(heights), hp(widths), int(channels), dp(d_color), dp(d_triangle), dp(d_depth), dp(d_photos), dp(d_masks),
+           dp(d_view_depth), dp(d_view_keep), int(window), C.c_double(float(rel_tol)), dp(out["stats"]), dp(out.get("abs_error")),
+           dp(out.get("ssim_map")), dp(ws), need.value)
+    out["held"] = (ws, d_color, d_triangle, d_depth, d_photos, d_masks, d_view_depth, d_view_keep)        # alive while the call may still run
+    return RenderScore(out, heights, widths, channels, window, rel_tol, keep_maps)
+
+
+def score_render(color, triangle, depth, photos, view_depth=None, view_keep=None, masks=None, window=7, rel_tol=0.02, device=0):
+    """`sfm_render_score` on arrays that were made elsewhere: per view color uint8 [h,w] or [h,w,3], triangle int32 [h,w] and
+    depth float32 [h,w] as a render holds them, photos shaped like color; view_depth float32 [h,w] with view_keep uint8 [h,w]
+    per view (both or neither; view_keep None with view_depth keeps every pixel), masks uint8 [h,w].  Returns a `RenderScore`."""
+    import torch
+    try:
+        color = [np.asarray(c) for c in color]
+    except TypeError:
+        raise ValueError("color: one array per view") from None
+    if any(c.dtype != np.uint8 or c.ndim not in (2, 3) or (c.ndim == 3 and c.shape[2] != 3) for c in color) or len({c.ndim for c in color}) > 1:
+        raise ValueError("color: uint8 [h,w] or [h,w,3] arrays, all with the same channel count")
+    channels = 3 if (color and color[0].ndim == 3) else 1
+    heights = np.array([c.shape[0] for c in color], dtype=np.int32)
+    widths = np.array([c.shape[1] for c in color], dtype=np.int32)
+    flat_photos, flat_masks = check_score_arguments(heights, widths, channels, photos, masks, window, rel_tol)
+    if view_depth is None and view_keep is not None:
+        raise ValueError("view_keep comes with view_depth")
+
+    def flat(arrays, what, dtype):
+        arrays = list(arrays)
+        if len(arrays) != len(color) or any(np.shape(a) != (h, w) for a, h, w in zip(arrays, heights, widths)):
+            raise ValueError(f"{what}: one [h,w] array per view, shaped like the render")
+        return np.concatenate([np.ascontiguousarray(a, dtype=dtype).reshape(-1) for a in arrays] + [np.zeros(1, dtype)])
+
+    tri, dr = flat(triangle, "triangle", np.int32), flat(depth, "depth", np.float32)
+    vd = vk = None
+    if view_depth is not None:
+        vd = flat(view_depth, "view_depth", np.float32)
+        vk = np.ones(len(vd), np.uint8) if view_keep is None else flat(view_keep, "view_keep", np.uint8)
+    _lib.get_handle(device)
+    dev = torch.device("cuda", device)
+    up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
+    pad = lambda a: None if a is None else np.concatenate([a, np.zeros(1, a.dtype)])                          # a pointer must exist
+    col = pad(np.concatenate([c.reshape(-1) for c in color]) if color else np.zeros(0, np.uint8))
+    return _score(dev, heights, widths, channels, up(col), up(tri), up(dr), up(pad(flat_photos)), up(pad(flat_masks)), up(vd), up(vk), window, rel_tol, True)

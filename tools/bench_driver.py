@@ -1099,7 +1099,9 @@ def measure_depth(reps=20, emit=None, mesh=False):
     voxels, min_cos 0.35) with its vertex-view projections per second, and sfm_mesh_texture of the same mesh from the same views
     at texels 8 with its texel-view projections per second (the texels of the triangles' patches x views), then sfm_mesh_render
     of that mesh into its 36 views with that atlas (ms per camera, pixels and triangle-camera pairs per second, the length of
-    the large-box list), whole calls by HIP events; the row is then named "mesh"."""
+    the large-box list), then sfm_render_score of those 36 renders against the 36 images (window 7: once with both maps written and
+    the views' depth, once the statistics alone; ms per view and the pooled figures), whole calls by HIP events; the row is then
+    named "mesh"."""
     import torch
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from depth_reference import make_scene
@@ -1281,6 +1283,33 @@ def measure_depth(reps=20, emit=None, mesh=False):
                     "render_triangle_camera_pairs_per_s": nt * n_img / (ms_render * 1e-3),
                     "render_large_boxes": int(render_ws[:8].cpu().numpy().view(np.uint64)[0]), "render_workspace_bytes": render_need,
                     "render_share_of_pixels_drawn": float(drawn.float().mean().item())})
+        # the score of those 36 renders against their photographs (window 7, rel_tol 0.02): once with both maps written and
+        # with the views' depth, once the statistics alone; the render above and the filter pass are its yardsticks
+        h.check(h.lib.sfm_render_score_workspace_bytes(n_img, hp(heights), hp(widths), C.byref(need)), "sfm_render_score_workspace_bytes")
+        score_need = need.value
+        score_ws = torch.empty(score_need, dtype=torch.uint8, device=dev)
+        s_stats = torch.empty(n_img * 16, dtype=torch.int64, device=dev)
+        s_error = torch.empty(n_out * 3, dtype=torch.uint8, device=dev)
+        s_ssim = torch.empty(n_out, dtype=torch.float32, device=dev)
+
+        def run_score_full():
+            h.call("sfm_render_score", n_img, hp(heights), hp(widths), 3, _p(r_color), _p(r_tri), _p(r_depth), _p(d_bgr), None, _p(depth), _p(keep), 7,
+                   C.c_double(0.02), _p(s_stats), _p(s_error), _p(s_ssim), _p(score_ws), score_need)
+
+        def run_score_stats():
+            h.call("sfm_render_score", n_img, hp(heights), hp(widths), 3, _p(r_color), _p(r_tri), _p(r_depth), _p(d_bgr), None, None, None, 7,
+                   C.c_double(0.02), _p(s_stats), None, None, _p(score_ws), score_need)
+        for _ in range(3):
+            run_score_stats(); run_score_full()
+        ms_score_stats = timed(run_score_stats, reps) * 1e3
+        ms_score = timed(run_score_full, reps) * 1e3
+        pooled = mm.score_figures(s_stats.cpu().numpy(), 3)
+        row.update({"ms_render_score": ms_score, "ms_render_score_per_view": ms_score / n_img, "ms_render_score_stats_only": ms_score_stats,
+                    "ms_render_score_stats_only_per_view": ms_score_stats / n_img, "score_pixels_per_s": n_out / (ms_score * 1e-3),
+                    "score_window": 7, "score_mae": float(np.mean(pooled["mae"])), "score_psnr": pooled["psnr"], "score_ssim": pooled["ssim"],
+                    "score_windows": pooled["n_ssim"], "score_depth_agree": pooled["depth_agree"], "score_render_only": pooled["render_only"],
+                    "score_view_only": pooled["view_only"]})
+        del score_ws, s_stats, s_error, s_ssim
         del atlas, aviews, auv, texture_ws, render_ws, r_depth, r_tri, r_bary, r_color, drawn
         zv = vertices[:nv, 2].cpu().numpy()
         seen = int((weight != 0).sum().item())

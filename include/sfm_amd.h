@@ -404,6 +404,14 @@ int  sfm_ba_run_trf(sfm_handle h, sfm_ba_problem p, double* x, const sfm_trf_opt
  * row-major matrix and solves with the factor.  fail_flag: device int32, set when a pivot <= 0. */
 int sfm_dense_cholesky(sfm_handle h, double* a, int32_t n, int32_t* fail_flag);
 int sfm_dense_trsv(sfm_handle h, const double* l, int32_t n, double* b, int transpose);
+/* Test helpers: the solve's own path on a workspace the caller owns.  offsets_host [8]: the offsets, in doubles, of the
+ * regions Ld, Dinv, DinvT, inv64, flag, Lm, LmT and their total.  sfm_dense_factor_ws clears the flag word, factors
+ * a (device [nrows][n], nrows = n or n + 1: a last row leaves as L^-1 of it; a is consumed) into ws and synchronises;
+ * sfm_dense_trsv_ws solves L y = b (transpose 0) or L^T x = b (1) with what ws holds: b is destroyed, the flag is left
+ * as it is (1: a pivot was not positive, 2: a solve stalled). */
+int sfm_dense_ws_layout(int32_t n, int64_t* offsets_host);
+int sfm_dense_factor_ws(sfm_handle h, double* a, int32_t n, int32_t nrows, double* ws);
+int sfm_dense_trsv_ws(sfm_handle h, int32_t n, double* ws, double* b, double* xout, int transpose);
 
 /* ------------------------------------------------------------------ driver-side rows either side of the path
  * (SURVEY.md section 8f).  All three are batched over "segments" (one segment = one image pair), so the

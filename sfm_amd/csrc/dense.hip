@@ -964,3 +964,32 @@ extern "C" int sfm_dense_trsv(sfm_handle h, const double* l, int32_t n, double* 
   SFM_HIP(h, ws.release());
   return rc;
 }
+
+// The product path on a workspace the caller owns (tests read every region from it): the layout, the factorisation exactly as
+// ba_camera_cg.hip calls it - one cleared flag word, no other memset - and a solve on whatever the workspace holds.
+extern "C" int sfm_dense_ws_layout(int32_t n, int64_t* offsets_host) {
+  if (!offsets_host || n < 1) return SFM_ERR_ARG;
+  const DenseWsLayout l = dense_ws_layout(n);
+  const int64_t o[8] = {l.Ld, l.Dinv, l.DinvT, l.inv64, l.flag, l.Lm, l.LmT, l.total};
+  for (int i = 0; i < 8; ++i) offsets_host[i] = o[i];
+  return SFM_OK;
+}
+
+extern "C" int sfm_dense_factor_ws(sfm_handle h, double* a, int32_t n, int32_t nrows, double* ws) {
+  if (!h || !a || !ws || n < 1 || (nrows != n && nrows != n + 1)) return SFM_ERR_ARG;
+  DenseWs w; dense_ws_carve(ws, n, &w);
+  SFM_HIP(h, hipMemsetAsync(w.flag, 0, sizeof(int), h->stream));
+  const int rc = dense_cholesky(h, a, n, nrows, w);
+  if (rc != SFM_OK) return rc;
+  SFM_HIP(h, hipStreamSynchronize(h->stream));
+  return SFM_OK;
+}
+
+extern "C" int sfm_dense_trsv_ws(sfm_handle h, int32_t n, double* ws, double* b, double* xout, int transpose) {
+  if (!h || !ws || !b || !xout || n < 1) return SFM_ERR_ARG;
+  DenseWs w; dense_ws_carve(ws, n, &w);          // the flag keeps its value: a stalled solve stays visible as 2
+  const int rc = dense_trsv(h, n, w, b, xout, transpose ? 1 : 0);
+  if (rc != SFM_OK) return rc;
+  SFM_HIP(h, hipStreamSynchronize(h->stream));
+  return SFM_OK;
+}

@@ -1120,7 +1120,8 @@ int sfm_mesh_emit(sfm_handle h, const float* tsdf, int32_t nx, int32_t ny, int32
  *   n_views = min(m, 255) (uint8); best_view = best (int32, -1 for none).  colors is uint8 [n_vertices][channels].
  * Limits: one colour per vertex (sfm_mesh_texture below gives every triangle a patch of texels by the same rule), no
  *   exposure compensation; a vertex that no view sees gets fill and is not filled from its neighbours; every view that
- *   passes weighs by its angle only.
+ *   passes weighs by its angle only.  (Gains per view are estimated and applied in front of this call: "exposure of the
+ *   views" below.)
  * The workspace (sfm_mesh_colors_workspace_bytes) holds the view table.  Nothing is written at or above n_vertices, and
  *   the call returns at once for n_vertices == 0.  SFM_ERR_ARG before any device work for a null handle, what
  *   sfm_tsdf_integrate refuses about the views, channels not 1 or 3, n_vertices below 0 or above 2^31 - 1, tol not finite or
@@ -1134,6 +1135,61 @@ int sfm_mesh_colors(sfm_handle h, const int32_t* heights /* host */, const int32
                     const uint8_t* pixels, int32_t channels, int64_t n_vertices, const double* vertices, const float* normals,
                     double tol, double min_cos, int32_t fill, uint8_t* colors, uint8_t* n_views, int32_t* best_view,
                     void* workspace, int64_t workspace_bytes);
+
+/* ---- exposure of the views: one gain per view and channel, estimated from the mesh (sfm_amd/csrc/mesh_exposure.hip,
+ *      mesh_exposure_rule.h, mesh_exposure_plan.h) ----
+ * sfm_mesh_colors, sfm_mesh_texture and sfm_render_score assume that every photograph of a surface point holds the same
+ * value.  Where the exposure drifts between the shots, this stage estimates one gain per view and channel from the vertices
+ * that several views see and applies it to the images BEFORE they go to those calls, which do not change.  The device makes
+ * bytes and integer sums; the gains are solved on the host (sfm_amd/exposure.py, solve_gains).  NumPy reproduces every
+ * output byte (tests/mesh_exposure_reference.py).
+ * Sample (sfm_mesh_exposure_sample).  The views, the vertices, tol and min_cos are those of sfm_mesh_colors.  For vertex X
+ *   with the normal n and view v, steps 1 to 4 of sfm_mesh_colors unchanged: the view SEES the vertex iff it passes steps 1
+ *   to 3, and then q_k = (uint8) min(floor(s_k + 0.5), 255.0) with s_k the bilinear sample of step 4, float64 without FMA
+ *   contraction.  seen is uint8 [n_ref][n_vertices] holding 0 or 1, samples uint8 [n_ref][channels][n_vertices], 0 where the
+ *   view does not see the vertex.  Every element of both is written.
+ * Tables (sfm_mesh_exposure_gram).  With f_i(x) = (seen[i][x] != 0):
+ *     overlap[i][j]  = #{x : f_i(x) and f_j(x)}                             int64 [n_ref][n_ref]
+ *     sums[i][j][k]  = sum of samples[i][k][x] over those x                 int64 [n_ref][n_ref][channels]
+ *   the diagonal included: what view i sees at all.  Both are INTEGER sums, so no order of summation exists and the tables
+ *   are the same bytes whatever the launch geometry.  The call clears its outputs itself.  On the device they are the
+ *   products F F^T and Q_k F^T over the vertex axis on the i8 matrix cores, Q - 128 where seen as the signed operand and
+ *   sums = product + 128 * overlap; a workgroup takes a tile of 32 x 32 view pairs and a chunk of vertices
+ *   (sfm_mesh_exposure_plan: out[0], out[1] the tile sides, out[2] the chunk length, out[3] the workgroups of the launch),
+ *   accumulates in int32 - 128 * chunk < 2^31 - and adds its tile to the tables with integer atomics.
+ * Gains (host, float64; not part of this library).  Per channel k: a view with sum over j != i of overlap[i][j] == 0 (pairs
+ *   below min_overlap count as 0) gets the gain 1 and leaves the system.  For every ordered pair i != j with
+ *   N = overlap[i][j] > 0, a = sums[i][j][k] / N and b = sums[j][i][k] / N:
+ *     A[i][i] += N (a a / sigma_n^2 + 1 / sigma_g^2),  A[j][j] += N b b / sigma_n^2,  A[i][j] -= N a b / sigma_n^2,
+ *     A[j][i] -= N a b / sigma_n^2,  rhs[i] += N / sigma_g^2,   and g = solve(A, rhs).
+ *   This is the gain compensation of panorama stitching (Brown and Lowe 2007) with the mesh's vertices in the place of the
+ *   image overlaps: it minimises sum N ((g_i a - g_j b)^2 / sigma_n^2 + (1 - g_i)^2 / sigma_g^2).
+ * Apply (sfm_images_gain).  n_img images back to back, uint8 [h][w][channels]; gains HOST float64 [n_img][channels], each
+ *   finite and >= 0.  out = (uint8) min(floor((double)in * g + 0.5), 255.0) per pixel and channel: the product is rounded,
+ *   then the sum (no FMA contraction).  pixels_out may be pixels_in.
+ * Limits: one gain per view and channel - no offsets, no per-channel curves, no vignetting; no seam levelling inside the atlas;
+ *   the gains are not applied inside the blend kernels and not estimated from the render's residuals; the solve is plain
+ *   least squares, a wrong sample (a highlight, an occlusion the depth test missed) is not down-weighted; n_ref <= 1024.
+ * The workspace (sfm_mesh_exposure_workspace_bytes) holds the view table of the sample call; the gram call takes the same
+ *   workspace and leaves it alone.  Nothing is written outside the outputs.  SFM_ERR_ARG before any device work for a null
+ *   handle, n_ref above 1024, whatever sfm_mesh_colors refuses about the views, channels, n_vertices, tol and min_cos, a gain
+ *   that is negative or not finite, an image side outside 0 .. 32768, a null pointer (keep excepted; depth / pixels may be
+ *   null only when there is no pixel, vertices / normals only when n_vertices is 0, seen / samples only without a vertex or
+ *   a view, the tables only without a view, gains only without an image), or a workspace that is missing or too small. */
+int sfm_mesh_exposure_workspace_bytes(int32_t n_ref, int32_t channels, int64_t n_vertices, int64_t* bytes_host);
+int sfm_mesh_exposure_plan(int32_t n_ref, int32_t channels, int64_t n_vertices, int32_t* out_host /* [4] */);
+int sfm_mesh_exposure_sample(sfm_handle h, const int32_t* heights /* host */, const int32_t* widths /* host */, int32_t n_img,
+                             int32_t n_ref, const int32_t* ref_image /* host */, const double* proj /* device [n_ref][12] */,
+                             const double* centres /* device [n_ref][3] */, const float* depth, const uint8_t* keep /* or NULL */,
+                             const uint8_t* pixels, int32_t channels, int64_t n_vertices, const double* vertices,
+                             const float* normals, double tol, double min_cos, uint8_t* seen /* [n_ref][n_vertices] */,
+                             uint8_t* samples /* [n_ref][channels][n_vertices] */, void* workspace, int64_t workspace_bytes);
+int sfm_mesh_exposure_gram(sfm_handle h, int32_t n_ref, int32_t channels, int64_t n_vertices, const uint8_t* seen,
+                           const uint8_t* samples, int64_t* overlap /* [n_ref][n_ref] */,
+                           int64_t* sums /* [n_ref][n_ref][channels] */, void* workspace, int64_t workspace_bytes);
+int sfm_images_gain(sfm_handle h, const int32_t* heights /* host */, const int32_t* widths /* host */, int32_t n_img,
+                    int32_t channels, const double* gains /* host [n_img][channels] */, const uint8_t* pixels_in,
+                    uint8_t* pixels_out);
 
 /* ---- texture of the mesh: a patch of texels per triangle in one atlas, every texel blended over the views that see it
  *      (sfm_amd/csrc/mesh_texture.hip, mesh_texture_rule.h, mesh_texture_plan.h) ----
@@ -1165,7 +1221,8 @@ int sfm_mesh_colors(sfm_handle h, const int32_t* heights /* host */, const int32
  *   triangle, those with bad indices included.
  * Limits: one patch size for all triangles (the triangles of marching tetrahedra are all voxel-sized; slivers waste
  *   texels), no chart merging (triangles that share an edge share no texel), no view culling per triangle, no exposure
- *   compensation, no fill-in of unseen texels, no mip levels.
+ *   compensation, no fill-in of unseen texels, no mip levels.  (Gains per view are estimated and applied in front of this
+ *   call: "exposure of the views" above.)
  * The workspace (sfm_mesh_texture_workspace_bytes) holds the view table.  The call returns at once for n_triangles == 0.
  *   SFM_ERR_ARG before any device work for a null handle, what sfm_mesh_colors refuses about the views and the scalars
  *   (channels, n_vertices, tol, min_cos, fill), texels outside 1 .. 64, cells_per_row < 1, W or H above 32768, n_triangles
@@ -1272,7 +1329,8 @@ int sfm_mesh_render(sfm_handle h, int32_t n_cam, const int32_t* heights /* host 
  *      mean SSIM q_ssim / (2^24 n_ssim) are formed by the caller in double from these integers; pooled figures come from the
  *      summed integers.
  * Limits: a uniform window only (no Gaussian weights), one scale, no learned metric; no exposure compensation is estimated;
- *   pixels the mesh does not cover are counted (n_view_only) and not penalised in the error.
+ *   pixels the mesh does not cover are counted (n_view_only) and not penalised in the error.  (Gains per view come from the
+ *   mesh, not from these residuals: "exposure of the views" above.)
  * abs_error (uint8 [h][w][c]) and ssim_map (float32 [h][w]) may each be NULL: statistics only.  The workspace
  *   (sfm_render_score_workspace_bytes; render_score_plan.h has the layout) holds the table of the views.
  *   sfm_render_score_tile gives the sides of the tile one workgroup takes.  Nothing is written outside the pixels of the

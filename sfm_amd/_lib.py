@@ -190,6 +190,11 @@ SIGNATURES = {
     "sfm_mesh_emit": (C.c_int, [vp, vp, i32, i32, i32, vp, f64, i64, i64, vp, vp, vp, vp, i64]),
     "sfm_mesh_colors_workspace_bytes": (C.c_int, [i32, C.POINTER(i64)]),
     "sfm_mesh_colors": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i64, vp, vp, f64, f64, i32, vp, vp, vp, vp, i64]),
+    "sfm_mesh_exposure_workspace_bytes": (C.c_int, [i32, i32, i64, C.POINTER(i64)]),
+    "sfm_mesh_exposure_plan": (C.c_int, [i32, i32, i64, C.POINTER(i32)]),
+    "sfm_mesh_exposure_sample": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i64, vp, vp, f64, f64, vp, vp, vp, i64]),
+    "sfm_mesh_exposure_gram": (C.c_int, [vp, i32, i32, i64, vp, vp, vp, vp, vp, i64]),
+    "sfm_images_gain": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp]),
     "sfm_mesh_texture_size": (C.c_int, [i64, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
     "sfm_mesh_texture_workspace_bytes": (C.c_int, [i32, C.POINTER(i64)]),
     "sfm_mesh_texture": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i64, vp, vp, i64, vp, i32, i32, f64, f64, i32, vp, vp, vp,

@@ -6,8 +6,9 @@ are not filled and zero-area triangles are kept.  `sfm_mesh_colors` (sfm_amd/csr
 blended over the views whose own depth maps see it, `sfm_mesh_texture` (sfm_amd/csrc/mesh_texture.hip) every triangle a
 patch of texels in an atlas by the same blend, and `sfm_mesh_render` (sfm_amd/csrc/mesh_render.hip) draws the mesh through
 any camera: depth, triangle, barycentrics and colour per pixel; `sfm_render_score` (sfm_amd/csrc/render_score.hip) scores such a
-render against the photographs: error, PSNR and SSIM sums and the distance to the views' own depth.  No CPU fallback: without the
-library or a GPU the calls raise.
+render against the photographs: error, PSNR and SSIM sums and the distance to the views' own depth.  `Mesh.exposure`
+(sfm_amd/exposure.py) estimates one gain per view and channel for images whose exposure differs, to be applied before they go
+to the colour calls.  No CPU fallback: without the library or a GPU the calls raise.
 """
 from __future__ import annotations
 
@@ -104,6 +105,17 @@ class Mesh:
         for name in ("vertex_colors", "n_views", "best_view"):
             self._host.pop(name, None)
         return self.vertex_colors
+
+    def exposure(self, images, maps=None, tol=None, min_cos=0.35, sigma_n=10.0, sigma_g=1.0, min_overlap=1):
+        """One gain per view and channel from the vertices that several views see (`sfm_mesh_exposure_sample`,
+        `sfm_mesh_exposure_gram`; include/sfm_amd.h states the rule): every view's sample of every vertex it sees, as
+        `colors()` would take it, the counts and sums over the vertices two views share, and the least-squares gains that
+        make those sums agree (`solve_gains`; sigma_n the noise of a sample in grey levels, sigma_g how far a gain may stray
+        from 1, min_overlap the common vertices a pair needs).  images, maps, tol and min_cos are those of `colors()`; a mesh
+        whose volume came from `tsdf_volume_from_depth_arrays` takes one image per view.  Returns an `ExposureGains`; its
+        `apply(images)` gives the images to hand to `colors()`, `texture()` and `score()`."""
+        from .exposure import mesh_exposure
+        return mesh_exposure(self, images, maps, tol, min_cos, sigma_n, sigma_g, min_overlap)
 
     atlas = None                                                   # the `MeshTexture` of the last texture(); None before
 
@@ -359,6 +371,7 @@ def _integrate(dev, heights, widths, ref_image, proj, d_depth, d_keep, origin, v
            C.c_double(voxel), shape[0], shape[1], shape[2], C.c_double(float(trunc)), dp(tsdf), dp(weight), dp(ws), need.value)
     vol = TsdfVolume(tsdf, weight, origin, voxel, shape)
     vol.trunc, vol.proj, vol._ws = float(trunc), proj, (ws, d_proj, d_depth, d_keep)       # alive while the call may still run
+    vol._views = (heights, widths, ref_image, d_depth, d_keep)     # what Mesh.exposure() projects into without a DepthMaps
     return vol
 
 

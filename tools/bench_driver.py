@@ -1096,7 +1096,8 @@ def measure_depth(reps=20, emit=None, mesh=False):
     sfm_features_detect + sfm_features_describe on the same images, as a known quantity.  With mesh=True also the surface
     of the same run: sfm_tsdf_integrate of the 36 filtered maps into 256^3 nodes (a cube around the kept pixels, truncation 3
     voxels), sfm_mesh_mark and sfm_mesh_emit (min_weight 1), then sfm_mesh_colors of that mesh from the 36 views (BGR, tol 3
-    voxels, min_cos 0.35) with its vertex-view projections per second, and sfm_mesh_texture of the same mesh from the same views
+    voxels, min_cos 0.35) with its vertex-view projections per second, beside it sfm_mesh_exposure_sample and
+    sfm_mesh_exposure_gram of the same mesh and views and sfm_images_gain over the 36 images, and sfm_mesh_texture of the same mesh from the same views
     at texels 8 with its texel-view projections per second (the texels of the triangles' patches x views), then sfm_mesh_render
     of that mesh into its 36 views with that atlas (ms per camera, pixels and triangle-camera pairs per second, the length of
     the large-box list), then sfm_render_score of those 36 renders against the 36 images (window 7: once with both maps written and
@@ -1239,6 +1240,40 @@ def measure_depth(reps=20, emit=None, mesh=False):
                    _p(d_bgr), 3, nv, _p(vertices), _p(vnormals), C.c_double(3.0 * voxel), C.c_double(0.35), 0, _p(vcolors), _p(vviews),
                    _p(vbest), _p(colors_ws), colors_need)
         run_mesh_colors()
+        # the exposure stage on the same mesh and views, beside the colour call above as its yardstick: the samples, the two
+        # tables, and the gains applied to the 36 images (a gain of 0.9 .. 1.1 per image and channel)
+        h.check(h.lib.sfm_mesh_exposure_workspace_bytes(n_img, 3, nv, C.byref(need)), "sfm_mesh_exposure_workspace_bytes")
+        exposure_need = need.value
+        exposure_ws = torch.empty(exposure_need, dtype=torch.uint8, device=dev)
+        e_seen = torch.empty(max(n_img * nv, 1), dtype=torch.uint8, device=dev)
+        e_samples = torch.empty(max(n_img * 3 * nv, 1), dtype=torch.uint8, device=dev)
+        e_overlap = torch.empty(n_img * n_img, dtype=torch.int64, device=dev)
+        e_sums = torch.empty(n_img * n_img * 3, dtype=torch.int64, device=dev)
+        e_gained = torch.empty_like(d_bgr)
+        e_gains = np.ascontiguousarray(np.random.default_rng(0).uniform(0.9, 1.1, (n_img, 3)))
+
+        def run_exposure_sample():
+            h.call("sfm_mesh_exposure_sample", hp(heights), hp(widths), n_img, n_img, hp(ref_image), _p(d_proj), _p(d_centres), _p(depth), _p(keep),
+                   _p(d_bgr), 3, nv, _p(vertices), _p(vnormals), C.c_double(3.0 * voxel), C.c_double(0.35), _p(e_seen), _p(e_samples),
+                   _p(exposure_ws), exposure_need)
+
+        def run_exposure_gram():
+            h.call("sfm_mesh_exposure_gram", n_img, 3, nv, _p(e_seen), _p(e_samples), _p(e_overlap), _p(e_sums), _p(exposure_ws), exposure_need)
+
+        def run_images_gain():
+            h.call("sfm_images_gain", hp(heights), hp(widths), n_img, 3, hp(e_gains), _p(d_bgr), _p(e_gained))
+        for _ in range(3):
+            run_exposure_sample(); run_exposure_gram(); run_images_gain()
+        e_plan = (C.c_int32 * 4)()
+        h.check(h.lib.sfm_mesh_exposure_plan(n_img, 3, nv, e_plan), "sfm_mesh_exposure_plan")
+        ov = e_overlap.cpu().numpy().reshape(n_img, n_img)
+        row.update({"ms_mesh_exposure_sample": timed(run_exposure_sample, reps) * 1e3, "ms_mesh_exposure_gram": timed(run_exposure_gram, reps) * 1e3,
+                    "ms_images_gain": timed(run_images_gain, reps) * 1e3, "ms_mesh_colors_beside_exposure": timed(run_mesh_colors, reps) * 1e3,
+                    "exposure_gram_workgroups": int(e_plan[3]), "exposure_gram_multiply_adds": n_img * n_img * nv * 4,
+                    "exposure_pairs_with_common_vertices": int((np.triu(ov, 1) > 0).sum()), "exposure_largest_overlap": int(np.triu(ov, 1).max()),
+                    "exposure_vertices_seen_per_view": float(np.diag(ov).mean()), "gain_bytes": int(d_bgr.numel())})
+        row["gain_bytes_per_s_read_plus_written"] = 2 * row["gain_bytes"] / (row["ms_images_gain"] * 1e-3)
+        del exposure_ws, e_seen, e_samples, e_overlap, e_sums, e_gained
         # the texture of the same mesh from the same views: texels 8, the square atlas of Mesh.texture; 20 calls after 3
         texels, cells_per_row, aw, ah = 8, mm.check_texture_layout(nt, 8, None)[0], C.c_int32(), C.c_int32()
         h.check(h.lib.sfm_mesh_texture_size(nt, texels, cells_per_row, C.byref(aw), C.byref(ah)), "sfm_mesh_texture_size")

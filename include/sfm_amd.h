@@ -1093,6 +1093,71 @@ int sfm_mesh_emit(sfm_handle h, const float* tsdf, int32_t nx, int32_t ny, int32
                   double voxel, int64_t n_vertices, int64_t n_triangles, double* vertices, float* normals,
                   int32_t* triangles, void* workspace, int64_t workspace_bytes);
 
+/* ---- connected components of a mesh and the removal of the small ones (sfm_amd/csrc/mesh_clean.hip, mesh_clean_rule.h,
+ *      mesh_clean_plan.h) ----
+ * Integers only: every output byte is a function of the inputs, the same from run to run, and NumPy / SciPy reproduce it
+ * (tests/mesh_clean_reference.py).  Nothing depends on the order of the triangles, of the indices within a triangle, or of
+ * the lanes.
+ *
+ * Input.  n_vertices, 0 .. 2^31 - 1, and triangles int32 [n_triangles][3] with n_triangles 0 .. 2^31 - 1.
+ * Sound triangles.  A triangle is sound iff its three indices lie in [0, n_vertices).  An unsound triangle joins nothing:
+ *   its component is -1, it is counted in counts[1], it is never kept, and no kernel uses its indices as addresses.  A
+ *   repeated index inside a triangle is allowed, and a zero-area triangle is a triangle like any other.
+ * Components.  The vertices are the nodes and every sound triangle joins its three vertices.  A vertex in no sound triangle
+ *   is a component of its own with 0 triangles.  Components are numbered in ascending order of their smallest vertex index,
+ *   comp_root.  sfm_mesh_components writes vertex_component int32 [n_vertices], triangle_component int32 [n_triangles] (the
+ *   component of its vertices, -1 when unsound), the first n_components entries of comp_root, comp_vertices and
+ *   comp_triangles (int32; the caller provides n_vertices entries of each; comp_triangles counts sound triangles), and
+ *   counts, device int64 [3]: components, unsound triangles, status.  Status is 0; it is 1 when a walk towards a root ran
+ *   out of its step budget (4 n_vertices + 1024 steps, which no input reaches), and the call then returns SFM_ERR_NUMERIC
+ *   instead of spinning.  The call reads the status behind its last launch, so it returns with the stream synchronised.
+ * Selection.  min_triangles >= 0 and keep_largest >= 0, where 0 means no limit.  Component c is a candidate iff
+ *   comp_triangles[c] >= min_triangles.  With keep_largest = k > 0 and more than k candidates the cut of the feature
+ *   selection applies to the candidates' triangle counts: the size s with #(size > s) < k <= #(size >= s); all candidates
+ *   above s are kept, and of those at s the first k - #(size > s) in component order.  Nothing is sorted.  Otherwise every
+ *   candidate is kept.  The result is comp_keep, uint8 [n_components], 1 = kept.  mesh_clean_rule.h holds this rule in plain
+ *   C++ for host and device: four passes of 8-bit histograms over the sizes, most significant byte first, then the ties.
+ * Compaction.  A vertex is kept iff its component is kept; a triangle is kept iff it is sound and its component is kept.
+ *   Kept vertices and kept triangles stay in their old order.  vertex_map int32 [nv'] is the old index of each new vertex,
+ *   ascending, triangle_map int32 [nt'] likewise; the new triangles int32 [nt'][3] hold, for every index, the rank of its
+ *   vertex among the kept ones; vertices (float64 x 3) and normals (float32 x 3) are copied bit for bit.  A mesh of which
+ *   everything is kept comes out byte for byte as it went in.
+ * Limits: no threshold as a fraction of the largest component, no components by area or bounding box, no removal of
+ *   zero-area triangles or non-manifold edges, no hole filling, no decimation.
+ *
+ * Calls, in the shape of sfm_mesh_mark / sfm_mesh_emit: the host reads a count between them and allocates.
+ * sfm_mesh_components: the labels, the per-component tables and counts.  Union-find with "the larger root goes under the
+ *   smaller id", one lane per triangle and two unions each, every find halving the path it walks, and one more find per
+ *   lane from its largest vertex, so that chains hooked at the same moment are shortened at once; the roots are numbered
+ *   by the block counts and the two-level scan of every compaction here, the per-component counts are integer atomic adds,
+ *   one per run of equal components within a wavefront.
+ * sfm_mesh_clean_mark: takes the labels and comp_triangles of that call with the two parameters, writes comp_keep and
+ *   counts, device int64 [3]: kept components, kept vertices, kept triangles, and leaves the first slots of every block of
+ *   both compactions in the workspace (sfm_mesh_clean_workspace_bytes).  The selection is one workgroup: serial in the number
+ *   of components.
+ * sfm_mesh_clean_emit: takes the same workspace, untouched, with the same labels and comp_keep, and the capacities of the
+ *   outputs; it writes nothing at or above the capacities and returns at once when both are 0.
+ * sfm_mesh_gather_rows: dst row i = src row map[i], i < n, rows of row_bytes bytes; it applies vertex_map to any per-vertex
+ *   array (vertex_colors, n_views, best_view).  Every map[i] must be a row of src; a negative one leaves its row untouched.
+ * Every call returns SFM_ERR_ARG before any device work for a null handle, a count or a capacity below 0 or above 2^31 - 1,
+ * n_components outside 0 .. n_vertices, a negative min_triangles or keep_largest, row_bytes < 1, a null pointer (allowed
+ * only where its count is 0), or a workspace that is missing or too small. */
+int sfm_mesh_components_workspace_bytes(int64_t n_vertices, int64_t* bytes_host);
+int sfm_mesh_components(sfm_handle h, int64_t n_vertices, int64_t n_triangles, const int32_t* triangles,
+                        int32_t* vertex_component, int32_t* triangle_component, int32_t* comp_root, int32_t* comp_vertices,
+                        int32_t* comp_triangles, int64_t* counts /* device [3] */, void* workspace, int64_t workspace_bytes);
+int sfm_mesh_clean_workspace_bytes(int64_t n_vertices, int64_t n_triangles, int64_t* bytes_host);
+int sfm_mesh_clean_mark(sfm_handle h, int64_t n_vertices, int64_t n_triangles, int64_t n_components,
+                        const int32_t* vertex_component, const int32_t* triangle_component, const int32_t* comp_triangles,
+                        int64_t min_triangles, int64_t keep_largest, uint8_t* comp_keep, int64_t* counts /* device [3] */,
+                        void* workspace, int64_t workspace_bytes);
+int sfm_mesh_clean_emit(sfm_handle h, int64_t n_vertices, int64_t n_triangles, int64_t n_components,
+                        const int32_t* vertex_component, const int32_t* triangle_component, const uint8_t* comp_keep,
+                        const int32_t* triangles, const double* vertices, const float* normals, int64_t cap_vertices,
+                        int64_t cap_triangles, int32_t* vertex_map, int32_t* triangle_map, int32_t* triangles_out,
+                        double* vertices_out, float* normals_out, void* workspace, int64_t workspace_bytes);
+int sfm_mesh_gather_rows(sfm_handle h, const void* src, int64_t row_bytes, const int32_t* map, int64_t n, void* dst);
+
 /* ---- colours of the mesh: per vertex a blend over the views that see it (sfm_amd/csrc/mesh_color.hip,
  *      mesh_color_rule.h, mesh_color_plan.h) ----
  * A pure function of its inputs: float64 without FMA contraction, no visit order, no atomics, no randomness, so NumPy

@@ -10,7 +10,8 @@
 #define SFM_PINNED_DOUBLES 64
 #define SFM_PIN_CG1 32
 #define SFM_PIN_TRACKS 48    /* sfm_tracks_build: the status word of the call (one int64), read once behind its last launch */
-#define SFM_PIN_CGB 40       /* tile-streaming CG: its status words as the deciding launch writes them, word 7 = the system's ticket */
+#define SFM_PIN_MESH_CC 49   /* sfm_mesh_components: the status word of the call (one int64), read once behind its last launch */
+#define SFM_PIN_CGB 40      /* tile-streaming CG: its status words as the deciding launch writes them, word 7 = the system's ticket */
 struct sfm_prof_slot {
   hipEvent_t start[SFM_PROF_RING], stop[SFM_PROF_RING];
   int pending;             // recorded, not yet folded into total_ms

@@ -496,7 +496,8 @@ def depth_maps_from_arrays(shapes, refs, src_ptr, src_image, warps, backproj, de
 
 
 def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=256, radius=2, rel_tol=0.01, max_cost=None,
-                              min_consistent=2, colors=None, device=0, fuse=False, mesh=False, texture=None):
+                              min_consistent=2, colors=None, device=0, fuse=False, mesh=False, texture=None,
+                              min_triangles=None, keep_largest=None):
     """The chain on a `Reconstruction`: sources by shared points (`select_sources`), the depth interval of every view from
     its sparse points (`depth_ranges`), planes at most one pixel apart (`plane_depths`), `depth_maps`, `.filter`,
     `.point_cloud`.  images: one per image position of rec.tracks.  Returns (points, index, DepthMaps) - or (points, index,
@@ -504,7 +505,16 @@ def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=2
     is (FusedCloud, DepthMaps); the colours are then `FusedCloud.colors(colors)`.  With mesh=True the surface of the kept
     pixels, `maps.tsdf().mesh()`, is appended to whichever of those is returned; with colors (uint8 images) it is coloured
     by `Mesh.colors(colors)`, and with texture (an integer, the texels per triangle leg) it also gets the atlas of
-    `Mesh.texture(colors, texels=texture)` as `Mesh.atlas`; the tuple keeps its shape."""
+    `Mesh.texture(colors, texels=texture)` as `Mesh.atlas`; the tuple keeps its shape.  With min_triangles or keep_largest
+    (both None: nothing changes) the mesh is `Mesh.clean(min_triangles, keep_largest)` of that surface - min_triangles None
+    is 1 then - cleaned before it is coloured."""
+    cleaning = min_triangles is not None or keep_largest is not None
+    if cleaning:
+        from .mesh_clean import check_clean_arguments
+        if not mesh:
+            raise ValueError("min_triangles and keep_largest need mesh=True")
+        min_triangles = 1 if min_triangles is None else min_triangles
+        check_clean_arguments(min_triangles, keep_largest)
     if texture is not None:
         if not (isinstance(texture, (int, np.integer)) and 1 <= texture <= 64):
             raise ValueError("texture must be None or the texels per triangle leg, an integer 1 .. 64")
@@ -523,6 +533,8 @@ def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=2
     maps = depth_maps(images, rec.K, rec.poses, src, planes, radius, device)
     maps.filter(rel_tol, max_cost, min_consistent)
     surface = (maps.tsdf().mesh(),) if mesh else ()
+    if cleaning:
+        surface = (surface[0].clean(min_triangles, keep_largest),)
     if mesh and colors is not None:
         surface[0].colors(colors)
         if texture is not None:

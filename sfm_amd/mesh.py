@@ -8,7 +8,9 @@ patch of texels in an atlas by the same blend, and `sfm_mesh_render` (sfm_amd/cs
 any camera: depth, triangle, barycentrics and colour per pixel; `sfm_render_score` (sfm_amd/csrc/render_score.hip) scores such a
 render against the photographs: error, PSNR and SSIM sums and the distance to the views' own depth.  `Mesh.exposure`
 (sfm_amd/exposure.py) estimates one gain per view and channel for images whose exposure differs, to be applied before they go
-to the colour calls.  No CPU fallback: without the library or a GPU the calls raise.
+to the colour calls.  `Mesh.components` and `Mesh.clean` (sfm_amd/mesh_clean.py; `sfm_mesh_components`, `sfm_mesh_clean_mark` /
+`sfm_mesh_clean_emit`, sfm_amd/csrc/mesh_clean.hip) label the connected components of the mesh and remove the small ones.  No
+CPU fallback: without the library or a GPU the calls raise.
 """
 from __future__ import annotations
 
@@ -63,6 +65,28 @@ class Mesh:
     vertex_colors = property(lambda self: self._get("vertex_colors", self.n_vertices))
     n_views = property(lambda self: self._get("n_views", self.n_vertices))
     best_view = property(lambda self: self._get("best_view", self.n_vertices))
+    # on what clean() returns: int32 [nv] / [nt], the index each vertex / triangle had in the mesh it was cleaned from; None otherwise
+    vertex_map = property(lambda self: self._get("vertex_map", self.n_vertices))
+    triangle_map = property(lambda self: self._get("triangle_map", self.n_triangles))
+    components_before = None                                       # on what clean() returns: the `MeshComponents` it used
+
+    def components(self):
+        """The connected components on the device (`sfm_mesh_components`; include/sfm_amd.h states the rule): vertices are the
+        nodes, every triangle joins its three, components are numbered by their smallest vertex.  Returns a `MeshComponents`;
+        ValueError when a triangle has an index outside 0 .. nv - 1."""
+        from .mesh_clean import components_of
+        return components_of(self)
+
+    def clean(self, min_triangles=1, keep_largest=None, components=None):
+        """A new `Mesh` without the small components (`sfm_mesh_clean_mark` / `sfm_mesh_clean_emit`): a component stays when
+        it has at least min_triangles triangles and, with keep_largest = k, is among the k with the most triangles (equal
+        sizes: the lower component number).  components: what `components()` returned for this mesh, None to label it now.
+        Kept vertices and triangles keep their order; vertex_colors, n_views and best_view come along when the mesh has them;
+        vertex_map and triangle_map give the old indices, components_before the `MeshComponents` used.  The volume is
+        carried over, so colors(), texture(), render_views() and score() keep their defaults; atlas is None - its layout is
+        a function of the triangle number, so call texture() again.  This mesh is untouched."""
+        from .mesh_clean import clean
+        return clean(self, min_triangles, keep_largest, components)
 
     def _view_inputs(self, what, images, maps, tol, min_cos, fill):
         """What colors() and texture() share: the maps and tol with their defaults, the checked scalars, the views' pixels
@@ -1018,3 +1042,6 @@ def score_render(color, triangle, depth, photos, view_depth=None, view_keep=None
     pad = lambda a: None if a is None else np.concatenate([a, np.zeros(1, a.dtype)])                          # a pointer must exist
     col = pad(np.concatenate([c.reshape(-1) for c in color]) if color else np.zeros(0, np.uint8))
     return _score(dev, heights, widths, channels, up(col), up(tri), up(dr), up(pad(flat_photos)), up(pad(flat_masks)), up(vd), up(vk), window, rel_tol, True)
+
+
+from .mesh_clean import MeshComponents, check_clean_arguments, clean_mesh, mesh_components  # noqa: E402,F401

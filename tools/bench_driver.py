@@ -1086,6 +1086,69 @@ def measure_guided(reps=20, emit=None):
     return [r]
 
 
+def measure_mesh_clean(h, dev, nv, nt, triangles, vertices, vnormals, reps=20, strips=(1 << 20, 1 << 22)):
+    """sfm_mesh_components, sfm_mesh_clean_mark and sfm_mesh_clean_emit (min_triangles 100) on a mesh that is resident on the
+    device, whole calls by HIP events around `reps` calls after 3 warm-up calls, and sfm_mesh_components on the strip whose
+    triangle i is (i, i + 1, i + 2) at each size of `strips`: the keys of the "mesh" row they belong to."""
+    import torch
+    from sfm_amd.driver import _p
+    need = C.c_int64()
+
+    def components_of(n_vertices, n_triangles, d_triangles):
+        h.check(h.lib.sfm_mesh_components_workspace_bytes(n_vertices, C.byref(need)), "sfm_mesh_components_workspace_bytes")
+        ws_bytes = need.value
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        out = [torch.empty(max(n, 1), dtype=torch.int32, device=dev) for n in (n_vertices, n_triangles, n_vertices, n_vertices, n_vertices)]
+        counts = torch.empty(3, dtype=torch.int64, device=dev)
+
+        def run():
+            h.call("sfm_mesh_components", n_vertices, n_triangles, _p(d_triangles), *[_p(t) for t in out], _p(counts), _p(ws), ws_bytes)
+        for _ in range(3):
+            run()
+        return run, out, counts
+
+    run_components, (vc, tc, c_root, c_vertices, c_triangles), cc_counts = components_of(nv, nt, triangles)
+    nc = int(cc_counts.cpu().numpy()[0])
+    sizes = np.sort(c_triangles[:nc].cpu().numpy())[::-1]
+    h.check(h.lib.sfm_mesh_clean_workspace_bytes(nv, nt, C.byref(need)), "sfm_mesh_clean_workspace_bytes")
+    clean_need = need.value
+    clean_ws = torch.empty(clean_need, dtype=torch.uint8, device=dev)
+    keep = torch.empty(max(nc, 1), dtype=torch.uint8, device=dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+
+    def run_clean_mark():
+        h.call("sfm_mesh_clean_mark", nv, nt, nc, _p(vc), _p(tc), _p(c_triangles), 100, 0, _p(keep), _p(counts), _p(clean_ws), clean_need)
+    for _ in range(3):
+        run_clean_mark()
+    kept, nv2, nt2 = (int(c) for c in counts.cpu().numpy())
+    vmap = torch.empty(max(nv2, 1), dtype=torch.int32, device=dev)
+    tmap = torch.empty(max(nt2, 1), dtype=torch.int32, device=dev)
+    tri2 = torch.empty((max(nt2, 1), 3), dtype=torch.int32, device=dev)
+    v2 = torch.empty((max(nv2, 1), 3), dtype=torch.float64, device=dev)
+    n2 = torch.empty((max(nv2, 1), 3), dtype=torch.float32, device=dev)
+
+    def run_clean_emit():
+        h.call("sfm_mesh_clean_emit", nv, nt, nc, _p(vc), _p(tc), _p(keep), _p(triangles), _p(vertices), _p(vnormals), nv2, nt2, _p(vmap), _p(tmap),
+               _p(tri2), _p(v2), _p(n2), _p(clean_ws), clean_need)
+    for _ in range(3):
+        run_clean_emit()
+    out = {"ms_mesh_components": timed(run_components, reps) * 1e3, "ms_mesh_clean_mark": timed(run_clean_mark, reps) * 1e3,
+           "ms_mesh_clean_emit": timed(run_clean_emit, reps) * 1e3, "mesh_components": nc, "mesh_component_triangles_largest": [int(s) for s in sizes[:8]],
+           "mesh_components_below_100_triangles": int((sizes < 100).sum()), "clean_min_triangles": 100, "clean_components_kept": kept,
+           "clean_vertices": nv2, "clean_triangles": nt2}
+    del vc, tc, c_root, c_vertices, c_triangles, clean_ws, vmap, tmap, tri2, v2, n2
+    for n in strips:
+        i = torch.arange(n - 2, dtype=torch.int32, device=dev)
+        strip = torch.stack([i, i + 1, i + 2], dim=1).contiguous()
+        run_strip, _, strip_counts = components_of(n, n - 2, strip)
+        assert strip_counts.cpu().numpy().tolist() == [1, 0, 0]
+        out[f"ms_mesh_components_strip_{n}"] = timed(run_strip, reps) * 1e3
+        del strip, run_strip
+    if len(strips) == 2:
+        out["mesh_components_strip_ratio"] = out[f"ms_mesh_components_strip_{strips[1]}"] / out[f"ms_mesh_components_strip_{strips[0]}"]
+    return out
+
+
 def measure_depth(reps=20, emit=None, mesh=False):
     """sfm_depth_census, sfm_depth_sweep and sfm_depth_filter on 36 synthetic 1024 x 768 views (the scene generator of
     tests/depth_reference.py: cameras on a line, baseline 0.1, f = 1228), every view a reference with its 4 nearest cameras
@@ -1101,8 +1164,10 @@ def measure_depth(reps=20, emit=None, mesh=False):
     at texels 8 with its texel-view projections per second (the texels of the triangles' patches x views), then sfm_mesh_render
     of that mesh into its 36 views with that atlas (ms per camera, pixels and triangle-camera pairs per second, the length of
     the large-box list), then sfm_render_score of those 36 renders against the 36 images (window 7: once with both maps written and
-    the views' depth, once the statistics alone; ms per view and the pooled figures), whole calls by HIP events; the row is then
-    named "mesh"."""
+    the views' depth, once the statistics alone; ms per view and the pooled figures), then the components of that mesh and its cleaning
+    at min_triangles 100 (sfm_mesh_components, sfm_mesh_clean_mark, sfm_mesh_clean_emit) and sfm_mesh_components on the ascending strip
+    at 2^20 and 2^22 vertices with the ratio of the two times (`measure_mesh_clean`), whole calls by HIP events; the row is then named
+    "mesh"."""
     import torch
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from depth_reference import make_scene
@@ -1346,6 +1411,10 @@ def measure_depth(reps=20, emit=None, mesh=False):
                     "score_view_only": pooled["view_only"]})
         del score_ws, s_stats, s_error, s_ssim
         del atlas, aviews, auv, texture_ws, render_ws, r_depth, r_tri, r_bary, r_color, drawn
+        # the components of the same mesh and its cleaning at min_triangles 100, whole calls, 20 after 3; sfm_mesh_mark and
+        # sfm_mesh_emit of this row are their yardsticks.  Then the labelling alone on the ascending strip at 2^20 and 2^22
+        # vertices: linear work gives a time ratio of 4, work bound by the chain 16.
+        row.update(measure_mesh_clean(h, dev, nv, nt, triangles, vertices, vnormals, reps))
         zv = vertices[:nv, 2].cpu().numpy()
         seen = int((weight != 0).sum().item())
         row.update({"grid_nodes": [nx, ny, nz], "voxel": float(voxel), "nodes_seen": seen, "projections": nx * ny * nz * n_img,
@@ -1403,7 +1472,7 @@ def main():
     ap.add_argument("--pyramid-only", action="store_true", help="only the multi-scale feature row (beside the single-scale stage on the same images); no other selection runs it")
     ap.add_argument("--guided-only", action="store_true", help="only the guided-matching row (beside the blind matcher)")
     ap.add_argument("--depth-only", action="store_true", help="only the dense-depth row (beside the feature stage on the same images)")
-    ap.add_argument("--mesh-only", action="store_true", help="only the meshing row: TSDF integration, mark and emit beside the sweep and the fusion of the same run")
+    ap.add_argument("--mesh-only", action="store_true", help="only the meshing row: TSDF integration, mark and emit beside the sweep and the fusion of the same run, and the stages on that mesh up to its components and cleaning")
     a = ap.parse_args()
     emit = lambda d: print(json.dumps(d), flush=True)
     only = a.fundamental_only or a.essential_only or a.homography_only or a.pnp_only or a.pose_only or a.tracks_only or a.triangulate_only or a.incremental_only or \

@@ -1158,6 +1158,81 @@ int sfm_mesh_clean_emit(sfm_handle h, int64_t n_vertices, int64_t n_triangles, i
                         double* vertices_out, float* normals_out, void* workspace, int64_t workspace_bytes);
 int sfm_mesh_gather_rows(sfm_handle h, const void* src, int64_t row_bytes, const int32_t* map, int64_t n, void* dst);
 
+/* ---- the edge table of a mesh, its boundary loops and the filling of the small holes (sfm_amd/csrc/mesh_fill.hip,
+ *      mesh_fill_rule.h, mesh_fill_plan.h) ----
+ * Integers except for the new vertices and their normals; every output byte is a function of the inputs, the same from run
+ * to run, and NumPy reproduces it (tests/mesh_fill_reference.py).
+ *
+ * Input.  n_vertices, 0 .. 2^31 - 1, and triangles int32 [n_triangles][3] with n_triangles 0 .. (2^31 - 1) / 3.
+ * Half-edges.  Half-edge h = 3 t + k of triangle t runs from a_h = tri[t][k] to b_h = tri[t][(k + 1) % 3].  It is live iff
+ *   the triangle is sound (all three indices in [0, n_vertices), as for sfm_mesh_components) and a_h != b_h.
+ * Uses and twin.  uses[h] is the number of live half-edges on the same unordered pair {a, b}, itself included, and 0 for a
+ *   half-edge that is not live.  twin[h] is the other half-edge of the pair iff uses == 2 and the two run in opposite
+ *   directions, otherwise -1.  An edge is boundary when uses == 1, inconsistent when uses == 2 without a twin, non-manifold
+ *   when uses > 2.
+ * Successor.  For a boundary half-edge h rotate about b_h inside the surface: g = the next half-edge of h's triangle; while
+ *   g is live and not boundary: stop with -1 if it has no twin, otherwise g = the next half-edge of the triangle of
+ *   twin[g].  next[h] = g if the walk ended on a boundary half-edge, otherwise -1 (a half-edge that is not live, or an
+ *   inconsistent or non-manifold edge in the fan); -1 for every h that is not boundary.  The walk visits each triangle of
+ *   the fan once; it has a budget of n_triangles + 1 steps, which no valid twin table exhausts, and raises the status word
+ *   when it runs out.  Rotation through twins is reversible, so next is injective where it is defined.
+ * Loops.  From a boundary half-edge follow next for at most 64 steps.  If the walk returns to h, h lies on a short loop of
+ *   that length, named by its smallest half-edge, its leader; otherwise on none (the walk met -1, or the cycle is longer
+ *   than 64: the wavefront).  Short loops are numbered in ascending order of their leaders; a loop has at least 3 edges, so
+ *   there are at most n_triangles.
+ * Sub-loops.  Where two holes touch in a vertex the surface about it is two fans, and one loop passes that vertex twice.
+ *   Walk the loop from its leader in next order with a stack: push h; if some stack entry p has a_p == b_h, the entries
+ *   p .. top are a sub-loop: emit and pop them.  At most one p can match (the start vertices on the stack are distinct at
+ *   all times) and the stack is empty when the walk ends.  A sub-loop has distinct vertices and at least 3 edges; it is
+ *   named by its smallest half-edge and is filled iff 3 <= n <= max_edges, 1 <= max_edges <= 64.
+ * Fill.  The filled sub-loops in ascending order of their names get the new vertices n_vertices + r.  Walk the sub-loop from
+ *   its name in its own cyclic order (the stack order): c = (((v[a_0] + v[a_1]) + ...)) / (double)n per coordinate, in
+ *   float64, sequentially, without FMA.  The new normal is unit(sum over the same order of cross(v[a_h] - v[b_h],
+ *   c - v[b_h])): every product and sum rounds on its own, l2 = (x x + y y) + z z, each component is divided by sqrt(l2) and
+ *   rounded once to float32; (0, 0, 0) when l2 is 0 or not finite.  Every half-edge h of a filled sub-loop gives one
+ *   triangle (b_h, a_h, n_vertices + r), the triangles in ascending order of h.  Old vertices, normals and triangles are not
+ *   touched: the new ones are to be appended.  NaN and infinite coordinates propagate; no input bit pattern changes an
+ *   address.
+ * Limits: boundary cycles of more than 64 edges - an outline is one - and the holes that touch them stay open and are only
+ *   counted by their edges; the centroid fan is the only patch, without a planarity test and without refinement of large
+ *   patches; non-manifold and inconsistent edges are reported, not repaired, and a hole whose fan holds one stays open; the
+ *   outline of a lone fragment of at most max_edges edges is a short loop too and is filled: clean first.
+ *
+ * sfm_mesh_edges: halfedge_uses, halfedge_twin, halfedge_next and halfedge_loop (the number of the short loop or -1), int32
+ *   [3 n_triangles]; the first n_loops entries of loop_leader and loop_edges (int32; the caller provides n_triangles entries
+ *   of each); counts, device int64 [8]: distinct live edges, boundary edges, inconsistent edges, non-manifold edges, short
+ *   loops, boundary half-edges on no short loop, unsound triangles, status (0; 1 when a rotation ran out of its budget: the
+ *   table is then not to be used).  uses and twin come out of one stable radix sort of (key, h) with the key (min(a, b) <<
+ *   32) | max(a, b), all ones for a half-edge that is not live, and one lane per sorted slot that finds the ends of its run
+ *   of equal keys: near-linear on a fan about one vertex.  The workspace holds the sort's temporary storage, which the
+ *   library measures on the handle's device: sfm_mesh_edges_workspace_bytes takes the handle.
+ * sfm_mesh_fill_mark: takes halfedge_next, n_loops and loop_leader of that call with max_edges; writes halfedge_fill, int32
+ *   [3 n_triangles]: the rank r of the filled sub-loop the half-edge belongs to, or -1; counts, device int64 [4]: filled
+ *   sub-loops, fill triangles, sub-loops left open, status (1 when the tables are not those of sfm_mesh_edges for these
+ *   triangles: such a loop is left alone); and leaves the first slot of every block's fill triangles in the workspace
+ *   (sfm_mesh_fill_workspace_bytes).  One wavefront per short loop.
+ * sfm_mesh_fill_emit: takes the same workspace, untouched, with the same tables and halfedge_fill, the vertices (float64
+ *   [n_vertices][3]) and the capacities of the outputs: fill_vertices float64 [cap_fill][3], fill_normals float32
+ *   [cap_fill][3], fill_name int32 [cap_fill] (the name of sub-loop r), fill_triangles int32 [cap_triangles][3] and
+ *   fill_triangle_halfedge int32 [cap_triangles] (the h of each).  It writes nothing at or above the capacities and returns
+ *   at once when both are 0.
+ * Every call returns SFM_ERR_ARG before any device work for a null handle, n_vertices outside 0 .. 2^31 - 1, n_triangles
+ * outside 0 .. (2^31 - 1) / 3, n_loops outside 0 .. n_triangles, max_edges outside 1 .. 64, a capacity below 0 or above
+ * 2^31 - 1, a null pointer (allowed only where its count is 0), or a workspace that is missing or too small. */
+int sfm_mesh_edges_workspace_bytes(sfm_handle h, int64_t n_triangles, int64_t* bytes_host);
+int sfm_mesh_edges(sfm_handle h, int64_t n_vertices, int64_t n_triangles, const int32_t* triangles, int32_t* halfedge_uses,
+                   int32_t* halfedge_twin, int32_t* halfedge_next, int32_t* halfedge_loop, int32_t* loop_leader,
+                   int32_t* loop_edges, int64_t* counts /* device [8] */, void* workspace, int64_t workspace_bytes);
+int sfm_mesh_fill_workspace_bytes(int64_t n_triangles, int64_t* bytes_host);
+int sfm_mesh_fill_mark(sfm_handle h, int64_t n_vertices, int64_t n_triangles, const int32_t* triangles,
+                       const int32_t* halfedge_next, int64_t n_loops, const int32_t* loop_leader, int64_t max_edges,
+                       int32_t* halfedge_fill, int64_t* counts /* device [4] */, void* workspace, int64_t workspace_bytes);
+int sfm_mesh_fill_emit(sfm_handle h, int64_t n_vertices, int64_t n_triangles, const int32_t* triangles,
+                       const int32_t* halfedge_next, int64_t n_loops, const int32_t* loop_leader, const int32_t* halfedge_fill,
+                       const double* vertices, int64_t cap_fill, int64_t cap_triangles, double* fill_vertices,
+                       float* fill_normals, int32_t* fill_name, int32_t* fill_triangles, int32_t* fill_triangle_halfedge,
+                       void* workspace, int64_t workspace_bytes);
+
 /* ---- colours of the mesh: per vertex a blend over the views that see it (sfm_amd/csrc/mesh_color.hip,
  *      mesh_color_rule.h, mesh_color_plan.h) ----
  * A pure function of its inputs: float64 without FMA contraction, no visit order, no atomics, no randomness, so NumPy

@@ -15,4 +15,5 @@ from .depth import (DepthMaps, FusedCloud, dense_from_reconstruction, depth_maps
 from .mesh import (Mesh, MeshRender, MeshTexture, RenderScore, TsdfVolume, check_score_arguments, mesh_texture, mesh_vertex_colors, render_mesh,  # noqa: F401
                    score_render, tsdf_volume_from_arrays)
 from .mesh_clean import MeshComponents, check_clean_arguments, clean_mesh, mesh_components  # noqa: F401
+from .mesh_fill import MeshEdges, check_fill_arguments, fill_mesh_holes, mesh_edges  # noqa: F401
 from .exposure import ExposureGains, apply_gains, check_exposure_arguments, mesh_exposure_tables, solve_gains  # noqa: F401

@@ -194,6 +194,11 @@ SIGNATURES = {
     "sfm_mesh_clean_mark": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, i64, i64, vp, vp, vp, i64]),
     "sfm_mesh_clean_emit": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, i64]),
     "sfm_mesh_gather_rows": (C.c_int, [vp, vp, i64, vp, i64, vp]),
+    "sfm_mesh_edges_workspace_bytes": (C.c_int, [vp, i64, C.POINTER(i64)]),
+    "sfm_mesh_edges": (C.c_int, [vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_mesh_fill_workspace_bytes": (C.c_int, [i64, C.POINTER(i64)]),
+    "sfm_mesh_fill_mark": (C.c_int, [vp, i64, i64, vp, vp, i64, vp, i64, vp, vp, vp, i64]),
+    "sfm_mesh_fill_emit": (C.c_int, [vp, i64, i64, vp, vp, i64, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, i64]),
     "sfm_mesh_colors_workspace_bytes": (C.c_int, [i32, C.POINTER(i64)]),
     "sfm_mesh_colors": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i64, vp, vp, f64, f64, i32, vp, vp, vp, vp, i64]),
     "sfm_mesh_exposure_workspace_bytes": (C.c_int, [i32, i32, i64, C.POINTER(i64)]),

@@ -497,7 +497,7 @@ def depth_maps_from_arrays(shapes, refs, src_ptr, src_image, warps, backproj, de
 
 def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=256, radius=2, rel_tol=0.01, max_cost=None,
                               min_consistent=2, colors=None, device=0, fuse=False, mesh=False, texture=None,
-                              min_triangles=None, keep_largest=None):
+                              min_triangles=None, keep_largest=None, fill_holes=None):
     """The chain on a `Reconstruction`: sources by shared points (`select_sources`), the depth interval of every view from
     its sparse points (`depth_ranges`), planes at most one pixel apart (`plane_depths`), `depth_maps`, `.filter`,
     `.point_cloud`.  images: one per image position of rec.tracks.  Returns (points, index, DepthMaps) - or (points, index,
@@ -507,7 +507,13 @@ def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=2
     by `Mesh.colors(colors)`, and with texture (an integer, the texels per triangle leg) it also gets the atlas of
     `Mesh.texture(colors, texels=texture)` as `Mesh.atlas`; the tuple keeps its shape.  With min_triangles or keep_largest
     (both None: nothing changes) the mesh is `Mesh.clean(min_triangles, keep_largest)` of that surface - min_triangles None
-    is 1 then - cleaned before it is coloured."""
+    is 1 then - cleaned before it is coloured.  With fill_holes (None: nothing changes; otherwise max_edges, 1 .. 64) the
+    mesh is then `Mesh.fill_holes(fill_holes)` of that: filled after the cleaning and before it is coloured."""
+    if fill_holes is not None:
+        from .mesh_fill import check_fill_arguments
+        if not mesh:
+            raise ValueError("fill_holes needs mesh=True")
+        check_fill_arguments(fill_holes)
     cleaning = min_triangles is not None or keep_largest is not None
     if cleaning:
         from .mesh_clean import check_clean_arguments
@@ -535,6 +541,8 @@ def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=2
     surface = (maps.tsdf().mesh(),) if mesh else ()
     if cleaning:
         surface = (surface[0].clean(min_triangles, keep_largest),)
+    if fill_holes is not None:
+        surface = (surface[0].fill_holes(int(fill_holes)),)
     if mesh and colors is not None:
         surface[0].colors(colors)
         if texture is not None:

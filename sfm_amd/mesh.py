@@ -88,6 +88,31 @@ class Mesh:
         from .mesh_clean import clean
         return clean(self, min_triangles, keep_largest, components)
 
+    # on what fill_holes() returns: where the new vertices and triangles start, how many sub-loops were filled with how many
+    # triangles, how many short sub-loops stayed open, the `MeshEdges` it used; None otherwise
+    fill_vertex_start = fill_triangle_start = n_filled = n_fill_triangles = n_open = edges_before = None
+    # int32 [n_fill_triangles]: the half-edge of the old mesh that each new triangle closes; None otherwise
+    fill_triangle_halfedge = property(lambda self: self._get("fill_triangle_halfedge", self.n_fill_triangles))
+
+    def edges(self):
+        """The edge table on the device (`sfm_mesh_edges`; include/sfm_amd.h states the rule): per half-edge 3 t + k how many
+        live half-edges use its edge, its twin, the next boundary half-edge about its end and the short boundary loop it is
+        on.  Returns a `MeshEdges` with the counts, `is_closed` and `euler`."""
+        from .mesh_fill import edges_of
+        return edges_of(self)
+
+    def fill_holes(self, max_edges=16, edges=None):
+        """A new `Mesh` with the small holes closed (`sfm_mesh_fill_mark` / `sfm_mesh_fill_emit`): every boundary loop of at
+        most 64 edges is split where it passes a vertex twice, and every part of 3 .. max_edges edges gets a vertex at the
+        mean of its own and one triangle per edge.  edges: what `edges()` returned for this mesh, None to build it now.  The
+        old vertices, normals and triangles are byte for byte in front; fill_vertex_start, fill_triangle_start, n_filled,
+        n_fill_triangles, fill_triangle_halfedge and edges_before say what was added.  The volume is carried over;
+        vertex_colors, n_views, best_view and atlas are None - a new vertex has no colour, so call colors() or texture()
+        again.  Longer boundary cycles, an outline among them, stay open; the outline of a lone fragment of at most
+        max_edges edges is closed too, so clean() first.  This mesh is untouched."""
+        from .mesh_fill import fill_holes
+        return fill_holes(self, max_edges, edges)
+
     def _view_inputs(self, what, images, maps, tol, min_cos, fill):
         """What colors() and texture() share: the maps and tol with their defaults, the checked scalars, the views' pixels
         back to back with their channel count, and proj / centres of the views on the host."""
@@ -1045,3 +1070,4 @@ def score_render(color, triangle, depth, photos, view_depth=None, view_keep=None
 
 
 from .mesh_clean import MeshComponents, check_clean_arguments, clean_mesh, mesh_components  # noqa: E402,F401
+from .mesh_fill import MeshEdges, check_fill_arguments, fill_mesh_holes, mesh_edges  # noqa: E402,F401

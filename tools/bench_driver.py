@@ -1149,6 +1149,72 @@ def measure_mesh_clean(h, dev, nv, nt, triangles, vertices, vnormals, reps=20, s
     return out
 
 
+def measure_mesh_fill(h, dev, nv, nt, triangles, vertices, reps=20, fan=1 << 20):
+    """sfm_mesh_edges, sfm_mesh_fill_mark and sfm_mesh_fill_emit (max_edges 16) on a mesh that is resident on the device, whole
+    calls by HIP events around `reps` calls after 3 warm-up calls, with the counts they report, and sfm_mesh_edges on a fan of
+    `fan` triangles (0, 1 + i, 1 + (i + 1) % fan) about one vertex beside the strip (i, i + 1, i + 2) of as many: the keys of
+    the "mesh" row they belong to.  The yardsticks are ms_mesh_components and ms_mesh_clean_mark + ms_mesh_clean_emit of
+    the same row."""
+    import torch
+    from sfm_amd.driver import _p
+    need = C.c_int64()
+
+    def edges_of(n_vertices, n_triangles, d_triangles):
+        h.call("sfm_mesh_edges_workspace_bytes", n_triangles, C.byref(need))
+        ws_bytes = need.value
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        out = [torch.empty(max(n, 1), dtype=torch.int32, device=dev) for n in (3 * n_triangles,) * 4 + (n_triangles,) * 2]
+        counts = torch.empty(8, dtype=torch.int64, device=dev)
+
+        def run():
+            h.call("sfm_mesh_edges", n_vertices, n_triangles, _p(d_triangles), *[_p(t) for t in out], _p(counts), _p(ws), ws_bytes)
+        for _ in range(3):
+            run()
+        return run, out, counts, ws_bytes
+
+    run_edges, (uses, twin, nxt, loop, leader, length), e_counts, edges_ws_bytes = edges_of(nv, nt, triangles)
+    ec = [int(c) for c in e_counts.cpu().numpy()]
+    n_loops = ec[4]
+    h.check(h.lib.sfm_mesh_fill_workspace_bytes(nt, C.byref(need)), "sfm_mesh_fill_workspace_bytes")
+    fill_need = need.value
+    fill_ws = torch.empty(fill_need, dtype=torch.uint8, device=dev)
+    flags = torch.empty(max(3 * nt, 1), dtype=torch.int32, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+
+    def run_fill_mark():
+        h.call("sfm_mesh_fill_mark", nv, nt, _p(triangles), _p(nxt), n_loops, _p(leader), 16, _p(flags), _p(counts), _p(fill_ws), fill_need)
+    for _ in range(3):
+        run_fill_mark()
+    filled, n_tri, n_open, status = (int(c) for c in counts.cpu().numpy())
+    fv = torch.empty((max(filled, 1), 3), dtype=torch.float64, device=dev)
+    fn = torch.empty((max(filled, 1), 3), dtype=torch.float32, device=dev)
+    name = torch.empty(max(filled, 1), dtype=torch.int32, device=dev)
+    ft = torch.empty((max(n_tri, 1), 3), dtype=torch.int32, device=dev)
+    fh = torch.empty(max(n_tri, 1), dtype=torch.int32, device=dev)
+
+    def run_fill_emit():
+        h.call("sfm_mesh_fill_emit", nv, nt, _p(triangles), _p(nxt), n_loops, _p(leader), _p(flags), _p(vertices), filled, n_tri, _p(fv), _p(fn), _p(name),
+               _p(ft), _p(fh), _p(fill_ws), fill_need)
+    for _ in range(3):
+        run_fill_emit()
+    lengths = np.sort(length[:n_loops].cpu().numpy())
+    out = {"ms_mesh_edges": timed(run_edges, reps) * 1e3, "ms_mesh_fill_mark": timed(run_fill_mark, reps) * 1e3,
+           "ms_mesh_fill_emit": timed(run_fill_emit, reps) * 1e3, "mesh_edges": ec[0], "mesh_boundary_edges": ec[1], "mesh_inconsistent_edges": ec[2],
+           "mesh_nonmanifold_edges": ec[3], "mesh_short_loops": ec[4], "mesh_long_boundary_edges": ec[5], "mesh_edges_status": ec[7],
+           "mesh_short_loop_edges": {str(int(k)): int((lengths == k).sum()) for k in np.unique(lengths)}, "mesh_edges_workspace_bytes": edges_ws_bytes,
+           "fill_max_edges": 16, "fill_sub_loops": filled, "fill_triangles": n_tri, "fill_left_open": n_open, "fill_status": status}
+    del uses, twin, nxt, loop, leader, length, fill_ws, flags, fv, fn, name, ft, fh
+    i = torch.arange(fan, dtype=torch.int32, device=dev)
+    for shape, tri, n_vertices, want in (("fan", torch.stack([torch.zeros_like(i), 1 + i, 1 + (i + 1) % fan], dim=1).contiguous(), fan + 1, [2 * fan, fan]),
+                                         ("strip", torch.stack([i, i + 1, i + 2], dim=1).contiguous(), fan + 2, [2 * fan + 1, fan + 2])):
+        run, _, shape_counts, _ = edges_of(n_vertices, fan, tri)
+        assert shape_counts.cpu().numpy().tolist()[:2] == want
+        out[f"ms_mesh_edges_{shape}_{fan}"] = timed(run, reps) * 1e3
+        del tri, run
+    out["mesh_edges_fan_over_strip"] = out[f"ms_mesh_edges_fan_{fan}"] / out[f"ms_mesh_edges_strip_{fan}"]
+    return out
+
+
 def measure_depth(reps=20, emit=None, mesh=False):
     """sfm_depth_census, sfm_depth_sweep and sfm_depth_filter on 36 synthetic 1024 x 768 views (the scene generator of
     tests/depth_reference.py: cameras on a line, baseline 0.1, f = 1228), every view a reference with its 4 nearest cameras
@@ -1166,8 +1232,9 @@ def measure_depth(reps=20, emit=None, mesh=False):
     the large-box list), then sfm_render_score of those 36 renders against the 36 images (window 7: once with both maps written and
     the views' depth, once the statistics alone; ms per view and the pooled figures), then the components of that mesh and its cleaning
     at min_triangles 100 (sfm_mesh_components, sfm_mesh_clean_mark, sfm_mesh_clean_emit) and sfm_mesh_components on the ascending strip
-    at 2^20 and 2^22 vertices with the ratio of the two times (`measure_mesh_clean`), whole calls by HIP events; the row is then named
-    "mesh"."""
+    at 2^20 and 2^22 vertices with the ratio of the two times (`measure_mesh_clean`), then the edge table of that mesh and the filling of
+    its holes at max_edges 16 (sfm_mesh_edges, sfm_mesh_fill_mark, sfm_mesh_fill_emit) and sfm_mesh_edges on a fan and on a strip of 2^20
+    triangles (`measure_mesh_fill`), whole calls by HIP events; the row is then named "mesh"."""
     import torch
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from depth_reference import make_scene
@@ -1415,6 +1482,10 @@ def measure_depth(reps=20, emit=None, mesh=False):
         # sfm_mesh_emit of this row are their yardsticks.  Then the labelling alone on the ascending strip at 2^20 and 2^22
         # vertices: linear work gives a time ratio of 4, work bound by the chain 16.
         row.update(measure_mesh_clean(h, dev, nv, nt, triangles, vertices, vnormals, reps))
+        # the edge table of the same mesh and the filling of its holes at max_edges 16, whole calls, 20 after 3; the labelling
+        # and the cleaning above are their yardsticks.  Then the table alone on a fan of 2^20 triangles about one vertex and
+        # on a strip of as many: the sort keeps the fan near the strip.
+        row.update(measure_mesh_fill(h, dev, nv, nt, triangles, vertices, reps))
         zv = vertices[:nv, 2].cpu().numpy()
         seen = int((weight != 0).sum().item())
         row.update({"grid_nodes": [nx, ny, nz], "voxel": float(voxel), "nodes_seen": seen, "projections": nx * ny * nz * n_img,
@@ -1472,7 +1543,7 @@ def main():
     ap.add_argument("--pyramid-only", action="store_true", help="only the multi-scale feature row (beside the single-scale stage on the same images); no other selection runs it")
     ap.add_argument("--guided-only", action="store_true", help="only the guided-matching row (beside the blind matcher)")
     ap.add_argument("--depth-only", action="store_true", help="only the dense-depth row (beside the feature stage on the same images)")
-    ap.add_argument("--mesh-only", action="store_true", help="only the meshing row: TSDF integration, mark and emit beside the sweep and the fusion of the same run, and the stages on that mesh up to its components and cleaning")
+    ap.add_argument("--mesh-only", action="store_true", help="only the meshing row: TSDF integration, mark and emit beside the sweep and the fusion of the same run, and the stages on that mesh up to its components and cleaning, its edge table and the filling of its holes")
     a = ap.parse_args()
     emit = lambda d: print(json.dumps(d), flush=True)
     only = a.fundamental_only or a.essential_only or a.homography_only or a.pnp_only or a.pose_only or a.tracks_only or a.triangulate_only or a.incremental_only or \

@@ -147,6 +147,69 @@ def refit(K, R, t, X, uv):
     return rodrigues(o.x[:3]), o.x[3:6].copy()
 
 
+def _exp_so3(w):
+    th = np.linalg.norm(w)
+    Kx = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0.0]])
+    if th < 1e-2:
+        a, b = 1 - th * th / 6 + th ** 4 / 120, 0.5 - th * th / 24 + th ** 4 / 720
+    else:
+        a, b = np.sin(th) / th, (1 - np.cos(th)) / (th * th)
+    return np.eye(3) + a * Kx + b * (Kx @ Kx)
+
+
+def local_sums(K, R, t, X, uv):
+    """(J^T J [6,6], J^T r [6], r^T r) of the reprojection residuals in pixels, for the unknowns (w, t) of the local
+    parametrisation R <- exp([w]x) R taken at w = 0: d(pixel)/dy [-[R X]x | I] with y = R X + t."""
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    q = X @ R.T
+    y = q + t
+    iz = 1.0 / y[:, 2]
+    ru, rv = fx * y[:, 0] * iz + cx - uv[:, 0], fy * y[:, 1] * iz + cy - uv[:, 1]
+    a0, a2, c1, c2 = fx * iz, -fx * y[:, 0] * iz * iz, fy * iz, -fy * y[:, 1] * iz * iz
+    z = np.zeros_like(iz)
+    ju = np.stack([a2 * q[:, 1], a0 * q[:, 2] - a2 * q[:, 0], -a0 * q[:, 1], a0, z, a2], 1)
+    jv = np.stack([c2 * q[:, 1] - c1 * q[:, 2], -c2 * q[:, 0], c1 * q[:, 0], z, c1, c2], 1)
+    return ju.T @ ju + jv.T @ jv, ju.T @ ru + jv.T @ rv, float(ru @ ru + rv @ rv)
+
+
+LM_ITERS = 30
+
+
+def lm_refit(K, R, t, X, uv, max_steps=LM_ITERS):
+    """The kernel's Levenberg-Marquardt (k_pnp_refine) in float64 NumPy over the given points: the same update
+    R <- exp([w]x) R, t <- t + d, the same damping (H + mu diag H, mu from 1e-3, x 0.1 on a step that lowers the cost and
+    never under 1e-12, x 10 otherwise) and the same stop, |step| <= 1e-12 (1 + |(angle(R), t)|) or max_steps steps.
+    Returns (R, t, the number of steps tried)."""
+    X, uv = np.asarray(X, np.float64).reshape(-1, 3), np.asarray(uv, np.float64).reshape(-1, 2)
+    R, t = np.array(R, np.float64), np.array(t, np.float64).reshape(3)
+    Rn, tn, mu, have, it = R, t, 1e-3, None, 0
+    for it in range(max_steps + 1):
+        with np.errstate(all="ignore"):
+            got = local_sums(K, Rn, tn, X, uv)
+        if it == 0 or got[2] < have[2]:
+            have, R, t = got, Rn, tn
+            if it > 0:
+                mu = max(mu * 0.1, 1e-12)
+        else:
+            mu *= 10.0
+        if it == max_steps or not np.isfinite(have[2]):
+            break
+        Hm, g, _ = have
+        try:
+            L = np.linalg.cholesky(Hm + mu * np.diag(np.diag(Hm)))
+        except np.linalg.LinAlgError:
+            break
+        d = -np.linalg.solve(L.T, np.linalg.solve(L, g))
+        if not np.isfinite(d).all():
+            break
+        v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+        ang = np.arctan2(0.5 * np.linalg.norm(v), 0.5 * (np.trace(R) - 1.0))
+        if np.linalg.norm(d) <= 1e-12 * (1.0 + np.sqrt(ang * ang + t @ t)):
+            break
+        Rn, tn = _exp_so3(d[:3]) @ R, t + d[3:]
+    return R, t, it
+
+
 def ransac(X, uv, K, samples, threshold=8.0, refine=False):
     """Follows the device for one segment on given samples [H,3].  Returns a dict: `hyp_count` [H] (best candidate
     count per hypothesis), `status` (0 ok, 1 fewer than 4 points, 2 no model), `R`, `t` (or None), `mask` [M] bool,

@@ -8,7 +8,9 @@ tests/solver_truth.py.  One call per stage through the C ABI (refine = 0) with a
 
 The segments are the scenes of solver_truth.scenes() in order, then one segment below the minimal size and one whose
 match 0 holds a NaN.  H = 65 for the essential stage (workgroups of 64 over the flat (segment, hypothesis) index straddle
-the segments and the last one is partial; 25 hypotheses per scoring workgroup) and 257 for the 256-lane kernels."""
+the segments and the last one is partial; 25 hypotheses per scoring workgroup) and 257 for the 256-lane kernels.  The
+Hartley transforms T are only read here; they, and the refits that follow the models, are judged in
+tests/test_refit_truth_gpu.py."""
 import ctypes as C
 import functools
 

@@ -72,6 +72,17 @@ class BALayout(C.Structure):
 # n_img, kp_ptr, kp_xy, n_nodes, track_ptr, n_tracks, obs_image, obs_kp, n_obs
 TRACK_SOURCE = (vp, i32, vp, i32, vp, vp, i64, vp, i64, vp, vp, i64)
 
+# the views as the per-view mesh calls take them after the handle (sfm_amd/_views.py spells the values).  VIEW_MAPS, for
+# sfm_tsdf_integrate: heights, widths, n_img, n_ref, ref_image, proj, depth, keep.  VIEW_SOURCE, for sfm_mesh_colors,
+# sfm_mesh_texture and sfm_mesh_exposure_sample: the same with centres behind proj and pixels, channels behind keep
+VIEW_MAPS = (vp, vp, i32, i32, vp, vp, vp, vp)
+VIEW_SOURCE = (vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32)
+
+
+# the pointer of a device tensor / of a host array as an argument; None passes null
+dp = lambda t: None if t is None else vp(t.data_ptr())
+hp = lambda a: None if a is None else vp(a.ctypes.data)
+
 # name -> (restype, argtypes); every symbol include/sfm_amd.h declares
 SIGNATURES = {
     "sfm_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
@@ -184,7 +195,7 @@ SIGNATURES = {
     "sfm_depth_fuse_mark": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f64, i32, f64, vp, vp, vp, vp, vp, i64]),
     "sfm_depth_fuse_gather": (C.c_int, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64]),
     "sfm_tsdf_workspace_bytes": (C.c_int, [i32, C.POINTER(i64)]),
-    "sfm_tsdf_integrate": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, f64, i32, i32, i32, f64, vp, vp, vp, i64]),
+    "sfm_tsdf_integrate": (C.c_int, [vp, *VIEW_MAPS, vp, f64, i32, i32, i32, f64, vp, vp, vp, i64]),
     "sfm_mesh_workspace_bytes": (C.c_int, [i32, i32, i32, C.POINTER(i64)]),
     "sfm_mesh_mark": (C.c_int, [vp, vp, vp, i32, i32, i32, i32, vp, vp, i64]),
     "sfm_mesh_emit": (C.c_int, [vp, vp, i32, i32, i32, vp, f64, i64, i64, vp, vp, vp, vp, i64]),
@@ -200,16 +211,15 @@ SIGNATURES = {
     "sfm_mesh_fill_mark": (C.c_int, [vp, i64, i64, vp, vp, i64, vp, i64, vp, vp, vp, i64]),
     "sfm_mesh_fill_emit": (C.c_int, [vp, i64, i64, vp, vp, i64, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, i64]),
     "sfm_mesh_colors_workspace_bytes": (C.c_int, [i32, C.POINTER(i64)]),
-    "sfm_mesh_colors": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i64, vp, vp, f64, f64, i32, vp, vp, vp, vp, i64]),
+    "sfm_mesh_colors": (C.c_int, [vp, *VIEW_SOURCE, i64, vp, vp, f64, f64, i32, vp, vp, vp, vp, i64]),
     "sfm_mesh_exposure_workspace_bytes": (C.c_int, [i32, i32, i64, C.POINTER(i64)]),
     "sfm_mesh_exposure_plan": (C.c_int, [i32, i32, i64, C.POINTER(i32)]),
-    "sfm_mesh_exposure_sample": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i64, vp, vp, f64, f64, vp, vp, vp, i64]),
+    "sfm_mesh_exposure_sample": (C.c_int, [vp, *VIEW_SOURCE, i64, vp, vp, f64, f64, vp, vp, vp, i64]),
     "sfm_mesh_exposure_gram": (C.c_int, [vp, i32, i32, i64, vp, vp, vp, vp, vp, i64]),
     "sfm_images_gain": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp]),
     "sfm_mesh_texture_size": (C.c_int, [i64, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
     "sfm_mesh_texture_workspace_bytes": (C.c_int, [i32, C.POINTER(i64)]),
-    "sfm_mesh_texture": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i64, vp, vp, i64, vp, i32, i32, f64, f64, i32, vp, vp, vp,
-                                   vp, i64]),
+    "sfm_mesh_texture": (C.c_int, [vp, *VIEW_SOURCE, i64, vp, vp, i64, vp, i32, i32, f64, f64, i32, vp, vp, vp, vp, i64]),
     "sfm_mesh_render_workspace_bytes": (C.c_int, [i32, vp, vp, i64, i64, C.POINTER(i64)]),
     "sfm_mesh_render": (C.c_int, [vp, i32, vp, vp, vp, i64, vp, i64, vp, i32, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i64]),
     "sfm_render_score_tile": (C.c_int, [C.POINTER(i32), C.POINTER(i32)]),

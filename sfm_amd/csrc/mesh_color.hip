@@ -12,6 +12,7 @@
 #include "common.h"
 #include "mesh_color_rule.h"
 #include "mesh_color_plan.h"
+#include "view_table.h"
 
 #pragma clang fp contract(off)
 
@@ -109,21 +110,15 @@ extern "C" int sfm_mesh_colors(sfm_handle h, const int32_t* heights, const int32
                                void* workspace, int64_t workspace_bytes) {
   if (!h) return SFM_ERR_ARG;
   const char* what = "sfm_mesh_colors";
-  std::vector<TsdfView> views((size_t)(n_ref > 0 && n_ref <= TSDF_MAX_VIEWS ? n_ref : 0) + 1);
-  int bad = tsdf_check_views(n_img, heights, widths, n_ref, ref_image, views.data());
+  ViewTable views;
+  int bad = view_table_build(n_img, heights, widths, n_ref, ref_image, &views);
   if (bad) return sfm_fail(h, SFM_ERR_ARG, what, MESH_WHY[bad]);
   bad = mesh_color_check(channels, n_vertices, tol, min_cos, fill);
-  if (bad) return sfm_fail(h, SFM_ERR_ARG, what, MESH_COLOR_WHY[bad]);
-  int64_t n_out = 0;
-  for (int r = 0; r < n_ref; ++r) n_out += (int64_t)views[(size_t)r].h * views[(size_t)r].w;
-  bad = mesh_color_check_buffers(n_ref, n_out, n_vertices, proj, centres, depth, pixels, vertices, normals, colors, n_views, best_view, workspace,
-                                 workspace_bytes);
+  if (!bad) bad = mesh_color_check_buffers(n_ref, views.n_out, n_vertices, proj, centres, depth, pixels, vertices, normals, colors, n_views,
+                                           best_view, workspace, workspace_bytes);
   if (bad) return sfm_fail(h, SFM_ERR_ARG, what, MESH_COLOR_WHY[bad]);
   if (n_vertices == 0) return SFM_OK;
-  views[(size_t)n_ref] = TsdfView{n_out, 0, 0};
-  // the view table is pageable host memory: the copy must have left it on return
-  SFM_HIP(h, hipMemcpyAsync(workspace, views.data(), views.size() * sizeof(TsdfView), hipMemcpyHostToDevice, h->stream));
-  SFM_HIP(h, hipStreamSynchronize(h->stream));
+  if (const int rc = sfm_put_views(h, views, workspace)) return rc;
   const dim3 grid((unsigned)mesh_color_blocks(n_vertices)), block(MESH_BLOCK);
   if (channels == 1)
     hipLaunchKernelGGL((k_mesh_colors<1, MESH_COLOR_BATCH>), grid, block, 0, h->stream, (const TsdfView*)workspace, n_ref, proj, centres, depth,

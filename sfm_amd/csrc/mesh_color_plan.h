@@ -35,8 +35,7 @@ inline int mesh_color_check_buffers(int64_t n_ref, int64_t n_out, int64_t n_vert
                                     const void* pixels, const void* vertices, const void* normals, const void* colors, const void* n_views,
                                     const void* best_view, const void* workspace, int64_t workspace_bytes) {
   if (!workspace || workspace_bytes < mesh_color_workspace_bytes(n_ref)) return 6;
-  if (n_ref > 0 && (!proj || !centres)) return 7;
-  if (n_out > 0 && (!depth || !pixels)) return 7;
+  if (!view_pointers_ok(n_ref, n_out, proj, centres, depth, pixels)) return 7;
   if (n_vertices > 0 && (!vertices || !normals || !colors || !n_views || !best_view)) return 7;
   return 0;
 }

@@ -60,8 +60,7 @@ inline int mesh_exposure_check_sample_buffers(int64_t n_ref, int64_t n_out, int6
                                               const void* pixels, const void* vertices, const void* normals, const void* seen, const void* samples,
                                               const void* workspace, int64_t workspace_bytes) {
   if (!workspace || workspace_bytes < mesh_exposure_workspace_bytes(n_ref)) return 4;
-  if (n_ref > 0 && (!proj || !centres)) return 5;
-  if (n_out > 0 && (!depth || !pixels)) return 5;
+  if (!view_pointers_ok(n_ref, n_out, proj, centres, depth, pixels)) return 5;
   if (n_vertices > 0 && (!vertices || !normals)) return 5;
   if (n_vertices > 0 && n_ref > 0 && (!seen || !samples)) return 5;
   return 0;

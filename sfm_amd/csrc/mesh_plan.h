@@ -109,5 +109,27 @@ inline int tsdf_check_views(int64_t n_img, const int32_t* heights, const int32_t
   }
   return 0;
 }
+// The views of a call as the kernels of tsdf.hip, mesh_color.hip, mesh_texture.hip and mesh_exposure.hip read them: n_ref
+// records and one that closes the list (out_off = n_out, no pixel); n_out the pixels of all views together.
+struct ViewTable { std::vector<TsdfView> views; int64_t n_out = 0; };
+
+// tsdf_check_views and, where it passes, the table.  0 = fine; otherwise an index into MESH_WHY.  The vector is sized before
+// n_ref is checked, so an n_ref out of range gets the closing record alone.
+inline int view_table_build(int64_t n_img, const int32_t* heights, const int32_t* widths, int64_t n_ref, const int32_t* ref_image, ViewTable* t) {
+  t->views.assign((size_t)(n_ref > 0 && n_ref <= TSDF_MAX_VIEWS ? n_ref : 0) + 1, TsdfView{0, 0, 0});
+  t->n_out = 0;
+  const int bad = tsdf_check_views(n_img, heights, widths, n_ref, ref_image, t->views.data());
+  if (bad) return bad;
+  for (int64_t r = 0; r < n_ref; ++r) t->n_out += (int64_t)t->views[(size_t)r].h * t->views[(size_t)r].w;
+  t->views[(size_t)n_ref] = TsdfView{t->n_out, 0, 0};
+  return 0;
+}
+
+// the view pointers of a call whose sizes passed: keep may always be null, proj / centres without a view, depth / pixels when
+// the views have no pixel
+inline bool view_pointers_ok(int64_t n_ref, int64_t n_out, const void* proj, const void* centres, const void* depth, const void* pixels) {
+  return !(n_ref > 0 && (!proj || !centres)) && !(n_out > 0 && (!depth || !pixels));
+}
+
 inline int tsdf_check_trunc(double trunc) { return (trunc > 0.0) ? 0 : 5; }
 inline int64_t tsdf_workspace_bytes(int64_t n_ref) { return mesh_align((n_ref + 1) * (int64_t)sizeof(TsdfView)) + 256; }

@@ -11,11 +11,14 @@
 // so occupancy hides the two dependent round trips per view and the thread takes MESH_TEXTURE_BATCH = 1 view at a time; the
 // batch is a template parameter as in k_mesh_colors, and the sums stay strictly in view order whatever it is.  The walk over
 // the views stands here as it does in k_mesh_colors, on the same functions of mesh_color_rule.h: moved into one inlined
-// function for both kernels it cost the colouring 4.5 % (tools/experiments/README.md).
+// function for both kernels it cost the colouring 4.5 % (tools/experiments/README.md).  k_exposure_sample
+// (mesh_exposure.hip) is the third place where the walk stands; what the host does around the three is spelt once
+// (ViewTable in mesh_plan.h, view_table.h).
 // A pure function of its inputs: no atomics, no visit order.
 #include "common.h"
 #include "mesh_texture_rule.h"
 #include "mesh_texture_plan.h"
+#include "view_table.h"
 
 #pragma clang fp contract(off)
 
@@ -150,24 +153,18 @@ extern "C" int sfm_mesh_texture(sfm_handle h, const int32_t* heights, const int3
                                 uint8_t* texture, uint8_t* views_out, float* uv, void* workspace, int64_t workspace_bytes) {
   if (!h) return SFM_ERR_ARG;
   const char* what = "sfm_mesh_texture";
-  std::vector<TsdfView> views((size_t)(n_ref > 0 && n_ref <= TSDF_MAX_VIEWS ? n_ref : 0) + 1);
-  int bad = tsdf_check_views(n_img, heights, widths, n_ref, ref_image, views.data());
+  ViewTable views;
+  int bad = view_table_build(n_img, heights, widths, n_ref, ref_image, &views);
   if (bad) return sfm_fail(h, SFM_ERR_ARG, what, MESH_WHY[bad]);
   bad = mesh_color_check(channels, n_vertices, tol, min_cos, fill);
   if (bad) return sfm_fail(h, SFM_ERR_ARG, what, MESH_COLOR_WHY[bad]);
   int32_t W = 0, H = 0;
   bad = mesh_texture_size(n_triangles, texels, cells_per_row, &W, &H);
-  if (bad) return sfm_fail(h, SFM_ERR_ARG, what, MESH_TEXTURE_WHY[bad]);
-  int64_t n_out = 0;
-  for (int r = 0; r < n_ref; ++r) n_out += (int64_t)views[(size_t)r].h * views[(size_t)r].w;
-  bad = mesh_texture_check_buffers(n_ref, n_out, n_vertices, n_triangles, proj, centres, depth, pixels, vertices, normals, triangles, texture,
-                                   views_out, uv, workspace, workspace_bytes);
+  if (!bad) bad = mesh_texture_check_buffers(n_ref, views.n_out, n_vertices, n_triangles, proj, centres, depth, pixels, vertices, normals,
+                                             triangles, texture, views_out, uv, workspace, workspace_bytes);
   if (bad) return sfm_fail(h, SFM_ERR_ARG, what, MESH_TEXTURE_WHY[bad]);
   if (n_triangles == 0) return SFM_OK;
-  views[(size_t)n_ref] = TsdfView{n_out, 0, 0};
-  // the view table is pageable host memory: the copy must have left it on return
-  SFM_HIP(h, hipMemcpyAsync(workspace, views.data(), views.size() * sizeof(TsdfView), hipMemcpyHostToDevice, h->stream));
-  SFM_HIP(h, hipStreamSynchronize(h->stream));
+  if (const int rc = sfm_put_views(h, views, workspace)) return rc;
   const dim3 grid((unsigned)mesh_texture_tiles_x(W), (unsigned)mesh_texture_tiles_y(H)), block(MESH_BLOCK);
   if (channels == 1)
     hipLaunchKernelGGL((k_mesh_texture<1, MESH_TEXTURE_BATCH>), grid, block, 0, h->stream, (const TsdfView*)workspace, n_ref, proj, centres, depth,

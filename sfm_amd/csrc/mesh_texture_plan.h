@@ -46,8 +46,7 @@ inline int mesh_texture_check_buffers(int64_t n_ref, int64_t n_out, int64_t n_ve
                                       const void* depth, const void* pixels, const void* vertices, const void* normals, const void* triangles,
                                       const void* texture, const void* views, const void* uv, const void* workspace, int64_t workspace_bytes) {
   if (!workspace || workspace_bytes < mesh_texture_workspace_bytes(n_ref)) return 5;
-  if (n_ref > 0 && (!proj || !centres)) return 6;
-  if (n_out > 0 && (!depth || !pixels)) return 6;
+  if (!view_pointers_ok(n_ref, n_out, proj, centres, depth, pixels)) return 6;
   if (n_vertices > 0 && (!vertices || !normals)) return 6;
   if (n_triangles > 0 && (!triangles || !texture || !views || !uv)) return 6;
   return 0;

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "tsdf_rule.h"
 #include "mesh_plan.h"
+#include "view_table.h"
 
 #pragma clang fp contract(off)
 
@@ -48,20 +49,15 @@ extern "C" int sfm_tsdf_integrate(sfm_handle h, const int32_t* heights, const in
                                   void* workspace, int64_t workspace_bytes) {
   if (!h) return SFM_ERR_ARG;
   const char* what = "sfm_tsdf_integrate";
-  std::vector<TsdfView> views((size_t)(n_ref > 0 && n_ref <= TSDF_MAX_VIEWS ? n_ref : 0) + 1);
-  int bad = tsdf_check_views(n_img, heights, widths, n_ref, ref_image, views.data());
+  ViewTable views;
+  int bad = view_table_build(n_img, heights, widths, n_ref, ref_image, &views);
   if (!bad) bad = mesh_check_grid(nx, ny, nz);
   if (!bad) bad = mesh_check_frame(origin, voxel);
   if (!bad) bad = tsdf_check_trunc(trunc);
   if (bad) return sfm_fail(h, SFM_ERR_ARG, what, MESH_WHY[bad]);
   if (!workspace || workspace_bytes < tsdf_workspace_bytes(n_ref)) return sfm_fail(h, SFM_ERR_ARG, what, "workspace missing or too small");
-  int64_t n_out = 0;
-  for (int r = 0; r < n_ref; ++r) n_out += (int64_t)views[(size_t)r].h * views[(size_t)r].w;
-  if (!tsdf || !weight || (n_ref > 0 && !proj) || (n_out > 0 && !depth)) return sfm_fail(h, SFM_ERR_ARG, what, "null pointer");
-  views[(size_t)n_ref] = TsdfView{n_out, 0, 0};
-  // the view table is pageable host memory: the copy must have left it on return
-  SFM_HIP(h, hipMemcpyAsync(workspace, views.data(), views.size() * sizeof(TsdfView), hipMemcpyHostToDevice, h->stream));
-  SFM_HIP(h, hipStreamSynchronize(h->stream));
+  if (!tsdf || !weight || (n_ref > 0 && !proj) || (views.n_out > 0 && !depth)) return sfm_fail(h, SFM_ERR_ARG, what, "null pointer");
+  if (const int rc = sfm_put_views(h, views, workspace)) return rc;
   const int64_t n_nodes = mesh_nodes(nx, ny, nz);
   hipLaunchKernelGGL(k_tsdf_integrate, dim3((unsigned)mesh_blocks(n_nodes)), dim3(MESH_BLOCK), 0, h->stream, (const TsdfView*)workspace, n_ref,
                      proj, depth, keep, origin[0], origin[1], origin[2], voxel, nx, ny, nz, trunc, (uint32_t*)tsdf, weight);

@@ -12,6 +12,8 @@ from numbers import Real
 import numpy as np
 
 from . import _lib
+from ._lib import dp, hp
+from ._views import ViewSet, centres_from_projections, check_color_images, workspace  # noqa: F401
 
 MAX_VIEWS = 1024
 
@@ -75,12 +77,6 @@ def solve_gains(overlap, sums, sigma_n=10.0, sigma_g=1.0, min_overlap=1):
     return gains
 
 
-def centres_from_projections(proj):
-    """float64 [n,3]: the camera centres C = -M^-1 p of row-major [M | p] = [K R | K t]."""
-    P = np.asarray(proj, dtype=np.float64).reshape(-1, 3, 4)
-    return np.array([-np.linalg.solve(p[:, :3], p[:, 3]) for p in P]).reshape(-1, 3)
-
-
 class ExposureGains:
     """What `Mesh.exposure` returns.  gains float64 [n_views, channels], overlap int64 [n_views, n_views], sums int64
     [n_views, n_views, channels]; seen uint8 [n_views, nv] and samples uint8 [n_views, channels, nv] stay on the device until
@@ -132,31 +128,23 @@ def sample_spread(seen, samples):
     return np.where(seen.sum(axis=0) >= 2, (hi - lo).astype(np.float64), np.nan).T
 
 
-def _tables(dev, heights, widths, ref_image, proj, centres, d_depth, d_keep, d_pixels, channels, n_vertices, d_vertices, d_normals, tol, min_cos):
-    """The two device calls: heights / widths (int32 per image), ref_image (int32 per view), proj [n_ref,12] and centres
-    [n_ref,3] on the host; the maps, the pixels, the vertices and the normals on the device (d_keep may be None).  Returns the
-    device state: seen, samples, overlap, sums."""
+def _tables(views, n_vertices, d_vertices, d_normals, tol, min_cos):
+    """The two device calls: a `ViewSet` with its pixels; the vertices and the normals on the device.  Returns the device
+    state: seen, samples, overlap, sums."""
     import torch
+    dev = views.depth.device
     h = _lib.get_handle(dev.index)
-    n_ref, n_img, nv = len(ref_image), len(heights), int(n_vertices)
-    table = lambda a, k: (torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, k)).to(dev) if n_ref
-                          else torch.zeros((1, k), dtype=torch.float64, device=dev))
-    d_proj, d_centres = table(proj, 12), table(centres, 3)
-    need = C.c_int64()
-    h.check(h.lib.sfm_mesh_exposure_workspace_bytes(n_ref, int(channels), nv, C.byref(need)), "sfm_mesh_exposure_workspace_bytes")
-    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    n_ref, channels, nv = views.n_ref, views.channels, int(n_vertices)
+    ws, ws_bytes = workspace(h, dev, "sfm_mesh_exposure_workspace_bytes", n_ref, channels, nv)
     out = {"seen": torch.empty(max(n_ref * nv, 1), dtype=torch.uint8, device=dev),
            "samples": torch.empty(max(n_ref * channels * nv, 1), dtype=torch.uint8, device=dev),
            "overlap": torch.empty(max(n_ref * n_ref, 1), dtype=torch.int64, device=dev),
            "sums": torch.empty(max(n_ref * n_ref * channels, 1), dtype=torch.int64, device=dev)}
-    dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    hp = lambda a: C.c_void_p(a.ctypes.data)
-    h.call("sfm_mesh_exposure_sample", hp(heights), hp(widths), n_img, n_ref, hp(ref_image), dp(d_proj), dp(d_centres), dp(d_depth), dp(d_keep),
-           dp(d_pixels), int(channels), nv, dp(d_vertices), dp(d_normals), C.c_double(float(tol)), C.c_double(float(min_cos)),
-           dp(out["seen"]), dp(out["samples"]), dp(ws), need.value)
-    h.call("sfm_mesh_exposure_gram", n_ref, int(channels), nv, dp(out["seen"]), dp(out["samples"]), dp(out["overlap"]), dp(out["sums"]),
-           dp(ws), need.value)
-    out["held"] = (ws, d_proj, d_centres, d_depth, d_keep, d_pixels, d_vertices, d_normals)      # alive while the calls may still run
+    h.call("sfm_mesh_exposure_sample", *views.args(), nv, dp(d_vertices), dp(d_normals), C.c_double(float(tol)), C.c_double(float(min_cos)),
+           dp(out["seen"]), dp(out["samples"]), dp(ws), ws_bytes)
+    h.call("sfm_mesh_exposure_gram", n_ref, channels, nv, dp(out["seen"]), dp(out["samples"]), dp(out["overlap"]), dp(out["sums"]),
+           dp(ws), ws_bytes)
+    out["held"] = (ws, d_vertices, d_normals) + views.alive()       # alive while the calls may still run
     return out
 
 
@@ -170,32 +158,12 @@ def mesh_exposure_tables(vertices, normals, proj, centres, depth, keep, images, 
     """`sfm_mesh_exposure_sample` and `sfm_mesh_exposure_gram` on arrays that were made elsewhere; the arguments are those of
     `mesh_vertex_colors`.  Returns (seen uint8 [n,nv], samples uint8 [n,channels,nv], overlap int64 [n,n], sums int64
     [n,n,channels])."""
-    import torch
-    from .mesh import check_color_images
-    check_exposure_arguments(tol, min_cos, n_views=len(depth))
-    vertices = np.ascontiguousarray(vertices, dtype=np.float64)
-    normals = np.ascontiguousarray(normals, dtype=np.float32)
-    if vertices.ndim != 2 or vertices.shape[1] != 3 or normals.shape != vertices.shape:
-        raise ValueError("vertices and normals must be [nv,3]")
-    depth = [np.ascontiguousarray(d, dtype=np.float32) for d in depth]
-    if any(d.ndim != 2 for d in depth) or np.shape(proj) != (len(depth), 12) or np.shape(centres) != (len(depth), 3):
-        raise ValueError("depth: [h,w] maps; proj: 12 numbers and centres: 3 numbers for each")
-    if keep is not None and [np.shape(k) for k in keep] != [d.shape for d in depth]:
-        raise ValueError("keep must be None or one [h,w] array per view, shaped like its depth map")
-    flat, channels = check_color_images(images, [d.shape for d in depth])
-    _lib.get_handle(device)
-    dev = torch.device("cuda", device)
-
-    def up(arrays, dtype):
-        return torch.from_numpy(np.concatenate([np.asarray(a, dtype=dtype).reshape(-1) for a in arrays] + [np.zeros(1, dtype)])).to(dev)
-
-    pad = lambda a: np.concatenate([a, np.zeros((1, 3), a.dtype)])           # one row more: a pointer must exist
-    heights = np.array([d.shape[0] for d in depth], dtype=np.int32)
-    widths = np.array([d.shape[1] for d in depth], dtype=np.int32)
-    n, nv = len(depth), len(vertices)
-    st = _tables(dev, heights, widths, np.arange(n, dtype=np.int32), proj, centres, up(depth, np.float32),
-                 None if keep is None else up(keep, np.uint8), torch.from_numpy(flat).to(dev), channels, nv,
-                 torch.from_numpy(pad(vertices)).to(dev), torch.from_numpy(pad(normals)).to(dev), tol, min_cos)
+    from .mesh import check_mesh_arrays, upload_rows
+    check_exposure_arguments(tol, min_cos)
+    vertices, normals, _ = check_mesh_arrays(vertices, normals)
+    views = ViewSet.from_arrays(proj, centres, depth, keep, MAX_VIEWS, images).to(device)
+    dev, n, nv, channels = views.depth.device, views.n_ref, len(vertices), views.channels
+    st = _tables(views, nv, upload_rows(vertices, dev), upload_rows(normals, dev), tol, min_cos)
     overlap, sums = _host_tables(st, n, channels)
     return (st["seen"].cpu().numpy()[:n * nv].reshape(n, nv), st["samples"].cpu().numpy()[:n * channels * nv].reshape(n, channels, nv),
             overlap, sums)
@@ -205,7 +173,6 @@ def apply_gains(images, gains, device=0):
     """`sfm_images_gain`: images one uint8 [h,w] or [h,w,3] array each, all with the same channel count, gains float64
     [n, channels], each finite and >= 0.  Returns the arrays with out = min(floor(in * g + 0.5), 255) per pixel and channel."""
     import torch
-    from .mesh import check_color_images
     arrays = [np.asarray(a) for a in images]
     flat, channels = check_color_images(arrays, [a.shape[:2] for a in arrays])
     g = check_gains(gains, len(arrays), channels)
@@ -215,9 +182,8 @@ def apply_gains(images, gains, device=0):
     widths = np.array([a.shape[1] for a in arrays] + [0], dtype=np.int32)
     d_in = torch.from_numpy(flat).to(dev)
     d_out = torch.empty_like(d_in)
-    hp = lambda a: C.c_void_p(a.ctypes.data)
     gp = np.concatenate([g.reshape(-1), np.ones(1)])               # one element more: a pointer must exist
-    h.call("sfm_images_gain", hp(heights), hp(widths), len(arrays), int(channels), hp(gp), C.c_void_p(d_in.data_ptr()), C.c_void_p(d_out.data_ptr()))
+    h.call("sfm_images_gain", hp(heights), hp(widths), len(arrays), int(channels), hp(gp), dp(d_in), dp(d_out))
     host = d_out.cpu().numpy()                                     # waits for the call: gp and d_in may go
     out, o = [], 0
     for a in arrays:
@@ -228,40 +194,11 @@ def apply_gains(images, gains, device=0):
 
 def mesh_exposure(mesh, images, maps=None, tol=None, min_cos=0.35, sigma_n=10.0, sigma_g=1.0, min_overlap=1):
     """What `Mesh.exposure` does."""
-    import torch
-    from .mesh import check_color_images
-    vol = mesh._volume
-    maps = getattr(vol, "_maps", None) if maps is None else maps
-    if tol is None:
-        if vol is None:
-            raise ValueError("exposure() needs tol: the mesh has no volume")
-        tol = getattr(vol, "trunc", 3.0 * vol.voxel)
-    dev = mesh._m["vertices"].device if "vertices" in mesh._m else None
-    if maps is not None:
-        if getattr(maps, "keep", None) is None:
-            raise ValueError("exposure() needs filter() first")
-        check_exposure_arguments(tol, min_cos, sigma_n, sigma_g, min_overlap, len(maps.views))
-        s = maps._s
-        if len(images) != len(s["imgs"]):
-            raise ValueError("images: one array per image of the set")
-        flat, channels = check_color_images([images[r] for r in maps.views], maps.shapes)
-        n_ref, views, n_images = len(maps.views), list(maps.views), len(s["imgs"])
-        backproj = s["backproj"].cpu().numpy()[:n_ref].reshape(-1, 3, 4)
-        from .mesh import projections_from_backprojections
-        proj, centres = projections_from_backprojections(backproj), np.ascontiguousarray(backproj[:, :, 3])
-        heights, widths, ref_image, d_depth, d_keep = s["heights"], s["widths"], s["ref_image"], s["depth"], s["keep"]
-    else:
-        held = getattr(vol, "_views", None)
-        if held is None:
-            raise ValueError("exposure() needs maps: the mesh's volume was not integrated from depth maps")
-        heights, widths, ref_image, d_depth, d_keep = held
-        check_exposure_arguments(tol, min_cos, sigma_n, sigma_g, min_overlap, len(ref_image))
-        n_ref, views, n_images = len(ref_image), [int(r) for r in ref_image], len(heights)
-        if len(images) != n_images:
-            raise ValueError("images: one array per view")
-        flat, channels = check_color_images([images[r] for r in views], [(int(heights[r]), int(widths[r])) for r in views])
-        proj, centres = vol.proj, centres_from_projections(vol.proj)
-    st = _tables(dev, heights, widths, ref_image, proj, centres, d_depth, d_keep, torch.from_numpy(flat).to(dev), channels, mesh.n_vertices,
-                 mesh._m["vertices"], mesh._m["normals"], tol, min_cos)
-    overlap, sums = _host_tables(st, n_ref, channels)
-    return ExposureGains(st, solve_gains(overlap, sums, sigma_n, sigma_g, min_overlap), overlap, sums, mesh.n_vertices, channels, views, n_images)
+    tol = mesh._tol("exposure", tol)
+    check_exposure_arguments(tol, min_cos, sigma_n, sigma_g, min_overlap)
+    views = mesh._views("exposure", maps, images, arrays_too=True)
+    check_exposure_arguments(tol, min_cos, n_views=views.n_ref)
+    st = _tables(views, mesh.n_vertices, mesh._m["vertices"], mesh._m["normals"], tol, min_cos)
+    overlap, sums = _host_tables(st, views.n_ref, views.channels)
+    return ExposureGains(st, solve_gains(overlap, sums, sigma_n, sigma_g, min_overlap), overlap, sums, mesh.n_vertices, views.channels, views.views,
+                         views.n_images)

@@ -20,6 +20,8 @@ from numbers import Real
 import numpy as np
 
 from . import _lib
+from ._lib import dp, hp
+from ._views import ViewSet, check_color_images, projections_from_backprojections, workspace  # noqa: F401
 
 MIN_DIM, MAX_DIM, MAX_VIEWS = 2, 1024, 65535
 
@@ -113,27 +115,30 @@ class Mesh:
         from .mesh_fill import fill_holes
         return fill_holes(self, max_edges, edges)
 
+    def _views(self, what, maps, images=None, arrays_too=False):
+        """The `ViewSet` of a per-view call, with the pixels of images where they are given: that of `maps`, None for the one
+        the mesh's volume remembers.  A volume integrated from arrays has no `DepthMaps` behind its set and no centres in
+        it; only a caller that says arrays_too takes it."""
+        if maps is not None:
+            return ViewSet.from_maps(maps, what, images)
+        views = getattr(self._volume, "views", None)
+        if views is None or (views.maps is None and not arrays_too):
+            raise ValueError(f"{what}() needs maps: the mesh's volume was not " + ("integrated from depth maps" if arrays_too else "built by DepthMaps.tsdf()"))
+        return views if images is None else views.with_centres().with_images(images)
+
+    def _tol(self, what, tol):
+        """tol, None for the truncation of the mesh's volume."""
+        if tol is not None:
+            return tol
+        if self._volume is None:
+            raise ValueError(f"{what}() needs tol: the mesh has no volume")
+        return getattr(self._volume, "trunc", 3.0 * self._volume.voxel)
+
     def _view_inputs(self, what, images, maps, tol, min_cos, fill):
-        """What colors() and texture() share: the maps and tol with their defaults, the checked scalars, the views' pixels
-        back to back with their channel count, and proj / centres of the views on the host."""
-        maps = getattr(self._volume, "_maps", None) if maps is None else maps
-        if maps is None:
-            raise ValueError(f"{what}() needs maps: the mesh's volume was not built by DepthMaps.tsdf()")
-        if getattr(maps, "keep", None) is None:
-            raise ValueError(f"{what}() needs filter() first")
-        if tol is None:
-            vol = self._volume
-            if vol is None:
-                raise ValueError(f"{what}() needs tol: the mesh has no volume")
-            tol = getattr(vol, "trunc", 3.0 * vol.voxel)
+        """What colors() and texture() share: the views with their pixels, and tol with its default; both checked."""
+        tol = self._tol(what, tol)
         check_color_scalars(tol, min_cos, fill)
-        s = maps._s
-        if len(images) != len(s["imgs"]):
-            raise ValueError("images: one array per image of the set")
-        flat, channels = check_color_images([images[r] for r in maps.views], maps.shapes)
-        n_ref = len(maps.views)
-        backproj = s["backproj"].cpu().numpy()[:n_ref].reshape(-1, 3, 4)
-        return maps, tol, flat, channels, projections_from_backprojections(backproj), np.ascontiguousarray(backproj[:, :, 3])
+        return self._views(what, maps, images), tol
 
     def colors(self, images, maps=None, tol=None, min_cos=0.35, fill=0):
         """A colour per vertex on the device (`sfm_mesh_colors`; include/sfm_amd.h states the rule): the vertex is projected
@@ -144,13 +149,8 @@ class Mesh:
         `DepthMaps`, None for those the mesh's volume was integrated from; tol: None for the truncation of the volume
         (3 voxels); fill: the colour of a vertex that no view sees.  Returns uint8 [nv] or [nv,3] and fills vertex_colors,
         n_views and best_view (the position of the view with the largest weight, -1 for none)."""
-        maps, tol, flat, channels, proj, centres = self._view_inputs("colors", images, maps, tol, min_cos, fill)
-        s = maps._s
-        import torch
-        dev = self._m["vertices"].device
-        out = _colors(dev, s["heights"], s["widths"], s["ref_image"], proj, centres, s["depth"], s["keep"], torch.from_numpy(flat).to(dev),
-                      channels, self.n_vertices, self._m["vertices"], self._m["normals"], tol, min_cos, fill)
-        self._m.update(out)
+        views, tol = self._view_inputs("colors", images, maps, tol, min_cos, fill)
+        self._m.update(_colors(views, self.n_vertices, self._m["vertices"], self._m["normals"], tol, min_cos, fill))
         for name in ("vertex_colors", "n_views", "best_view"):
             self._host.pop(name, None)
         return self.vertex_colors
@@ -176,13 +176,9 @@ class Mesh:
         of `colors()`; fill is also the colour of the texels that belong to no triangle.  Returns a `MeshTexture` and keeps
         it as `atlas`."""
         cells_per_row = check_texture_layout(self.n_triangles, texels, cells_per_row)[0]
-        maps, tol, flat, channels, proj, centres = self._view_inputs("texture", images, maps, tol, min_cos, fill)
-        s = maps._s
-        import torch
-        dev = self._m["vertices"].device
-        self.atlas = _texture(dev, s["heights"], s["widths"], s["ref_image"], proj, centres, s["depth"], s["keep"], torch.from_numpy(flat).to(dev),
-                              channels, self.n_vertices, self._m["vertices"], self._m["normals"], self.n_triangles, self._m["triangles"],
-                              texels, cells_per_row, tol, min_cos, fill)
+        views, tol = self._view_inputs("texture", images, maps, tol, min_cos, fill)
+        self.atlas = _texture(views, self.n_vertices, self._m["vertices"], self._m["normals"], self.n_triangles, self._m["triangles"], texels,
+                              cells_per_row, tol, min_cos, fill)
         return self.atlas
 
     def render(self, cameras, sizes, colors="auto", fill=0):
@@ -209,11 +205,8 @@ class Mesh:
     def render_views(self, maps=None, colors="auto", fill=0):
         """`render()` through the cameras of the views of a `DepthMaps`, each at the size of its maps: the render of every
         input photograph that has a depth map.  maps: None for those the mesh's volume was integrated from."""
-        maps = getattr(self._volume, "_maps", None) if maps is None else maps
-        if maps is None:
-            raise ValueError("render_views() needs maps: the mesh's volume was not built by DepthMaps.tsdf()")
-        n_ref = len(maps.views)
-        proj = projections_from_backprojections(maps._s["backproj"].cpu().numpy()[:n_ref])
+        maps = self._views("render_views", None).maps if maps is None else maps       # no filter() is needed here
+        proj = projections_from_backprojections(maps._s["backproj"].cpu().numpy()[:len(maps.views)])
         return self.render(list(proj), [(w, h) for h, w in maps.shapes], colors, fill)
 
     def score(self, images, maps=None, colors="auto", **options):
@@ -221,9 +214,7 @@ class Mesh:
         photograph and its own depth map (`sfm_render_score`).  images: one array per IMAGE of the set, as `colors()` and
         `texture()` take them, or one per view; options: masks, window, rel_tol, keep_maps of `MeshRender.compare`.
         Returns a `RenderScore`."""
-        maps = getattr(self._volume, "_maps", None) if maps is None else maps
-        if maps is None:
-            raise ValueError("score() needs maps: the mesh's volume was not built by DepthMaps.tsdf()")
+        maps = self._views("score", None).maps if maps is None else maps
         if len(images) == len(maps._s["imgs"]):
             images = [images[r] for r in maps.views]
         return self.render_views(maps, colors).compare(images, maps, **options)
@@ -308,19 +299,16 @@ class TsdfVolume:
         dev = self._tsdf.device
         h = _lib.get_handle(dev.index)
         nx, ny, nz = self.shape
-        need = C.c_int64()
-        h.check(h.lib.sfm_mesh_workspace_bytes(nx, ny, nz, C.byref(need)), "sfm_mesh_workspace_bytes")
-        ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        ws, ws_bytes = workspace(h, dev, "sfm_mesh_workspace_bytes", nx, ny, nz)
         counts = torch.empty(2, dtype=torch.int64, device=dev)
-        dp = lambda t: C.c_void_p(t.data_ptr())
         origin = np.ascontiguousarray(self.origin, dtype=np.float64)
-        h.call("sfm_mesh_mark", dp(self._tsdf), dp(self._weight), nx, ny, nz, int(min_weight), dp(counts), dp(ws), need.value)
+        h.call("sfm_mesh_mark", dp(self._tsdf), dp(self._weight), nx, ny, nz, int(min_weight), dp(counts), dp(ws), ws_bytes)
         nv, nt = (int(c) for c in counts.cpu().numpy())            # waits for the mark call: the counts size the outputs
         m = {"vertices": torch.empty((max(nv, 1), 3), dtype=torch.float64, device=dev),
              "normals": torch.empty((max(nv, 1), 3), dtype=torch.float32, device=dev),
              "triangles": torch.empty((max(nt, 1), 3), dtype=torch.int32, device=dev)}
-        h.call("sfm_mesh_emit", dp(self._tsdf), nx, ny, nz, C.c_void_p(origin.ctypes.data), C.c_double(self.voxel), nv, nt,
-               dp(m["vertices"]), dp(m["normals"]), dp(m["triangles"]), dp(ws), need.value)
+        h.call("sfm_mesh_emit", dp(self._tsdf), nx, ny, nz, hp(origin), C.c_double(self.voxel), nv, nt,
+               dp(m["vertices"]), dp(m["normals"]), dp(m["triangles"]), dp(ws), ws_bytes)
         m["ws"] = ws                                               # alive until the outputs are: the emit call may still run
         return Mesh(m, nv, nt, self)
 
@@ -339,16 +327,6 @@ def tsdf_volume_from_arrays(tsdf, weight, origin, voxel, device=0):
     dev = torch.device("cuda", device)
     return TsdfVolume(torch.from_numpy(tsdf.reshape(-1)).to(dev), torch.from_numpy(weight.astype(np.uint16).view(np.int16).reshape(-1)).to(dev),
                       origin, voxel, shape)
-
-
-def projections_from_backprojections(backproj):
-    """[n,12] [P | p] = [K R | K t] from the [M | c] = [R^T K^-1 | -R^T t] that `view_backprojection` makes: P = M^-1, p = -P c."""
-    B = np.asarray(backproj, dtype=np.float64).reshape(-1, 3, 4)
-    out = np.zeros((len(B), 12))
-    for v, b in enumerate(B):
-        P = np.linalg.inv(b[:, :3])
-        out[v] = np.c_[P, -P @ b[:, 3]].reshape(12)
-    return out
 
 
 def bounding_grid(points, resolution=256, margin=0.05):
@@ -382,7 +360,6 @@ def integrate_depth_maps(maps, origin=None, voxel=None, shape=None, resolution=2
         raise ValueError("origin, voxel and shape come together or not at all")
     if not (isinstance(min_weight, (int, np.integer)) and min_weight >= 0):
         raise ValueError("min_weight must be an integer >= 0")
-    s = maps._s
     if len(maps.views) > MAX_VIEWS:
         raise ValueError(f"at most {MAX_VIEWS} views")
     if not all(given):
@@ -392,61 +369,35 @@ def integrate_depth_maps(maps, origin=None, voxel=None, shape=None, resolution=2
     trunc = 3.0 * voxel if trunc is None else trunc
     if not (isinstance(trunc, Real) and trunc > 0):
         raise ValueError("trunc must be None or a number > 0")
-    n_ref = len(maps.views)
-    proj = projections_from_backprojections(s["backproj"].cpu().numpy()[:n_ref])
-    vol = _integrate(s["depth"].device, s["heights"], s["widths"], s["ref_image"], proj, s["depth"], s["keep"], origin, voxel, shape, trunc)
+    vol = _integrate(ViewSet.from_maps(maps, "tsdf"), origin, voxel, shape, trunc)
     vol.min_weight = int(min_weight)
-    vol._maps = maps                                               # what Mesh.colors() projects into by default
     return vol
 
 
-def _integrate(dev, heights, widths, ref_image, proj, d_depth, d_keep, origin, voxel, shape, trunc):
-    """The device call: heights / widths (int32 per image) and ref_image (int32 per view) on the host, proj float64 [n_ref,12]
-    on the host, the maps of the views back to back on the device (d_keep may be None)."""
+def _integrate(views, origin, voxel, shape, trunc):
+    """The device call.  The volume remembers the views: what Mesh.colors(), texture(), exposure(), render_views() and score()
+    project into by default, and what keeps the call's inputs alive while it may still run."""
     import torch
+    dev = views.depth.device
     h = _lib.get_handle(dev.index)
-    n_ref, n_img = len(ref_image), len(heights)
-    proj = np.ascontiguousarray(proj, dtype=np.float64).reshape(-1, 12)
-    d_proj = torch.from_numpy(proj).to(dev) if n_ref else torch.zeros((1, 12), dtype=torch.float64, device=dev)
-    need = C.c_int64()
-    h.check(h.lib.sfm_tsdf_workspace_bytes(n_ref, C.byref(need)), "sfm_tsdf_workspace_bytes")
-    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    ws, ws_bytes = workspace(h, dev, "sfm_tsdf_workspace_bytes", views.n_ref)
     n = shape[0] * shape[1] * shape[2]
     tsdf = torch.empty(n, dtype=torch.float32, device=dev)
     weight = torch.empty(n, dtype=torch.int16, device=dev)
-    dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    hp = lambda a: C.c_void_p(a.ctypes.data)
-    h.call("sfm_tsdf_integrate", hp(heights), hp(widths), n_img, n_ref, hp(ref_image), dp(d_proj), dp(d_depth), dp(d_keep), hp(origin),
-           C.c_double(voxel), shape[0], shape[1], shape[2], C.c_double(float(trunc)), dp(tsdf), dp(weight), dp(ws), need.value)
+    h.call("sfm_tsdf_integrate", *views.args(maps_only=True), hp(origin), C.c_double(voxel), shape[0], shape[1], shape[2],
+           C.c_double(float(trunc)), dp(tsdf), dp(weight), dp(ws), ws_bytes)
     vol = TsdfVolume(tsdf, weight, origin, voxel, shape)
-    vol.trunc, vol.proj, vol._ws = float(trunc), proj, (ws, d_proj, d_depth, d_keep)       # alive while the call may still run
-    vol._views = (heights, widths, ref_image, d_depth, d_keep)     # what Mesh.exposure() projects into without a DepthMaps
+    vol.trunc, vol.proj, vol.views, vol._held = float(trunc), views.proj, views, ws
     return vol
 
 
 def tsdf_volume_from_depth_arrays(proj, depth, keep, origin, voxel, shape, trunc, device=0):
     """A `TsdfVolume` integrated from maps that were made elsewhere: proj float64 [n,12] (row-major [K R | K t]), depth one
     float32 [h,w] per view, keep one uint8 [h,w] per view or None (every finite depth counts)."""
-    import torch
     origin, voxel, shape = check_grid(origin, voxel, shape)
     if not (isinstance(trunc, Real) and trunc > 0):
         raise ValueError("trunc must be a number > 0")
-    depth = [np.ascontiguousarray(d, dtype=np.float32) for d in depth]
-    if any(d.ndim != 2 for d in depth) or np.shape(proj) != (len(depth), 12) or len(depth) > MAX_VIEWS:
-        raise ValueError(f"depth: at most {MAX_VIEWS} [h,w] maps; proj: 12 numbers for each")
-    if keep is not None and [np.shape(k) for k in keep] != [d.shape for d in depth]:
-        raise ValueError("keep must be None or one [h,w] array per view, shaped like its depth map")
-    _lib.get_handle(device)
-    dev = torch.device("cuda", device)
-
-    def up(arrays, dtype):
-        flat = np.concatenate([np.asarray(a, dtype=dtype).reshape(-1) for a in arrays] + [np.zeros(1, dtype)])
-        return torch.from_numpy(flat).to(dev)
-
-    heights = np.array([d.shape[0] for d in depth], dtype=np.int32)
-    widths = np.array([d.shape[1] for d in depth], dtype=np.int32)
-    return _integrate(dev, heights, widths, np.arange(len(depth), dtype=np.int32), proj, up(depth, np.float32),
-                      None if keep is None else up(keep, np.uint8), origin, voxel, shape, trunc)
+    return _integrate(ViewSet.from_arrays(proj, None, depth, keep, MAX_VIEWS, integration_only=True).to(device), origin, voxel, shape, trunc)
 
 
 # ------------------------------------------------------------------------------------------- colours
@@ -459,47 +410,38 @@ def check_color_scalars(tol, min_cos, fill):
         raise ValueError("fill must be an integer 0 .. 255")
 
 
-def check_color_images(images, shapes):
-    """(the views' pixels back to back as uint8 [n_out * channels + 1], channels) from one uint8 [h,w] or [h,w,3] array per
-    VIEW, shaped like shapes; ValueError says what is wrong."""
-    arrays = [np.asarray(a) for a in images]
-    if len(arrays) != len(shapes):
-        raise ValueError("images: one array per view")
-    tails = {a.shape[2:] for a in arrays if a.ndim in (2, 3)}
-    if any(a.ndim not in (2, 3) for a in arrays) or len(tails) > 1 or (tails and next(iter(tails)) not in ((), (3,))):
-        raise ValueError("images must all be [h,w] or all be [h,w,3]")
-    if any(a.dtype != np.uint8 for a in arrays):
-        raise ValueError("images must be uint8")
-    for v, (a, sh) in enumerate(zip(arrays, shapes)):
-        if a.shape[:2] != tuple(sh):
-            raise ValueError(f"view {v}: the image must have the shape of its maps, {tuple(sh)}")
-    channels = 3 if tails and next(iter(tails)) == (3,) else 1
-    flat = np.concatenate([a.reshape(-1) for a in arrays] + [np.zeros(1, np.uint8)])          # one element more: a pointer must exist
-    return np.ascontiguousarray(flat), channels
+def check_mesh_arrays(vertices, normals, triangles=None):
+    """(vertices float64 [nv,3], normals float32 [nv,3], triangles int32 [nt,3] or None) of a mesh made elsewhere, or ValueError."""
+    vertices = np.ascontiguousarray(vertices, dtype=np.float64)
+    normals = np.ascontiguousarray(normals, dtype=np.float32)
+    if vertices.ndim != 2 or vertices.shape[1] != 3 or normals.shape != vertices.shape:
+        raise ValueError("vertices and normals must be [nv,3]")
+    if triangles is None:
+        return vertices, normals, None
+    tri = np.asarray(triangles)
+    if tri.ndim != 2 or tri.shape[1] != 3 or tri.dtype.kind not in "iu" or (tri.size and (tri.min() < -0x80000000 or tri.max() > 0x7FFFFFFF)):
+        raise ValueError("triangles must be [nt,3] integers that fit int32")
+    return vertices, normals, np.ascontiguousarray(tri, dtype=np.int32)
 
 
-def _colors(dev, heights, widths, ref_image, proj, centres, d_depth, d_keep, d_pixels, channels, n_vertices, d_vertices, d_normals,
-            tol, min_cos, fill):
-    """The device call: heights / widths (int32 per image), ref_image (int32 per view), proj [n_ref,12] and centres [n_ref,3]
-    on the host; the maps, the pixels, the vertices and the normals on the device (d_keep may be None)."""
+def upload_rows(a, dev):
+    """[n,3] on the device with one row more: a pointer must exist."""
     import torch
+    return torch.from_numpy(np.concatenate([a, np.zeros((1, 3), a.dtype)])).to(dev)
+
+
+def _colors(views, n_vertices, d_vertices, d_normals, tol, min_cos, fill):
+    """The device call: a `ViewSet` with its pixels; the vertices and the normals on the device."""
+    import torch
+    dev = views.depth.device
     h = _lib.get_handle(dev.index)
-    n_ref, n_img = len(ref_image), len(heights)
-    table = lambda a, k: (torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, k)).to(dev) if n_ref
-                          else torch.zeros((1, k), dtype=torch.float64, device=dev))
-    d_proj, d_centres = table(proj, 12), table(centres, 3)
-    need = C.c_int64()
-    h.check(h.lib.sfm_mesh_colors_workspace_bytes(n_ref, C.byref(need)), "sfm_mesh_colors_workspace_bytes")
-    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    ws, ws_bytes = workspace(h, dev, "sfm_mesh_colors_workspace_bytes", views.n_ref)
     n = max(int(n_vertices), 1)
-    out = {"vertex_colors": torch.empty(n if channels == 1 else (n, 3), dtype=torch.uint8, device=dev),
+    out = {"vertex_colors": torch.empty(n if views.channels == 1 else (n, 3), dtype=torch.uint8, device=dev),
            "n_views": torch.empty(n, dtype=torch.uint8, device=dev), "best_view": torch.empty(n, dtype=torch.int32, device=dev)}
-    dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    hp = lambda a: C.c_void_p(a.ctypes.data)
-    h.call("sfm_mesh_colors", hp(heights), hp(widths), n_img, n_ref, hp(ref_image), dp(d_proj), dp(d_centres), dp(d_depth), dp(d_keep),
-           dp(d_pixels), int(channels), int(n_vertices), dp(d_vertices), dp(d_normals), C.c_double(float(tol)), C.c_double(float(min_cos)),
-           int(fill), dp(out["vertex_colors"]), dp(out["n_views"]), dp(out["best_view"]), dp(ws), need.value)
-    out["colors_ws"] = (ws, d_proj, d_centres, d_depth, d_keep, d_pixels)      # alive while the call may still run
+    h.call("sfm_mesh_colors", *views.args(), int(n_vertices), dp(d_vertices), dp(d_normals), C.c_double(float(tol)), C.c_double(float(min_cos)),
+           int(fill), dp(out["vertex_colors"]), dp(out["n_views"]), dp(out["best_view"]), dp(ws), ws_bytes)
+    out["colors_ws"] = (ws,) + views.alive()                       # alive while the call may still run
     return out
 
 
@@ -508,31 +450,11 @@ def mesh_vertex_colors(vertices, normals, proj, centres, depth, keep, images, to
     [n,12] (row-major [K R | K t]), centres float64 [n,3], depth one float32 [h,w] per view, keep one uint8 [h,w] per view or
     None (every finite depth counts), images one uint8 [h,w] or [h,w,3] per VIEW.  Returns (colors uint8 [nv] or [nv,3],
     n_views uint8 [nv], best_view int32 [nv])."""
-    import torch
     check_color_scalars(tol, min_cos, fill)
-    vertices = np.ascontiguousarray(vertices, dtype=np.float64)
-    normals = np.ascontiguousarray(normals, dtype=np.float32)
-    if vertices.ndim != 2 or vertices.shape[1] != 3 or normals.shape != vertices.shape:
-        raise ValueError("vertices and normals must be [nv,3]")
-    depth = [np.ascontiguousarray(d, dtype=np.float32) for d in depth]
-    if any(d.ndim != 2 for d in depth) or np.shape(proj) != (len(depth), 12) or np.shape(centres) != (len(depth), 3) or len(depth) > MAX_VIEWS:
-        raise ValueError(f"depth: at most {MAX_VIEWS} [h,w] maps; proj: 12 numbers and centres: 3 numbers for each")
-    if keep is not None and [np.shape(k) for k in keep] != [d.shape for d in depth]:
-        raise ValueError("keep must be None or one [h,w] array per view, shaped like its depth map")
-    flat, channels = check_color_images(images, [d.shape for d in depth])
-    _lib.get_handle(device)
-    dev = torch.device("cuda", device)
-
-    def up(arrays, dtype):
-        return torch.from_numpy(np.concatenate([np.asarray(a, dtype=dtype).reshape(-1) for a in arrays] + [np.zeros(1, dtype)])).to(dev)
-
-    pad = lambda a: np.concatenate([a, np.zeros((1, 3), a.dtype)])           # one row more: a pointer must exist
-    heights = np.array([d.shape[0] for d in depth], dtype=np.int32)
-    widths = np.array([d.shape[1] for d in depth], dtype=np.int32)
-    nv = len(vertices)
-    out = _colors(dev, heights, widths, np.arange(len(depth), dtype=np.int32), proj, centres, up(depth, np.float32),
-                  None if keep is None else up(keep, np.uint8), torch.from_numpy(flat).to(dev), channels, nv,
-                  torch.from_numpy(pad(vertices)).to(dev), torch.from_numpy(pad(normals)).to(dev), tol, min_cos, fill)
+    vertices, normals, _ = check_mesh_arrays(vertices, normals)
+    views = ViewSet.from_arrays(proj, centres, depth, keep, MAX_VIEWS, images).to(device)
+    dev, nv = views.depth.device, len(vertices)
+    out = _colors(views, nv, upload_rows(vertices, dev), upload_rows(normals, dev), tol, min_cos, fill)
     return tuple(out[name].cpu().numpy()[:nv] for name in ("vertex_colors", "n_views", "best_view"))
 
 
@@ -560,32 +482,23 @@ def check_texture_layout(n_triangles, texels, cells_per_row):
     return int(cells_per_row), W, H
 
 
-def _texture(dev, heights, widths, ref_image, proj, centres, d_depth, d_keep, d_pixels, channels, n_vertices, d_vertices, d_normals,
-             n_triangles, d_triangles, texels, cells_per_row, tol, min_cos, fill):
-    """The device call: the views as `_colors` takes them; the vertices, the normals and the triangles on the device."""
+def _texture(views, n_vertices, d_vertices, d_normals, n_triangles, d_triangles, texels, cells_per_row, tol, min_cos, fill):
+    """The device call: a `ViewSet` with its pixels; the vertices, the normals and the triangles on the device."""
     import torch
+    dev, channels = views.depth.device, views.channels
     h = _lib.get_handle(dev.index)
-    n_ref, n_img = len(ref_image), len(heights)
-    table = lambda a, k: (torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64).reshape(-1, k)).to(dev) if n_ref
-                          else torch.zeros((1, k), dtype=torch.float64, device=dev))
-    d_proj, d_centres = table(proj, 12), table(centres, 3)
     W, H = C.c_int32(), C.c_int32()
     if h.lib.sfm_mesh_texture_size(int(n_triangles), int(texels), int(cells_per_row), C.byref(W), C.byref(H)) != 0:
         raise ValueError("sfm_mesh_texture_size refuses this layout")
     W, H = W.value, H.value
-    need = C.c_int64()
-    h.check(h.lib.sfm_mesh_texture_workspace_bytes(n_ref, C.byref(need)), "sfm_mesh_texture_workspace_bytes")
-    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    ws, ws_bytes = workspace(h, dev, "sfm_mesh_texture_workspace_bytes", views.n_ref)
     out = {"image": torch.empty(max(H * W * channels, 1), dtype=torch.uint8, device=dev),
            "views": torch.empty(max(H * W, 1), dtype=torch.uint8, device=dev),
            "uv": torch.empty(max(int(n_triangles) * 6, 1), dtype=torch.float32, device=dev)}
-    dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    hp = lambda a: C.c_void_p(a.ctypes.data)
-    h.call("sfm_mesh_texture", hp(heights), hp(widths), n_img, n_ref, hp(ref_image), dp(d_proj), dp(d_centres), dp(d_depth), dp(d_keep),
-           dp(d_pixels), int(channels), int(n_vertices), dp(d_vertices), dp(d_normals), int(n_triangles), dp(d_triangles), int(texels),
+    h.call("sfm_mesh_texture", *views.args(), int(n_vertices), dp(d_vertices), dp(d_normals), int(n_triangles), dp(d_triangles), int(texels),
            int(cells_per_row), C.c_double(float(tol)), C.c_double(float(min_cos)), int(fill), dp(out["image"]), dp(out["views"]), dp(out["uv"]),
-           dp(ws), need.value)
-    out["ws"] = (ws, d_proj, d_centres, d_depth, d_keep, d_pixels, d_vertices, d_normals, d_triangles)      # alive while the call may still run
+           dp(ws), ws_bytes)
+    out["ws"] = (ws, d_vertices, d_normals, d_triangles) + views.alive()       # alive while the call may still run
     return MeshTexture(out, (W, H), texels, cells_per_row, channels, n_triangles)
 
 
@@ -594,36 +507,13 @@ def mesh_texture(vertices, normals, triangles, proj, centres, depth, keep, image
     """`sfm_mesh_texture` on arrays that were made elsewhere: vertices float64 [nv,3], normals float32 [nv,3], triangles int32
     [nt,3] (a triangle with an index outside 0 .. nv - 1 is seen by no view), the views as `mesh_vertex_colors` takes them,
     images one uint8 [h,w] or [h,w,3] per VIEW.  Returns a `MeshTexture`."""
-    import torch
     check_color_scalars(tol, min_cos, fill)
-    vertices = np.ascontiguousarray(vertices, dtype=np.float64)
-    normals = np.ascontiguousarray(normals, dtype=np.float32)
-    if vertices.ndim != 2 or vertices.shape[1] != 3 or normals.shape != vertices.shape:
-        raise ValueError("vertices and normals must be [nv,3]")
-    tri = np.asarray(triangles)
-    if tri.ndim != 2 or tri.shape[1] != 3 or tri.dtype.kind not in "iu" or (tri.size and (tri.min() < -0x80000000 or tri.max() > 0x7FFFFFFF)):
-        raise ValueError("triangles must be [nt,3] integers that fit int32")
-    tri = np.ascontiguousarray(tri, dtype=np.int32)
+    vertices, normals, tri = check_mesh_arrays(vertices, normals, triangles)
     cells_per_row = check_texture_layout(len(tri), texels, cells_per_row)[0]
-    depth = [np.ascontiguousarray(d, dtype=np.float32) for d in depth]
-    if any(d.ndim != 2 for d in depth) or np.shape(proj) != (len(depth), 12) or np.shape(centres) != (len(depth), 3) or len(depth) > MAX_VIEWS:
-        raise ValueError(f"depth: at most {MAX_VIEWS} [h,w] maps; proj: 12 numbers and centres: 3 numbers for each")
-    if keep is not None and [np.shape(k) for k in keep] != [d.shape for d in depth]:
-        raise ValueError("keep must be None or one [h,w] array per view, shaped like its depth map")
-    flat, channels = check_color_images(images, [d.shape for d in depth])
-    _lib.get_handle(device)
-    dev = torch.device("cuda", device)
-
-    def up(arrays, dtype):
-        return torch.from_numpy(np.concatenate([np.asarray(a, dtype=dtype).reshape(-1) for a in arrays] + [np.zeros(1, dtype)])).to(dev)
-
-    pad = lambda a: np.concatenate([a, np.zeros((1, 3), a.dtype)])           # one row more: a pointer must exist
-    heights = np.array([d.shape[0] for d in depth], dtype=np.int32)
-    widths = np.array([d.shape[1] for d in depth], dtype=np.int32)
-    return _texture(dev, heights, widths, np.arange(len(depth), dtype=np.int32), proj, centres, up(depth, np.float32),
-                    None if keep is None else up(keep, np.uint8), torch.from_numpy(flat).to(dev), channels, len(vertices),
-                    torch.from_numpy(pad(vertices)).to(dev), torch.from_numpy(pad(normals)).to(dev), len(tri), torch.from_numpy(pad(tri)).to(dev),
-                    texels, cells_per_row, tol, min_cos, fill)
+    views = ViewSet.from_arrays(proj, centres, depth, keep, MAX_VIEWS, images).to(device)
+    dev = views.depth.device
+    return _texture(views, len(vertices), upload_rows(vertices, dev), upload_rows(normals, dev), len(tri), upload_rows(tri, dev), texels,
+                    cells_per_row, tol, min_cos, fill)
 
 
 # ------------------------------------------------------------------------------------------- render
@@ -820,21 +710,17 @@ def _render(dev, proj, heights, widths, n_vertices, d_vertices, n_triangles, d_t
     n_cam = len(heights)
     heights, widths = np.ascontiguousarray(heights, dtype=np.int32), np.ascontiguousarray(widths, dtype=np.int32)
     d_proj = torch.from_numpy(np.ascontiguousarray(proj, dtype=np.float64).reshape(-1, 12)).to(dev) if n_cam else torch.zeros((1, 12), dtype=torch.float64, device=dev)
-    hp = lambda a: C.c_void_p(a.ctypes.data) if len(a) else None
-    need = C.c_int64()
-    h.check(h.lib.sfm_mesh_render_workspace_bytes(n_cam, hp(heights), hp(widths), int(n_vertices), int(n_triangles), C.byref(need)),
-            "sfm_mesh_render_workspace_bytes")
-    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    hp_some = lambda a: hp(a) if len(a) else None
+    ws, ws_bytes = workspace(h, dev, "sfm_mesh_render_workspace_bytes", n_cam, hp_some(heights), hp_some(widths), int(n_vertices), int(n_triangles))
     n_pix = int((heights.astype(np.int64) * widths.astype(np.int64)).sum())
     n = max(n_pix, 1)
     out = {"depth": torch.empty(n, dtype=torch.float32, device=dev), "triangle": torch.empty(n, dtype=torch.int32, device=dev),
            "bary": torch.empty(n * 3, dtype=torch.float32, device=dev)}
     if mode != RENDER_NONE:
         out["color"] = torch.empty(n * channels, dtype=torch.uint8, device=dev)
-    dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    h.call("sfm_mesh_render", n_cam, hp(heights), hp(widths), dp(d_proj), int(n_vertices), dp(d_vertices), int(n_triangles), dp(d_triangles),
+    h.call("sfm_mesh_render", n_cam, hp_some(heights), hp_some(widths), dp(d_proj), int(n_vertices), dp(d_vertices), int(n_triangles), dp(d_triangles),
            int(mode), int(channels), dp(d_vertex_colors), dp(d_uv), dp(d_atlas), int(atlas_size[0]), int(atlas_size[1]), int(fill),
-           dp(out["depth"]), dp(out["triangle"]), dp(out["bary"]), dp(out.get("color")), dp(ws), need.value)
+           dp(out["depth"]), dp(out["triangle"]), dp(out["bary"]), dp(out.get("color")), dp(ws), ws_bytes)
     out["ws"] = ws
     out["held"] = (d_proj, d_vertices, d_triangles, d_vertex_colors, d_uv, d_atlas)         # alive while the call may still run
     return MeshRender(out, heights, widths, channels, mode != RENDER_NONE)
@@ -1015,19 +901,16 @@ def _score(dev, heights, widths, channels, d_color, d_triangle, d_depth, d_photo
     h = _lib.get_handle(dev.index)
     n_view = len(heights)
     heights, widths = np.ascontiguousarray(heights, dtype=np.int32), np.ascontiguousarray(widths, dtype=np.int32)
-    hp = lambda a: C.c_void_p(a.ctypes.data) if len(a) else None
-    dp = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    need = C.c_int64()
-    h.check(h.lib.sfm_render_score_workspace_bytes(n_view, hp(heights), hp(widths), C.byref(need)), "sfm_render_score_workspace_bytes")
-    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    hp_some = lambda a: hp(a) if len(a) else None
+    ws, ws_bytes = workspace(h, dev, "sfm_render_score_workspace_bytes", n_view, hp_some(heights), hp_some(widths))
     n = max(int((heights.astype(np.int64) * widths.astype(np.int64)).sum()), 1)
     out = {"stats": torch.empty(max(n_view, 1) * SCORE_COLUMNS, dtype=torch.int64, device=dev)}
     if keep_maps:
         out["abs_error"] = torch.empty(n * channels, dtype=torch.uint8, device=dev)
         out["ssim_map"] = torch.empty(n, dtype=torch.float32, device=dev)
-    h.call("sfm_render_score", n_view, hp(heights), hp(widths), int(channels), dp(d_color), dp(d_triangle), dp(d_depth), dp(d_photos), dp(d_masks),
+    h.call("sfm_render_score", n_view, hp_some(heights), hp_some(widths), int(channels), dp(d_color), dp(d_triangle), dp(d_depth), dp(d_photos), dp(d_masks),
            dp(d_view_depth), dp(d_view_keep), int(window), C.c_double(float(rel_tol)), dp(out["stats"]), dp(out.get("abs_error")),
-           dp(out.get("ssim_map")), dp(ws), need.value)
+           dp(out.get("ssim_map")), dp(ws), ws_bytes)
     out["held"] = (ws, d_color, d_triangle, d_depth, d_photos, d_masks, d_view_depth, d_view_keep)        # alive while the call may still run
     return RenderScore(out, heights, widths, channels, window, rel_tol, keep_maps)
 

@@ -243,6 +243,24 @@ static int check_plan(uint64_t seed) {
   REQUIRE(tsdf_check_views(3, hs, ws, -1, refs, nullptr) == 9 && tsdf_check_views(-1, hs, ws, 0, refs, nullptr) == 10);
   REQUIRE(tsdf_check_views(70000, hs, ws, TSDF_MAX_VIEWS + 1, refs, nullptr) == 6 && tsdf_check_views(3, nullptr, ws, 1, refs, nullptr) == 2);
   REQUIRE(tsdf_workspace_bytes(3) >= 4 * (int64_t)sizeof(TsdfView));
+  // the table the four per-view calls put into the workspace: the records of the check, n_out and the closing record
+  ViewTable table;
+  REQUIRE(view_table_build(3, hs, ws, 3, refs, &table) == 0 && table.views.size() == 4 && table.n_out == 39);
+  for (int r = 0; r < 3; ++r) REQUIRE(table.views[r].out_off == views[r].out_off && table.views[r].h == views[r].h && table.views[r].w == views[r].w);
+  REQUIRE(table.views[3].out_off == 39 && table.views[3].h == 0 && table.views[3].w == 0);
+  REQUIRE(view_table_build(3, hs, ws, 1, refs, &table) == 0 && table.views.size() == 2 && table.n_out == 0 && table.views[1].out_off == 0);
+  REQUIRE(view_table_build(0, nullptr, nullptr, 0, nullptr, &table) == 0 && table.views.size() == 1 && table.n_out == 0);
+  // an n_ref out of range sizes nothing by itself, and the index is the check's own
+  REQUIRE(view_table_build(3, hs, ws, -1, refs, &table) == 9 && table.views.size() == 1);
+  REQUIRE(view_table_build(0x7FFFFFFFLL, hs, ws, 0x7FFFFFFFLL, refs, &table) == 6 && table.views.size() == 1);
+  REQUIRE(view_table_build(3, hs, ws, 4, refs, &table) == 9 && view_table_build(3, hs, ws, 2, twice, &table) == 9);
+  REQUIRE(view_table_build(3, neg, ws, 1, refs, &table) == 7 && view_table_build(3, hs, ws, 1, far, &table) == 8);
+  REQUIRE(view_table_build(-1, hs, ws, 0, refs, &table) == 10 && view_table_build(3, nullptr, ws, 1, refs, &table) == 2);
+  const int x = 0;
+  REQUIRE(view_pointers_ok(0, 0, nullptr, nullptr, nullptr, nullptr) && view_pointers_ok(2, 5, &x, &x, &x, &x));
+  REQUIRE(view_pointers_ok(2, 0, &x, &x, nullptr, nullptr) && view_pointers_ok(0, 5, nullptr, nullptr, &x, &x));
+  REQUIRE(!view_pointers_ok(2, 0, nullptr, &x, &x, &x) && !view_pointers_ok(2, 0, &x, nullptr, &x, &x));
+  REQUIRE(!view_pointers_ok(0, 5, &x, &x, nullptr, &x) && !view_pointers_ok(0, 5, &x, &x, &x, nullptr));
   for (int k = 1; k <= 11; ++k) REQUIRE(std::strlen(MESH_WHY[k]) > 0);
   std::printf("ok %d\n", cases);
   return 0;

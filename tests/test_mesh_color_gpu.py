@@ -8,6 +8,7 @@ import pytest
 
 import depth_reference as dr
 import mesh_color_reference as cr
+import view_calls as vc
 from test_mesh_color_reference import SEEN_SHARE, read_ply_coloured_mesh
 
 pytestmark = pytest.mark.gpu
@@ -122,11 +123,9 @@ def test_entry_point_rejects_bad_arguments(gpu_ready):
     from sfm_amd import _lib
     h = _lib.get_handle(0)
     lib = h.lib
-    hp = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
-    i32 = lambda *v: np.array(v, dtype=np.int32)
-    one = C.c_void_p(1)                                            # stands for a pointer that is there; never followed
-    good = dict(hs=i32(3, 4), ws=i32(4, 7), n_img=2, n_ref=2, refs=i32(1, 0), ch=3, nv=10, tol=0.1, min_cos=0.35, fill=0, ws_bytes=1 << 20,
-                workspace=one, proj=one, centres=one, depth=one, keep=None, pixels=one, V=one, N=one, colors=one, n_views=one, best=one)
+    hp, one = vc.hp, vc.ONE
+    good = dict(vc.GOOD, ch=3, nv=10, tol=0.1, min_cos=0.35, fill=0, ws_bytes=1 << 20, workspace=one, V=one, N=one, colors=one, n_views=one,
+                best=one)
     nan, inf = float("nan"), float("inf")
 
     def call(a):
@@ -135,21 +134,18 @@ def test_entry_point_rejects_bad_arguments(gpu_ready):
                                    a["n_views"], a["best"], a["workspace"], a["ws_bytes"])
 
     why = lambda: lib.sfm_last_error(h._h)
-    bad_views = [dict(hs=i32(3, -1)), dict(refs=i32(0, 2)), dict(refs=i32(-1, 0)), dict(refs=i32(1, 1)), dict(n_ref=3), dict(n_ref=-1),
-                 dict(n_ref=65536, n_img=65536), dict(n_img=-1), dict(hs=None), dict(refs=None)]
     bad_scalars = [dict(ch=0), dict(ch=2), dict(ch=4), dict(nv=-1), dict(nv=1 << 31), dict(tol=-0.1), dict(tol=nan), dict(tol=inf),
                    dict(min_cos=0.0), dict(min_cos=-0.2), dict(min_cos=1.01), dict(min_cos=nan), dict(min_cos=inf), dict(fill=-1), dict(fill=256)]
-    for kw in bad_views + bad_scalars + [dict(ws_bytes=8), dict(workspace=None)]:
+    for kw in vc.BAD_VIEWS + bad_scalars + [dict(ws_bytes=8), dict(workspace=None)]:
         assert call(dict(good, **kw)) == -1, kw
-        assert not why().endswith(b": null pointer") or kw in (dict(hs=None), dict(refs=None)), (kw, why())
-    for name in ("proj", "centres", "depth", "pixels", "V", "N", "colors", "n_views", "best"):
+        assert not why().endswith(b": null pointer") or kw in vc.NULL_ARRAYS, (kw, why())
+    for name in vc.VIEW_POINTERS + ("V", "N", "colors", "n_views", "best"):
         assert call(dict(good, **{name: None})) == -1 and why().endswith(b": null pointer"), name
     assert lib.sfm_mesh_colors(None, *[None] * 2, 0, 0, *[None] * 6, 3, 0, None, None, 0.1, 0.35, 0, None, None, None, None, 0) == -1
     # nothing to do: returns at once, with every pointer that has nothing behind it null
     none = dict(V=None, N=None, colors=None, n_views=None, best=None)
     assert call(dict(good, nv=0, **none)) == 0
-    assert call(dict(good, nv=0, n_ref=0, n_img=0, hs=None, ws=None, refs=None, proj=None, centres=None, depth=None, pixels=None, **none)) == 0
-    assert call(dict(good, nv=0, hs=i32(0, 4), ws=i32(4, 0), depth=None, pixels=None, **none)) == 0          # views without a pixel
+    assert call(dict(good, nv=0, **vc.NO_VIEW, **none)) == 0 and call(dict(good, nv=0, **vc.NO_PIXEL, **none)) == 0
     need = C.c_int64()
     assert lib.sfm_mesh_colors_workspace_bytes(2, C.byref(need)) == 0 and 3 * 16 <= need.value < (1 << 20)
     assert lib.sfm_mesh_colors_workspace_bytes(65536, C.byref(need)) == -1 and lib.sfm_mesh_colors_workspace_bytes(-1, C.byref(need)) == -1

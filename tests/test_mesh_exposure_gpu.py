@@ -9,6 +9,7 @@ import pytest
 
 import mesh_color_reference as cr
 import mesh_exposure_reference as er
+import view_calls as vc
 from test_mesh_exposure_reference import MEASURED, assert_same, assert_worth, scene_args
 
 pytestmark = pytest.mark.gpu
@@ -173,11 +174,8 @@ def test_sample_and_gram_reject_bad_arguments(gpu_ready):
     from sfm_amd import _lib
     h = _lib.get_handle(0)
     lib = h.lib
-    hp = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
-    i32 = lambda *v: np.array(v, dtype=np.int32)
-    one = C.c_void_p(1)
-    good = dict(hs=i32(3, 4), ws=i32(4, 7), n_img=2, n_ref=2, refs=i32(1, 0), ch=3, nv=10, tol=0.1, min_cos=0.35, ws_bytes=1 << 20, workspace=one,
-                proj=one, centres=one, depth=one, keep=None, pixels=one, V=one, N=one, seen=one, samples=one)
+    hp, one = vc.hp, vc.ONE
+    good = dict(vc.GOOD, ch=3, nv=10, tol=0.1, min_cos=0.35, ws_bytes=1 << 20, workspace=one, V=one, N=one, seen=one, samples=one)
     nan, inf = float("nan"), float("inf")
 
     def call(a):
@@ -185,15 +183,14 @@ def test_sample_and_gram_reject_bad_arguments(gpu_ready):
                                             a["keep"], a["pixels"], a["ch"], a["nv"], a["V"], a["N"], a["tol"], a["min_cos"], a["seen"], a["samples"],
                                             a["workspace"], a["ws_bytes"])
 
-    for kw in [dict(hs=i32(3, -1)), dict(refs=i32(0, 2)), dict(refs=i32(1, 1)), dict(n_ref=3), dict(n_ref=-1), dict(n_img=-1), dict(hs=None), dict(refs=None),
-               dict(n_ref=1025, n_img=1025), dict(ch=0), dict(ch=2), dict(nv=-1), dict(nv=1 << 31), dict(tol=-0.1), dict(tol=nan), dict(tol=inf),
+    for kw in vc.BAD_VIEWS + [dict(n_ref=1025, n_img=1025), dict(ch=0), dict(ch=2), dict(nv=-1), dict(nv=1 << 31), dict(tol=-0.1), dict(tol=nan), dict(tol=inf),
                dict(min_cos=0.0), dict(min_cos=1.01), dict(min_cos=nan), dict(ws_bytes=8), dict(workspace=None)]:
         assert call(dict(good, **kw)) == -1, kw
-    for name in ("proj", "centres", "depth", "pixels", "V", "N", "seen", "samples"):
+    for name in vc.VIEW_POINTERS + ("V", "N", "seen", "samples"):
         assert call(dict(good, **{name: None})) == -1 and lib.sfm_last_error(h._h).endswith(b": null pointer"), name
     none = dict(V=None, N=None, seen=None, samples=None)
     assert call(dict(good, nv=0, **none)) == 0
-    assert call(dict(good, nv=0, n_ref=0, n_img=0, hs=None, ws=None, refs=None, proj=None, centres=None, depth=None, pixels=None, **none)) == 0
+    assert call(dict(good, nv=0, **vc.NO_VIEW, **none)) == 0 and call(dict(good, nv=0, **vc.NO_PIXEL, **none)) == 0
     gram = lambda n_ref=2, ch=3, nv=10, seen=one, q=one, o=one, s=one, ws=one, b=1 << 20: lib.sfm_mesh_exposure_gram(h._h, n_ref, ch, nv, seen, q, o, s, ws, b)
     for kw in (dict(n_ref=-1), dict(n_ref=1025), dict(ch=2), dict(nv=-1), dict(nv=1 << 31), dict(seen=None), dict(q=None), dict(o=None), dict(s=None),
                dict(ws=None), dict(b=8)):

@@ -282,7 +282,9 @@ def test_argument_checks_without_gpu():
     with pytest.raises(ValueError, match="filter"):
         mesh.exposure([gray, gray], maps)
     maps.keep = [np.ones((2, 3), np.uint8)]
-    vol._maps = maps
+    from sfm_amd._views import ViewSet                            # what DepthMaps.tsdf() leaves in the volume, nothing on a device
+    vol.views = ViewSet(np.array([2, 2], np.int32), np.array([3, 3], np.int32), np.array([1], np.int32), np.zeros((1, 12)), np.zeros((1, 3)),
+                        None, None, maps)
     for images, kw in (([gray], {}), ([gray, gray, gray], {}), ([gray, np.zeros((3, 2), np.uint8)], {}), ([gray, gray.astype(np.float32)], {}),
                        ([gray, gray], dict(tol=-1.0)), ([gray, gray], dict(min_cos=0.0)), ([gray, gray], dict(sigma_n=0.0)),
                        ([gray, gray], dict(sigma_g=nan)), ([gray, gray], dict(min_overlap=0))):

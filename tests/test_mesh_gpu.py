@@ -207,16 +207,13 @@ def test_entry_points_reject_bad_arguments(gpu_ready):
     from sfm_amd import _lib
     h = _lib.get_handle(0)
     lib = h.lib
-    hp = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
-    i32, f64 = (lambda *v: np.array(v, dtype=np.int32)), (lambda *v: np.array(v, dtype=np.float64))
-    good = dict(hs=i32(3, 4), ws=i32(4, 7), n_img=2, n_ref=2, refs=i32(1, 0), o=f64(0, 0, 0), s=0.5, nx=4, ny=5, nz=6, trunc=1.0,
-                mw=1, nv=10, nt=10, ws_bytes=1 << 20)
+    import view_calls as vc
+    hp, f64 = vc.hp, (lambda *v: np.array(v, dtype=np.float64))
+    good = dict(vc.GOOD, o=f64(0, 0, 0), s=0.5, nx=4, ny=5, nz=6, trunc=1.0, mw=1, nv=10, nt=10, ws_bytes=1 << 20)
     nan, inf = float("nan"), float("inf")
     bad_grid = [dict(nx=1), dict(ny=1025), dict(nz=0), dict(nx=-4)]
     bad_frame = [dict(o=f64(0, nan, 0)), dict(o=f64(inf, 0, 0)), dict(s=0.0), dict(s=-1.0), dict(s=nan), dict(s=inf), dict(o=None)]
-    bad_views = [dict(hs=i32(3, -1)), dict(refs=i32(0, 2)), dict(refs=i32(-1, 0)), dict(refs=i32(1, 1)), dict(n_ref=3), dict(n_ref=-1),
-                 dict(n_ref=65536, n_img=65536), dict(trunc=0.0), dict(trunc=-1.0), dict(trunc=nan)]
-
+    bad_views = vc.BAD_SIZES + [dict(trunc=0.0), dict(trunc=-1.0), dict(trunc=nan)]
     def integrate(a):
         return lib.sfm_tsdf_integrate(h._h, hp(a["hs"]), hp(a["ws"]), a["n_img"], a["n_ref"], hp(a["refs"]), None, None, None, hp(a["o"]),
                                       a["s"], a["nx"], a["ny"], a["nz"], a["trunc"], None, None, C.c_void_p(1), a["ws_bytes"])

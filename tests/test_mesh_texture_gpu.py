@@ -10,6 +10,8 @@ import pytest
 import depth_reference as dr
 import mesh_color_reference as cr
 import mesh_texture_reference as tr
+import view_calls as vc
+from test_mesh_color_gpu import default_scene_maps
 from test_mesh_texture_reference import assert_obj_files
 
 pytestmark = pytest.mark.gpu
@@ -157,17 +159,6 @@ def test_textured_sphere_from_the_device_mesh(gpu_ready):
     assert mesh.n_triangles > 10000 and t.views[tri >= 0].min() >= 1 and (t.views[tri < 0] == 0).all()
 
 
-def default_scene_maps():
-    from sfm_amd import depth as dm
-    from sfm_amd import depth_maps
-    s = dr.default_scene()
-    refs, sources = [0, 1, 2], [[1, 2], [0, 2], [0, 1]]
-    warps = [dm.view_warps(s.K, s.poses, r, src) for r, src in zip(refs, sources)]
-    planes = {r: dm.plane_depths(s.d_min, s.d_max, warps[r], s.size) for r in refs}
-    maps = depth_maps(s.images, s.K, s.poses, {r: src for r, src in zip(refs, sources)}, planes, radius=2)
-    return s, maps.filter(rel_tol=0.02, max_cost=12.0, min_consistent=1)
-
-
 def test_default_scene_from_depth_maps_to_obj_files(gpu_ready, tmp_path):
     """depth_maps -> filter -> tsdf -> mesh -> texture -> save_obj on the default scene (96 x 72, 3 cameras), gray and BGR:
     the restatement's bytes on the device's own maps and mesh, and the three files read back."""
@@ -238,12 +229,9 @@ def test_entry_point_rejects_bad_arguments(gpu_ready):
     from sfm_amd import _lib
     h = _lib.get_handle(0)
     lib = h.lib
-    hp = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
-    i32 = lambda *v: np.array(v, dtype=np.int32)
-    one = C.c_void_p(1)                                            # stands for a pointer that is there; never followed
-    good = dict(hs=i32(3, 4), ws=i32(4, 7), n_img=2, n_ref=2, refs=i32(1, 0), ch=3, nv=10, nt=6, s=8, cpr=2, tol=0.1, min_cos=0.35, fill=0,
-                ws_bytes=1 << 20, workspace=one, proj=one, centres=one, depth=one, keep=None, pixels=one, V=one, N=one, T=one, image=one, views=one,
-                uv=one)
+    hp, one = vc.hp, vc.ONE
+    good = dict(vc.GOOD, ch=3, nv=10, nt=6, s=8, cpr=2, tol=0.1, min_cos=0.35, fill=0, ws_bytes=1 << 20, workspace=one, V=one, N=one, T=one,
+                image=one, views=one, uv=one)
     nan, inf = float("nan"), float("inf")
 
     def call(a):
@@ -252,24 +240,21 @@ def test_entry_point_rejects_bad_arguments(gpu_ready):
                                     a["min_cos"], a["fill"], a["image"], a["views"], a["uv"], a["workspace"], a["ws_bytes"])
 
     why = lambda: lib.sfm_last_error(h._h)
-    bad_views = [dict(hs=i32(3, -1)), dict(refs=i32(0, 2)), dict(refs=i32(-1, 0)), dict(refs=i32(1, 1)), dict(n_ref=3), dict(n_ref=-1),
-                 dict(n_ref=65536, n_img=65536), dict(n_img=-1), dict(hs=None), dict(refs=None)]
     bad_scalars = [dict(ch=0), dict(ch=2), dict(ch=4), dict(nv=-1), dict(nv=1 << 31), dict(tol=-0.1), dict(tol=nan), dict(tol=inf),
                    dict(min_cos=0.0), dict(min_cos=1.01), dict(min_cos=nan), dict(fill=-1), dict(fill=256)]
     bad_layout = [dict(s=0), dict(s=65), dict(s=-1), dict(cpr=0), dict(cpr=-1), dict(s=64, cpr=490), dict(s=64, cpr=489, nt=2 * 489 * 489 + 1),
                   dict(nt=-1), dict(nt=1 << 31, cpr=32768, s=1)]
-    for kw in bad_views + bad_scalars + bad_layout + [dict(ws_bytes=8), dict(workspace=None)]:
+    for kw in vc.BAD_VIEWS + bad_scalars + bad_layout + [dict(ws_bytes=8), dict(workspace=None)]:
         assert call(dict(good, **kw)) == -1, kw
-        assert not why().endswith(b": null pointer") or kw in (dict(hs=None), dict(refs=None)), (kw, why())
-    for name in ("proj", "centres", "depth", "pixels", "V", "N", "T", "image", "views", "uv"):
+        assert not why().endswith(b": null pointer") or kw in vc.NULL_ARRAYS, (kw, why())
+    for name in vc.VIEW_POINTERS + ("V", "N", "T", "image", "views", "uv"):
         assert call(dict(good, **{name: None})) == -1 and why().endswith(b": null pointer"), name
     assert lib.sfm_mesh_texture(None, *[None] * 2, 0, 0, *[None] * 6, 3, 0, None, None, 0, None, 8, 1, 0.1, 0.35, 0, None, None, None, None, 0) == -1
     # nothing to do: returns at once, with every pointer that has nothing behind it null
     none = dict(T=None, image=None, views=None, uv=None)
     assert call(dict(good, nt=0, **none)) == 0
     assert call(dict(good, nt=0, nv=0, V=None, N=None, **none)) == 0
-    assert call(dict(good, nt=0, n_ref=0, n_img=0, hs=None, ws=None, refs=None, proj=None, centres=None, depth=None, pixels=None, **none)) == 0
-    assert call(dict(good, nt=0, hs=i32(0, 4), ws=i32(4, 0), depth=None, pixels=None, **none)) == 0          # views without a pixel
+    assert call(dict(good, nt=0, **vc.NO_VIEW, **none)) == 0 and call(dict(good, nt=0, **vc.NO_PIXEL, **none)) == 0
     W, H = C.c_int32(), C.c_int32()
     assert lib.sfm_mesh_texture_size(6, 8, 2, C.byref(W), C.byref(H)) == 0 and (W.value, H.value) == (22, 22)
     assert lib.sfm_mesh_texture_size(6, 65, 2, C.byref(W), C.byref(H)) == -1

@@ -342,7 +342,9 @@ def test_argument_checks_without_gpu():
     with pytest.raises(ValueError, match="filter"):
         mesh.texture([gray, gray], maps=maps)
     maps.keep = [np.ones((2, 3), np.uint8)]                        # as after filter(): the checks come before the device
-    vol._maps = maps
+    from sfm_amd._views import ViewSet                            # what DepthMaps.tsdf() leaves in the volume, nothing on a device
+    vol.views = ViewSet(np.array([2, 2], np.int32), np.array([3, 3], np.int32), np.array([1], np.int32), np.zeros((1, 12)), np.zeros((1, 3)),
+                        None, None, maps)
     for images, kw in (([gray], {}), ([gray, np.zeros((3, 2), np.uint8)], {}), ([gray, gray.astype(np.float32)], {}),
                        ([gray, gray], dict(texels=0)), ([gray, gray], dict(texels=65)), ([gray, gray], dict(texels=4.0)),
                        ([gray, gray], dict(cells_per_row=0)), ([gray, gray], dict(texels=64, cells_per_row=490)),

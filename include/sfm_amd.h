@@ -74,6 +74,12 @@ int sfm_profile_read(sfm_handle h, int slot, double* total_ms_host, int64_t* cou
 /* ------------------------------------------------------------------ matcher
  * Replaces cv2.BFMatcher(norm).knnMatch(desc1, desc2, k=2) + the ratio loop
  * (find_matches.py:144-153).  Distances are float32 as OpenCV's DMatch.distance.
+ *
+ * Non-finite distances (SFM_METRIC_L2_F32 only: a float32 sum that overflows, a NaN or infinite input value; the uint8
+ * and Hamming distances are always finite).  Rows are ranked by (float32 distance, train index).  +inf is a distance
+ * like any other and ranks after every finite one, by index.  A NaN distance never enters the top-2.  A slot with no
+ * rankable row reports index -1 and distance +inf.  The ratio test then drops a query with no neighbour
+ * (inf < r * inf is false) and keeps a query with exactly one (d1 < r * inf): no match ever carries train index -1.
  */
 enum {
   SFM_METRIC_L2_U8   = 0,  /* uint8 [n,dim], dim % 32 == 0 (SIFT: 128): exact integer d^2 on i8 MFMA */

@@ -60,8 +60,26 @@ def hamming(desc1, desc2):
     return out.astype(np.float32)
 
 
+def _first_min(dist, valid):
+    """Per row the lowest index among the valid entries of least distance (+inf included), and that distance;
+    (-1, +inf) for a row without a valid entry."""
+    rows = np.arange(dist.shape[0])
+    key = np.where(valid, dist, np.float32(np.inf))
+    i = np.argmin(key, axis=1)                            # first occurrence = lowest index
+    # least key +inf: every valid entry of the row is +inf, and argmin may have stopped at an invalid one before them
+    i = np.where(np.isinf(key[rows, i]), np.where(valid.any(axis=1), np.argmax(valid, axis=1), -1), i)
+    d = np.where(i >= 0, dist[rows, np.maximum(i, 0)], np.float32(np.inf)).astype(np.float32)
+    return i, d
+
+
 def knn2(desc1, desc2, metric="l2", chunk=2048):
-    """cv2.BFMatcher(norm).knnMatch(desc1, desc2, k=2) -> idx1, idx2 [Nq] int32, d1, d2 [Nq] f32."""
+    """cv2.BFMatcher(norm).knnMatch(desc1, desc2, k=2) -> idx1, idx2 [Nq] int32, d1, d2 [Nq] f32.
+
+    Non-finite distances (float32 L2 only: a sum that overflows, a NaN or infinite value).  Rows are ranked by
+    (float32 distance, train index).  +inf is a distance like any other and ranks after every finite one, by index.
+    A NaN distance never enters the top-2.  A slot with no rankable row reports index -1 and distance +inf.  The
+    ratio test then drops a query with no neighbour (inf < r * inf is false) and keeps a query with exactly one
+    (d1 < r * inf)."""
     desc1 = np.asarray(desc1); desc2 = np.asarray(desc2)
     nq, nt = desc1.shape[0], desc2.shape[0]
     if nt < 2:
@@ -71,18 +89,18 @@ def knn2(desc1, desc2, metric="l2", chunk=2048):
     for s in range(0, nq, chunk):
         e = min(nq, s + chunk)
         if metric == "l2":
-            dist = np.sqrt(sq_l2(desc1[s:e], desc2))      # correctly rounded sqrtf
+            with np.errstate(over="ignore", invalid="ignore"):     # a sum that overflows is +inf, NaN stays NaN: see above
+                dist = np.sqrt(sq_l2(desc1[s:e], desc2))      # correctly rounded sqrtf
         elif metric == "hamming":
             dist = hamming(desc1[s:e], desc2)
         else:
             raise ValueError(metric)
-        rows = np.arange(e - s)
-        i1 = np.argmin(dist, axis=1)                      # first occurrence = lowest index
-        v1 = dist[rows, i1].copy()
-        dist[rows, i1] = np.inf
-        i2 = np.argmin(dist, axis=1)
+        valid = ~np.isnan(dist)
+        i1, v1 = _first_min(dist, valid)
+        valid[np.nonzero(i1 >= 0)[0], i1[i1 >= 0]] = False
+        i2, v2 = _first_min(dist, valid)
         idx1[s:e] = i1; idx2[s:e] = i2
-        d1[s:e] = v1; d2[s:e] = dist[rows, i2]
+        d1[s:e] = v1; d2[s:e] = v2
     return idx1, idx2, d1, d2
 
 

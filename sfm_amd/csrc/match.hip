@@ -775,7 +775,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((QB == 2 &&
 // ------------------------------------------------------------------------------------ generic VALU kernel
 // METRIC 1: float32, d^2 accumulated over k ascending with separately rounded multiply and add (the
 // oracle's stated order), distance = sqrtf(d^2).  METRIC 2: Hamming popcount over dim bytes (dim % 4 == 0).
-// One thread = one query (held in registers), train rows broadcast from LDS, 64-row tiles.
+// One thread = one query (held in registers), train rows broadcast from LDS, 32-row tiles.
 template <int METRIC, int DIMW>   // DIMW = 32-bit words per row
 __global__ __launch_bounds__(256) void k_knn2_valu(const uint32_t* __restrict__ q, int64_t nq,
                                                    const uint32_t* __restrict__ t, int64_t nt, int nsplit,
@@ -802,7 +802,7 @@ __global__ __launch_bounds__(256) void k_knn2_valu(const uint32_t* __restrict__ 
   uint32_t qr[DIMW];
 #pragma unroll
   for (int k = 0; k < DIMW; ++k) qr[k] = (qi < nq) ? q[qi * DIMW + k] : 0u;
-  float b1d = 3.0e38f, b2d = 3.0e38f; int b1i = -1, b2i = -1;
+  float b1d = INFINITY, b2d = INFINITY; int b1i = -1, b2i = -1;   // +inf ranks like any distance: (inf, i) before the empty (inf, -1); NaN never enters
   for (int64_t base = t_beg; base < t_end; base += TILE) {
     const int cnt = (int)((t_end - base) < TILE ? (t_end - base) : TILE);
     __syncthreads();
@@ -844,7 +844,7 @@ __global__ __launch_bounds__(256) void k_merge_splits(int64_t nq, int nsplit, co
                                                       float* __restrict__ d1, float* __restrict__ d2) {
   const int64_t qi = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (qi >= nq) return;
-  float b1d = 3.0e38f, b2d = 3.0e38f; int b1i = -1, b2i = -1;
+  float b1d = INFINITY, b2d = INFINITY; int b1i = -1, b2i = -1;   // a slot no row could be ranked into reports (-1, +inf)
   for (int s = 0; s < nsplit; ++s) {
     const Cand* c = part + ((int64_t)s * nq + qi) * 2;
     top2_insert(c[0].d, c[0].i, b1d, b1i, b2d, b2i);
@@ -1067,9 +1067,9 @@ static int match_launch(sfm_ctx* h, int metric, const void* q, int64_t nq_rows, 
       else if (dim == 64) VALU_LAUNCH(1, 64);
       else VALU_LAUNCH(1, 32);
     } else {
-      if (dim == 32) VALU_LAUNCH(2, 8);
-      else if (dim == 64) VALU_LAUNCH(2, 16);
-      else VALU_LAUNCH(2, 4);
+      // 16 and 32 bytes were rerouted to the int8 kernels by both entry points (bits): 64 bytes is all that arrives here
+      if (dim != 64) return sfm_fail(h, SFM_ERR_ARG, "sfm_match_knn2", "HAMMING on the popcount kernel needs dim 64");
+      VALU_LAUNCH(2, 16);
     }
 #undef VALU_LAUNCH
     hipLaunchKernelGGL(k_merge_splits, dim3(cdiv(n_out, 256)), dim3(256), 0, h->stream, n_out, wg ? 8 : nsplit, w.part, idx1, idx2, d1, d2);

@@ -191,7 +191,9 @@ def match_arrays(desc1, desc2, ratio=0.75, metric="auto", device=0):
     Degenerate inputs follow the reference: with no query or no train descriptors knnMatch hands back
     an empty list and the ratio loop yields [] (find_matches.py:147-155); with exactly ONE train
     descriptor every knn row holds a single DMatch and `for m, n in matches` (find_matches.py:151)
-    raises ValueError, which the per-pair try/except at :344-350 turns into a skipped pair."""
+    raises ValueError, which the per-pair try/except at :344-350 turns into a skipped pair.
+    Non-finite float32 distances follow the rule of include/sfm_amd.h: a query none of whose distances can be ranked
+    (all NaN) yields no match, one with a single rankable train row keeps it (d1 < ratio * inf)."""
     n1 = int(desc1.shape[0]) if desc1 is not None else 0
     n2 = int(desc2.shape[0]) if desc2 is not None else 0
     if n1 == 0 or n2 == 0:
@@ -200,7 +202,15 @@ def match_arrays(desc1, desc2, ratio=0.75, metric="auto", device=0):
         raise ValueError("not enough values to unpack (expected 2, got 1)")
     idx1, _, d1, d2 = knn2(desc1, desc2, metric, device)
     q, t, d = ratio_filter(idx1, d1, d2, ratio, device)
-    return q.cpu().numpy(), t.cpu().numpy(), d.cpu().numpy()
+    return q.cpu().numpy(), _ranked(t.cpu().numpy()), d.cpu().numpy()
+
+
+def _ranked(train_idx):
+    """The train indices of a match list, checked: a slot no row could be ranked into (index -1: every distance NaN)
+    carries distance +inf, and `d1 < ratio * d2` is false for d1 = +inf, so no match may hold it (include/sfm_amd.h)."""
+    if train_idx.size and int(train_idx.min()) < 0:
+        raise AssertionError("a match without a train row passed the ratio test")
+    return train_idx
 
 
 _STAGE = {}
@@ -268,7 +278,7 @@ def _run_batch(h, dev, rows, ptr, code, dim, seg_pairs, ratio):
            dp(dd), dp(seg_ptr), dp(ws), need.value)
     sp = seg_ptr.cpu().numpy()
     m = int(sp[-1])
-    qh, th, dh = qi[:m].cpu().numpy(), ti[:m].cpu().numpy(), dd[:m].cpu().numpy()
+    qh, th, dh = qi[:m].cpu().numpy(), _ranked(ti[:m].cpu().numpy()), dd[:m].cpu().numpy()
     # disjoint views of the three result arrays (444 copies were 0.25 ms of a 1.2 ms call)
     return [(qh[int(sp[k]):int(sp[k + 1])], th[int(sp[k]):int(sp[k + 1])], dh[int(sp[k]):int(sp[k + 1])]) for k in range(n_seg)]
 

@@ -982,222 +982,6 @@ __global__ __launch_bounds__(256) void k_f32_to_u8(const float* __restrict__ src
   if (!ok) *all_integral = 0;
 }
 
-// ------------------------------------------------------------------------------------ host
-
-// workspace carve (bytes): per-split candidates | train norms | query norms | ratio scratch | re-rank list + counter |
-// (batched only) workgroup records + segment table
-struct MatchWs {
-  Cand* part; uint8_t* tf; uint8_t* qbits; uint8_t* tbits; int* th; int* par; int* qn; int* u2; int* fix_list; int* fix_cnt; char* plan; int64_t total;
-};
-static MatchWs match_ws_carve(char* ws, int64_t n_out, int64_t nt_rows, int64_t nq_rows, int64_t plan_bytes, bool bits = false) {
-  MatchWs w;
-  int64_t off = 0;
-  w.part = (Cand*)(ws + off); off += align_up(8 * n_out * 2 * (int64_t)sizeof(Cand), 256);   // nsplit <= 8
-  w.tf = (uint8_t*)(ws + off); off += align_up((nt_rows + 32) * (bits ? 256 : 128), 256);       // int8 copy of the train rows + padding (dim <= 128; 256 for unpacked bits)
-  w.qbits = w.tbits = nullptr;
-  if (bits) {                                                                                  // Hamming: rows unpacked to one byte per bit (<= 256 bits)
-    w.qbits = (uint8_t*)(ws + off); off += align_up(nq_rows * 256, 256);
-    w.tbits = (uint8_t*)(ws + off); off += align_up(nt_rows * 256, 256);
-  }
-  w.th = (int*)(ws + off); off += align_up((nt_rows + 32) * 4, 256);
-  w.par = (int*)(ws + off); off += align_up((nt_rows + 1) * 4, 256);
-  w.qn = (int*)(ws + off); off += align_up(nq_rows * 4, 256);
-  w.u2 = (int*)(ws + off); off += align_up((n_out + 128) * 4, 256);                             // shared candidate thresholds (whole 128-query wave blocks)
-  off += align_up(((n_out + 255) / 256) * 8 + 64, 256);                                        // sfm_match_ratio's scratch may alias here
-  w.fix_list = (int*)(ws + off); off += align_up(n_out * 4, 256);
-  w.fix_cnt = (int*)(ws + off); off += 256;
-  w.plan = ws + off; off += align_up(plan_bytes, 256);
-  w.total = off + 1024;
-  return w;
-}
-
-extern "C" int sfm_match_workspace_bytes(int metric, int64_t nq, int64_t nt, int dim, int64_t* bytes) {
-  if (!bytes || nq < 0 || nt < 0 || dim <= 0) return SFM_ERR_ARG;
-  (void)metric;
-  *bytes = match_ws_carve(nullptr, nq, nt, nq, 0, metric == SFM_METRIC_HAMMING && dim <= 32).total;
-  return SFM_OK;
-}
-
-// The distance + top-2 stage for one segment (wg == nullptr) or a planned batch.  n_out = output rows.
-static int match_launch(sfm_ctx* h, int metric, const void* q, int64_t nq_rows, const void* t, int64_t nt_rows, int dim,
-                        int nsplit, int64_t rps, int64_t qpw /* queries per workgroup */, int64_t filter_rows /* train rows of the longest segment */,
-                        const MatchWG* wg, unsigned grid, int64_t n_out, MatchSegs segs,
-                        const MatchWs& w, int32_t* idx1, int32_t* idx2, float* d1, float* d2, bool take_root = true) {
-  const uint8_t* q8 = (const uint8_t*)q; const uint8_t* t8 = (const uint8_t*)t;
-  const uint32_t* qq = (const uint32_t*)q; const uint32_t* tt = (const uint32_t*)t;
-  if (wg)   // segments choose their own number of splits: slots a segment does not use must read as "empty" (i = -1)
-    SFM_HIP(h, hipMemsetAsync(w.part, 0xFF, (size_t)8 * n_out * 2 * sizeof(Cand), h->stream));
-  if (metric == SFM_METRIC_L2_U8) {
-    const MatchU8Choice k = match_u8_kernel(dim, nq_rows, nt_rows, qpw, wg != nullptr, filter_rows, grid, nsplit);
-    if (k.kernel != MATCH_U8_LDS) {
-      // one pre-pass launch: train tiles, then the query norms, and the bounds' initial value on the side
-      const unsigned tb = (unsigned)((nt_rows + 31) >> 5);
-      const int64_t n_u2 = n_out + 128;
-      if (k.kernel == MATCH_U8_DIRECT2_KS8) hipLaunchKernelGGL(k_train_tile_u8<8>, dim3(tb + cdiv(nq_rows * 16, 512)), dim3(512), 0, h->stream, t8, nt_rows, w.tf, w.th, w.par, w.fix_cnt,
-                                                               (int)tb, q8, nq_rows, w.qn, w.u2, n_u2);
-      else hipLaunchKernelGGL(k_train_tile_u8<4>, dim3(tb + cdiv(nq_rows * 8, 256)), dim3(256), 0, h->stream, t8, nt_rows, w.tf, w.th, w.par, w.fix_cnt,
-                              (int)tb, q8, nq_rows, w.qn, w.u2, n_u2);
-    } else {
-      hipLaunchKernelGGL(k_train_prep_u8, dim3(cdiv((nt_rows + 1) * (dim >> 4), 256)), dim3(256), 0, h->stream, t8, nt_rows, dim, w.tf, w.th, w.par, w.fix_cnt);
-      hipLaunchKernelGGL(k_row_norm_u8, dim3(cdiv(nq_rows * (dim >> 4), 256)), dim3(256), 0, h->stream, q8, nq_rows, dim, 0x7F, 0, w.qn);
-    }
-    if (k.filter) SFM_HIP(h, hipMemsetAsync(w.u2, 0x7F, (size_t)(n_out + 128) * sizeof(int), h->stream));      // "no bound yet" (the direct path's pre-pass writes it)
-    sfm_prof_begin(h, SFM_PROF_KNN);
-#define DIRECT_LAUNCH(...) hipLaunchKernelGGL((k_knn2_u8_direct<__VA_ARGS__>), dim3(grid), dim3(256), 0, h->stream, q8, nq_rows, w.tf, nt_rows, w.th, w.par, w.qn, nsplit, rps, w.part, w.u2, k.w_first, k.w_second)
-#define KNN_LAUNCH(KS, F) hipLaunchKernelGGL((k_knn2_u8<KS, F>), dim3(grid), dim3(256), 0, h->stream, q8, nq_rows, w.tf, nt_rows, w.th, w.par, w.qn, nsplit, rps, wg, n_out, w.part, w.u2)
-    if (k.kernel == MATCH_U8_DIRECT2_KS8) DIRECT_LAUNCH(2, 8);
-    else if (k.kernel == MATCH_U8_DIRECT2) DIRECT_LAUNCH(2);
-    else if (k.kernel == MATCH_U8_DIRECT4) DIRECT_LAUNCH(4);
-    else if (k.filter) {
-      if (dim == 256) KNN_LAUNCH(8, true); else if (dim == 128) KNN_LAUNCH(4, true); else if (dim == 64) KNN_LAUNCH(2, true); else KNN_LAUNCH(1, true);
-    } else {
-      if (dim == 256) KNN_LAUNCH(8, false); else if (dim == 128) KNN_LAUNCH(4, false); else if (dim == 64) KNN_LAUNCH(2, false); else KNN_LAUNCH(1, false);
-    }
-#undef KNN_LAUNCH
-#undef DIRECT_LAUNCH
-    sfm_prof_end(h, SFM_PROF_KNN);
-    hipLaunchKernelGGL(k_merge_splits_u8, dim3(cdiv(n_out, 256)), dim3(256), 0, h->stream, n_out, wg ? 8 : nsplit, w.part, idx1, idx2,
-                       d1, d2, w.fix_cnt, w.fix_list, take_root ? 1 : 0);
-    hipLaunchKernelGGL(k_knn2_u8_rerank, dim3(n_out < 2048 ? (unsigned)n_out : 2048u), dim3(256), 0, h->stream, q8, t8, nt_rows, dim,
-                       segs, w.fix_cnt, w.fix_list, idx1, idx2, d1, d2);
-  } else {
-#define VALU_LAUNCH(M, W) hipLaunchKernelGGL((k_knn2_valu<M, W>), dim3(grid), dim3(256), 0, h->stream, qq, nq_rows, tt, nt_rows, nsplit, rps, wg, n_out, w.part)
-    if (metric == SFM_METRIC_L2_F32) {
-      if (dim == 128) VALU_LAUNCH(1, 128);
-      else if (dim == 64) VALU_LAUNCH(1, 64);
-      else VALU_LAUNCH(1, 32);
-    } else {
-      // 16 and 32 bytes were rerouted to the int8 kernels by both entry points (bits): 64 bytes is all that arrives here
-      if (dim != 64) return sfm_fail(h, SFM_ERR_ARG, "sfm_match_knn2", "HAMMING on the popcount kernel needs dim 64");
-      VALU_LAUNCH(2, 16);
-    }
-#undef VALU_LAUNCH
-    hipLaunchKernelGGL(k_merge_splits, dim3(cdiv(n_out, 256)), dim3(256), 0, h->stream, n_out, wg ? 8 : nsplit, w.part, idx1, idx2, d1, d2);
-  }
-  SFM_LAUNCH_CHECK(h, "sfm_match_knn2");
-  return SFM_OK;
-}
-
-static int match_check_metric(sfm_ctx* h, int metric, int dim, const char* what) {
-  if (metric == SFM_METRIC_L2_U8) {
-    if (dim != 32 && dim != 64 && dim != 128) return sfm_fail(h, SFM_ERR_ARG, what, "L2_U8 needs dim 32, 64 or 128");
-  } else if (metric == SFM_METRIC_L2_F32) {
-    if (dim != 32 && dim != 64 && dim != 128) return sfm_fail(h, SFM_ERR_ARG, what, "L2_F32 supports dim 32, 64, 128");
-  } else if (metric == SFM_METRIC_HAMMING) {
-    if (dim != 16 && dim != 32 && dim != 64) return sfm_fail(h, SFM_ERR_ARG, what, "HAMMING supports dim 16, 32, 64 bytes");
-  } else {
-    return sfm_fail(h, SFM_ERR_ARG, what, "unknown metric");
-  }
-  return SFM_OK;
-}
-// queries one workgroup of the distance kernel takes
-// rows of train data per split and queries per workgroup of the kernel a metric uses
-
-extern "C" int sfm_match_knn2(sfm_handle h, int metric, const void* q, int64_t nq, const void* t, int64_t nt,
-                              int dim, int32_t* idx1, int32_t* idx2, float* d1, float* d2, void* workspace,
-                              int64_t workspace_bytes) {
-  if (!h) return SFM_ERR_ARG;
-  if (!q || !t || !idx1 || !idx2 || !d1 || !d2 || !workspace) return sfm_fail(h, SFM_ERR_ARG, "sfm_match_knn2", "null pointer");
-  if (nq < 1 || nt < 2) return sfm_fail(h, SFM_ERR_ARG, "sfm_match_knn2", "needs nq >= 1 and nt >= 2");
-  if (nt > 0x7FFFFF00LL || nq > 0x7FFFFF00LL) return sfm_fail(h, SFM_ERR_ARG, "sfm_match_knn2", "too many rows");
-  int rc = match_check_metric(h, metric, dim, "sfm_match_knn2"); if (rc) return rc;
-  const bool bits = metric == SFM_METRIC_HAMMING && dim <= 32;      // 128 / 256 bits: on the int8 kernels (k_unpack_bits)
-  const MatchWs w = match_ws_carve((char*)workspace, nq, nt, nq, 0, bits);
-  if (workspace_bytes < w.total) return sfm_fail(h, SFM_ERR_WORKSPACE, "sfm_match_knn2", "workspace too small");
-  if (bits) {
-    hipLaunchKernelGGL(k_unpack_bits, dim3(cdiv(nq * dim, 256)), dim3(256), 0, h->stream, (const uint8_t*)q, nq * dim, w.qbits);
-    hipLaunchKernelGGL(k_unpack_bits, dim3(cdiv(nt * dim, 256)), dim3(256), 0, h->stream, (const uint8_t*)t, nt * dim, w.tbits);
-    q = w.qbits; t = w.tbits; metric = SFM_METRIC_L2_U8; dim *= 8;
-  }
-  int nsplit; int64_t rps;
-  const int64_t qpw = match_qpw(metric, dim, nq, false);
-  match_tiling(metric, nq, qpw, nt, &nsplit, &rps);
-  const unsigned grid = cdiv(nq, qpw) * nsplit;
-  MatchSegs none = {nullptr, nullptr, nullptr, nullptr, 0};
-  return match_launch(h, metric, q, nq, t, nt, dim, nsplit, rps, qpw, nt, nullptr, grid, nq, none, w, idx1, idx2, d1, d2, !bits);
-}
-
-// ---- batched: every image pair of a preprocessing step in one launch
-
-extern "C" int sfm_match_batched_workspace_bytes(int metric, int32_t n_seg, const int64_t* q_beg_host, const int64_t* q_end_host,
-                                                 const int64_t* t_beg_host, const int64_t* t_end_host, int64_t nq_rows,
-                                                 int64_t nt_rows, int64_t* n_out_host, int64_t* bytes_host) {
-  if (n_seg < 1 || !q_beg_host || !q_end_host || !t_beg_host || !t_end_host || !n_out_host || !bytes_host) return SFM_ERR_ARG;
-  std::vector<MatchWG> wgs; std::vector<int64_t> out_ptr;
-  plan_segments(metric, 32 /* the descriptor size is not known here: the smallest pieces, i.e. the longest plan */, n_seg, q_beg_host,
-                q_end_host, t_beg_host, t_end_host, &wgs, &out_ptr);
-  *n_out_host = out_ptr[n_seg];
-  const int64_t plan_bytes = (int64_t)wgs.size() * sizeof(MatchWG) + 4 * ((int64_t)n_seg + 1) * 8 + 256;
-  *bytes_host = match_ws_carve(nullptr, out_ptr[n_seg] > 0 ? out_ptr[n_seg] : 1, nt_rows, nq_rows, plan_bytes, metric == SFM_METRIC_HAMMING).total;
-  return SFM_OK;
-}
-
-extern "C" int sfm_match_knn2_batched(sfm_handle h, int metric, const void* q, int64_t nq_rows, const void* t, int64_t nt_rows,
-                                      int dim, int32_t n_seg, const int64_t* q_beg_host, const int64_t* q_end_host,
-                                      const int64_t* t_beg_host, const int64_t* t_end_host, int32_t* idx1, int32_t* idx2,
-                                      float* d1, float* d2, int64_t* out_ptr_device, void* workspace, int64_t workspace_bytes) {
-  if (!h) return SFM_ERR_ARG;
-  if (!q || !t || !idx1 || !idx2 || !d1 || !d2 || !workspace || !q_beg_host || !q_end_host || !t_beg_host || !t_end_host || n_seg < 1)
-    return sfm_fail(h, SFM_ERR_ARG, "sfm_match_knn2_batched", "null pointer / no segments");
-  int rc = match_check_metric(h, metric, dim, "sfm_match_knn2_batched"); if (rc) return rc;
-  if (nq_rows > 0x7FFFFF00LL || nt_rows > 0x7FFFFF00LL) return sfm_fail(h, SFM_ERR_ARG, "sfm_match_knn2_batched", "too many rows");
-  for (int s = 0; s < n_seg; ++s) {
-    if (q_beg_host[s] < 0 || q_end_host[s] < q_beg_host[s] || q_end_host[s] > nq_rows || t_beg_host[s] < 0 || t_end_host[s] > nt_rows)
-      return sfm_fail(h, SFM_ERR_ARG, "sfm_match_knn2_batched", "segment outside the descriptor arrays");
-    if (q_end_host[s] > q_beg_host[s] && t_end_host[s] - t_beg_host[s] < 2)
-      return sfm_fail(h, SFM_ERR_ARG, "sfm_match_knn2_batched", "a segment with queries needs at least 2 train rows");
-  }
-  const bool bits = metric == SFM_METRIC_HAMMING && dim <= 32;      // 128 / 256 bits: on the int8 kernels (k_unpack_bits)
-  const int plan_metric = bits ? SFM_METRIC_L2_U8 : metric, plan_dim = bits ? dim * 8 : dim;
-  std::vector<MatchWG> wgs; std::vector<int64_t> out_ptr;
-  plan_segments(plan_metric, plan_dim, n_seg, q_beg_host, q_end_host, t_beg_host, t_end_host, &wgs, &out_ptr);
-  const int64_t n_out = out_ptr[n_seg];
-  if (n_out < 1) return sfm_fail(h, SFM_ERR_ARG, "sfm_match_knn2_batched", "no query rows");
-  const int64_t wg_bytes = (int64_t)wgs.size() * sizeof(MatchWG), seg_bytes = ((int64_t)n_seg + 1) * 8;
-  const MatchWs w = match_ws_carve((char*)workspace, n_out, nt_rows, nq_rows, wg_bytes + 4 * seg_bytes + 256, metric == SFM_METRIC_HAMMING);
-  if (workspace_bytes < w.total) return sfm_fail(h, SFM_ERR_WORKSPACE, "sfm_match_knn2_batched", "workspace too small");
-  if (bits) {
-    const bool same = q == t && nq_rows == nt_rows;                  // match_pairs hands one array for both sides
-    hipLaunchKernelGGL(k_unpack_bits, dim3(cdiv(nt_rows * dim, 256)), dim3(256), 0, h->stream, (const uint8_t*)t, nt_rows * dim, w.tbits);
-    if (!same) hipLaunchKernelGGL(k_unpack_bits, dim3(cdiv(nq_rows * dim, 256)), dim3(256), 0, h->stream, (const uint8_t*)q, nq_rows * dim, w.qbits);
-    q = same ? w.tbits : w.qbits; t = w.tbits; metric = SFM_METRIC_L2_U8; dim *= 8;
-  }
-  // plan -> device: workgroup records, then q_beg | t_beg | t_end | out_ptr
-  char* dp = w.plan;
-  int64_t* d_seg = (int64_t*)(dp + align_up(wg_bytes, 256));
-  SFM_HIP(h, hipMemcpyAsync(dp, wgs.data(), (size_t)wg_bytes, hipMemcpyHostToDevice, h->stream));
-  SFM_HIP(h, hipMemcpyAsync(d_seg, q_beg_host, (size_t)n_seg * 8, hipMemcpyHostToDevice, h->stream));
-  SFM_HIP(h, hipMemcpyAsync(d_seg + (n_seg + 1), t_beg_host, (size_t)n_seg * 8, hipMemcpyHostToDevice, h->stream));
-  SFM_HIP(h, hipMemcpyAsync(d_seg + 2 * (n_seg + 1), t_end_host, (size_t)n_seg * 8, hipMemcpyHostToDevice, h->stream));
-  SFM_HIP(h, hipMemcpyAsync(d_seg + 3 * (n_seg + 1), out_ptr.data(), (size_t)seg_bytes, hipMemcpyHostToDevice, h->stream));
-  if (out_ptr_device)
-    SFM_HIP(h, hipMemcpyAsync(out_ptr_device, out_ptr.data(), (size_t)seg_bytes, hipMemcpyHostToDevice, h->stream));
-  SFM_HIP(h, hipStreamSynchronize(h->stream));          // the host vectors are pageable: the copies must have left them
-  MatchSegs segs = {d_seg, d_seg + (n_seg + 1), d_seg + 2 * (n_seg + 1), d_seg + 3 * (n_seg + 1), n_seg};
-  int64_t longest = 0;
-  for (int s = 0; s < n_seg; ++s) longest = (t_end_host[s] - t_beg_host[s]) > longest ? (t_end_host[s] - t_beg_host[s]) : longest;
-  return match_launch(h, metric, q, nq_rows, t, nt_rows, dim, 1, 0, 256, longest, (const MatchWG*)dp, (unsigned)wgs.size(), n_out, segs, w,
-                      idx1, idx2, d1, d2, !bits);
-}
-
-extern "C" int sfm_match_ratio(sfm_handle h, int64_t nq, const int32_t* idx1, const float* d1, const float* d2,
-                               double ratio, int32_t* query_idx, int32_t* train_idx, float* dist,
-                               int64_t* n_matches, void* workspace, int64_t workspace_bytes) {
-  if (!h) return SFM_ERR_ARG;
-  if (!idx1 || !d1 || !d2 || !query_idx || !train_idx || !dist || !n_matches || !workspace || nq < 1)
-    return sfm_fail(h, SFM_ERR_ARG, "sfm_match_ratio", "bad argument");
-  const int nblk = (int)cdiv(nq, 256);
-  if (workspace_bytes < (int64_t)nblk * 8) return sfm_fail(h, SFM_ERR_WORKSPACE, "sfm_match_ratio", "workspace too small");
-  int* blk_cnt = (int*)workspace;
-  int* blk_off = blk_cnt + nblk;
-  hipLaunchKernelGGL(k_ratio_count, dim3(nblk), dim3(256), 0, h->stream, nq, d1, d2, ratio, blk_cnt);
-  hipLaunchKernelGGL(k_ratio_scan, dim3(1), dim3(256), 0, h->stream, nblk, blk_cnt, blk_off, n_matches);
-  hipLaunchKernelGGL(k_ratio_scatter, dim3(nblk), dim3(256), 0, h->stream, nq, idx1, d1, d2, ratio, blk_off,
-                     query_idx, train_idx, dist);
-  SFM_LAUNCH_CHECK(h, "sfm_match_ratio");
-  return SFM_OK;
-}
-
 // after the compaction of a batch: where each segment's matches begin, and query indices relative to their segment
 __global__ __launch_bounds__(256) void k_seg_split(int64_t n_out, int n_seg, const int64_t* __restrict__ out_ptr,
                                                    const int64_t* __restrict__ n_matches, int* __restrict__ query_idx,
@@ -1221,29 +1005,245 @@ __global__ __launch_bounds__(256) void k_seg_localise(int n_seg, const int64_t* 
   query_idx[i] = (int)(row - out_ptr[lo]);
 }
 
+// ------------------------------------------------------------------------------------ host
+// What a call decides on the host - its route, the argument checks, the workspace layout, the tiling and every grid - is
+// match_plan.h.  Here the workspace is carved by that layout, the kernel instantiation is picked and the launches are issued.
+static_assert(sizeof(Cand) == MATCH_CAND_BYTES, "match_plan.h sizes the candidate region");
+
+static int match_refuse(sfm_ctx* h, const char* what, int bad) { return sfm_fail(h, match_why_code(bad), what, MATCH_WHY[bad]); }
+
+struct MatchWs {
+  Cand* part; uint8_t* tf; uint8_t* qbits; uint8_t* tbits; int* th; int* par; int* qn; int* u2; int* fix_list; int* fix_cnt; char* plan;
+};
+static MatchWs match_ws(void* workspace, const MatchLayout& L) {
+  char* ws = (char*)workspace;
+  MatchWs w;
+  w.part = (Cand*)(ws + L.part);
+  w.tf = (uint8_t*)(ws + L.tf);
+  w.qbits = L.qbits < 0 ? nullptr : (uint8_t*)(ws + L.qbits);
+  w.tbits = L.tbits < 0 ? nullptr : (uint8_t*)(ws + L.tbits);
+  w.th = (int*)(ws + L.th);
+  w.par = (int*)(ws + L.par);
+  w.qn = (int*)(ws + L.qn);
+  w.u2 = (int*)(ws + L.u2);
+  w.fix_list = (int*)(ws + L.fix_list);
+  w.fix_cnt = (int*)(ws + L.fix_cnt);
+  w.plan = ws + L.plan;
+  return w;
+}
+
+// the instantiation behind a planner's choice
+// (the order of the instantiations below is the order in which the device code is emitted)
+using TileKernel = decltype(&k_train_tile_u8<8>);
+static TileKernel train_tile_kernel(MatchU8Kernel kernel) {
+  return kernel == MATCH_U8_DIRECT2_KS8 ? k_train_tile_u8<8> : k_train_tile_u8<4>;
+}
+using DirectKernel = decltype(&k_knn2_u8_direct<2, 8>);
+static DirectKernel knn2_direct_kernel(MatchU8Kernel kernel) {
+  switch (kernel) {
+    case MATCH_U8_DIRECT2_KS8: return k_knn2_u8_direct<2, 8>;
+    case MATCH_U8_DIRECT2: return k_knn2_u8_direct<2>;
+    default: return k_knn2_u8_direct<4>;
+  }
+}
+using KnnU8Kernel = decltype(&k_knn2_u8<8, true>);
+static KnnU8Kernel knn2_u8_kernel(int dim, bool filter) {
+  if (filter) switch (dim) {
+    case 256: return k_knn2_u8<8, true>;
+    case 128: return k_knn2_u8<4, true>;
+    case 64: return k_knn2_u8<2, true>;
+    default: return k_knn2_u8<1, true>;
+  }
+  switch (dim) {
+    case 256: return k_knn2_u8<8, false>;
+    case 128: return k_knn2_u8<4, false>;
+    case 64: return k_knn2_u8<2, false>;
+    default: return k_knn2_u8<1, false>;
+  }
+}
+using ValuKernel = decltype(&k_knn2_valu<1, 128>);
+static ValuKernel knn2_valu_kernel(int metric, int dim) {
+  if (metric == SFM_METRIC_L2_F32) switch (dim) {
+    case 128: return k_knn2_valu<1, 128>;
+    case 64: return k_knn2_valu<1, 64>;
+    default: return k_knn2_valu<1, 32>;
+  }
+  return k_knn2_valu<2, 16>;      // HAMMING at 64 bytes: all that match_check_metric lets through to this kernel
+}
+
+extern "C" int sfm_match_workspace_bytes(int metric, int64_t nq, int64_t nt, int dim, int64_t* bytes) {
+  if (!bytes || nq < 0 || nt < 0 || dim <= 0) return SFM_ERR_ARG;
+  *bytes = match_layout(nq, nt, nq, 0, match_route(metric, dim).bits).bytes;
+  return SFM_OK;
+}
+
+// Hamming on 128 / 256 bits: the rows unpacked to one byte per bit, where the int8 kernels read them.  share_one_array (the
+// batched call: match_pairs hands one array for both sides) unpacks such an array once.
+static void match_unpack(sfm_ctx* h, int packed_dim, const void** q, int64_t nq_rows, const void** t, int64_t nt_rows, const MatchWs& w,
+                         bool share_one_array) {
+  const bool same = share_one_array && *q == *t && nq_rows == nt_rows;
+  const int64_t t_bytes = match_packed_bytes(nt_rows, packed_dim), q_bytes = match_packed_bytes(nq_rows, packed_dim);
+  hipLaunchKernelGGL(k_unpack_bits, dim3(match_blocks(t_bytes)), dim3(256), 0, h->stream, (const uint8_t*)*t, t_bytes, w.tbits);
+  if (!same) hipLaunchKernelGGL(k_unpack_bits, dim3(match_blocks(q_bytes)), dim3(256), 0, h->stream, (const uint8_t*)*q, q_bytes, w.qbits);
+  *q = same ? w.tbits : w.qbits;
+  *t = w.tbits;
+}
+
+// The distance + top-2 stage of a routed call (what = its entry point) for one segment (wg == nullptr) or a planned batch.
+// n_out = output rows, filter_rows = train rows of the longest segment.
+static int match_launch(sfm_ctx* h, const char* what, const MatchRoute& r, const void* q, int64_t nq_rows, const void* t, int64_t nt_rows,
+                        int nsplit, int64_t rps, int64_t qpw /* queries per workgroup */, int64_t filter_rows, const MatchWG* wg, unsigned grid,
+                        int64_t n_out, MatchSegs segs, const MatchWs& w, int32_t* idx1, int32_t* idx2, float* d1, float* d2) {
+  const int merge_splits = wg ? (int)MATCH_MAX_SPLITS : nsplit;
+  if (wg)   // segments choose their own number of splits: slots a segment does not use must read as "empty" (i = -1)
+    SFM_HIP(h, hipMemsetAsync(w.part, 0xFF, (size_t)match_part_bytes(n_out), h->stream));
+  if (r.metric == SFM_METRIC_L2_U8) {
+    const uint8_t* q8 = (const uint8_t*)q; const uint8_t* t8 = (const uint8_t*)t;
+    const MatchU8Choice k = match_u8_kernel(r.dim, nq_rows, nt_rows, qpw, wg != nullptr, filter_rows, grid, nsplit);
+    if (k.kernel != MATCH_U8_LDS) {
+      // one pre-pass launch: train tiles, then the query norms, and the bounds' initial value on the side
+      const MatchPrepass p = match_prepass(nt_rows, nq_rows, k.kernel == MATCH_U8_DIRECT2_KS8);
+      hipLaunchKernelGGL(train_tile_kernel(k.kernel), dim3(p.grid), dim3(p.threads), 0, h->stream,
+                         t8, nt_rows, w.tf, w.th, w.par, w.fix_cnt, (int)p.tile_blocks, q8, nq_rows, w.qn, w.u2, match_u2_count(n_out));
+    } else {
+      hipLaunchKernelGGL(k_train_prep_u8, dim3(match_prep_grid(nt_rows, r.dim)), dim3(256), 0, h->stream, t8, nt_rows, r.dim, w.tf, w.th, w.par, w.fix_cnt);
+      hipLaunchKernelGGL(k_row_norm_u8, dim3(match_norm_grid(nq_rows, r.dim)), dim3(256), 0, h->stream, q8, nq_rows, r.dim, 0x7F, 0, w.qn);
+    }
+    if (k.filter) SFM_HIP(h, hipMemsetAsync(w.u2, 0x7F, (size_t)match_u2_count(n_out) * sizeof(int), h->stream));      // "no bound yet" (the direct path's pre-pass writes it)
+    sfm_prof_begin(h, SFM_PROF_KNN);
+    if (k.kernel != MATCH_U8_LDS)
+      hipLaunchKernelGGL(knn2_direct_kernel(k.kernel), dim3(grid), dim3(256), 0, h->stream, q8, nq_rows, w.tf, nt_rows, w.th, w.par, w.qn, nsplit, rps,
+                         w.part, w.u2, k.w_first, k.w_second);
+    else
+      hipLaunchKernelGGL(knn2_u8_kernel(r.dim, k.filter), dim3(grid), dim3(256), 0, h->stream, q8, nq_rows, w.tf, nt_rows, w.th, w.par, w.qn, nsplit, rps,
+                         wg, n_out, w.part, w.u2);
+    sfm_prof_end(h, SFM_PROF_KNN);
+    hipLaunchKernelGGL(k_merge_splits_u8, dim3(match_blocks(n_out)), dim3(256), 0, h->stream, n_out, merge_splits, w.part, idx1, idx2,
+                       d1, d2, w.fix_cnt, w.fix_list, r.bits ? 0 : 1);      // unpacked bits: d^2 is the popcount, no root
+    hipLaunchKernelGGL(k_knn2_u8_rerank, dim3(match_rerank_grid(n_out)), dim3(256), 0, h->stream, q8, t8, nt_rows, r.dim,
+                       segs, w.fix_cnt, w.fix_list, idx1, idx2, d1, d2);
+  } else {
+    hipLaunchKernelGGL(knn2_valu_kernel(r.metric, r.dim), dim3(grid), dim3(256), 0, h->stream, (const uint32_t*)q, nq_rows, (const uint32_t*)t, nt_rows,
+                       nsplit, rps, wg, n_out, w.part);
+    hipLaunchKernelGGL(k_merge_splits, dim3(match_blocks(n_out)), dim3(256), 0, h->stream, n_out, merge_splits, w.part, idx1, idx2, d1, d2);
+  }
+  SFM_LAUNCH_CHECK(h, what);
+  return SFM_OK;
+}
+
+extern "C" int sfm_match_knn2(sfm_handle h, int metric, const void* q, int64_t nq, const void* t, int64_t nt,
+                              int dim, int32_t* idx1, int32_t* idx2, float* d1, float* d2, void* workspace,
+                              int64_t workspace_bytes) {
+  static const char* const what = "sfm_match_knn2";
+  if (!h) return SFM_ERR_ARG;
+  int bad = match_check_knn2(metric, q, nq, t, nt, dim, idx1, idx2, d1, d2, workspace);
+  if (bad) return match_refuse(h, what, bad);
+  const MatchRoute r = match_route(metric, dim);
+  const MatchLayout L = match_layout(nq, nt, nq, 0, r.bits);
+  bad = match_check_workspace(workspace_bytes, L.bytes);
+  if (bad) return match_refuse(h, what, bad);
+  const MatchWs w = match_ws(workspace, L);
+  if (r.bits) match_unpack(h, dim, &q, nq, &t, nt, w, false);
+  int nsplit; int64_t rps;
+  const int64_t qpw = match_qpw(r.metric, r.dim, nq, false);
+  match_tiling(r.metric, nq, qpw, nt, &nsplit, &rps);
+  MatchSegs none = {nullptr, nullptr, nullptr, nullptr, 0};
+  return match_launch(h, what, r, q, nq, t, nt, nsplit, rps, qpw, nt, nullptr, match_grid(nq, qpw, nsplit), nq, none, w, idx1, idx2, d1, d2);
+}
+
+// ---- batched: every image pair of a preprocessing step in one launch
+
+extern "C" int sfm_match_batched_workspace_bytes(int metric, int32_t n_seg, const int64_t* q_beg_host, const int64_t* q_end_host,
+                                                 const int64_t* t_beg_host, const int64_t* t_end_host, int64_t nq_rows,
+                                                 int64_t nt_rows, int64_t* n_out_host, int64_t* bytes_host) {
+  if (n_seg < 1 || !q_beg_host || !q_end_host || !t_beg_host || !t_end_host || !n_out_host || !bytes_host) return SFM_ERR_ARG;
+  const MatchRoute r = match_route_largest(metric);      // the descriptor size is not known here
+  std::vector<MatchWG> wgs; std::vector<int64_t> out_ptr;
+  plan_segments(r.metric, r.dim, n_seg, q_beg_host, q_end_host, t_beg_host, t_end_host, &wgs, &out_ptr);
+  *n_out_host = out_ptr[n_seg];
+  *bytes_host = match_layout(out_ptr[n_seg] > 0 ? out_ptr[n_seg] : 1, nt_rows, nq_rows, match_plan_bytes((int64_t)wgs.size(), n_seg), r.bits).bytes;
+  return SFM_OK;
+}
+
+extern "C" int sfm_match_knn2_batched(sfm_handle h, int metric, const void* q, int64_t nq_rows, const void* t, int64_t nt_rows,
+                                      int dim, int32_t n_seg, const int64_t* q_beg_host, const int64_t* q_end_host,
+                                      const int64_t* t_beg_host, const int64_t* t_end_host, int32_t* idx1, int32_t* idx2,
+                                      float* d1, float* d2, int64_t* out_ptr_device, void* workspace, int64_t workspace_bytes) {
+  static const char* const what = "sfm_match_knn2_batched";
+  if (!h) return SFM_ERR_ARG;
+  int bad = match_check_batched(metric, q, nq_rows, t, nt_rows, dim, n_seg, q_beg_host, q_end_host, t_beg_host, t_end_host, idx1, idx2, d1, d2, workspace);
+  if (bad) return match_refuse(h, what, bad);
+  const MatchRoute r = match_route(metric, dim);
+  std::vector<MatchWG> wgs; std::vector<int64_t> out_ptr;
+  plan_segments(r.metric, r.dim, n_seg, q_beg_host, q_end_host, t_beg_host, t_end_host, &wgs, &out_ptr);
+  const int64_t n_out = out_ptr[n_seg];
+  const MatchPlanLayout P = match_plan_layout((int64_t)wgs.size(), n_seg);
+  const MatchLayout L = match_layout(n_out, nt_rows, nq_rows, P.bytes, r.bits);
+  bad = match_check_workspace(workspace_bytes, L.bytes);
+  if (bad) return match_refuse(h, what, bad);
+  const MatchWs w = match_ws(workspace, L);
+  if (r.bits) match_unpack(h, dim, &q, nq_rows, &t, nt_rows, w, true);
+  // plan -> device: workgroup records, then q_beg | t_beg | t_end | out_ptr
+  SFM_HIP(h, hipMemcpyAsync(w.plan + P.wg, wgs.data(), (size_t)P.wg_bytes, hipMemcpyHostToDevice, h->stream));
+  SFM_HIP(h, hipMemcpyAsync(w.plan + P.q_beg, q_beg_host, (size_t)P.in_bytes, hipMemcpyHostToDevice, h->stream));
+  SFM_HIP(h, hipMemcpyAsync(w.plan + P.t_beg, t_beg_host, (size_t)P.in_bytes, hipMemcpyHostToDevice, h->stream));
+  SFM_HIP(h, hipMemcpyAsync(w.plan + P.t_end, t_end_host, (size_t)P.in_bytes, hipMemcpyHostToDevice, h->stream));
+  SFM_HIP(h, hipMemcpyAsync(w.plan + P.out_ptr, out_ptr.data(), (size_t)P.out_bytes, hipMemcpyHostToDevice, h->stream));
+  if (out_ptr_device)
+    SFM_HIP(h, hipMemcpyAsync(out_ptr_device, out_ptr.data(), (size_t)P.out_bytes, hipMemcpyHostToDevice, h->stream));
+  SFM_HIP(h, hipStreamSynchronize(h->stream));          // the host vectors are pageable: the copies must have left them
+  MatchSegs segs = {(const int64_t*)(w.plan + P.q_beg), (const int64_t*)(w.plan + P.t_beg), (const int64_t*)(w.plan + P.t_end),
+                    (const int64_t*)(w.plan + P.out_ptr), n_seg};
+  return match_launch(h, what, r, q, nq_rows, t, nt_rows, 1, 0, 256, match_longest_segment(n_seg, t_beg_host, t_end_host),
+                      (const MatchWG*)(w.plan + P.wg), (unsigned)wgs.size(), n_out, segs, w, idx1, idx2, d1, d2);
+}
+
+extern "C" int sfm_match_ratio(sfm_handle h, int64_t nq, const int32_t* idx1, const float* d1, const float* d2,
+                               double ratio, int32_t* query_idx, int32_t* train_idx, float* dist,
+                               int64_t* n_matches, void* workspace, int64_t workspace_bytes) {
+  static const char* const what = "sfm_match_ratio";
+  if (!h) return SFM_ERR_ARG;
+  int bad = match_check_ratio(nq, idx1, d1, d2, query_idx, train_idx, dist, n_matches, workspace);
+  if (!bad) bad = match_check_workspace(workspace_bytes, match_ratio_scratch_bytes(nq));
+  if (bad) return match_refuse(h, what, bad);
+  const int nblk = (int)match_blocks(nq);
+  int* blk_cnt = (int*)workspace;
+  int* blk_off = blk_cnt + nblk;
+  hipLaunchKernelGGL(k_ratio_count, dim3(nblk), dim3(256), 0, h->stream, nq, d1, d2, ratio, blk_cnt);
+  hipLaunchKernelGGL(k_ratio_scan, dim3(1), dim3(256), 0, h->stream, nblk, blk_cnt, blk_off, n_matches);
+  hipLaunchKernelGGL(k_ratio_scatter, dim3(nblk), dim3(256), 0, h->stream, nq, idx1, d1, d2, ratio, blk_off,
+                     query_idx, train_idx, dist);
+  SFM_LAUNCH_CHECK(h, what);
+  return SFM_OK;
+}
+
 extern "C" int sfm_match_ratio_batched(sfm_handle h, int64_t n_out, int32_t n_seg, const int64_t* out_ptr, const int32_t* idx1,
                                        const float* d1, const float* d2, double ratio, int32_t* query_idx, int32_t* train_idx,
                                        float* dist, int64_t* seg_match_ptr, void* workspace, int64_t workspace_bytes) {
+  static const char* const what = "sfm_match_ratio_batched";
   if (!h) return SFM_ERR_ARG;
-  if (!out_ptr || !seg_match_ptr || n_seg < 1) return sfm_fail(h, SFM_ERR_ARG, "sfm_match_ratio_batched", "bad argument");
-  const int64_t need = (int64_t)cdiv(n_out, 256) * 8 + 64;
-  if (workspace_bytes < need) return sfm_fail(h, SFM_ERR_WORKSPACE, "sfm_match_ratio_batched", "workspace too small");
-  int64_t* n_matches = (int64_t*)((char*)workspace + align_up((int64_t)cdiv(n_out, 256) * 8, 8));
-  int rc = sfm_match_ratio(h, n_out, idx1, d1, d2, ratio, query_idx, train_idx, dist, n_matches, workspace, (int64_t)cdiv(n_out, 256) * 8);
+  int bad = match_check_ratio_batched(n_seg, out_ptr, seg_match_ptr);
+  if (!bad) bad = match_check_workspace(workspace_bytes, match_ratio_scratch_bytes(n_out, true));
+  if (bad) return match_refuse(h, what, bad);
+  const int64_t counts_bytes = match_ratio_scratch_bytes(n_out);      // the total sits behind the block counts and offsets
+  int64_t* n_matches = (int64_t*)((char*)workspace + counts_bytes);
+  int rc = sfm_match_ratio(h, n_out, idx1, d1, d2, ratio, query_idx, train_idx, dist, n_matches, workspace, counts_bytes);
   if (rc) return rc;
   // the split reads the global (output-row) query indices: it must run before they are made segment-relative
-  hipLaunchKernelGGL(k_seg_split, dim3(cdiv((int64_t)n_seg + 1, 256)), dim3(256), 0, h->stream, n_out, n_seg, out_ptr, n_matches,
+  hipLaunchKernelGGL(k_seg_split, dim3(match_blocks((int64_t)n_seg + 1)), dim3(256), 0, h->stream, n_out, n_seg, out_ptr, n_matches,
                      query_idx, seg_match_ptr);
-  hipLaunchKernelGGL(k_seg_localise, dim3(cdiv(n_out, 256)), dim3(256), 0, h->stream, n_seg, out_ptr, n_matches, query_idx);
-  SFM_LAUNCH_CHECK(h, "sfm_match_ratio_batched");
+  hipLaunchKernelGGL(k_seg_localise, dim3(match_blocks(n_out)), dim3(256), 0, h->stream, n_seg, out_ptr, n_matches, query_idx);
+  SFM_LAUNCH_CHECK(h, what);
   return SFM_OK;
 }
 
 extern "C" int sfm_match_f32_to_u8(sfm_handle h, const float* src, int64_t n_elems, uint8_t* dst, int32_t* all_integral) {
+  static const char* const what = "sfm_match_f32_to_u8";
   if (!h) return SFM_ERR_ARG;
-  if (!src || !dst || !all_integral || n_elems < 1) return sfm_fail(h, SFM_ERR_ARG, "sfm_match_f32_to_u8", "bad argument");
+  const int bad = match_check_f32_to_u8(src, n_elems, dst, all_integral);
+  if (bad) return match_refuse(h, what, bad);
   SFM_HIP(h, hipMemsetD32Async((hipDeviceptr_t)all_integral, 1, 1, h->stream));
-  hipLaunchKernelGGL(k_f32_to_u8, dim3(cdiv(n_elems, 256)), dim3(256), 0, h->stream, src, n_elems, dst, all_integral);
-  SFM_LAUNCH_CHECK(h, "sfm_match_f32_to_u8");
+  hipLaunchKernelGGL(k_f32_to_u8, dim3(match_blocks(n_elems)), dim3(256), 0, h->stream, src, n_elems, dst, all_integral);
+  SFM_LAUNCH_CHECK(h, what);
   return SFM_OK;
 }

@@ -111,6 +111,38 @@ def _resolve_metric(q, t, metric):
     return metric
 
 
+def _metric_code(is_u8, dim, metric):
+    """The metric code of a resolved metric ("l2" / "hamming") over uint8 (is_u8) or other rows of `dim` columns - or None:
+    float rows at dims 32 / 64 / 128 take the exact uint8 path if their values are integers in [0, 255], which the caller
+    finds out its own way (knn2 over the two sets, match_pairs per image)."""
+    if metric == "hamming":
+        if not is_u8:
+            raise ValueError("hamming needs uint8 descriptors")
+        return _lib.METRIC_HAMMING
+    if dim not in (32, 64, 128):
+        return _lib.METRIC_L2_F32
+    return _lib.METRIC_L2_U8 if is_u8 else None
+
+
+def _knn_outputs(n, dev):
+    """idx1, idx2, d1, d2 of n output rows"""
+    import torch
+    return (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+            torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev))
+
+
+def _ratio_outputs(n, dev):
+    """query index, train index, distance of at most n matches"""
+    import torch
+    return (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+            torch.empty(n, dtype=torch.float32, device=dev))
+
+
+def _ratio_ws_bytes(n):
+    """Scratch of sfm_match_ratio_batched over n rows (include/sfm_amd.h); sfm_match_ratio needs 64 bytes less."""
+    return ((n + 255) // 256) * 8 + 64
+
+
 def knn2(desc1, desc2, metric="auto", device=0):
     """cv2.BFMatcher(norm).knnMatch(desc1, desc2, k=2) -> (idx1, idx2, d1, d2) CUDA tensors.
 
@@ -119,6 +151,7 @@ def knn2(desc1, desc2, metric="auto", device=0):
     are all integers in [0,255] (what SIFT emits) take the exact integer path on the matrix cores.
     """
     import torch
+    dp = _lib.dp
     h = _lib.get_handle(device)
     dev = torch.device("cuda", device)
     q, t = _to_device(desc1, dev), _to_device(desc2, dev)
@@ -130,57 +163,38 @@ def knn2(desc1, desc2, metric="auto", device=0):
     nt = t.shape[0]
     if nt < 2 or nq < 1:
         raise ValueError("knn2 needs at least 1 query and 2 train descriptors")
-    metric = _resolve_metric(q, t, metric)
-    if metric == "hamming":
-        if q.dtype != torch.uint8:
-            raise ValueError("hamming needs uint8 descriptors")
-        code = _lib.METRIC_HAMMING
-    elif q.dtype == torch.uint8:
-        if dim in (32, 64, 128):
-            code = _lib.METRIC_L2_U8
-        else:
-            q, t, code = q.float(), t.float(), _lib.METRIC_L2_F32
-    else:
+    code = _metric_code(q.dtype == torch.uint8, dim, _resolve_metric(q, t, metric))
+    if code is None or code == _lib.METRIC_L2_F32:
         q, t = q.float(), t.float()
+    if code is None:
         code = _lib.METRIC_L2_F32
-        if dim in (32, 64, 128):
-            flag = torch.ones(2, dtype=torch.int32, device=dev)
-            q8 = torch.empty(q.shape, dtype=torch.uint8, device=dev)
-            t8 = torch.empty(t.shape, dtype=torch.uint8, device=dev)
-            h.call("sfm_match_f32_to_u8", C.c_void_p(q.data_ptr()), q.numel(), C.c_void_p(q8.data_ptr()),
-                   C.c_void_p(flag[0:1].data_ptr()))
-            h.call("sfm_match_f32_to_u8", C.c_void_p(t.data_ptr()), t.numel(), C.c_void_p(t8.data_ptr()),
-                   C.c_void_p(flag[1:2].data_ptr()))
-            if bool((flag == 1).all().item()):
-                q, t, code = q8, t8, _lib.METRIC_L2_U8
+        flag = torch.ones(2, dtype=torch.int32, device=dev)
+        q8 = torch.empty(q.shape, dtype=torch.uint8, device=dev)
+        t8 = torch.empty(t.shape, dtype=torch.uint8, device=dev)
+        h.call("sfm_match_f32_to_u8", dp(q), q.numel(), dp(q8), dp(flag[0:1]))
+        h.call("sfm_match_f32_to_u8", dp(t), t.numel(), dp(t8), dp(flag[1:2]))
+        if bool((flag == 1).all().item()):
+            q, t, code = q8, t8, _lib.METRIC_L2_U8
     need = C.c_int64()
     h.check(h.lib.sfm_match_workspace_bytes(code, nq, nt, dim, C.byref(need)), "sfm_match_workspace_bytes")
     ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-    idx1 = torch.empty(nq, dtype=torch.int32, device=dev)
-    idx2 = torch.empty(nq, dtype=torch.int32, device=dev)
-    d1 = torch.empty(nq, dtype=torch.float32, device=dev)
-    d2 = torch.empty(nq, dtype=torch.float32, device=dev)
-    h.call("sfm_match_knn2", code, C.c_void_p(q.data_ptr()), nq, C.c_void_p(t.data_ptr()), nt, dim,
-           C.c_void_p(idx1.data_ptr()), C.c_void_p(idx2.data_ptr()), C.c_void_p(d1.data_ptr()),
-           C.c_void_p(d2.data_ptr()), C.c_void_p(ws.data_ptr()), need.value)
+    idx1, idx2, d1, d2 = _knn_outputs(nq, dev)
+    h.call("sfm_match_knn2", code, dp(q), nq, dp(t), nt, dim, dp(idx1), dp(idx2), dp(d1), dp(d2), dp(ws), need.value)
     return idx1, idx2, d1, d2
 
 
 def ratio_filter(idx1, d1, d2, ratio=0.75, device=0):
     """`m.distance < ratio * n.distance` (find_matches.py:152) + compaction in query order."""
     import torch
+    dp = _lib.dp
     h = _lib.get_handle(device)
     dev = idx1.device
     nq = idx1.shape[0]
-    qi = torch.empty(nq, dtype=torch.int32, device=dev)
-    ti = torch.empty(nq, dtype=torch.int32, device=dev)
-    dd = torch.empty(nq, dtype=torch.float32, device=dev)
+    qi, ti, dd = _ratio_outputs(nq, dev)
     cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws_bytes = ((nq + 255) // 256) * 8 + 64
+    ws_bytes = _ratio_ws_bytes(nq)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    h.call("sfm_match_ratio", nq, C.c_void_p(idx1.data_ptr()), C.c_void_p(d1.data_ptr()),
-           C.c_void_p(d2.data_ptr()), C.c_double(ratio), C.c_void_p(qi.data_ptr()), C.c_void_p(ti.data_ptr()),
-           C.c_void_p(dd.data_ptr()), C.c_void_p(cnt.data_ptr()), C.c_void_p(ws.data_ptr()), ws_bytes)
+    h.call("sfm_match_ratio", nq, dp(idx1), dp(d1), dp(d2), C.c_double(ratio), dp(qi), dp(ti), dp(dd), dp(cnt), dp(ws), ws_bytes)
     m = int(cnt.item())
     return qi[:m], ti[:m], dd[:m]
 
@@ -255,24 +269,18 @@ def _run_batch(h, dev, rows, ptr, code, dim, seg_pairs, ratio):
     q_end = np.array([ptr[i + 1] for i, _ in seg_pairs], dtype=np.int64)
     t_beg = np.array([ptr[j] for _, j in seg_pairs], dtype=np.int64)
     t_end = np.array([ptr[j + 1] for _, j in seg_pairs], dtype=np.int64)
-    hp = lambda a: C.c_void_p(a.ctypes.data)
+    dp, hp = _lib.dp, _lib.hp
     n_out, need = C.c_int64(), C.c_int64()
     n_rows = int(rows.shape[0])
     h.check(h.lib.sfm_match_batched_workspace_bytes(code, n_seg, hp(q_beg), hp(q_end), hp(t_beg), hp(t_end), n_rows, n_rows,
                                                     C.byref(n_out), C.byref(need)), "sfm_match_batched_workspace_bytes")
     n = n_out.value
     ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
-    idx1 = torch.empty(n, dtype=torch.int32, device=dev)
-    idx2 = torch.empty(n, dtype=torch.int32, device=dev)
-    d1 = torch.empty(n, dtype=torch.float32, device=dev)
-    d2 = torch.empty(n, dtype=torch.float32, device=dev)
+    idx1, idx2, d1, d2 = _knn_outputs(n, dev)
     out_ptr = torch.empty(n_seg + 1, dtype=torch.int64, device=dev)
-    dp = lambda t: C.c_void_p(t.data_ptr())
     h.call("sfm_match_knn2_batched", code, dp(rows), n_rows, dp(rows), n_rows, dim, n_seg, hp(q_beg), hp(q_end), hp(t_beg),
            hp(t_end), dp(idx1), dp(idx2), dp(d1), dp(d2), dp(out_ptr), dp(ws), need.value)
-    qi = torch.empty(n, dtype=torch.int32, device=dev)
-    ti = torch.empty(n, dtype=torch.int32, device=dev)
-    dd = torch.empty(n, dtype=torch.float32, device=dev)
+    qi, ti, dd = _ratio_outputs(n, dev)
     seg_ptr = torch.empty(n_seg + 1, dtype=torch.int64, device=dev)
     h.call("sfm_match_ratio_batched", n, n_seg, dp(out_ptr), dp(idx1), dp(d1), dp(d2), C.c_double(ratio), dp(qi), dp(ti),
            dp(dd), dp(seg_ptr), dp(ws), need.value)
@@ -316,31 +324,27 @@ def match_pairs(descs, pairs, ratio=0.75, metric="auto", device=0):
     rows, ptr, dim = _upload_sets([np.ascontiguousarray(descs[i]) for i in used], dev)
     metric = _resolve_metric(rows, rows, metric)
     seg = [(slot[pairs[s][0]], slot[pairs[s][1]]) for s in live]
+    everything = list(range(len(live)))
+    code = _metric_code(rows.dtype == torch.uint8, dim, metric)
     groups = []                                            # (rows, metric code, positions in `live`)
-    if metric == "hamming":
-        if rows.dtype != torch.uint8:
-            raise ValueError("hamming needs uint8 descriptors")
-        groups.append((rows, _lib.METRIC_HAMMING, list(range(len(live)))))
-    elif rows.dtype == torch.uint8:
-        groups.append((rows, _lib.METRIC_L2_U8, list(range(len(live)))) if dim in (32, 64, 128)
-                      else (rows.float(), _lib.METRIC_L2_F32, list(range(len(live)))))
-    else:
+    if code is None:
         rows = rows.float()
-        if dim in (32, 64, 128):
-            # per image: every value an integer in [0, 255]?  (what SIFT emits)
-            row_ok = ((rows == rows.round()) & (rows >= 0) & (rows <= 255)).all(dim=1)
-            csum = torch.zeros(rows.shape[0] + 1, dtype=torch.int64, device=dev)
-            torch.cumsum(row_ok.to(torch.int64), 0, out=csum[1:])
-            tp = torch.from_numpy(ptr).to(dev)
-            img_ok = ((csum[tp[1:]] - csum[tp[:-1]]) == (tp[1:] - tp[:-1])).cpu().numpy()
-            exact = [k for k, (a, b) in enumerate(seg) if img_ok[a] and img_ok[b]]
-            other = [k for k, (a, b) in enumerate(seg) if not (img_ok[a] and img_ok[b])]
-            if exact:
-                groups.append((rows.to(torch.uint8), _lib.METRIC_L2_U8, exact))     # rows of other images are never read by this group
-            if other:
-                groups.append((rows, _lib.METRIC_L2_F32, other))
-        else:
-            groups.append((rows, _lib.METRIC_L2_F32, list(range(len(live)))))
+        # per image: every value an integer in [0, 255]?  (what SIFT emits)
+        row_ok = ((rows == rows.round()) & (rows >= 0) & (rows <= 255)).all(dim=1)
+        csum = torch.zeros(rows.shape[0] + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(row_ok.to(torch.int64), 0, out=csum[1:])
+        tp = torch.from_numpy(ptr).to(dev)
+        img_ok = ((csum[tp[1:]] - csum[tp[:-1]]) == (tp[1:] - tp[:-1])).cpu().numpy()
+        exact = [k for k, (a, b) in enumerate(seg) if img_ok[a] and img_ok[b]]
+        other = [k for k, (a, b) in enumerate(seg) if not (img_ok[a] and img_ok[b])]
+        if exact:
+            groups.append((rows.to(torch.uint8), _lib.METRIC_L2_U8, exact))     # rows of other images are never read by this group
+        if other:
+            groups.append((rows, _lib.METRIC_L2_F32, other))
+    elif code == _lib.METRIC_L2_F32:
+        groups.append((rows.float(), code, everything))
+    else:
+        groups.append((rows, code, everything))
     for grows, code, pos in groups:
         for k, res in zip(pos, _run_batch(h, dev, grows, ptr, code, dim, [seg[k] for k in pos], ratio)):
             out[live[k]] = res

@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._lib import dp as _dp
 
 MAX_COUNT = 0x7FFFFFFF
 
@@ -89,10 +90,6 @@ class MeshComponents:
             raise ValueError("k must be an integer >= 0")
         order = np.argsort(-self.n_triangles.astype(np.int64), kind="stable")
         return [int(c) for c in order[:k]]
-
-
-def _dp(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _components(dev, n_vertices, n_triangles, d_triangles):

@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._lib import dp as _dp
 from .mesh_clean import _up, _whole, check_clean_arguments
 
 MAX_EDGES = 64
@@ -74,10 +75,6 @@ class MeshEdges:
             ok = ((tri >= 0) & (tri < self.n_mesh_vertices)).all(axis=1)
             self._host["euler"] = int(len(np.unique(tri[ok])) - self.n_edges + int(ok.sum()))
         return self._host["euler"]
-
-
-def _dp(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _edges(dev, n_vertices, n_triangles, d_triangles, host_triangles):

@@ -354,7 +354,10 @@ def test_matcher_plan_under_address_and_ub_sanitizers(tmp_path):
     """sfm_amd/csrc/match_plan.h (how a batch of image pairs is cut into workgroup pieces, how many train splits and
     which uint8 distance kernel a launch takes) is plain C++: built here with g++ -fsanitize=address,undefined and driven over random segment tables
     (empty images, images around the 512-row split limit, large ones).  Found on its first run: a division by zero for a
-    segment without train rows in sfm_match_batched_workspace_bytes, which validates nothing before it plans."""
+    segment without train rows in sfm_match_batched_workspace_bytes, which validates nothing before it plans.
+    The header also holds the route, the workspace layout, the argument checks and the grids of every matcher entry point; the
+    same program replays those: layouts over a grid of sizes against the totals of the layout they replaced, the sizing calls
+    against the calls they size, every refusal and its firing order."""
     import shutil, subprocess
     if shutil.which("g++") is None:
         pytest.skip("no g++")

@@ -352,3 +352,189 @@ def test_batched_pairs_vs_oracle_and_degenerate_sizes(gpu_ready):
     got = match_pairs([far_q, far_t, ordinary], [(2, 2), (0, 1), (2, 1)], ratio=2.0)     # ratio 2: every query row is kept
     ref = mo.knn2(far_q, far_t, "l2")
     assert np.array_equal(got[1][1], ref[0]) and np.array_equal(got[1][2], ref[2]) and len(got[1][0]) == 40
+
+
+# ------------------------------------------------------------------ the C ABI at the edge of its workspace and of its arguments
+ROUTES = [("l2_u8", 32), ("l2_u8", 64), ("l2_u8", 128), ("l2_f32", 32), ("l2_f32", 64), ("l2_f32", 128),
+          ("hamming", 16), ("hamming", 32), ("hamming", 64)]
+_ROUTE_CODE = {"l2_u8": 0, "l2_f32": 1, "hamming": 2}
+_route_cases = {}
+
+
+def _route_case(route, dim, nq, nt):
+    """(queries, train rows, oracle result) of one route and shape: drawn and ranked once."""
+    from oracle import matcher_oracle as mo
+    key = (route, dim, nq, nt)
+    if key not in _route_cases:
+        rng = np.random.default_rng(1000 * dim + nq + _ROUTE_CODE[route])
+        if route == "l2_f32":
+            q, t = rng.random((nq, dim), dtype=np.float32), rng.random((nt, dim), dtype=np.float32)
+        else:
+            q, t = rng.integers(0, 256, size=(nq, dim), dtype=np.uint8), rng.integers(0, 256, size=(nt, dim), dtype=np.uint8)
+        _route_cases[key] = (q, t, mo.knn2(q, t, "hamming" if route == "hamming" else "l2"))
+    return _route_cases[key]
+
+
+def _untouched_outputs(n, dev):
+    from sfm_amd import matcher
+    outs = matcher._knn_outputs(n, dev)
+    for o in outs:
+        o.fill_(-7)
+    return outs
+
+
+def _last_error(h):
+    return h.lib.sfm_last_error(h._h).decode()
+
+
+@pytest.mark.parametrize("nq,nt", [(1, 2), (257, 1025)])
+@pytest.mark.parametrize("route,dim", ROUTES)
+def test_knn2_in_exactly_the_workspace_it_asks_for(gpu_ready, route, dim, nq, nt):
+    """sfm_match_knn2 through the C ABI with exactly the bytes sfm_match_workspace_bytes reports, for every route (uint8 and
+    float32 L2 at dims 32 / 64 / 128, Hamming at 16 / 32 bytes - unpacked to bytes - and at 64), at the smallest shape there
+    is and at 257 x 1025 (two query blocks, two train splits): bit for bit the oracle.  With one byte less the host check
+    refuses the call before anything is launched: the outputs keep what they held."""
+    import ctypes as C
+    import torch
+    from sfm_amd import _lib, matcher
+    h, dev, dp = _lib.get_handle(0), torch.device("cuda", 0), _lib.dp
+    q, t, ref = _route_case(route, dim, nq, nt)
+    dq, dt = torch.from_numpy(q).to(dev), torch.from_numpy(t).to(dev)
+    code = _ROUTE_CODE[route]
+    need = C.c_int64()
+    assert h.lib.sfm_match_workspace_bytes(code, nq, nt, dim, C.byref(need)) == 0
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+    outs = matcher._knn_outputs(nq, dev)
+    assert h.lib.sfm_match_knn2(h._h, code, dp(dq), nq, dp(dt), nt, dim, *[dp(o) for o in outs], dp(ws), need.value) == 0
+    assert_knn_equal([o.cpu().numpy() for o in outs], ref)
+    kept = _untouched_outputs(nq, dev)
+    assert h.lib.sfm_match_knn2(h._h, code, dp(dq), nq, dp(dt), nt, dim, *[dp(o) for o in kept], dp(ws), need.value - 1) == -3
+    assert _last_error(h) == "sfm_match_knn2: workspace too small"
+    torch.cuda.synchronize()
+    assert all(bool((o == -7).all().item()) for o in kept)
+
+
+@pytest.mark.parametrize("route,dim", [("hamming", 32), ("l2_u8", 128)])
+def test_batched_knn2_in_exactly_the_workspace_it_asks_for(gpu_ready, route, dim):
+    """The batched pair of calls on three segments over ONE array for both sides (as match_pairs hands it): a segment without
+    queries, one of 1 x 2 and one of 257 x 1025 that shares its rows with the second.  Hamming at 32 bytes is unpacked (and
+    unpacks the shared array once), uint8 at dim 128 is not.  Exactly the reported bytes: every segment bit for bit the
+    oracle; one byte less: refused on the host, nothing written."""
+    import ctypes as C
+    import torch
+    from oracle import matcher_oracle as mo
+    from sfm_amd import _lib, matcher
+    h, dev, dp, hp = _lib.get_handle(0), torch.device("cuda", 0), _lib.dp, _lib.hp
+    n_rows = 1026
+    rows = np.random.default_rng(dim).integers(0, 256, size=(n_rows, dim), dtype=np.uint8)
+    q_beg, q_end = np.array([5, 0, 0], np.int64), np.array([5, 1, 257], np.int64)
+    t_beg, t_end = np.array([0, 1, 1], np.int64), np.array([10, 3, 1026], np.int64)
+    code = _ROUTE_CODE[route]
+    d_rows = torch.from_numpy(rows).to(dev)
+    n_out, need = C.c_int64(), C.c_int64()
+    assert h.lib.sfm_match_batched_workspace_bytes(code, 3, hp(q_beg), hp(q_end), hp(t_beg), hp(t_end), n_rows, n_rows,
+                                                   C.byref(n_out), C.byref(need)) == 0
+    assert n_out.value == 258
+    ws = torch.empty(need.value, dtype=torch.uint8, device=dev)
+
+    def call(outs, out_ptr, ws_bytes):
+        return h.lib.sfm_match_knn2_batched(h._h, code, dp(d_rows), n_rows, dp(d_rows), n_rows, dim, 3, hp(q_beg), hp(q_end), hp(t_beg),
+                                            hp(t_end), *[dp(o) for o in outs], dp(out_ptr), dp(ws), ws_bytes)
+    outs = matcher._knn_outputs(258, dev)
+    out_ptr = torch.empty(4, dtype=torch.int64, device=dev)
+    assert call(outs, out_ptr, need.value) == 0
+    assert out_ptr.cpu().tolist() == [0, 0, 1, 258]
+    got = [o.cpu().numpy() for o in outs]
+    for s, first in ((1, 0), (2, 1)):
+        ref = mo.knn2(rows[q_beg[s]:q_end[s]], rows[t_beg[s]:t_end[s]], "hamming" if route == "hamming" else "l2")
+        assert_knn_equal([g[first:first + int(q_end[s] - q_beg[s])] for g in got], ref)
+    kept = _untouched_outputs(258, dev)
+    kept_ptr = torch.full((4,), -7, dtype=torch.int64, device=dev)
+    assert call(kept, kept_ptr, need.value - 1) == -3
+    assert _last_error(h) == "sfm_match_knn2_batched: workspace too small"
+    torch.cuda.synchronize()
+    assert all(bool((o == -7).all().item()) for o in kept) and bool((kept_ptr == -7).all().item())
+
+
+def _refusals():
+    """(id, entry point, changed arguments, return code, text of sfm_last_error): every refusal of the matcher's argument
+    checks that a caller of the C ABI can reach, each from a valid call with one argument (where a case says so, two) made bad."""
+    many = 0x7FFFFF01
+    out = []
+    knn2, batched = "sfm_match_knn2", "sfm_match_knn2_batched"
+    for name in ("q", "t", "idx1", "idx2", "d1", "d2", "ws"):
+        out.append((f"knn2-null-{name}", knn2, {name: None}, -1, "sfm_match_knn2: null pointer"))
+    out += [("knn2-nq-0", knn2, {"nq": 0}, -1, "sfm_match_knn2: needs nq >= 1 and nt >= 2"),
+            ("knn2-nt-1", knn2, {"nt": 1}, -1, "sfm_match_knn2: needs nq >= 1 and nt >= 2"),
+            ("knn2-nq-many", knn2, {"nq": many}, -1, "sfm_match_knn2: too many rows"),
+            ("knn2-nt-many", knn2, {"nt": many}, -1, "sfm_match_knn2: too many rows"),
+            ("knn2-u8-dim", knn2, {"metric": 0, "dim": 96}, -1, "sfm_match_knn2: L2_U8 needs dim 32, 64 or 128"),
+            ("knn2-f32-dim", knn2, {"metric": 1, "dim": 16}, -1, "sfm_match_knn2: L2_F32 supports dim 32, 64, 128"),
+            ("knn2-hamming-dim", knn2, {"metric": 2, "dim": 128}, -1, "sfm_match_knn2: HAMMING supports dim 16, 32, 64 bytes"),
+            ("knn2-metric", knn2, {"metric": 3}, -1, "sfm_match_knn2: unknown metric"),
+            ("knn2-null-before-rows", knn2, {"q": None, "nq": 0}, -1, "sfm_match_knn2: null pointer"),
+            ("knn2-rows-before-metric", knn2, {"nt": 1, "metric": 3}, -1, "sfm_match_knn2: needs nq >= 1 and nt >= 2"),
+            ("knn2-workspace", knn2, {"ws_bytes": 1}, -3, "sfm_match_knn2: workspace too small")]
+    for name in ("q", "t", "idx1", "idx2", "d1", "d2", "ws", "q_beg", "q_end", "t_beg", "t_end"):
+        out.append((f"batched-null-{name}", batched, {name: None}, -1, "sfm_match_knn2_batched: null pointer / no segments"))
+    out += [("batched-n_seg-0", batched, {"n_seg": 0}, -1, "sfm_match_knn2_batched: null pointer / no segments"),
+            ("batched-u8-dim", batched, {"metric": 0, "dim": 16}, -1, "sfm_match_knn2_batched: L2_U8 needs dim 32, 64 or 128"),
+            ("batched-f32-dim", batched, {"metric": 1, "dim": 256}, -1, "sfm_match_knn2_batched: L2_F32 supports dim 32, 64, 128"),
+            ("batched-hamming-dim", batched, {"metric": 2, "dim": 48}, -1, "sfm_match_knn2_batched: HAMMING supports dim 16, 32, 64 bytes"),
+            ("batched-metric", batched, {"metric": -1}, -1, "sfm_match_knn2_batched: unknown metric"),
+            ("batched-nq-many", batched, {"nq_rows": many}, -1, "sfm_match_knn2_batched: too many rows"),
+            ("batched-nt-many", batched, {"nt_rows": many}, -1, "sfm_match_knn2_batched: too many rows"),
+            ("batched-metric-before-rows", batched, {"metric": 5, "nt_rows": many}, -1, "sfm_match_knn2_batched: unknown metric"),
+            ("batched-q_beg-negative", batched, {"q_beg": [4, -1, 4]}, -1, "sfm_match_knn2_batched: segment outside the descriptor arrays"),
+            ("batched-q_end-past-rows", batched, {"q_end": [4, 4, 11]}, -1, "sfm_match_knn2_batched: segment outside the descriptor arrays"),
+            ("batched-q_end-before-q_beg", batched, {"q_end": [3, 4, 10]}, -1, "sfm_match_knn2_batched: segment outside the descriptor arrays"),
+            ("batched-t_beg-negative", batched, {"t_beg": [0, -1, 0]}, -1, "sfm_match_knn2_batched: segment outside the descriptor arrays"),
+            ("batched-t_end-past-rows", batched, {"t_end": [4, 11, 2]}, -1, "sfm_match_knn2_batched: segment outside the descriptor arrays"),
+            ("batched-one-train-row", batched, {"t_end": [4, 10, 1]}, -1,
+             "sfm_match_knn2_batched: a segment with queries needs at least 2 train rows"),
+            ("batched-outside-before-train-rows", batched, {"q_beg": [4, -1, 4], "t_end": [4, 10, 1]}, -1,
+             "sfm_match_knn2_batched: segment outside the descriptor arrays"),
+            ("batched-no-queries", batched, {"n_seg": 1}, -1, "sfm_match_knn2_batched: no query rows"),
+            ("batched-workspace", batched, {"ws_bytes": 1}, -3, "sfm_match_knn2_batched: workspace too small")]
+    for name in ("idx1", "d1", "d2", "query_idx", "train_idx", "dist", "n_matches", "ws"):
+        out.append((f"ratio-null-{name}", "sfm_match_ratio", {name: None}, -1, "sfm_match_ratio: bad argument"))
+    out += [("ratio-nq-0", "sfm_match_ratio", {"nq": 0}, -1, "sfm_match_ratio: bad argument"),
+            ("ratio-workspace", "sfm_match_ratio", {"ws_bytes": 15}, -3, "sfm_match_ratio: workspace too small"),
+            ("ratio_batched-null-out_ptr", "sfm_match_ratio_batched", {"out_ptr": None}, -1, "sfm_match_ratio_batched: bad argument"),
+            ("ratio_batched-null-seg_match_ptr", "sfm_match_ratio_batched", {"seg_match_ptr": None}, -1, "sfm_match_ratio_batched: bad argument"),
+            ("ratio_batched-n_seg-0", "sfm_match_ratio_batched", {"n_seg": 0}, -1, "sfm_match_ratio_batched: bad argument"),
+            ("ratio_batched-workspace", "sfm_match_ratio_batched", {"ws_bytes": 79}, -3, "sfm_match_ratio_batched: workspace too small"),
+            ("ratio_batched-null-idx1", "sfm_match_ratio_batched", {"idx1": None}, -1, "sfm_match_ratio: bad argument"),
+            ("f32_to_u8-null-src", "sfm_match_f32_to_u8", {"src": None}, -1, "sfm_match_f32_to_u8: bad argument"),
+            ("f32_to_u8-null-dst", "sfm_match_f32_to_u8", {"dst": None}, -1, "sfm_match_f32_to_u8: bad argument"),
+            ("f32_to_u8-null-flag", "sfm_match_f32_to_u8", {"all_integral": None}, -1, "sfm_match_f32_to_u8: bad argument"),
+            ("f32_to_u8-n-0", "sfm_match_f32_to_u8", {"n_elems": 0}, -1, "sfm_match_f32_to_u8: bad argument")]
+    return out
+
+
+@pytest.mark.parametrize("entry,changed,code,text", [pytest.param(*r[1:], id=r[0]) for r in _refusals()])
+def test_refusals_keep_their_code_and_text(gpu_ready, entry, changed, code, text):
+    """Every argument refusal of the matcher's entry points: its return code and, character for character, the text
+    sfm_last_error gives.  All are decided on the host before any launch, so one small buffer stands for every array."""
+    import torch
+    from sfm_amd import _lib
+    h, dev = _lib.get_handle(0), torch.device("cuda", 0)
+    buf = torch.zeros(1 << 16, dtype=torch.uint8, device=dev)
+    p, big = _lib.dp(buf), 1 << 16
+    # rows 0 .. 9 of one array: a segment without queries, 4 x 6 and 6 x 2
+    segs = {"q_beg": [4, 0, 4], "q_end": [4, 4, 10], "t_beg": [0, 4, 0], "t_end": [4, 10, 2]}
+    valid = {
+        "sfm_match_knn2": dict(metric=0, q=p, nq=1, t=p, nt=2, dim=128, idx1=p, idx2=p, d1=p, d2=p, ws=p, ws_bytes=big),
+        "sfm_match_knn2_batched": dict(metric=2, q=p, nq_rows=10, t=p, nt_rows=10, dim=32, n_seg=3, **segs, idx1=p, idx2=p, d1=p, d2=p,
+                                       out_ptr=p, ws=p, ws_bytes=big),
+        "sfm_match_ratio": dict(nq=257, idx1=p, d1=p, d2=p, ratio=0.75, query_idx=p, train_idx=p, dist=p, n_matches=p, ws=p, ws_bytes=big),
+        "sfm_match_ratio_batched": dict(n_out=257, n_seg=1, out_ptr=p, idx1=p, d1=p, d2=p, ratio=0.75, query_idx=p, train_idx=p, dist=p,
+                                        seg_match_ptr=p, ws=p, ws_bytes=big),
+        "sfm_match_f32_to_u8": dict(src=p, n_elems=4, dst=p, all_integral=p),
+    }[entry]
+    args = {**valid, **changed}
+    keep = [np.array(v, dtype=np.int64) for v in args.values() if isinstance(v, list)]
+    it = iter(keep)
+    rc = getattr(h.lib, entry)(h._h, *[_lib.hp(next(it)) if isinstance(v, list) else v for v in args.values()])
+    assert rc == code
+    assert _last_error(h) == text

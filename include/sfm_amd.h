@@ -1129,7 +1129,7 @@ int sfm_mesh_emit(sfm_handle h, const float* tsdf, int32_t nx, int32_t ny, int32
  *   vertex among the kept ones; vertices (float64 x 3) and normals (float32 x 3) are copied bit for bit.  A mesh of which
  *   everything is kept comes out byte for byte as it went in.
  * Limits: no threshold as a fraction of the largest component, no components by area or bounding box, no removal of
- *   zero-area triangles or non-manifold edges, no hole filling, no decimation.
+ *   zero-area triangles or non-manifold edges, no hole filling, decimation by clustering only: see Decimation.
  *
  * Calls, in the shape of sfm_mesh_mark / sfm_mesh_emit: the host reads a count between them and allocates.
  * sfm_mesh_components: the labels, the per-component tables and counts.  Union-find with "the larger root goes under the
@@ -1238,6 +1238,87 @@ int sfm_mesh_fill_emit(sfm_handle h, int64_t n_vertices, int64_t n_triangles, co
                        const double* vertices, int64_t cap_fill, int64_t cap_triangles, double* fill_vertices,
                        float* fill_normals, int32_t* fill_name, int32_t* fill_triangles, int32_t* fill_triangle_halfedge,
                        void* workspace, int64_t workspace_bytes);
+
+/* ---- decimation of a mesh: vertex clustering on a uniform grid with a quadric-optimal vertex per cell
+ *      (sfm_amd/csrc/mesh_decimate.hip, mesh_decimate_rule.h, mesh_decimate_plan.h) ----
+ * Rossignac-Borrel clustering with Lindstrom's placement.  float64 without FMA contraction, every sum in one stated order,
+ * no float atomics and no order decided by an atomic: every output byte is a function of the inputs, the same from run to
+ * run, and NumPy reproduces it (tests/mesh_decimate_reference.py).
+ *
+ * Input.  n_vertices, 0 .. 2^31 - 1, with vertices float64 [n_vertices][3] and normals float32 [n_vertices][3] or NULL;
+ *   triangles int32 [n_triangles][3] with n_triangles 0 .. (2^31 - 1) / 3; origin, host [3], finite; cell, finite and > 0;
+ *   placement, 0 for the mean and 1 for the quadric.
+ * Cell of a vertex.  Per axis q_a = floor((v_a - origin_a) / cell) in float64.  The vertex is sound iff its three
+ *   coordinates are finite and 0 <= q_a < 2^21 on every axis; its key is then (iz << 42) | (iy << 21) | ix.  An unsound
+ *   vertex has no cell and vertex_cluster = -1.  The comparisons are made on the double: no bit pattern of a coordinate
+ *   becomes an address.
+ * Clusters.  The distinct keys in ascending order are the clusters 0 .. nc - 1, so the order is z-major.  The members of a
+ *   cluster are its vertices in ascending index; cluster_first[c] is the smallest member, so sfm_mesh_gather_rows carries any
+ *   per-vertex array across; cluster_size[c] is the member count.
+ * Mean.  Per coordinate m = (((v_0 + v_1) + ...)) / (double)n over the members in that order.
+ * Normal (when normals are given).  The float32 normals of the members, widened, are summed in the same order; l2 = (x x +
+ *   y y) + z z; each component is divided by sqrt(l2) and rounded once to float32; zeros when l2 is 0 or not finite.
+ * Sound triangle.  Its three indices lie in [0, n_vertices) and its three vertices are sound.
+ * Quadric (placement = 1).  The corners of a cluster c are the h = 3 t + k of sound triangles with
+ *   vertex_cluster[tri[t][k]] == c, in ascending h; a triangle with two corners in the cell counts twice.  For each corner,
+ *   with p0, p1, p2 the triangle's vertices in its own order, whatever k is: e1 = p1 - p0, e2 = p2 - p0, n = (e1y e2z - e1z
+ *   e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), r = p0 - m, s = (nx rx + ny ry) + nz rz; then A00 += nx nx, A01 += nx ny,
+ *   A02 += nx nz, A11 += ny ny, A12 += ny nz, A22 += nz nz and g_a += n_a s, every product rounding on its own.  tr = (A00 +
+ *   A11) + A22, lambda = tr * 2^-6, B = A with lambda added to its diagonal.  B y = g is solved in this order: d0 = B00, l10
+ *   = B01 / d0, l20 = B02 / d0, d1 = B11 - l10 B01, u = B12 - l20 B01, l21 = u / d1, d2 = (B22 - l20 B02) - l21 u, z1 = g1
+ *   - l10 g0, z2 = (g2 - l20 g0) - l21 z1, y2 = z2 / d2, y1 = z1 / d1 - l21 y2, y0 = (g0 / d0 - l10 y1) - l20 y2.  x = m +
+ *   y.  The position is x iff tr > 0, d0 > 0, d1 > 0, d2 > 0, x is finite and lo_a <= x_a <= hi_a on every axis, with lo_a
+ *   = origin_a + cell * (double)i_a and hi_a = origin_a + cell * (double)(i_a + 1); otherwise it is m.  cluster_placed[c]
+ *   (uint8) says which was taken.  The regularisation pulls towards the mean, so a flat cell moves along its normal only
+ *   and no eigen-decomposition is needed.
+ * New triangles.  A sound triangle maps to (c0, c1, c2); it is degenerate when two of them are equal.  The others are
+ *   grouped by their sorted triple; within a group E are those whose order is an even permutation of the sorted triple and
+ *   O the odd ones.  If |E| > |O| the first of E in old triangle order is kept, if |O| > |E| the first of O, if |E| == |O|
+ *   none: clustering folds small fins flat, and two triangles on one triple with opposite orientation cancel.  Kept triangles
+ *   stay in old order; triangle_map[t'] is the old index.  Every cluster is an output vertex, referenced or not.
+ * Limits: decimation by clustering only.  The grid is uniform: no adaptation to curvature, no target triangle count;
+ *   features thinner than a cell pinch into non-manifold edges, which sfm_mesh_edges reports; unreferenced clusters stay as
+ *   vertices until the mesh is cleaned; boundaries shrink towards the cell means; a run of r equal triples costs its head
+ *   lane r steps; there is no edge-collapse refinement afterwards.
+ *
+ * Calls, in the shape of sfm_mesh_fill_mark / sfm_mesh_fill_emit: the host reads a count between them and allocates.  ONE
+ * workspace (sfm_mesh_decimate_workspace_bytes, which takes the handle because it sizes the library's radix sorts on its
+ * device) goes through the three calls untouched: it carries the vertices sorted by cell, the corners sorted by cluster and
+ * the first slots of every block of kept triangles from one call to the next.
+ * sfm_mesh_decimate_cluster: keys, one stable sort of (key, vertex) - over 64 bits: the 64th keeps the vertices without a
+ *   cell apart from the last cell of the grid -, run heads, block counts and the two-level scan; writes vertex_cluster int32
+ *   [n_vertices], and of cluster_start (int32; the caller provides n_vertices + 1 entries; positions in the sorted vertex
+ *   list) the first nc + 1 entries, of cluster_first and cluster_size (int32; n_vertices entries each) the first nc; counts,
+ *   device int64 [2]: clusters, unsound vertices.
+ * sfm_mesh_decimate_mark: takes n_clusters and vertex_cluster of that call; a stable sort of (cluster, h) over the bits
+ *   n_clusters needs gives the corner list of every cluster; the non-degenerate triangles are sorted by (triple, t), in one
+ *   pass when three cluster numbers fit 63 bits and in two stable passes otherwise, the output bytes being the same either
+ *   way; the head of every run of equal triples applies the duplicate rule.  Writes triangle_keep uint8 [n_triangles];
+ *   counts, device int64 [5]: kept triangles, unsound triangles, degenerate triangles, triangles dropped by the duplicate
+ *   rule, status (1 when vertex_cluster holds a number outside -1 .. n_clusters - 1: such a triangle counts as unsound).
+ * sfm_mesh_decimate_emit: takes the same tables and the capacities of the outputs: new_vertices float64 [cap_clusters][3],
+ *   new_normals float32 [cap_clusters][3] (not written, and may be NULL, when normals is NULL), cluster_placed uint8
+ *   [cap_clusters], new_triangles int32 [cap_triangles][3] and triangle_map int32 [cap_triangles].  One lane per cluster
+ *   walks its members and its corners in the rule's order.  It writes nothing at or above the capacities and returns at once
+ *   when both are 0.
+ * Every call returns SFM_ERR_ARG before any device work for a null handle, n_vertices outside 0 .. 2^31 - 1, n_triangles
+ * outside 0 .. (2^31 - 1) / 3, n_clusters outside 0 .. n_vertices, a capacity below 0 or above 2^31 - 1, placement outside
+ * 0 .. 1, an origin that is not finite, a cell that is not finite or <= 0, a null pointer (allowed only where its count is
+ * 0), or a workspace that is missing or too small. */
+int sfm_mesh_decimate_workspace_bytes(sfm_handle h, int64_t n_vertices, int64_t n_triangles, int64_t* bytes_host);
+int sfm_mesh_decimate_cluster(sfm_handle h, int64_t n_vertices, int64_t n_triangles, const double* vertices,
+                              const double* origin /* host [3] */, double cell, int32_t* vertex_cluster, int32_t* cluster_start,
+                              int32_t* cluster_first, int32_t* cluster_size, int64_t* counts /* device [2] */, void* workspace,
+                              int64_t workspace_bytes);
+int sfm_mesh_decimate_mark(sfm_handle h, int64_t n_vertices, int64_t n_triangles, int64_t n_clusters, const int32_t* triangles,
+                           const int32_t* vertex_cluster, uint8_t* triangle_keep, int64_t* counts /* device [5] */,
+                           void* workspace, int64_t workspace_bytes);
+int sfm_mesh_decimate_emit(sfm_handle h, int64_t n_vertices, int64_t n_triangles, int64_t n_clusters, const double* vertices,
+                           const float* normals, const int32_t* triangles, const int32_t* vertex_cluster,
+                           const int32_t* cluster_start, const uint8_t* triangle_keep, const double* origin /* host [3] */,
+                           double cell, int placement, int64_t cap_clusters, int64_t cap_triangles, double* new_vertices,
+                           float* new_normals, uint8_t* cluster_placed, int32_t* new_triangles, int32_t* triangle_map,
+                           void* workspace, int64_t workspace_bytes);
 
 /* ---- colours of the mesh: per vertex a blend over the views that see it (sfm_amd/csrc/mesh_color.hip,
  *      mesh_color_rule.h, mesh_color_plan.h) ----

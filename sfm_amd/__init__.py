@@ -16,4 +16,5 @@ from .mesh import (Mesh, MeshRender, MeshTexture, RenderScore, TsdfVolume, check
                    score_render, tsdf_volume_from_arrays)
 from .mesh_clean import MeshComponents, check_clean_arguments, clean_mesh, mesh_components  # noqa: F401
 from .mesh_fill import MeshEdges, check_fill_arguments, fill_mesh_holes, mesh_edges  # noqa: F401
+from .mesh_decimate import check_decimate_arguments, decimate_mesh  # noqa: F401
 from .exposure import ExposureGains, apply_gains, check_exposure_arguments, mesh_exposure_tables, solve_gains  # noqa: F401

@@ -210,7 +210,11 @@ SIGNATURES = {
     "sfm_mesh_fill_workspace_bytes": (C.c_int, [i64, C.POINTER(i64)]),
     "sfm_mesh_fill_mark": (C.c_int, [vp, i64, i64, vp, vp, i64, vp, i64, vp, vp, vp, i64]),
     "sfm_mesh_fill_emit": (C.c_int, [vp, i64, i64, vp, vp, i64, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, i64]),
-    "sfm_mesh_colors_workspace_bytes": (C.c_int, [i32, C.POINTER(i64)]),
+    "sfm_mesh_decimate_workspace_bytes": (C.c_int, [vp, i64, i64, C.POINTER(i64)]),
+    "sfm_mesh_decimate_cluster": (C.c_int, [vp, i64, i64, vp, vp, f64, vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_mesh_decimate_mark": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, vp, vp, i64]),
+    "sfm_mesh_decimate_emit": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, f64, C.c_int, i64, i64, vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_mesh_colors_workspace_bytes":(C.c_int, [i32, C.POINTER(i64)]),
     "sfm_mesh_colors": (C.c_int, [vp, *VIEW_SOURCE, i64, vp, vp, f64, f64, i32, vp, vp, vp, vp, i64]),
     "sfm_mesh_exposure_workspace_bytes": (C.c_int, [i32, i32, i64, C.POINTER(i64)]),
     "sfm_mesh_exposure_plan": (C.c_int, [i32, i32, i64, C.POINTER(i32)]),

@@ -9,7 +9,9 @@ any camera: depth, triangle, barycentrics and colour per pixel; `sfm_render_scor
 render against the photographs: error, PSNR and SSIM sums and the distance to the views' own depth.  `Mesh.exposure`
 (sfm_amd/exposure.py) estimates one gain per view and channel for images whose exposure differs, to be applied before they go
 to the colour calls.  `Mesh.components` and `Mesh.clean` (sfm_amd/mesh_clean.py; `sfm_mesh_components`, `sfm_mesh_clean_mark` /
-`sfm_mesh_clean_emit`, sfm_amd/csrc/mesh_clean.hip) label the connected components of the mesh and remove the small ones.  No
+`sfm_mesh_clean_emit`, sfm_amd/csrc/mesh_clean.hip) label the connected components of the mesh and remove the small ones.
+`Mesh.decimate` (sfm_amd/mesh_decimate.py; `sfm_mesh_decimate_cluster`, `sfm_mesh_decimate_mark` / `sfm_mesh_decimate_emit`,
+sfm_amd/csrc/mesh_decimate.hip) clusters the vertices on a uniform grid and places one vertex per cell by its quadric.  No
 CPU fallback: without the library or a GPU the calls raise.
 """
 from __future__ import annotations
@@ -67,7 +69,8 @@ class Mesh:
     vertex_colors = property(lambda self: self._get("vertex_colors", self.n_vertices))
     n_views = property(lambda self: self._get("n_views", self.n_vertices))
     best_view = property(lambda self: self._get("best_view", self.n_vertices))
-    # on what clean() returns: int32 [nv] / [nt], the index each vertex / triangle had in the mesh it was cleaned from; None otherwise
+    # on what clean() returns: int32 [nv] / [nt], the index each vertex / triangle had in the mesh it was cleaned from; on what
+    # decimate() returns: triangle_map alone, likewise; None otherwise
     vertex_map = property(lambda self: self._get("vertex_map", self.n_vertices))
     triangle_map = property(lambda self: self._get("triangle_map", self.n_triangles))
     components_before = None                                       # on what clean() returns: the `MeshComponents` it used
@@ -114,6 +117,31 @@ class Mesh:
         max_edges edges is closed too, so clean() first.  This mesh is untouched."""
         from .mesh_fill import fill_holes
         return fill_holes(self, max_edges, edges)
+
+    # on what decimate() returns: the vertices of the mesh it was made from, how many of them and of its triangles were
+    # unsound, how many triangles had two corners in one cell, how many the duplicate rule dropped, the grid; None otherwise
+    n_source_vertices = n_unsound_vertices = n_unsound_triangles = n_degenerate = n_cancelled = cell = origin = None
+    # int32 [n_source_vertices]: the cluster of each old vertex (-1: unsound); per new vertex int32 its smallest member, int32
+    # its member count, uint8 whether the quadric placed it (0: the mean); None otherwise
+    vertex_cluster = property(lambda self: self._get("vertex_cluster", self.n_source_vertices))
+    cluster_first = property(lambda self: self._get("cluster_first", self.n_vertices))
+    cluster_size = property(lambda self: self._get("cluster_size", self.n_vertices))
+    cluster_placed = property(lambda self: self._get("cluster_placed", self.n_vertices))
+
+    def decimate(self, cell=None, factor=2.0, origin=None, placement="quadric"):
+        """A new `Mesh` with fewer triangles (`sfm_mesh_decimate_cluster`, `sfm_mesh_decimate_mark`, `sfm_mesh_decimate_emit`;
+        include/sfm_amd.h states the rule): the vertices are clustered by the cells of a uniform grid of side cell (None:
+        factor times the voxel of the mesh's volume) from origin (None: the per-axis minimum of the finite coordinates; the
+        extent over cell must then stay below 2^21), every cell becomes one vertex - placement "quadric": where the planes
+        of the triangles at the cell meet, kept inside the cell; "mean": the mean of its members -, a triangle stays when its
+        vertices land in three cells, and of those on one triple of cells the first of the prevailing orientation, none on a
+        tie.  The result carries vertex_cluster, cluster_first, cluster_size, cluster_placed, triangle_map, n_degenerate,
+        n_cancelled, n_unsound_vertices, n_unsound_triangles, cell and origin; the volume is carried over; vertex_colors,
+        n_views, best_view and atlas are None, so call colors() or texture() again.  Thin features pinch into non-manifold
+        edges, which edges() reports; cells that no kept triangle uses stay as vertices until clean().  This mesh is
+        untouched."""
+        from .mesh_decimate import decimate
+        return decimate(self, cell, factor, origin, placement)
 
     def _views(self, what, maps, images=None, arrays_too=False):
         """The `ViewSet` of a per-view call, with the pixels of images where they are given: that of `maps`, None for the one
@@ -954,3 +982,4 @@ def score_render(color, triangle, depth, photos, view_depth=None, view_keep=None
 
 from .mesh_clean import MeshComponents, check_clean_arguments, clean_mesh, mesh_components  # noqa: E402,F401
 from .mesh_fill import MeshEdges, check_fill_arguments, fill_mesh_holes, mesh_edges  # noqa: E402,F401
+from .mesh_decimate import check_decimate_arguments, decimate_mesh  # noqa: E402,F401

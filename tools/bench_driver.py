@@ -1215,6 +1215,99 @@ def measure_mesh_fill(h, dev, nv, nt, triangles, vertices, reps=20, fan=1 << 20)
     return out
 
 
+def measure_mesh_decimate(h, dev, nv, nt, triangles, vertices, vnormals, voxel, view_args, render_args, reps=20):
+    """sfm_mesh_decimate_cluster, sfm_mesh_decimate_mark and sfm_mesh_decimate_emit on a mesh that is resident on the device, at
+    cells of 2 and 4 voxels from the per-axis minimum of the vertices, with the mean and with the quadric: whole calls by HIP
+    events around `reps` calls after 3 warm-up calls, with the counts they report.  The yardstick is ms_mesh_edges of the same
+    row, one radix sort of 3 nt keys.  Then what the feature buys: sfm_mesh_texture (texels 8) and sfm_mesh_render of the mesh
+    decimated at factor 2 with the quadric, beside ms_mesh_texture and ms_mesh_render of the full mesh in the same row.
+    view_args: the arguments of sfm_mesh_texture up to the channel count; render_args: (n_img, heights, widths, d_proj, n_out)."""
+    import torch
+    from sfm_amd import mesh as mm
+    from sfm_amd.driver import _p
+    hp = lambda a: C.c_void_p(a.ctypes.data)
+    need = C.c_int64()
+    h.call("sfm_mesh_decimate_workspace_bytes", nv, nt, C.byref(need))
+    ws_bytes = need.value
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    per = lambda n: torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    vc, start, first, size = per(nv), per(nv + 1), per(nv), per(nv)
+    keep = torch.empty(max(nt, 1), dtype=torch.uint8, device=dev)
+    counts, marks = torch.empty(2, dtype=torch.int64, device=dev), torch.empty(5, dtype=torch.int64, device=dev)
+    origin = np.ascontiguousarray(vertices[:nv].amin(0).cpu().numpy(), dtype=np.float64) if nv else np.zeros(3)
+    out = {"decimate_workspace_bytes": ws_bytes}
+    kept_mesh = None
+    for factor in (2, 4):
+        cell = float(factor) * voxel
+
+        def run_cluster():
+            h.call("sfm_mesh_decimate_cluster", nv, nt, _p(vertices), hp(origin), C.c_double(cell), _p(vc), _p(start), _p(first), _p(size), _p(counts), _p(ws),
+                   ws_bytes)
+        for _ in range(3):
+            run_cluster()
+        nc, bad = (int(c) for c in counts.cpu().numpy())
+
+        def run_mark():
+            h.call("sfm_mesh_decimate_mark", nv, nt, nc, _p(triangles), _p(vc), _p(keep), _p(marks), _p(ws), ws_bytes)
+        for _ in range(3):
+            run_mark()
+        kept, unsound, degenerate, dropped, status = (int(c) for c in marks.cpu().numpy())
+        v2 = torch.empty((max(nc, 1), 3), dtype=torch.float64, device=dev)
+        n2 = torch.empty((max(nc, 1), 3), dtype=torch.float32, device=dev)
+        placed = torch.empty(max(nc, 1), dtype=torch.uint8, device=dev)
+        t2 = torch.empty((max(kept, 1), 3), dtype=torch.int32, device=dev)
+        tmap = per(kept)
+        key = f"decimate_{factor}"
+        out.update({f"ms_{key}_cluster": timed(run_cluster, reps) * 1e3, f"ms_{key}_mark": timed(run_mark, reps) * 1e3, f"{key}_clusters": nc,
+                    f"{key}_triangles": kept, f"{key}_degenerate": degenerate, f"{key}_cancelled": dropped, f"{key}_unsound_vertices": bad,
+                    f"{key}_unsound_triangles": unsound, f"{key}_status": status})
+        for placement, name in ((0, "mean"), (1, "quadric")):
+            def run_emit():
+                h.call("sfm_mesh_decimate_emit", nv, nt, nc, _p(vertices), _p(vnormals), _p(triangles), _p(vc), _p(start), _p(keep), hp(origin),
+                       C.c_double(cell), placement, nc, kept, _p(v2), _p(n2), _p(placed), _p(t2), _p(tmap), _p(ws), ws_bytes)
+            for _ in range(3):
+                run_emit()
+            out[f"ms_{key}_emit_{name}"] = timed(run_emit, reps) * 1e3
+        out[f"{key}_placed_by_quadric"] = int(placed[:nc].sum().item())
+        out[f"ms_{key}_quadric"] = out[f"ms_{key}_cluster"] + out[f"ms_{key}_mark"] + out[f"ms_{key}_emit_quadric"]
+        if factor == 2:
+            kept_mesh = (nc, kept, v2, n2, t2)
+    # the texture and the render of the mesh decimated at factor 2 (the quadric's vertices are the last ones written)
+    nc, kept, v2, n2, t2 = kept_mesh
+    texels, cells_per_row, aw, ah = 8, mm.check_texture_layout(kept, 8, None)[0], C.c_int32(), C.c_int32()
+    h.check(h.lib.sfm_mesh_texture_size(kept, texels, cells_per_row, C.byref(aw), C.byref(ah)), "sfm_mesh_texture_size")
+    aw, ah = aw.value, ah.value
+    n_img, heights, widths, d_proj, n_out = render_args
+    h.check(h.lib.sfm_mesh_texture_workspace_bytes(n_img, C.byref(need)), "sfm_mesh_texture_workspace_bytes")
+    texture_need = need.value
+    texture_ws = torch.empty(texture_need, dtype=torch.uint8, device=dev)
+    atlas = torch.empty(max(ah * aw * 3, 1), dtype=torch.uint8, device=dev)
+    aviews = torch.empty(max(ah * aw, 1), dtype=torch.uint8, device=dev)
+    auv = torch.empty(max(kept * 6, 1), dtype=torch.float32, device=dev)
+
+    def run_texture():
+        h.call("sfm_mesh_texture", *view_args, nc, _p(v2), _p(n2), kept, _p(t2), texels, cells_per_row, C.c_double(3.0 * voxel), C.c_double(0.35), 0,
+               _p(atlas), _p(aviews), _p(auv), _p(texture_ws), texture_need)
+    for _ in range(3):
+        run_texture()
+    h.check(h.lib.sfm_mesh_render_workspace_bytes(n_img, hp(heights), hp(widths), nc, kept, C.byref(need)), "sfm_mesh_render_workspace_bytes")
+    render_need = need.value
+    render_ws = torch.empty(render_need, dtype=torch.uint8, device=dev)
+    r_depth = torch.empty(n_out, dtype=torch.float32, device=dev)
+    r_tri = torch.empty(n_out, dtype=torch.int32, device=dev)
+    r_bary = torch.empty(n_out * 3, dtype=torch.float32, device=dev)
+    r_color = torch.empty(n_out * 3, dtype=torch.uint8, device=dev)
+
+    def run_render():
+        h.call("sfm_mesh_render", n_img, hp(heights), hp(widths), _p(d_proj), nc, _p(v2), kept, _p(t2), 2, 3, None, _p(auv), _p(atlas), aw, ah, 0,
+               _p(r_depth), _p(r_tri), _p(r_bary), _p(r_color), _p(render_ws), render_need)
+    for _ in range(3):
+        run_render()
+    out.update({"decimate_2_texture_atlas": [aw, ah], "ms_decimate_2_mesh_texture": timed(run_texture, reps) * 1e3,
+                "ms_decimate_2_mesh_render": timed(run_render, reps) * 1e3, "decimate_2_render_share_of_pixels_drawn": float((r_tri >= 0).float().mean().item())})
+    return out
+
+
 def measure_depth(reps=20, emit=None, mesh=False):
     """sfm_depth_census, sfm_depth_sweep and sfm_depth_filter on 36 synthetic 1024 x 768 views (the scene generator of
     tests/depth_reference.py: cameras on a line, baseline 0.1, f = 1228), every view a reference with its 4 nearest cameras
@@ -1234,7 +1327,9 @@ def measure_depth(reps=20, emit=None, mesh=False):
     at min_triangles 100 (sfm_mesh_components, sfm_mesh_clean_mark, sfm_mesh_clean_emit) and sfm_mesh_components on the ascending strip
     at 2^20 and 2^22 vertices with the ratio of the two times (`measure_mesh_clean`), then the edge table of that mesh and the filling of
     its holes at max_edges 16 (sfm_mesh_edges, sfm_mesh_fill_mark, sfm_mesh_fill_emit) and sfm_mesh_edges on a fan and on a strip of 2^20
-    triangles (`measure_mesh_fill`), whole calls by HIP events; the row is then named "mesh"."""
+    triangles (`measure_mesh_fill`), then the decimation of that mesh at cells of 2 and 4 voxels with both placements (sfm_mesh_decimate_cluster,
+    sfm_mesh_decimate_mark, sfm_mesh_decimate_emit) and sfm_mesh_texture and sfm_mesh_render of the decimated mesh (`measure_mesh_decimate`),
+    whole calls by HIP events; the row is then named "mesh"."""
     import torch
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from depth_reference import make_scene
@@ -1486,7 +1581,12 @@ def measure_depth(reps=20, emit=None, mesh=False):
         # and the cleaning above are their yardsticks.  Then the table alone on a fan of 2^20 triangles about one vertex and
         # on a strip of as many: the sort keeps the fan near the strip.
         row.update(measure_mesh_fill(h, dev, nv, nt, triangles, vertices, reps))
-        zv = vertices[:nv, 2].cpu().numpy()
+        # the decimation of the same mesh at cells of 2 and 4 voxels, both placements, whole calls, 20 after 3; the edge table
+        # above is the yardstick.  Then the texture and the render of the decimated mesh beside those of the full one above.
+        row.update(measure_mesh_decimate(h, dev, nv, nt, triangles, vertices, vnormals, float(voxel),
+                                         (hp(heights), hp(widths), n_img, n_img, hp(ref_image), _p(d_proj), _p(d_centres), _p(depth), _p(keep), _p(d_bgr), 3),
+                                         (n_img, heights, widths, d_proj, n_out), reps))
+        zv =vertices[:nv, 2].cpu().numpy()
         seen = int((weight != 0).sum().item())
         row.update({"grid_nodes": [nx, ny, nz], "voxel": float(voxel), "nodes_seen": seen, "projections": nx * ny * nz * n_img,
                     "mesh_vertices": nv, "mesh_triangles": nt,
@@ -1543,7 +1643,7 @@ def main():
     ap.add_argument("--pyramid-only", action="store_true", help="only the multi-scale feature row (beside the single-scale stage on the same images); no other selection runs it")
     ap.add_argument("--guided-only", action="store_true", help="only the guided-matching row (beside the blind matcher)")
     ap.add_argument("--depth-only", action="store_true", help="only the dense-depth row (beside the feature stage on the same images)")
-    ap.add_argument("--mesh-only", action="store_true", help="only the meshing row: TSDF integration, mark and emit beside the sweep and the fusion of the same run, and the stages on that mesh up to its components and cleaning, its edge table and the filling of its holes")
+    ap.add_argument("--mesh-only", action="store_true", help="only the meshing row: TSDF integration, mark and emit beside the sweep and the fusion of the same run, and the stages on that mesh up to its components and cleaning, its edge table, the filling of its holes and its decimation")
     a = ap.parse_args()
     emit = lambda d: print(json.dumps(d), flush=True)
     only = a.fundamental_only or a.essential_only or a.homography_only or a.pnp_only or a.pose_only or a.tracks_only or a.triangulate_only or a.incremental_only or \

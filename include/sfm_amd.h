@@ -1239,6 +1239,69 @@ int sfm_mesh_fill_emit(sfm_handle h, int64_t n_vertices, int64_t n_triangles, co
                        float* fill_normals, int32_t* fill_name, int32_t* fill_triangles, int32_t* fill_triangle_halfedge,
                        void* workspace, int64_t workspace_bytes);
 
+/* ---- smoothing of a mesh: the vertex adjacency, Taubin steps over it, area-weighted vertex normals
+ *      (sfm_amd/csrc/mesh_smooth.hip, mesh_smooth_rule.h, mesh_smooth_plan.h) ----
+ * Taubin's lambda | mu smoothing with uniform weights.  float64 without FMA contraction, every sum in one stated order, no
+ * float atomics and no order decided by an atomic: every output byte is a function of the inputs, the same from run to run,
+ * and NumPy reproduces it (tests/mesh_smooth_reference.py).
+ *
+ * Adjacency (integers only).  Half-edge h = 3 t + k runs from a = tri[t][k] to b = tri[t][(k + 1) % 3].  A triangle is sound
+ *   iff its three indices lie in [0, n_vertices); a half-edge is live iff its triangle is sound and a != b.  uses(a, b) is
+ *   the number of live half-edges on the unordered pair.  The neighbours of v are the distinct other ends of its live
+ *   half-edges in ascending index: index[ptr[v] .. ptr[v + 1]).  vertex_flags bit 0 (boundary) is set iff some neighbour j
+ *   has uses(v, j) != 2 - boundary, non-manifold and doubled edges alike -, bit 1 (isolated) iff v has no neighbour.
+ * State (uint8 per vertex, fixed before the first step).  Bit 0: boundary and pin_boundary.  Bit 1: pinned[v] != 0.  Bit 2:
+ *   unsound, a coordinate of the INPUT is not finite.  Bit 3: isolated.
+ * Step with factor f.  A vertex whose state is not 0 keeps its bytes.  Otherwise, over its neighbours j in ascending order
+ *   whose state has bit 2 clear, per axis s = ((0 + x_j1) + x_j2) + ..., n their number; n == 0 keeps the bytes; otherwise
+ *   m = s / (double)n and x' = x + f * (m - x), the product and the two sums rounding on their own.  Every step reads the
+ *   vertices of the step before only (Jacobi, two buffers).  One iteration is a step with lam, then, when has_mu, one with
+ *   mu; without mu the steps are plain Laplacian.  An unsound vertex is never read as a neighbour and never moves, so one
+ *   NaN does not spread; values that overflow during the steps propagate.  No bit pattern of a coordinate becomes an
+ *   address.
+ * Normals.  The corners of v are the h = 3 t + k of the sound triangles with tri[t][k] == v, in ascending h.  Each adds the
+ *   face normal of its triangle, with p0, p1, p2 its vertices in its own order whatever k is: e1 = p1 - p0, e2 = p2 - p0,
+ *   n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), not normalised, so a triangle weighs with its area; per
+ *   axis ns = ((0 + n_1) + n_2) + ...; l2 = (x x + y y) + z z; each component is divided by sqrt(l2) and rounded once to
+ *   float32; zeros when l2 is 0 or not finite.  A triangle (a, a, b) is sound and adds a zero; the bytes depend on the order
+ *   of the triangles, the direction does not.
+ * Limits: uniform weights - no cotangent or bilateral weights, no feature preservation; a pinned outline stays jagged; a
+ *   vertex of degree d costs its lane d dependent additions, and a run of r equal entries its head lane r steps; the
+ *   normals' bytes depend on the order of the triangles.
+ *
+ * Calls.  Each has a workspace of its own (the _workspace_bytes functions take the handle because two of them size the
+ * library's radix sorts on its device); nothing is read back inside a call.
+ * sfm_mesh_adjacency: the symmetrised keys (a << 32) | b, two per live half-edge and all ones otherwise, ONE keys-only radix
+ *   sort over the 32 + bits(n_vertices) bits they need, run heads, block counts and the two-level scan, a scatter of the
+ *   heads and one lane per vertex.  Writes ptr int32 [n_vertices + 1], of index (int32; the caller provides 6 n_triangles
+ *   elements, the upper bound) the first counts[0], vertex_flags uint8 [n_vertices]; counts, device int64 [4]: entries,
+ *   boundary vertices, isolated vertices, unsound triangles.
+ * sfm_mesh_smooth: takes those tables and n_index, the number of elements of index that may be read (the entries, or the
+ *   capacity).  Enqueues the state kernel and one launch per step back to back on the handle's stream.  Writes vertices_out
+ *   float64 [n_vertices][3] (not vertices_in; with iterations = 0 a copy of it) and vertex_state uint8 [n_vertices];
+ *   counts, device int64 [5]: vertices pinned as boundary, pinned by the caller, unsound, isolated, status.  The status is
+ *   1 when ptr decreases or leaves [0, n_index] or an entry lies outside [0, n_vertices): such a table is not of these
+ *   triangles; the entry is skipped, the vertex with such a ptr keeps its bytes, and neither is ever an address.  The
+ *   workspace holds the second buffer.
+ * sfm_mesh_vertex_normals: one stable sort of (vertex, h) over the bits n_vertices needs, then one lane per vertex.  Writes
+ *   normals float32 [n_vertices][3].
+ * Every call returns SFM_ERR_ARG before any device work for a null handle, n_vertices outside 0 .. 2^31 - 1, n_triangles
+ * outside 0 .. (2^31 - 1) / 6, n_index outside 0 .. 2^31 - 1, iterations outside 0 .. 1000, lam not finite in (0, 1], mu
+ * (when has_mu) not finite in [-2, -lam), vertices_out == vertices_in, a null pointer (allowed only where its count is 0;
+ * pinned may always be NULL), or a workspace that is missing or too small. */
+int sfm_mesh_adjacency_workspace_bytes(sfm_handle h, int64_t n_vertices, int64_t n_triangles, int64_t* bytes_host);
+int sfm_mesh_adjacency(sfm_handle h, int64_t n_vertices, int64_t n_triangles, const int32_t* triangles, int32_t* ptr,
+                       int32_t* index /* capacity 6 n_triangles */, uint8_t* vertex_flags, int64_t* counts /* device [4] */,
+                       void* workspace, int64_t workspace_bytes);
+int sfm_mesh_smooth_workspace_bytes(sfm_handle h, int64_t n_vertices, int64_t* bytes_host);
+int sfm_mesh_smooth(sfm_handle h, int64_t n_vertices, const double* vertices_in, const int32_t* ptr, const int32_t* index,
+                    int64_t n_index, const uint8_t* vertex_flags, const uint8_t* pinned /* or NULL */, int pin_boundary,
+                    double lam, double mu, int has_mu, int64_t iterations, double* vertices_out, uint8_t* vertex_state,
+                    int64_t* counts /* device [5] */, void* workspace, int64_t workspace_bytes);
+int sfm_mesh_vertex_normals_workspace_bytes(sfm_handle h, int64_t n_vertices, int64_t n_triangles, int64_t* bytes_host);
+int sfm_mesh_vertex_normals(sfm_handle h, int64_t n_vertices, int64_t n_triangles, const double* vertices,
+                            const int32_t* triangles, float* normals, void* workspace, int64_t workspace_bytes);
+
 /* ---- decimation of a mesh: vertex clustering on a uniform grid with a quadric-optimal vertex per cell
  *      (sfm_amd/csrc/mesh_decimate.hip, mesh_decimate_rule.h, mesh_decimate_plan.h) ----
  * Rossignac-Borrel clustering with Lindstrom's placement.  float64 without FMA contraction, every sum in one stated order,

@@ -17,4 +17,5 @@ from .mesh import (Mesh, MeshRender, MeshTexture, RenderScore, TsdfVolume, check
 from .mesh_clean import MeshComponents, check_clean_arguments, clean_mesh, mesh_components  # noqa: F401
 from .mesh_fill import MeshEdges, check_fill_arguments, fill_mesh_holes, mesh_edges  # noqa: F401
 from .mesh_decimate import check_decimate_arguments, decimate_mesh  # noqa: F401
+from .mesh_smooth import MeshAdjacency, check_smooth_arguments, mesh_adjacency, mesh_vertex_normals, smooth_mesh  # noqa: F401
 from .exposure import ExposureGains, apply_gains, check_exposure_arguments, mesh_exposure_tables, solve_gains  # noqa: F401

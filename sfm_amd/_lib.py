@@ -210,6 +210,12 @@ SIGNATURES = {
     "sfm_mesh_fill_workspace_bytes": (C.c_int, [i64, C.POINTER(i64)]),
     "sfm_mesh_fill_mark": (C.c_int, [vp, i64, i64, vp, vp, i64, vp, i64, vp, vp, vp, i64]),
     "sfm_mesh_fill_emit": (C.c_int, [vp, i64, i64, vp, vp, i64, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_mesh_adjacency_workspace_bytes": (C.c_int, [vp, i64, i64, C.POINTER(i64)]),
+    "sfm_mesh_adjacency": (C.c_int, [vp, i64, i64, vp, vp, vp, vp, vp, vp, i64]),
+    "sfm_mesh_smooth_workspace_bytes": (C.c_int, [vp, i64, C.POINTER(i64)]),
+    "sfm_mesh_smooth": (C.c_int, [vp, i64, vp, vp, vp, i64, vp, vp, C.c_int, f64, f64, C.c_int, i64, vp, vp, vp, vp, i64]),
+    "sfm_mesh_vertex_normals_workspace_bytes": (C.c_int, [vp, i64, i64, C.POINTER(i64)]),
+    "sfm_mesh_vertex_normals": (C.c_int, [vp, i64, i64, vp, vp, vp, vp, i64]),
     "sfm_mesh_decimate_workspace_bytes": (C.c_int, [vp, i64, i64, C.POINTER(i64)]),
     "sfm_mesh_decimate_cluster": (C.c_int, [vp, i64, i64, vp, vp, f64, vp, vp, vp, vp, vp, vp, i64]),
     "sfm_mesh_decimate_mark": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, vp, vp, i64]),

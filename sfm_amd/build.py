@@ -7,7 +7,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRC = [os.path.join(HERE, "csrc", f) for f in ("ctx.hip", "ba.hip", "ba_model.hip", "ba_camera_cg.hip", "ba_pcg.hip", "problem.hip", "trf.hip", "dense.hip", "match.hip", "guided.hip", "driver.hip", "twoview.hip", "essential.hip", "homography.hip", "pnp.hip", "pose.hip", "tracks.hip", "triangulate.hip", "resection.hip", "features.hip", "features_pyramid.hip", "depth.hip", "depth_fuse.hip", "tsdf.hip", "mesh.hip", "mesh_clean.hip", "mesh_fill.hip", "mesh_decimate.hip", "mesh_color.hip", "mesh_exposure.hip", "mesh_texture.hip", "mesh_render.hip", "render_score.hip", "comm_rccl.hip")]
+SRC = [os.path.join(HERE, "csrc", f) for f in ("ctx.hip", "ba.hip", "ba_model.hip", "ba_camera_cg.hip", "ba_pcg.hip", "problem.hip", "trf.hip", "dense.hip", "match.hip", "guided.hip", "driver.hip", "twoview.hip", "essential.hip", "homography.hip", "pnp.hip", "pose.hip", "tracks.hip", "triangulate.hip", "resection.hip", "features.hip", "features_pyramid.hip", "depth.hip", "depth_fuse.hip", "tsdf.hip", "mesh.hip", "mesh_clean.hip", "mesh_fill.hip", "mesh_smooth.hip", "mesh_decimate.hip", "mesh_color.hip", "mesh_exposure.hip", "mesh_texture.hip", "mesh_render.hip", "render_score.hip", "comm_rccl.hip")]
 import glob
 # every header under csrc/ (match_plan.h and trf_loop.h were missing from a hand-kept list once: a stale library then
 # ran under the GPU tests while the CPU sanitizer tests compiled the new header)

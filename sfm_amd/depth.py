@@ -497,7 +497,7 @@ def depth_maps_from_arrays(shapes, refs, src_ptr, src_image, warps, backproj, de
 
 def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=256, radius=2, rel_tol=0.01, max_cost=None,
                               min_consistent=2, colors=None, device=0, fuse=False, mesh=False, texture=None,
-                              min_triangles=None, keep_largest=None, fill_holes=None, decimate=None):
+                              min_triangles=None, keep_largest=None, fill_holes=None, decimate=None, smooth=None):
     """The chain on a `Reconstruction`: sources by shared points (`select_sources`), the depth interval of every view from
     its sparse points (`depth_ranges`), planes at most one pixel apart (`plane_depths`), `depth_maps`, `.filter`,
     `.point_cloud`.  images: one per image position of rec.tracks.  Returns (points, index, DepthMaps) - or (points, index,
@@ -510,7 +510,14 @@ def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=2
     is 1 then - cleaned before it is coloured.  With fill_holes (None: nothing changes; otherwise max_edges, 1 .. 64) the
     mesh is then `Mesh.fill_holes(fill_holes)` of that: filled after the cleaning and before it is coloured.  With decimate
     (None: nothing changes; otherwise a factor, a finite number > 0) the mesh is then `Mesh.decimate(factor=decimate)` of that:
-    clustered on cells of that many voxels after the cleaning and the filling and before it is coloured."""
+    clustered on cells of that many voxels after the cleaning and the filling and before it is coloured.  With smooth (None:
+    nothing changes; otherwise an iteration count, 0 .. 1000) the mesh is `Mesh.smooth(smooth)` after the cleaning and the
+    filling and before the decimation, so that the quadrics see the smoothed faces."""
+    if smooth is not None:
+        from .mesh_smooth import check_smooth_arguments
+        if not mesh:
+            raise ValueError("smooth needs mesh=True")
+        check_smooth_arguments(smooth)
     if decimate is not None:
         if not mesh:
             raise ValueError("decimate needs mesh=True")
@@ -550,6 +557,8 @@ def dense_from_reconstruction(rec, images, n_sources=4, margin=0.2, max_planes=2
         surface = (surface[0].clean(min_triangles, keep_largest),)
     if fill_holes is not None:
         surface = (surface[0].fill_holes(int(fill_holes)),)
+    if smooth is not None:
+        surface = (surface[0].smooth(int(smooth)),)
     if decimate is not None:
         surface = (surface[0].decimate(factor=float(decimate)),)
     if mesh and colors is not None:

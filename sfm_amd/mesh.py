@@ -11,7 +11,10 @@ render against the photographs: error, PSNR and SSIM sums and the distance to th
 to the colour calls.  `Mesh.components` and `Mesh.clean` (sfm_amd/mesh_clean.py; `sfm_mesh_components`, `sfm_mesh_clean_mark` /
 `sfm_mesh_clean_emit`, sfm_amd/csrc/mesh_clean.hip) label the connected components of the mesh and remove the small ones.
 `Mesh.decimate` (sfm_amd/mesh_decimate.py; `sfm_mesh_decimate_cluster`, `sfm_mesh_decimate_mark` / `sfm_mesh_decimate_emit`,
-sfm_amd/csrc/mesh_decimate.hip) clusters the vertices on a uniform grid and places one vertex per cell by its quadric.  No
+sfm_amd/csrc/mesh_decimate.hip) clusters the vertices on a uniform grid and places one vertex per cell by its quadric.
+`Mesh.adjacency`, `Mesh.smooth` and `Mesh.recompute_normals` (sfm_amd/mesh_smooth.py; `sfm_mesh_adjacency`, `sfm_mesh_smooth`,
+`sfm_mesh_vertex_normals`, sfm_amd/csrc/mesh_smooth.hip) build the neighbours of every vertex, move the vertices by Taubin steps
+and re-derive the normals from the faces.  No
 CPU fallback: without the library or a GPU the calls raise.
 """
 from __future__ import annotations
@@ -117,6 +120,40 @@ class Mesh:
         max_edges edges is closed too, so clean() first.  This mesh is untouched."""
         from .mesh_fill import fill_holes
         return fill_holes(self, max_edges, edges)
+
+    # on what smooth() returns: how many vertices the boundary rule and the caller pinned, how many have no neighbour (with
+    # n_unsound_vertices: those with a coordinate that is not finite), the `MeshAdjacency` it used; None otherwise
+    n_pinned_boundary = n_pinned_given = n_isolated = adjacency_before = None
+    # uint8 [nv]: why a vertex stayed (bit 0 boundary, 1 pinned by the caller, 2 not finite, 3 isolated; 0: it moved); None otherwise
+    vertex_state = property(lambda self: self._get("vertex_state", self.n_vertices))
+
+    def adjacency(self):
+        """The vertex adjacency on the device (`sfm_mesh_adjacency`; include/sfm_amd.h states the rule): per vertex its
+        neighbours - the other ends of its live half-edges - in ascending index as ptr / index, and vertex_flags with bit 0
+        for a vertex on an edge that is not used exactly twice and bit 1 for one without a neighbour.  Returns a
+        `MeshAdjacency` with the counts."""
+        from .mesh_smooth import adjacency_of
+        return adjacency_of(self)
+
+    def smooth(self, iterations=10, lam=0.5, mu=-0.53, pin_boundary=True, pinned=None, normals="recompute", adjacency=None):
+        """A new `Mesh` with smoothed vertices (`sfm_mesh_smooth`; include/sfm_amd.h states the rule): every iteration moves
+        each free vertex by lam towards the mean of its neighbours and then, unless mu is None, by mu (negative: away) with
+        respect to the new mean - Taubin's pair, which keeps the volume that plain Laplacian steps (mu=None) lose.  Boundary
+        vertices (pin_boundary), the vertices with pinned[v] != 0 (uint8 / bool [nv]), vertices that are not finite and
+        vertices without a neighbour stay; vertex_state says why, n_pinned_boundary, n_pinned_given, n_unsound_vertices and
+        n_isolated count them.  normals: "recompute" for area-weighted normals of the moved faces (`sfm_mesh_vertex_normals`),
+        "keep" for the old ones.  adjacency: what `adjacency()` returned for this mesh, None to build it now.  The triangles
+        are carried over byte for byte and so is the volume; vertex_colors, n_views, best_view and atlas are None, so call
+        colors() or texture() again.  iterations=0 returns the vertices byte for byte.  This mesh is untouched."""
+        from .mesh_smooth import smooth
+        return smooth(self, iterations, lam, mu, pin_boundary, pinned, normals, adjacency)
+
+    def recompute_normals(self):
+        """A new `Mesh` with the same vertices and triangles and area-weighted normals (`sfm_mesh_vertex_normals`): the unit
+        of the sum of (p1 - p0) x (p2 - p0) over the triangles at each vertex, zeros where that sum has no finite positive
+        length.  What a mesh of `decimate_mesh` / `fill_mesh_holes` without normals needs before colors()."""
+        from .mesh_smooth import recompute_normals
+        return recompute_normals(self)
 
     # on what decimate() returns: the vertices of the mesh it was made from, how many of them and of its triangles were
     # unsound, how many triangles had two corners in one cell, how many the duplicate rule dropped, the grid; None otherwise
@@ -983,3 +1020,4 @@ def score_render(color, triangle, depth, photos, view_depth=None, view_keep=None
 from .mesh_clean import MeshComponents, check_clean_arguments, clean_mesh, mesh_components  # noqa: E402,F401
 from .mesh_fill import MeshEdges, check_fill_arguments, fill_mesh_holes, mesh_edges  # noqa: E402,F401
 from .mesh_decimate import check_decimate_arguments, decimate_mesh  # noqa: E402,F401
+from .mesh_smooth import MeshAdjacency, check_smooth_arguments, mesh_adjacency, mesh_vertex_normals, smooth_mesh  # noqa: E402,F401

@@ -1215,6 +1215,59 @@ def measure_mesh_fill(h, dev, nv, nt, triangles, vertices, reps=20, fan=1 << 20)
     return out
 
 
+def measure_mesh_smooth(h, dev, nv, nt, triangles, vertices, iterations=10, reps=20):
+    """sfm_mesh_adjacency, sfm_mesh_smooth (`iterations` Taubin iterations at 0.5 | -0.53, boundary pinned) and
+    sfm_mesh_vertex_normals on a mesh that is resident on the device: whole calls by HIP events around `reps` calls after 3
+    warm-up calls, with the counts they report.  The yardstick is ms_mesh_edges of the same row, one radix sort plus passes on
+    half as many keys."""
+    import torch
+    from sfm_amd.driver import _p
+    need = C.c_int64()
+    h.call("sfm_mesh_adjacency_workspace_bytes", nv, nt, C.byref(need))
+    adj_bytes = need.value
+    adj_ws = torch.empty(adj_bytes, dtype=torch.uint8, device=dev)
+    ptr = torch.empty(nv + 1, dtype=torch.int32, device=dev)
+    index = torch.empty(max(6 * nt, 1), dtype=torch.int32, device=dev)
+    flags = torch.empty(max(nv, 1), dtype=torch.uint8, device=dev)
+    a_counts, s_counts = torch.empty(4, dtype=torch.int64, device=dev), torch.empty(5, dtype=torch.int64, device=dev)
+
+    def run_adjacency():
+        h.call("sfm_mesh_adjacency", nv, nt, _p(triangles), _p(ptr), _p(index), _p(flags), _p(a_counts), _p(adj_ws), adj_bytes)
+    for _ in range(3):
+        run_adjacency()
+    entries, boundary, isolated, unsound = (int(c) for c in a_counts.cpu().numpy())
+    h.call("sfm_mesh_smooth_workspace_bytes", nv, C.byref(need))
+    smooth_bytes = need.value
+    smooth_ws = torch.empty(smooth_bytes, dtype=torch.uint8, device=dev)
+    moved = torch.empty((max(nv, 1), 3), dtype=torch.float64, device=dev)
+    state = torch.empty(max(nv, 1), dtype=torch.uint8, device=dev)
+
+    def run_smooth(n=iterations):
+        h.call("sfm_mesh_smooth", nv, _p(vertices), _p(ptr), _p(index), entries, _p(flags), None, 1, C.c_double(0.5), C.c_double(-0.53), 1, n, _p(moved),
+               _p(state), _p(s_counts), _p(smooth_ws), smooth_bytes)
+    for _ in range(3):
+        run_smooth()
+    sc = [int(c) for c in s_counts.cpu().numpy()]
+    h.call("sfm_mesh_vertex_normals_workspace_bytes", nv, nt, C.byref(need))
+    normals_bytes = need.value
+    normals_ws = torch.empty(normals_bytes, dtype=torch.uint8, device=dev)
+    normals = torch.empty((max(nv, 1), 3), dtype=torch.float32, device=dev)
+
+    def run_normals():
+        h.call("sfm_mesh_vertex_normals", nv, nt, _p(moved), _p(triangles), _p(normals), _p(normals_ws), normals_bytes)
+    for _ in range(3):
+        run_normals()
+    out = {"smooth_iterations": iterations, "ms_mesh_adjacency": timed(run_adjacency, reps) * 1e3, "ms_mesh_smooth": timed(run_smooth, reps) * 1e3,
+           "ms_mesh_smooth_1_iteration": timed(lambda: run_smooth(1), reps) * 1e3, "ms_mesh_vertex_normals": timed(run_normals, reps) * 1e3,
+           "adjacency_entries": entries, "adjacency_boundary_vertices": boundary, "adjacency_isolated_vertices": isolated, "adjacency_unsound_triangles": unsound,
+           "smooth_pinned_boundary": sc[0], "smooth_unsound_vertices": sc[2], "smooth_isolated": sc[3], "smooth_status": sc[4],
+           "mean_vertex_degree": entries / nv if nv else 0.0, "adjacency_workspace_bytes": adj_bytes, "smooth_workspace_bytes": smooth_bytes,
+           "vertex_normals_workspace_bytes": normals_bytes}
+    out["ms_mesh_smooth_per_step"] = out["ms_mesh_smooth"] / (2 * iterations)
+    out["smooth_vertex_steps_per_s"] = nv * 2 * iterations / (out["ms_mesh_smooth"] * 1e-3)
+    return out
+
+
 def measure_mesh_decimate(h, dev, nv, nt, triangles, vertices, vnormals, voxel, view_args, render_args, reps=20):
     """sfm_mesh_decimate_cluster, sfm_mesh_decimate_mark and sfm_mesh_decimate_emit on a mesh that is resident on the device, at
     cells of 2 and 4 voxels from the per-axis minimum of the vertices, with the mean and with the quadric: whole calls by HIP
@@ -1327,7 +1380,8 @@ def measure_depth(reps=20, emit=None, mesh=False):
     at min_triangles 100 (sfm_mesh_components, sfm_mesh_clean_mark, sfm_mesh_clean_emit) and sfm_mesh_components on the ascending strip
     at 2^20 and 2^22 vertices with the ratio of the two times (`measure_mesh_clean`), then the edge table of that mesh and the filling of
     its holes at max_edges 16 (sfm_mesh_edges, sfm_mesh_fill_mark, sfm_mesh_fill_emit) and sfm_mesh_edges on a fan and on a strip of 2^20
-    triangles (`measure_mesh_fill`), then the decimation of that mesh at cells of 2 and 4 voxels with both placements (sfm_mesh_decimate_cluster,
+    triangles (`measure_mesh_fill`), then its adjacency, ten Taubin iterations and the normals of the moved faces (sfm_mesh_adjacency,
+    sfm_mesh_smooth, sfm_mesh_vertex_normals; `measure_mesh_smooth`), then the decimation of that mesh at cells of 2 and 4 voxels with both placements (sfm_mesh_decimate_cluster,
     sfm_mesh_decimate_mark, sfm_mesh_decimate_emit) and sfm_mesh_texture and sfm_mesh_render of the decimated mesh (`measure_mesh_decimate`),
     whole calls by HIP events; the row is then named "mesh"."""
     import torch
@@ -1581,6 +1635,9 @@ def measure_depth(reps=20, emit=None, mesh=False):
         # and the cleaning above are their yardsticks.  Then the table alone on a fan of 2^20 triangles about one vertex and
         # on a strip of as many: the sort keeps the fan near the strip.
         row.update(measure_mesh_fill(h, dev, nv, nt, triangles, vertices, reps))
+        # the adjacency of the same mesh, ten Taubin iterations over it and the normals of the moved faces, whole calls, 20
+        # after 3; the edge table above is the yardstick
+        row.update(measure_mesh_smooth(h, dev, nv, nt, triangles, vertices, 10, reps))
         # the decimation of the same mesh at cells of 2 and 4 voxels, both placements, whole calls, 20 after 3; the edge table
         # above is the yardstick.  Then the texture and the render of the decimated mesh beside those of the full one above.
         row.update(measure_mesh_decimate(h, dev, nv, nt, triangles, vertices, vnormals, float(voxel),
@@ -1643,7 +1700,7 @@ def main():
     ap.add_argument("--pyramid-only", action="store_true", help="only the multi-scale feature row (beside the single-scale stage on the same images); no other selection runs it")
     ap.add_argument("--guided-only", action="store_true", help="only the guided-matching row (beside the blind matcher)")
     ap.add_argument("--depth-only", action="store_true", help="only the dense-depth row (beside the feature stage on the same images)")
-    ap.add_argument("--mesh-only", action="store_true", help="only the meshing row: TSDF integration, mark and emit beside the sweep and the fusion of the same run, and the stages on that mesh up to its components and cleaning, its edge table, the filling of its holes and its decimation")
+    ap.add_argument("--mesh-only", action="store_true", help="only the meshing row: TSDF integration, mark and emit beside the sweep and the fusion of the same run, and the stages on that mesh up to its components and cleaning, its edge table, the filling of its holes, its smoothing and its decimation")
     a = ap.parse_args()
     emit = lambda d: print(json.dumps(d), flush=True)
     only = a.fundamental_only or a.essential_only or a.homography_only or a.pnp_only or a.pose_only or a.tracks_only or a.triangulate_only or a.incremental_only or \
